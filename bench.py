@@ -20,6 +20,9 @@ Metric (BASELINE.json): Mpix/s for 3584x1320 14-bit unpack + cs5x5 + stripes
   extra     = same process, outside the timed headline, rank 0 @ N=1 only: configs[1] (cs2x2),
               other footage kinds through the same kernel, configs[3] (full dual-ISO), and the
               PCIe-inclusive rates (batch API, drop-in symbols).  Never part of `value`.
+  --dump-outputs DIR  after the timed steps, rank 0 writes a seeded sample of the frames its last
+              step computed to DIR/frames.npy (float32), so that two builds can be compared output
+              for output: the inputs are seeded, identical from run to run for the same arguments.
 
 Multi-GPU: one rank per GPU.  `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the
 environment) starts its own ranks: the parent -- before it imports torch or touches HIP --
@@ -63,6 +66,8 @@ def spawn_ranks(args) -> int:
         cmd.append("--no-cpu-baseline")
     if args.no_extras:
         cmd.append("--no-extras")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     res = subprocess.run(cmd, stdout=subprocess.PIPE, env=env, text=True)
     line = None
@@ -504,6 +509,27 @@ def extra_pcie(N=128, threads=16):
     return res
 
 
+# ------------------------------------------------------------------------------------------ output dump
+DUMP_FRAMES = 3                      # 3 frames of 3584x1320 in float32: 57 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(path, out, lo, F, distinct):
+    """The frames out[lo:lo + F] of the last timed step -- what a caller of ClipStream.process receives -- as DIR/frames.npy:
+    a seeded sample of DUMP_FRAMES of them, in float32 (exact for 16-bit pixels).  Frame lo + i of the resident stream holds
+    synthetic frame (lo + i) % distinct and comes out like it (checked after the timed region), so the sample is drawn by content: the
+    same arguments give the same arrays whichever slot of the stream the last step ran on.  Returns the record for the result line."""
+    from mlvfs_amd.stream import to_numpy_u16
+    content = (lo + np.arange(F)) % distinct
+    kinds = np.unique(content)
+    pick = sorted(np.random.default_rng(1).choice(kinds, size=min(DUMP_FRAMES, len(kinds)), replace=False).tolist())
+    idx = [int(np.flatnonzero(content == c)[0]) for c in pick]
+    frames = np.stack([to_numpy_u16(out[lo + i]) for i in idx]).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frames.npy"), frames)
+    return {"dir": os.path.abspath(path), "arrays": {"frames": list(frames.shape)}, "dtype": "float32",
+            "frames_of_last_step": idx, "synthetic_frames": pick, "bytes": int(frames.nbytes)}
+
+
 # ------------------------------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -516,6 +542,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--cs", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of the last step's output frames to DIR/frames.npy")
     args = ap.parse_args()
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -695,6 +723,9 @@ def main():
         dist.all_gather(parts, torch.tensor([my_kernel_fps], dtype=torch.float64, device=dev))
         per_rank_fps = [round(float(p.item()), 1) for p in parts]
 
+    # ---- the output of the last timed step, before anything below writes into `out` again
+    dumped = dump_outputs(args.dump_outputs, out, (K - 1) % slots * F, F, distinct) if args.dump_outputs and rank == 0 else None
+
     # ---- the same hot path at 100 frames per launch, the default of rounds 1-3 (round-to-round deltas must not mix kernel
     # changes with the change of the launch size): a few launches, wall clock, beside the headline -- never `value`
     at100 = None
@@ -836,6 +867,8 @@ def main():
     }
     if valu:
         result["valu"] = valu
+    if dumped:
+        result["dump_outputs"] = dumped
     all_ok = bool(int(ok_flag.item()))
     # the headline's buffers are not needed any more: the extras allocate their own
     del packed, out, base

@@ -1,6 +1,6 @@
 /* Prints size and field offsets of `struct frame_headers`.  Compiled twice by
- * tests/test_abi.py: against include/mlvfs_abi.h, and (only where /root/reference
- * exists) with -DUSE_REFERENCE against the reference's own mlvfs.h. */
+ * tests/test_abi.py against include/mlvfs_abi.h, and by tests/golden/make_reference_facts.py
+ * with -DUSE_REFERENCE against the reference's own mlvfs.h. */
 #include <stddef.h>
 #include <stdio.h>
 #ifdef USE_REFERENCE

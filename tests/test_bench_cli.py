@@ -170,3 +170,26 @@ def test_bench_single_rank_in_an_rccl_group(gpu):
     assert res["n_gpus"] == 1 and res["parity"]["ok"] is True
     assert res["config"]["stripe_coeffs"] == golden["B_cs5_badpix_stripes_coeffs"]
     assert "RCCL" in res["config"]["collective"] and res["config"]["strong_scaling"]["frames_per_rank"] == [12]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_same_for_the_same_content(gpu, tmp_path):
+    """--dump-outputs DIR: a seeded sample of the last timed step's frames in DIR/frames.npy (float32, at most 64 MB), drawn by content.
+    With 64 frames per step every step holds each of the 64 distinct synthetic frames once, so runs whose last steps land on different
+    slots of the resident stream (--steps 2 and 3) dump the same arrays; the run's own parity check vouches for the output."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MLVFS_BENCH_REHEARSAL", "MLVFS_BENCH_GROUP1")}
+    dumps = []
+    for steps in (2, 3):
+        d = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--frames-per-step", "64",
+                            "--preheat-ms", "20", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        res = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert res["steps"] == steps and res["ms_per_step"] > 0 and res["parity"]["ok"] is True
+        assert sorted(os.listdir(d)) == ["frames.npy"] and os.path.getsize(d / "frames.npy") <= 64 * 2**20
+        frames = np.load(d / "frames.npy")
+        assert frames.dtype == np.float32 and frames.shape == (3, 1320, 3584) and res["dump_outputs"]["arrays"]["frames"] == [3, 1320, 3584]
+        dumps.append((res["dump_outputs"]["synthetic_frames"], frames))
+    assert dumps[0][0] == dumps[1][0] and np.array_equal(dumps[0][1], dumps[1][1])
+    assert len({f.tobytes() for f in dumps[0][1]}) == 3

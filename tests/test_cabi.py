@@ -1,6 +1,7 @@
 """The C-ABI library loads and exports every symbol include/mlvfs_amd.h declares; the
 host-only entry points work without a GPU (no compute calls here)."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -10,6 +11,10 @@ import numpy as np
 from mlvfs_amd import lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def reference_facts():
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "reference_facts.json")))
 
 
 def declared_functions():
@@ -127,26 +132,12 @@ def test_stripes_correction_list(amd):
     assert not amd.stripes_get_correction(b"/x/a.MLV")
 
 
-def test_library_covers_what_the_callers_import_from_the_replaced_objects(amd, tmp_path):
+def test_library_covers_what_the_callers_import_from_the_replaced_objects(amd):
     """Link-level drop-in: every global function of the objects the library replaces (mlvfs/Makefile:24,34-38)
     that the rest of MLVFS calls -- main.c, gif.c, webgui.c, resource_manager.c, ... -- must be exported by libmlvfs_amd.so.
-    main.c itself cannot be compiled here (<fuse.h>), so its calls are found in its text."""
-    ref = "/root/reference/mlvfs"
-    if not os.path.isdir(ref):
-        import pytest
-        pytest.skip("needs the reference tree")
-    replaced = ["dng.c", "cs.c", "stripes.c", "hdr.c", "amaze_demosaic_RT.c", "histogram.c", "patternnoise.c"]
-    defined = set()
-    for src in replaced:
-        obj = str(tmp_path / (src + ".o"))
-        subprocess.run(["gcc", "-c", "-O0", "-w", "-std=gnu99", "-D_FILE_OFFSET_BITS=64", "-I", ref, os.path.join(ref, src), "-o", obj], check=True)
-        out = subprocess.run(["nm", "--defined-only", obj], capture_output=True, text=True, check=True).stdout
-        defined |= {l.split()[-1] for l in out.splitlines() if " T " in l}
-    callers = [f for f in os.listdir(ref) if f.endswith(".c") and f not in replaced]
-    needed = set()
-    for f in callers:
-        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ref, f), errors="replace").read(), flags=re.S)
-        needed |= {s for s in defined if re.search(r"\b" + re.escape(s) + r"\s*\(", text)}
+    main.c itself cannot be compiled (<fuse.h>), so its calls are found in its text; the set is recorded from the reference tree by
+    tests/golden/make_reference_facts.py."""
+    needed = set(reference_facts()["called_from_callers"])
     assert {"dng_get_header_data", "dng_get_image_data", "chroma_smooth", "stripes_compute_correction", "cr2hdr20_convert_data",
             "hdr_convert_data", "fix_pattern_noise", "hist_median"} <= needed
     out = subprocess.run(["nm", "-D", "--defined-only", lib.SO_PATH], capture_output=True, text=True, check=True).stdout
@@ -158,8 +149,8 @@ def test_wrap_shim_links_and_brackets_process_frame_only(amd, tmp_path):
     """integration/mlvfs_amd_wrap.c: a host that calls mlvfs_load_chunks / mlvfs_close_chunks from one
     object and defines them in another (like main.o / resource_manager.o) links with the two --wrap flags, its calls then go
     through the shim and the shim's through to the host's definitions.  No compute: the bracket calls do not touch a GPU.  And
-    where the reference tree is present: the pixel stages of process_frame sit between the two wrapped calls (main.c:923-998),
-    gif.c's do not (it uses index.c's load_chunks / close_chunks)."""
+    in the reference: the pixel stages of process_frame sit between the two wrapped calls (main.c:923-998),
+    gif.c's do not (it uses index.c's load_chunks / close_chunks): recorded by tests/golden/make_reference_facts.py."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     host = tmp_path / "host.c"
     host.write_text('#include <stdint.h>\n#include <stdio.h>\n'
@@ -181,15 +172,13 @@ def test_wrap_shim_links_and_brackets_process_frame_only(amd, tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)          # no GPU here: the bracket must not need one
     assert r.returncode == 0 and "closed" in r.stdout, r.stderr[-1000:]
     assert amd.mlvfs_amd_frame_begin() == 0 and amd.mlvfs_amd_frame_end() == 0 and amd.mlvfs_amd_frame_sync(None) == 0
-    ref = "/root/reference/mlvfs"
-    if os.path.isdir(ref):
-        main_c = open(os.path.join(ref, "main.c"), errors="replace").read()
-        body = main_c[main_c.index("static int process_frame("):main_c.index("int create_preview(")]
-        a, b = body.index("mlvfs_load_chunks("), body.index("mlvfs_close_chunks(")
-        for stage in ("get_image_data(", "fix_pattern_noise(", "cr2hdr20_convert_data(", "fix_bad_pixels(", "chroma_smooth(", "stripes_apply_correction("):
-            assert a < body.index(stage) < b, stage
-        gif_c = open(os.path.join(ref, "gif.c"), errors="replace").read()
-        assert "mlvfs_load_chunks" not in gif_c and "mlvfs_close_chunks" not in gif_c and "load_chunks(path" in gif_c
+    facts = reference_facts()
+    calls = facts["process_frame_calls"]
+    a, b = calls.index("mlvfs_load_chunks"), calls.index("mlvfs_close_chunks")
+    for stage in ("get_image_data", "fix_pattern_noise", "cr2hdr20_convert_data", "fix_bad_pixels", "chroma_smooth", "stripes_apply_correction"):
+        assert a < calls.index(stage) < b, stage
+    gif_c = facts["gif_c_calls"]
+    assert not gif_c["mlvfs_load_chunks"] and not gif_c["mlvfs_close_chunks"] and gif_c["load_chunks(path"]
 
 
 def test_worker_threads_are_bound_round_robin_in_pci_order(amd):
