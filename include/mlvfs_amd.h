@@ -412,6 +412,56 @@ int mlvfs_amd_test_device_order(const char *const *bus_ids, int n, int workers, 
  * side in one wave (a last column of <= 14 items: 4, <= 30 items: 2), tasks per frame.                                              */
 int mlvfs_amd_test_stream_plan(int width, int height, int seg_rows, int *cols, int *segs, int *fold, int *tasks_per_frame);
 
+/* -- batched stages of process_frame that existed only per frame ------------- */
+/* Pattern noise (patternnoise.c:357-380, debug_flags 0) on `nframes` device frames of one geometry (even width and height), `stride`
+ * bytes apart, in place; geom->white = raw_info.white_level.  Every kernel has the frame as a grid dimension: a batch costs the 12
+ * launches of one frame per sub-batch (scratch of about 8 bytes per pixel and frame, bounded).  Synchronises the stream.         */
+int mlvfs_amd_fix_pattern_noise_dev(const mlvfs_amd_geom_t *geom, void *d_frames, size_t stride, int nframes, void *stream);
+/* Test hook: the scratch a batch of mlvfs_amd_fix_pattern_noise_dev (and the mount) may use, in bytes (0: the default again, 256 MB or
+ * MLVFS_AMD_PN_SCRATCH_MB); returns the cap before.  A batch that does not fit is cut into even sub-batches.                 */
+size_t mlvfs_amd_test_pn_scratch_cap(size_t bytes);
+/* Deflicker (main.c:895-906) of `nframes` device frames: one histogram launch, one median launch (a workgroup per frame, the
+ * reference's 16-bit counters), one copy of the medians; exposure_bias[2 * f], [2 * f + 1] as mlvfs_amd_deflicker_dev gives them.
+ * size_bytes: each frame's size in bytes as main.c:943 passes it.  Synchronises the stream.                                   */
+int mlvfs_amd_deflicker_batch_dev(const mlvfs_amd_geom_t *geom, const void *d_frames, size_t stride, int nframes, size_t size_bytes,
+                                  int target, int32_t *exposure_bias, void *stream);
+/* Dual-ISO preview (hdr_convert_data, hdr.c:40-227, without the focus-pixel repair) of `nframes` device frames, in place: one
+ * histogram launch, the fit per frame on the host, one conversion launch.  results[f] = 1 converted, 0 not dual ISO (the frame is
+ * left untouched).  max_size as hdr_convert_data takes it (bytes).  Synchronises the stream.                                  */
+int mlvfs_amd_hdr_preview_batch_dev(const mlvfs_amd_geom_t *geom, void *d_frames, size_t stride, int nframes, size_t max_size,
+                                    int *results, void *stream);
+
+/* -- a clip served as MLVFS serves it (main.c:908-1005) ------------------------ */
+/* The mount options of struct mlvfs (mlvfs.h:32-48) that shape a frame's .dng file. */
+typedef struct {
+    int32_t chroma_smooth;              /* 0, 2, 3, 5 */
+    int32_t fix_bad_pixels;             /* 0, 1, 2 (aggressive) */
+    int32_t fix_stripes;
+    int32_t dual_iso;                   /* 0, 1 preview (hdr_convert_data), 2 full (cr2hdr20_convert_data) */
+    int32_t hdr_interpolation_method;   /* 0 AMaZE + edge-directed, 1 mean23 */
+    int32_t hdr_no_fullres;
+    int32_t hdr_no_alias_map;
+    int32_t deflicker;                  /* target level, 0 = off (main.c:895-906, 943) */
+    int32_t fix_pattern_noise;
+    int32_t rand_mode;                  /* stripe dither: 0 = the application's rand(), like the drop-in symbols; 1 = a private stream
+                                           seeded with 1 (what a fresh process draws) */
+    double fps;                         /* header fps override, 0 = the clip's */
+} mlvfs_amd_mount_opts_t;
+/* One clip of an opened reader (mlvfs_amd_mlv_open) served with these options, as a fresh MLVFS process serves it: successive calls
+ * serve frames in call order and the order-dependent state follows that order -- the stripe correction comes from the first frame
+ * that reaches the stripes stage, the bad-pixel map (shared per clip GUID within the process, like cs.c's) from the first that
+ * reaches fix_bad_pixels, the dual-ISO table caches (process-wide, mlvfs_amd_dualiso_reset) from the first that converts.
+ * mlv_basename: what process_frame hands dng_get_header_data (the .dng path up to its last separator).  The reader must outlive the
+ * handle.  NULL on bad arguments (mlvfs_amd_last_error).                                                                           */
+void *mlvfs_amd_mount_open(const void *reader, const mlvfs_amd_mount_opts_t *opts, const char *mlv_basename);
+/* Frames first .. first + count - 1 as their .dng files: dng_get_size bytes each (65536 header bytes, then the pixels) at
+ * h_out + k * out_stride.  Batches of batch_frames frames (<= 0: 8) go file -> GPU (read, decode or unpack) -> deflicker -> pattern
+ * noise -> dual ISO -> focus / bad pixels, chroma smoothing, stripes (the fused pass) -> host, the headers written on the host from
+ * each frame's headers after its stages.  io_threads: reader threads (<= 0: 8).  results[k] (optional) = 1 when the frame was
+ * converted as dual ISO.  Calls on one handle are serialised.                                                                       */
+int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results);
+void mlvfs_amd_mount_close(void *mount);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):

@@ -5,6 +5,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -153,6 +154,41 @@ int launch_pixfix_for_frame_kernel(int packed, const void *frames, size_t stride
 int launch_pixfix_cells(int packed, const void *frames, size_t stride, int w, int h, const CellRec *recs, int n_rec,
                         const void *patches, int n_entries, void *cells, int nframes, hipStream_t stream);
 int launch_deflicker_hist(const void *d_frame, uint32_t samples, uint32_t white, unsigned *d_hist, hipStream_t s);
+// batches of frames `fstride` bytes apart (k_hdr.hip): the deflicker histograms of every frame in one launch and their medians (the
+// reference's 16-bit counters, one workgroup per frame) into d_med[nframes]
+int launch_deflicker_batch(const void *d_frames, size_t fstride, int nframes, uint32_t samples, uint32_t white, uint32_t middle, unsigned *d_hist,
+                           uint16_t *d_med, hipStream_t s);
+// the dual-ISO preview's fit of one frame of a batch (hdr.c:98-176); active = 0: not dual ISO, the frame is left alone
+struct HdrPreviewParams {
+    double a, b;
+    int dark_row_start, shadow, active, pad;
+};
+int launch_hdr_row_hist_batch(const void *d_frames, size_t fstride, int nframes, int w, int h, int white, unsigned *d_hist, hipStream_t stream);
+int launch_hdr_preview_batch(const void *d_frames, void *d_out, size_t fstride, int nframes, int w, int h, int black, int white,
+                             const HdrPreviewParams *d_params, size_t shift_count, hipStream_t stream);
+// pattern noise on batches (k_pnoise.hip): scratch per frame of a sub-batch, and the 12 launches per sub-batch
+size_t pattern_noise_batch_frame_bytes(int w, int h);
+// bytes of scratch a batch of pattern noise may use (MLVFS_AMD_PN_SCRATCH_MB, default 256; mlvfs_amd_test_pn_scratch_cap)
+size_t pattern_noise_scratch_cap();
+int launch_pattern_noise_batch(void *d_frames, size_t fstride, int nframes, int w, int h, int white, void *d_scratch, size_t scratch_bytes,
+                               hipStream_t stream);
+// the dual-ISO preview of a batch on the device (hdr.cpp): results[f] = 1 converted (written to d_out + f * fstride), 0 not;
+// fhs (optional, per frame): the converted frames get the dual-ISO focus-pixel repair before the matching (hdr.c:104)
+int hdr_preview_batch_device(ThreadCtx *c, const Geom &g, void *d_frames, void *d_out, size_t fstride, int nframes, size_t max_size,
+                             unsigned *d_hist, HdrPreviewParams *d_params, struct frame_headers *fhs, int *results, hipStream_t stream);
+// the deflicker medians of a batch (hdr.cpp; synchronises the stream once): med[f] for every frame
+int deflicker_batch_device(const void *d_frames, size_t fstride, int nframes, int bpp, size_t size_bytes, void *d_scratch, size_t scratch_bytes,
+                           uint16_t *med, hipStream_t stream);
+size_t deflicker_batch_scratch_bytes(int bpp, int nframes);
+void deflicker_bias(int target, int black_level, uint16_t median, int32_t exposure_bias[2]);
+// the mount's reader half (mlvreader.cpp): frames of one geometry from the file to 16-bit pixels in HBM; synchronises s
+int reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
+                      hipStream_t s);
+// the clip's bad-pixel map if it has been detected already (dropin.cpp)
+bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
+int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,
+                      int white14, int interp_method, int use_fullres, int use_alias_map, int chroma_smooth, int bad_pixels_mode,
+                      hipStream_t stream, int *results);
 int launch_hist_add(const void *d_frame, uint32_t first, uint32_t step, uint32_t samples, uint32_t white, unsigned *d_hist, hipStream_t s);
 int launch_badpix_detect(const void *d_frame, int w, int h, int black, int aggressive, int crop_x, int crop_y,
                          void *d_mask, int words_per_row, int *d_row_count, void *d_list, int cap,

@@ -733,6 +733,16 @@ int cr2hdr20_device(ThreadCtx *c, struct frame_headers *fh, void *d_frame, int w
     return rc < 0 ? rc : result;
 }
 
+// the mount (mount.cpp): a batch without frame headers, or one frame with them (then its focus / bad pixels are repaired first,
+// like the drop-in symbol's)
+int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,
+                      int white14, int interp_method, int use_fullres, int use_alias_map, int chroma_smooth, int bad_pixels_mode,
+                      hipStream_t stream, int *results)
+{
+    const DiOptions o{ interp_method, use_fullres, use_alias_map, chroma_smooth };
+    return cr2hdr20_batch(c, fh, d_frames, img_stride, nframes, w, H, black14, white14, o, bad_pixels_mode, stream, results, nullptr);
+}
+
 }  // namespace mlv
 
 using namespace mlv;

@@ -121,6 +121,77 @@ int hdr_preview_device(const Geom &g, const void *d_frame, void *d_out, size_t m
     return 1;
 }
 
+int hdr_preview_batch_device(ThreadCtx *c, const Geom &g, void *d_frames, void *d_out, size_t fstride, int nframes, size_t max_size,
+                             unsigned *d_hist, HdrPreviewParams *d_params, struct frame_headers *fhs, int *results, hipStream_t stream)
+{
+    const int white16 = (int)(uint16_t)g.white, black16 = (int)(uint16_t)g.black;
+    for (int f = 0; f < nframes; f++) results[f] = 0;
+    if (nframes <= 0) return MLVFS_AMD_OK;
+    int rc = launch_hdr_row_hist_batch(d_frames, fstride, nframes, g.w, g.h, white16, d_hist, stream);
+    if (rc) return rc;
+    const size_t hist_fs = 4 * (size_t)(white16 + 1);
+    std::vector<unsigned> hist(hist_fs * nframes);
+    MLV_HIP(hipMemcpyAsync(hist.data(), d_hist, hist.size() * 4, hipMemcpyDeviceToHost, stream));
+    MLV_HIP(hipStreamSynchronize(stream));
+    std::vector<HdrPreviewParams> pp(nframes);
+    int any = 0;
+    for (int f = 0; f < nframes; f++) {
+        HdrFit fit;
+        pp[f] = HdrPreviewParams{ 0.0, 0.0, 0, 0, 0, 0 };
+        if (!hdr_analyse(hist.data() + f * hist_fs, g.w, g.h, g.black, g.white, &fit)) {
+            fprintf(stderr, "Could not detect dual ISO interlaced lines\n");
+            continue;
+        }
+        pp[f] = HdrPreviewParams{ fit.a, fit.b, fit.dark_row_start, (int)fit.shadow, 1, 0 };
+        results[f] = 1;
+        any = 1;
+        if (fhs) {                                                      // hdr.c:104, only on frames found to be dual ISO
+            rc = focus_pixels_device(&fhs[f], c, (uint8_t *)d_frames + f * fstride, 1, nullptr);
+            if (rc) return rc;
+        }
+    }
+    if (!any) return MLVFS_AMD_OK;
+    MLV_HIP(hipMemcpyAsync(d_params, pp.data(), sizeof(HdrPreviewParams) * nframes, hipMemcpyHostToDevice, stream));
+    rc = launch_hdr_preview_batch(d_frames, d_out, fstride, nframes, g.w, g.h, black16, white16, d_params, max_size / 2, stream);
+    if (rc) return rc;
+    MLV_HIP(hipStreamSynchronize(stream));                              // (pp lives on this stack frame)
+    return MLVFS_AMD_OK;
+}
+
+size_t deflicker_batch_scratch_bytes(int bpp, int nframes)
+{
+    const size_t white = ((size_t)1 << bpp) + 1;
+    return ((white + 1) * sizeof(unsigned) * nframes + 255) / 256 * 256 + (size_t)nframes * sizeof(uint16_t);
+}
+
+int deflicker_batch_device(const void *d_frames, size_t fstride, int nframes, int bpp, size_t size_bytes, void *d_scratch, size_t scratch_bytes,
+                           uint16_t *med, hipStream_t stream)
+{
+    if (bpp < 1 || bpp > 15 || size_bytes < 2) { set_error("deflicker: unsupported bit depth / size"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes <= 0) return MLVFS_AMD_OK;
+    if (scratch_bytes < deflicker_batch_scratch_bytes(bpp, nframes)) { set_error("deflicker: scratch too small"); return MLVFS_AMD_ERR_ARG; }
+    const uint32_t white = (1u << bpp) + 1;                            // (uint16_t)((1 << bpp) + 1)
+    const uint32_t size = (uint32_t)((size_bytes - 1) / 2);            // elements handed to hist_add behind data + 1
+    const uint32_t samples = (size + 1) / 2;                           // i = 0, 2, 4, ... < size
+    const uint32_t middle = (size / 2) / 2;                            // hist_median: count = size / 2 (histogram.c:57)
+    unsigned *d_hist = (unsigned *)d_scratch;
+    uint16_t *d_med = (uint16_t *)((uint8_t *)d_scratch + (((size_t)white + 1) * sizeof(unsigned) * nframes + 255) / 256 * 256);
+    int rc = launch_deflicker_batch(d_frames, fstride, nframes, samples, white, middle, d_hist, d_med, stream);
+    if (rc) return rc;
+    MLV_HIP(hipMemcpyAsync(med, d_med, sizeof(uint16_t) * nframes, hipMemcpyDeviceToHost, stream));
+    MLV_HIP(hipStreamSynchronize(stream));
+    return MLVFS_AMD_OK;
+}
+
+// exposure_bias as main.c:903-905 stores it, from a median (host libm)
+void deflicker_bias(int target, int black_level, uint16_t median, int32_t exposure_bias[2])
+{
+    const uint16_t black = (uint16_t)black_level;
+    const double correction = log2((double)(target - black) / (median - black));
+    exposure_bias[0] = (int32_t)(correction * 10000);
+    exposure_bias[1] = 10000;
+}
+
 }  // namespace mlv
 
 using namespace mlv;
@@ -211,6 +282,66 @@ int mlvfs_amd_deflicker_dev(const mlvfs_amd_geom_t *geom, const void *d_frame, s
     const double correction = log2((double)(target - black) / (median - black));
     exposure_bias[0] = (int32_t)(correction * 10000);
     exposure_bias[1] = 10000;
+    return MLVFS_AMD_OK;
+}
+
+static bool batch_args_ok(const mlvfs_amd_geom_t *geom, const void *d_frames, size_t stride, int nframes, const char *what)
+{
+    if (!geom || !d_frames || nframes < 0) { set_error("%s: null argument", what); return false; }
+    if (geom->width < 2 || geom->height < 2) { set_error("%s: %dx%d frame not supported", what, geom->width, geom->height); return false; }
+    if (nframes > 1 && (stride < (size_t)geom->width * geom->height * 2 || (stride & 1))) { set_error("%s: stride smaller than a frame or odd", what); return false; }
+    if (nframes > 65535) { set_error("%s: at most 65535 frames per call", what); return false; }
+    return true;
+}
+
+// the deflicker of `nframes` device frames: one histogram launch, one median launch (a workgroup per frame), one copy of the
+// medians; log2 on the host.  Synchronises the stream.
+int mlvfs_amd_deflicker_batch_dev(const mlvfs_amd_geom_t *geom, const void *d_frames, size_t stride, int nframes, size_t size_bytes, int target,
+                                  int32_t *exposure_bias, void *stream)
+{
+    if (!batch_args_ok(geom, d_frames, stride, nframes, "deflicker_batch") || !exposure_bias) {
+        if (!exposure_bias) set_error("deflicker_batch: null argument");
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (geom->bpp < 1 || geom->bpp > 15 || size_bytes < 2 || size_bytes > (size_t)geom->width * geom->height * 2) {
+        set_error("deflicker_batch: unsupported bit depth / size");
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    const size_t need = deflicker_batch_scratch_bytes(geom->bpp, nframes);
+    if (c->ensure(0, need)) return MLVFS_AMD_ERR_HIP;
+    std::vector<uint16_t> med(nframes);
+    const int rc = deflicker_batch_device(d_frames, stride, nframes, geom->bpp, size_bytes, c->d_b, need, med.data(), pick_stream(stream, c));
+    if (rc) return rc;
+    for (int f = 0; f < nframes; f++) deflicker_bias(target, geom->black, med[f], exposure_bias + 2 * f);
+    return MLVFS_AMD_OK;
+}
+
+// the dual-ISO preview of `nframes` device frames, in place: results[f] = 1 converted, 0 not dual ISO (left untouched).
+// Synchronises the stream.
+int mlvfs_amd_hdr_preview_batch_dev(const mlvfs_amd_geom_t *geom, void *d_frames, size_t stride, int nframes, size_t max_size, int *results,
+                                    void *stream)
+{
+    if (!batch_args_ok(geom, d_frames, stride, nframes, "hdr_preview_batch")) return MLVFS_AMD_ERR_ARG;
+    if (!results) { set_error("hdr_preview_batch: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    const Geom g{ geom->width, geom->height, geom->bpp, geom->black, geom->white };
+    const size_t bytes = (size_t)g.w * g.h * 2, fs = nframes > 1 ? stride : bytes;
+    const size_t hist_bytes = (4 * (size_t)((uint16_t)g.white + 1) * sizeof(unsigned) * nframes + 255) / 256 * 256;
+    const size_t par_at = hist_bytes, out_at = par_at + (sizeof(HdrPreviewParams) * nframes + 255) / 256 * 256;
+    if (c->ensure(0, out_at + fs * (nframes - 1) + bytes)) return MLVFS_AMD_ERR_HIP;
+    hipStream_t s = pick_stream(stream, c);
+    uint8_t *b = (uint8_t *)c->d_b;
+    int rc = hdr_preview_batch_device(c, g, d_frames, b + out_at, fs, nframes, max_size, (unsigned *)b, (HdrPreviewParams *)(b + par_at), nullptr,
+                                      results, s);
+    if (rc) return rc;
+    for (int f = 0; f < nframes; f++)
+        if (results[f] == 1) MLV_HIP(hipMemcpyAsync((uint8_t *)d_frames + f * fs, b + out_at + f * fs, bytes, hipMemcpyDeviceToDevice, s));
+    MLV_HIP(hipStreamSynchronize(s));                                   // d_b is the thread's scratch (see mlvfs_amd_hdr_preview_dev)
     return MLVFS_AMD_OK;
 }
 

@@ -20,6 +20,10 @@
 //                        (patternnoise.c:185-254)
 //                        (the same kernel, "plain", gives the lower median of a plane's column offsets, patternnoise.c:268)
 //   k_pn_apply           add offsets (clamp +-32767), remove their median (clamp 0..32760)
+//
+// Every kernel takes the frame index from its grid (the last dimension it uses) and the distance between frames, in elements, for
+// each buffer it touches: a batch of N frames costs the launches of one (mlvfs_amd_fix_pattern_noise_dev; the drop-in symbol is a
+// batch of one).
 #include "clip.h"
 
 namespace mlv {
@@ -29,9 +33,12 @@ __device__ __forceinline__ int plane_px(const int16_t *raw, int w, int c, int x,
     return raw[(2 * x + (c & 1)) + (size_t)(2 * y + (c >> 1)) * w];
 }
 
-__global__ __launch_bounds__(256) void k_pn_transpose(const int16_t *__restrict__ in, int16_t *__restrict__ out, int w, int h)
+__global__ __launch_bounds__(256) void k_pn_transpose(const int16_t *__restrict__ in, int16_t *__restrict__ out, int w, int h, size_t in_fs,
+                                                      size_t out_fs)
 {
     __shared__ int16_t tile[32][33];
+    in += blockIdx.z * in_fs;
+    out += blockIdx.z * out_fs;
     const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
     for (int r = threadIdx.y; r < 32; r += 8) {
         const int x = bx + threadIdx.x, y = by + r;
@@ -83,8 +90,10 @@ __device__ __forceinline__ int pn_lower_median(const int16_t *arr, int ws, const
 }
 
 __global__ __launch_bounds__(256) void k_pn_smooth(const int16_t *__restrict__ raw, int w, int hw, int reach, int thr,
-                                                   int16_t *__restrict__ smooth /* [4][hh][hw] */, int hh)
+                                                   int16_t *__restrict__ smooth /* [4][hh][hw] */, int hh, size_t raw_fs, size_t sm_fs)
 {
+    raw += blockIdx.y * raw_fs;
+    smooth += blockIdx.y * sm_fs;
     extern __shared__ __attribute__((aligned(16))) int16_t row[];     // avg, g1, g2, drg, dbg: 5 x (hw + 2 PN_PAD), hw rounded up to even
     const int hs = ((hw + 1) & ~1) + 2 * PN_PAD;
     int16_t *avg = row, *g1 = row + hs, *g2 = row + 2 * hs, *drg = row + 3 * hs, *dbg = row + 4 * hs;
@@ -143,10 +152,14 @@ __device__ __forceinline__ bool noise_at(const int16_t *raw, int w, int hw, size
 // side.  (Until the end of round 3 a workgroup per column and plane walked the column in the frame itself: 83 us per pass.)
 constexpr int PN_MASKED = 1 << 20;                           // above every int16
 __global__ __launch_bounds__(256) void k_pn_noise_t(const int16_t *__restrict__ raw, int w, int hw, int hh, int white,
-                                                    const int16_t *__restrict__ smooth, int *__restrict__ T /* [4][hw][hh] */)
+                                                    const int16_t *__restrict__ smooth, int *__restrict__ T /* [4][hw][hh] */,
+                                                    size_t raw_fs, size_t sm_fs, size_t t_fs)
 {
     __shared__ int tile[32][33];
-    const int c = blockIdx.z, bx = blockIdx.x * 32, by = blockIdx.y * 32;
+    const int c = blockIdx.z & 3, f = blockIdx.z >> 2, bx = blockIdx.x * 32, by = blockIdx.y * 32;      // z = 4 * frame + plane
+    raw += f * raw_fs;
+    smooth += f * sm_fs;
+    T += f * t_fs;
     const size_t n = (size_t)hw * hh;
     const int16_t *sm = smooth + (size_t)c * n;
     for (int r = threadIdx.y; r < 32; r += 8) {
@@ -170,9 +183,12 @@ __global__ __launch_bounds__(256) void k_pn_noise_t(const int16_t *__restrict__ 
 // plain: the lower median itself, whatever the number of samples (the median of a plane's column offsets, patternnoise.c:268:
 // T = the offsets [4][1][hw], one "column" per plane)
 template <int R>
-__global__ __launch_bounds__(256) void k_pn_column_offsets(const int *__restrict__ T, int hw, int hh, int *__restrict__ offs /* [4][hw] */, bool plain)
+__global__ __launch_bounds__(256) void k_pn_column_offsets(const int *__restrict__ T, int hw, int hh, int *__restrict__ offs /* [4][hw] */, bool plain,
+                                                           size_t t_fs, size_t o_fs)
 {
     const int x = blockIdx.x, c = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    T += blockIdx.y * t_fs;
+    offs += blockIdx.y * o_fs;
     const int *col = T + ((size_t)c * hw + x) * hh;
     int v[R > 0 ? R : 1];
     int cnt = 0, lo = 0x7FFFFFFF, hi = -0x7FFFFFFF - 1;
@@ -213,8 +229,11 @@ __global__ __launch_bounds__(256) void k_pn_column_offsets(const int *__restrict
 }
 
 __global__ __launch_bounds__(256) void k_pn_apply(int16_t *__restrict__ raw, int w, int h, int hw, const int *__restrict__ offs,
-                                                  const int *__restrict__ mc)
+                                                  const int *__restrict__ mc, size_t raw_fs, size_t o_fs, size_t mc_fs)
 {
+    raw += blockIdx.z * raw_fs;
+    offs += blockIdx.z * o_fs;
+    mc += blockIdx.z * mc_fs;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= (w & ~1) || y >= (h & ~1)) return;
     const int c = (x & 1) + 2 * (y & 1);
@@ -244,30 +263,54 @@ __global__ __launch_bounds__(256) void k_pn_debug_view(const int16_t *__restrict
     view[(size_t)(2 * y + (c >> 1)) * w + 2 * x + (c & 1)] = v;
 }
 
+// where one direction of a batch works: frame f of each buffer starts f * its *_fs elements behind the pointer
+struct PnPass {
+    int16_t *raw; size_t raw_fs;             // the frames (or their transposes)
+    int16_t *smooth; size_t sm_fs;           // 4 smoothed half-res planes per frame
+    int *noise_t; size_t t_fs;               // transposed noise samples, 4 * hw * hh per frame
+    int *offs; size_t o_fs;                  // 4 * hw column offsets per frame
+    int *mc; size_t mc_fs;                   // 4 medians of the offsets per frame
+};
+
+// one direction on nf frames of w x h int16 (rows of w elements, frames raw_fs apart): 5 launches whatever nf is
+static int column_pass_batch(const PnPass &p, int w, int h, int white, int nf, hipStream_t stream)
+{
+    const int hw = w / 2, hh = h / 2;
+    if (hw <= 0 || hh <= 0 || nf <= 0) return MLVFS_AMD_OK;
+    const size_t shmem = (size_t)5 * (((hw + 1) & ~1) + 2 * PN_PAD) * sizeof(int16_t);
+    if (shmem > 150 * 1024) { set_error("fix_pattern_noise: rows of %d pixels do not fit in LDS", w); return MLVFS_AMD_ERR_ARG; }
+    MLV_HIP(hipFuncSetAttribute((const void *)k_pn_smooth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL(k_pn_smooth, dim3(hh, nf), dim3(256), shmem, stream, p.raw, w, hw, 50 / 2, 500, p.smooth, hh, p.raw_fs, p.sm_fs);
+    hipLaunchKernelGGL(k_pn_noise_t, dim3((hw + 31) / 32, (hh + 31) / 32, 4 * nf), dim3(32, 8), 0, stream, p.raw, w, hw, hh, white, p.smooth,
+                       p.noise_t, p.raw_fs, p.sm_fs, p.t_fs);
+    auto offsets = hh <= 64 * 12 ? k_pn_column_offsets<12> : (hh <= 64 * 32 ? k_pn_column_offsets<32> : k_pn_column_offsets<0>);
+    hipLaunchKernelGGL(offsets, dim3(hw, nf), dim3(256), 0, stream, p.noise_t, hw, hh, p.offs, false, p.t_fs, p.o_fs);
+    // lower median of each plane's offsets: one workgroup per frame
+    auto median = hw <= 64 * 12 ? k_pn_column_offsets<12> : (hw <= 64 * 32 ? k_pn_column_offsets<32> : k_pn_column_offsets<0>);
+    hipLaunchKernelGGL(median, dim3(1, nf), dim3(256), 0, stream, p.offs, 1, hw, p.mc, true, p.o_fs, p.mc_fs);
+    hipLaunchKernelGGL(k_pn_apply, dim3((w + 255) / 256, h, nf), dim3(256), 0, stream, p.raw, w, h, hw, p.offs, p.mc, p.raw_fs, p.o_fs, p.mc_fs);
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
 // one direction on a device frame (w x h int16).  scratch: smooth 4*hw*hh int16, offs 4*hw int, mc 4 int
 static int column_pass(int16_t *d_raw, int w, int h, int white, int16_t *d_smooth, int *d_offs, int *d_mc, int *d_noise_t, hipStream_t stream, int flags)
 {
     const int hw = w / 2, hh = h / 2;
     if (hw <= 0 || hh <= 0) return MLVFS_AMD_OK;
-    const size_t shmem = (size_t)5 * (((hw + 1) & ~1) + 2 * PN_PAD) * sizeof(int16_t);
-    if (shmem > 150 * 1024) { set_error("fix_pattern_noise: rows of %d pixels do not fit in LDS", w); return MLVFS_AMD_ERR_ARG; }
-    MLV_HIP(hipFuncSetAttribute((const void *)k_pn_smooth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(k_pn_smooth, dim3(hh), dim3(256), shmem, stream, d_raw, w, hw, 50 / 2, 500, d_smooth, hh);
     if (flags & (2 | 4 | 8)) {
+        const size_t shmem = (size_t)5 * (((hw + 1) & ~1) + 2 * PN_PAD) * sizeof(int16_t);
+        if (shmem > 150 * 1024) { set_error("fix_pattern_noise: rows of %d pixels do not fit in LDS", w); return MLVFS_AMD_ERR_ARG; }
+        MLV_HIP(hipFuncSetAttribute((const void *)k_pn_smooth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        hipLaunchKernelGGL(k_pn_smooth, dim3(hh), dim3(256), shmem, stream, d_raw, w, hw, 50 / 2, 500, d_smooth, hh, (size_t)0, (size_t)0);
         int16_t *d_view = (int16_t *)d_noise_t;                       // the samples' buffer is free in this mode
         hipLaunchKernelGGL(k_pn_debug_view, dim3((unsigned)(((size_t)hw * hh + 255) / 256), 4), dim3(256), 0, stream, d_raw, w, hw, hh, white, d_smooth, flags, d_view);
         MLV_HIP(hipGetLastError());
         MLV_HIP(hipMemcpyAsync(d_raw, d_view, (size_t)w * h * 2, hipMemcpyDeviceToDevice, stream));
         return MLVFS_AMD_OK;
     }
-    hipLaunchKernelGGL(k_pn_noise_t, dim3((hw + 31) / 32, (hh + 31) / 32, 4), dim3(32, 8), 0, stream, d_raw, w, hw, hh, white, d_smooth, d_noise_t);
-    auto offsets = hh <= 64 * 12 ? k_pn_column_offsets<12> : (hh <= 64 * 32 ? k_pn_column_offsets<32> : k_pn_column_offsets<0>);
-    hipLaunchKernelGGL(offsets, dim3(hw), dim3(256), 0, stream, d_noise_t, hw, hh, d_offs, false);
-    auto median = hw <= 64 * 12 ? k_pn_column_offsets<12> : (hw <= 64 * 32 ? k_pn_column_offsets<32> : k_pn_column_offsets<0>);
-    hipLaunchKernelGGL(median, dim3(1), dim3(256), 0, stream, d_offs, 1, hw, d_mc, true);      // lower median of each plane's offsets
-    hipLaunchKernelGGL(k_pn_apply, dim3((w + 255) / 256, h), dim3(256), 0, stream, d_raw, w, h, hw, d_offs, d_mc);
-    MLV_HIP(hipGetLastError());
-    return MLVFS_AMD_OK;
+    const PnPass p{ d_raw, 0, d_smooth, 0, d_noise_t, 0, d_offs, 0, d_mc, 0 };
+    return column_pass_batch(p, w, h, white, 1, stream);
 }
 
 size_t pattern_noise_scratch_bytes(int w, int h)
@@ -290,11 +333,53 @@ int launch_pattern_noise(void *d_raw, int w, int h, int white, void *d_scratch, 
     int rc = MLVFS_AMD_OK;
     if (!flags || !(flags & 1)) rc = column_pass(raw, w, h, white, d_smooth, d_offs, d_mc, d_noise_t, stream, flags);
     if (rc || (flags && !(flags & 1))) return rc;
-    hipLaunchKernelGGL(k_pn_transpose, dim3((w + 31) / 32, (h + 31) / 32), dim3(32, 8), 0, stream, raw, d_t, w, h);
+    hipLaunchKernelGGL(k_pn_transpose, dim3((w + 31) / 32, (h + 31) / 32), dim3(32, 8), 0, stream, raw, d_t, w, h, (size_t)0, (size_t)0);
     rc = column_pass(d_t, h, w, white, d_smooth, d_offs, d_mc, d_noise_t, stream, flags);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_pn_transpose, dim3((h + 31) / 32, (w + 31) / 32), dim3(32, 8), 0, stream, d_t, raw, h, w);
+    hipLaunchKernelGGL(k_pn_transpose, dim3((h + 31) / 32, (w + 31) / 32), dim3(32, 8), 0, stream, d_t, raw, h, w, (size_t)0, (size_t)0);
     MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+// ---- batches (mlvfs_amd_fix_pattern_noise_dev, the mount): per frame of a sub-batch the transposed frame, the smoothed planes,
+// the transposed noise samples, the offsets and their medians -- 8 bytes per pixel and a little; a batch larger than the scratch
+// is cut into sub-batches that each cost the 12 launches of one frame
+static size_t pn_up(size_t b) { return (b + 255) / 256 * 256; }
+static size_t pn_offs_elems(int w, int h) { return (size_t)2 * (w > h ? w : h) + 8; }
+size_t pattern_noise_batch_frame_bytes(int w, int h)
+{
+    const size_t n = (size_t)w * h;
+    return pn_up(n * 2) + pn_up(n * 2) + pn_up(n * 4) + pn_up(pn_offs_elems(w, h) * 4) + 256;
+}
+
+// d_frames: nframes w x h int16 frames, fstride BYTES apart (even); white: the frames' raw_info.white_level
+int launch_pattern_noise_batch(void *d_frames, size_t fstride, int nframes, int w, int h, int white, void *d_scratch, size_t scratch_bytes,
+                               hipStream_t stream)
+{
+    const size_t per = pattern_noise_batch_frame_bytes(w, h), n = (size_t)w * h, raw_fs = fstride / 2;
+    const int fit = (int)std::min<size_t>((size_t)nframes, scratch_bytes / per);
+    if (fit < 1) { set_error("fix_pattern_noise: scratch smaller than one frame's"); return MLVFS_AMD_ERR_ARG; }
+    const int parts = (nframes + fit - 1) / fit, sub = (nframes + parts - 1) / parts;      // even sub-batches: 8 frames that fit 7 go 4 + 4
+    uint8_t *b = (uint8_t *)d_scratch;
+    int16_t *d_t = (int16_t *)b;
+    int16_t *d_smooth = (int16_t *)(b + sub * pn_up(n * 2));
+    int *d_noise = (int *)(b + sub * (pn_up(n * 2) * 2));
+    int *d_offs = (int *)(b + sub * (pn_up(n * 2) * 2 + pn_up(n * 4)));
+    int *d_mc = (int *)(b + sub * (pn_up(n * 2) * 2 + pn_up(n * 4) + pn_up(pn_offs_elems(w, h) * 4)));
+    const size_t sm_fs = pn_up(n * 2) / 2, t_fs = pn_up(n * 4) / 4, o_fs = pn_up(pn_offs_elems(w, h) * 4) / 4, mc_fs = 64;
+    for (int f0 = 0; f0 < nframes; f0 += sub) {
+        const int nf = std::min(sub, nframes - f0);
+        int16_t *raw = (int16_t *)d_frames + (size_t)f0 * raw_fs;
+        PnPass p{ raw, raw_fs, d_smooth, sm_fs, d_noise, t_fs, d_offs, o_fs, d_mc, mc_fs };
+        int rc = column_pass_batch(p, w, h, white, nf, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_pn_transpose, dim3((w + 31) / 32, (h + 31) / 32, nf), dim3(32, 8), 0, stream, raw, d_t, w, h, raw_fs, sm_fs);
+        p.raw = d_t; p.raw_fs = sm_fs;
+        rc = column_pass_batch(p, h, w, white, nf, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_pn_transpose, dim3((h + 31) / 32, (w + 31) / 32, nf), dim3(32, 8), 0, stream, d_t, raw, h, w, sm_fs, raw_fs);
+        MLV_HIP(hipGetLastError());
+    }
     return MLVFS_AMD_OK;
 }
 

@@ -101,6 +101,30 @@ struct Reader {
     }
 };
 
+// ---- the reader's staging, shared by its streaming calls (called with stage_mu held) -----------------------------------------
+// two page-locked buffers of at least `bytes` each; false: out of page-locked memory (nothing is left allocated)
+bool ensure_stage(const Reader &r, size_t bytes)
+{
+    if (r.stage_bytes >= bytes) return true;
+    mlvfs_amd_host_free(r.stage[0]);
+    mlvfs_amd_host_free(r.stage[1]);
+    r.stage[0] = (uint8_t *)mlvfs_amd_host_alloc(bytes);
+    r.stage[1] = (uint8_t *)mlvfs_amd_host_alloc(bytes);
+    r.stage_bytes = (r.stage[0] && r.stage[1]) ? bytes : 0;
+    return r.stage_bytes != 0;
+}
+
+// the device buffer packed payloads are uploaded to before the unpack
+int ensure_packed_dev(const Reader &r, size_t bytes)
+{
+    if (r.di_packed_bytes >= bytes) return MLVFS_AMD_OK;
+    if (r.d_di_packed) (void)hipFree(r.d_di_packed);
+    r.d_di_packed = nullptr; r.di_packed_bytes = 0;
+    MLV_HIP(hipMalloc(&r.d_di_packed, bytes));
+    r.di_packed_bytes = bytes;
+    return MLVFS_AMD_OK;
+}
+
 // ---- chunks ---------------------------------------------------------------------------------------------------------
 bool open_chunks(Reader &r)
 {
@@ -375,6 +399,45 @@ int read_frames(const Reader &r, int first, int count, uint8_t *dst, size_t stri
 
 }  // namespace
 
+// The mount (mount.cpp): frames first .. first + count - 1 of one geometry as 16-bit pixels in HBM, `dstride` bytes apart, on `s` --
+// payloads read by io_threads threads into the reader's page-locked staging (LZMA decoded there), then uploaded and unpacked
+// (k_unpack) or, LJ92 clips, decoded on the GPU.  Returns with the stream drained: the staging is the next caller's again.
+int mlv::reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
+                           hipStream_t s)
+{
+    const Reader &r = *(const Reader *)reader;
+    if (count <= 0) return MLVFS_AMD_OK;
+    frame_headers fh0;
+    if (!frame_headers_of(r, first, &fh0)) { set_error("mlv: frame %d has no usable headers", first); return MLVFS_AMD_ERR_ARG; }
+    const bool lj92 = (fh0.file_hdr.videoClass & CLASS_LJ92) && !(fh0.file_hdr.videoClass & CLASS_LZMA);
+    size_t stride = 0;
+    for (int k = 0; k < count; k++) {
+        Span sp;
+        if (!payload_span(r, first + k, &sp, lj92)) return MLVFS_AMD_ERR_ARG;
+        stride = std::max(stride, lj92 ? sp.bytes : sp.bytes + 2);
+    }
+    stride = (stride + 15) / 16 * 16;
+    std::lock_guard<std::mutex> lk(r.stage_mu);                     // one streaming call per reader at a time
+    if (!ensure_stage(r, stride * count)) return MLVFS_AMD_ERR_NOMEM;
+    std::vector<size_t> sizes(count);
+    int rc = read_frames(r, first, count, r.stage[0], stride, io_threads, lj92, sizes.data());
+    if (rc) return rc;
+    if (lj92) {
+        std::vector<const void *> ptr(count);
+        std::vector<size_t> len(count);
+        for (int i = 0; i < count; i++) { ptr[i] = r.stage[0] + (size_t)i * stride + 4; len[i] = sizes[i] - 4; }
+        return mlvfs_amd_lj92_decode_dev(ptr.data(), len.data(), count, w, h, d_frames, dstride, s);     // (synchronises s)
+    }
+    rc = ensure_packed_dev(r, stride * count);
+    if (rc) return rc;
+    const mlvfs_amd_geom_t geom{ w, h, bpp, 0, 0, 0, 0 };
+    MLV_HIP(hipMemcpyAsync(r.d_di_packed, r.stage[0], stride * count, hipMemcpyHostToDevice, s));
+    rc = mlvfs_amd_unpack_dev(&geom, r.d_di_packed, stride, d_frames, dstride, count, s);
+    if (rc) return rc;
+    MLV_HIP(hipStreamSynchronize(s));
+    return MLVFS_AMD_OK;
+}
+
 extern "C" {
 
 void *mlvfs_amd_mlv_open(const char *mlv_path, int use_idx_file)
@@ -452,15 +515,8 @@ int mlvfs_amd_mlv_process(const void *reader, mlvfs_amd_clip_t *clip, int first,
         stride = (s0.bytes + 2 + 15) / 16 * 16;
     }
     std::lock_guard<std::mutex> lk(r.stage_mu);                     // one streaming call per reader at a time
-    if (r.stage_bytes < stride * batch_frames) {
-        mlvfs_amd_host_free(r.stage[0]);
-        mlvfs_amd_host_free(r.stage[1]);
-        r.stage[0] = (uint8_t *)mlvfs_amd_host_alloc(stride * batch_frames);
-        r.stage[1] = (uint8_t *)mlvfs_amd_host_alloc(stride * batch_frames);
-        r.stage_bytes = (r.stage[0] && r.stage[1]) ? stride * batch_frames : 0;
-    }
     uint8_t *const *stage = r.stage;
-    int rc = r.stage_bytes ? MLVFS_AMD_OK : MLVFS_AMD_ERR_NOMEM;
+    int rc = ensure_stage(r, stride * batch_frames) ? MLVFS_AMD_OK : MLVFS_AMD_ERR_NOMEM;
     std::vector<size_t> sizes[2] = { std::vector<size_t>(batch_frames), std::vector<size_t>(batch_frames) };
     const size_t px_bytes = (size_t)fh0.rawi_hdr.xRes * fh0.rawi_hdr.yRes * 2, dstride = (px_bytes + 255) / 256 * 256;
     if (rc == MLVFS_AMD_OK && lj92 && r.dev_bytes < dstride * batch_frames) {
@@ -554,20 +610,8 @@ int mlvfs_amd_mlv_process_dualiso(const void *reader, int first, int count, void
     mlv::ThreadCtx *c = mlv::thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
     std::lock_guard<std::mutex> lk(r.stage_mu);                     // one streaming call per reader at a time
-    if (r.stage_bytes < stride * batch_frames) {
-        mlvfs_amd_host_free(r.stage[0]);
-        mlvfs_amd_host_free(r.stage[1]);
-        r.stage[0] = (uint8_t *)mlvfs_amd_host_alloc(stride * batch_frames);
-        r.stage[1] = (uint8_t *)mlvfs_amd_host_alloc(stride * batch_frames);
-        r.stage_bytes = (r.stage[0] && r.stage[1]) ? stride * batch_frames : 0;
-        if (!r.stage_bytes) return MLVFS_AMD_ERR_NOMEM;
-    }
-    if (r.di_packed_bytes < stride * batch_frames) {
-        if (r.d_di_packed) (void)hipFree(r.d_di_packed);
-        r.d_di_packed = nullptr; r.di_packed_bytes = 0;
-        MLV_HIP(hipMalloc(&r.d_di_packed, stride * batch_frames));
-        r.di_packed_bytes = stride * batch_frames;
-    }
+    if (!ensure_stage(r, stride * batch_frames)) return MLVFS_AMD_ERR_NOMEM;
+    if (int rc0 = ensure_packed_dev(r, stride * batch_frames)) return rc0;
     if (r.di_frames_bytes < dstride * batch_frames) {
         for (int k = 0; k < 2; k++) {
             if (r.d_di_frames[k]) (void)hipFree(r.d_di_frames[k]);

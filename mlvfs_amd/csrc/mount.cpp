@@ -1,0 +1,275 @@
+// mount.cpp -- a clip served as MLVFS serves it: process_frame (mlvfs/main.c:908-1005) and the two dng_get_header_data calls of it,
+// batch by batch, for every mount option that shapes a frame's .dng file.
+//
+// Per batch, in main.c's order: read + decode / unpack (the reader's staging, mlvreader.cpp), deflicker (one histogram launch, one
+// median launch, log2 on the host), the frame's header, pattern noise (12 launches per sub-batch), dual ISO (the batched preview,
+// or the batched full conversion), then per frame the route main.c takes: a converted frame gets the header again (x4 levels) and
+// chroma smoothing (preview only) + stripes; any other frame focus pixels, bad pixels, chroma smoothing (not under dual_iso = 2),
+// stripes.  Chroma smoothing and stripes run as the fused pass over runs of consecutive frames of one route and level set.
+//
+// Order-dependent state, as a fresh process builds it from the frames it serves in order:
+//   stripes       one correction per mount, from the first frame that reaches the stage (stripes.c:31-69, main.c:979-993)
+//   bad pixels    the process's map per clip GUID (dropin.cpp, cs.c:233-312), detected by the first frame that reaches a repair; under
+//                 dual_iso = 2 a converted frame repairs inside the conversion, so until the map exists frames are served one by one
+//   dual ISO      the table caches of dualiso.cpp (process-wide), filled by the first frame that converts
+#include "clip.h"
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace mlv;
+
+namespace {
+
+struct Mount {
+    const void *reader = nullptr;
+    mlvfs_amd_mount_opts_t o{};
+    std::vector<char> basename;              // dng_get_header_data takes a char *
+    std::mutex mu;
+    bool stripes_known = false;              // stripes_get_correction(mlv_filename) != NULL
+    int stripes_needed = 0;
+    int32_t coef[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    int device = -1;
+    void *d_frames = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    size_t frames_bytes = 0, scratch_bytes = 0;
+
+    void release()
+    {
+        if (d_frames) (void)hipFree(d_frames);
+        if (d_out) (void)hipFree(d_out);
+        if (d_scratch) (void)hipFree(d_scratch);
+        d_frames = d_out = d_scratch = nullptr;
+        frames_bytes = scratch_bytes = 0;
+    }
+    ~Mount() { release(); }
+
+    int ensure(int dev, size_t fbytes, size_t sbytes)
+    {
+        if (dev != device) { release(); device = dev; }
+        if (frames_bytes < fbytes) {
+            if (d_frames) (void)hipFree(d_frames);
+            if (d_out) (void)hipFree(d_out);
+            d_frames = d_out = nullptr;
+            frames_bytes = 0;
+            MLV_HIP(hipMalloc(&d_frames, fbytes));
+            MLV_HIP(hipMalloc(&d_out, fbytes));
+            frames_bytes = fbytes;
+        }
+        if (scratch_bytes < sbytes) {
+            if (d_scratch) (void)hipFree(d_scratch);
+            d_scratch = nullptr;
+            scratch_bytes = 0;
+            MLV_HIP(hipMalloc(&d_scratch, sbytes));
+            scratch_bytes = sbytes;
+        }
+        return MLVFS_AMD_OK;
+    }
+};
+
+bool same_levels(const frame_headers &a, const frame_headers &b)
+{
+    return a.rawi_hdr.raw_info.black_level == b.rawi_hdr.raw_info.black_level && a.rawi_hdr.raw_info.white_level == b.rawi_hdr.raw_info.white_level;
+}
+
+size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+// pattern-noise scratch of a batch: whole frames, at most pattern_noise_scratch_cap() (sub-batches beyond that)
+size_t o_pn_bytes(const mlvfs_amd_mount_opts_t &o, int w, int h, int batch)
+{
+    if (!o.fix_pattern_noise) return 0;
+    const size_t per = pattern_noise_batch_frame_bytes(w, h);
+    return per * std::max<size_t>(1, std::min<size_t>((size_t)batch, pattern_noise_scratch_cap() / per));
+}
+
+// frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride)
+int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results)
+{
+    const mlvfs_amd_mount_opts_t &o = m.o;
+    hipStream_t s = c->stream;
+    const int w = fh[0].rawi_hdr.xRes, h = fh[0].rawi_hdr.yRes, bpp = fh[0].rawi_hdr.raw_info.bits_per_pixel;
+    const size_t img = (size_t)w * h * 2, hdr = dng_get_header_size();
+    uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
+    int rc = MLVFS_AMD_OK;
+    // deflicker (main.c:943): before the header, which writes exposure_bias as BaselineExposure
+    if (o.deflicker) {
+        std::vector<uint16_t> med(n);
+        rc = deflicker_batch_device(F, dstride, n, bpp, img, m.d_scratch, m.scratch_bytes, med.data(), s);
+        if (rc) return rc;
+        for (int k = 0; k < n; k++) deflicker_bias(o.deflicker, fh[k].rawi_hdr.raw_info.black_level, med[k], fh[k].rawi_hdr.raw_info.exposure_bias);
+    }
+    for (int k = 0; k < n; k++) (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, hdr, o.fps, m.basename.data());    // main.c:944
+    // pattern noise (main.c:946-949): runs of one white level
+    if (o.fix_pattern_noise && w >= 2 && h >= 2 && !(w & 1) && !(h & 1)) {
+        for (int k0 = 0, k1; k0 < n; k0 = k1) {
+            for (k1 = k0 + 1; k1 < n && fh[k1].rawi_hdr.raw_info.white_level == fh[k0].rawi_hdr.raw_info.white_level; k1++) {}
+            rc = launch_pattern_noise_batch(F + k0 * dstride, dstride, k1 - k0, w, h, fh[k0].rawi_hdr.raw_info.white_level, m.d_scratch,
+                                            m.scratch_bytes, s);
+            if (rc) return rc;
+        }
+    }
+    // dual ISO (main.c:951-960)
+    std::vector<int> conv(n, 0);
+    if (o.dual_iso == 1) {
+        for (int k0 = 0, k1; k0 < n; k0 = k1) {
+            for (k1 = k0 + 1; k1 < n && same_levels(fh[k1], fh[k0]); k1++) {}
+            const auto &ri = fh[k0].rawi_hdr.raw_info;
+            const Geom g{ w, h, bpp, ri.black_level, ri.white_level };
+            const size_t hist = up256(4 * (size_t)((uint16_t)g.white + 1) * sizeof(unsigned) * (k1 - k0));
+            rc = hdr_preview_batch_device(c, g, F + k0 * dstride, O + k0 * dstride, dstride, k1 - k0, img, (unsigned *)m.d_scratch,
+                                          (HdrPreviewParams *)((uint8_t *)m.d_scratch + hist), fh + k0, conv.data() + k0, s);
+            if (rc) return rc;
+        }
+        for (int k = 0; k < n; k++)
+            if (conv[k]) MLV_HIP(hipMemcpyAsync(F + k * dstride, O + k * dstride, img, hipMemcpyDeviceToDevice, s));
+    } else if (o.dual_iso == 2) {
+        // the drop-in's repairs before the conversion (focus map, fix_bad_pixels mode) need the frame's headers: one frame at a time
+        bool per_frame = o.fix_bad_pixels != 0;
+        for (int k = 0; k < n && !per_frame; k++) per_frame = focus_map_applies(&fh[k], c, 1);
+        for (int k0 = 0, k1; k0 < n; k0 = k1) {
+            for (k1 = k0 + 1; !per_frame && k1 < n && same_levels(fh[k1], fh[k0]); k1++) {}
+            const auto &ri = fh[k0].rawi_hdr.raw_info;
+            rc = cr2hdr20_batch_fh(c, per_frame ? &fh[k0] : nullptr, F + k0 * dstride, per_frame ? img : dstride, k1 - k0, w, h, ri.black_level,
+                                   ri.white_level, o.hdr_interpolation_method, !o.hdr_no_fullres, !o.hdr_no_alias_map, o.chroma_smooth,
+                                   o.fix_bad_pixels, s, conv.data() + k0);
+            if (rc < 0) return rc;
+            rc = MLVFS_AMD_OK;
+        }
+    }
+    for (int k = 0; k < n; k++) {
+        if (results) results[k] = conv[k] == 1;
+        if (conv[k] != 1) continue;
+        fh[k].rawi_hdr.raw_info.black_level *= 4;                      // hdr.c:223-224, 1951-1952
+        fh[k].rawi_hdr.raw_info.white_level *= 4;
+        (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, img, o.fps, m.basename.data());   // main.c:962-966
+    }
+    // frames that were not converted: focus pixels, bad pixels (main.c:967-975), in serve order
+    for (int k = 0; k < n; k++) {
+        if (conv[k] == 1) continue;
+        rc = focus_pixels_device(&fh[k], c, F + k * dstride, 0, nullptr);
+        if (!rc && o.fix_bad_pixels) rc = bad_pixels_device(&fh[k], c, F + k * dstride, o.fix_bad_pixels == 2, 0, nullptr);
+        if (rc) return rc;
+    }
+    // chroma smoothing (main.c:977-980) and stripes (main.c:982-995): the fused pass over runs of one route and level set
+    std::vector<uint8_t *> final_at(n);
+    auto cs_of = [&](int k) {
+        const int cs = o.chroma_smooth;
+        if (!cs || o.dual_iso == 2) return 0;
+        if (cs != 2 && cs != 3 && cs != 5) { fprintf(stderr, "Unsupported chroma smooth method\n"); return 0; }
+        if (fh[k].rawi_hdr.raw_info.black_level > 16384) { fprintf(stderr, "Black level too large for processing\n"); return 0; }
+        return cs;
+    };
+    for (int k0 = 0, k1; k0 < n; k0 = k1) {
+        const int cs = cs_of(k0);
+        for (k1 = k0 + 1; k1 < n && same_levels(fh[k1], fh[k0]) && (conv[k1] == 1) == (conv[k0] == 1) && cs_of(k1) == cs; k1++) {}
+        const auto &ri = fh[k0].rawi_hdr.raw_info;
+        const Geom g{ w, h, ri.bits_per_pixel, ri.black_level, ri.white_level };
+        int a = k0;
+        if (o.fix_stripes && !m.stripes_known) {
+            // the clip's correction from this frame as it is after chroma smoothing (stripes_compute_correction), then applied to it
+            uint8_t *src = F + a * dstride;
+            if (cs) {
+                rc = launch_frame(c->dev, g, false, src, img, O + a * dstride, img, 1, cs, nullptr, false, nullptr, s);
+                if (rc) return rc;
+                src = O + a * dstride;
+            }
+            Clip cl;
+            cl.g = g;
+            cl.pan_x = fh[a].vidf_hdr.panPosX;
+            cl.pan_y = fh[a].vidf_hdr.panPosY;
+            cl.device = c->dev->id;
+            rc = cl.stripes_compute(src, ri.frame_size, o.rand_mode ? 1 : 0, s);
+            if (rc) return rc;                                     // a library failure: the handle has no correction yet, the call fails
+            memcpy(m.coef, cl.coef, sizeof m.coef);
+            m.stripes_needed = cl.needed;
+            m.stripes_known = true;
+            if (m.stripes_needed && w % 8 == 0) {
+                rc = launch_stripes_apply(src, img, (size_t)w * h, w, g.black, g.white, m.coef, 1, s);
+                if (rc) return rc;
+            }
+            final_at[a] = src;
+            a++;
+        }
+        const bool stripes = o.fix_stripes && m.stripes_needed && w % 8 == 0;
+        for (int k = a; k < k1; k++) final_at[k] = (cs || stripes) ? O + k * dstride : F + k * dstride;
+        if (a < k1 && (cs || stripes)) {
+            rc = launch_frame(c->dev, g, false, F + a * dstride, dstride, O + a * dstride, dstride, k1 - a, cs, nullptr, stripes, m.coef, s);
+            if (rc) return rc;
+        }
+    }
+    for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], img, hipMemcpyDeviceToHost, s));
+    MLV_HIP(hipStreamSynchronize(s));
+    return MLVFS_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void *mlvfs_amd_mount_open(const void *reader, const mlvfs_amd_mount_opts_t *opts, const char *mlv_basename)
+{
+    if (!reader || !opts) { set_error("mount: null argument"); return nullptr; }
+    const mlvfs_amd_mount_opts_t &o = *opts;
+    if (o.chroma_smooth < 0 || o.fix_bad_pixels < 0 || o.fix_bad_pixels > 2 || o.dual_iso < 0 || o.dual_iso > 2 ||
+        o.hdr_interpolation_method < 0 || o.hdr_interpolation_method > 1 || o.deflicker < 0 || o.rand_mode < 0 || o.rand_mode > 1 ||
+        !(o.fps >= 0.0)) {
+        set_error("mount: option out of range");
+        return nullptr;
+    }
+    Mount *m = new Mount;
+    m->reader = reader;
+    m->o = o;
+    const char *b = mlv_basename ? mlv_basename : "";
+    m->basename.assign(b, b + strlen(b) + 1);
+    return m;
+}
+
+void mlvfs_amd_mount_close(void *mount) { delete (Mount *)mount; }
+
+int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results)
+{
+    if (!mount || !h_out) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    if (count < 0) { set_error("mount: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    if (count == 0) return MLVFS_AMD_OK;
+    const int frames = mlvfs_amd_mlv_frame_count(m.reader);
+    if (first < 0 || (long long)first + count > frames) { set_error("mount: frames %d..%d outside the clip (%d frames)", first, first + count - 1, frames); return MLVFS_AMD_ERR_ARG; }
+    std::vector<frame_headers> fh(count);
+    for (int k = 0; k < count; k++)
+        if (!mlvfs_amd_mlv_frame_headers(m.reader, first + k, &fh[k])) { set_error("mount: frame %d has no usable headers", first + k); return MLVFS_AMD_ERR_ARG; }
+    const int w = fh[0].rawi_hdr.xRes, h = fh[0].rawi_hdr.yRes, bpp = fh[0].rawi_hdr.raw_info.bits_per_pixel;
+    if (w <= 0 || h <= 0 || bpp < 1 || bpp > 16) { set_error("mount: unsupported frame %dx%d at %d bits", w, h, bpp); return MLVFS_AMD_ERR_ARG; }
+    for (int k = 1; k < count; k++)
+        if (fh[k].rawi_hdr.xRes != w || fh[k].rawi_hdr.yRes != h || fh[k].rawi_hdr.raw_info.bits_per_pixel != bpp) {
+            set_error("mount: frames of more than one geometry in one call (frame %d)", first + k);
+            return MLVFS_AMD_ERR_ARG;
+        }
+    const size_t size = dng_get_size(&fh[0]);
+    if (out_stride < size) { set_error("mount: out_stride %zu smaller than a .dng file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
+    if (batch_frames <= 0) batch_frames = 8;
+    batch_frames = std::min(batch_frames, count);
+    LibcRandGuard rand_guard;                      // HIP code runs: the caller's rand() stream stays out of its reach (rand_mode 0 draws from it)
+    std::lock_guard<std::mutex> lk(m.mu);
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    const size_t img = (size_t)w * h * 2, dstride = up256(img);
+    const size_t pn = o_pn_bytes(m.o, w, h, batch_frames);
+    size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
+    scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
+    int rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
+    for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
+        int n = std::min(batch_frames, count - f0);
+        if (m.o.dual_iso == 2 && m.o.fix_bad_pixels) {
+            std::shared_ptr<Clip> known;
+            if (!cached_bad_clip(&fh[f0], c, m.o.fix_bad_pixels == 2, &known)) n = 1;     // until the map exists: strictly in serve order
+        }
+        rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream);
+        if (rc == MLVFS_AMD_OK)
+            rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr);
+        f0 += n;
+    }
+    if (rc != MLVFS_AMD_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+}  // extern "C"

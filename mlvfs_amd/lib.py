@@ -17,11 +17,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(HERE, "libmlvfs_amd.so")
 
 OK = 0
+ERR_HIP, ERR_ARG, ERR_LUT, ERR_NOMEM = -1, -2, -3, -4
 
 
 class Geom(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bpp", C.c_int32), ("black", C.c_int32),
                 ("white", C.c_int32), ("pan_x", C.c_int32), ("pan_y", C.c_int32)]
+
+
+class MountOpts(C.Structure):
+    """mlvfs_amd_mount_opts_t (include/mlvfs_amd.h)"""
+    _fields_ = [("chroma_smooth", C.c_int32), ("fix_bad_pixels", C.c_int32), ("fix_stripes", C.c_int32), ("dual_iso", C.c_int32),
+                ("hdr_interpolation_method", C.c_int32), ("hdr_no_fullres", C.c_int32), ("hdr_no_alias_map", C.c_int32),
+                ("deflicker", C.c_int32), ("fix_pattern_noise", C.c_int32), ("rand_mode", C.c_int32), ("fps", C.c_double)]
 
 
 # every symbol include/mlvfs_amd.h declares (tests/test_cabi.py checks the export table against the header)
@@ -48,6 +56,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_mlv_xref", "mlvfs_amd_mlv_frame_headers", "mlvfs_amd_mlv_read_frames", "mlvfs_amd_mlv_process", "mlvfs_amd_mlv_process_dualiso",
     "mlvfs_amd_lj92_info", "mlvfs_amd_lj92_decode_dev", "mlvfs_amd_lj92_decode_untiled", "mlvfs_amd_lj92_encode_table", "mlvfs_amd_test_rand_layout", "mlvfs_amd_test_device_order", "mlvfs_amd_test_stream_plan", "mlvfs_amd_lzma_uncompress",
     "mlvfs_amd_gif_size", "mlvfs_amd_gif_render", "mlvfs_amd_mlv_gif_data", "mlvfs_amd_process_unpacked_dev", "mlvfs_amd_deflicker_dev",
+    "mlvfs_amd_fix_pattern_noise_dev", "mlvfs_amd_test_pn_scratch_cap", "mlvfs_amd_deflicker_batch_dev", "mlvfs_amd_hdr_preview_batch_dev",
+    "mlvfs_amd_mount_open", "mlvfs_amd_mount_dng", "mlvfs_amd_mount_close",
 ]
 
 
@@ -196,6 +206,13 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_mlv_read_frames", i, [vp, i, i, vp, sz, i])
     sig("mlvfs_amd_mlv_process", i, [vp, vp, i, i, vp, sz, i, i, i, i, i])
     sig("mlvfs_amd_mlv_process_dualiso", i, [vp, i, i, vp, sz, i, i, i, i, i, i, vp])
+    sig("mlvfs_amd_fix_pattern_noise_dev", i, [gp, vp, sz, i, vp])
+    sig("mlvfs_amd_test_pn_scratch_cap", sz, [sz])
+    sig("mlvfs_amd_deflicker_batch_dev", i, [gp, vp, sz, i, sz, i, vp, vp])
+    sig("mlvfs_amd_hdr_preview_batch_dev", i, [gp, vp, sz, i, sz, vp, vp])
+    sig("mlvfs_amd_mount_open", vp, [vp, C.POINTER(MountOpts), C.c_char_p])
+    sig("mlvfs_amd_mount_dng", i, [vp, i, i, vp, sz, i, i, vp])
+    sig("mlvfs_amd_mount_close", None, [vp])
     _lib = L
     return L
 

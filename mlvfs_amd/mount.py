@@ -1,0 +1,72 @@
+"""A clip served as MLVFS serves it, batch by batch (mlvfs_amd_mount_*, csrc/mount.cpp).
+
+    with mlvfile.MlvReader(path) as r, Mount(r, MlvfsOptions(chroma_smooth=5, fix_pattern_noise=1), deflicker=3000,
+                                              basename="/M07-1234.MLV") as m:
+        files = m.dng(0, 16, batch=8)       # (16, dng_size) uint8: 65536 header bytes + pixels per frame
+
+Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import lib
+from .pipeline import MlvfsOptions
+
+
+def mount_opts(opt: MlvfsOptions, deflicker: int = 0, fps: float = 0.0, rand_mode: int = 1) -> lib.MountOpts:
+    return lib.MountOpts(chroma_smooth=opt.chroma_smooth, fix_bad_pixels=opt.fix_bad_pixels, fix_stripes=opt.fix_stripes,
+                         dual_iso=opt.dual_iso, hdr_interpolation_method=opt.hdr_interpolation_method,
+                         hdr_no_fullres=opt.hdr_no_fullres, hdr_no_alias_map=opt.hdr_no_alias_map, deflicker=deflicker,
+                         fix_pattern_noise=opt.fix_pattern_noise, rand_mode=rand_mode, fps=fps)
+
+
+class Mount:
+    """reader: an open mlvfile.MlvReader (or a raw mlvfs_amd_mlv_open handle); it must stay open while the Mount lives."""
+
+    def __init__(self, reader, opt: MlvfsOptions, deflicker: int = 0, fps: float = 0.0, basename: str = "", rand_mode: int = 1):
+        self.L = lib.load()
+        self._reader = reader
+        handle = getattr(reader, "h", reader)
+        self.opts = mount_opts(opt, deflicker, fps, rand_mode)
+        self.h = self.L.mlvfs_amd_mount_open(handle, C.byref(self.opts), basename.encode())
+        if not self.h:
+            raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
+        self.frame_count = self.L.mlvfs_amd_mlv_frame_count(handle)
+
+    def dng_size(self, index: int = 0) -> int:
+        from . import abi
+        fh = abi.FrameHeaders()
+        if not self.L.mlvfs_amd_mlv_frame_headers(getattr(self._reader, "h", self._reader), index, C.byref(fh)):
+            raise lib.MlvfsAmdError(f"frame {index} has no usable headers")
+        return int(self.L.dng_get_size(C.byref(fh)))
+
+    def dng(self, first: int, count: int, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None) -> np.ndarray:
+        """Frames first .. first + count - 1 as .dng files: a (count, dng_size) uint8 array."""
+        out = np.zeros((count, self.dng_size(first) if count else 0), np.uint8)
+        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
+                                        and results.size >= count):
+            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
+        res = np.zeros(max(count, 1), np.int32) if results is None else results
+        lib.check(self.L.mlvfs_amd_mount_dng(self.h, first, count, lib.ptr(out), out.shape[1], batch, io_threads, lib.ptr(res)),
+                  "mount_dng")
+        return out
+
+    def close(self) -> None:
+        if self.h:
+            self.L.mlvfs_amd_mount_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
