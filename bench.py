@@ -11,18 +11,25 @@ Metric (BASELINE.json): Mpix/s for 3584x1320 14-bit unpack + cs5x5 + stripes
   roofline  = dominant kernel k_frame<5,packed,patch,stripes>: algorithmic bytes per launch
               (3.75 B/px x pixels per launch) / mean launch duration measured with HIP
               events on the launching stream inside the timed region; peak 8 TB/s
+  --dump-outputs DIR  after the timed steps, rank 0 writes a seeded sample of the frames its last
+              step computed to DIR/frames.npy (float32), so that two builds can be compared output
+              for output: the inputs are seeded, identical from run to run for the same arguments.
+
+A plain run does only that: set-up, preheat, warm-up, the timed steps, the dump, the result line.
+Everything below is measured or checked with --full alone (--no-extras and --no-cpu-baseline drop parts of it):
+  first_frame_next_clip_ms = the clip's first-frame analysis again, on a second clip object
+  value_at_100_frames_per_step = the hot path at 100 frames per launch (N = 1; an extra)
+  strong_scaling = N > 1: one clip of the N = 1 size split over the ranks
   parity    = after the timed region frames 0 and 1 of rank 0's output are hashed and compared
               with the hashes of the REFERENCE's output for the same seeded frames
-              (tests/golden/golden.json); a mismatch fails the run
+              (tests/golden/golden.json), later frames of the stream with the first occurrence
+              of their content; a mismatch fails the run
   cpu_baseline = the reference's own code (oracle/_ref, kind "reference") or the C
               restatement (kind "port") on the host cores, bounded sample, rank 0 @ N=1:
               one thread, and the best of a sweep of thread counts (one frame per thread)
   extra     = same process, outside the timed headline, rank 0 @ N=1 only: configs[1] (cs2x2),
               other footage kinds through the same kernel, configs[3] (full dual-ISO), and the
               PCIe-inclusive rates (batch API, drop-in symbols).  Never part of `value`.
-  --dump-outputs DIR  after the timed steps, rank 0 writes a seeded sample of the frames its last
-              step computed to DIR/frames.npy (float32), so that two builds can be compared output
-              for output: the inputs are seeded, identical from run to run for the same arguments.
 
 Multi-GPU: one rank per GPU.  `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the
 environment) starts its own ranks: the parent -- before it imports torch or touches HIP --
@@ -62,6 +69,8 @@ def spawn_ranks(args) -> int:
            f"--nproc-per-node={args.gpus}", os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--preheat-ms", str(args.preheat_ms),
            "--frames-per-step", str(args.frames_per_step), "--cs", str(args.cs)]
+    if args.full:
+        cmd.append("--full")
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.no_extras:
@@ -539,8 +548,11 @@ def main():
     ap.add_argument("--preheat-ms", type=float, default=200.0, help="untimed run of the hot path before the warm-up steps (clock settling)")
     ap.add_argument("--frames-per-step", type=int, default=400,
                     help="frames per launch of the fused kernel (one step); 400 = 3.3 GB of packed stream in, 3.8 GB of pixels out")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the second clip's first frame, parity against the reference's hashes, "
+                         "strong scaling, extras and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extras")
     ap.add_argument("--cs", type=int, default=5)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write a seeded sample of the last step's output frames to DIR/frames.npy")
@@ -677,10 +689,12 @@ def main():
     ff, first_frame_ms, needed, coeffs = first_frame(s)
     # the same on a SECOND clip object: what every further clip of a mounted directory costs, without what the process pays once
     # (code objects of the analysis kernels, the black level's output table, the thread's scratch buffers)
-    s2 = ClipStream(W, H, BPP, synth.BLACK, synth.WHITE, device=local)
-    ff2, first_frame_next_clip_ms, needed2, coeffs2 = first_frame(s2)
-    assert int(needed2) == int(needed) and [int(c) for c in coeffs2] == [int(c) for c in coeffs]
-    s2.close()
+    ff2, first_frame_next_clip_ms = None, None
+    if args.full:
+        s2 = ClipStream(W, H, BPP, synth.BLACK, synth.WHITE, device=local)
+        ff2, first_frame_next_clip_ms, needed2, coeffs2 = first_frame(s2)
+        assert int(needed2) == int(needed) and [int(c) for c in coeffs2] == [int(c) for c in coeffs]
+        s2.close()
 
     def step(b):
         b %= slots
@@ -729,7 +743,7 @@ def main():
     # ---- the same hot path at 100 frames per launch, the default of rounds 1-3 (round-to-round deltas must not mix kernel
     # changes with the change of the launch size): a few launches, wall clock, beside the headline -- never `value`
     at100 = None
-    if F > 100 and not grouped and not args.no_extras:       # (an extra: --no-extras keeps a profiled run to launches of one size)
+    if F > 100 and not grouped and args.full and not args.no_extras:   # (an extra: --no-extras keeps a profiled run to launches of one size)
         n100 = 16
         for i in range(4):
             s.process(packed[(i % 4) * 100:(i % 4 + 1) * 100], out[(i % 4) * 100:(i % 4 + 1) * 100], cs=args.cs, fix_pixels=True, stripes=True)
@@ -744,7 +758,7 @@ def main():
     # ---- strong scaling, reported beside the weak headline (never `value`): ONE clip of K*F frames -- the N = 1 workload -- split
     # into contiguous frame ranges (mlvfs_amd.dist.frame_range), no data-path collective; time = slowest rank between two barriers
     strong = None
-    if grouped:
+    if grouped and args.full:
         a, b = mdist.frame_range(K * F, rank, world)
         def strong_pass():
             for lo in range(a, b, F):
@@ -764,36 +778,38 @@ def main():
                   "ms": round(float(ts.item()) * 1e3, 3), "fps": round(K * F / float(ts.item()), 1),
                   "note": "one clip of the N = 1 size split by frame ranges; launches of <= frames_per_step frames; beside the weak headline"}
 
-    # ---- the timed output is checked: frames 0 and 1 of the clip against the REFERENCE's hashes --------------------
-    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "golden.json")))["full_size"]
-    parity = None
-    if rank == 0 and args.cs == 5 and K * F >= 2:
-        got = [synth.fnv1a(to_numpy_u16(out[k])) for k in range(2)]
-        want = [golden["B_cs5_badpix_stripes_frame0"], golden["B_cs5_badpix_stripes_frame1"]]
-        co_ok = [int(c) for c in coeffs] == golden["B_cs5_badpix_stripes_coeffs"] and int(needed) == golden["B_cs5_badpix_stripes_needed"]
-        map_ok = int(len(s.get_pixel_map())) == golden["B_cs5_badpix_stripes_badpix_count"]
-        parity = {"checked": "out[0], out[1] after the timed region vs tests/golden/golden.json B_cs5_badpix_stripes_frame0/1 "
-                             "(hashes of the reference's output), stripe coefficients, pixel-map size",
-                  "hashes": got, "reference": want, "ok": bool(got == want and co_ok and map_ok)}
-    # ... and the rest of the timed output against those: the resident stream repeats its `distinct` synthetic frames, so frame i of
-    # every launch must come out like frame i % distinct -- the last frames of a launch, of the last step, a seeded sample in between
-    # (a launch walks its tile list across 400 frames: the first two alone would not show a fault further down the list)
-    rep_ok, rep_n = True, 0
-    if slots * F > distinct:
-        gsel = torch.Generator().manual_seed(1 + rank)
-        sample = {slots * F - 1, F - 1, min(F, slots * F - 1), min(2 * F + 17, slots * F - 1)}
-        sample |= set(torch.randint(distinct, slots * F, (28,), generator=gsel).tolist())
-        for i in sorted(sample):
-            if i >= distinct:
-                rep_ok = rep_ok and bool(torch.equal(out[i], out[i % distinct]))
-                rep_n += 1
-    if parity is not None:
-        parity["later_frames"] = {"checked": rep_n, "equal_to_their_first_occurrence": rep_ok}
-        parity["checked"] += "; %d later frames of the resident stream against the first occurrence of their content" % rep_n
-        parity["ok"] = bool(parity["ok"] and rep_ok)
-    ok_flag = torch.tensor([1 if ((parity is None or parity["ok"]) and rep_ok) else 0], dtype=torch.int32, device=dev)
-    if grouped:
-        dist.all_reduce(ok_flag, op=dist.ReduceOp.MIN)
+    # ---- with --full the timed output is checked: frames 0 and 1 of the clip against the REFERENCE's hashes ------------
+    parity, all_ok = None, True
+    if args.full:
+        golden = json.load(open(os.path.join(ROOT, "tests", "golden", "golden.json")))["full_size"]
+        if rank == 0 and args.cs == 5 and K * F >= 2:
+            got = [synth.fnv1a(to_numpy_u16(out[k])) for k in range(2)]
+            want = [golden["B_cs5_badpix_stripes_frame0"], golden["B_cs5_badpix_stripes_frame1"]]
+            co_ok = [int(c) for c in coeffs] == golden["B_cs5_badpix_stripes_coeffs"] and int(needed) == golden["B_cs5_badpix_stripes_needed"]
+            map_ok = int(len(s.get_pixel_map())) == golden["B_cs5_badpix_stripes_badpix_count"]
+            parity = {"checked": "out[0], out[1] after the timed region vs tests/golden/golden.json B_cs5_badpix_stripes_frame0/1 "
+                                 "(hashes of the reference's output), stripe coefficients, pixel-map size",
+                      "hashes": got, "reference": want, "ok": bool(got == want and co_ok and map_ok)}
+        # ... and the rest of the timed output against those: the resident stream repeats its `distinct` synthetic frames, so frame i of
+        # every launch must come out like frame i % distinct -- the last frames of a launch, of the last step, a seeded sample in between
+        # (a launch walks its tile list across 400 frames: the first two alone would not show a fault further down the list)
+        rep_ok, rep_n = True, 0
+        if slots * F > distinct:
+            gsel = torch.Generator().manual_seed(1 + rank)
+            sample = {slots * F - 1, F - 1, min(F, slots * F - 1), min(2 * F + 17, slots * F - 1)}
+            sample |= set(torch.randint(distinct, slots * F, (28,), generator=gsel).tolist())
+            for i in sorted(sample):
+                if i >= distinct:
+                    rep_ok = rep_ok and bool(torch.equal(out[i], out[i % distinct]))
+                    rep_n += 1
+        if parity is not None:
+            parity["later_frames"] = {"checked": rep_n, "equal_to_their_first_occurrence": rep_ok}
+            parity["checked"] += "; %d later frames of the resident stream against the first occurrence of their content" % rep_n
+            parity["ok"] = bool(parity["ok"] and rep_ok)
+        ok_flag = torch.tensor([1 if ((parity is None or parity["ok"]) and rep_ok) else 0], dtype=torch.int32, device=dev)
+        if grouped:
+            dist.all_reduce(ok_flag, op=dist.ReduceOp.MIN)
+        all_ok = bool(int(ok_flag.item()))
 
     npx = W * H
     total_px = world * K * F * npx
@@ -840,7 +856,7 @@ def main():
         "value": round(total_px / dt / 1e6, 1),
         "unit": "Mpix/s",
         "fps": round(world * K * F / dt, 1),
-        "n_gpus": world, "steps": K, "warmup": Wm, "preheat_ms": args.preheat_ms,
+        "n_gpus": world, "steps": K, "warmup": Wm, "preheat_ms": args.preheat_ms, "full": bool(args.full),
         "ms_per_step": round(dt / K * 1e3, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u16/int32", "data": "synthetic",
@@ -848,7 +864,7 @@ def main():
                    "frames_per_step": F, "value_at_100_frames_per_step": at100, "frames_per_rank": K * F, "resident_frames_per_rank": slots * F, "chroma_smooth": args.cs,
                    "bad_pixels_in_map": int(len(s.get_pixel_map())), "stripe_coeffs": [int(c) for c in coeffs],
                    "parallelism": f"frames x{world}", "first_frame_ms": round(first_frame_ms, 2), "first_frame_split_ms": ff,
-                   "first_frame_next_clip_ms": round(first_frame_next_clip_ms, 2), "first_frame_next_clip_split_ms": ff2,
+                   "first_frame_next_clip_ms": None if first_frame_next_clip_ms is None else round(first_frame_next_clip_ms, 2), "first_frame_next_clip_split_ms": ff2,
                    "ranks_seen": ranks_info["ranks_seen"], "devices_seen": ranks_info["devices_seen"], "device_ids": ranks_info["device_ids"],
                    "ranks_sharing_a_device": ranks_info["shared"], "per_rank_kernel_fps": per_rank_fps, "strong_scaling": strong,
                    "collective": None if not grouped else ("gloo (rehearsal)" if rehearsal else "RCCL all_gather + all_reduce int32[8][65536], once per clip")},
@@ -869,11 +885,10 @@ def main():
         result["valu"] = valu
     if dumped:
         result["dump_outputs"] = dumped
-    all_ok = bool(int(ok_flag.item()))
     # the headline's buffers are not needed any more: the extras allocate their own
     del packed, out, base
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_extras:
             extra = {}
             for name, fn in (("configs1_cs2x2", lambda: extra_cs2x2(golden, synth.fnv1a)), ("footage", extra_footage),

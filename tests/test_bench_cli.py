@@ -41,7 +41,7 @@ def test_bench_gpus2_starts_two_ranks_rehearsal(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MLVFS_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames-per-step", "4",
-                        "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -80,7 +80,7 @@ def test_bench_gpus4_rehearsal_weak_and_strong(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MLVFS_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--steps", "2", "--warmup", "1", "--frames-per-step", "6", "--preheat-ms", "20",
-                        "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     assert res["n_gpus"] == 4 and res["config"]["parallelism"] == "frames x4" and res["scaling"] == "weak"
@@ -164,7 +164,7 @@ def test_bench_single_rank_in_an_rccl_group(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MLVFS_BENCH_GROUP1="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames-per-step", "6", "--preheat-ms", "20",
-                        "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     assert res["n_gpus"] == 1 and res["parity"]["ok"] is True
@@ -182,7 +182,7 @@ def test_bench_dump_outputs_are_the_same_for_the_same_content(gpu, tmp_path):
     for steps in (2, 3):
         d = tmp_path / f"steps{steps}"
         r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--frames-per-step", "64",
-                            "--preheat-ms", "20", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(d)],
+                            "--preheat-ms", "20", "--full", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(d)],
                            env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         res = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
@@ -193,3 +193,31 @@ def test_bench_dump_outputs_are_the_same_for_the_same_content(gpu, tmp_path):
         dumps.append((res["dump_outputs"]["synthetic_frames"], frames))
     assert dumps[0][0] == dumps[1][0] and np.array_equal(dumps[0][1], dumps[1][1])
     assert len({f.tobytes() for f in dumps[0][1]}) == 3
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_what_full_dumps(gpu, tmp_path):
+    """A plain run (no --full) measures and writes what the headline needs: the result line's headline fields, the kernel timer's
+    roofline and the dump -- no second clip, no parity check, no extras, no CPU baseline, although neither --no-extras nor
+    --no-cpu-baseline is given.  Its dump equals that of a --full run of the same arguments, whose parity check vouches for it."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MLVFS_BENCH_REHEARSAL", "MLVFS_BENCH_GROUP1")}
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames-per-step", "64", "--preheat-ms", "20"]
+    r = subprocess.run([sys.executable, BENCH, *args, "--dump-outputs", str(tmp_path / "plain")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    plain = json.loads(lines[0])
+    assert plain["full"] is False and plain["steps"] == 2 and plain["warmup"] == 1 and plain["unit"] == "Mpix/s"
+    assert plain["higher_is_better"] is True and plain["dtype"] == "u16/int32" and plain["metric"].startswith("Mpix/s")
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["frac"] > 0
+    assert plain["parity"] is None and "extra" not in plain and "cpu_baseline" not in plain
+    assert plain["config"]["first_frame_next_clip_ms"] is None and plain["config"]["first_frame_ms"] > 0
+
+    r = subprocess.run([sys.executable, BENCH, *args, "--full", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path / "full")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    full = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert full["full"] is True and full["parity"]["ok"] is True and full["config"]["first_frame_next_clip_ms"] > 0
+    assert plain["dump_outputs"]["synthetic_frames"] == full["dump_outputs"]["synthetic_frames"]
+    assert np.array_equal(np.load(tmp_path / "plain" / "frames.npy"), np.load(tmp_path / "full" / "frames.npy"))
