@@ -411,6 +411,13 @@ int mlvfs_amd_test_device_order(const char *const *bus_ids, int n, int workers, 
  * into tasks -- columns of 62 items (8 pixels each), segments of seg_rows cell rows, `fold` segments of a narrow last column side by
  * side in one wave (a last column of <= 14 items: 4, <= 30 items: 2), tasks per frame.                                              */
 int mlvfs_amd_test_stream_plan(int width, int height, int seg_rows, int *cols, int *segs, int *fold, int *tasks_per_frame);
+/* Test hook, host only: the fused pass's plan for one launch (csrc/frame_plan.cpp), the switches MLVFS_AMD_KF_P / _KF_P5 / _KF_S read
+ * from the environment as a launch reads them.  in[13] = {width, height, bits per pixel, black, chroma smoothing method, packed, input
+ * layout (0 any, 1 / 2 rows of whole 16- / 8-pixel groups, 3 12-bit, 4 10-bit), pixel map, stripes (0 none, 1 packed form, 2 other),
+ * frames, CUs, held back, some tiles listed}.  out[15] = {first kernel (0 none, 1 k_frame_p, 2 k_frame_p5, 3 k_frame_s), list-mode
+ * k_frame follows, k_frame's grid, groups, run, singles, first kernel's grid, rows per task, columns, segments, fold, tasks, k_frame_s
+ * steps, work-list entries, status word watched (-1 none)}.  0, or MLVFS_AMD_ERR_ARG for a launch the fused pass refuses.          */
+int mlvfs_amd_test_frame_plan(const int *in, long long *out);
 
 /* -- batched stages of process_frame that existed only per frame ------------- */
 /* Pattern noise (patternnoise.c:357-380, debug_flags 0) on `nframes` device frames of one geometry (even width and height), `stride`

@@ -30,6 +30,7 @@
 //   * persistent workgroups; the four residents of a CU draw runs of tiles from that CU's contiguous range of the tile list
 //     (the ranges of an XCD's CUs adjacent, so halo re-reads hit its own L2), the last tiles of a range one by one
 // No MFMA: this is a stencil / gather / selection path.
+#include "frame_plan.h"
 #include "k_frame_dev.h"
 
 namespace mlv {
@@ -193,10 +194,6 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
     { const Src s0 = src_of(cold_args()); if (vec) issue_tile(&s0, cur); }
     __syncthreads();                           // T16 copy complete
 
-#ifdef KF_DIAG_TIMES
-    const uint64_t rt0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long diag_n[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-#endif
     int par = 0;                               // tile parity: which of the two dark_items counters this tile uses
 #ifdef KF_W_LOW
     int lpar = 0, low_prev = 3;                // which of the two low-pixel records; the record of the tile before (bit 0: low, bit 1: dim)
@@ -462,12 +459,6 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
                 calm = nfb == 0 ? calm + 1 : 0;
                 robust = nfb > FB_ROBUST || (robust && calm < 4);
             }
-#ifdef KF_DIAG_TIMES
-            // tiles, tiles that skipped the packed networks, strips settled densely, tiles that continued the one above (summed per
-            // workgroup, added once at its end: an atomic per tile on one address serialised the whole launch)
-            diag_n[0]++; diag_n[1] += skip_packed ? 1 : 0; diag_n[2] += nfb; diag_n[3] += cont ? 1 : 0;
-            diag_n[4] += nfb > 0 ? 1 : 0; diag_n[5] += robust ? 1 : 0; diag_n[6] += nfb > 64 ? 1 : 0; diag_n[7] += (nfb > 0 && nfb <= 4) ? 1 : 0;
-#endif
             if (nfb > 0) {
                 if ((tid & ~63) < nfb) {                               // this wave has entries
                     const int e = sm.fb_queue[min(tid, nfb - 1)];
@@ -502,66 +493,69 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
         if (atomicAdd(&tickets[2 * groups], 1) == (int)gridDim.x - 1)
             for (int i = 0; i <= 2 * groups; i++) tickets[i] = 0;   // last workgroup out: ready for the next launch on this stream
     }
-#ifdef KF_DIAG_TIMES
-    if (threadIdx.x == 0 && a.times) {
-        a.times[2 * blockIdx.x] = rt0; a.times[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-        for (int i = 0; i < 8; i++) atomicAdd(&a.times[4096 + i], diag_n[i]);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------- host launcher
-// zeroed counters per stream (launches on one stream run one after the other and leave the counters zeroed)
-constexpr int MAX_GROUPS = 1024;
-#ifndef KF_P_BUSY_PERCENT
-#define KF_P_BUSY_PERCENT 30     // of a launch's tiles listed for k_frame: the next launches skip the packed-once kernel
-#endif
-#ifndef KF_P_HOLD_MIN
-#define KF_P_HOLD_MIN 8
-#endif
-#ifndef KF_P_HOLD_MAX
-#define KF_P_HOLD_MAX 64
-#endif
-#ifndef KF_RUN_MAX
-#define KF_RUN_MAX 22
-#endif
+// What the library keeps per (device, stream): the kernels' zeroed counters (launches on one stream run one after the other and leave
+// them zeroed), the work list between k_frame_p / k_frame_p5 and the list-mode k_frame, and the back-off of the two status words.
+constexpr int KF_P_BUSY_PERCENT = 30;      // of a launch's tiles listed for k_frame: the next launches skip the packed-once kernel
+constexpr int KF_P5_CALM_PERCENT = 5;      // of the tiles listed: "some listed", k_frame_p rather than k_frame_p5 (StreamVerdict)
+constexpr int KF_S_BUSY_PERCENT = 10;      // of k_frame_s's steps dark: the next launches go to k_frame
+constexpr int KF_P_HOLD_MIN = 8, KF_P_HOLD_MAX = 64;
 namespace {
+// Which kernels a launch on a stream uses (round 5).  The first kernel of a launch leaves a running count of the work it did badly in a
+// page-locked status word when it ends -- word 0: the tiles k_frame_p / k_frame_p5 listed for k_frame (hard colour edges, deep
+// shadows), word 1: k_frame_s's steps that took the loader's form for pixels at or below black (deep shadows, colour patches: k_frame,
+// which decides per item group and hides it behind its other workgroups, is faster there -- cs2x2, 3584x1320: low light 5.4 against
+// 6.7 us per frame, colour patches 6.0 against 8.4; the benchmark's frames 4.8 against 4.7).  The NEXT launches read the word without
+// waiting for anything: where a word's launches did more than their share badly, k_frame runs alone for `hold` launches, then one
+// launch probes again.
+struct Backoff {
+    int seen = 0;                // the word when it was last looked at
+    long long pending = 0;       // work of the launches since then (tiles, steps)
+    int wide_left = 0, hold = 0; // launches still to go to k_frame alone; how many after the next busy look
+    // what the launches that have ended since the last look reported, against the work of all launches that were under way (a launch
+    // that has not ended yet counts with its work and nothing reported: the verdict errs towards "calm"); false: nothing new
+    bool look(int word, long long *reported, long long *of)
+    {
+        if (word == seen) return false;
+        *reported = (long long)(unsigned)(word - seen); *of = pending;
+        seen = word; pending = 0;
+        return true;
+    }
+    void judge(bool busy) { hold = busy ? (hold ? std::min(2 * hold, KF_P_HOLD_MAX) : KF_P_HOLD_MIN) : 0; if (busy) wide_left = hold; }
+};
 struct StreamState {
     int *tickets = nullptr;      // group tickets of the range-mode launches, then the three work-list counters (FrameArgs::wl_ctl)
-    int2 *wl = nullptr;          // work list between k_frame_p and the list-mode k_frame: one entry per run of tiles
+    int2 *wl = nullptr;          // work list between k_frame_p / k_frame_p5 and the list-mode k_frame: one entry per run of tiles
     long long wl_cap = 0;
-    // Which kernels a launch on this stream uses (round 5).  The list-mode launch leaves the stream's count of listed tiles in a
-    // page-locked word when it ends; the NEXT launches read it without waiting for anything: footage the packed-once kernel lists
-    // most tiles of (hard colour edges, deep shadows) goes to k_frame alone for `hold` launches, then one launch probes again.
-    int *h_stat = nullptr;       // (host pointer, mapped)
+    int *h_stat = nullptr;       // the two status words (host pointer, mapped)
     int *d_stat = nullptr;
-    int stat_seen = 0;           // h_stat when it was last looked at
-    long long pending_tiles = 0; // tiles of the two-kernel launches whose list counts have not been seen yet
-    int wide_left = 0, hold = 0; // launches still to go to k_frame alone; how many after the next busy probe
-    bool some_listed = false;    // the last verdict found more than KF_P5_CALM_PERCENT of the tiles listed: the tile kernel k_frame_p, which
-                                 // skips the tiles behind an uncertain one unseen, does better there than the streaming k_frame_p5
-    // the same for the streaming cs2x2 kernel (k_frame_s.hip): its steps that took the loader's form for pixels at or below black,
-    // out of all steps (word 1 of h_stat; the cumulative count lives in tickets[S_STAT_AT])
-    int s_seen = 0;
-    long long s_pending = 0;
-    int s_wide_left = 0, s_hold = 0;
+    Backoff back[2];
+    bool some_listed = false;    // word 0's last look: StreamVerdict::some_listed
 };
 std::mutex g_ticket_mu;
 std::map<std::pair<int, hipStream_t>, StreamState> g_tickets;
-constexpr int TICKET_INTS = 2 * MAX_GROUPS + 1 + 4 + 2;
-#ifndef KF_P5_CALM_PERCENT
-#define KF_P5_CALM_PERCENT 5
-#endif
-constexpr int S_STAT_AT = 2 * MAX_GROUPS + 1 + 4;      // k_frame_s: cumulative dark steps
-#ifndef KF_S_BUSY_PERCENT
-#define KF_S_BUSY_PERCENT 10
-#endif
+constexpr int TICKET_INTS = 2 * FRAME_MAX_GROUPS + 1 + 4 + 2;
+constexpr int WL_CTL_AT = 2 * FRAME_MAX_GROUPS + 1;            // k_frame, k_frame_p, k_frame_p5: the work-list counters
+constexpr int S_STAT_AT = 2 * FRAME_MAX_GROUPS + 1 + 4;        // k_frame_s: cumulative dark steps
 }
-// wl_tiles > 0: the launch may use both kernels and then needs a work list that holds that many entries; *two says whether it does
-static int stream_state(hipStream_t stream, long long wl_tiles, int policy, StreamState *out, bool *two)
+// (without the word every launch starts with its first kernel)
+static void ensure_status_word(StreamState &st)
 {
+    if (st.h_stat) return;
+    if (hipHostMalloc((void **)&st.h_stat, 64, hipHostMallocMapped) == hipSuccess) {
+        st.h_stat[0] = 0; st.h_stat[1] = 0;
+        if (hipHostGetDevicePointer((void **)&st.d_stat, st.h_stat, 0) != hipSuccess) { (void)hipHostFree(st.h_stat); st.h_stat = nullptr; st.d_stat = nullptr; }
+    } else st.h_stat = nullptr;
+    (void)hipGetLastError();
+}
+// The plan of a launch on `stream` (frame_plan.h), and the stream's buffers for it (*out): the watched status word is looked at, the
+// plan made, then committed -- the hold counted down, or the launch's work added to what the word's next look weighs.
+static int plan_on_stream(hipStream_t stream, const FramePassInputs &in, FramePlan *pl, StreamState *out)
+{
+    const FrameSwitches sw = frame_switches();
     int dev = 0;
-    *two = false;
     if (hipGetDevice(&dev) != hipSuccess) return MLVFS_AMD_ERR_HIP;
     std::lock_guard<std::mutex> lk(g_ticket_mu);
     StreamState &st = g_tickets[{ dev, stream }];
@@ -577,87 +571,30 @@ static int stream_state(hipStream_t stream, long long wl_tiles, int policy, Stre
             return MLVFS_AMD_ERR_HIP;
         }
     }
-    if (wl_tiles > 0 && policy != 0) {
-        if (!st.h_stat) {                                 // (without the word every launch uses both kernels)
-            if (hipHostMalloc((void **)&st.h_stat, 64, hipHostMallocMapped) == hipSuccess) {
-                st.h_stat[0] = 0; st.h_stat[1] = 0;
-                if (hipHostGetDevicePointer((void **)&st.d_stat, st.h_stat, 0) != hipSuccess) { (void)hipHostFree(st.h_stat); st.h_stat = nullptr; st.d_stat = nullptr; }
-            } else st.h_stat = nullptr;
-            (void)hipGetLastError();
+    const FrameWatch wt = frame_pass_watch(in, sw);
+    if (wt.status) ensure_status_word(st);
+    StreamVerdict v;
+    if (wt.adaptive && st.h_stat) {
+        Backoff &b = st.back[wt.word];
+        long long reported = 0, of = 0;
+        if (b.look(__atomic_load_n(&st.h_stat[wt.word], __ATOMIC_RELAXED), &reported, &of)) {
+            b.judge(reported * 100 > of * (wt.word == 0 ? KF_P_BUSY_PERCENT : KF_S_BUSY_PERCENT));
+            if (wt.word == 0) st.some_listed = reported * 100 > of * KF_P5_CALM_PERCENT;
         }
-        bool use_p = true;
-        if (policy == 1 && st.h_stat) {
-            const int seen = __atomic_load_n(st.h_stat, __ATOMIC_RELAXED);
-            if (seen != st.stat_seen || st.pending_tiles > 0) {
-                // what the launches that have ended since listed, against the tiles of all launches that were under way (a
-                // launch that has not ended yet counts with its tiles and no listed ones: the verdict errs towards "calm")
-                const long long listed = (long long)(unsigned)(seen - st.stat_seen);
-                if (seen != st.stat_seen) {
-                    const bool busy = listed * 100 > st.pending_tiles * KF_P_BUSY_PERCENT;
-                    st.some_listed = listed * 100 > st.pending_tiles * KF_P5_CALM_PERCENT;
-                    if (busy) { st.hold = st.hold ? std::min(2 * st.hold, KF_P_HOLD_MAX) : KF_P_HOLD_MIN; st.wide_left = st.hold; }
-                    else st.hold = 0;
-                    st.stat_seen = seen;
-                    st.pending_tiles = 0;
-                }
-            }
-            if (st.wide_left > 0) { st.wide_left--; use_p = false; }
-        }
-        if (use_p) {
-            if (wl_tiles > st.wl_cap) {
-                // (hipFree waits for the device: no launch on this stream still reads the old list)
-                if (st.wl) (void)hipFree(st.wl);
-                st.wl = nullptr; st.wl_cap = 0;
-                const long long cap = std::max(wl_tiles, 4096ll);
-                if (hipMalloc(&st.wl, (size_t)cap * sizeof(int2)) != hipSuccess) { set_error("work list: allocation of %lld entries failed", cap); return MLVFS_AMD_ERR_HIP; }
-                st.wl_cap = cap;
-            }
-            st.pending_tiles += wl_tiles;
-            *two = true;
-        }
+        v.held = b.wide_left > 0;
     }
-    *out = st;
-    return MLVFS_AMD_OK;
-}
-// k_frame_s's launches: `steps` wave-steps are about to be launched; *use_s says whether the streaming kernel takes them.  Footage
-// with pixels at or below black in most rows (deep shadows, colour patches) runs the loader's slower form in whole waves there, and
-// k_frame -- which decides per item group and hides it behind its other workgroups -- is faster (cs2x2, 3584x1320: low light 5.4
-// against 6.7 us per frame, colour patches 6.0 against 8.4; the benchmark's frames 4.8 against 4.7): such streams go back to
-// k_frame for a while, like the packed-once kernel's (stream_state).
-static int stream_state_s(hipStream_t stream, long long steps, StreamState *out, bool *use_s)
-{
-    bool two = false;
-    int rc = stream_state(stream, 0, 0, out, &two);
-    if (rc) return rc;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(g_ticket_mu);
-    StreamState &st = g_tickets[{ dev, stream }];
-    *use_s = true;
-    const char *e = getenv("MLVFS_AMD_KF_S");
-    const int policy = e ? atoi(e) : 1;                      // 2: always (frame_s_takes)
-    if (policy == 1) {
-        if (!st.h_stat) {
-            if (hipHostMalloc((void **)&st.h_stat, 64, hipHostMallocMapped) == hipSuccess) {
-                st.h_stat[0] = 0; st.h_stat[1] = 0;
-                if (hipHostGetDevicePointer((void **)&st.d_stat, st.h_stat, 0) != hipSuccess) { (void)hipHostFree(st.h_stat); st.h_stat = nullptr; st.d_stat = nullptr; }
-            } else st.h_stat = nullptr;
-            (void)hipGetLastError();
-        }
-        if (st.h_stat) {
-            const int seen = __atomic_load_n(&st.h_stat[1], __ATOMIC_RELAXED);
-            if (seen != st.s_seen) {
-                const long long dark = (long long)(unsigned)(seen - st.s_seen);
-                const bool busy = dark * 100 > st.s_pending * KF_S_BUSY_PERCENT;
-                if (busy) { st.s_hold = st.s_hold ? std::min(2 * st.s_hold, KF_P_HOLD_MAX) : KF_P_HOLD_MIN; st.s_wide_left = st.s_hold; }
-                else st.s_hold = 0;
-                st.s_seen = seen;
-                st.s_pending = 0;
-            }
-            if (st.s_wide_left > 0) { st.s_wide_left--; *use_s = false; }
-        }
+    v.some_listed = st.some_listed;
+    if (const int rc = plan_frame_pass(in, sw, v, pl)) return rc;
+    if (wt.adaptive && v.held) st.back[wt.word].wide_left--;
+    if (pl->list_after && pl->wl_entries > st.wl_cap) {
+        // (hipFree waits for the device: no launch on this stream still reads the old list)
+        if (st.wl) (void)hipFree(st.wl);
+        st.wl = nullptr; st.wl_cap = 0;
+        if (hipMalloc(&st.wl, (size_t)pl->wl_entries * sizeof(int2)) != hipSuccess) { set_error("work list: allocation of %lld entries failed", pl->wl_entries); return MLVFS_AMD_ERR_HIP; }
+        st.wl_cap = pl->wl_entries;
     }
-    if (*use_s) st.s_pending += steps;
+    if (pl->first == FirstKernel::s) st.back[1].pending += pl->steps;
+    if (pl->list_after) st.back[0].pending += pl->tiles;
     *out = st;
     return MLVFS_AMD_OK;
 }
@@ -763,112 +700,9 @@ static int e2r_table(const Device *dev, int black, const uint2 **out, hipStream_
     return MLVFS_AMD_OK;
 }
 
-// The packed-once kernel (k_frame_p.hip) exists for the chroma-smoothing methods on the vector layouts; everything else is
-// k_frame's alone.  MLVFS_AMD_KF_P=0 sends every launch to k_frame as rounds 1-4 did (A/B).
-bool frame_p_exists(int method, int vec);
-void launch_frame_p_kernel(int method, bool packed, int vec, bool spread, int grid, hipStream_t stream, const FrameArgs &a, bool prefer_tiles);
-// k_frame_s.hip: cs2x2 as a streaming kernel without barriers (what it takes: frame_s_takes)
-bool frame_s_takes(int method, bool packed, int vec, int num_cu, const FrameArgs &a);
-void launch_frame_s_kernel(int method, bool spread, int vec, int num_cu, hipStream_t stream, const FrameArgs &a);
-long long frame_s_steps(const FrameArgs &a);
-
-template <int METHOD, bool PACKED, int VEC, bool SPREAD>
-static int launch_frame_t(const FrameArgs &a_in, int num_cu, hipStream_t stream)
-{
-    const long long total = (long long)a_in.tiles_x * a_in.tiles_y * a_in.nframes;
-    static const int env_wgs = [] { const char *e = getenv("MLVFS_AMD_KF_WGS_PER_CU"); return e ? atoi(e) : 0; }();      // (occupancy experiments)
-    int grid = (num_cu > 0 ? num_cu : 256) * (env_wgs > 0 ? env_wgs : 4);          // 4 workgroups per CU (39 KiB LDS, <= 128 VGPRs)
-    grid = (grid + 7) / 8 * 8;
-    if (grid > total) grid = (int)((total + 7) / 8 * 8);
-    if (frame_s_takes(METHOD, PACKED, VEC, num_cu, a_in)) {
-        FrameArgs as = a_in;
-        StreamState sst;
-        bool use_s = true;
-        const int rcs = stream_state_s(stream, frame_s_steps(a_in), &sst, &use_s);
-        if (rcs) return rcs;
-        if (use_s) {
-        as.tickets = sst.tickets;
-        as.wl_ctl = sst.tickets + S_STAT_AT;                  // (k_frame_s: [0] its cumulative count of dark steps)
-        as.wl_stat = sst.d_stat ? sst.d_stat + 1 : nullptr;
-        KernelTimer &tms = kernel_timer();
-        const bool timed_s = tms.on && tms.used + 2 <= (int)tms.ev.size();
-        if (timed_s) MLV_HIP(hipEventRecord(tms.ev[tms.used], stream));
-        launch_frame_s_kernel(METHOD, SPREAD, VEC, num_cu, stream, as);
-        if (timed_s) { MLV_HIP(hipEventRecord(tms.ev[tms.used + 1], stream)); tms.used += 2; }
-        MLV_HIP(hipGetLastError());
-        return MLVFS_AMD_OK;
-        }
-    }
-    auto kern = k_frame<METHOD, PACKED, VEC, SPREAD>;
-    // MLVFS_AMD_KF_P: 0 = k_frame alone (rounds 1-4), 1 = both kernels, k_frame alone while the footage is busy (default), 2 = always both
-    const char *e_p = getenv("MLVFS_AMD_KF_P");                 // (read at every launch: the tests switch it)
-    const int env_p = e_p ? atoi(e_p) : 1;
-    FrameArgs a = a_in;
-    StreamState st;
-    bool two = false;
-    int rc = stream_state(stream, frame_p_exists(METHOD, VEC) ? total : 0, env_p, &st, &two);
-    if (rc) return rc;
-    a.wl_stat = st.d_stat;
-    a.tickets = st.tickets;
-    a.wl = st.wl;
-    a.wl_ctl = st.tickets + 2 * MAX_GROUPS + 1;
-    a.list_mode = 0;
-    // Groups: workgroups that draw from one range of the tile list.  Until round 4 a group was one CU's four residents; the CUs
-    // of a chip do not run at one speed (their workgroups ended between 780 and 835 us of an 844-us launch: 5.5 % of the launch
-    // was its tail, -DKF_DIAG_TIMES), and drawing runs instead of single tiles made the atomics rare enough for larger groups:
-    // eight CUs (a quarter of an XCD: blocks b, b + groups, ... share b % 8, i.e. their XCD, as long as groups is a multiple of 8)
-    // share a range, 123.0 -> 128.4 k fps; 16 / 24 / 32 / 64 groups and runs of 11 / 22 / 44 tiles are within 0.5 % of each other,
-    // one group per XCD (8) loses the gain to its 1 408 single tiles (profiles/r04/ab_groups.log).  MLVFS_AMD_KF_GROUPS overrides.
-    const int per_cu = std::min(std::max(grid / 4, 1), MAX_GROUPS);
-    a.groups = per_cu >= 64 ? per_cu / 8 / 8 * 8 : per_cu;
-    static const int env_groups = [] { const char *e = getenv("MLVFS_AMD_KF_GROUPS"); return e ? atoi(e) : 0; }();
-    if (env_groups > 0 && env_groups <= per_cu) a.groups = env_groups;
-    // tiles per run and tiles that go out one by one at the end of a group's range (tools/kbench.py sweeps them: KB_RUN / KB_SINGLES)
-    static const int env_run = [] { const char *e = getenv("MLVFS_AMD_KF_RUN"); return e ? atoi(e) : 0; }();
-    static const int env_singles = [] { const char *e = getenv("MLVFS_AMD_KF_SINGLES"); return e ? atoi(e) : -1; }();
-    // default: at most half a column of the benchmark's geometry per run (same-box sweep with one CU per group: 4 / 8 / 11 / 22 / 44
-    // tiles per run -> 117.2 / 117.5 / 117.7 / 118.0-121.0 / 120.5 k fps), a sixteenth of the range for short launches
-    const int band = (int)(total / a.groups);
-    a.run = env_run > 0 ? env_run : std::min(std::max(band / 16, 1), KF_RUN_MAX);
-    a.singles = env_singles >= 0 ? env_singles : (a.run > 1 ? 8 * std::max(grid / a.groups, 1) : 0);      // eight per workgroup of the group
-#ifdef KF_DIAG_TIMES
-    static unsigned long long *d_times = nullptr;
-    if (!d_times) hipMalloc(&d_times, (2048 * 2 + 8) * sizeof(unsigned long long));
-    hipMemsetAsync(d_times + 4096, 0, 8 * sizeof(unsigned long long), stream);
-    const_cast<FrameArgs &>(a).times = d_times;
-#endif
-    KernelTimer &tm = kernel_timer();
-    const bool timed = tm.on && tm.used + 2 <= (int)tm.ev.size();
-    if (timed) MLV_HIP(hipEventRecord(tm.ev[tm.used], stream));
-    if (two) {
-        // k_frame_p does every tile whose packed medians are certain and lists the rest; k_frame in list mode does those again
-        // (nothing listed: its workgroups end at once).  Both inside the timer's bracket: the pair is the pass.
-        launch_frame_p_kernel(METHOD, PACKED, VEC, SPREAD, grid, stream, a, st.some_listed);
-        a.list_mode = 1;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, a);
-    } else
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, a);
-    if (timed) { MLV_HIP(hipEventRecord(tm.ev[tm.used + 1], stream)); tm.used += 2; }
-    MLV_HIP(hipGetLastError());
-    static const bool env_dbg = [] { const char *e = getenv("MLVFS_AMD_KF_P_DEBUG"); return e && atoi(e) != 0; }();
-    if (two && env_dbg) {                                // (A/B aid: how many tiles the packed-once kernel left to k_frame)
-        int listed = 0;
-        static int before = 0;
-        if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(&listed, a.wl_ctl + 3, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "k_frame_p<%d>: %lld tiles, %d listed for k_frame (%.2f %%)\n", METHOD, total, listed - before, 100.0 * (listed - before) / (double)total);
-            if (listed - before > 0 && listed - before < 64) {       // a few: which ones (the list's first entries as the last launch left them)
-                int2 e[8];
-                if (hipMemcpy(e, a.wl, sizeof(e), hipMemcpyDeviceToHost) == hipSuccess)
-                    for (int i = 0; i < 8; i++) {
-                        const int tpf = a.tiles_x * a.tiles_y, r = e[i].x % tpf;
-                        fprintf(stderr, "    entry %d: frame %d tile column %d row %d, %d tile(s)\n", i, e[i].x / tpf, r / a.tiles_y, r % a.tiles_y, e[i].y);
-                    }
-            }
-            before = listed;
-        }
-    }
-    return MLVFS_AMD_OK;
-}
+// the first kernels of a plan (k_frame_p.hip: k_frame_p or k_frame_p5; k_frame_s.hip)
+void launch_frame_p(const FramePlan &pl, int method, bool packed, int vec, bool spread, hipStream_t stream, const FrameArgs &a);
+void launch_frame_s(const FramePlan &pl, int method, int vec, bool spread, hipStream_t stream, const FrameArgs &a);
 
 // Which packed streams the fused kernel reads itself: 14 bits in any geometry; 12 bits (8 pixels = 12 bytes: every group
 // dword-aligned) with rows of whole groups; 10 bits (8 pixels = 10 bytes) with rows of whole 16-pixel groups (every row then
@@ -886,19 +720,6 @@ int launch_frame(const Device *dev, const Geom &g, bool packed, const void *src,
                  const int32_t *coef, hipStream_t stream, bool spread)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    const int geo = frame_geo_of(method);
-    if ((long long)frame_tiles_x(g.w) * frame_tiles_y(g.h, geo) * nframes >= (1ll << 30)) {
-        set_error("too many tiles in one launch (%d frames): split the batch", nframes);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (g.w < 2 || g.h < 2 || (g.w & 1) || (long long)g.w * g.h >= (1ll << 28)) {      // 32-bit bit / byte offsets inside a frame
-        set_error("frame geometry %dx%d unsupported", g.w, g.h);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (packed && !frame_kernel_takes(g, src, src_stride, dst, dst_stride, nframes)) {
-        set_error("fused path: %d-bit input at %dx%d needs an unpack pass first", g.bpp, g.w, g.h);
-        return MLVFS_AMD_ERR_ARG;
-    }
     FrameArgs a{};
     a.src = (const uint8_t *)src; a.src_stride = src_stride;
     a.src_bytes = (unsigned)(((size_t)g.w * g.h * (packed ? g.bpp : 16) / 8 + 3) / 4 * 4);  // one frame as the loader's range-checked buffer
@@ -906,12 +727,8 @@ int launch_frame(const Device *dev, const Geom &g, bool packed, const void *src,
     a.w = g.w; a.h = g.h; a.black = g.black; a.white = g.white;
     a.nframes = nframes;
     a.tiles_x = frame_tiles_x(g.w);
-    a.tiles_y = frame_tiles_y(g.h, geo);
+    a.tiles_y = frame_tiles_y(g.h, frame_geo_of(method));
     a.t16 = dev->luts.t16;
-    if (method != 0) {
-        int rc = e2r_table(dev, g.black, &a.e2d, stream);
-        if (rc) return rc;
-    }
     a.patch = pv && pv->n_rec > 0;
     if (a.patch) { a.cells = (const int4 *)pv->cells; a.n_rec = pv->n_rec; a.tile_off = pv->tile_off; }
     a.stripes = stripes ? 1 : 0;
@@ -924,33 +741,50 @@ int launch_frame(const Device *dev, const Geom &g, bool packed, const void *src,
     // vector path: rows are whole 8-pixel groups (14 bytes of stream) and the buffers 16-byte aligned: every row of a 16-pixel-multiple
     // width starts dword-aligned (1); widths that are 8 mod 16 alternate between dword-aligned rows and rows that start in the upper
     // half of a dword (2; an even height keeps the frame's last group off the end of the buffer)
-    static const bool no_half8 = [] { const char *e = getenv("MLVFS_AMD_KF_HALF8"); return e && atoi(e) == 0; }();      // (A/B: the any-geometry path instead)
     const bool strides_ok = nframes == 1 || (src_stride % 16 == 0 && dst_stride % 16 == 0);
     int vec = ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0 && strides_ok && g.w >= 16
-                        ? ((g.w % 16) == 0 ? 1 : ((g.w % 16) == 8 && (g.h % 2) == 0 && !no_half8 ? 2 : 0)) : 0;
+                        ? ((g.w % 16) == 0 ? 1 : ((g.w % 16) == 8 && (g.h % 2) == 0 ? 2 : 0)) : 0;
     if (packed && g.bpp == 12) vec = 3;                  // (frame_kernel_takes has checked the geometry)
     if (packed && g.bpp == 10) vec = 4;
-#define MLV_DISPATCH_S(M, S)                                                                              \
-    return packed ? (vec == 1 ? launch_frame_t<M, true, 1, S>(a, dev->num_cu, stream)                     \
-                   : vec == 2 ? launch_frame_t<M, true, 2, S>(a, dev->num_cu, stream)                     \
-                   : vec == 3 ? launch_frame_t<M, true, 3, S>(a, dev->num_cu, stream)                     \
-                   : vec == 4 ? launch_frame_t<M, true, 4, S>(a, dev->num_cu, stream)                     \
-                              : launch_frame_t<M, true, 0, S>(a, dev->num_cu, stream))                    \
-                  : (vec == 1 ? launch_frame_t<M, false, 1, S>(a, dev->num_cu, stream)                    \
-                   : vec == 2 ? launch_frame_t<M, false, 2, S>(a, dev->num_cu, stream)                    \
-                              : launch_frame_t<M, false, 0, S>(a, dev->num_cu, stream))
-#define MLV_DISPATCH(M)                                                                                   \
-    if (spread && M != 0) { MLV_DISPATCH_S(M, true); }                                                    \
-    MLV_DISPATCH_S(M, false)
-    switch (method) {
-        case 0: MLV_DISPATCH(0);
-        case 2: MLV_DISPATCH(2);
-        case 3: MLV_DISPATCH(3);
-        case 5: MLV_DISPATCH(5);
-        default: set_error("Unsupported chroma smooth method %d", method); return MLVFS_AMD_ERR_ARG;
+    const FramePassInputs in{ g.w, g.h, packed ? g.bpp : 16, g.black, method, packed, vec, a.patch != 0,
+                              !stripes ? StripeForm::none : a.coef_pk ? StripeForm::packed : StripeForm::generic, nframes, dev->num_cu };
+    if (const int rc = check_frame_pass(in)) return rc;
+    if (packed && !frame_kernel_takes(g, src, src_stride, dst, dst_stride, nframes)) {
+        set_error("fused path: %d-bit input at %dx%d needs an unpack pass first", g.bpp, g.w, g.h);
+        return MLVFS_AMD_ERR_ARG;
     }
-#undef MLV_DISPATCH
-#undef MLV_DISPATCH_S
+    if (method != 0) {
+        int rc = e2r_table(dev, g.black, &a.e2d, stream);
+        if (rc) return rc;
+    }
+    FramePlan pl;
+    StreamState sb;
+    if (const int rc = plan_on_stream(stream, in, &pl, &sb)) return rc;
+
+    a.tickets = sb.tickets;
+    KernelTimer &tm = kernel_timer();
+    const bool timed = tm.on && tm.used + 2 <= (int)tm.ev.size();
+    if (timed) MLV_HIP(hipEventRecord(tm.ev[tm.used], stream));
+    if (pl.first == FirstKernel::s) {
+        a.wl_ctl = sb.tickets + S_STAT_AT;               // (k_frame_s: [0] its cumulative count of dark steps)
+        a.wl_stat = sb.d_stat ? sb.d_stat + 1 : nullptr;
+        launch_frame_s(pl, method, vec, spread, stream, a);
+    } else {
+        a.wl = sb.wl;
+        a.wl_ctl = sb.tickets + WL_CTL_AT;
+        a.wl_stat = sb.d_stat;
+        a.groups = pl.groups; a.run = pl.run; a.singles = pl.singles;
+        // k_frame_p / k_frame_p5 do what they can settle and list the rest; k_frame in list mode does that again (nothing listed: its
+        // workgroups end at once).  Both inside the timer's bracket: the pair is the pass.
+        if (pl.first != FirstKernel::none) launch_frame_p(pl, method, packed, vec, spread, stream, a);
+        a.list_mode = pl.list_after ? 1 : 0;
+        with_layout(method, packed, vec, spread, [&](auto M, auto P, auto V, auto S) {
+            hipLaunchKernelGGL((k_frame<M.value, P.value, V.value, S.value>), dim3(pl.grid), dim3(256), 0, stream, a);
+        });
+    }
+    if (timed) { MLV_HIP(hipEventRecord(tm.ev[tm.used + 1], stream)); tm.used += 2; }
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
 }
 
 // ---------------------------------------------------------------- which T16 layout suits a clip

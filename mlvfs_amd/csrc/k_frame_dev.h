@@ -8,6 +8,7 @@
 #include <vector>
 #include <algorithm>
 #include <cstdio>
+#include <type_traits>
 
 // two 16-bit lanes per register: v_pk_min_i16 / v_pk_max_i16 issue at the rate of v_min_i32 (tools/valu_rate.hip)
 typedef short mlv_pk16 __attribute__((ext_vector_type(2)));
@@ -85,9 +86,6 @@ struct FrameArgs {
     int *wl_ctl;             // [0] entries pushed, [1] entries drawn, [2] workgroups of the list-mode launch done (the last one zeroes all three), [3] tiles listed so far (statistics)
     int list_mode;
     int *wl_stat;            // page-locked host word: tiles listed so far on this stream, written by the list-mode launch when it ends
-#ifdef KF_DIAG_TIMES
-    unsigned long long *times;
-#endif
 };
 
 // Table look-ups as buffer loads with idxen: the address unit scales the index by the descriptor's stride, no VALU address arithmetic
@@ -1192,7 +1190,6 @@ __device__ __forceinline__ unsigned long long lanes_lt(int a, int b) { return __
 //   RAWREG (k_frame_s): the strip's pixels come in registers (rtop / rbot) instead of from the tile's LDS rows, and go back there
 //   (store = false: the caller stores them).
 struct NoSmem {};
-// (frame_stream_colw / _cols / _fold -- the streaming kernels' launch plan, host arithmetic -- live in common.h)
 template <int METHOD, bool PACKED, bool VECST, bool CLAMP, bool XM, bool ANYSTRIPES, bool BRIGHT, class SM, bool RAWREG = false>
 __device__ __forceinline__ void strip_output_t(const SM &sm, const OutArgs &oa, int w, int h, int black, int f, int tx0, int ty0, int jj, int kk,
                                                unsigned long long msmooth, const int (&gev)[STRIP], int gev_off, const int (&er)[STRIP], const int (&eb)[STRIP], bool store,
@@ -1309,6 +1306,33 @@ __device__ __forceinline__ void strip_output(const SM &sm, const OutArgs &oa, in
         else
 #endif
         strip_output_t<METHOD, PACKED, VECST, false, false, false, false, SM>(sm, oa, w, h, black, f, tx0, ty0, jj, kk, msmooth, gev, gev_off, er, eb, store);
+    }
+}
+
+// The one place where a launch's layout becomes template arguments: f(M, P, V, S) with std::integral_constant arguments -- chroma
+// smoothing method, packed input, vector layout (launch_frame: vec), spread table layout.  Layouts 3 and 4 (12- and 10-bit streams)
+// exist only packed, and without chroma smoothing there is no table to spread (that instantiation is compiled, never launched);
+// each launcher names its own kernel's instantiations among these with if constexpr.
+template <int N> using IntC = std::integral_constant<int, N>;
+template <class F>
+void with_layout(int method, bool packed, int vec, bool spread, F &&f)
+{
+    auto with_v = [&](auto M, auto P) {
+        auto go = [&](auto V) { if (spread && M.value != 0) f(M, P, V, std::true_type{}); else f(M, P, V, std::false_type{}); };
+        switch (vec) {
+            case 1: return go(IntC<1>{});
+            case 2: return go(IntC<2>{});
+            case 3: if constexpr (P.value) return go(IntC<3>{}); break;
+            case 4: if constexpr (P.value) return go(IntC<4>{}); break;
+        }
+        go(IntC<0>{});
+    };
+    auto with_p = [&](auto M) { if (packed) with_v(M, std::true_type{}); else with_v(M, std::false_type{}); };
+    switch (method) {               // (check_frame_pass has refused every other method)
+        case 0: return with_p(IntC<0>{});
+        case 2: return with_p(IntC<2>{});
+        case 3: return with_p(IntC<3>{});
+        case 5: return with_p(IntC<5>{});
     }
 }
 

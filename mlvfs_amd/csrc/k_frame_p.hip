@@ -1,5 +1,6 @@
-// k_frame_p.hip -- the packed-once kernel of the fused pass (round 5); launched by k_frame.hip's launch_frame_t before the
+// k_frame_p.hip -- the packed-once kernel of the fused pass (round 5); launched by k_frame.hip's launch_frame before the
 // list-mode k_frame.  Its own translation unit: its own scheduler flags (Makefile), and the two kernels compile in parallel.
+#include "frame_plan.h"
 #include "k_frame_dev.h"
 
 namespace mlv {
@@ -655,21 +656,13 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
     }
 }
 
-// (2x2 and 3x3: k_frame's int32 networks compile to three-input min / max / med3 and the packed two-input ones save them nothing;
-// MLVFS_AMD_KF_P_ALL=1 sends them through k_frame_p all the same: A/B)
-bool frame_p_exists(int method, int vec)
-{
-    static const bool all = [] { const char *e = getenv("MLVFS_AMD_KF_P_ALL"); return e && e[0] == '1'; }();
-    return (method == 5 || (all && method != 0)) && vec != 0;
-}
-
 // ================================================================ k_frame_p5: the packed-once pass as a streaming kernel (round 5, end)
 // k_frame_s's form (k_frame_s.hip) for cs5x5: a WAVE owns a column of the frame 62 items wide (lanes 0 / 63: the halo items), walks down it a
 // cell row per step, keeps the five packed rows of the window in registers, gets the right-hand group's sorted columns and rank window
 // from the next lane (v_mov_b32_dpp wave_shl, as k_frame_p's lanes do inside a row) and finishes row r - 2 when row r is in.  No
 // s_barrier after the table load, no planes in LDS (only the pixels of the three rows between load and output wait there, in the
 // wave's own 6 KiB): 113 VGPRs, 40 KiB of LDS, four workgroups per CU -- and 6.0 instead of 6.8 us per frame (profiles/r05/ab_p5.log).
-//   * Reference: one per task (a column of KF_P5_SEG rows), the median of five cells at its centre like k_frame_p's.
+//   * Reference: one per task (a column of seg_rows rows), the median of five cells at its centre like k_frame_p's.
 //   * A strip whose packed median is not provably exact marks its lane and row; when the task ends, the tiles of k_frame's geometry
 //     that those strips lie in go on the launch's work list and the list-mode k_frame does them again (what this kernel wrote there
 //     is overwritten).
@@ -679,14 +672,11 @@ bool frame_p_exists(int method, int vec)
 //     chosen per row from the five rows of its window.
 // Takes long launches of 14-bit streams (rows of whole 8-pixel groups, even heights, black >= 0, stripes packed or none); everything
 // else, and every short launch, stays with k_frame_p / k_frame.
-#ifndef KF_P5_SEG
-#define KF_P5_SEG 60
-#endif
 __device__ __forceinline__ int dpp_prev_ii(int v) { return __builtin_amdgcn_mov_dpp(v, 0x138, 0xf, 0xf, true); }
 template <bool SPREAD, int VEC>
 __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols, int segs, int seg_rows, int fold, int S_OUT)
 {
-    constexpr int BPP = 14;                              // (S_OUT: items a wave writes per row, k_frame_dev.h: frame_stream_colw)
+    constexpr int BPP = 14;                              // (S_OUT: items a wave writes per row, frame_plan.h: FRAME_STREAM_COLW)
     __shared__ __align__(16) uint16_t t16[MLV_T16_N + (SPREAD ? 64 : 0)];
     // (the dark-clip table layout is 128 bytes longer: there only the 62 lanes that write a row park it, which keeps the workgroup at 40 KiB)
     constexpr int PARK_LANES = SPREAD ? 62 : 64;
@@ -979,63 +969,26 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
     }
 }
 
-// does the streaming form take this two-kernel launch, and in tasks of how many rows?  0: no  (launch_frame_p_kernel)
-static int frame_p5_takes(int method, bool packed, int vec, int num_cu, const FrameArgs &a)
+// The plan's first kernel of a cs5x5 launch (frame_plan.cpp): k_frame_p5 where it takes the launch, else k_frame_p.  (k_frame_p is
+// instantiated for cs2x2 / cs3x3 as well, which the plan never gives it: k_frame's int32 networks compile to three-input min / max /
+// med3 and the packed two-input ones save them nothing; tools/kfp_resources.sh and tools/isa_classes.py compare the two.)
+void launch_frame_p(const FramePlan &pl, int method, bool packed, int vec, bool spread, hipStream_t stream, const FrameArgs &a)
 {
-    if (method != 5 || !packed || (vec != 1 && vec != 2)) return 0;
-    const char *e = getenv("MLVFS_AMD_KF_P5");                                  // 0 never, 1 (default) long launches, 2 whenever it can
-    const int policy = e ? atoi(e) : 1;
-    if (policy == 0) return 0;
-    if ((a.stripes && !a.coef_pk) || a.black < 0) return 0;
-    if (!(a.w >= 16 && a.w % 8 == 0 && a.h >= 2 && a.h % 2 == 0)) return 0;
-    static const int env_seg = [] { const char *e = getenv("MLVFS_AMD_KF_P5_SEG"); return e ? atoi(e) : 0; }();      // (experiments)
-    if (env_seg > 0) return env_seg;
-    // at least 3.5 tasks per wave (k_frame_s.hip: why), in tasks of 60 rows or, for launches half as long, of 30 (two warm-up rows per
-    // task: 3584x1320, us per frame at 50 / 100 / 200 / 400 frames per launch: k_frame_p 7.7 / 7.4 / 7.1 / 6.9, tasks of 60 rows 8.3 /
-    // 7.4 / 6.6 / 6.1, of 30 rows 8.6 / 6.9 / 6.7 / 6.2; profiles/r05/ab_p5.log)
-    const long long cols = frame_stream_cols(a.w), rows = a.h / 2;
-    const long long waves = (long long)(num_cu > 0 ? num_cu : 256) * 16;
-    for (int seg : { KF_P5_SEG, KF_P5_SEG / 2 })
-        if ((long long)a.nframes * cols * ((rows + seg - 1) / seg) * 2 >= waves * 7) return seg;
-    return policy == 2 ? KF_P5_SEG / 2 : 0;
-}
-// prefer_tiles: the stream's last launches listed more than a few per cent of their tiles (k_frame.hip: stream_state) -- footage with
-// regions of uncertain strips, where k_frame_p's skipping of the tiles behind an uncertain one saves what k_frame_p5 would do in vain
-// (low light, 400 frames per launch: 8.2 against 8.8 us per frame)
-void launch_frame_p_kernel(int method, bool packed, int vec, bool spread, int grid, hipStream_t stream, const FrameArgs &a, bool prefer_tiles)
-{
-#ifndef KFP_ONLY
-    const char *e5 = getenv("MLVFS_AMD_KF_P5");
-    if (prefer_tiles && !(e5 && atoi(e5) == 2)) {}
-    else if (const int seg_rows = frame_p5_takes(method, packed, vec, grid / 4, a)) {
-        const int cols = frame_stream_cols(a.w), segs = (a.h / 2 + seg_rows - 1) / seg_rows;
-        // a narrow last column: several of its segments side by side in one wave (k_frame_p5: fold)
-        const int fold = frame_stream_fold(a.w, cols, segs);
-#define KFP5_GO(S, V) hipLaunchKernelGGL((k_frame_p5<S, V>), dim3(grid), dim3(256), 0, stream, a, cols, segs, seg_rows, fold, frame_stream_colw())
-        if (vec == 2) { if (spread) KFP5_GO(true, 2); else KFP5_GO(false, 2); }
-        else { if (spread) KFP5_GO(true, 1); else KFP5_GO(false, 1); }
-#undef KFP5_GO
-        return;
-    }
-#endif
-#ifdef KFP_ONLY          // (tools: one or two instantiations, seconds to compile)
-    if (method == 5) hipLaunchKernelGGL((k_frame_p<5, true, 1, false>), dim3(grid), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((k_frame_p<2, true, 1, false>), dim3(grid), dim3(256), 0, stream, a);
+#ifdef KFP_ONLY          // (tools: two instantiations, seconds to compile)
+    if (method == 5) hipLaunchKernelGGL((k_frame_p<5, true, 1, false>), dim3(pl.first_grid), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((k_frame_p<2, true, 1, false>), dim3(pl.first_grid), dim3(256), 0, stream, a);
 #else
-#define MLV_P(M, P, V, S) hipLaunchKernelGGL((k_frame_p<M, P, V, S>), dim3(grid), dim3(256), 0, stream, a)
-#define MLV_P_S(M, S)                                                                                             \
-    do {                                                                                                          \
-        if (packed) { if (vec == 1) MLV_P(M, true, 1, S); else if (vec == 2) MLV_P(M, true, 2, S);                \
-                      else if (vec == 3) MLV_P(M, true, 3, S); else if (vec == 4) MLV_P(M, true, 4, S); }         \
-        else { if (vec == 1) MLV_P(M, false, 1, S); else if (vec == 2) MLV_P(M, false, 2, S); }                   \
-    } while (0)
-#define MLV_P_M(M) do { if (spread) MLV_P_S(M, true); else MLV_P_S(M, false); } while (0)
-    if (method == 2) MLV_P_M(2);
-    else if (method == 3) MLV_P_M(3);
-    else if (method == 5) MLV_P_M(5);
-#undef MLV_P_M
-#undef MLV_P_S
-#undef MLV_P
+    with_layout(method, packed, vec, spread, [&](auto M, auto P, auto V, auto S) {
+        if constexpr (M.value == 5 && P.value && (V.value == 1 || V.value == 2)) {
+            if (pl.first == FirstKernel::p5) {
+                hipLaunchKernelGGL((k_frame_p5<S.value, V.value>), dim3(pl.first_grid), dim3(256), 0, stream, a, pl.cols, pl.segs, pl.seg_rows,
+                                   pl.fold, FRAME_STREAM_COLW);
+                return;
+            }
+        }
+        if constexpr (M.value != 0 && V.value != 0)
+            hipLaunchKernelGGL((k_frame_p<M.value, P.value, V.value, S.value>), dim3(pl.first_grid), dim3(256), 0, stream, a);
+    });
 #endif
 }
 

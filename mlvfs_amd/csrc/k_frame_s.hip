@@ -19,14 +19,12 @@
 // row r's table look-ups are under way, so that neither wait is exposed (186 VGPRs: the in-flight conversion, three rows of colour
 // differences, the medians' operands and two sets of look-ups do not fit four waves per SIMD).
 // What it takes: 14-bit streams whose rows are whole 8-pixel groups (on the buffers the vector path wants), even heights, no pixel
-// map, stripes in the packed 16-bit form (or none), black >= 0.  Everything else stays with k_frame (k_frame.hip: launch_frame_t).
+// map, stripes in the packed 16-bit form (or none), black >= 0.  Everything else stays with k_frame (frame_plan.cpp).
+#include "frame_plan.h"
 #include "k_frame_dev.h"
 
 namespace mlv {
 
-#ifndef KF_S_SEG
-#define KF_S_SEG 60
-#endif
 #ifndef KF_S_PARK
 #define KF_S_PARK 0                   // 1: a row's pixels wait for their medians in LDS instead of in registers (measured: no gain)
 #endif
@@ -246,48 +244,14 @@ __global__ __launch_bounds__(256, KF_S_WGS) void k_frame_s(const FrameArgs a, in
     }
 }
 
-// does the streaming kernel take this launch?  (k_frame.hip: launch_frame_t asks before it sets up its own)
-bool frame_s_takes(int method, bool packed, int vec, int num_cu, const FrameArgs &a)
+// k_frame_s as the plan lays it out (frame_plan.cpp: which launches it takes, its grid and tasks)
+void launch_frame_s(const FramePlan &pl, int method, int vec, bool spread, hipStream_t stream, const FrameArgs &a)
 {
-    // MLVFS_AMD_KF_S: 0 never, 1 (default) long launches of footage without many pixels at or below black, 2 whenever the kernel can
-    // (read at every launch: the tests switch it)
-    if ((method != 2 && method != 3) || !packed || (vec != 1 && vec != 2)) return false;
-    const char *e = getenv("MLVFS_AMD_KF_S");
-    const int policy = e ? atoi(e) : 1;
-    if (policy == 0) return false;
-    if (a.patch || (a.stripes && !a.coef_pk) || a.black < 0) return false;
-    if (!(a.w >= 16 && a.w % 8 == 0 && a.h >= 2 && a.h % 2 == 0)) return false;
-    // Long launches only: a task is a column of 60 rows (~50 us of one wave), and a wave needs a handful of them for the chip to end
-    // together -- 3584x1320, us per frame at 8 / 25 / 50 / 100 / 200 / 400 frames per launch: k_frame 10.7 / 5.7 / 5.7 / 5.5 / 5.3 / 4.9,
-    // this kernel 13.1 / 7.3 / 7.1 / 5.5 / 5.0 / 4.8 (shorter tasks do not help: two rows of warm-up each; profiles/r05/ab_kframe_s.log)
-    const long long cols = frame_stream_cols(a.w), segs = (a.h / 2 + KF_S_SEG - 1) / KF_S_SEG;
-    const long long waves = (long long)(num_cu > 0 ? num_cu : 256) * KF_S_WGS * 4;
-    return policy == 2 || (long long)a.nframes * cols * segs * 2 >= waves * 7;             // >= 3.5 tasks per wave
-}
-
-// wave-steps of a launch (what the dark steps it reports are a share of)
-long long frame_s_steps(const FrameArgs &a)
-{
-    const long long cols = frame_stream_cols(a.w);
-    const int fold = frame_stream_fold(a.w, (int)cols, (a.h / 2 + KF_S_SEG - 1) / KF_S_SEG);
-    return (long long)a.nframes * ((cols - 1) * fold + 1) * (a.h / 2) / fold;
-}
-
-void launch_frame_s_kernel(int method, bool spread, int vec, int num_cu, hipStream_t stream, const FrameArgs &a)
-{
-    const int cols = frame_stream_cols(a.w), rows = a.h / 2;
-    static const int env_seg = [] { const char *e = getenv("MLVFS_AMD_KF_S_SEG"); return e ? atoi(e) : 0; }();
-    const int seg_rows = std::max(env_seg > 0 ? env_seg : KF_S_SEG, 1), segs = (rows + seg_rows - 1) / seg_rows;
-    const int fold = frame_stream_fold(a.w, cols, segs);
-    const long long tasks = (long long)a.nframes * (fold > 1 ? (cols - 1) * segs + (segs + fold - 1) / fold : cols * segs);
-    int grid = (num_cu > 0 ? num_cu : 256) * KF_S_WGS;   // five workgroups per CU: 20 waves, 80 KiB of LDS (five copies of the table)
-    if ((long long)grid * 4 > tasks) grid = (int)((tasks + 3) / 4);
-#define KFS_GO(S, V, M) hipLaunchKernelGGL((k_frame_s<S, V, M>), dim3(grid), dim3(256), 0, stream, a, cols, segs, seg_rows, fold, frame_stream_colw())
-#define KFS_M(S, V) do { if (method == 3) KFS_GO(S, V, 3); else KFS_GO(S, V, 2); } while (0)
-    if (vec == 2) { if (spread) KFS_M(true, 2); else KFS_M(false, 2); }
-    else { if (spread) KFS_M(true, 1); else KFS_M(false, 1); }
-#undef KFS_M
-#undef KFS_GO
+    with_layout(method, true, vec, spread, [&](auto M, auto P, auto V, auto S) {
+        if constexpr ((M.value == 2 || M.value == 3) && P.value && (V.value == 1 || V.value == 2))
+            hipLaunchKernelGGL((k_frame_s<S.value, V.value, M.value>), dim3(pl.first_grid), dim3(256), 0, stream, a, pl.cols, pl.segs, pl.seg_rows,
+                               pl.fold, FRAME_STREAM_COLW);
+    });
 }
 
 void preload_k_frame_s() { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, (const void *)k_frame_s<false, 1, 2>); (void)hipGetLastError(); }

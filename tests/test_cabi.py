@@ -224,3 +224,68 @@ def test_streaming_kernels_plan():
     assert plan(656, 190, 30) == (0, (2, 4, 2, 4 + 2))           # 82 items: 62 + 20
     assert plan(3584, 66) == (0, (8, 1, 1, 8))                   # one segment: nothing to fold
     assert plan(3583, 1320)[0] != 0 and plan(3584, 1321)[0] != 0
+
+
+PLAN_KEYS = ("first", "list_after", "grid", "groups", "run", "singles", "first_grid", "seg_rows", "cols", "segs", "fold", "tasks", "steps",
+             "wl_entries", "word")
+P_NONE, P_TILES, P_P5, P_S = 0, 1, 2, 3          # first kernel: k_frame alone, k_frame_p, k_frame_p5, k_frame_s
+
+
+def test_fused_pass_plan(amd, monkeypatch):
+    """Which kernels a launch of the fused pass runs and how they are laid out (csrc/frame_plan.cpp, no GPU): every GPU test passes
+    whichever kernel runs, so the choice is pinned here.  The numbers are those the launcher computed before the plan was one function;
+    only the work list may be larger -- k_frame_p5 can append more entries than a frame has tiles where a frame is one tile row high."""
+    for v in ("MLVFS_AMD_KF_P", "MLVFS_AMD_KF_P5", "MLVFS_AMD_KF_S"):
+        monkeypatch.delenv(v, raising=False)
+
+    def plan(w=3584, h=1320, bpp=14, black=2048, cs=5, packed=1, vec=1, pmap=1, stripes=1, nframes=400, cus=256, held=0, some_listed=0, **sw):
+        for k, v in sw.items():
+            monkeypatch.setenv("MLVFS_AMD_KF_" + k.upper(), str(v))
+        out = (C.c_longlong * 15)()
+        rc = amd.mlvfs_amd_test_frame_plan((C.c_int * 13)(w, h, bpp, black, cs, packed, vec, pmap, stripes, nframes, cus, held, some_listed), out)
+        for k in sw:
+            monkeypatch.delenv("MLVFS_AMD_KF_" + k.upper())
+        return None if rc else dict(zip(PLAN_KEYS, out))
+
+    def pick(p, keys):
+        return tuple(p[k] for k in keys.split())
+
+    # 3584x1320 cs5x5 with a pixel map and stripes, 256 CUs: k_frame's grid, groups of eight CUs, runs of 22 tiles
+    p = plan()
+    assert pick(p, "grid groups run singles word") == (1024, 32, 22, 256, 0)
+    # long launches: k_frame_p5 on k_frame's grid in tasks of 60 rows, at 100 frames of 30; at 50 frames k_frame_p -- and the list-mode
+    # k_frame behind either.  The work list holds every tile (k_frame_p5 appends fewer: 154 000 entries at most).
+    fields = "first list_after first_grid seg_rows cols segs fold tasks wl_entries"
+    assert pick(p, fields) == (P_P5, 1, 1024, 60, 8, 11, 4, 400 * (7 * 11 + 3), 28 * 44 * 400)
+    assert pick(plan(nframes=100), fields) == (P_P5, 1, 1024, 30, 8, 22, 4, 100 * (7 * 22 + 6), 28 * 44 * 100)
+    assert pick(plan(nframes=50), fields) == (P_TILES, 1, 1024, 0, 0, 0, 0, 0, 28 * 44 * 50)
+    # what k_frame_p5 does not read goes to k_frame_p: 12-bit streams, 16-bit frames, stripes beyond the packed form
+    for kw in (dict(bpp=12, vec=3), dict(bpp=16, packed=0), dict(stripes=2)):
+        assert pick(plan(**kw), "first list_after wl_entries") == (P_TILES, 1, 28 * 44 * 400), kw
+    # the stream's verdicts: some tiles listed -> k_frame_p (unless KF_P5=2); held back -> k_frame alone (unless KF_P=2)
+    assert pick(plan(some_listed=1), "first list_after") == (P_TILES, 1)
+    assert pick(plan(some_listed=1, p5=2), "first seg_rows") == (P_P5, 60)
+    assert pick(plan(held=1), "first list_after first_grid wl_entries word") == (P_NONE, 0, 0, 0, 0)
+    assert pick(plan(held=1, p=2), "first list_after") == (P_P5, 1)
+    assert pick(plan(p=0), "first list_after word") == (P_NONE, 0, -1)
+    assert pick(plan(p5=0), "first") == (P_TILES,)
+    # cs2x2: k_frame_s alone on long launches without a pixel map, k_frame with one; 8 frames are too short unless KF_S=2
+    s_fields = "first list_after first_grid seg_rows cols segs fold tasks steps word"
+    assert pick(plan(cs=2, pmap=0), s_fields) == (P_S, 0, 1024, 60, 8, 11, 4, 400 * 80, 400 * (7 * 4 + 1) * 660 // 4, 1)
+    assert pick(plan(cs=2, pmap=1), s_fields) == (P_NONE, 0, 0, 0, 0, 0, 0, 0, 0, -1)
+    assert pick(plan(cs=2, pmap=0, nframes=8), s_fields + " run") == (P_NONE, 0, 0, 0, 0, 0, 0, 0, 0, -1, 19)
+    assert pick(plan(cs=2, pmap=0, nframes=8, s=2), s_fields) == (P_S, 0, 160, 60, 8, 11, 4, 8 * 80, 8 * 29 * 660 // 4, 1)
+    assert pick(plan(cs=2, pmap=0, held=1), "first word") == (P_NONE, 1)
+    assert pick(plan(cs=3, pmap=0, held=1, s=2), "first") == (P_S,)
+    assert pick(plan(cs=2, pmap=0, s=0), "first word") == (P_NONE, -1)
+    # no chroma smoothing: k_frame alone
+    assert pick(plan(cs=0), "first list_after word grid") == (P_NONE, 0, -1, 1024)
+    # 112x250: one column of 14 items, its segments folded four to a wave
+    assert pick(plan(w=112, h=250, cs=2, vec=2, pmap=0, s=2), s_fields) == (P_S, 0, 100, 60, 1, 3, 4, 400, 400 * 125 // 4, 1)
+    assert pick(plan(w=112, h=250, vec=2, nframes=3600), fields) == (P_P5, 1, 1024, 30, 1, 5, 4, 3600 * 2, 9 * 3600)
+    # 3584x30 (one tile row) forced through k_frame_p5: eight tasks of up to five tile columns each per frame, more than its 28 tiles
+    p = plan(h=30, nframes=160, pmap=0, p=2, p5=2)
+    assert pick(p, "first seg_rows cols segs fold tasks") == (P_P5, 30, 8, 1, 1, 160 * 8)
+    assert p["wl_entries"] >= 160 * 8 * 5 > 28 * 160
+    # a launch the fused pass refuses
+    assert plan(w=3583) is None and plan(cs=4) is None and plan(nframes=0) is None

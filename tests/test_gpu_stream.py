@@ -93,13 +93,14 @@ def test_fused_pipeline_rows_of_half_groups(torch_cuda, oracle, w, h, cs):
         s.close()
 
 
-@pytest.mark.parametrize("w,h", [(256, 130), (1008, 44), (16, 12), (48, 10), (496, 122), (512, 124), (1736, 64), (136, 62), (3584, 66), (608, 250), (656, 190), (3584, 252)])
+@pytest.mark.parametrize("w,h", [(256, 130), (1008, 44), (16, 12), (48, 10), (496, 122), (512, 124), (1736, 64), (136, 62), (3584, 66), (608, 250), (656, 190), (3584, 252),
+                                 (112, 250)])
 @pytest.mark.parametrize("cs,stripes", [(2, 0), (2, 1), (3, 0), (3, 1)])
 def test_streaming_kernel_matches_oracle(torch_cuda, oracle, w, h, cs, stripes, monkeypatch):
     """k_frame_s (cs2x2 / cs3x3 without a pixel map: a wave per 62-item column, rows in registers, no barriers) takes long launches only
     (and hands footage with many pixels at or below black back to k_frame); MLVFS_AMD_KF_S=2 forces it wherever it can run, so that
-    its corners are compared with the oracle: one and several columns (496 px each), a last column of one item, widths that are 8
-    mod 16, two-row frames, frames of one task and of several, every footage kind (the loader's form for pixels at or below
+    its corners are compared with the oracle: one and several columns (496 px each), a last column of one item, a frame of one
+    narrow column whose segments are folded side by side (112 px), widths that are 8 mod 16, two-row frames, frames of one task and of several, every footage kind (the loader's form for pixels at or below
     black, clamped look-ups), with and without the stripes epilogue.  The same launches through k_frame (MLVFS_AMD_KF_S=0) must
     give the same bytes."""
     from mlvfs_amd.stream import to_numpy_u16
@@ -149,12 +150,34 @@ def test_streaming_cs5x5_kernel_matches_oracle(torch_cuda, oracle, w, h, bad, st
             assert np.array_equal(got[k], want[k]), f"{kind} frame {k}: {(got[k] != want[k]).sum()} px differ"
 
 
+def test_streaming_cs5x5_one_tile_row(torch_cuda, oracle, monkeypatch):
+    """Frames one tile row high (3584x30) forced through k_frame_p5 (MLVFS_AMD_KF_P=2, MLVFS_AMD_KF_P5=2): a task lists up to five tile
+    columns, so 160 frames of colour patches, where most strips are uncertain, can list more entries than the launch has tiles.  The
+    work list is sized from the plan (csrc/frame_plan.cpp); every frame equals the oracle's."""
+    from mlvfs_amd.stream import to_numpy_u16
+    monkeypatch.setenv("MLVFS_AMD_KF_P", "2")
+    monkeypatch.setenv("MLVFS_AMD_KF_P5", "2")
+    w, h, nf = 3584, 30, 160
+    frames = [synth.colour_cast_frame(w, h, seed=3 + k) for k in range(8)]
+    want, _, _ = oracle_clip(oracle, frames, w, h, 5, 0, 0)
+    s = make_stream(w, h)
+    base = s.upload_packed([synth.pack_bits(f) for f in frames])
+    s.analyse_first_frame(base, cs=5, bad_pix=0, stripes=False, rand_mode=1)
+    packed = s.alloc_packed(nf)
+    for i in range(0, nf, 8):
+        packed[i:i + 8] = base
+    got = to_numpy_u16(s.process(packed, cs=5, fix_pixels=False, stripes=False))
+    s.close()
+    for i in range(nf):
+        assert np.array_equal(got[i], want[i % 8]), f"frame {i}: {(got[i] != want[i % 8]).sum()} px differ"
+
+
 @pytest.mark.parametrize("kind", ["normal", "low_light", "colour_cast"])
 @pytest.mark.parametrize("cs,bad", [(5, 1), (5, 0), (2, 0)])
 def test_long_launches_default_policy(torch_cuda, oracle, kind, cs, bad):
     """The library's own choice of kernels (no switches set) on launches long enough for the streaming kernels -- 3 600 frames of
     512x124: k_frame_p5 / k_frame_s take the first launch, the status words of finished launches then move low-light footage to
-    k_frame_p + list and colour patches to k_frame alone (csrc/k_frame.hip: stream_state, stream_state_s).  Five launches in a row,
+    k_frame_p + list and colour patches to k_frame alone (csrc/k_frame.hip: Backoff).  Five launches in a row,
     the first three with the stream drained in between (every status word seen), the last two back to back: every launch's first,
     middle and last frames equal the oracle's."""
     import torch
