@@ -418,6 +418,11 @@ int mlvfs_amd_test_stream_plan(int width, int height, int seg_rows, int *cols, i
  * k_frame follows, k_frame's grid, groups, run, singles, first kernel's grid, rows per task, columns, segments, fold, tasks, k_frame_s
  * steps, work-list entries, status word watched (-1 none)}.  0, or MLVFS_AMD_ERR_ARG for a launch the fused pass refuses.          */
 int mlvfs_amd_test_frame_plan(const int *in, long long *out);
+/* Test hook, host only: how a batch of `nframes` AMaZE dual-ISO conversions of width x height frames goes out (csrc/dualiso.cpp:
+ * dualiso_parts), MLVFS_AMD_DI_PART read from the environment as a conversion reads it.  parts[2k] / parts[2k + 1]: first frame /
+ * frames of part k; *tail: 1 if what follows each part's AMaZE runs on a second stream.  Returns the number of parts (at most
+ * max_parts), or MLVFS_AMD_ERR_ARG.                                                                                                */
+int mlvfs_amd_test_dualiso_parts(int width, int height, int nframes, int *parts, int max_parts, int *tail);
 
 /* -- batched stages of process_frame that existed only per frame ------------- */
 /* Pattern noise (patternnoise.c:357-380, debug_flags 0) on `nframes` device frames of one geometry (even width and height), `stride`

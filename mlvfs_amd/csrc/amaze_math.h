@@ -62,8 +62,8 @@ __device__ __forceinline__ float diag_bound(float rb, float centre, float lo, fl
     return r > CLIP_PT ? ulim(r, lo, hi) : r;
 }
 
-// What the dual-ISO conversion looks up of the three planes (hdr.c:1041-1062; k_dualiso.hip: k_di_amaze_ev did this in a pass of its own
-// until round 5): green's scaling undone, the three clamped to 20 bits, interp_raw2ev of each and of the gray value.  r, g, b: the
+// What the dual-ISO conversion looks up of the three planes (hdr.c:1041-1062), made by AMaZE's output stage instead of a pass of its
+// own: green's scaling undone, the three clamped to 20 bits, interp_raw2ev of each and of the gray value.  r, g, b: the
 // planes' values as the kernels would store them (65535 x the tile's value).
 __device__ __forceinline__ void ev_of_planes(const int *__restrict__ r2e, int black, float r, float g_stored, float b, int &ev_r, int &ev_g, int &ev_b, int &ev_gray)
 {

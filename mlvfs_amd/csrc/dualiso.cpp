@@ -14,7 +14,6 @@
 #include "clip.h"
 #include "dualiso.h"
 
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -304,20 +303,6 @@ static int candidate_slopes(int device, const double **d_ta, const double **h_ta
     return MLVFS_AMD_OK;
 }
 
-// MLVFS_AMD_DI_TIMING=1: wall-clock of the host-visible phases of one conversion on stderr (tuning aid)
-struct PhaseTimer {
-    bool on;
-    std::chrono::steady_clock::time_point t0;
-    PhaseTimer() : on(getenv("MLVFS_AMD_DI_TIMING") != nullptr), t0(std::chrono::steady_clock::now()) {}
-    void mark(const char *what)
-    {
-        if (!on) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[di] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
-
 // ------------------------------------------------------------------ from a frame's integer decisions to its parameters
 // What the reference decides after its analysis passes, in its order, with its progress lines: the checks that make it give up
 // (return 0: the frame is left alone), the exposure fit's scalars and the libm values derived from them.  `d` comes from the
@@ -433,6 +418,37 @@ static void squeezed_rows(const DiParams &p, int *sq, int hs)
     for (int y = 0; y < hs; y++) sq[2 * hs + y] = y < h ? owner[y] : 0;         // squeezed row -> its source row, -1: no exposure lands on it (stays zero)
 }
 
+// How an AMaZE batch goes out (cr2hdr20_batch): a batch of 8 or more frames uses a second stream, which takes everything behind a
+// part's AMaZE (interpolation, alias map, blend: table- and bandwidth-bound) and runs it under the next part's AMaZE, which is bound by
+// instruction issue -- what two host threads with a batch each get, for one.  A part holds enough complete AMaZE tiles for about four
+// rounds of k_amaze_rows' 256 workgroups (3584x1320: 282 per frame -> 4 frames; 1736x976: 84 -> 13, a batch of 8 stays one part --
+// in parts of 4 it took 4.4 instead of 3.9 ms), or MLVFS_AMD_DI_PART frames (read per call: tests).  The last part is smaller than
+// the others (3/4 of an even share: 8 frames = 5 + 3): what follows its AMaZE runs with the chip to itself, and the less of that the
+// better (1 037 -> 1 074 conversions/s, profiles/r05/di_experiments.log).  Returns whether the second stream is used; parts[k] =
+// {first frame, frames}.
+struct DiPart { int f0, n; };
+static bool dualiso_parts(int w, int H, int nframes, std::vector<DiPart> &parts)
+{
+    parts.assign(1, DiPart{ 0, nframes });
+    if (nframes < 8) return false;
+    const char *e = getenv("MLVFS_AMD_DI_PART");
+    const int part_env = e && atoi(e) > 0 ? atoi(e) : 0;
+    int nfx = 0, nfy = 0;
+    amaze_rows_extent(w, H, &nfx, &nfy);
+    const int per_frame = nfx * nfy > 0 ? nfx * nfy : 1;
+    const int part = part_env ? part_env : std::max(4, (1024 + per_frame - 1) / per_frame);
+    const int nparts = nframes / part;
+    if (nparts <= 1) return true;
+    const int last = std::max(1, (3 * (nframes / nparts) + 2) / 4), front = nframes - last;
+    parts.clear();
+    for (int k = 0; k < nparts - 1; k++) {
+        const int f0 = (int)((long long)front * k / (nparts - 1));
+        parts.push_back(DiPart{ f0, (int)((long long)front * (k + 1) / (nparts - 1)) - f0 });
+    }
+    parts.push_back(DiPart{ front, last });
+    return true;
+}
+
 // AMaZE tile planes of a batch: frame f's blocks at f * stride; a slot is zeroed when it is (re)allocated or when the rows of the
 // frame in it change (RGGB and GBRG frames of one clip differ by a row), like the reference's calloc per call
 struct AmazeSlots : DiWork { int w = 0, H = 0; std::vector<int> slot_h; size_t stride = 0; };
@@ -450,7 +466,6 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
 {
     if (frame_touched) *frame_touched = false;
     for (int f = 0; f < nframes; f++) results[f] = 0;
-    PhaseTimer pt;
     if (w <= 0 || H <= 8 || nframes <= 0) return 0;
     if (fh && nframes != 1) { set_error("cr2hdr20: frame headers go with a single frame"); return MLVFS_AMD_ERR_ARG; }
     const size_t N = (size_t)w * H, S = (N + 63) / 64 * 64, NF = (size_t)nframes;
@@ -482,9 +497,8 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
     const size_t cells_stride = ((size_t)3 * (H / 2) * (w / 2) + 63) / 64 * 64;
     const size_t o_full_s = take(cs ? NF * S * 4 : 0), o_half_s = take(cs ? NF * S * 4 : 0), o_cells = take(cs ? NF * cells_stride * 4 : 0);
     const bool amaze = o.interp_method == 0;
-    const size_t o_cfa = take(amaze ? NF * S * 4 : 0), o_red = take(amaze ? NF * S * 4 : 0), o_green = take(amaze ? NF * S * 4 : 0),
-                 o_blue = take(amaze ? NF * S * 4 : 0), o_ev = take(amaze ? NF * S * 12 : NF * S * 4), o_gray = take(amaze ? NF * S * 4 : 0), o_dir = take(amaze ? NF * S : 0),
-                 o_sq = take(amaze ? NF * (size_t)H * 12 : 0), o_stats = take(NF * 16 * DI_STAT_SLOTS);
+    const size_t o_cfa = take(amaze ? NF * S * 4 : 0), o_ev = take(amaze ? NF * S * 12 : NF * S * 4), o_gray = take(amaze ? NF * S * 4 : 0),
+                 o_dir = take(amaze ? NF * S : 0), o_sq = take(amaze ? NF * (size_t)H * 12 : 0), o_stats = take(NF * 16 * DI_STAT_SLOTS);
     DiWork &wk = t_work[c->dev->id];
     rc = wk.ensure(off);
     if (rc) return rc;
@@ -528,7 +542,6 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
         double *check = (double *)(PH + ph_check);
         MLV_HIP(hipMemcpyAsync(check, B + o_check, 16, hipMemcpyDeviceToHost, stream));
         MLV_HIP(hipStreamSynchronize(stream));
-        pt.mark("analyse (kernel + D2H)");
         if (!(check[0] / check[1] > 0.5)) return 0;                     // hdr_check, hdr.c:432-438
         bool ch1 = false, ch2 = false;
         rc = focus_pixels_device(fh, c, d_frames, 1, &ch1);
@@ -564,7 +577,6 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
     if (rc) return rc;
     MLV_HIP(hipMemcpyAsync(dd, B + o_dd, NF * sizeof(DiDecide), hipMemcpyDeviceToHost, stream));
     MLV_HIP(hipStreamSynchronize(stream));                  // <- the round trip of the batch
-    pt.mark("decisions (device) + D2H");
 
     if (getenv("MLVFS_AMD_DI_DEBUG"))
         for (int f = 0; f < nframes; f++) {
@@ -590,7 +602,6 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
         for (int k = 0; k < bt.nheights; k++) seen = seen || bt.heights[k] == pp[f].h;
         if (!seen && bt.nheights < 2) bt.heights[bt.nheights++] = pp[f].h;
     }
-    pt.mark("checks + scalars + tables (host)");
     if (nconv == 0) return 0;
     MLV_HIP(hipMemcpyAsync(B + o_pp, pp, NF * sizeof(DiParams), hipMemcpyHostToDevice, stream));
 
@@ -626,20 +637,18 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
                 MLV_HIP(hipMemsetAsync((float *)as.base + (size_t)f * a_stride, 0, a_stride * sizeof(float), stream));
             as.slot_h[f] = pp[f].h;
         }
-        P.cfa = (float *)(B + o_cfa); P.red = (float *)(B + o_red); P.green = (float *)(B + o_green); P.blue = (float *)(B + o_blue);
+        P.cfa = (float *)(B + o_cfa);
         P.ev_red = (int *)(B + o_ev); P.ev_green = P.ev_red + NF * S; P.ev_blue = P.ev_green + NF * S;
         P.gray_ev = (int *)(B + o_gray); P.dir = (uint8_t *)(B + o_dir);
         P.sq_dst = (const int *)(B + o_sq); P.sq_row = P.sq_dst + H;
         P.stats = (unsigned *)(B + o_stats); P.amaze_scratch = (float *)as.base; P.amaze_scratch_stride = a_stride;
-        // A batch of 8 or more goes out in parts of 4 frames: the parts' AMaZE one after the other on the caller's stream, everything
-        // behind a part's AMaZE (interpolation, alias map, blend: table- and bandwidth-bound) on a second stream, where it runs under
-        // the next part's AMaZE, which is bound by instruction issue -- what two host threads with a batch each get, for one.
+        // the parts' AMaZE one after the other on the caller's stream, the rest of each part on the second stream (dualiso_parts).
         // (The first form alternated the PARTS between the two streams.  Same dependencies for two parts, yet its speed depended on
         // the order in which the process had created its streams -- 8.5 or 9.2 ms per batch of 8, each reproducible: the tail then
         // competes with the NEXT part's AMaZE from whichever queue it happens to share, and loses where that queue is served last,
         // exactly as when the tail's stream is given low priority.  tools/hwq_probe.sh.)
-        static const bool split_on = [] { const char *e = getenv("MLVFS_AMD_DI_SPLIT"); return !e || atoi(e) != 0; }();
-        if (split_on && nframes >= 8) {
+        std::vector<DiPart> parts;
+        if (dualiso_parts(w, H, nframes, parts)) {
             struct Half {
                 hipStream_t st = nullptr; hipEvent_t fork = nullptr, amaze_a = nullptr, join = nullptr;
                 ~Half() { if (fork) (void)hipEventDestroy(fork); if (amaze_a) (void)hipEventDestroy(amaze_a); if (join) (void)hipEventDestroy(join); if (st) (void)hipStreamDestroy(st); }
@@ -647,35 +656,18 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
             static thread_local std::map<int, Half> t_half;
             Half &hf = t_half[c->dev->id];
             if (!hf.st) {
-                // (priority: a knob for experiments.  Which of the queues is served first while AMaZE workgroups wait for a free CU decides
-                // whether the tail overlaps at all)
-                static const int prio = [] { const char *e = getenv("MLVFS_AMD_DI_TAIL_PRIO"); return e ? atoi(e) : 0; }();
-                MLV_HIP(hipStreamCreateWithPriority(&hf.st, hipStreamNonBlocking, prio));
+                // (priority 0.  Which of the queues is served first while AMaZE workgroups wait for a free CU decides whether the tail
+                // overlaps at all)
+                MLV_HIP(hipStreamCreateWithPriority(&hf.st, hipStreamNonBlocking, 0));
                 MLV_HIP(hipEventCreateWithFlags(&hf.fork, hipEventDisableTiming));
                 MLV_HIP(hipEventCreateWithFlags(&hf.amaze_a, hipEventDisableTiming));
                 MLV_HIP(hipEventCreateWithFlags(&hf.join, hipEventDisableTiming));
             }
-            // frames per part: enough complete AMaZE tiles for about four rounds of k_amaze_rows' 256 workgroups (3584x1320: 282 per
-            // frame -> 4 frames; 1736x976: 84 -> 13, a batch of 8 stays whole -- in parts of 4 it took 4.4 instead of 3.9 ms)
-            const int part_env = [] { const char *e = getenv("MLVFS_AMD_DI_PART"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();   // (read per call: tests)
-            int nfx = 0, nfy = 0;
-            amaze_rows_extent(w, H, &nfx, &nfy);
-            const int per_frame = nfx * nfy > 0 ? nfx * nfy : 1;
-            const int part = part_env ? part_env : std::max(4, (1024 + per_frame - 1) / per_frame);
-            const int nparts = nframes / part > 1 ? nframes / part : 1;
             MLV_HIP(hipEventRecord(hf.fork, stream));
             MLV_HIP(hipStreamWaitEvent(hf.st, hf.fork, 0));
-            // The last part is smaller than the others (3/4 of an even share: 8 frames = 5 + 3): what follows its AMaZE -- interpolation,
-            // alias map, blend -- runs with the chip to itself, and the less of that the better (1 037 -> 1 074 conversions/s,
-            // profiles/r05/di_experiments.log).  MLVFS_AMD_DI_FIRST=n (two parts): n frames in the first one (experiments).
-            static const int first_env = [] { const char *e = getenv("MLVFS_AMD_DI_FIRST"); return e ? atoi(e) : 0; }();
-            const int even = nframes / nparts, last = nparts > 1 ? std::max(1, (3 * even + 2) / 4) : nframes, front = nframes - last;
-            for (int k = 0; k < nparts; k++) {
+            for (const DiPart &pt : parts) {
                 DiBatch bk = bt;
-                if (nparts == 1) { bk.f0 = 0; bk.nframes = nframes; }
-                else if (k == nparts - 1) { bk.f0 = front; bk.nframes = last; }
-                else { bk.f0 = (int)((long long)front * k / (nparts - 1)); bk.nframes = (int)((long long)front * (k + 1) / (nparts - 1)) - bk.f0; }
-                if (first_env > 0 && first_env < nframes && nparts == 2) { bk.f0 = k ? first_env : 0; bk.nframes = k ? nframes - first_env : first_env; }
+                bk.f0 = pt.f0; bk.nframes = pt.n;
                 rc = di_launch_amaze_interp(d_frames, bk, H, L, P, stream, hf.amaze_a, hf.st);
                 if (!rc) rc = di_launch_convert(bk, H, L, P, amaze, d_frames, hf.st);
                 if (rc) break;
@@ -713,7 +705,6 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
             printf("Deep shadows    : %.02f%%\n", s4[2] * 100.0 / (s4[2] + s4[3]));
         }
     } else MLV_HIP(hipStreamSynchronize(stream));
-    pt.mark("match + interpolation + blend");
     for (int f = 0; f < nframes; f++) {
         if (results[f] != 1) continue;
         printf("Noise level     : %.02f (20-bit), ideally %.02f\n", 8.0, 8.0);
@@ -819,6 +810,19 @@ void mlvfs_amd_amaze_rows_extent(int width, int height, int *nfx, int *nfy)
     g_amaze_rows_mode = before;
     if (nfx) *nfx = fx;
     if (nfy) *nfy = fy;
+}
+
+// Test hook, host only: how cr2hdr20_batch cuts an AMaZE batch of nframes width x height frames into parts (dualiso_parts).
+// parts[2k], parts[2k + 1]: first frame and frames of part k; *tail: the second stream is used.  Returns the number of parts, or
+// MLVFS_AMD_ERR_ARG where they do not fit max_parts.
+int mlvfs_amd_test_dualiso_parts(int width, int height, int nframes, int *parts, int max_parts, int *tail)
+{
+    if (!parts || !tail || nframes <= 0) return MLVFS_AMD_ERR_ARG;
+    std::vector<DiPart> v;
+    *tail = dualiso_parts(width, height, nframes, v) ? 1 : 0;
+    if ((int)v.size() > max_parts) return MLVFS_AMD_ERR_ARG;
+    for (size_t k = 0; k < v.size(); k++) { parts[2 * k] = v[k].f0; parts[2 * k + 1] = v[k].n; }
+    return (int)v.size();
 }
 
 // Test hook: the heads of output-less chains through k_amaze_rows.hip as well (k_amaze_rows.hip: amaze_rows_extra).  mode -1: the

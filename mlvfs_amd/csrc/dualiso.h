@@ -84,8 +84,8 @@ struct DiPlanes {
     uint16_t *over, *amap, *aux, *amap2;
     int *cells;                // [3][h/2][w/2] work planes of the chroma smoothing
     // AMaZE path only
-    float *cfa, *red, *green, *blue;   // squeezed Bayer plane and its demosaic, [h][w]
-    int *ev_red, *ev_green, *ev_blue;  // interp_raw2ev of the clamped demosaic (k_di_amaze_clamp): each is looked up by up to six pixels
+    float *cfa;                        // squeezed Bayer plane, [h][w]
+    int *ev_red, *ev_green, *ev_blue;  // interp_raw2ev of its clamped demosaic (AMaZE's output stage): each is looked up by up to six pixels
     int *gray_ev;              // raw2ev of the gray image, squeezed like the planes it comes from, [h][w]
     uint8_t *dir;              // chosen edge direction, [h][w]
     const int *sq_dst, *sq_row;        // per image row: squeezed row it is written to (-1 none) / looked up at (0 if none)
@@ -102,8 +102,8 @@ constexpr int AMAZE_TILE_FLOATS = 13 * AMAZE_TS * AMAZE_TS + 13 * AMAZE_TS * AMA
 int amaze_launch(const float *d_raw, int w, int h, float *d_red, float *d_green, float *d_blue, float *d_scratch, hipStream_t s,
                  int nframes = 1, size_t plane_stride = 0, size_t scratch_stride = 0, const int *h_of = nullptr, int h_stride = 0,
                  float *d_rows_dbg = nullptr, const int *d_r2e = nullptr, int ev_black = 0, int *d_gray = nullptr);
-// d_r2e (round 5): the three plane pointers are INT planes and take interp_raw2ev of the clamped plane values, d_gray that of the gray
-// value (what k_di_amaze_ev made of the float planes in a pass of its own: amaze_math.h, ev_of_planes)
+// d_r2e: the three plane pointers are INT planes and take interp_raw2ev of the clamped plane values, d_gray that of the gray value
+// (amaze_math.h, ev_of_planes)
 size_t amaze_scratch_bytes(int w, int h);
 // k_amaze_rows.hip: the complete tiles (the first nfx x nfy of the tile grid), row-streamed through LDS
 extern int g_amaze_rows_mode;

@@ -52,12 +52,6 @@ static_assert(AMAZE_TILE_FLOATS == 13 * TT + 13 * HALF, "scratch layout");
 //     walked by ONE workgroup in the reference's order (`rows_per_wg`, chain_len = tiles_x).
 // Not reproduced: what equal-size neighbours leave INSIDE each other's written range; the only reads of that kind
 // are the overrun lanes of the pmwt sweep, which are 0 and provably stay 0 unless the garbage case above applies.
-#ifdef AMAZE_DIAG
-__device__ unsigned long long g_amaze_stamps[16];
-#define AMZ_STAMP(k) do { if (blockIdx.x == 0 && threadIdx.x == 0 && tk == 0) g_amaze_stamps[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define AMZ_STAMP(k) do { } while (0)
-#endif
 __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, int w, int h, float *__restrict__ red,
                                                  float *__restrict__ green_out, float *__restrict__ blue, float *__restrict__ scratch,
                                                  int tiles_x, int row0, int wgs_per_row, int chain_len, int rows_per_wg, int copy_from,
@@ -104,7 +98,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     const float *c = t.cfa;
     auto RAW = [&](int y, int x) -> float { return x < w ? raw[(size_t)y * w + x] : 0.0f; };   // the reference's rows are zero padded
 
-    AMZ_STAMP(0);
     // ---- tile load + mirrored apron (:361-469; w % 4 == 0, so the vector groups of the loader never straddle a region).
     // The fills address the tile by FLAT index and run in the reference's order, because they overlap: a right-edge
     // fill that starts less than 16 columns before the end of a tile row (ccmax + 16 > 160) runs on into the first
@@ -171,7 +164,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     for (int n = tid; n < HALF; n += nt) { s_nyq[n] = 0; t.rbint[n] = 0.0f; }
     __syncthreads();
 
-    AMZ_STAMP(1);
     // ---- gradients (:537-613)
     {
         const int cw = (cc1 + 3) & ~3, rows = rr1 - 4;
@@ -195,7 +187,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     }
     __syncthreads();
 
-    AMZ_STAMP(2);
     // ---- directional colour differences (:622-675)
     {
         const float *d0 = t.dw0, *d1 = t.dw1;
@@ -226,7 +217,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     }
     __syncthreads();
 
-    AMZ_STAMP(3);
     // ---- refinement of the colour differences (:766-801)
     {
         const int lanes = 4 * iters(4, cc1 - 4, 4), rows = rr1 - 8;
@@ -293,7 +283,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     __syncthreads();
     const float *hc = t.hcd2, *vc = t.vcd;
 
-    AMZ_STAMP(4);
     // ---- horizontal/vertical weight (:881-925) and the Nyquist texture test (:969-996)
     int flagged = 0;
     {
@@ -342,7 +331,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     flagged = __syncthreads_or(flagged);
 
     if (flagged) {
-        AMZ_STAMP(5);
         // ---- majority vote in raster order (:998-1010) as wavefronts of constant 2*row + col
         const int tau_lo = 2 * 8 + 8, tau_hi = 2 * (rr1 - 9) + (cc1 - 9);
         for (int tau = tau_lo; tau <= tau_hi; tau++) {
@@ -359,7 +347,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
             }
             __syncthreads();
         }
-        AMZ_STAMP(6);
         // ---- area interpolation in Nyquist regions (:1016-1044)
         const int rows = rr1 - 16, sites_max = iters(8, cc1 - 8, 2);
         for (int n = tid; n < rows * sites_max; n += nt) {
@@ -384,7 +371,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
         __syncthreads();
     }
 
-    AMZ_STAMP(7);
     // ---- G at R/B sites (:1046-1073): the weight update reads the updated row above -> one row per barrier in LDS
     for (int n = tid; n < HALF; n += nt) s_w[n] = t.hvwt[n];
     __syncthreads();
@@ -440,7 +426,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
         }
     }
 
-    AMZ_STAMP(8);
     // ---- diagonal interpolation (:1112-1276)
     {
         const float G_EVEN[2] = { 0.13719494435797422f, 0.05640252782101291f };
@@ -531,7 +516,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     }
     __syncthreads();
 
-    AMZ_STAMP(9);
     // ---- chrominance (:1345-1395)
     {
         const int rows = iters(13, rr1 - 12, 2), sites = iters(13, cc1 - 12, 2);
@@ -561,7 +545,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
     }
     __syncthreads();
 
-    AMZ_STAMP(10);
     // ---- the three planes of the tile interior (:1397-1470)
     {
         const float *hw = t.hvwt, *g = t.green;
@@ -594,7 +577,6 @@ __global__ __launch_bounds__(1024) void k_amaze(const float *__restrict__ raw, i
         }
     }
     __syncthreads();
-    AMZ_STAMP(11);
     }   // tiles of this workgroup
 }
 
@@ -606,12 +588,11 @@ int amaze_launch(const float *d_raw, int w, int h, float *d_red, float *d_green,
     const int step = AMAZE_TS - 32;
     const int tiles_x = (w + 16 + step - 1) / step, tiles_y = (h + 16 + step - 1) / step;
     const int cc1_last = w + 16 - (-16 + (tiles_x - 1) * step), rr1_last = h + 16 - (-16 + (tiles_y - 1) * step);
-    static const int threads = [] { const char *e = getenv("MLVFS_AMD_AMAZE_THREADS"); const int v = e ? atoi(e) : 1024; return v >= 64 && v <= 1024 ? v / 64 * 64 : 1024; }();
     int nfx = 0, nfy = 0;
     amaze_rows_extent(w, h, &nfx, &nfy);                                         // the complete tiles go through LDS (k_amaze_rows.hip)
     const int dead_rows = d_rows_dbg ? 0 : amaze_rows_extra(w, h, nframes);               // and so do the heads of chains that have no output
     auto launch = [&](int row0, int nrows, int wgs_per_row, int chain_len, int rows_per_wg, int copy_from) {
-        hipLaunchKernelGGL(k_amaze, dim3(nrows * wgs_per_row, nframes), dim3(threads), 0, s, d_raw, w, h, d_red, d_green, d_blue, d_scratch, tiles_x,
+        hipLaunchKernelGGL(k_amaze, dim3(nrows * wgs_per_row, nframes), dim3(1024), 0, s, d_raw, w, h, d_red, d_green, d_blue, d_scratch, tiles_x,
                            row0, wgs_per_row, chain_len, rows_per_wg, copy_from, plane_stride, scratch_stride, h_of, h_stride, nfx, nfy, dead_rows, d_r2e, ev_black, d_gray);
     };
     // The complete tiles run on a side stream, next to this stream's launches for the incomplete ones: those are few workgroups in
@@ -655,13 +636,6 @@ int amaze_launch(const float *d_raw, int w, int h, float *d_red, float *d_green,
         MLV_HIP(hipEventRecord(side->done, side->st));
         return MLVFS_AMD_OK;
     };
-    static const bool rows_only = [] { const char *e = getenv("MLVFS_AMD_AMAZE_ROWS_ONLY"); return e && atoi(e); }();      // timing experiments
-    if (rows_only && nfx) {
-        const int rc = rows_now();
-        if (rc) return rc;
-        MLV_HIP(hipStreamWaitEvent(s, side->done, 0));
-        return MLVFS_AMD_OK;
-    }
     // incomplete tiles at the right end of a row, chained behind the last complete one
     const int incomplete_x = cc1_last >= AMAZE_TS ? 0 : (cc1_last < 32 ? 2 : 1);
     if (tiles_x < incomplete_x + 1 || tiles_x < 3) {
@@ -686,22 +660,6 @@ int amaze_launch(const float *d_raw, int w, int h, float *d_red, float *d_green,
     { const int rc = rows_now(); if (rc) return rc; }
     if (side && nfx) MLV_HIP(hipStreamWaitEvent(s, side->done, 0));
     MLV_HIP(hipGetLastError());
-#ifdef AMAZE_DIAG
-    {
-        static int shown = 0;
-        if (shown++ == 3) {
-            unsigned long long st[16];
-            hipStreamSynchronize(s);
-            hipMemcpyFromSymbol(st, HIP_SYMBOL(g_amaze_stamps), sizeof st);
-            const char *names[12] = { "load + apron", "gradients", "directional differences", "refinement (vcd walk)", "hv weight + nyquist test",
-                                      "majority vote", "area interpolation", "G at R/B (row by row)", "diagonal interpolation (row by row)",
-                                      "chrominance", "output planes", "" };
-            fprintf(stderr, "AMAZE_DIAG cycles of workgroup 0, first tile (s_memtime):");
-            for (int k = 0; k + 1 < 12; k++) fprintf(stderr, "\n  %-36s %8lld", names[k], (long long)(st[k + 1] - st[k]));
-            fprintf(stderr, "\n  total %lld\n", (long long)(st[11] - st[0]));
-        }
-    }
-#endif
     return MLVFS_AMD_OK;
 }
 

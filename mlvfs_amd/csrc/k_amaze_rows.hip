@@ -28,8 +28,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <vector>
-#include <algorithm>
 
 namespace mlv {
 
@@ -61,16 +59,12 @@ enum { P_LOAD, P_DIRDIFF, P_NYQTEST, P_HVWT, P_AREA, P_CURV, P_CGRAD, P_PMSWEEP,
 constexpr int LAG[NPASS] = { 0, 3, 6, 7, 11, 13, 9, 12, 17,   1, 3, 4, 7, 12, 10, 12, 14, 18 };
 constexpr int LAG_MAX = 18;
 #define IT(p, c) ((p) * 8 + (c))
-// Which wave runs which items is decided on the host (amaze_rows_launch): the items of a phase, longest first, each to the wave with
-// the least work so far (measured cycles per item below, MLVFS_AMD_AMAZE_ROWS_PROF=2; taking items from a counter in LDS balanced
-// no better and cost 54 same-address atomics per step).  AREA is priced as if idle: where the Nyquist test fired it is by far the
-// longest item, elsewhere it returns at once.  LOAD keeps the next row pair in registers across steps: it must stay with one wave.
-constexpr int NCHUNKS[NPASS] = { 1, 5, 3, 3, 3, 3, 3, 1, 3,   5, 5, 5, 1, 1, 3, 3, 3, 4 };
-constexpr int COST[NPASS] = { 1000, 1000, 1000, 1000, 1000, 1000, 1000, 1000, 1000,   1000, 1000, 1000, 1000, 1000, 1000, 1000, 1000, 1000 };
-// The deal in use: found by local search (moves and swaps of items between waves; tools/amaze_rows_assign_search.py), first with the
-// kernel's time on 2 254 unflagged tiles as the objective (3.26 ms where the deal by item count takes 3.71 and the one by measured
-// cycles per item 4.07), then with a batch of 8 dual-ISO conversions (9.15 -> 8.92 ms, best of 5; after the analysis kernel's change 8.78 -> 8.67; 760 candidates in all).  What an item costs depends on what runs
-// beside it on its SIMD, and no cost table captures that.
+// Which wave runs which items: TUNED, uploaded to c_desc once per device (amaze_rows_launch).  Found by local search (moves and swaps
+// of items between waves), first with the kernel's time on 2 254 unflagged tiles as the objective (3.26 ms where the deal by item
+// count takes 3.71 and the one by measured cycles per item 4.07), then with a batch of 8 dual-ISO conversions (9.15 -> 8.92 ms, best
+// of 5; after the analysis kernel's change 8.78 -> 8.67; 760 candidates in all).  What an item costs depends on what runs beside it
+// on its SIMD, and no cost table captures that; taking items from a counter in LDS balanced no better and cost 54 same-address
+// atomics per step.  LOAD keeps the next row pair in registers across steps: it must stay with one wave.
 constexpr unsigned long long TUNED[2][16] = {
     { 0xffffffff06100c38ull, 0xffffffff030a0612ull, 0xffffffff03090d28ull, 0xffffffffffff030cull, 0xffffffffffff030bull, 0xffffffff00000931ull, 0xffffffff07181140ull, 0xffffffff06110b21ull, 0xffffffff11420d29ull, 0xffffffff09320b22ull, 0xffffffffffff0308ull, 0xffffffff0d2a071aull, 0xffffffffffff1141ull, 0xffffffffffff0b20ull, 0xffffffffffff0930ull, 0xffffffffffff0719ull },
     { 0xffffffff0c680e82ull, 0xffffffff0a700352ull, 0xffffffff0a71014aull, 0xffffffffffff0a72ull, 0xffff0148014b0351ull, 0xffffffff0c790e80ull, 0xffff045a0c7a0354ull, 0xffffffff03500353ull, 0xffffffffffff0e81ull, 0xffffffff0c780149ull, 0xffffffff12880458ull, 0xffffffff12890459ull, 0xffffffffffff128aull, 0xffffffff0760128bull, 0xffffffff014c045cull, 0xffffffffffff045bull } };
@@ -180,7 +174,7 @@ template <bool DBG>
 __global__ __launch_bounds__(1024) void k_amaze_rows(const float *__restrict__ raw, int w, int h, float *__restrict__ red,
                                                       float *__restrict__ green_out, float *__restrict__ blue, int nfx, int ntiles, int nrect,
                                                       size_t plane_stride, const int *__restrict__ h_of, int h_stride,
-                                                      float *__restrict__ dbg, unsigned long long *__restrict__ prof, unsigned skip_mask, int *__restrict__ tile_ctr,
+                                                      float *__restrict__ dbg, int *__restrict__ tile_ctr,
                                                       const int *__restrict__ r2e, int ev_black, int *__restrict__ gray)
 {
     __shared__ float sm[LDS_FLOATS];                          // static: row offsets are compile-time constants (a dynamic array costs an add each)
@@ -249,8 +243,6 @@ __global__ __launch_bounds__(1024) void k_amaze_rows(const float *__restrict__ r
     __syncthreads();
 
     const unsigned long long desc_a = c_desc[0][wave], desc_b = c_desc[1][wave];       // this wave's items
-    unsigned long long prof_busy[2] = { 0, 0 }, prof_wait[2] = { 0, 0 }, prof_items[2] = { 0, 0 }, prof_n = 0, t_phase = 0;
-    const bool prof_detail = prof && prof[2 * NPASS + 5 * 16] != 0;
     for (int s = 0;; s++) {
         const int nq = __builtin_amdgcn_readfirstlane(ctl[4]);         // (written in phase A of an earlier step, if at all)
         if (s - LAG_MAX >= nq) break;
@@ -261,10 +253,8 @@ __global__ __launch_bounds__(1024) void k_amaze_rows(const float *__restrict__ r
                 const unsigned d16 = (unsigned)((phase ? desc_b : desc_a) >> (16 * it)) & 0xFFFFu;
                 if (d16 == 0xFFFFu) break;
                 const int pass = (d16 & 255u) >> 3, ck = d16 & 7u;
-                if (skip_mask >> pass & 1u) continue;                              // (timing experiments only: MLVFS_AMD_AMAZE_ROWS_SKIP)
                 const int q = s - (int)(d16 >> 8);
                 if (q < 0 || q >= nq) continue;
-                const unsigned long long t_item = prof_detail ? __builtin_amdgcn_s_memtime() : 0;
                 const int p = q % NP;
                 unsigned tabv;                                                    // lane j: byte offset of pair j of this pass's table (rows of pair q)
                 {
@@ -862,26 +852,9 @@ __global__ __launch_bounds__(1024) void k_amaze_rows(const float *__restrict__ r
                 } break;
                 default: break;
                 }
-                if (prof_detail && s >= 2 * LAG_MAX && s < nq && blockIdx.x == 0 && blockIdx.y == 0) {   // steady state: cycles per item
-                    const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_item;
-                    prof_items[phase] += dt;
-                    if (lane == 0) { atomicAdd(&prof[2 * pass], dt); atomicAdd(&prof[2 * pass + 1], 1ull); }
-                }
             }
-            const unsigned long long t_bar = prof ? __builtin_amdgcn_s_memtime() : 0;
-            if (!(skip_mask >> 31)) __syncthreads();                               // (bit 31: timing of the empty loop without its barriers)
-            if (prof && s >= 2 * LAG_MAX && s < nq) {
-                const unsigned long long t_now = __builtin_amdgcn_s_memtime();
-                prof_busy[phase] += t_bar - t_phase; prof_wait[phase] += t_now - t_bar; prof_n++;
-                t_phase = t_now;
-            } else if (prof) t_phase = __builtin_amdgcn_s_memtime();
+            __syncthreads();
         }
-    }
-    if (prof && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && prof_n) {     // per wave of workgroup 0: busy A, wait A, busy B, wait B, phases
-        unsigned long long *o = prof + 2 * NPASS + 5 * wave;
-        o[0] = prof_busy[0]; o[1] = prof_wait[0]; o[2] = prof_busy[1]; o[3] = prof_wait[1];
-        if (prof_detail) { o[1] = prof_items[0]; o[3] = prof_items[1]; }                // (detail mode: the items' own time in place of the waits)
-        o[4] = prof_n | (unsigned long long)__builtin_amdgcn_s_getreg(4 | (4 << 6) | (1 << 11)) << 56;       // HW_ID.SIMD_ID
     }
 }
 #undef C
@@ -941,34 +914,6 @@ int amaze_rows_extra(int w, int h, int nframes)
 int amaze_rows_launch(const float *d_raw, int w, int h, float *d_red, float *d_green, float *d_blue, hipStream_t s, int nframes,
                       size_t plane_stride, const int *h_of, int h_stride, float *d_dbg, int *d_ctr, const int *d_r2e, int ev_black, int *d_gray)
 {
-    // MLVFS_AMD_AMAZE_ROWS_PROF=1: cycles per item of each pass and per wave at the barriers (workgroup 0, steady state), printed at exit
-    static unsigned long long *d_prof = [] {
-        unsigned long long *p = nullptr;
-        const char *e = getenv("MLVFS_AMD_AMAZE_ROWS_PROF");
-        if (e && atoi(e)) {
-            constexpr int N = 2 * NPASS + 5 * 16 + 1;
-            if (hipMalloc(&p, 8 * N) != hipSuccess) return (unsigned long long *)nullptr;
-            unsigned long long init[N] = {};
-            init[N - 1] = atoi(e) > 1;                                     // 2: cycles per item of each pass as well (atomics: slower)
-            (void)hipMemcpy(p, init, sizeof init, hipMemcpyHostToDevice);
-            static unsigned long long *keep; keep = p;
-            atexit([] {
-                unsigned long long hst[N];
-                if (hipMemcpy(hst, keep, sizeof hst, hipMemcpyDeviceToHost) != hipSuccess) return;
-                const char *names[NPASS] = { "LOAD", "DIRDIFF", "NYQTEST", "HVWT", "AREA", "CURV", "CGRAD", "PMSWEEP", "CHROMA", "GRAD", "HREF", "VWALK", "VOTE",
-                                             "HVSWEEP", "DIAG", "RBINT", "GFINAL", "OUTPUT" };
-                for (int k = 0; k < NPASS; k++)
-                    if (hst[2 * k + 1]) fprintf(stderr, "AMAZE_ROWS_PROF %-8s %8.0f cycles per item (%llu items)\n", names[k], (double)hst[2 * k] / hst[2 * k + 1], hst[2 * k + 1]);
-                for (int k = 0; k < 16; k++) {
-                    const unsigned long long *o = hst + 2 * NPASS + 5 * k;
-                    const unsigned long long n = o[4] & 0xFFFFFFFFFFFFFFull;
-                    if (n) fprintf(stderr, "AMAZE_ROWS_PROF wave %2d (SIMD %d): phase A busy %6.0f wait %6.0f, phase B busy %6.0f wait %6.0f cycles per step\n", k,
-                                   (int)(o[4] >> 56), 2.0 * o[0] / n, 2.0 * o[1] / n, 2.0 * o[2] / n, 2.0 * o[3] / n);
-                }
-            });
-        }
-        return p;
-    }();
     int nfx, nfy;
     amaze_rows_extent(w, h, &nfx, &nfy);
     if (!nfx) return MLVFS_AMD_OK;
@@ -980,64 +925,23 @@ int amaze_rows_launch(const float *d_raw, int w, int h, float *d_red, float *d_g
         std::lock_guard<std::mutex> lk(mu);
         if (dev < 64 && !g_tab_ready[dev]) {
             MLV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_tables), &H_TABLES, sizeof H_TABLES));
-            {   // items to waves: longest first, each to the wave with the least work so far
-                int cost[NPASS];
-                for (int k = 0; k < NPASS; k++) cost[k] = COST[k];
-                if (const char *e = getenv("MLVFS_AMD_AMAZE_ROWS_COSTS")) {          // tuning: NPASS comma separated cycle counts
-                    int k = 0;
-                    for (const char *q = e; *q && k < NPASS; k++) { cost[k] = atoi(q); while (*q && *q != ',') q++; if (*q) q++; }
-                }
-                unsigned long long desc[2][16];
-                for (int ph = 0; ph < 2; ph++) {
-                    struct Item { int code, cost; };
-                    std::vector<Item> items;
-                    for (int pass = ph ? P_GRAD : 0; pass < (ph ? NPASS : P_GRAD); pass++)
-                        for (int ck = 0; ck < NCHUNKS[pass]; ck++) items.push_back({ IT(pass, ck), cost[pass] });
-                    std::stable_sort(items.begin(), items.end(), [](const Item &x, const Item &y) { return x.cost > y.cost; });
-                    int load[16] = {}, cnt[16] = {}, simd[4] = {};                     // waves w, w + 4, w + 8, w + 12 share a SIMD: its sum counts too
-                    for (int w2 = 0; w2 < 16; w2++) desc[ph][w2] = ~0ull;
-                    for (const Item &it : items) {
-                        int best = -1;
-                        for (int w2 = 0; w2 < 16; w2++)
-                            if (cnt[w2] < 4 && (best < 0 || 2 * load[w2] + simd[w2 & 3] < 2 * load[best] + simd[best & 3])) best = w2;
-                        simd[best & 3] += it.cost;
-                        const unsigned long long v = (unsigned)it.code | (unsigned)LAG[it.code >> 3] << 8;
-                        desc[ph][best] = (desc[ph][best] & ~(0xFFFFull << (16 * cnt[best]))) | v << (16 * cnt[best]);
-                        cnt[best]++; load[best] += it.cost;
-                    }
-                }
-                if (!getenv("MLVFS_AMD_AMAZE_ROWS_COSTS"))
-                    for (int ph = 0; ph < 2; ph++)
-                        for (int w2 = 0; w2 < 16; w2++) desc[ph][w2] = TUNED[ph][w2];
-                if (const char *e = getenv("MLVFS_AMD_AMAZE_ROWS_ASSIGN")) {         // tuning: the 32 descriptors themselves, hex, comma separated
-                    int k = 0;
-                    for (const char *q = e; *q && k < 32; k++) { desc[k / 16][k % 16] = strtoull(q, nullptr, 16); while (*q && *q != ',') q++; if (*q) q++; }
-                }
-                if (getenv("MLVFS_AMD_AMAZE_ROWS_SHOW")) {
-                    for (int ph = 0; ph < 2; ph++)
-                        for (int w2 = 0; w2 < 16; w2++) fprintf(stderr, "%016llx%s", desc[ph][w2], ph == 1 && w2 == 15 ? "\n" : ",");
-                }
-                MLV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_desc), desc, sizeof desc));
-            }
+            MLV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_desc), TUNED, sizeof TUNED));
             hipDeviceProp_t pr;
             MLV_HIP(hipGetDeviceProperties(&pr, dev));
             cus[dev] = pr.multiProcessorCount;
             g_tab_ready[dev] = true;
         }
     }
-    static const unsigned skip = [] { const char *e = getenv("MLVFS_AMD_AMAZE_ROWS_SKIP"); return e ? (unsigned)strtoul(e, nullptr, 16) : 0u; }();
     const int nrect = nfx * nfy, ntiles = nrect + (d_dbg ? 0 : amaze_rows_extra(w, h, nframes));       // (the debug dump is laid out for the block only)
     // one workgroup per CU (the rings fill its LDS); the frames of a batch share the CUs
     int per_frame = (dev < 64 && cus[dev] ? cus[dev] : 256) / (nframes > 0 ? nframes : 1);
-    static const int cap = [] { const char *e = getenv("MLVFS_AMD_AMAZE_ROWS_WGS"); return e ? atoi(e) : 0; }();    // tests: few workgroups, many tiles each
-    if (cap > 0 && per_frame > cap) per_frame = cap;
     per_frame = per_frame < 1 ? 1 : (per_frame > ntiles ? ntiles : per_frame);
     if (d_dbg)
         hipLaunchKernelGGL(k_amaze_rows<true>, dim3(per_frame, nframes), dim3(1024), 0, s, d_raw, w, h, d_red, d_green, d_blue, nfx,
-                           ntiles, nrect, plane_stride, h_of, h_stride, d_dbg, d_prof, skip, d_ctr, d_r2e, ev_black, d_gray);
+                           ntiles, nrect, plane_stride, h_of, h_stride, d_dbg, d_ctr, d_r2e, ev_black, d_gray);
     else
         hipLaunchKernelGGL(k_amaze_rows<false>, dim3(per_frame, nframes), dim3(1024), 0, s, d_raw, w, h, d_red, d_green, d_blue, nfx,
-                           ntiles, nrect, plane_stride, h_of, h_stride, d_dbg, d_prof, skip, d_ctr, d_r2e, ev_black, d_gray);
+                           ntiles, nrect, plane_stride, h_of, h_stride, d_dbg, d_ctr, d_r2e, ev_black, d_gray);
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;
 }

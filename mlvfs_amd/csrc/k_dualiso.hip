@@ -12,8 +12,8 @@
 //                   (match_exposures, :650-722)
 //   k_di_score      RANSAC-like score of every candidate slope (:752-772)
 //   k_di_match      14 -> 20 bit and per-pixel exposure correction in double (:781-803, :825-837)
-//   k_di_match (with the squeeze), k_di_amaze_ev, k_di_edge_dir   the AMaZE-based interpolator around k_amaze.hip
-//                   (:954-1173); k_di_interp<true> then interpolates along the chosen edge direction (:1181-1208)
+//   k_di_match (with the squeeze), k_di_edge_dir   the AMaZE-based interpolator around k_amaze.hip, whose output stage
+//                   writes the EV planes (:954-1173); k_di_interp<true> then interpolates along the chosen edge direction (:1181-1208)
 //   k_di_interp     mean23 + borders + full-res pick + half-res mix + overexposure flag +
 //                   alias-map error, fused per pixel (:1231-1380, :1588-1612, :1404-1418, :1620-1626)
 //   k_di_alias_rank 6th largest of 37 neighbours (:1423-1443)
@@ -32,18 +32,6 @@ namespace mlv {
 #define DI_EVR 32768
 
 __device__ __forceinline__ int di_bright(const DiParams &p, int y) { return (p.is_bright_bits >> (y & 3)) & 1; }
-
-// Which 256-pixel piece of a pass a workgroup of the grid-stride kernels takes.  The dispatcher deals workgroups b, b + 1, ... to the
-// chip's eight XCDs in turn, each with an L2 of its own: with piece = b the fourteen pieces of a 3584-pixel row, and the rows two
-// above and below that every one of these kernels also reads, lie in eight different L2s and every line is fetched several times.
-// Workgroup b takes piece (b % 8) * (G / 8) + b / 8 instead (G = the grid's size, a multiple of 8: flat_grid): an XCD's workgroups
-// cover one band of consecutive rows per pass, its neighbours' rows are in its own L2.  OFF by default (flat_grid: measured, slower);
-// MLVFS_AMD_DI_XCD=1 in the launcher's environment switches it on (a grid that is no multiple of 8 keeps the plain order).
-__device__ __forceinline__ unsigned di_xcd_block()
-{
-    const unsigned b = blockIdx.x, G = gridDim.x;
-    return (G & 7u) ? b : (b & 7u) * (G >> 3) + (b >> 3);
-}
 
 // The frame of a batch this workgroup works on -- blockIdx.y, or blockIdx.z for the kernels whose grid is two-dimensional -- and
 // its parameters (dualiso.h: DiBatch); false: the batch leaves this frame alone.
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(256) void k_di_match(const uint16_t *__restrict__ i
     if (ev) ev += (size_t)f * bt.S;
     const size_t n = (size_t)p.w * p.h;
     const double a = p.a, b20 = p.b20;
-    for (size_t i = (size_t)di_xcd_block() * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         int v = (int)(((uint32_t)img[i] << 6) & 0xFFFFFu);
         if (v != 0) {
             const int y = (int)(i / p.w);
@@ -379,17 +367,16 @@ __constant__ signed char k_edge_dirs[11][8] = {
     { 2, 2, 1, 1, -2, -2, -3, -3 }, { 3, 2, 1, 1, -3, -2, -4, -3 }, { 4, 2, 2, 1, -4, -2, -6, -3 } };
 
 struct DiAmazeIn {              // inputs of the edge-directed interpolation (null planes = mean23)
-    const int *red, *green, *blue;      // interp_raw2ev of the clamped demosaic (k_di_amaze_clamp)
+    const int *red, *green, *blue;      // interp_raw2ev of the clamped demosaic (AMaZE's output stage)
     const uint8_t *dir;
     const int *sq_row;
     size_t sq_stride;           // ints between the frames' squeezed-row maps
 };
 
-// one pixel of the interpolation and everything behind it (the body of k_di_interp).  DIR >= 0: the edge direction comes with the
-// call (k_di_edge_interp), else from A.dir
+// one pixel of the interpolation and everything behind it (the body of k_di_interp)
 template <bool AMAZE>
 __device__ __forceinline__ void di_interp_pixel(const DiParams &p, const DiLuts &L, const DiAmazeIn &A, const uint32_t *__restrict__ raw,
-                                                size_t i, int x, int y, int dir_given,
+                                                size_t i, int x, int y,
                                                 uint32_t *__restrict__ dark, uint32_t *__restrict__ bright,
                                                 uint32_t *__restrict__ fullres, uint32_t *__restrict__ halfres,
                                                 uint16_t *__restrict__ over, uint16_t *__restrict__ amap, bool ev_out, double k_lo, double k_hi)
@@ -407,7 +394,7 @@ __device__ __forceinline__ void di_interp_pixel(const DiParams &p, const DiLuts 
     else if (AMAZE) {                                         // hdr.c:940-952, 1181-1208
         const int s = (di_bright(p, y) == di_bright(p, y + 1)) ? -1 : 1;
         const int *plane = (y & 1) == 0 ? ((x & 1) == 0 ? A.red : A.green) : ((x & 1) == 0 ? A.green : A.blue);
-        const int d = dir_given >= 0 ? dir_given : (int)A.dir[i];
+        const int d = A.dir[i];
         const int dd[3] = { d, min(d + 1, 10), max(d - 1, 0) };
         // of a direction's table row only a.x and b.x vary (a.y = 1, b.y = -2 for all eleven, hdr.c:916-938): two rows of the
         // plane for the three directions, the column offsets from two packed constants instead of twelve byte loads per pixel
@@ -464,36 +451,11 @@ __global__ __launch_bounds__(256) void k_di_interp(const uint32_t *__restrict__ 
     const int w = p.w, h = p.h;
     const size_t n = (size_t)w * h;
     const double k_lo = di_mix_weight(p, 0.0), k_hi = di_mix_weight(p, p.overlap);
-    for (size_t i = (size_t)di_xcd_block() * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        di_interp_pixel<AMAZE>(p, L, A, raw, i, (int)(i % w), (int)(i / w), -1, dark, bright, fullres, halfres, over, amap, ev_out, k_lo, k_hi);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        di_interp_pixel<AMAZE>(p, L, A, raw, i, (int)(i % w), (int)(i / w), dark, bright, fullres, halfres, over, amap, ev_out, k_lo, k_hi);
 }
 
 // ------------------------------------------------------------------ AMaZE-based interpolation, hdr.c:954-1229
-// undo the green scaling, clamp (hdr.c:1041-1050); what leaves this kernel are the table values everything downstream looks up:
-// raw2ev of the three clamped planes (the edge-directed interpolation, hdr.c:1181-1208: up to six pixels ask for each) and raw2ev of
-// the gray image (hdr.c:1055-1059, 1157-1168) -- still squeezed: k_di_edge_dir de-squeezes through the row map when it stages its rows
-__global__ __launch_bounds__(256) void k_di_amaze_ev(const float *__restrict__ red, const float *__restrict__ green, const float *__restrict__ blue,
-                                                     DiBatch bt, const int *__restrict__ r2e, int *__restrict__ ev_red,
-                                                     int *__restrict__ ev_green, int *__restrict__ ev_blue, int *__restrict__ gray_sq)
-{
-    int f; DiParams p;
-    if (!di_frame<1>(bt, f, p)) return;
-    red += (size_t)f * bt.S; green += (size_t)f * bt.S; blue += (size_t)f * bt.S;
-    ev_red += (size_t)f * bt.S; ev_green += (size_t)f * bt.S; ev_blue += (size_t)f * bt.S; gray_sq += (size_t)f * bt.S;
-    const size_t n = (size_t)p.w * p.h;
-    const int black = p.black20;
-    // (four pixels per thread -- float4 in, int4 out, sixteen look-ups in flight -- made this kernel 10 % shorter and the batch of 8
-    // 4.5 % LONGER, three rounds round-robin: it runs beside AMaZE's kernels on the other stream and took more of the chip from them;
-    // profiles/r04/ab_di_bench.log)
-    for (size_t i = (size_t)di_xcd_block() * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float fb = (float)black, hi = 1048575.0f;
-        const float g = (green[i] - fb) * 2.0f + fb, r = red[i], b = blue[i];
-        const float gc = g < hi ? (g > 0.0f ? g : 0.0f) : hi, rc = r < hi ? (r > 0.0f ? r : 0.0f) : hi, bc = b < hi ? (b > 0.0f ? b : 0.0f) : hi;
-        ev_green[i] = r2e[(int)gc]; ev_red[i] = r2e[(int)rc]; ev_blue[i] = r2e[(int)bc];
-        gray_sq[i] = r2e[(unsigned)(gc / 2 + rc / 4 + bc / 4)];
-    }
-}
-
 // best of 11 edge directions where the interpolation has to be good (hdr.c:1096-1173)
 // A workgroup owns 256 pixels of one row.  All eleven directions compare the same four rows (y + 2s, y + s, y - 2s, y - 3s) at
 // column shifts within +-11: the rows' 278 values are staged in LDS once (only when a pixel of the segment searches at all),
@@ -580,92 +542,6 @@ __global__ __launch_bounds__(256) void k_di_edge_dir(const uint32_t *__restrict_
     }
 }
 
-// k_di_edge_dir and k_di_interp<true> in one (round 5): the direction a pixel's search finds goes straight into its interpolation --
-// no direction plane, one pass over the matched frame instead of two, and the search's arithmetic runs beside the interpolation's
-// table look-ups in the same workgroup
-__global__ __launch_bounds__(256, 4) void k_di_edge_interp(const uint32_t *__restrict__ raw, const int *__restrict__ gray_sq, DiBatch bt,
-                                                        const int *__restrict__ sq_row, size_t sq_stride, int fullres_thr,
-                                                        unsigned *__restrict__ stats, DiLuts L, DiAmazeIn A,
-                                                        uint32_t *__restrict__ dark, uint32_t *__restrict__ bright,
-                                                        uint32_t *__restrict__ fullres, uint32_t *__restrict__ halfres,
-                                                        uint16_t *__restrict__ over, uint16_t *__restrict__ amap, bool ev_out)
-{
-    constexpr int REACH = 11, SPAN = 256 + 2 * REACH, BIAS = 10 * DI_EVR;        // raw2ev >= -10 EV
-    __shared__ unsigned s_rows[4][SPAN];
-    int f; DiParams p;
-    if (!di_frame<2>(bt, f, p)) return;
-    raw += (size_t)f * bt.S; gray_sq += (size_t)f * bt.S; sq_row += (size_t)f * sq_stride;
-    {
-        const size_t o = (size_t)f * bt.S;
-        dark += o; bright += o; fullres += o; halfres += o; over += o;
-        if (amap) amap += o;
-        A.red += o; A.green += o; A.blue += o; A.sq_row = sq_row;
-    }
-    const double k_lo = di_mix_weight(p, 0.0), k_hi = di_mix_weight(p, p.overlap);
-    stats += ((size_t)f * DI_STAT_SLOTS + ((blockIdx.x + blockIdx.y) & (DI_STAT_SLOTS - 1))) * 4;
-    const int w = p.w, h = p.h, x0 = blockIdx.x * 256, x = x0 + (int)threadIdx.x;
-    unsigned n_search = 0, n_plain = 0;                                          // this lane's pixels, bright rows in the low half, dark rows << 16
-    // (consecutive rows per workgroup, unlike k_di_edge_dir's stride of gridDim.y: the rows of the planes and of the gray image that
-    // one row reads are the next row's too -- with the stride the kernel fetched 582 MB per frame, 136 more than the two kernels it replaces)
-    const int rows_per = (h + (int)gridDim.y - 1) / (int)gridDim.y;
-    for (int y = (int)blockIdx.y * rows_per, y_end = min(y + rows_per, h); y < y_end; y++) {                            // (a band of rows per workgroup: 4 atomics per workgroup, not per row)
-    const size_t i = (size_t)y * w + x;
-    const int br = di_bright(p, y);
-    bool search = false;
-    if (x >= 5 && x < w - 5 && y >= 5 && y < h - 5) {
-        const int v = (int)raw[i];
-        search = br ? !(v < p.white_darkened) : v < fullres_thr;                  // !(fullres_curve[v] > 0.8)
-        if (search) n_search += br ? 1u : 0x10000u; else n_plain += br ? 1u : 0x10000u;
-    }
-    int best = 5;
-    if (__syncthreads_or(search)) {
-        const int s = (br == di_bright(p, y + 1)) ? -1 : 1;
-        for (int k = threadIdx.x; k < 4 * SPAN; k += 256) {
-            const int rr = k / SPAN, cc = k - rr * SPAN;
-            const int row = y + (rr == 0 ? 2 : rr == 1 ? 1 : rr == 2 ? -2 : -3) * s;
-            int gy = row, gx = x0 + cc - REACH;                                  // the reference indexes the gray image flat: columns off
-            if (gx < 0) { gy--; gx += w; }                                       // the row's ends are the neighbouring rows'
-            while (gx >= w && gy < h - 1) { gy++; gx -= w; }
-            gx = gx < w ? gx : w - 1;                                            // (beyond the image's last pixel: nobody reads it)
-            s_rows[rr][cc] = (unsigned)(gray_sq[(size_t)sq_row[gy] * w + gx] + BIAS);    // de-squeezed here (hdr.c:1055-1059)
-        }
-        __syncthreads();
-        if (search) {
-            unsigned win[4][2 * REACH + 1];
-#pragma unroll
-            for (int rr = 0; rr < 4; rr++)
-#pragma unroll
-                for (int c = 0; c < 2 * REACH + 1; c++) win[rr][c] = s_rows[rr][threadIdx.x + c];
-            unsigned e_best = 0xFFFFFFFFu;
-#pragma unroll
-            for (int d = 0; d < 11; d++) {
-                unsigned err = (unsigned)((d > 5 ? d - 5 : 5 - d) * DI_EVR / 8);
-#pragma unroll
-                for (int j = -5; j <= 5; j++) {
-                    const unsigned p1 = win[0][REACH + EDGE_DIRS[d][0] + j], p2 = win[1][REACH + EDGE_DIRS[d][2] + j];
-                    const unsigned p3 = win[2][REACH + EDGE_DIRS[d][4] + j], p4 = win[3][REACH + EDGE_DIRS[d][6] + j];
-                    err = di_sad(p1, p2, err); err = di_sad(p2, p3, err); err = di_sad(p3, p4, err);
-                }
-                if (err < e_best) { e_best = err; best = d; }
-            }
-        }
-    }
-    if (x < w) di_interp_pixel<true>(p, L, A, raw, i, x, y, best, dark, bright, fullres, halfres, over, amap, ev_out, k_lo, k_hi);
-    __syncthreads();                                                             // (s_rows is reused by the next row)
-    }
-    {   // the reference's four counters: semi-overexposed / not (bright rows), deep shadow / not (dark rows)
-        unsigned a = n_search & 0xFFFFu, b = n_plain & 0xFFFFu, c = n_search >> 16, d = n_plain >> 16;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); c += __shfl_xor(c, o); d += __shfl_xor(d, o); }
-        if ((threadIdx.x & 63) == 0) {
-            if (a) atomicAdd(&stats[0], a);
-            if (b) atomicAdd(&stats[1], b);
-            if (c) atomicAdd(&stats[2], c);
-            if (d) atomicAdd(&stats[3], d);
-        }
-    }
-}
-
 // alias error from the chroma-smoothed planes (hdr.c:1620: build_alias_map gets fullres_smooth / halfres_smooth)
 __global__ __launch_bounds__(256) void k_di_alias_err(const uint32_t *__restrict__ bright, const uint32_t *__restrict__ fullres_s,
                                                       const uint32_t *__restrict__ halfres_s, DiBatch bt, DiLuts L,
@@ -675,7 +551,7 @@ __global__ __launch_bounds__(256) void k_di_alias_err(const uint32_t *__restrict
     if (!di_frame<1>(bt, f, p)) return;
     bright += (size_t)f * bt.S; fullres_s += (size_t)f * bt.S; halfres_s += (size_t)f * bt.S; amap += (size_t)f * bt.S;
     const size_t n = (size_t)p.w * p.h;
-    for (size_t i = (size_t)di_xcd_block() * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         amap[i] = (uint16_t)di_alias_err(p, L, (int)bright[i], (int)fullres_s[i], (int)halfres_s[i]);
 }
 
@@ -817,7 +693,7 @@ __global__ __launch_bounds__(256) void k_di_blend(const uint32_t *__restrict__ d
     const int w = p.w, h = p.h;
     const size_t n = (size_t)w * h;
     const int *r2e = L.blend_raw2ev, *e2r = L.blend_ev2raw;
-    for (size_t i = (size_t)di_xcd_block() * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int x = (int)(i % w), y = (int)(i / w);
         const int b = (int)bright[i], d = (int)dark[i];
         // overexposure blur, hdr.c:1631-1651
@@ -995,12 +871,6 @@ template <int BINS> __device__ __forceinline__ void kth_resolve(const unsigned *
 // wh [2][32768] (white histograms by exposure, overwritten samples taken out)
 constexpr size_t DI_DERIVED_WORDS = 4 * 16384 + 4 * 16385 + 3 + 2 * 32768;
 
-#ifdef DI_DIAG
-__device__ unsigned long long g_dp_stamps[16];
-#define DP_STAMP(k) do { __syncthreads(); if (blockIdx.x == 0 && threadIdx.x == 0) g_dp_stamps[k] = wall_clock64(); } while (0)
-#else
-#define DP_STAMP(k) do {} while (0)
-#endif
 // analyse()'s host half, the pattern, the bright / dark fields and the white levels of dualiso.cpp (is_rggb_from_hist,
 // bright_dark_from_hist, whites_from_hist) for frame blockIdx.x; writes dd[f] and the geometry part of pp[f]
 __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__restrict__ frames, size_t img_stride, int w, int H, int black14,
@@ -1021,7 +891,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         dd.n = 0; dd.bmed = dd.b_lo = dd.b_hi = dd.dmed = 0; dd.hi_n = 0; dd.best = -1; dd.best_score = 0;
         dd.check_ok = D.check_passed || (dd.check_n > 0 && dd.check_sum / dd.check_n > 0.5);      // hdr.c:432-438
     }
-    DP_STAMP(0);
     // ---- the four Bayer-phase histograms over rows [0, H / 4 * 4) (hdr.c:453): all rows' classes minus the rows below that range
 #pragma unroll 16
     for (int i = tid; i < 4 * 16384; i += DNT) {
@@ -1033,7 +902,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
     for (int y = R0; y < H; y++)
         for (int x = tid; x < w; x += DNT) atomicSub(&hb[(size_t)((y & 1) * 2 + (x & 1)) * 16384 + (frame[(size_t)y * w + x] & 16383)], 1u);
     __syncthreads();
-    DP_STAMP(1);
     {   // is_rggb_from_hist: sum over v of |acc1 - acc2| against |acc0 - acc3| (integers far below 2^53: the doubles of the host are exact)
         const int per = 16384 / DNT, i0 = tid * per;
         unsigned long long run[4];
@@ -1056,7 +924,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         if (tid == 0) s_rggb = d_rggb < d_gbrg;
         __syncthreads();
     }
-    DP_STAMP(2);
     const int rggb = s_rggb, ay1 = rggb ? 0 : 1, h = rggb ? H : H - 1;
     // ---- greens by row phase: the frame as it is (RGGB: x & 1 != y & 1, rows [0, R0)) or one row lower (GBRG: rows 4 <= y - 1 < R1)
 #pragma unroll 16
@@ -1067,7 +934,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         g[(size_t)ph * 16385 + v] = dev[DI_D_CLASS + (size_t)(q * 2 + px) * 16384 + v];
     }
     __syncthreads();
-    DP_STAMP(3);
     // rows outside the range (dualiso.cpp: take_out): RGGB [R0, H); GBRG y - 1 < 4 or y - 1 >= R1, i.e. [0, 5) and [R1 + 1, H)
     for (int pass = 0; pass < 2; pass++) {
         const int ya = rggb ? (pass ? H : R0) : (pass ? R1 + 1 : 0), yb = rggb ? H : (pass ? H : min(5, H));
@@ -1078,12 +944,10 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         }
     }
     __syncthreads();
-    DP_STAMP(4);
     // ---- bright_dark_from_hist in closed form.  The host walks ref upwards and moves every class to raw_i(ref) = the smallest r whose
     // count of values below r reaches ref; it records `off` while ref < ref_off and all classes are below the threshold, and stops at
     // the first ref that takes a class to 10000 or at ref_max.  The state only depends on ref, so the stops are evaluated directly.
     for (int k = 0; k < 4; k++) block_prefix_in_place<16384>(g + (size_t)k * 16385, sh);
-    DP_STAMP(5);
     if (tid < 64) {
         // lanes 0..3: raw of row phase k = lane, lanes 4..7: off of phase k = lane - 4 (eight binary searches side by side; the other
         // lanes repeat them); the minima over the four phases by shuffles within the groups of four lanes
@@ -1116,7 +980,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         dd.rggb = rggb;
     }
     __syncthreads();
-    DP_STAMP(6);
     // ---- whites_from_hist: the every-3rd-pixel histograms by exposure; the samples the reference's list cap overwrote (class
     // indices max_pix - 1 .. total - 2, only ever in the last rows) are taken out; 11th / 51st largest
     const int isb[4] = { s_bright[0], s_bright[1], s_bright[2], s_bright[3] };
@@ -1130,7 +993,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         wh[v] = s0;
         wh[32768 + v] = s1;
     }
-    DP_STAMP(7);
     const int spr = (w + 2) / 3, tail_rows = min(h, 32);
     const long long max_pix = (long long)w * h / 2 / 9;
     if (tid == 0) {
@@ -1154,7 +1016,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         s_nrows = n;
     }
     __syncthreads();
-    DP_STAMP(8);
     unsigned long long removed[2] = { 0, 0 };
     for (int r = 0; r < s_nrows; r++) {
         const int y = s_rows[r][0], c = isb[y % 4];
@@ -1171,7 +1032,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
     removed[0] = block_sum_u64(removed[0], sh);
     removed[1] = block_sum_u64(removed[1], sh);
     __syncthreads();
-    DP_STAMP(9);
     int wlev[2];
     for (int c = 0; c < 2; c++) {
         const long long kept = shl[c] - (long long)removed[c];
@@ -1186,7 +1046,6 @@ __global__ __launch_bounds__(DNT) void k_di_decide_pattern(const uint16_t *__res
         }
         wlev[c] = val;
     }
-    DP_STAMP(10);
     if (tid == 0) {
         const int w0 = wlev[0] - 100, w1 = wlev[1] - 1500;
         dd.white_dark = w0 < 10000 ? 10000 : (w0 > 16383 ? 16383 : w0);
@@ -1307,12 +1166,8 @@ static inline dim3 flat_grid(size_t n, int nframes = 1)
     size_t b = (n + 255) / 256;
     const size_t cap = nframes > 4 ? 2048 : 8192;       // a batch fills the chip with its frames
     if (b > cap) b = cap;
-    // (di_xcd_block: measured and left OFF -- profiles/r05/di_xcd/: 6 % less traffic per conversion, k_di_blend's fetches -31 %, but
-    // k_di_interp 216 -> 270 us, k_di_amaze_ev 93 -> 113 us per frame: a band of rows per XCD concentrates each pass on few memory
-    // channels, and the traffic of these kernels is gathers in the 4 MB tables, not re-read rows.  MLVFS_AMD_DI_XCD=1 switches it on.)
-    static const bool xcd = [] { const char *e = getenv("MLVFS_AMD_DI_XCD"); return e && e[0] == '1'; }();
-    if (xcd) b = (b + 7) / 8 * 8;                       // (workgroups beyond the last piece find nothing to do)
-    else if ((b & 7) == 0) b += 1;                      // (an odd grid keeps the plain order)
+    // (workgroups dealt to the XCDs as one band of rows each were measured and removed, profiles/r05/: k_di_interp 216 -> 270 us
+    // per frame -- the traffic of these kernels is gathers in the 4 MB tables, not re-read rows)
     return dim3((unsigned)b, (unsigned)nframes);
 }
 
@@ -1331,7 +1186,7 @@ int di_launch_analyse(const void *d_img, int w, int H, int black, int white, con
             MLV_HIP(hipMemsetAsync(d_check, 0, 2 * sizeof(double), s));
         }
     }
-    static const int band_max = [] { const char *e = getenv("MLVFS_AMD_ANALYSE_BAND"); const int v = e ? atoi(e) : 128; return v >= 4 ? v / 4 * 4 : 128; }();
+    constexpr int band_max = 128;
     int band = H * 4 * nframes / 256 / 4 * 4;                                   // at least a workgroup per CU
     band = band < 16 ? 16 : (band > band_max ? band_max : band);
     while (band > 4 && (band / 4) * (w / 2 + 1) >= 65536) band -= 4;            // the 16-bit counters of a class
@@ -1417,12 +1272,10 @@ int di_launch_match(const void *d_img, const DiBatch &b, int h_launch, const DiL
 
 // squeeze -> AMaZE -> clamp -> gray -> edge directions; the planes feed k_di_interp<true>.  P.sq_dst: per frame sq_dst | sq_row of
 // h_launch ints each
-// rows per workgroup of the edge search.  MLVFS_AMD_DI_EDGE_FUSED=1: direction search and interpolation in one kernel (k_di_edge_interp;
-// identical results).  OFF: 4 % more conversions per second in batches of 8 (985 -> 1 026 on one box), but 582-636 MB of HBM-side
-// traffic per frame where the two kernels need 446 (profiles/r05/di_experiments.log) -- the wrong direction for VERDICT r4 #3 until
-// the table look-ups of the interpolation are localised.
-static int di_edge_rows() { static const int v = [] { const char *e = getenv("MLVFS_AMD_EDGE_ROWS"); const int r = e ? atoi(e) : 4; return r > 0 ? r : 4; }(); return v; }
-static bool di_edge_fused() { const char *e = getenv("MLVFS_AMD_DI_EDGE_FUSED"); return e && atoi(e) != 0; }
+// rows per workgroup of the edge search.  (Direction search and interpolation in one kernel were measured and removed: 4 % more
+// conversions per second in batches of 8, 985 -> 1 026 on one box, but 582-636 MB of HBM-side traffic per frame where the two kernels
+// need 446 -- the wrong direction until the interpolation's table look-ups are localised; profiles/r05/di_experiments.log.)
+constexpr int EDGE_DIR_ROWS = 4;
 int di_launch_amaze_interp(const void *d_img, const DiBatch &b, int h_launch, const DiLuts &L, const DiPlanes &P, hipStream_t s, hipEvent_t after_amaze,
                            hipStream_t tail)
 {
@@ -1432,22 +1285,18 @@ int di_launch_amaze_interp(const void *d_img, const DiBatch &b, int h_launch, co
     hipLaunchKernelGGL(k_di_match, flat_grid(n, nf), dim3(256), 0, s, (const uint16_t *)d_img, P.raw, b, P.sq_dst, sq_stride, h_launch, P.cfa,
                        (const int *)nullptr, (int *)nullptr);
     // AMaZE's output stage makes the look-ups of the planes itself (amaze_math.h: ev_of_planes): the three int planes and the gray
-    // plane are what it writes, the float planes and k_di_amaze_ev's pass over them (134 MB and 93 us per 3584x1320 frame) are gone.
-    // MLVFS_AMD_DI_EV_FUSED=0: the separate pass (A/B; identical results)
-    static const bool ev_fused = [] { const char *e = getenv("MLVFS_AMD_DI_EV_FUSED"); return !e || atoi(e) != 0; }();
-    const bool fused = ev_fused && w % 4 == 0;
-    float *const o_red = fused ? (float *)P.ev_red : P.red, *const o_green = fused ? (float *)P.ev_green : P.green, *const o_blue = fused ? (float *)P.ev_blue : P.blue;
-    const int *const r2e = fused ? L.interp_raw2ev : nullptr;
-    int *const o_gray = fused ? P.gray_ev : nullptr;
+    // plane are what it writes.  (Float planes and a pass of their own over them cost 134 MB and 93 us per 3584x1320 frame.)
+    float *const o_red = (float *)P.ev_red, *const o_green = (float *)P.ev_green, *const o_blue = (float *)P.ev_blue;
     // a frame's AMaZE geometry follows its own row count (one less for GBRG): the launch plan is made per distinct height
     int rc = MLVFS_AMD_OK;
     if (b.pp) {
         static_assert(sizeof(DiParams) % sizeof(int) == 0, "h of frame f sits f * sizeof(DiParams) / 4 ints behind h of frame 0");
         for (int k = 0; k < b.nheights && !rc; k++)
             rc = amaze_launch(P.cfa + fo, w, b.heights[k], o_red + fo, o_green + fo, o_blue + fo, P.amaze_scratch + (size_t)b.f0 * P.amaze_scratch_stride, s,
-                              nf, b.S, P.amaze_scratch_stride, &b.pp[b.f0].h, (int)(sizeof(DiParams) / sizeof(int)), nullptr, r2e, b.p0.black20,
-                              o_gray ? o_gray + fo : nullptr);
-    } else rc = amaze_launch(P.cfa, w, b.p0.h, o_red, o_green, o_blue, P.amaze_scratch, s, 1, 0, 0, nullptr, 0, nullptr, r2e, b.p0.black20, o_gray);
+                              nf, b.S, P.amaze_scratch_stride, &b.pp[b.f0].h, (int)(sizeof(DiParams) / sizeof(int)), nullptr, L.interp_raw2ev,
+                              b.p0.black20, P.gray_ev + fo);
+    } else rc = amaze_launch(P.cfa, w, b.p0.h, o_red, o_green, o_blue, P.amaze_scratch, s, 1, 0, 0, nullptr, 0, nullptr, L.interp_raw2ev, b.p0.black20,
+                             P.gray_ev);
     if (rc) return rc;
     if (after_amaze) MLV_HIP(hipEventRecord(after_amaze, s));
     if (tail && tail != s) {                                           // what follows AMaZE goes on with the planes on another stream
@@ -1455,12 +1304,8 @@ int di_launch_amaze_interp(const void *d_img, const DiBatch &b, int h_launch, co
         MLV_HIP(hipStreamWaitEvent(tail, after_amaze, 0));
         s = tail;
     }
-    if (!fused)
-        hipLaunchKernelGGL(k_di_amaze_ev, flat_grid(n, nf), dim3(256), 0, s, P.red, P.green, P.blue, b, L.interp_raw2ev, P.ev_red, P.ev_green, P.ev_blue,
-                           P.gray_ev);
-    if (!di_edge_fused())                                             // (fused: the search runs inside the interpolation's kernel, di_launch_convert)
-        hipLaunchKernelGGL(k_di_edge_dir, dim3((w + 255) / 256, (h_launch + di_edge_rows() - 1) / di_edge_rows(), nf), dim3(256), 0, s, P.raw, P.gray_ev, b, P.sq_row, sq_stride,
-                           L.fullres_thr, P.dir, P.stats);
+    hipLaunchKernelGGL(k_di_edge_dir, dim3((w + 255) / 256, (h_launch + EDGE_DIR_ROWS - 1) / EDGE_DIR_ROWS, nf), dim3(256), 0, s, P.raw, P.gray_ev, b, P.sq_row,
+                       sq_stride, L.fullres_thr, P.dir, P.stats);
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;
 }
@@ -1474,10 +1319,7 @@ int di_launch_convert(const DiBatch &b, int h_launch, const DiLuts &L, const DiP
     uint16_t *amap_fused = (p.use_alias_map && !p.chroma_smooth) ? P.amap : nullptr;
     const DiAmazeIn A{ P.ev_red, P.ev_green, P.ev_blue, P.dir, P.sq_row, 3 * (size_t)h_launch };
     const bool ev_planes = !p.chroma_smooth && L.blend_is_mix;                // halfres / fullres travel as EV (the blend's lookups, done early)
-    if (amaze && di_edge_fused())
-        hipLaunchKernelGGL(k_di_edge_interp, dim3((p.w + 255) / 256, (h_launch + di_edge_rows() - 1) / di_edge_rows(), nf), dim3(256), 0, s, P.raw, P.gray_ev, b, P.sq_row,
-                           3 * (size_t)h_launch, L.fullres_thr, P.stats, L, A, P.dark, P.bright, P.fullres, P.halfres, P.over, amap_fused, ev_planes);
-    else if (amaze)
+    if (amaze)
         hipLaunchKernelGGL(k_di_interp<true>, flat_grid(n, nf), dim3(256), 0, s, P.raw, b, L, A, P.dark, P.bright, P.fullres, P.halfres,
                            P.over, amap_fused, ev_planes);
     else
@@ -1515,19 +1357,6 @@ size_t di_derived_words() { return DI_DERIVED_WORDS; }
 int di_launch_decide_pattern(const void *d_frames, const DiBatch &b, int H, int black14, const DiDecideBuffers &D, hipStream_t s)
 {
     hipLaunchKernelGGL(k_di_decide_pattern, dim3(b.nframes), dim3(DNT), 0, s, (const uint16_t *)d_frames, b.img_stride, b.p0.w, H, black14, D);
-#ifdef DI_DIAG
-    {
-        static int shown = 0;
-        if (shown++ == 3) {
-            unsigned long long st[16];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpyFromSymbol(st, HIP_SYMBOL(g_dp_stamps), sizeof st);
-            fprintf(stderr, "DI_DIAG k_di_decide_pattern, 10 ns ticks between stamps:");
-            for (int k = 0; k < 10; k++) fprintf(stderr, " %lld", (long long)(st[k + 1] - st[k]));
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;
 }

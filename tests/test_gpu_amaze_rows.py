@@ -98,7 +98,7 @@ def test_the_tile_planes_of_the_two_kernels_agree(gpu):
 
 
 def test_a_workgroup_streams_through_many_tiles(gpu, oracle, monkeypatch):
-    """MLVFS_AMD_AMAZE_ROWS_WGS is read once per process: this test only checks the default grid on a plane with more tiles than CUs."""
+    """The default grid on a plane with more complete tiles than CUs: a workgroup takes several tiles from the frame's counter."""
     w, h = 128 * 20 + 32 + 128, 128 * 16 + 32 + 128               # 21 x 17 = 357 complete tiles > 256 workgroups
     raw = _textured(w, h, 5)
     want = oracle.amaze_demosaic(raw)
