@@ -43,6 +43,11 @@ size_t dng_get_image_data(struct frame_headers *frame_headers, uint16_t *packed_
  * works without a HIP device.                                                       */
 size_t dng_get_header_data(struct frame_headers *frame_headers, uint8_t *output_buffer, off_t offset, size_t max_size,
                            double fps_override, char *mlv_basename);
+/* dng_get_header_data for a frame whose strip is one lossless-JPEG stream of stream_bytes bytes: the same 65536 bytes except the
+ * value fields of two IFD0 entries, Compression (259) = 7 and StripByteCounts (279) = stream_bytes.  BitsPerSample stays 16 (the
+ * stream's precision), StripOffsets 65536, one strip.  Host code.                                                              */
+size_t mlvfs_amd_dng_header_lossless(struct frame_headers *frame_headers, uint8_t *output_buffer, off_t offset, size_t max_size,
+                                     double fps_override, const char *mlv_basename, uint32_t stream_bytes);
 /* replaces mlvfs/dng.h:30,32,33 (dng.c:797-800, 879-891) */
 size_t dng_get_header_size(void);
 size_t dng_get_image_size(struct frame_headers *frame_headers);
@@ -252,6 +257,20 @@ int mlvfs_amd_lj92_decode_untiled(lj92 lj, uint16_t *dst, int xres, int yres);
 /* host-only test hook: the encoder's Huffman table for a histogram of the 17 classes; out[68] = bits[1..16], number of DHT
  * values, the 17 values, then length and code per class.  0, or -1 (error string set) where lj92_encode would refuse.          */
 int mlvfs_amd_lj92_encode_table(const uint32_t hist[17], int npix, int *out);
+/* The same encoder on a batch of frames that already lie in device memory: nframes frames of width x height uint16 values, `stride`
+ * bytes apart, each to the COMPLETE stream (SOI .. EOI) lj92_encode writes for it with readLength = width * height, skipLength 0 and
+ * no delinearisation table, at d_out + f * out_stride (device memory, 4-byte aligned, out_stride a multiple of 4).  One launch
+ * sequence and one host round trip (the Huffman tables) serve the batch.  lengths[f]: bytes of the stream; status[f]: one of
+ * MLVFS_AMD_LJ92ENC_*; max_class[f] (optional): the highest difference class SSSS in use, 17 for a 17-bit difference.  A frame the
+ * reference cannot encode inside its arrays, or whose stream is longer than out_stride, says so in status[f] (length 0, its part of
+ * d_out undefined) and does not disturb the others.  Class 16 is encoded as the reference encodes it, with 16 value bits behind the
+ * code, which the JPEG standard does not do: callers that write files for other decoders check max_class.  Synchronises `stream`. */
+#define MLVFS_AMD_LJ92ENC_OK      0
+#define MLVFS_AMD_LJ92ENC_DIFF17  1     /* a difference of 17 bits */
+#define MLVFS_AMD_LJ92ENC_TABLE   2     /* all 17 classes in use, or a Huffman code longer than 16 bits */
+#define MLVFS_AMD_LJ92ENC_NOFIT   3     /* the stream is longer than out_stride */
+int mlvfs_amd_lj92_encode_batch_dev(const void *d_frames, size_t stride, int nframes, int width, int height, int bitdepth, void *d_out,
+                                    size_t out_stride, uint32_t *lengths, int *status, int *max_class, void *stream);
 
 /* -- LZMA payloads ----------------------------------------- */
 /* One VIDF payload of an LZMA-compressed clip (MLV_VIDEO_CLASS_FLAG_LZMA; main.c:598-616): [u32 size of the packed frame][5 LZMA
@@ -472,6 +491,17 @@ void *mlvfs_amd_mount_open(const void *reader, const mlvfs_amd_mount_opts_t *opt
  * each frame's headers after its stages.  io_threads: reader threads (<= 0: 8).  results[k] (optional) = 1 when the frame was
  * converted as dual ISO.  Calls on one handle are serialised.                                                                       */
 int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results);
+/* The same frames as losslessly compressed .dng files: the pixel data of a file is ONE lossless-JPEG stream (TIFF Compression 7,
+ * mlvfs_amd_lj92_encode_batch_dev at 16 bits) of the frame mlvfs_amd_mount_dng would serve, encoded where it lies after the fused
+ * pass; only the stream crosses the link.  A w x h frame with even h is encoded as one component of 2w x h/2 (predictor 6 then
+ * predicts from the same colour two sensor rows up), an odd h as w x h.  sizes[k]: bytes of file k (65536 + the stream); bytes of
+ * h_out behind them are left untouched.  flags[k] bit 0: the frame is served UNCOMPRESSED, byte for byte mlvfs_amd_mount_dng's file
+ * (sizes[k] = dng_get_size) -- a frame the encoder refuses, whose stream would be longer than its pixels, or whose highest
+ * difference class is 16 (the reference's encoder writes value bits behind class 16 that other decoders do not expect).
+ * out_stride >= dng_get_size as before.  The stages, their order and the order-dependent state are mlvfs_amd_mount_dng's: calls of
+ * both kinds on one handle interleave in serve order.                                                                            */
+int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,
+                                 int batch_frames, int io_threads, int *results);
 void mlvfs_amd_mount_close(void *mount);
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */

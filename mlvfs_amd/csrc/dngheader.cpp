@@ -319,10 +319,9 @@ private:
 
 uint8_t bcd(int v) { return (uint8_t)(((v / 10) << 4) | (v % 10)); }
 
-}  // namespace
-
-extern "C" size_t dng_get_header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offset, size_t max_size,
-                                      double fps_override, char *mlv_basename)
+// compression / strip_bytes: TIFF tags 259 and 279 -- 1 and the image's size (dng.c), or 7 and the length of the lossless-JPEG stream
+size_t header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offset, size_t max_size, double fps_override, const char *mlv_basename,
+                   uint32_t compression, uint32_t strip_bytes)
 {
     std::vector<uint8_t> header(kHeaderBytes, 0);
     struct raw_info &ri = fh->rawi_hdr.raw_info;
@@ -392,7 +391,7 @@ extern "C" size_t dng_get_header_data(struct frame_headers *fh, uint8_t *output_
     t.inl(256, LONG, 1, fh->rawi_hdr.xRes);                             // ImageWidth
     t.inl(257, LONG, 1, fh->rawi_hdr.yRes);                             // ImageLength
     t.inl(258, SHORT, 1, 16);                                           // BitsPerSample
-    t.inl(259, SHORT, 1, 1);                                            // Compression: none
+    t.inl(259, SHORT, 1, compression);                                  // Compression: 1 none, 7 lossless JPEG
     t.inl(262, SHORT, 1, 32803);                                        // PhotometricInterpretation: CFA
     t.inl(266, SHORT, 1, 1);                                            // FillOrder
     t.ascii(271, make);                                                 // Make
@@ -401,7 +400,7 @@ extern "C" size_t dng_get_header_data(struct frame_headers *fh, uint8_t *output_
     t.inl(274, SHORT, 1, 1);                                            // Orientation
     t.inl(277, SHORT, 1, 1);                                            // SamplesPerPixel
     t.inl(278, SHORT, 1, fh->rawi_hdr.yRes);                            // RowsPerStrip
-    t.inl(279, LONG, 1, (uint32_t)dng_get_image_size(fh));              // StripByteCounts
+    t.inl(279, LONG, 1, strip_bytes);                                   // StripByteCounts
     t.inl(284, SHORT, 1, 1);                                            // PlanarConfiguration
     t.ascii(305, "MLVFS");                                              // Software (mlvfs.h:65)
     t.ascii(306, datetime);                                             // DateTime
@@ -455,4 +454,20 @@ extern "C" size_t dng_get_header_data(struct frame_headers *fh, uint8_t *output_
         if (have < n) memset(output_buffer + have, 0, n - have);
     }
     return n;
+}
+
+}  // namespace
+
+extern "C" size_t dng_get_header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offset, size_t max_size,
+                                      double fps_override, char *mlv_basename)
+{
+    return header_data(fh, output_buffer, offset, max_size, fps_override, mlv_basename, 1, (uint32_t)dng_get_image_size(fh));
+}
+
+// The header of a frame whose strip is one lossless-JPEG stream of stream_bytes bytes (TIFF Compression 7): dng_get_header_data's
+// 65536 bytes but for the value fields of tags 259 and 279.  BitsPerSample stays 16 -- the stream's SOF3 precision.
+extern "C" size_t mlvfs_amd_dng_header_lossless(struct frame_headers *fh, uint8_t *output_buffer, off_t offset, size_t max_size,
+                                                double fps_override, const char *mlv_basename, uint32_t stream_bytes)
+{
+    return header_data(fh, output_buffer, offset, max_size, fps_override, mlv_basename, 7, stream_bytes);
 }

@@ -3,7 +3,12 @@
 //   table      mlvfs/lj92.c:788-937 (createEncodeTable): code sizes by merging the two rarest of 18 entries in FLOAT frequencies
 //              (17 SSSS classes + one reserved entry of frequency 1.0), the value list in order of size, canonical codes
 //   header     mlvfs/lj92.c:939-984 (SOI, SOF3, DHT, SOS with predictor 6, EOI)
-//   kernels    csrc/k_lj92enc.hip (histogram, bit packing, byte stuffing)
+//   kernels    csrc/k_lj92enc.hip (histogram, bit packing, byte stuffing), every one with the frame as a grid dimension
+//   batch      lje_encode_batch: n frames in device memory -> n complete streams in device memory with ONE host round trip (n x 20
+//              counters down, n tables with their marker segments up) and one copy of lengths and states.  The mount's lossless
+//              .dng files (mount.cpp), mlvfs_amd_lj92_encode_batch_dev and -- as a batch of one -- lj92_encode all go through it.
+//              The bits a frame needs are known exactly once its table is (sum of count x (code length + class)): the bit buffer
+//              is sized from that, not from 32 bits per pixel.
 //
 // What the reference's table builder does and a textbook one does not -- all of it kept, the streams are compared byte for byte:
 //  * the reserved entry has the LARGEST frequency, so it takes a short code instead of the longest one;
@@ -16,16 +21,11 @@
 // a code longer than 16 bits (bits[17+]), a value beyond the delinearisation table, an empty image.
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
-#include "lj92.h"
+#include "lj92enc.h"
 
 namespace mlv {
-
-int lje_classify(const uint16_t *d_img, const uint16_t *d_delin, int delin_len, int width, uint32_t npix, int bitdepth, uint32_t *d_code,
-                 uint32_t *d_hist, hipStream_t s);
-uint32_t lje_blocks(uint64_t n);
-int lje_pack(const uint32_t *d_code, uint32_t npix, const uint8_t len[17], const uint16_t codes[17], uint32_t *d_blocks, uint32_t *d_sums,
-             uint32_t *d_bits, uint8_t *d_out, hipStream_t s);
 
 namespace {
 
@@ -98,13 +98,120 @@ int write_header(uint8_t *e, int width, int height, int bitdepth, const EncTable
     return w;
 }
 
+
 enum { LJ92_OK = 0, LJ92_CORRUPT = -1, LJ92_NO_MEMORY = -2 };      // lj92.h:29-35
 size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
+struct FixedLayout {
+    size_t src_at, hist_at, blockhist_at, off_at, ffoff_at, tabs_at, res_at, bytes;
+    FixedLayout(uint32_t npix, int n)
+    {
+        const size_t nb = lje_blocks(npix);
+        size_t a = 0;
+        src_at = a; a += up256(sizeof(void *) * n);
+        hist_at = a; a += up256(sizeof(uint32_t) * LJE_HIST * n);
+        blockhist_at = a; a += up256(sizeof(uint32_t) * 17 * nb * n);
+        off_at = a; a += up256(sizeof(uint32_t) * (nb + 1) * n);
+        ffoff_at = a; a += up256(sizeof(uint32_t) * (nb + 1) * n);
+        tabs_at = a; a += up256(sizeof(LjeFrame) * n);
+        res_at = a; a += up256(sizeof(LjeOut) * n);
+        bytes = a;
+    }
+};
+
 }  // namespace
+
+size_t lje_fixed_bytes(uint32_t npix, int nframes) { return FixedLayout(npix, nframes).bytes; }
+
+int lje_encode_batch(const uint16_t *const *h_src, int n, int width, int height, int bitdepth, const uint16_t *d_delin, int delin_len,
+                     void *d_fixed, LjeRoom &room, uint8_t **d_out_used, size_t *out_stride_used, LjeResult *res, hipStream_t s)
+{
+    const uint32_t npix = (uint32_t)((uint64_t)width * height);
+    const FixedLayout L(npix, n);
+    uint8_t *A = (uint8_t *)d_fixed;
+    const uint16_t *const *d_src = (const uint16_t *const *)(A + L.src_at);
+    uint32_t *d_hist = (uint32_t *)(A + L.hist_at);
+    MLV_HIP(hipMemcpyAsync(A + L.src_at, h_src, sizeof(void *) * n, hipMemcpyHostToDevice, s));
+    MLV_HIP(hipMemsetAsync(d_hist, 0, sizeof(uint32_t) * LJE_HIST * n, s));
+    int rc = lje_launch_hist(d_src, d_delin, delin_len, width, npix, bitdepth, n, d_hist, (uint32_t *)(A + L.blockhist_at), s);
+    if (rc) return rc;
+    // ---- the one round trip: the batch's histograms down, its tables, marker segments and bit offsets up
+    std::vector<uint32_t> hist((size_t)LJE_HIST * n);
+    MLV_HIP(hipMemcpyAsync(hist.data(), d_hist, sizeof(uint32_t) * hist.size(), hipMemcpyDeviceToHost, s));
+    MLV_HIP(hipStreamSynchronize(s));
+    std::vector<LjeFrame> tabs(n);
+    size_t bits_dwords = 0, worst_stream = 0;
+    int good = 0;
+    for (int f = 0; f < n; f++) {
+        const uint32_t *h = &hist[(size_t)LJE_HIST * f];
+        LjeFrame &t = tabs[f];
+        memset(&t, 0, sizeof t);
+        LjeResult &r = res[f];
+        r = LjeResult();
+        for (int c = 0; c < 18; c++) if (h[c]) r.max_class = c;
+        EncTable et;
+        uint64_t total = 0;
+        if (h[18]) r.status = LJE_DELIN;
+        else if (h[17]) r.status = LJE_DIFF17;
+        else if ((r.why = build_table(h, (int)npix, &et))) r.status = LJE_TABLE;
+        else {
+            for (int c = 0; c < 17; c++) total += (uint64_t)h[c] * (et.len[c] + c);
+            if (total >= 0xFFF00000ull) { r.status = LJE_TABLE; r.why = "a stream of 2^32 bits or more"; }
+        }
+        t.status = (uint32_t)r.status;
+        if (r.status != LJE_OK) continue;
+        for (int c = 0; c < 17; c++) { t.len[c] = et.len[c]; t.code[c] = et.code[c]; }
+        t.head_len = (uint8_t)write_header(t.head, width, height, bitdepth, et);
+        t.bits_at = (uint32_t)bits_dwords;
+        bits_dwords += ((size_t)(total >> 5) + 1 + 63) / 64 * 64;             // whole 256-byte lines per frame
+        worst_stream = std::max(worst_stream, (size_t)t.head_len + 2 * (size_t)((total + 7) >> 3) + 2);
+        good++;
+    }
+    if (bits_dwords >= 0xFFFFFFFFull) { set_error("lj92 encoder: a batch of more than 2^32 dwords of bits"); return MLVFS_AMD_ERR_ARG; }
+    if (good) {
+        void *d_bits = nullptr;
+        rc = room.get(bits_dwords * 4, (worst_stream + 3) / 4 * 4, &d_bits, d_out_used, out_stride_used);
+        if (rc) return rc;
+        LjeFrame *d_tabs = (LjeFrame *)(A + L.tabs_at);
+        LjeOut *d_res = (LjeOut *)(A + L.res_at);
+        MLV_HIP(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(LjeFrame) * n, hipMemcpyHostToDevice, s));
+        rc = lje_launch_pack(d_src, d_delin, delin_len, width, npix, bitdepth, n, d_tabs, (const uint32_t *)(A + L.blockhist_at),
+                             (uint32_t *)(A + L.off_at), (uint32_t *)(A + L.ffoff_at), (uint32_t *)d_bits, *d_out_used, *out_stride_used, d_res, s);
+        if (rc) return rc;
+        std::vector<LjeOut> out(n);
+        MLV_HIP(hipMemcpyAsync(out.data(), d_res, sizeof(LjeOut) * n, hipMemcpyDeviceToHost, s));
+        MLV_HIP(hipStreamSynchronize(s));
+        for (int f = 0; f < n; f++) {
+            if (res[f].status != LJE_OK) continue;
+            res[f].status = (int)out[f].status;
+            res[f].length = out[f].length;
+        }
+    }
+    return MLVFS_AMD_OK;
+}
+
 }  // namespace mlv
 
 using namespace mlv;
+
+namespace {
+
+// the thread's scratch: d_a holds the caller's part and the fixed scratch, d_b the bit streams and (drop-in) the stream
+struct ThreadRoom : LjeRoom {
+    ThreadCtx *c;
+    bool own_out;
+    ThreadRoom(ThreadCtx *c_, bool own_out_) : c(c_), own_out(own_out_) {}
+    int get(size_t bits_bytes, size_t stream_bytes, void **d_bits, uint8_t **d_out, size_t *out_stride) override
+    {
+        const size_t bits = up256(bits_bytes);
+        if (c->ensure(c->cap_a, bits + (own_out ? stream_bytes : 0))) return MLVFS_AMD_ERR_NOMEM;
+        *d_bits = c->d_b;
+        if (own_out) { *d_out = (uint8_t *)c->d_b + bits; *out_stride = stream_bytes; }
+        return MLVFS_AMD_OK;
+    }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -124,6 +231,39 @@ int mlvfs_amd_lj92_encode_table(const uint32_t hist[17], int npix, int *out)
     return 0;
 }
 
+int mlvfs_amd_lj92_encode_batch_dev(const void *d_frames, size_t stride, int nframes, int width, int height, int bitdepth, void *d_out,
+                                    size_t out_stride, uint32_t *lengths, int *status, int *max_class, void *stream)
+{
+    if (!d_frames || !d_out || !lengths || !status) { set_error("lj92_encode_batch: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("lj92_encode_batch: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || (uint64_t)width * height >= (1u << 27)) {
+        set_error("lj92_encode_batch: %dx%d not supported", width, height);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (bitdepth < 1 || bitdepth > 16) { set_error("lj92_encode_batch: bit depth %d out of range", bitdepth); return MLVFS_AMD_ERR_ARG; }
+    const size_t img = (size_t)width * height * 2;
+    if (((uintptr_t)d_frames & 1) || (nframes > 1 && (stride < img || (stride & 1)))) { set_error("lj92_encode_batch: stride %zu too small or odd", stride); return MLVFS_AMD_ERR_ARG; }
+    if (((uintptr_t)d_out & 3) || (out_stride & 3) || out_stride < 128) { set_error("lj92_encode_batch: out_stride %zu too small or no multiple of 4", out_stride); return MLVFS_AMD_ERR_ARG; }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    if (c->ensure(lje_fixed_bytes((uint32_t)(img / 2), nframes), 0)) return MLVFS_AMD_ERR_NOMEM;
+    hipStream_t s = pick_stream(stream, c);
+    std::vector<const uint16_t *> src(nframes);
+    for (int f = 0; f < nframes; f++) src[f] = (const uint16_t *)((const uint8_t *)d_frames + (size_t)f * stride);
+    std::vector<LjeResult> res(nframes);
+    ThreadRoom room(c, false);
+    uint8_t *out = (uint8_t *)d_out;
+    const int rc = lje_encode_batch(src.data(), nframes, width, height, bitdepth, nullptr, 0, c->d_a, room, &out, &out_stride, res.data(), s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    for (int f = 0; f < nframes; f++) {
+        lengths[f] = res[f].length;
+        status[f] = res[f].status;
+        if (max_class) max_class[f] = res[f].max_class;
+    }
+    return MLVFS_AMD_OK;
+}
+
 int lj92_encode(uint16_t *image, int width, int height, int bitdepth, int readLength, int skipLength,
                 uint16_t *delinearize, int delinearizeLength, uint8_t **encoded, int *encodedLength)               // lj92.h:65-68
 {
@@ -135,19 +275,13 @@ int lj92_encode(uint16_t *image, int width, int height, int bitdepth, int readLe
     LibcRandGuard rand_guard;                      // HIP code may run: keep the caller's rand() stream out of its reach
     ThreadCtx *c = thread_ctx();
     if (!c) return LJ92_NO_MEMORY;
-    // ---- device layout: d_a = tile, table, codes, counters; d_b = bit stream, stuffed bytes
-    const uint32_t nb = lje_blocks(npix), nbb = lje_blocks((uint64_t)npix * 4 + 8);
+    // ---- device layout: d_a = tile, table, the batch's fixed scratch; d_b = bit stream, stuffed bytes (sized once the table is known)
     size_t a = 0;
     const size_t img_at = a; a += up256((size_t)npix * 2);
     const size_t delin_at = a; a += up256(delinearize ? (size_t)delinearizeLength * 2 : 0);
-    const size_t code_at = a; a += up256((size_t)npix * 4);
-    const size_t blocks_at = a; a += up256(((size_t)nb + nbb) * 4);
-    const size_t hist_at = a; a += 256;                               // 19 counters, then the two sums at +128
-    size_t b = 0;
-    const size_t bits_at = b; b += up256(((size_t)npix + 2) * 4);
-    const size_t out_at = b; b += up256((size_t)npix * 8 + 16);
-    if (c->ensure(a, b)) return LJ92_NO_MEMORY;
-    uint8_t *A = (uint8_t *)c->d_a, *B = (uint8_t *)c->d_b;
+    const size_t fixed_at = a; a += lje_fixed_bytes(npix, 1);
+    if (c->ensure(a, 0)) return LJ92_NO_MEMORY;
+    uint8_t *A = (uint8_t *)c->d_a;
     hipStream_t s = c->stream;
     auto hip_ok = [](hipError_t e, const char *what) { if (e != hipSuccess) { set_error("lj92_encode: %s: %s", what, hipGetErrorString(e)); return false; } return true; };
     // ---- the tile: readLength values, skipLength apart (lj92.c:766-769), contiguous on the device
@@ -168,31 +302,27 @@ int lj92_encode(uint16_t *image, int width, int height, int bitdepth, int readLe
         if (!ok) return LJ92_CORRUPT;
     }
     if (delinearize && !hip_ok(hipMemcpyAsync(A + delin_at, delinearize, (size_t)delinearizeLength * 2, hipMemcpyHostToDevice, s), "upload")) return LJ92_CORRUPT;
-    if (!hip_ok(hipMemsetAsync(A + hist_at, 0, 256, s), "memset") || !hip_ok(hipMemsetAsync(B + bits_at, 0, ((size_t)npix + 2) * 4, s), "memset")) return LJ92_CORRUPT;
-    if (lje_classify((const uint16_t *)(A + img_at), delinearize ? (const uint16_t *)(A + delin_at) : nullptr, delinearizeLength, width, npix, bitdepth,
-                     (uint32_t *)(A + code_at), (uint32_t *)(A + hist_at), s)) return LJ92_CORRUPT;
-    uint32_t hist[19];
-    if (!hip_ok(hipMemcpyAsync(hist, A + hist_at, sizeof hist, hipMemcpyDeviceToHost, s), "download") || !hip_ok(hipStreamSynchronize(s), "histogram")) return LJ92_CORRUPT;
-    if (hist[18]) { set_error("lj92_encode: a value beyond the delinearisation table"); return LJ92_CORRUPT; }
-    if (hist[17]) { set_error("lj92_encode: a difference of 17 bits (the reference counts and looks it up behind its tables)"); return LJ92_CORRUPT; }
-    EncTable t;
-    if (const char *why = build_table(hist, (int)npix, &t)) { set_error("lj92_encode: %s", why); return LJ92_CORRUPT; }
-    uint32_t *d_sums = (uint32_t *)(A + hist_at + 128);
-    if (lje_pack((const uint32_t *)(A + code_at), npix, t.len, t.code, (uint32_t *)(A + blocks_at), d_sums, (uint32_t *)(B + bits_at), B + out_at, s)) return LJ92_CORRUPT;
-    uint32_t sums[2];
-    if (!hip_ok(hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, s), "download") || !hip_ok(hipStreamSynchronize(s), "packing")) return LJ92_CORRUPT;
-    const size_t body = (size_t)((sums[0] + 7) >> 3) + sums[1];
-    uint8_t head[64];
-    const int hl = write_header(head, width, height, bitdepth, t);
-    if (hl + body + 2 > 0x7FFFFFFFu) { set_error("lj92_encode: stream longer than an int can say"); return LJ92_NO_MEMORY; }
-    uint8_t *e = (uint8_t *)malloc(hl + body + 2);                     // the caller frees it (lj92.c:1136-1139)
+    // ---- the batch path with one frame
+    const uint16_t *src = (const uint16_t *)(A + img_at);
+    ThreadRoom room(c, true);
+    uint8_t *d_out = nullptr;
+    size_t out_stride = 0;
+    LjeResult r;
+    if (lje_encode_batch(&src, 1, width, height, bitdepth, delinearize ? (const uint16_t *)(A + delin_at) : nullptr, delinearizeLength, A + fixed_at,
+                         room, &d_out, &out_stride, &r, s)) {
+        (void)hipStreamSynchronize(s);
+        return LJ92_CORRUPT;
+    }
+    if (r.status == LJE_DELIN) { set_error("lj92_encode: a value beyond the delinearisation table"); return LJ92_CORRUPT; }
+    if (r.status == LJE_DIFF17) { set_error("lj92_encode: a difference of 17 bits (the reference counts and looks it up behind its tables)"); return LJ92_CORRUPT; }
+    if (r.status == LJE_TABLE) { set_error("lj92_encode: %s", r.why); return LJ92_CORRUPT; }
+    if (r.status != LJE_OK) { set_error("lj92_encode: the stream does not fit its buffer"); return LJ92_CORRUPT; }
+    if (r.length > 0x7FFFFFFFu) { set_error("lj92_encode: stream longer than an int can say"); return LJ92_NO_MEMORY; }
+    uint8_t *e = (uint8_t *)malloc(r.length);                          // the caller frees it (lj92.c:1136-1139)
     if (!e) return LJ92_NO_MEMORY;
-    memcpy(e, head, hl);
-    if (body && (!hip_ok(hipMemcpyAsync(e + hl, B + out_at, body, hipMemcpyDeviceToHost, s), "download") || !hip_ok(hipStreamSynchronize(s), "download"))) { free(e); return LJ92_CORRUPT; }
-    e[hl + body] = 0xFF;
-    e[hl + body + 1] = 0xD9;
+    if (!hip_ok(hipMemcpyAsync(e, d_out, r.length, hipMemcpyDeviceToHost, s), "download") || !hip_ok(hipStreamSynchronize(s), "download")) { free(e); return LJ92_CORRUPT; }
     *encoded = e;
-    *encodedLength = (int)(hl + body + 2);
+    *encodedLength = (int)r.length;
     return LJ92_OK;
 }
 

@@ -12,7 +12,11 @@
 //   bad pixels    the process's map per clip GUID (dropin.cpp, cs.c:233-312), detected by the first frame that reaches a repair; under
 //                 dual_iso = 2 a converted frame repairs inside the conversion, so until the map exists frames are served one by one
 //   dual ISO      the table caches of dualiso.cpp (process-wide), filled by the first frame that converts
+//
+// mlvfs_amd_mount_dng_lossless serves the same frames through the same stages; only the last step differs: the batch's final frames
+// are encoded where they lie (lje_encode_batch, k_lj92enc.hip) and their streams, not their pixels, cross the link.
 #include "clip.h"
+#include "lj92enc.h"
 
 #include <cstring>
 #include <string>
@@ -31,16 +35,17 @@ struct Mount {
     int stripes_needed = 0;
     int32_t coef[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     int device = -1;
-    void *d_frames = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-    size_t frames_bytes = 0, scratch_bytes = 0;
+    void *d_frames = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_bits = nullptr;
+    size_t frames_bytes = 0, scratch_bytes = 0, bits_bytes = 0;   // d_bits: the encoder's bit streams, sized from a batch's histograms
 
     void release()
     {
         if (d_frames) (void)hipFree(d_frames);
         if (d_out) (void)hipFree(d_out);
         if (d_scratch) (void)hipFree(d_scratch);
-        d_frames = d_out = d_scratch = nullptr;
-        frames_bytes = scratch_bytes = 0;
+        if (d_bits) (void)hipFree(d_bits);
+        d_frames = d_out = d_scratch = d_bits = nullptr;
+        frames_bytes = scratch_bytes = bits_bytes = 0;
     }
     ~Mount() { release(); }
 
@@ -67,6 +72,31 @@ struct Mount {
     }
 };
 
+// where a lossless call wants its answers (frame 0 of the batch first)
+struct Lossless {
+    size_t *sizes;
+    int *flags;
+};
+
+// the encoder's room in a mount: the bit streams in a buffer of their own that grows with what a batch needs, the streams
+// (one frame stride each) behind the encoder's fixed scratch in d_scratch
+struct MountRoom : LjeRoom {
+    Mount &m;
+    explicit MountRoom(Mount &m_) : m(m_) {}
+    int get(size_t bits_bytes, size_t, void **d_bits, uint8_t **, size_t *) override
+    {
+        if (m.bits_bytes < bits_bytes) {
+            if (m.d_bits) (void)hipFree(m.d_bits);
+            m.d_bits = nullptr;
+            m.bits_bytes = 0;
+            MLV_HIP(hipMalloc(&m.d_bits, bits_bytes));
+            m.bits_bytes = bits_bytes;
+        }
+        *d_bits = m.d_bits;
+        return MLVFS_AMD_OK;
+    }
+};
+
 bool same_levels(const frame_headers &a, const frame_headers &b)
 {
     return a.rawi_hdr.raw_info.black_level == b.rawi_hdr.raw_info.black_level && a.rawi_hdr.raw_info.white_level == b.rawi_hdr.raw_info.white_level;
@@ -82,8 +112,48 @@ size_t o_pn_bytes(const mlvfs_amd_mount_opts_t &o, int w, int h, int batch)
     return per * std::max<size_t>(1, std::min<size_t>((size_t)batch, pattern_noise_scratch_cap() / per));
 }
 
-// frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride)
-int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results)
+// The batch's final frames as lossless-JPEG streams: encoded where they lie, one copy of lengths and states, then the streams.
+// hdr_max[k]: the max_size the frame's header was last written with.  A frame that is not to be served compressed gets its pixels.
+int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at,
+                   const std::vector<size_t> &hdr_max, uint8_t *h_out, size_t out_stride, const Lossless &ll)
+{
+    hipStream_t s = c->stream;
+    const int w = fh[0].rawi_hdr.xRes, h = fh[0].rawi_hdr.yRes;
+    const size_t img = (size_t)w * h * 2, hdr = dng_get_header_size();
+    const bool pairs = !(h & 1);                                       // 2w x h/2: the row above is the same colour
+    const int jw = pairs ? 2 * w : w, jh = pairs ? h / 2 : h;
+    std::vector<LjeResult> res(n);
+    const size_t cap = img / 4 * 4;                                    // a stream longer than the pixels is not worth serving
+    bool encode = jw <= 65535 && jh <= 65535 && (uint64_t)w * h < (1u << 27) && cap >= 128;
+    uint8_t *d_streams = (uint8_t *)m.d_scratch + lje_fixed_bytes((uint32_t)(img / 2), n);
+    if (encode) {
+        std::vector<const uint16_t *> src(n);
+        for (int k = 0; k < n; k++) src[k] = (const uint16_t *)final_at[k];
+        MountRoom room(m);
+        size_t stream_stride = dstride;
+        const int rc = lje_encode_batch(src.data(), n, jw, jh, 16, nullptr, 0, m.d_scratch, room, &d_streams, &stream_stride, res.data(), s);
+        if (rc) return rc;
+    }
+    for (int k = 0; k < n; k++) {
+        uint8_t *file = h_out + k * out_stride;
+        const bool plain = !encode || res[k].status != LJE_OK || res[k].max_class >= 16 || res[k].length > cap;
+        ll.flags[k] = plain ? 1 : 0;
+        if (plain) {
+            ll.sizes[k] = hdr + img;
+            MLV_HIP(hipMemcpyAsync(file + hdr, final_at[k], img, hipMemcpyDeviceToHost, s));
+            continue;
+        }
+        ll.sizes[k] = hdr + res[k].length;
+        (void)mlvfs_amd_dng_header_lossless(&fh[k], file, 0, hdr_max[k], m.o.fps, m.basename.data(), res[k].length);
+        MLV_HIP(hipMemcpyAsync(file + hdr, d_streams + k * dstride, res[k].length, hipMemcpyDeviceToHost, s));
+    }
+    MLV_HIP(hipStreamSynchronize(s));
+    return MLVFS_AMD_OK;
+}
+
+// frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly
+int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results,
+                const Lossless *ll)
 {
     const mlvfs_amd_mount_opts_t &o = m.o;
     hipStream_t s = c->stream;
@@ -110,6 +180,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
     }
     // dual ISO (main.c:951-960)
     std::vector<int> conv(n, 0);
+    std::vector<size_t> hdr_max(n, hdr);
     if (o.dual_iso == 1) {
         for (int k0 = 0, k1; k0 < n; k0 = k1) {
             for (k1 = k0 + 1; k1 < n && same_levels(fh[k1], fh[k0]); k1++) {}
@@ -142,6 +213,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
         fh[k].rawi_hdr.raw_info.black_level *= 4;                      // hdr.c:223-224, 1951-1952
         fh[k].rawi_hdr.raw_info.white_level *= 4;
         (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, img, o.fps, m.basename.data());   // main.c:962-966
+        hdr_max[k] = img;
     }
     // frames that were not converted: focus pixels, bad pixels (main.c:967-975), in serve order
     for (int k = 0; k < n; k++) {
@@ -197,6 +269,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             if (rc) return rc;
         }
     }
+    if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll);
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], img, hipMemcpyDeviceToHost, s));
     MLV_HIP(hipStreamSynchronize(s));
     return MLVFS_AMD_OK;
@@ -226,9 +299,11 @@ void *mlvfs_amd_mount_open(const void *reader, const mlvfs_amd_mount_opts_t *opt
 
 void mlvfs_amd_mount_close(void *mount) { delete (Mount *)mount; }
 
-int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results)
+// both entry points
+static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
+                       int batch_frames, int io_threads, int *results)
 {
-    if (!mount || !h_out) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!mount || !h_out || (lossless && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
     Mount &m = *(Mount *)mount;
     if (count < 0) { set_error("mount: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     if (count == 0) return MLVFS_AMD_OK;
@@ -256,6 +331,7 @@ int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t o
     const size_t pn = o_pn_bytes(m.o, w, h, batch_frames);
     size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
     scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
+    if (lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
     int rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
     for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
         int n = std::min(batch_frames, count - f0);
@@ -264,12 +340,26 @@ int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t o
             if (!cached_bad_clip(&fh[f0], c, m.o.fix_bad_pixels == 2, &known)) n = 1;     // until the map exists: strictly in serve order
         }
         rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream);
-        if (rc == MLVFS_AMD_OK)
-            rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr);
+        if (rc == MLVFS_AMD_OK) {
+            const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
+            rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
+                             lossless ? &ll : nullptr);
+        }
         f0 += n;
     }
     if (rc != MLVFS_AMD_OK) (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results)
+{
+    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results);
+}
+
+int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,
+                                 int batch_frames, int io_threads, int *results)
+{
+    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, true, batch_frames, io_threads, results);
 }
 
 }  // extern "C"

@@ -58,6 +58,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_gif_size", "mlvfs_amd_gif_render", "mlvfs_amd_mlv_gif_data", "mlvfs_amd_process_unpacked_dev", "mlvfs_amd_deflicker_dev",
     "mlvfs_amd_fix_pattern_noise_dev", "mlvfs_amd_test_pn_scratch_cap", "mlvfs_amd_deflicker_batch_dev", "mlvfs_amd_hdr_preview_batch_dev",
     "mlvfs_amd_mount_open", "mlvfs_amd_mount_dng", "mlvfs_amd_mount_close",
+    "mlvfs_amd_lj92_encode_batch_dev", "mlvfs_amd_dng_header_lossless", "mlvfs_amd_mount_dng_lossless",
 ]
 
 
@@ -215,6 +216,9 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_mount_open", vp, [vp, C.POINTER(MountOpts), C.c_char_p])
     sig("mlvfs_amd_mount_dng", i, [vp, i, i, vp, sz, i, i, vp])
     sig("mlvfs_amd_mount_close", None, [vp])
+    sig("mlvfs_amd_lj92_encode_batch_dev", i, [vp, sz, i, i, i, i, vp, sz, vp, vp, vp, vp])
+    sig("mlvfs_amd_dng_header_lossless", sz, [fhp, vp, C.c_long, sz, C.c_double, C.c_char_p, C.c_uint32])
+    sig("mlvfs_amd_mount_dng_lossless", i, [vp, i, i, vp, sz, vp, vp, i, i, vp])
     _lib = L
     return L
 

@@ -54,6 +54,39 @@ def encode(flat, w: int, h: int, bits: int = 14, read_len: int = 0, skip_len: in
         libc.free(enc)
 
 
+STATUS_OK, STATUS_DIFF17, STATUS_TABLE, STATUS_NOFIT = 0, 1, 2, 3           # MLVFS_AMD_LJ92ENC_*
+
+
+def encode_batch(frames, bits: int = 16, out_stride: int = 0, torch_stream=None):
+    """mlvfs_amd_lj92_encode_batch_dev: a batch of frames of one geometry -> (streams, classes, status).
+
+    frames: an (n, h, w) CUDA/HIP tensor of 16-bit values (int16 or uint16 bit patterns; dim 0 may have any even byte stride) or a
+    host array / list of arrays, which is uploaded.  streams[f]: the complete JPEG stream as bytes, or None where status[f] is not
+    STATUS_OK (what the reference's encoder cannot encode inside its arrays, or a stream longer than out_stride);
+    classes[f]: the highest difference class in use.  out_stride: room per stream on the device (0: 4 bytes per pixel, twice the pixels'
+    own size; the worst case -- 16-bit codes, 16 value bits, every byte stuffed -- is 8)."""
+    import torch
+    L = lib.load()
+    if not isinstance(frames, torch.Tensor):
+        frames = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f, np.uint16) for f in frames])).view(np.int16)).cuda()
+    if frames.dim() != 3 or frames.element_size() != 2 or not frames.is_cuda:
+        raise ValueError("frames must be an (n, h, w) tensor of 16-bit values on the GPU")
+    n, h, w = frames.shape
+    if n and (frames.stride(2) != 1 or frames.stride(1) != w):
+        raise ValueError("each frame must be contiguous")
+    cap = out_stride or w * h * 4 + 1024
+    out = torch.empty((max(n, 1), cap), dtype=torch.uint8, device=frames.device)
+    lengths = np.zeros(max(n, 1), np.uint32)
+    status = np.zeros(max(n, 1), np.int32)
+    classes = np.zeros(max(n, 1), np.int32)
+    st = C.c_void_p(torch_stream.cuda_stream) if torch_stream is not None else None
+    lib.check(L.mlvfs_amd_lj92_encode_batch_dev(C.c_void_p(frames.data_ptr()), frames.stride(0) * 2 if n > 1 else w * h * 2, n, w, h, bits,
+                                                C.c_void_p(out.data_ptr()), cap, lib.ptr(lengths), lib.ptr(status), lib.ptr(classes), st),
+              "lj92_encode_batch_dev")
+    streams = [out[f, :int(lengths[f])].cpu().numpy().tobytes() if status[f] == STATUS_OK else None for f in range(n)]
+    return streams, [int(c) for c in classes[:n]], [int(v) for v in status[:n]]
+
+
 def encode_table(hist, npix: int):
     """Host-only: the encoder's Huffman table for a class histogram (mlvfs_amd_lj92_encode_table), or None where it refuses."""
     L = lib.load()

@@ -4,6 +4,8 @@
                                               basename="/M07-1234.MLV") as m:
         files = m.dng(0, 16, batch=8)       # (16, dng_size) uint8: 65536 header bytes + pixels per frame
 
+        small, flags = m.dng_lossless(16, 16)   # the same files with their pixels as one lossless-JPEG stream each
+
 Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
 """
 from __future__ import annotations
@@ -53,6 +55,22 @@ class Mount:
         lib.check(self.L.mlvfs_amd_mount_dng(self.h, first, count, lib.ptr(out), out.shape[1], batch, io_threads, lib.ptr(res)),
                   "mount_dng")
         return out
+
+    def dng_lossless(self, first: int, count: int, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None):
+        """The same frames as losslessly compressed .dng files (TIFF Compression 7, one lossless-JPEG stream per file):
+        -> (files, flags): files[k] the bytes of file k, flags[k] bit 0 set where the frame is served uncompressed (the file is then
+        byte for byte dng()'s)."""
+        stride = self.dng_size(first) if count else 0
+        out = np.zeros((count, stride), np.uint8)
+        sizes = np.zeros(max(count, 1), np.uintp)
+        flags = np.zeros(max(count, 1), np.int32)
+        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
+                                        and results.size >= count):
+            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
+        res = np.zeros(max(count, 1), np.int32) if results is None else results
+        lib.check(self.L.mlvfs_amd_mount_dng_lossless(self.h, first, count, lib.ptr(out), stride, lib.ptr(sizes), lib.ptr(flags), batch,
+                                                      io_threads, lib.ptr(res)), "mount_dng_lossless")
+        return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
 
     def close(self) -> None:
         if self.h:
