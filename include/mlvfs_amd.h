@@ -437,6 +437,17 @@ int mlvfs_amd_test_stream_plan(int width, int height, int seg_rows, int *cols, i
  * k_frame follows, k_frame's grid, groups, run, singles, first kernel's grid, rows per task, columns, segments, fold, tasks, k_frame_s
  * steps, work-list entries, status word watched (-1 none)}.  0, or MLVFS_AMD_ERR_ARG for a launch the fused pass refuses.          */
 int mlvfs_amd_test_frame_plan(const int *in, long long *out);
+/* Test hook, host only: the plan that the calling thread's most recent launch of the fused pass took -- as committed on its stream,
+ * the status words' verdicts included --, in the 15 fields of mlvfs_amd_test_frame_plan.  A thread-local copy made on the host; 0, or
+ * MLVFS_AMD_ERR_ARG if the thread has launched nothing yet.                                                                      */
+int mlvfs_amd_test_last_frame_plan(long long out[15]);
+/* Test hook: how many of k_frame's tiles the cs5x5 first kernels (k_frame_p, k_frame_p5) have handed to the list-mode k_frame on
+ * `stream` of the current device since the library first launched on it -- every tile with a strip whose packed median was not
+ * provably exact, and every task region with more pixel-map records than a wave has lanes; k_frame does those again, so a first
+ * kernel that lists everything still gives the right bytes.  Counts the launches that have ended (synchronise first); the difference
+ * across a launch against that launch's tiles is what the back-off weighs.  0, or MLVFS_AMD_ERR_ARG before the stream's first cs5x5
+ * launch with a first kernel.                                                                                                      */
+int mlvfs_amd_test_stream_listed(void *stream, long long *tiles);
 /* Test hook, host only: how a batch of `nframes` AMaZE dual-ISO conversions of width x height frames goes out (csrc/dualiso.cpp:
  * dualiso_parts), MLVFS_AMD_DI_PART read from the environment as a conversion reads it.  parts[2k] / parts[2k + 1]: first frame /
  * frames of part k; *tail: 1 if what follows each part's AMaZE runs on a second stream.  Returns the number of parts (at most

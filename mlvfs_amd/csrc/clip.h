@@ -138,6 +138,9 @@ int launch_unpack(const void *d_packed, size_t packed_stride, void *d_out, size_
 int launch_frame(const Device *dev, const Geom &g, bool packed, const void *src, size_t src_stride, void *dst,
                  size_t dst_stride, int nframes, int method, const PatchView *pv, bool stripes,
                  const int32_t *coef, hipStream_t stream, bool spread = false);       // spread: T16 layout for dark clips (k_frame.hip)
+// tiles that k_frame_p / k_frame_p5 have listed for the list-mode k_frame on `stream` of the current device since the stream's state
+// was created, as the launches that have ended reported them (status word 0: k_frame.hip); MLVFS_AMD_ERR_ARG: no such word yet
+int stream_listed_tiles(hipStream_t stream, long long *tiles);
 // share of sampled pixels of one frame that lie 1 .. 511 above black, in 1/1024 (synchronises the stream)
 int dark_share(int packed_bpp, const void *d_frame, int w, int h, int black, hipStream_t stream, int *share_1024);      // packed_bpp 0: 16-bit frames
 // does the fused kernel read this packed stream itself (k_frame.hip), or does it take an unpack pass first?

@@ -154,6 +154,21 @@ int plan_frame_pass(const FramePassInputs &in, const FrameSwitches &sw, const St
     return MLVFS_AMD_OK;
 }
 
+namespace {
+struct LastPlan { FramePlan plan; bool set = false; };
+LastPlan &last_plan() { static thread_local LastPlan t; return t; }
+
+// a plan as the 15 fields of the test hooks (include/mlvfs_amd.h: mlvfs_amd_test_frame_plan)
+void plan_fields(const FramePlan &p, long long *out)
+{
+    const long long o[15] = { (long long)p.first, p.list_after, p.grid, p.groups, p.run, p.singles, p.first_grid,
+                              p.seg_rows, p.cols, p.segs, p.fold, p.tasks, p.steps, p.wl_entries, p.watch.word };
+    for (int i = 0; i < 15; i++) out[i] = o[i];
+}
+}  // namespace
+
+void record_frame_plan(const FramePlan &p) { LastPlan &l = last_plan(); l.plan = p; l.set = true; }
+
 }  // namespace mlv
 
 // Test hook, host only (no GPU): how the streaming kernels cut a frame of width x height pixels into tasks of seg_rows cell rows
@@ -176,8 +191,21 @@ extern "C" int mlvfs_amd_test_frame_plan(const int *in, long long *out)
     const mlv::StreamVerdict v{ in[11] != 0, in[12] != 0 };
     mlv::FramePlan p;
     if (const int rc = mlv::plan_frame_pass(fi, mlv::frame_switches(), v, &p)) return rc;
-    const long long o[15] = { (long long)p.first, p.list_after, p.grid, p.groups, p.run, p.singles, p.first_grid,
-                              p.seg_rows, p.cols, p.segs, p.fold, p.tasks, p.steps, p.wl_entries, p.watch.word };
-    for (int i = 0; i < 15; i++) out[i] = o[i];
+    mlv::plan_fields(p, out);
+    return MLVFS_AMD_OK;
+}
+
+// Test hook: what the finished launches on a stream have listed for the list-mode k_frame (clip.h: stream_listed_tiles)
+extern "C" int mlvfs_amd_test_stream_listed(void *stream, long long *tiles)
+{
+    return tiles ? mlv::stream_listed_tiles((hipStream_t)stream, tiles) : MLVFS_AMD_ERR_ARG;
+}
+
+// Test hook, host only: the plan that the calling thread's most recent launch of the fused pass committed, in the same 15 fields
+extern "C" int mlvfs_amd_test_last_frame_plan(long long *out)
+{
+    const mlv::LastPlan &l = mlv::last_plan();
+    if (!out || !l.set) return MLVFS_AMD_ERR_ARG;
+    mlv::plan_fields(l.plan, out);
     return MLVFS_AMD_OK;
 }

@@ -62,4 +62,8 @@ struct FramePlan {
 int check_frame_pass(const FramePassInputs &in);
 int plan_frame_pass(const FramePassInputs &in, const FrameSwitches &sw, const StreamVerdict &v, FramePlan *out);
 
+// The plan the calling thread's most recent launch committed, kept for mlvfs_amd_test_last_frame_plan (a thread-local copy on the host:
+// the tests ask which kernels the launch they have just made took)
+void record_frame_plan(const FramePlan &p);
+
 }  // namespace mlv

@@ -598,6 +598,16 @@ static int plan_on_stream(hipStream_t stream, const FramePassInputs &in, FramePl
     *out = st;
     return MLVFS_AMD_OK;
 }
+int stream_listed_tiles(hipStream_t stream, long long *tiles)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return MLVFS_AMD_ERR_HIP;
+    std::lock_guard<std::mutex> lk(g_ticket_mu);
+    const auto it = g_tickets.find({ dev, stream });
+    if (it == g_tickets.end() || !it->second.h_stat) return MLVFS_AMD_ERR_ARG;
+    *tiles = (long long)(unsigned)__atomic_load_n(&it->second.h_stat[0], __ATOMIC_RELAXED);
+    return MLVFS_AMD_OK;
+}
 // The streams this library creates (per host thread, per host pipeline) give their counters back when they are destroyed: a
 // recycled stream handle then starts from freshly zeroed counters instead of whatever an aborted launch left behind, and
 // retired worker threads leak nothing.  Streams the caller owns keep their 8 KiB (and their list) until the process ends.
@@ -760,6 +770,7 @@ int launch_frame(const Device *dev, const Geom &g, bool packed, const void *src,
     FramePlan pl;
     StreamState sb;
     if (const int rc = plan_on_stream(stream, in, &pl, &sb)) return rc;
+    record_frame_plan(pl);
 
     a.tickets = sb.tickets;
     KernelTimer &tm = kernel_timer();

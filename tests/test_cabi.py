@@ -289,3 +289,23 @@ def test_fused_pass_plan(amd, monkeypatch):
     assert p["wl_entries"] >= 160 * 8 * 5 > 28 * 160
     # a launch the fused pass refuses
     assert plan(w=3583) is None and plan(cs=4) is None and plan(nframes=0) is None
+
+
+def test_last_frame_plan_hook_before_any_launch(amd):
+    """mlvfs_amd_test_last_frame_plan hands out the plan the calling thread's last launch of the fused pass took (the GPU tests of the
+    streaming kernels ask it which kernel they ran); a thread that has launched nothing gets MLVFS_AMD_ERR_ARG and its buffer back
+    untouched.  Host only; exported and declared like every other entry point."""
+    import threading
+    assert "mlvfs_amd_test_last_frame_plan" in lib.DEVICE_SYMBOLS and "mlvfs_amd_test_last_frame_plan" in declared_functions()
+    got = {}
+
+    def fresh_thread():
+        out = (C.c_longlong * 15)(*([-7] * 15))
+        got["rc"] = amd.mlvfs_amd_test_last_frame_plan(out)
+        got["out"] = list(out)
+        got["null"] = amd.mlvfs_amd_test_last_frame_plan(None)
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert got == {"rc": lib.ERR_ARG, "out": [-7] * 15, "null": lib.ERR_ARG}

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import stream_shapes as S
 from mlvfs_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -99,10 +100,16 @@ def test_fused_pipeline_rows_of_half_groups(torch_cuda, oracle, w, h, cs):
 def test_streaming_kernel_matches_oracle(torch_cuda, oracle, w, h, cs, stripes, monkeypatch):
     """k_frame_s (cs2x2 / cs3x3 without a pixel map: a wave per 62-item column, rows in registers, no barriers) takes long launches only
     (and hands footage with many pixels at or below black back to k_frame); MLVFS_AMD_KF_S=2 forces it wherever it can run, so that
-    its corners are compared with the oracle: one and several columns (496 px each), a last column of one item, a frame of one
-    narrow column whose segments are folded side by side (112 px), widths that are 8 mod 16, two-row frames, frames of one task and of several, every footage kind (the loader's form for pixels at or below
-    black, clamped look-ups), with and without the stripes epilogue.  The same launches through k_frame (MLVFS_AMD_KF_S=0) must
-    give the same bytes."""
+    its corners are compared with the oracle: one and several columns (496 px each); among the frames of two segments and more, one
+    column of 32 and of 62 items, last columns of 2 items (512 px: folded four to a wave, two parts), of 14 (608, 3584 and the single
+    column of 112 px: folded in four, three parts) and of 20 (656 px: folded in two, both parts), last segments of 1, 2, 5, 6 and 35
+    rows, one folded task per column; widths that are 8 mod 16 (one segment: never folded), two-row frames, frames of one task and of
+    several, every footage kind (the loader's form for pixels at or below black, clamped look-ups), with and without the stripes
+    epilogue.  The same launches through k_frame (MLVFS_AMD_KF_S=0) must give the same bytes, and each launch took the kernel it is
+    there for (mlvfs_amd_test_last_frame_plan): k_frame_s, except where a clip's stripe coefficients fall outside the packed 16-bit
+    form it reads (16x12 low-light frames), which is k_frame's.  There is no last column of one item here (columns are 62 items wide); that, the
+    widths on either side of the fold thresholds, folded columns of 8-mod-16 widths, four parts or one of two in the last folded
+    task, a full last segment and several folded tasks per column are in tests/test_gpu_stream_shapes.py."""
     from mlvfs_amd.stream import to_numpy_u16
     for kind in ("normal", "low_light", "colour_cast", "adversarial"):
         if kind in ("low_light", "colour_cast"):
@@ -117,6 +124,10 @@ def test_streaming_kernel_matches_oracle(torch_cuda, oracle, w, h, cs, stripes, 
             packed = s.upload_packed([synth.pack_bits(f) for f in frames])
             s.analyse_first_frame(packed, cs=cs, bad_pix=0, stripes=bool(stripes), rand_mode=1)
             out[mode] = to_numpy_u16(s.process(packed, cs=cs, fix_pixels=False, stripes=bool(stripes)))
+            generic = S.stripes_form(s, stripes) == 2         # coefficients beyond the packed form: k_frame's
+            if generic:
+                print(f"{w}x{h} {kind} cs {cs}: stripe coefficients beyond the packed form")
+            S.assert_took(S.P_S if mode == "2" and not generic else S.P_NONE, w, h, 60, f"{kind} MLVFS_AMD_KF_S={mode}")
             s.close()
         for k in range(3):
             assert np.array_equal(out["2"][k], want[k]), f"{kind} frame {k}: {(out['2'][k] != want[k]).sum()} px differ (k_frame_s)"
@@ -129,9 +140,15 @@ def test_streaming_cs5x5_kernel_matches_oracle(torch_cuda, oracle, w, h, bad, st
     """k_frame_p5 (the packed-once pass as a streaming kernel: a wave per 62-item column, the five packed rows of the window in
     registers, pixel-map records collected per task, uncertain strips' tiles to the work list for the list-mode k_frame) takes long
     launches only; MLVFS_AMD_KF_P5=2 with MLVFS_AMD_KF_P=2 forces it (and the list-mode launch behind it) wherever it can run: one
-    and several columns, a last column of one item, widths that are 8 mod 16, tasks of a few rows, every footage kind (adversarial:
+    and several columns, in tasks of 30 rows (a forced short launch never gets 60); among the frames of two segments and more, one
+    column of 32 and of 62 items, last columns of 2 items (512 and 1008 px: folded four to a wave, three and two parts), of 14 (3584
+    px: two parts; 608 px: two folded tasks, one part in the last), of 20 (656 px: folded in two, two tasks of two parts) and of 31
+    (1736 px, 8 mod 16: not folded), last segments of 1, 2, 3 and 5 rows; tasks of a few rows, every footage kind (adversarial:
     thousands of pixel-map cells and pixels at black -- the dense-map and the dark-row paths; colour patches: everything uncertain),
-    pixel maps of both detection modes, with and without stripes."""
+    pixel maps of both detection modes, with and without stripes.  Every launch took k_frame_p5 (mlvfs_amd_test_last_frame_plan),
+    except where a clip's stripe coefficients fall outside the packed 16-bit form it reads (16x12: k_frame_p takes those).
+    There is no last column of one item here (columns are 62 items wide); the other task shapes, 60-row tasks and focus-pixel maps
+    are in tests/test_gpu_stream_shapes.py."""
     from mlvfs_amd.stream import to_numpy_u16
     monkeypatch.setenv("MLVFS_AMD_KF_P", "2")
     monkeypatch.setenv("MLVFS_AMD_KF_P5", "2")
@@ -145,6 +162,10 @@ def test_streaming_cs5x5_kernel_matches_oracle(torch_cuda, oracle, w, h, bad, st
         packed = s.upload_packed([synth.pack_bits(f) for f in frames])
         s.analyse_first_frame(packed, cs=5, bad_pix=bad, stripes=bool(stripes), rand_mode=1)
         got = to_numpy_u16(s.process(packed, cs=5, fix_pixels=bool(bad), stripes=bool(stripes)))
+        generic = S.stripes_form(s, stripes) == 2             # coefficients beyond the packed form: k_frame_p's
+        if generic:
+            print(f"{w}x{h} {kind} bad {bad}: stripe coefficients beyond the packed form")
+        S.assert_took(S.P_TILES if generic else S.P_P5, w, h, 30, f"{kind} bad {bad} stripes {stripes}")
         s.close()
         for k in range(3):
             assert np.array_equal(got[k], want[k]), f"{kind} frame {k}: {(got[k] != want[k]).sum()} px differ"
@@ -153,7 +174,8 @@ def test_streaming_cs5x5_kernel_matches_oracle(torch_cuda, oracle, w, h, bad, st
 def test_streaming_cs5x5_one_tile_row(torch_cuda, oracle, monkeypatch):
     """Frames one tile row high (3584x30) forced through k_frame_p5 (MLVFS_AMD_KF_P=2, MLVFS_AMD_KF_P5=2): a task lists up to five tile
     columns, so 160 frames of colour patches, where most strips are uncertain, can list more entries than the launch has tiles.  The
-    work list is sized from the plan (csrc/frame_plan.cpp); every frame equals the oracle's."""
+    work list is sized from the plan (csrc/frame_plan.cpp); every frame equals the oracle's, and the launch took k_frame_p5 in eight
+    tasks of one segment per frame."""
     from mlvfs_amd.stream import to_numpy_u16
     monkeypatch.setenv("MLVFS_AMD_KF_P", "2")
     monkeypatch.setenv("MLVFS_AMD_KF_P5", "2")
@@ -167,6 +189,8 @@ def test_streaming_cs5x5_one_tile_row(torch_cuda, oracle, monkeypatch):
     for i in range(0, nf, 8):
         packed[i:i + 8] = base
     got = to_numpy_u16(s.process(packed, cs=5, fix_pixels=False, stripes=False))
+    p = S.assert_took(S.P_P5, w, h, 30, "3584x30")
+    assert (p["cols"], p["segs"], p["fold"], p["tasks"]) == (8, 1, 1, 8 * nf) and p["wl_entries"] >= 8 * 5 * nf
     s.close()
     for i in range(nf):
         assert np.array_equal(got[i], want[i % 8]), f"frame {i}: {(got[i] != want[i % 8]).sum()} px differ"
@@ -176,10 +200,12 @@ def test_streaming_cs5x5_one_tile_row(torch_cuda, oracle, monkeypatch):
 @pytest.mark.parametrize("cs,bad", [(5, 1), (5, 0), (2, 0)])
 def test_long_launches_default_policy(torch_cuda, oracle, kind, cs, bad):
     """The library's own choice of kernels (no switches set) on launches long enough for the streaming kernels -- 3 600 frames of
-    512x124: k_frame_p5 / k_frame_s take the first launch, the status words of finished launches then move low-light footage to
-    k_frame_p + list and colour patches to k_frame alone (csrc/k_frame.hip: Backoff).  Five launches in a row,
-    the first three with the stream drained in between (every status word seen), the last two back to back: every launch's first,
-    middle and last frames equal the oracle's."""
+    512x124: k_frame_s (cs2x2) and, on the benchmark's footage kind, k_frame_p5 (60-row tasks: two segments, the last of two rows) take
+    the first launch; the status words of finished launches move low-light footage to k_frame_p + list and colour patches to k_frame
+    alone (csrc/k_frame.hip: Backoff) -- with cs5x5 from the first launch on, which the first frame's analysis precedes.  Five
+    launches in a row, the first three with the stream drained in between (every status word seen), the last two back to back: every launch's first,
+    middle and last frames equal the oracle's.  On a stream of its own: the back-off is kept per stream, and what the tests before
+    this one left in the default stream's would decide the first launch, whose kernel is asserted."""
     import torch
     from mlvfs_amd.stream import to_numpy_u16
     for v in ("MLVFS_AMD_KF_P", "MLVFS_AMD_KF_P5", "MLVFS_AMD_KF_S"):
@@ -190,23 +216,31 @@ def test_long_launches_default_policy(torch_cuda, oracle, kind, cs, bad):
     else:
         frames = [getattr(synth, kind + "_frame")(w, h, seed=5 + k) for k in range(8)]
     want, pixels, corr = oracle_clip(oracle, frames, w, h, cs, bad, 1)
-    s = make_stream(w, h)
-    base = s.upload_packed([synth.pack_bits(f) for f in frames])
-    s.analyse_first_frame(base, cs=cs, bad_pix=bad, stripes=True, rand_mode=1)
-    packed = s.alloc_packed(nf)
-    for i in range(0, nf, 8):
-        packed[i:i + 8] = base
-    out = s.alloc_out(nf)
-    sample = list(range(8)) + list(range(1796, 1804)) + list(range(nf - 8, nf))
-    for launch in range(5):
-        out.zero_()
-        s.process(packed, out, cs=cs, fix_pixels=bool(bad), stripes=True)
-        if launch < 3:
-            torch.cuda.synchronize()
-        got = to_numpy_u16(out[sample])
-        for n, i in enumerate(sample):
-            assert np.array_equal(got[n], want[i % 8]), f"{kind} cs{cs} launch {launch} frame {i}: {(got[n] != want[i % 8]).sum()} px differ"
-    s.close()
+    # the first launch: the streaming kernel -- unless, cs5x5, the chroma smoothing of the first frame's analysis (k_frame_p + list on that
+    # one frame, same stream) has already reported its share listed: over 5 % on low-light footage, over 30 % on colour patches
+    first_kernel = S.P_S if cs != 5 else {"normal": S.P_P5, "low_light": S.P_TILES, "colour_cast": S.P_NONE}[kind]
+    with torch.cuda.stream(torch.cuda.Stream()):
+        s = make_stream(w, h)
+        base = s.upload_packed([synth.pack_bits(f) for f in frames])
+        s.analyse_first_frame(base, cs=cs, bad_pix=bad, stripes=True, rand_mode=1)
+        packed = s.alloc_packed(nf)
+        for i in range(0, nf, 8):
+            packed[i:i + 8] = base
+        out = s.alloc_out(nf)
+        sample = list(range(8)) + list(range(1796, 1804)) + list(range(nf - 8, nf))
+        for launch in range(5):
+            out.zero_()
+            s.process(packed, out, cs=cs, fix_pixels=bool(bad), stripes=True)
+            if launch == 0:
+                p = S.last_plan()
+                assert p["first"] == first_kernel, p
+                assert p["seg_rows"] == 0 or (p["cols"], p["segs"], p["fold"]) == S.stream_plan(w, h, p["seg_rows"])[:3], p
+            if launch < 3:
+                torch.cuda.synchronize()
+            got = to_numpy_u16(out[sample])
+            for n, i in enumerate(sample):
+                assert np.array_equal(got[n], want[i % 8]), f"{kind} cs{cs} launch {launch} frame {i}: {(got[n] != want[i % 8]).sum()} px differ"
+        s.close()
 
 
 def test_fused_adversarial(torch_cuda, oracle):
