@@ -112,6 +112,7 @@ int *get_ev2raw(void);
 #define MLVFS_AMD_ERR_ARG      -2     /* bad geometry / argument                      */
 #define MLVFS_AMD_ERR_LUT      -3     /* host libm tables fail the compression check  */
 #define MLVFS_AMD_ERR_NOMEM    -4
+#define MLVFS_AMD_ERR_IO       -5     /* a file could not be created, read or written (mlvfs_amd_mlv_transcode) */
 
 typedef struct {
     int32_t width, height;        /* rawi_hdr.xRes / yRes                         */
@@ -155,6 +156,13 @@ size_t mlvfs_amd_clip_get_pixel_map(const mlvfs_amd_clip_t *clip, int32_t *xy, s
 /* frames are `nframes` buffers spaced by the given strides (bytes)           */
 int mlvfs_amd_unpack_dev(const mlvfs_amd_geom_t *geom, const void *d_packed, size_t packed_stride,
                          void *d_out, size_t out_stride, int nframes, void *stream);
+/* the inverse of mlvfs_amd_unpack_dev (csrc/k_mlvpack.hip): 16-bit frames -> packed payloads of geom->bpp bits (1..16), pixel i in
+ * bits [i * bpp, (i + 1) * bpp) of an MSB-first stream of little-endian 16-bit words.  Exactly ceil(width * height * bpp / 16) words
+ * are written per frame -- the unused low bits of the last word are zero, nothing behind it is touched --; pixels are masked to bpp
+ * bits.  14 / 12 / 10 bits with width * height a multiple of 16, d_frames 16-byte and d_packed 4-byte aligned (strides likewise)
+ * take the fast form: 16 pixels in, bpp / 2 dwords out per lane.                                                             */
+int mlvfs_amd_pack_dev(const mlvfs_amd_geom_t *geom, const void *d_frames, size_t stride, void *d_packed, size_t packed_stride,
+                       int nframes, void *stream);
 int mlvfs_amd_chroma_smooth_dev(const mlvfs_amd_geom_t *geom, const void *d_in, void *d_out, size_t stride,
                                 int method, int nframes, void *stream);
 /* detection on one frame; fills the clip's pixel map (synchronises the stream) */
@@ -271,6 +279,13 @@ int mlvfs_amd_lj92_encode_table(const uint32_t hist[17], int npix, int *out);
 #define MLVFS_AMD_LJ92ENC_NOFIT   3     /* the stream is longer than out_stride */
 int mlvfs_amd_lj92_encode_batch_dev(const void *d_frames, size_t stride, int nframes, int width, int height, int bitdepth, void *d_out,
                                     size_t out_stride, uint32_t *lengths, int *status, int *max_class, void *stream);
+/* What an MLV writer hands to that encoder: the four Bayer channels of a frame as the four quadrants of one image, the inverse of
+ * get_image_data's untiling loop (main.c:656-667).  Tiled row y, column x holds source pixel (ty, tx), ty = (2y) % H + (2y) / H,
+ * tx = (2x) % W + (2x) / W.  nframes frames of width x height 16-bit pixels `stride` bytes apart -> the same at d_out, out_stride
+ * bytes apart; d_out != d_frames.  For an odd width or height the reference's map is no bijection (H = 5: rows 1 and 3 are never
+ * written): refused.  A width that is a multiple of 8 with 16-byte aligned buffers and strides takes the fast form.              */
+int mlvfs_amd_lj92_tile_dev(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int width, int height, int nframes,
+                            void *stream);
 
 /* -- LZMA payloads ----------------------------------------- */
 /* One VIDF payload of an LZMA-compressed clip (MLV_VIDEO_CLASS_FLAG_LZMA; main.c:598-616): [u32 size of the packed frame][5 LZMA
@@ -307,6 +322,25 @@ int    mlvfs_amd_mlv_process(const void *reader, mlvfs_amd_clip_t *clip, int fir
  * level 4x the headers'), 0: no dual-ISO frame, h_out holds it unpacked.  Plain and LZMA clips. */
 int    mlvfs_amd_mlv_process_dualiso(const void *reader, int first, int count, void *h_out, size_t out_stride, int interp_method,
                                      int fullres, int use_alias_map, int chroma_smooth, int batch_frames, int io_threads, int *results);
+/* An opened clip, whatever its payloads are (plain, LZMA, LJ92), written again as an MLV with lossless-JPEG payloads (what
+ * `mlv_dump -c` writes) or plain packed ones (`-d`) -- csrc/mlvwriter.cpp.  out_path ends in .MLV; source chunk i (.M00, ...) becomes
+ * out_path with its last two characters replaced by the chunk's number.  Every output chunk holds its source chunk's blocks in the
+ * source's file order, byte for byte, except: MLVI gets MLV_VIDEO_CLASS_FLAG_LJ92 (0x100) set or cleared and the LZMA flag (0x80)
+ * cleared; VIDF keeps its header with frameSpace = 0 and blockSize = header + payload; NULL and XREF blocks are dropped; no .IDX is
+ * written.  An LJ92 payload is [u32 = w * h * 2][the stream lj92_encode writes for the quadrant-tiled frame as one component of
+ * w x h at bits_per_pixel precision] with nothing behind it; a plain one is ceil(w * h * bpp / 16) words.  Frames go through the GPU
+ * in batches of batch_frames (<= 0: 8) frames of one geometry, in a chunk's file order: decode / unpack, mlvfs_amd_lj92_tile_dev and
+ * the batch encoder, or (LJ92 to plain) mlvfs_amd_pack_dev.  Plain output of a plain or LZMA clip is host code and needs no HIP device.
+ * MLVFS_AMD_ERR_ARG before any device work: a null argument, an out_path that does not end in .MLV / .mlv or names a file of the
+ * source, an output file or <stem>.IDX that exists (nothing is overwritten), a video class other than raw or with the DELTA flag,
+ * LJ92 output of a frame of odd width or height.  A frame the encoder cannot encode inside the reference's arrays, or one with a
+ * difference of class 16 (the reference then writes value bits the JPEG standard does not have), fails the call; the error names the
+ * frame.  A source block that cannot be read in full and an output file that cannot be created, written or closed are
+ * MLVFS_AMD_ERR_IO.  After any failure none of the call's output files are left.  stats: {video frames written, payload bytes in the source,
+ * payload bytes written, files written}.  Calls on one reader are serialised with its other streaming calls.                      */
+#define MLVFS_AMD_MLV_PLAIN 0
+#define MLVFS_AMD_MLV_LJ92  1
+int    mlvfs_amd_mlv_transcode(const void *reader, const char *out_path, int payload, int batch_frames, int io_threads, long long stats[4]);
 
 /* -- animated GIF preview (gif.c:82-244) ---------------------- */
 /* = gif_get_size: size of the preview file of a clip with these frame headers                                        */

@@ -5,6 +5,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -187,6 +188,26 @@ void deflicker_bias(int target, int black_level, uint16_t median, int32_t exposu
 // the mount's reader half (mlvreader.cpp): frames of one geometry from the file to 16-bit pixels in HBM; synchronises s
 int reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
                       hipStream_t s);
+// the same for frames named one by one (all of one geometry and payload kind); stage_locked: the caller holds reader_stage_mutex
+int reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
+                     hipStream_t s, bool stage_locked);
+// what the transcoder (mlvwriter.cpp) asks of an opened clip: its path and chunk files, where a frame's VIDF block lies, the bytes of
+// its payload as read_frames (lj92: as the LJ92 decoder) takes it, packed payloads of plain and LZMA frames (host only), and the
+// mutex that serialises the reader's streaming calls
+const char *reader_path(const void *reader);
+int reader_chunk_fd(const void *reader, int chunk);
+bool reader_frame_place(const void *reader, int index, int *chunk, uint64_t *offset);
+bool reader_payload_bytes(const void *reader, int index, bool lj92, size_t *bytes);
+int reader_read_list(const void *reader, const int *list, int count, uint8_t *dst, size_t stride, int io_threads);
+// every block of every chunk in file order, exactly as the reader's own index scan walks them (NULL blocks included):
+// visit(chunk, position, tag, block size, the MLVI block's header or nullptr); false ends the walk
+void reader_walk_blocks(const void *reader, const std::function<bool(int, uint64_t, const uint8_t *, uint32_t, const mlv_file_hdr_t *)> &visit);
+std::mutex &reader_stage_mutex(const void *reader);
+// quadrant tiling and bit packing (k_mlvpack.hip)
+int launch_mlv_tile(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int nframes, hipStream_t stream);
+int launch_mlv_pack(const void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int nframes,
+                    hipStream_t stream);
+void preload_k_mlvpack();
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

@@ -1,0 +1,184 @@
+// k_mlvpack.hip -- the two passes that turn 16-bit frames in HBM back into what an MLV file stores (csrc/mlvwriter.cpp):
+//
+//   k_mlv_tile_*   the four Bayer channels of a frame as the four quadrants of one image, what an MLV writer hands to lj92_encode.
+//                  The inverse of the untiling loop of get_image_data (mlvfs/main.c:656-667): tiled row y, column x holds source
+//                  pixel (ty, tx) with ty = (2y) % H + (2y) / H, tx = (2x) % W + (2x) / W.  For even W and H that is a bijection:
+//                  source pixel (sy, sx) goes to row sy / 2 + (sy & 1) * H / 2, column sx / 2 + (sx & 1) * W / 2.  (For an odd size
+//                  the reference's map writes some rows twice and others never; the launcher refuses those.)
+//   k_mlv_pack_*   16-bit pixels -> packed payload, the inverse of k_unpack.hip: pixel i is bits [i*bpp, (i+1)*bpp) of an MSB-first
+//                  bit stream stored as little-endian 16-bit words (mlvfs/raw.h:41-79).  Exactly ceil(npix * bpp / 16) words are
+//                  written; pixels are masked to bpp bits.
+//
+// Both are HBM-bound (tile: 2 B read + 2 B written per pixel; pack at 14 bits: 2 B + 1.75 B, k_unpack_x16<14>'s traffic the other
+// way round).  One lane moves 16 bytes per load; the lanes of a wave are contiguous in the source and in the destination; frames
+// are batched in grid.y.
+//   k_mlv_tile_x<16 | 8> : one lane = 16 (8) consecutive pixels of one source row = two (one) 128-bit loads; their even and their odd
+//                  pixels leave as two runs of 16 (8) bytes, one into the left half of the destination row, one into the right.
+//   k_mlv_tile_generic : any even width and height; one lane = one destination pixel.
+//   k_mlv_pack_x16<14 | 12 | 10> : one lane = 16 pixels = two 128-bit loads and 7 / 6 / 5 coalesced dword stores.
+//   k_mlv_pack_generic : any bpp in 1..16, any length; one lane = one output word (the pixels that touch it: 2 at 14 bits, 16 at 1).
+#include "clip.h"
+
+namespace mlv {
+
+// the even (low) and the odd (high) halves of two dwords of pixel pairs
+__device__ __forceinline__ uint32_t evens(uint32_t a, uint32_t b) { return (a & 0xFFFFu) | (b << 16); }
+__device__ __forceinline__ uint32_t odds(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xFFFF0000u); }
+
+// PX = 16: W % 16 == 0; PX = 8: W % 8 == 0.  groups = W / PX * H per frame, in source order.
+template <int PX>
+__global__ __launch_bounds__(256) void k_mlv_tile_x(const uint8_t *__restrict__ frames, size_t stride, uint8_t *__restrict__ out,
+                                                    size_t out_stride, uint32_t groups, uint32_t groups_per_row, uint32_t w, uint32_t h)
+{
+    const uint4 *src = (const uint4 *)(frames + (size_t)blockIdx.y * stride);
+    uint16_t *dst = (uint16_t *)(out + (size_t)blockIdx.y * out_stride);
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        const uint32_t sy = g / groups_per_row, gx = g - sy * groups_per_row;
+        const uint32_t dy = (sy >> 1) + (sy & 1u) * (h >> 1);
+        uint16_t *row = dst + (size_t)dy * w + (size_t)gx * (PX / 2);
+        if (PX == 16) {
+            const uint4 a = src[(size_t)g * 2], b = src[(size_t)g * 2 + 1];
+            uint4 e, o;
+            e.x = evens(a.x, a.y); e.y = evens(a.z, a.w); e.z = evens(b.x, b.y); e.w = evens(b.z, b.w);
+            o.x = odds(a.x, a.y);  o.y = odds(a.z, a.w);  o.z = odds(b.x, b.y);  o.w = odds(b.z, b.w);
+            *(uint4 *)row = e;
+            *(uint4 *)(row + (w >> 1)) = o;
+        } else {
+            const uint4 a = src[g];
+            uint2 e, o;
+            e.x = evens(a.x, a.y); e.y = evens(a.z, a.w);
+            o.x = odds(a.x, a.y);  o.y = odds(a.z, a.w);
+            *(uint2 *)row = e;
+            *(uint2 *)(row + (w >> 1)) = o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mlv_tile_generic(const uint8_t *__restrict__ frames, size_t stride, uint8_t *__restrict__ out,
+                                                          size_t out_stride, uint32_t npix, uint32_t w, uint32_t h)
+{
+    const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
+    uint16_t *dst = (uint16_t *)(out + (size_t)blockIdx.y * out_stride);
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < npix; k += gridDim.x * blockDim.x) {
+        const uint32_t y = k / w, x = k - y * w;
+        const uint32_t ty = y < (h >> 1) ? 2 * y : 2 * y - h + 1, tx = x < (w >> 1) ? 2 * x : 2 * x - w + 1;
+        dst[k] = src[(size_t)ty * w + tx];
+    }
+}
+
+// 16 pixels of BPP bits (BPP even) -> BPP / 2 little-endian dwords of the MSB-first stream
+template <int BPP>
+__device__ __forceinline__ void pack_x16(const uint32_t (&px)[16], uint32_t (&le)[BPP / 2])
+{
+    constexpr uint32_t mask = (1u << BPP) - 1u;
+    uint32_t s[BPP / 2];
+#pragma unroll
+    for (int i = 0; i < BPP / 2; i++) s[i] = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const int bit = BPP * k, wi = bit >> 5, sh = bit & 31;
+        const uint32_t v = px[k] & mask;
+        if (sh + BPP <= 32) {
+            s[wi] |= v << (32 - BPP - sh);
+        } else {
+            s[wi] |= v >> (sh + BPP - 32);
+            s[wi + 1] |= v << (64 - BPP - sh);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < BPP / 2; i++) le[i] = (s[i] << 16) | (s[i] >> 16);      // 32 stream bits -> two little-endian words
+}
+
+template <int BPP>
+__global__ __launch_bounds__(256) void k_mlv_pack_x16(const uint8_t *__restrict__ frames, size_t stride, uint8_t *__restrict__ packed,
+                                                      size_t packed_stride, uint32_t groups)
+{
+    constexpr int NW = BPP / 2;
+    const uint4 *src = (const uint4 *)(frames + (size_t)blockIdx.y * stride);
+    uint32_t *dst = (uint32_t *)(packed + (size_t)blockIdx.y * packed_stride);
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        const uint4 a = src[(size_t)g * 2], b = src[(size_t)g * 2 + 1];
+        const uint32_t in[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+        uint32_t px[16], le[NW];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { px[2 * i] = in[i] & 0xFFFFu; px[2 * i + 1] = in[i] >> 16; }
+        pack_x16<BPP>(px, le);
+#pragma unroll
+        for (int i = 0; i < NW; i++) dst[(size_t)g * NW + i] = le[i];
+    }
+}
+
+// word j holds stream bits [16j, 16j + 16): the pixels floor(16j / bpp) .. floor((16j + 15) / bpp), as far as the frame has them
+__global__ __launch_bounds__(256) void k_mlv_pack_generic(const uint8_t *__restrict__ frames, size_t stride, uint8_t *__restrict__ packed,
+                                                          size_t packed_stride, uint32_t npix, uint32_t nwords, int bpp)
+{
+    const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
+    uint16_t *dst = (uint16_t *)(packed + (size_t)blockIdx.y * packed_stride);
+    const uint32_t mask = (1u << bpp) - 1u;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nwords; j += gridDim.x * blockDim.x) {
+        const uint32_t bit0 = j * 16u;
+        const uint32_t first = bit0 / (uint32_t)bpp;
+        uint32_t last = (bit0 + 15u) / (uint32_t)bpp;
+        if (last > npix - 1) last = npix - 1;
+        uint32_t word = 0;
+        for (uint32_t i = first; i <= last; i++) {
+            const uint32_t v = src[i] & mask;
+            // the pixel's lowest bit is stream bit i * bpp + bpp - 1; stream bit b of this word is bit 15 - (b - bit0)
+            const int sh = 15 - (int)(i * (uint32_t)bpp + (uint32_t)bpp - 1u - bit0);
+            word |= sh >= 0 ? v << sh : v >> -sh;
+        }
+        dst[j] = (uint16_t)word;
+    }
+}
+
+static uint32_t grid_x(uint32_t items, uint32_t cap) { return std::min<uint32_t>((items + 255) / 256, cap); }
+
+// d_out != d_frames; w and h even (the callers check)
+int launch_mlv_tile(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int nframes, hipStream_t stream)
+{
+    if (nframes <= 0) return MLVFS_AMD_OK;
+    if (w <= 0 || h <= 0 || (w & 1) || (h & 1)) { set_error("quadrant tiling takes even sizes, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;
+    const bool aligned = ((uintptr_t)d_frames % 16 == 0) && ((uintptr_t)d_out % 16 == 0) && (nframes == 1 || (stride % 16 == 0 && out_stride % 16 == 0));
+    const int px = !aligned ? 0 : (w % 16 == 0 ? 16 : (w % 8 == 0 ? 8 : 0));
+    if (px) {
+        const uint32_t gpr = (uint32_t)w / px, groups = gpr * (uint32_t)h;
+        const dim3 grid(grid_x(groups, 8192), nframes);
+        hipLaunchKernelGGL(px == 16 ? k_mlv_tile_x<16> : k_mlv_tile_x<8>, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                           (uint8_t *)d_out, out_stride, groups, gpr, (uint32_t)w, (uint32_t)h);
+    } else {
+        const dim3 grid(grid_x(npix, 16384), nframes);
+        hipLaunchKernelGGL(k_mlv_tile_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (uint8_t *)d_out, out_stride,
+                           npix, (uint32_t)w, (uint32_t)h);
+    }
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+int launch_mlv_pack(const void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int nframes,
+                    hipStream_t stream)
+{
+    if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
+    if (bpp < 1 || bpp > 16) { set_error("unsupported bits_per_pixel %d", bpp); return MLVFS_AMD_ERR_ARG; }
+    if (npix >= (1u << 27)) { set_error("more than 2^27 pixels"); return MLVFS_AMD_ERR_ARG; }       // bit positions are 32-bit
+    const bool fast = (bpp == 14 || bpp == 12 || bpp == 10) && npix % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) &&
+                      ((uintptr_t)d_packed % 4 == 0) && (nframes == 1 || (stride % 16 == 0 && packed_stride % 4 == 0));
+    if (fast) {
+        const uint32_t groups = npix / 16;
+        const dim3 grid(grid_x(groups, 8192), nframes);
+        auto kern = bpp == 14 ? k_mlv_pack_x16<14> : (bpp == 12 ? k_mlv_pack_x16<12> : k_mlv_pack_x16<10>);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (uint8_t *)d_packed, packed_stride, groups);
+    } else {
+        const uint32_t nwords = (uint32_t)(((uint64_t)npix * bpp + 15) / 16);
+        const dim3 grid(grid_x(nwords, 16384), nframes);
+        hipLaunchKernelGGL(k_mlv_pack_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (uint8_t *)d_packed,
+                           packed_stride, npix, nwords, bpp);
+    }
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+// (see preload_k_unpack: the transcoder asks before its first batch, so that the first batch's timing is the others')
+void preload_k_mlvpack() { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, (const void *)k_mlv_tile_x<16>); (void)hipGetLastError(); }
+
+}  // namespace mlv

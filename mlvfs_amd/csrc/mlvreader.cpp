@@ -147,38 +147,49 @@ bool open_chunks(Reader &r)
 // ---- index ----------------------------------------------------------------------------------------------------------
 struct Timed { uint64_t time; XrefEntry e; };
 
-void scan_chunks(Reader &r)
+// The one walk over the chunk files (index.c:216-341), block by block in file order, for the index below and for the transcoder
+// (mlvwriter.cpp: reader_walk_blocks): visit(chunk, position, block head, the MLVI block's header or nullptr); false ends the walk.
+// A chunk's walk ends at a block head that cannot be read, at an impossible size, and at an MLVI of another recording.
+template <typename Visit>
+void walk_blocks(const std::vector<int> &fds, Visit visit)
 {
-    std::vector<Timed> all;
     mlv_file_hdr_t first{};                                         // the MLVI with fileNum 0; all zero until one is seen
-    for (size_t c = 0; c < r.fds.size(); c++) {
+    for (size_t c = 0; c < fds.size(); c++) {
         uint64_t pos = 0;
         for (;;) {
             BlockHead h;
-            if (!read_at(r.fds[c], &h, sizeof h, pos)) break;
+            if (!read_at(fds[c], &h, sizeof h, pos)) break;
             if (h.size < sizeof h || h.size > (1u << 30)) {
                 fprintf(stderr, "Invalid header size: %d bytes at 0x%08llX\n", (int)h.size, (unsigned long long)pos);
                 break;
             }
-            uint64_t t = h.timestamp;
-            if (!memcmp(h.type, "MLVI", 4)) {
-                mlv_file_hdr_t fh{};
-                if (!read_at(r.fds[c], &fh, std::min<size_t>(sizeof fh, h.size), pos)) break;
+            mlv_file_hdr_t fh{};
+            const bool mlvi = !memcmp(h.type, "MLVI", 4);
+            if (mlvi) {
+                if (!read_at(fds[c], &fh, std::min<size_t>(sizeof fh, h.size), pos)) break;
                 if (fh.fileNum == 0) first = fh;
                 else if (first.fileGuid != fh.fileGuid) break;      // a chunk of another recording: stop reading it
-                t = 0;                                               // the bytes at the timestamp's place are the version string
             }
-            if (memcmp(h.type, "NULL", 4)) {
-                Timed x{};
-                x.time = t;
-                x.e.file = (uint16_t)c;
-                x.e.kind = !memcmp(h.type, "VIDF", 4) ? KIND_VIDF : !memcmp(h.type, "AUDF", 4) ? KIND_AUDF : KIND_OTHER;
-                x.e.offset = pos;
-                all.push_back(x);
-            }
+            if (!visit((int)c, pos, h, mlvi ? &fh : nullptr)) return;
             pos += h.size;
         }
     }
+}
+
+void scan_chunks(Reader &r)
+{
+    std::vector<Timed> all;
+    walk_blocks(r.fds, [&](int c, uint64_t pos, const BlockHead &h, const mlv_file_hdr_t *mlvi) {
+        if (memcmp(h.type, "NULL", 4)) {
+            Timed x{};
+            x.time = mlvi ? 0 : h.timestamp;                         // MLVI: the bytes at the timestamp's place are the version string
+            x.e.file = (uint16_t)c;
+            x.e.kind = !memcmp(h.type, "VIDF", 4) ? KIND_VIDF : !memcmp(h.type, "AUDF", 4) ? KIND_AUDF : KIND_OTHER;
+            x.e.offset = pos;
+            all.push_back(x);
+        }
+        return true;
+    });
     // the reference bubble-sorts on `>`: equal timestamps keep their scan order
     std::stable_sort(all.begin(), all.end(), [](const Timed &a, const Timed &b) { return a.time < b.time; });
     r.xref.resize(all.size());
@@ -351,13 +362,15 @@ bool payload_span(const Reader &r, int index, Span *s, bool lj92 = false)
     return true;
 }
 
+// list (optional): the frames to read, in the order they are stored in dst; without it frames first .. first + count - 1
 int read_frames(const Reader &r, int first, int count, uint8_t *dst, size_t stride, int threads, bool lj92 = false,
-                size_t *sizes = nullptr)
+                size_t *sizes = nullptr, const int *list = nullptr)
 {
     if (count <= 0) return MLVFS_AMD_OK;
     std::vector<Span> spans(count);
+    auto frame_of = [&](int k) { return list ? list[k] : first + k; };
     for (int k = 0; k < count; k++) {
-        if (!payload_span(r, first + k, &spans[k], lj92)) return MLVFS_AMD_ERR_ARG;
+        if (!payload_span(r, frame_of(k), &spans[k], lj92)) return MLVFS_AMD_ERR_ARG;
         if (sizes) sizes[k] = spans[k].bytes;
         if (spans[k].bytes > stride) { set_error("mlv: stride %zu smaller than a frame payload (%zu)", stride, spans[k].bytes); return MLVFS_AMD_ERR_ARG; }
     }
@@ -371,21 +384,21 @@ int read_frames(const Reader &r, int first, int count, uint8_t *dst, size_t stri
                 // is the frame's packed size (a shorter result leaves the rest of the reference's buffer undefined: zeros here)
                 std::vector<uint8_t> comp(spans[k].lzma_bytes);
                 size_t got = 0;
-                if (!read_at(spans[k].fd, comp.data(), comp.size(), spans[k].off)) { failed = first + k; continue; }
+                if (!read_at(spans[k].fd, comp.data(), comp.size(), spans[k].off)) { failed = frame_of(k); continue; }
                 const size_t want = (size_t)comp[0] | ((size_t)comp[1] << 8) | ((size_t)comp[2] << 16) | ((size_t)comp[3] << 24);
                 // the size word is a field of the file too: a frame cannot decode to much more than its packed size (the
                 // reference would malloc up to 4 GiB per worker here)
-                if (want > 8 * spans[k].bytes + (1u << 20)) { failed_lzma = first + k; continue; }
+                if (want > 8 * spans[k].bytes + (1u << 20)) { failed_lzma = frame_of(k); continue; }
                 std::vector<uint8_t> big;
                 uint8_t *out = d;
                 if (want > stride) { big.resize(want); out = big.data(); }      // a size word larger than the frame: decode all, keep the frame
-                if (mlv::lzma_decode(comp.data() + 4, comp.data() + 9, comp.size() - 9, out, want, &got) != 0) { failed_lzma = first + k; continue; }
+                if (mlv::lzma_decode(comp.data() + 4, comp.data() + 9, comp.size() - 9, out, want, &got) != 0) { failed_lzma = frame_of(k); continue; }
                 if (out != d) memcpy(d, out, std::min(got, spans[k].bytes));
                 if (got < spans[k].bytes) memset(d + got, 0, spans[k].bytes - got);
-            } else if (!read_at(spans[k].fd, d, spans[k].bytes, spans[k].off)) { failed = first + k; continue; }
+            } else if (!read_at(spans[k].fd, d, spans[k].bytes, spans[k].off)) { failed = frame_of(k); continue; }
             if (stride > spans[k].bytes) memset(d + spans[k].bytes, 0, std::min<size_t>(stride - spans[k].bytes, 64));   // the 2-pixel over-read of main.c:579 sees zeros
         } catch (const std::exception &) {               // out of memory in a reader thread: the frame fails, the host lives
-            if (spans[k].lzma_bytes) failed_lzma = first + k; else failed = first + k;
+            if (spans[k].lzma_bytes) failed_lzma = frame_of(k); else failed = frame_of(k);
         }
     };
     std::vector<std::thread> pool;
@@ -399,28 +412,30 @@ int read_frames(const Reader &r, int first, int count, uint8_t *dst, size_t stri
 
 }  // namespace
 
-// The mount (mount.cpp): frames first .. first + count - 1 of one geometry as 16-bit pixels in HBM, `dstride` bytes apart, on `s` --
-// payloads read by io_threads threads into the reader's page-locked staging (LZMA decoded there), then uploaded and unpacked
-// (k_unpack) or, LJ92 clips, decoded on the GPU.  Returns with the stream drained: the staging is the next caller's again.
-int mlv::reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                           hipStream_t s)
+// The mount (mount.cpp) and the transcoder (mlvwriter.cpp): `count` frames of one geometry and one payload kind, named by list[], as
+// 16-bit pixels in HBM, `dstride` bytes apart, on `s` -- payloads read by io_threads threads into the reader's page-locked staging
+// (LZMA decoded there), then uploaded and unpacked (k_unpack) or, LJ92 clips, decoded on the GPU.  Returns with the stream drained:
+// the staging is the next caller's again.  stage_locked: the caller holds the reader's staging mutex already.
+int mlv::reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
+                          hipStream_t s, bool stage_locked)
 {
     const Reader &r = *(const Reader *)reader;
     if (count <= 0) return MLVFS_AMD_OK;
     frame_headers fh0;
-    if (!frame_headers_of(r, first, &fh0)) { set_error("mlv: frame %d has no usable headers", first); return MLVFS_AMD_ERR_ARG; }
+    if (!frame_headers_of(r, list[0], &fh0)) { set_error("mlv: frame %d has no usable headers", list[0]); return MLVFS_AMD_ERR_ARG; }
     const bool lj92 = (fh0.file_hdr.videoClass & CLASS_LJ92) && !(fh0.file_hdr.videoClass & CLASS_LZMA);
     size_t stride = 0;
     for (int k = 0; k < count; k++) {
         Span sp;
-        if (!payload_span(r, first + k, &sp, lj92)) return MLVFS_AMD_ERR_ARG;
+        if (!payload_span(r, list[k], &sp, lj92)) return MLVFS_AMD_ERR_ARG;
         stride = std::max(stride, lj92 ? sp.bytes : sp.bytes + 2);
     }
     stride = (stride + 15) / 16 * 16;
-    std::lock_guard<std::mutex> lk(r.stage_mu);                     // one streaming call per reader at a time
+    std::unique_lock<std::mutex> lk(r.stage_mu, std::defer_lock);   // one streaming call per reader at a time
+    if (!stage_locked) lk.lock();
     if (!ensure_stage(r, stride * count)) return MLVFS_AMD_ERR_NOMEM;
     std::vector<size_t> sizes(count);
-    int rc = read_frames(r, first, count, r.stage[0], stride, io_threads, lj92, sizes.data());
+    int rc = read_frames(r, 0, count, r.stage[0], stride, io_threads, lj92, sizes.data(), list);
     if (rc) return rc;
     if (lj92) {
         std::vector<const void *> ptr(count);
@@ -437,6 +452,57 @@ int mlv::reader_load_batch(const void *reader, int first, int count, int w, int 
     MLV_HIP(hipStreamSynchronize(s));
     return MLVFS_AMD_OK;
 }
+
+// frames first .. first + count - 1
+int mlv::reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
+                           hipStream_t s)
+{
+    if (count <= 0) return MLVFS_AMD_OK;
+    std::vector<int> list(count);
+    for (int k = 0; k < count; k++) list[k] = first + k;
+    return reader_load_list(reader, list.data(), count, w, h, bpp, d_frames, dstride, io_threads, s, false);
+}
+
+// ---- what the transcoder (mlvwriter.cpp) asks of an opened clip -------------------------------------------------------------
+const char *mlv::reader_path(const void *reader) { return ((const Reader *)reader)->path.c_str(); }
+
+int mlv::reader_chunk_fd(const void *reader, int chunk)
+{
+    const Reader &r = *(const Reader *)reader;
+    return chunk >= 0 && (size_t)chunk < r.fds.size() ? r.fds[chunk] : -1;
+}
+
+bool mlv::reader_frame_place(const void *reader, int index, int *chunk, uint64_t *offset)
+{
+    const Reader &r = *(const Reader *)reader;
+    if (index < 0 || (size_t)index >= r.vidf.size()) return false;
+    const XrefEntry &e = r.xref[r.vidf[index]];
+    *chunk = e.file;
+    *offset = e.offset;
+    return true;
+}
+
+bool mlv::reader_payload_bytes(const void *reader, int index, bool lj92, size_t *bytes)
+{
+    Span sp;
+    if (!payload_span(*(const Reader *)reader, index, &sp, lj92)) return false;
+    *bytes = sp.bytes;
+    return true;
+}
+
+int mlv::reader_read_list(const void *reader, const int *list, int count, uint8_t *dst, size_t stride, int io_threads)
+{
+    return read_frames(*(const Reader *)reader, 0, count, dst, stride, io_threads, false, nullptr, list);
+}
+
+void mlv::reader_walk_blocks(const void *reader, const std::function<bool(int, uint64_t, const uint8_t *, uint32_t, const mlv_file_hdr_t *)> &visit)
+{
+    walk_blocks(((const Reader *)reader)->fds, [&](int c, uint64_t pos, const BlockHead &h, const mlv_file_hdr_t *mlvi) {
+        return visit(c, pos, h.type, h.size, mlvi);
+    });
+}
+
+std::mutex &mlv::reader_stage_mutex(const void *reader) { return ((const Reader *)reader)->stage_mu; }
 
 extern "C" {
 

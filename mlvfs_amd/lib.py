@@ -17,7 +17,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(HERE, "libmlvfs_amd.so")
 
 OK = 0
-ERR_HIP, ERR_ARG, ERR_LUT, ERR_NOMEM = -1, -2, -3, -4
+ERR_HIP, ERR_ARG, ERR_LUT, ERR_NOMEM, ERR_IO = -1, -2, -3, -4, -5
+MLV_PLAIN, MLV_LJ92 = 0, 1          # MLVFS_AMD_MLV_*: payload kinds mlvfs_amd_mlv_transcode writes
 
 
 class Geom(C.Structure):
@@ -59,6 +60,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_fix_pattern_noise_dev", "mlvfs_amd_test_pn_scratch_cap", "mlvfs_amd_deflicker_batch_dev", "mlvfs_amd_hdr_preview_batch_dev",
     "mlvfs_amd_mount_open", "mlvfs_amd_mount_dng", "mlvfs_amd_mount_close",
     "mlvfs_amd_lj92_encode_batch_dev", "mlvfs_amd_dng_header_lossless", "mlvfs_amd_mount_dng_lossless",
+    "mlvfs_amd_lj92_tile_dev", "mlvfs_amd_pack_dev", "mlvfs_amd_mlv_transcode",
 ]
 
 
@@ -221,6 +223,9 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_lj92_encode_batch_dev", i, [vp, sz, i, i, i, i, vp, sz, vp, vp, vp, vp])
     sig("mlvfs_amd_dng_header_lossless", sz, [fhp, vp, C.c_long, sz, C.c_double, C.c_char_p, C.c_uint32])
     sig("mlvfs_amd_mount_dng_lossless", i, [vp, i, i, vp, sz, vp, vp, i, i, vp])
+    sig("mlvfs_amd_lj92_tile_dev", i, [vp, sz, vp, sz, i, i, i, vp])
+    sig("mlvfs_amd_pack_dev", i, [gp, vp, sz, vp, sz, i, vp])
+    sig("mlvfs_amd_mlv_transcode", i, [vp, C.c_char_p, i, i, i, C.POINTER(C.c_longlong)])
     _lib = L
     return L
 

@@ -96,3 +96,63 @@ def encode_table(hist, npix: int):
         return None
     o = list(out)
     return dict(bits=o[0:16], nvalues=o[16], values=o[17:34], len=o[34:51], code=o[51:68])
+
+
+def _frames_3d(frames):
+    import torch
+    if not isinstance(frames, torch.Tensor):
+        frames = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f, np.uint16) for f in frames])).view(np.int16)).cuda()
+    if frames.dim() != 3 or frames.element_size() != 2 or not frames.is_cuda:
+        raise ValueError("frames must be an (n, h, w) tensor of 16-bit values on the GPU")
+    n, h, w = frames.shape
+    if n and (frames.stride(2) != 1 or frames.stride(1) != w):
+        raise ValueError("each frame must be contiguous")
+    return frames
+
+
+def _check_out(out, shape, frames):
+    """A caller's output tensor: 16-bit values on the frames' device, this shape, every frame (dim 0 may be strided) contiguous."""
+    import torch
+    if not isinstance(out, torch.Tensor) or out.element_size() != 2 or out.device != frames.device or tuple(out.shape) != tuple(shape):
+        raise ValueError(f"out must be a tensor of 16-bit values of shape {tuple(shape)} on {frames.device}")
+    inner = 1
+    for d in range(out.dim() - 1, 0, -1):
+        if shape[d] != 1 and out.stride(d) != inner:
+            raise ValueError("each frame of out must be contiguous")
+        inner *= shape[d]
+    if shape[0] > 1 and out.stride(0) < inner:
+        raise ValueError("the frames of out overlap")
+
+
+def tile_frames(frames, out=None, torch_stream=None):
+    """mlvfs_amd_lj92_tile_dev: (n, h, w) 16-bit frames on the GPU (or host arrays, which are uploaded) -> the same shape with the four
+    Bayer channels of each frame as its four quadrants, what an MLV writer compresses (the inverse of decode_frames' untiling)."""
+    import torch
+    L = lib.load()
+    frames = _frames_3d(frames)
+    n, h, w = frames.shape
+    if out is None:
+        out = torch.empty((n, h, w), dtype=frames.dtype, device=frames.device)
+    _check_out(out, (n, h, w), frames)
+    st = C.c_void_p(torch_stream.cuda_stream) if torch_stream is not None else None
+    lib.check(L.mlvfs_amd_lj92_tile_dev(C.c_void_p(frames.data_ptr()), frames.stride(0) * 2, C.c_void_p(out.data_ptr()), out.stride(0) * 2,
+                                        w, h, n, st), "lj92_tile_dev")
+    return out
+
+
+def pack_frames(frames, bpp: int = 14, out=None, torch_stream=None):
+    """mlvfs_amd_pack_dev: (n, h, w) 16-bit frames on the GPU (or host arrays) -> (n, ceil(w * h * bpp / 16)) int16 words of packed
+    payload per frame, as an MLV file stores them (the inverse of mlvfs_amd_unpack_dev)."""
+    import torch
+    L = lib.load()
+    frames = _frames_3d(frames)
+    n, h, w = frames.shape
+    words = (w * h * bpp + 15) // 16
+    if out is None:
+        out = torch.empty((n, words), dtype=torch.int16, device=frames.device)
+    _check_out(out, (n, words), frames)
+    geom = lib.Geom(w, h, bpp, 0, 0, 0, 0)
+    st = C.c_void_p(torch_stream.cuda_stream) if torch_stream is not None else None
+    lib.check(L.mlvfs_amd_pack_dev(C.byref(geom), C.c_void_p(frames.data_ptr()), frames.stride(0) * 2, C.c_void_p(out.data_ptr()),
+                                   out.stride(0) * 2, n, st), "pack_dev")
+    return out

@@ -180,3 +180,12 @@ class MlvReader:
         lib.check(self.L.mlvfs_amd_mlv_process_dualiso(self.h, first, count, lib.ptr(out), out.strides[0], interp, fullres, alias_map, cs, batch,
                                                        io_threads, lib.ptr(res)), "mlv_process_dualiso")
         return res
+
+    def transcode(self, out_path: str, lj92: bool = True, batch: int = 0, io_threads: int = 0) -> dict:
+        """mlvfs_amd_mlv_transcode: the clip written again as <out_path> (+ .M00 ...) with lossless-JPEG payloads (lj92=True, what
+        `mlv_dump -c` writes) or plain packed ones; blocks stay in the source's file order, NULL and XREF blocks are dropped, nothing is
+        overwritten.  Plain output of a plain or LZMA clip needs no GPU.  -> {frames, bytes_in, bytes_out, files}."""
+        stats = (C.c_longlong * 4)()
+        lib.check(self.L.mlvfs_amd_mlv_transcode(self.h, os.fsencode(out_path), lib.MLV_LJ92 if lj92 else lib.MLV_PLAIN, batch, io_threads,
+                                                 stats), "mlv_transcode")
+        return dict(frames=int(stats[0]), bytes_in=int(stats[1]), bytes_out=int(stats[2]), files=int(stats[3]))

@@ -1,0 +1,36 @@
+"""Rewrite a clip with lossless-JPEG payloads (what `mlv_dump -c` writes) or plain packed ones (--plain, `mlv_dump -d`) on the GPU:
+mlvfs_amd_mlv_transcode (csrc/mlvwriter.cpp).
+
+    python tools/mlv_transcode.py SRC.MLV DST.MLV [--plain] [--batch N] [--io-threads N]
+
+Source chunks SRC.M00 ... become DST.M00 ...; blocks keep the source's file order, NULL and XREF blocks are dropped, nothing is
+overwritten and no .IDX is written.  Plain output of a plain or LZMA clip needs no GPU."""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mlvfs_amd import mlvfile
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("src")
+    ap.add_argument("dst")
+    ap.add_argument("--plain", action="store_true", help="plain packed payloads instead of LJ92")
+    ap.add_argument("--batch", type=int, default=0, help="frames per GPU batch (default 8)")
+    ap.add_argument("--io-threads", type=int, default=0)
+    a = ap.parse_args()
+    with mlvfile.MlvReader(a.src) as r:
+        t0 = time.perf_counter()
+        s = r.transcode(a.dst, lj92=not a.plain, batch=a.batch, io_threads=a.io_threads)
+        dt = time.perf_counter() - t0
+    print(f"{s['frames']} frames in {s['files']} file(s), {dt:.3f} s ({s['frames'] / dt:.1f} frames/s): payload bytes {s['bytes_in']} -> {s['bytes_out']}"
+          f" ({s['bytes_out'] / max(s['bytes_in'], 1):.3f})")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
