@@ -19,11 +19,12 @@ int cus(const FramePassInputs &in) { return in.num_cu > 0 ? in.num_cu : 256; }
 
 int env_switch(const char *name) { const char *e = getenv(name); return e ? atoi(e) : 1; }
 
-// what the streaming kernels read: 14-bit streams in rows of whole 8-pixel groups (the vector layouts), even heights, black >= 0,
-// stripes in the packed 16-bit form or none
+// what the streaming kernels read: 14-bit streams in rows of whole 8-pixel groups (the vector layouts), even heights, a black level
+// of 0 .. 16384 (the range in which launch_frame admits the packed stripes form; above it the reference has no raw2ev table and
+// smooths nothing: main.c:171-175), stripes in the packed 16-bit form or none
 bool streamable(const FramePassInputs &in)
 {
-    return in.packed && in.bpp == 14 && (in.vec == 1 || in.vec == 2) && in.black >= 0 && in.stripes != StripeForm::generic &&
+    return in.packed && in.bpp == 14 && (in.vec == 1 || in.vec == 2) && in.black >= 0 && in.black <= 16384 && in.stripes != StripeForm::generic &&
            in.w >= 16 && in.w % 8 == 0 && in.h >= 2 && in.h % 2 == 0;
 }
 

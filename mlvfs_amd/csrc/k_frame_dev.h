@@ -1181,7 +1181,8 @@ __device__ __forceinline__ unsigned long long lanes_lt(int a, int b) { return __
 //   pixel-map cells).  Then every EV involved lies in [6, 14] stops: er and eb stay below 28 stops -- where the table goes on with
 //   its last value (E2D_RECORDS_EXT) -- so the clamp of chroma_smooth.c:67 is the table's own, and one below zero belongs to a cell
 //   that keeps its pixel (er > 1 stop fails; its look-up is out of range and reads 0).  And the stripes epilogue's "more than 64
-//   above black" holds for every pixel: no mask.
+//   above black" holds for every pixel the tile loaded, and for the smoothed ones as long as none of their EVs is low -- which the
+//   caller has looked at (smoothed_low): then no mask.
 //   XM: the tile touches the frame's left or right margin (chroma_smooth.c:27 leaves columns 0..3 and w-4.. alone).
 //   VECST: rows of whole 8-pixel groups on 16-byte aligned buffers (two 16-byte stores); else pixel by pixel.
 // The variants are separate instantiations chosen by scalar branches: written as conditions inside one body the compiler computed
@@ -1190,6 +1191,16 @@ __device__ __forceinline__ unsigned long long lanes_lt(int a, int b) { return __
 //   RAWREG (k_frame_s): the strip's pixels come in registers (rtop / rbot) instead of from the tile's LDS rows, and go back there
 //   (store = false: the caller stores them).
 struct NoSmem {};
+// A tile without a loaded pixel at most 64 above black can still get a SMOOTHED one there: a cell of dim greens among bright ones takes
+// its green EV plus its neighbours' median red-minus-green, a few levels above black -- which stripes.c:261 then leaves alone, while
+// the epilogue without its mask moved it (a gain below one: down by one; tests/test_gpu_levels.py).  A pixel lies at most 64 above
+// black only for an EV below log2(65) stops; below 7 stops anywhere in the wave's strips the callers take the variant for low pixels
+// (wave-uniform; on the benchmark's footage never).
+__device__ __forceinline__ bool smoothed_low(const int (&er)[STRIP], const int (&eb)[STRIP])
+{
+    const int lo = min(min(min(min(er[0], er[1]), er[2]), min(er[3], eb[0])), min(min(eb[1], eb[2]), eb[3]));       // (three-input minima)
+    return __any(lo < 7 * MLV_EV_RES);
+}
 template <int METHOD, bool PACKED, bool VECST, bool CLAMP, bool XM, bool ANYSTRIPES, bool BRIGHT, class SM, bool RAWREG = false>
 __device__ __forceinline__ void strip_output_t(const SM &sm, const OutArgs &oa, int w, int h, int black, int f, int tx0, int ty0, int jj, int kk,
                                                unsigned long long msmooth, const int (&gev)[STRIP], int gev_off, const int (&er)[STRIP], const int (&eb)[STRIP], bool store,
@@ -1293,6 +1304,7 @@ __device__ __forceinline__ void strip_output(const SM &sm, const OutArgs &oa, in
                                              bool store)
 {
     const bool xm = tx0 < 4 || tx0 + 2 * TCW > w - 4;                   // scalar
+    if (METHOD != 0 && !low_any && oa.stripes && smoothed_low(er, eb)) { low_any = true; bright = false; }
     if (oa.stripes && !(PACKED && oa.coef_pk)) {        // (gains beyond the packed form's range, 16-bit input: one variant, everything tested)
         strip_output_t<METHOD, PACKED, VECST, true, true, true, false, SM>(sm, oa, w, h, black, f, tx0, ty0, jj, kk, msmooth, gev, gev_off, er, eb, store);
     } else if (low_any) {

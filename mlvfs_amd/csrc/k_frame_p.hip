@@ -914,7 +914,8 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
                     bot[0] = b4.x; bot[1] = b4.y; bot[2] = b4.z; bot[3] = b4.w;
                 }
                 const OutArgs oa = out_args(cold_args());          // (read here, not held through the step: 39 -> 17 spilled scalars)
-                const int fl = fl0 | fl1 | fl2 | fl3 | fl4;                                 // the five rows of the window
+                // the five rows of the window, and what smoothing makes of them (smoothed_low)
+                const int fl = fl0 | fl1 | fl2 | fl3 | fl4 | (oa.stripes && smoothed_low(er, eb) ? 1 : 0);
 #define KFP5_OUT(CLAMP, XM, BRIGHT) strip_output_t<5, true, true, CLAMP, XM, false, BRIGHT, NoSmem, true>(NoSmem(), oa, w, h, black, f, tx0, 0, jr, pl, msmooth, \
                                                                                                           ge2, 0, er, eb, false, top, bot)
 #ifdef KFP5_EXP_NOOUT

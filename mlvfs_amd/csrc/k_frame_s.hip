@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, KF_S_WGS) void k_frame_s(const FrameArgs a, in
                     med9(db2, db1, db, eb);
                 }
                 const unsigned long long msmooth = lanes_ge(yl, 4) & lanes_lt(yl, h - 5);       // (a lane mask in a register pair: put_rb moves it to VCC)
-                const int fl = flags0 | flags1 | flags2;
+                const int fl = flags0 | flags1 | flags2 | (oa.stripes && smoothed_low(er, eb) ? 1 : 0);       // (the three rows loaded, and what smoothing makes of them)
                 // (the variants of strip_output, chosen by scalars: margins, low pixels, bright rows)
 #define KFS_OUT(CLAMP, XM, BRIGHT) strip_output_t<METHOD, true, true, CLAMP, XM, false, BRIGHT, NoSmem, true>(NoSmem(), oa, w, h, black, f, tx0, 0, jr, pl, msmooth, \
                                                                                                          ge1, 0, er, eb, false, top1, bot1)
