@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
         int nt, ne;
         draw(nt, ne);
         sm.next_tile = nt; sm.next_end = ne;
-        sm.dark_items[0] = 0; sm.dark_items[1] = 0; sm.fb_count = 0; sm.low[0] = 0; sm.low[1] = 0;
+        sm.dark_items[0] = 0; sm.dark_items[1] = 0; sm.fb_count = 0;
     }
     __syncthreads();
     int t = __builtin_amdgcn_readfirstlane(sm.next_tile), t_end = __builtin_amdgcn_readfirstlane(sm.next_end);
@@ -183,21 +183,13 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
     struct Src { const uint8_t *src; size_t src_stride; unsigned src_bytes; };
     auto src_of = [](KArgs ka) { Src s; s.src = ka->src; s.src_stride = ka->src_stride; s.src_bytes = ka->src_bytes; return s; };
     auto issue_tile = [&](const Src *ka, const Pos &p) {
-#ifndef KF_W_OLD_PREFETCH
         issue_tile_rows<BPP, VEC>(r0, r1, ka->src + (size_t)p.f * ka->src_stride, ka->src_bytes, IL, l_row, a.w, a.h, p.tcol * 2 * TCW, p.trow * 2 * TCH, NEW0);
-#else
-        const mlv_i32x4 rs = frame_rsrc(ka->src + (size_t)p.f * ka->src_stride, ka->src_bytes);
-        issue_item<BPP>(r0, r1, rs, IL, a.w, a.h, p.tcol * 2 * TCW, p.trow * 2 * TCH, NEW0 + l_row);
-#endif
     };
     Pos cur = pos_of(min(t, max(band_end - 1, 0)));
     { const Src s0 = src_of(cold_args()); if (vec) issue_tile(&s0, cur); }
     __syncthreads();                           // T16 copy complete
 
     int par = 0;                               // tile parity: which of the two dark_items counters this tile uses
-#ifdef KF_W_LOW
-    int lpar = 0, low_prev = 3;                // which of the two low-pixel records; the record of the tile before (bit 0: low, bit 1: dim)
-#endif
     int fb_skip = 0, fb_wait = FB_WAIT_MIN;    // 5x5: tiles still to go straight to the 32-bit chain; how many after the next busy tile
     bool robust = false;                       // 5x5: rows of lanes agree on their references (robust_ref)
     int calm = 0;                              //      tiles in a row without an uncertain strip
@@ -209,9 +201,6 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
             else draw(nt, ne);
         }
         const int f = cur.f, trow = cur.trow, tx0 = cur.tcol * 2 * TCW, ty0 = cur.trow * 2 * TCH;
-#ifdef KF_W_HOIST_SRC
-        const Src sa = src_of(cold_args());      // (asked for here, needed when the next tile is prefetched: no wait there)
-#endif
         const int tr = cur.trow * a.tiles_x + cur.tcol;          // the tile's number in the (row-major) pixel-map lists
         // ---- pixel-map entries of this tile (few tiles have any): list bounds now -- the wait that the uniform load implies is
         // for data the loader needs anyway --, the first 256 records themselves in flight while the loader phase runs
@@ -226,11 +215,7 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
             if (pbeg + tid < pend) my_rec = (ka->cells + (size_t)f * ka->n_rec)[pbeg + tid];
         }
         // ---- loader: prefetched registers -> EV planes + interior raw pixels
-#if !defined(KF_PRIO) || KF_PRIO == 1
         __builtin_amdgcn_s_setprio(0);
-#elif KF_PRIO == 2
-        __builtin_amdgcn_s_setprio(1);
-#endif
         // Lane predicates and wave-uniform switches are re-derived per tile from opaque copies: hoisted out of the loop they
         // became 64-bit SGPR masks, two scalar registers each, of which the kernel kept more than it has -- they were spilt
         // to VGPR lanes and came back through v_readlane, VECTOR instructions (about 40 per tile and wave).
@@ -256,20 +241,9 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
                 }
                 odd = (int)lo <= a.black;
                 beyond = (!PACKED && (int)hi - a.black > 16383) || (PACKED && a.black < 0);
-#ifdef KF_W_LOW
-                // what strip_output may skip: bit 1 = some pixel less than 256 above black (or 16-bit input), bit 0 = at most 64 above
-                if (!PACKED || a.black < 0 || __any((int)lo <= a.black + 255)) {
-                    const int v = (PACKED && a.black >= 0 && !__any((int)lo <= a.black + 64)) ? 2 : 3;
-                    if (lane == 0) atomicOr(&sm.low[lpar], v);        // (several waves: OR, not store)
-                }
-#endif
             }
-#ifdef KF_EXP_FASTLOADER
-            const bool slow = false, dark = false;
-#else
             const bool slow = (!PACKED || a.black < 0) && __any(beyond);
             const bool dark = slow || __any(odd);
-#endif
             if (METHOD == 5 && SPREAD && dark) {
                 const unsigned long long who = __ballot(odd || beyond);
                 if (lane == 0) atomicAdd(&sm.dark_items[par], __popcll(who));
@@ -293,10 +267,6 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
         if (threadIdx.x == 0) { sm.next_tile = nt; sm.next_end = ne; }
         lds_barrier();
         const int t_next = __builtin_amdgcn_readfirstlane(sm.next_tile), t_end_next = __builtin_amdgcn_readfirstlane(sm.next_end);
-#ifdef KF_W_LOW
-        if (tid == 0) sm.low[lpar ^ 1] = 0;      // (read by all before this barrier, written again behind the next tile's)
-        const int low_cur = (METHOD == 0 || tile_patched) ? 3 : __builtin_amdgcn_readfirstlane(sm.low[lpar]);
-#endif
         // the tile after this one continues it when it is the next of the list and not the top of a column
         const bool cont_next = METHOD != 0 && t_next == t + 1 && trow + 1 < a.tiles_y && t_next < band_end;       // scalar
         if (tile_patched) {
@@ -315,31 +285,17 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
         // is about to finish finishes sooner, its workgroup's barrier opens sooner, and the loader instructions of the others
         // fill the gaps.  Measured (tools/kbench.py): cs5x5 11.2-11.5 -> 10.2-10.4 us per frame, cs2x2 8.2 -> 7.8; which of the
         // levels 1..3 is used, and a third level for the output stage, make no difference.
-#if !defined(KF_PRIO) || KF_PRIO == 1
         if (METHOD != 0) __builtin_amdgcn_s_setprio(1);       // (without chroma smoothing the kernel is load-bound and this costs 8 %)
-#elif KF_PRIO == 2
-        if (METHOD != 0) __builtin_amdgcn_s_setprio(0);
-#endif
         // ---- prefetch the next tile while the medians run
         // (scalar branch: the first tile of another run -- or nothing left: the prefetch is unconditional, so it gets a valid tile;
         // the tile "below" the list's last one would lie in a frame behind the buffer)
         Pos nxt = pos_below(cur);
         if (t_next != t + 1 || t_next >= band_end) nxt = pos_of(min(t_next, band_end - 1));
-#ifdef KF_W_HOIST_SRC
-        if (vec) issue_tile(&sa, nxt);
-#else
         { const Src s1 = src_of(cold_args()); if (vec) issue_tile(&s1, nxt); }
-#endif
 
         // ---- medians + output: one thread = 4 cells = 8 px on two rows
-        // the rest of a strip once its medians are known: R / B replacement, stripes, store
-        // the rest of a strip once its medians are known: R / B replacement, stripes, store (strip_output, k_frame_dev.h; this kernel
-        // keeps no record of low pixels: always the clamped look-up and the masked stripes epilogue)
-#ifdef KF_W_LOW
-        const bool w_low_any = ((low_cur | low_prev) & 1) != 0, w_bright = (low_cur | low_prev) == 0;
-#else
-        const bool w_low_any = true, w_bright = false;
-#endif
+        // the rest of a strip once its medians are known: R / B replacement, stripes, store (strip_output, k_frame_dev.h: always with
+        // low_any, the clamped look-up and the masked stripes epilogue)
         const OutArgs oa = out_args(cold_args());
         auto finish_strip = [&](int jj, int kk, unsigned long long msmooth, const int (&mr)[STRIP], const int (&mb)[STRIP], bool store) {
             int gev[STRIP] = { 0, 0, 0, 0 }, er[STRIP] = { 0, 0, 0, 0 }, eb[STRIP] = { 0, 0, 0, 0 };
@@ -349,7 +305,7 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
 #pragma unroll
                 for (int c = 0; c < STRIP; c++) { er[c] = wadd(gev[c], mr[c]); eb[c] = wadd(gev[c], mb[c]); }
             }
-            strip_output<METHOD, PACKED, vec, Smem>(sm, oa, a.w, a.h, a.black, f, tx0, ty0, jj, kk, msmooth, gev, 0, er, eb, w_low_any, w_bright, store);
+            strip_output<METHOD, PACKED, vec, Smem>(sm, oa, a.w, a.h, a.black, f, tx0, ty0, jj, kk, msmooth, gev, 0, er, eb, true, false, store);
         };
         const int y = ty0 + 2 * j;
         const bool smooth_row = METHOD != 0 && y >= 4 && y < a.h - 5;                       // chroma_smooth.c:25
@@ -363,9 +319,6 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
             // everywhere: that is where the packed attempt plus the dense pass cost more than the 32-bit chain).
             const bool dark_tile = SPREAD && __builtin_amdgcn_readfirstlane(sm.dark_items[par]) >= DARK_ITEMS_MIN;
             skip_packed = dark_tile || fb_skip > 0;            // the same for every wave of the workgroup
-#ifdef KF_EXP_NOFALLBACK
-            skip_packed = false;
-#endif
             if (fb_skip > 0) fb_skip--;
             if (SPREAD && tid == 0) sm.dark_items[par ^ 1] = 0;
             bool unknown = true;
@@ -409,9 +362,6 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
                 unknown = chain_finish(g, n, mr, mb);
             }
             unknown = unknown && is_strip && smooth_row;
-#ifdef KF_EXP_NOFALLBACK
-            unknown = false;
-#endif
             if (unknown) sm.fb_queue[atomicAdd(&sm.fb_count, 1)] = (uint8_t)(j * 16 + k);      // settled below, densely
             if (is_strip && !unknown) finish_strip(j, k, msmooth_row, mr, mb, true);
         } else {
@@ -444,11 +394,7 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
             // Strips whose packed medians were not certain: all of the tile's, gathered in LDS, go through the 32-bit networks
             // one per lane -- as many waves as ceil(count / 64) run them, instead of every wave that had one such strip.
             lds_barrier();
-#if defined(KF_EXP_LEAN) || defined(KF_EXP_NOSETTLE)
-            const int nfb = 0;
-#else
             const int nfb = __builtin_amdgcn_readfirstlane(sm.fb_count);
-#endif
             if (!skip_packed) {
                 // more than FB_DIRECT uncertain strips: the next fb_wait tiles go to the 32-bit chain directly, and the wait doubles
                 // (up to FB_WAIT_MAX) each time the tile after it is no better -- a stray busy tile costs its few successors a
@@ -480,9 +426,6 @@ __global__ __launch_bounds__(256, 4) void k_frame(const FrameArgs a)
         cont = cont_next;
         cur = nxt;
         if (SPREAD) par ^= 1;
-#ifdef KF_W_LOW
-        lpar ^= 1; low_prev = low_cur;
-#endif
     }
     if (list_mode) {
         if (threadIdx.x == 0) list_done();

@@ -35,25 +35,10 @@ constexpr int GROUPS = TCW / 4;         // loader items (8 px) per tile row (16)
 constexpr int N_MAIN = TCH * GROUPS;    // threads 0..239: item (row t / 16, group t % 16); threads 240..254: edge item of row t - 240
 constexpr int N_ITEMS = N_MAIN + TCH;
 constexpr int N_TOP_MAIN = 2 * HC * GROUPS, N_TOP = N_TOP_MAIN + 2 * HC;      // first tile of a run: the four rows above, threads 0..67
-#ifndef KF_DARK_ITEMS_MIN
-#define KF_DARK_ITEMS_MIN 24
-#endif
-constexpr int DARK_ITEMS_MIN = KF_DARK_ITEMS_MIN;      // of the loader items of a tile
-#ifndef KF_FB_ROBUST
-#define KF_FB_ROBUST 12
-#endif
-constexpr int FB_ROBUST = KF_FB_ROBUST;           // 5x5: more uncertain strips than this: the next tiles' lanes share their references row by row
-#ifndef KF_FB_WAIT_MIN
-#define KF_FB_WAIT_MIN 1
-#endif
-#ifndef KF_FB_WAIT_MAX
-#define KF_FB_WAIT_MAX 15
-#endif
-constexpr int FB_WAIT_MIN = KF_FB_WAIT_MIN, FB_WAIT_MAX = KF_FB_WAIT_MAX;     // 5x5: tiles that skip the packed networks after a busy one
-#ifndef KF_FB_DIRECT
-#define KF_FB_DIRECT 60
-#endif
-constexpr int FB_DIRECT = KF_FB_DIRECT;          // 5x5: more uncertain strips than this (of 240): the next tiles go to the 32-bit networks directly
+constexpr int DARK_ITEMS_MIN = 24;      // 5x5, dark clips: this many of a tile's loader items at or below black: the tile skips the packed networks
+constexpr int FB_ROBUST = 12;           // 5x5: more uncertain strips than this: the next tiles' lanes share their references row by row
+constexpr int FB_WAIT_MIN = 1, FB_WAIT_MAX = 15;      // 5x5: tiles that skip the packed networks after a busy one
+constexpr int FB_DIRECT = 60;           // 5x5: more uncertain strips than this (of 240): the next tiles go to the 32-bit networks directly
 constexpr int PMAP_WORDS = 64;          // tiles per frame covered by the LDS patch bitmap: 2048 (3584x1320 has 1232)
 static_assert(N_ITEMS <= 255 && TCH * 17 <= 256 && N_TOP <= 128, "one item per thread; 17 median lanes per tile row");
 
@@ -115,17 +100,7 @@ __device__ __forceinline__ mlv_i32x4 table_rsrc(const void *p, unsigned stride, 
 constexpr int E2R_ENTRIES = 14 * MLV_EV_RES;
 constexpr int E2D_RECORDS = E2R_ENTRIES / 32;
 constexpr int E2D_RECORDS_EXT = 2 * E2D_RECORDS;       // the table goes on with its last value up to 28 stops (k_frame_p looks up unclamped EVs)
-#ifdef KF_EXP_LEAN          // timing experiment: every rare path compiled out (results are wrong where one would have been taken)
-#define KF_EXP_PKONLY
-#define KF_EXP_NOFALLBACK
-#define KF_EXP_FASTLOADER
-#endif
-#ifndef KF_SRC_AUX
-#define KF_SRC_AUX 0          // cache policy of the loader's stream loads (experiments, same encoding)
-#endif
-#ifndef KF_E2R_AUX
-#define KF_E2R_AUX 0          // cache policy of the output look-ups (experiments: 2 = nt, 16 = sc1, 17 = sc0 sc1)
-#endif
+constexpr int AUX_DEFAULT = 0;          // cache policy of the loader's stream loads and of the output look-ups: the default one (2 = nt, 16 = sc1, 17 = sc0 sc1)
 
 // SPREAD: the T16 table with entry i at i + (i >> 7).  A pixel below 2^e above black uses only every 2^(13-e)-th entry, so
 // the look-ups of dark footage crowd into a few LDS banks (below 128 DN: one); the spread form puts those entries into
@@ -147,7 +122,6 @@ struct __align__(16) SmemT {
     int next_tile, next_end;            // the tile after this one and the end of the run it belongs to (thread 0 -> all)
     int dark_items[2];                  // loader items of the current / next tile that hold pixels at or below black (5x5 only)
     int walk[5];                        // thread 0's: first tile of the group's range, tiles that go out in runs, tiles per run, group, runs all out
-    int low[2];                         // some pixel this tile / the tile before loaded lies at most 64 above black (by tile parity)
 };
 static_assert(sizeof(SmemT<true, true>) <= 40 * 1024, "four workgroups per CU need <= 40 KiB of LDS each");
 
@@ -482,7 +456,7 @@ __device__ __forceinline__ void issue_item(uint32_t (&d0)[4], uint32_t (&d1)[4],
         const int yy = TOP ? clampi(y + rr, 0, h - 1) : min(y + rr, h - 1);     // (only the rows above a tile's own can lie above the frame)
         const uint32_t row = __umul24((uint32_t)yy, pitch);                            // rows and row pitch < 2^24 (launcher)
         const uint32_t oa = (row + ga) & L.amask, ob = ((row + gb) & L.amask) + L.boff;
-        const mlv_u32x2 a = mlv_rbl_x2(rs, (int)oa, 0, KF_SRC_AUX), b = mlv_rbl_x2(rs, (int)ob, 0, KF_SRC_AUX);
+        const mlv_u32x2 a = mlv_rbl_x2(rs, (int)oa, 0, AUX_DEFAULT), b = mlv_rbl_x2(rs, (int)ob, 0, AUX_DEFAULT);
         uint32_t (&d)[4] = rr ? d1 : d0;
         d[0] = a.x; d[1] = a.y; d[2] = b.x; d[3] = b.y;
     }
@@ -802,6 +776,7 @@ struct ChainNext {
 };
 // wave_shl:1 with bound_ctrl: lane i reads lane i + 1, the wave's last lane reads 0; no "old" operand, so no move to set one up
 __device__ __forceinline__ int dpp_next_i(int v) { return __builtin_amdgcn_mov_dpp(v, 0x130, 0xf, 0xf, true); }
+__device__ __forceinline__ int dpp_prev_i(int v) { return __builtin_amdgcn_mov_dpp(v, 0x138, 0xf, 0xf, true); }        // wave_shr:1: lane i reads lane i - 1, the first lane reads 0
 __device__ __forceinline__ mlv_pk16 dpp_next(mlv_pk16 v) { return __builtin_bit_cast(mlv_pk16, dpp_next_i(__builtin_bit_cast(int, v))); }
 
 // in two parts, so that the LDS reads of a row's last strip (chain_collect_*) have arithmetic to hide behind: the sorted
@@ -1069,9 +1044,7 @@ typedef const __attribute__((address_space(4))) FrameArgs *KArgs;
 __device__ __forceinline__ KArgs cold_args()
 {
     KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-#ifndef KF_EXP_WARM_ARGS           // (A/B: the compiler sees through, hoists every load out of the tile loop and keeps the arguments live)
-    asm volatile("" : "+s"(p));
-#endif
+    asm volatile("" : "+s"(p));         // (seen through, the compiler hoists every load out of the tile loop and keeps the arguments live)
     return p;
 }
 
@@ -1125,8 +1098,8 @@ __device__ __forceinline__ void issue_tile_rows_pre(uint32_t (&r0)[4], uint32_t 
         asm volatile("" : "+v"(oa0), "+v"(ob0));       // (keeps this arm a branch target: as plain arithmetic the compiler runs BOTH arms on every tile and selects)
     }
     const mlv_i32x4 rs = frame_rsrc(frame + S, bytes - S);
-    const mlv_u32x2 a0 = mlv_rbl_x2(rs, (int)oa0, 0, KF_SRC_AUX), b0 = mlv_rbl_x2(rs, (int)ob0, 0, KF_SRC_AUX);
-    const mlv_u32x2 a1 = mlv_rbl_x2(rs, (int)oa1, 0, KF_SRC_AUX), b1 = mlv_rbl_x2(rs, (int)ob1, 0, KF_SRC_AUX);
+    const mlv_u32x2 a0 = mlv_rbl_x2(rs, (int)oa0, 0, AUX_DEFAULT), b0 = mlv_rbl_x2(rs, (int)ob0, 0, AUX_DEFAULT);
+    const mlv_u32x2 a1 = mlv_rbl_x2(rs, (int)oa1, 0, AUX_DEFAULT), b1 = mlv_rbl_x2(rs, (int)ob1, 0, AUX_DEFAULT);
     r0[0] = a0.x; r0[1] = a0.y; r0[2] = b0.x; r0[3] = b0.y;
     r1[0] = a1.x; r1[1] = a1.y; r1[2] = b1.x; r1[3] = b1.y;
 }
@@ -1229,12 +1202,8 @@ __device__ __forceinline__ void strip_output_t(const SM &sm, const OutArgs &oa, 
         for (int c = 0; c < STRIP; c++) {
             cr[c] = CLAMP ? min(max(er[c], 0), MLV_EV_MAX) : er[c];
             cb[c] = CLAMP ? min(max(eb[c], 0), MLV_EV_MAX) : eb[c];
-#ifdef KF_EXP_NOLOOKUP
-            dr2[c].x = cr[c]; dr2[c].y = 0; db2[c].x = cb[c]; db2[c].y = 0;
-#else
-            dr2[c] = mlv_sbl_x2(rs_e2d, cr[c] >> 5, 0, 0, KF_E2R_AUX);
-            db2[c] = mlv_sbl_x2(rs_e2d, cb[c] >> 5, 0, 0, KF_E2R_AUX);
-#endif
+            dr2[c] = mlv_sbl_x2(rs_e2d, cr[c] >> 5, 0, 0, AUX_DEFAULT);
+            db2[c] = mlv_sbl_x2(rs_e2d, cb[c] >> 5, 0, 0, AUX_DEFAULT);
         }
         read_raw();
         // (the fence keeps the eight look-ups together)
@@ -1313,11 +1282,8 @@ __device__ __forceinline__ void strip_output(const SM &sm, const OutArgs &oa, in
     } else if (xm) {
         strip_output_t<METHOD, PACKED, VECST, false, true, false, false, SM>(sm, oa, w, h, black, f, tx0, ty0, jj, kk, msmooth, gev, gev_off, er, eb, store);
     } else {
-#ifndef KF_EXP_NO_BRIGHT
         if (bright) strip_output_t<METHOD, PACKED, VECST, false, false, false, true, SM>(sm, oa, w, h, black, f, tx0, ty0, jj, kk, msmooth, gev, gev_off, er, eb, store);
-        else
-#endif
-        strip_output_t<METHOD, PACKED, VECST, false, false, false, false, SM>(sm, oa, w, h, black, f, tx0, ty0, jj, kk, msmooth, gev, gev_off, er, eb, store);
+        else strip_output_t<METHOD, PACKED, VECST, false, false, false, false, SM>(sm, oa, w, h, black, f, tx0, ty0, jj, kk, msmooth, gev, gev_off, er, eb, store);
     }
 }
 

@@ -1,16 +1,11 @@
 // k_frame_p.hip -- the packed-once kernel of the fused pass (round 5); launched by k_frame.hip's launch_frame before the
 // list-mode k_frame.  Its own translation unit: its own scheduler flags (Makefile), and the two kernels compile in parallel.
 #include "frame_plan.h"
-#include "k_frame_dev.h"
+#include "k_stream_dev.h"
 
 namespace mlv {
 
-#ifndef KF_P_WAIT_MIN
-#define KF_P_WAIT_MIN 1
-#endif
-#ifndef KF_P_WAIT_MAX
-#define KF_P_WAIT_MAX 15
-#endif
+constexpr int P_WAIT_MIN = 1, P_WAIT_MAX = 15;      // tiles that go to the list unseen after an uncertain one: doubling between these
 // ================================================================ packed-once kernel (round 5)
 // k_frame_p: the same pass with the colour differences packed ONCE, by the loader.
 //
@@ -32,7 +27,7 @@ namespace mlv {
 // tile that does not continue the one above) takes the median of three cells at the tile's centre, fetched and converted by every
 // wave for itself (16 lanes, one pixel each; scalar arithmetic from there: no exchange, no barrier); the tiles below it keep that
 // reference, so the four plane rows they inherit stay valid as they are.
-template <bool SPREAD_, bool CHAIN_>
+template <bool SPREAD_>
 struct __align__(16) SmemP {
     static constexpr bool SPREAD = SPREAD_;
     uint16_t raw[2 * RH][2 * TCW];      // interior pixels (post patch) + the four pixel rows below (the next tile's first), 8.5 KiB
@@ -40,7 +35,7 @@ struct __align__(16) SmemP {
     int ge[RH][TCW];                    // 4.25 KiB
     uint16_t t16[MLV_T16_N + (SPREAD_ ? 64 : 0)];
     uint32_t has_patch[PMAP_WORDS];
-    uint32_t xchg[CHAIN_ ? 3 : 1][XCHG_WORDS];
+    uint32_t xchg[3][XCHG_WORDS];       // sorted columns / pair list / rank window of the group held by lane 0 of waves 1..3
     int unc[2];                         // some strip of this tile / of the tile before is uncertain (by tile parity)
     int low[2];                         // some pixel this tile / the tile before loaded lies at most 64 above black
     int dim[2];                         // ... lies less than 256 above black (or the tile took the loader's slow form)
@@ -48,9 +43,6 @@ struct __align__(16) SmemP {
     int walk[5];                        // thread 0's: first tile of the group's range, tiles that go out in runs, tiles per run, group, runs all out
     int2 carry_at[256];                 // per thread: byte offsets {from, to} of the 16-byte piece it hands down to the tile below (2 KiB)
     uint4 carry_spare;                  // (what threads without a piece copy)
-#ifdef KFP_EXP_LDSPAD
-    char exp_pad[KFP_EXP_LDSPAD];       // (occupancy experiment: fewer workgroups per CU)
-#endif
 };
 
 struct PGroup {
@@ -125,46 +117,6 @@ __device__ __forceinline__ void pchain_finish(const PGroup &g, const PNext &n, m
     mlv_final6of11(q1, n.s2, t);   o[2] = t[0];      // 2..5 | 6
     mlv_final6of11(n.q, g.s[3], t); o[3] = t[0];     // 4..7 | 3
 }
-// plus-shaped 5 (chroma_smooth.c:44-47 with CHROMA_SMOOTH_2X2) and 3x3 on the packed plane: the strip's cells are plane columns
-// col0 + 2 .. col0 + 5 (col0 = 4 k: the halo is two cells), their rows jrow + 1 .. jrow + 3
-__device__ __forceinline__ void pstrip_median5(const uint32_t (*pk)[PW], int jrow, int col0, mlv_pk16 (&o)[STRIP])
-{
-    const uint2 u0 = *(const uint2 *)&pk[jrow + 1][col0 + 2], u1 = *(const uint2 *)&pk[jrow + 1][col0 + 4];
-    const uint4 c0 = *(const uint4 *)&pk[jrow + 2][col0], c1 = *(const uint4 *)&pk[jrow + 2][col0 + 4];
-    const uint2 d0 = *(const uint2 *)&pk[jrow + 3][col0 + 2], d1 = *(const uint2 *)&pk[jrow + 3][col0 + 4];
-    const uint32_t up[4] = { u0.x, u0.y, u1.x, u1.y }, dn[4] = { d0.x, d0.y, d1.x, d1.y };
-    const uint32_t ce[8] = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w };
-#pragma unroll
-    for (int c = 0; c < STRIP; c++) {
-        const mlv_pk16 v[5] = { as_pk(up[c]), as_pk(ce[c + 1]), as_pk(ce[c + 2]), as_pk(ce[c + 3]), as_pk(dn[c]) };
-        mlv_pk16 t[1];
-        mlv_median5(v, t);
-        o[c] = t[0];
-    }
-}
-__device__ __forceinline__ mlv_pk16 pk_med3(mlv_pk16 a, mlv_pk16 b, mlv_pk16 c) { return mlv_mx(mlv_mn(a, b), mlv_mn(mlv_mx(a, b), c)); }
-__device__ __forceinline__ void pstrip_median9(const uint32_t (*pk)[PW], int jrow, int col0, mlv_pk16 (&o)[STRIP])
-{
-    mlv_pk16 lo[STRIP + 2], mi[STRIP + 2], hi[STRIP + 2];
-    uint32_t v[3][8];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const uint4 a = *(const uint4 *)&pk[jrow + 1 + r][col0], b = *(const uint4 *)&pk[jrow + 1 + r][col0 + 4];
-        v[r][0] = a.x; v[r][1] = a.y; v[r][2] = a.z; v[r][3] = a.w; v[r][4] = b.x; v[r][5] = b.y; v[r][6] = b.z; v[r][7] = b.w;
-    }
-#pragma unroll
-    for (int c = 0; c < STRIP + 2; c++) {
-        const mlv_pk16 a = as_pk(v[0][c + 1]), b = as_pk(v[1][c + 1]), d = as_pk(v[2][c + 1]);
-        const mlv_pk16 mn = mlv_mn(a, b), mx = mlv_mx(a, b);
-        lo[c] = mlv_mn(mn, d);
-        hi[c] = mlv_mx(mx, d);
-        mi[c] = mlv_mx(mn, mlv_mn(mx, d));
-    }
-#pragma unroll
-    for (int c = 0; c < STRIP; c++)
-        o[c] = pk_med3(mlv_mx(mlv_mx(lo[c], lo[c + 1]), lo[c + 2]), pk_med3(mi[c], mi[c + 1], mi[c + 2]),
-                       mlv_mn(mlv_mn(hi[c], hi[c + 1]), hi[c + 2]));
-}
 // certain: every half of every median strictly inside (-32768, 32767).  t = v + 32769 (wraps) is 1 for -32768, 0 for 32767 and at
 // least 2 otherwise: the smallest t of the strip's eight halves tells (four adds, three minima, one saturating subtract)
 __device__ __forceinline__ bool pk_uncertain(const mlv_pk16 (&o)[STRIP])
@@ -225,7 +177,7 @@ __device__ __forceinline__ void cell_multi_pk_fast(const uint32_t *p0, const uin
     }
 }
 
-template <int METHOD, class SM>
+template <class SM>
 __device__ __forceinline__ void emit_item_p(SM &sm, int black, bool dark, bool slow, int ref_r, int ref_b, int p, int lk, bool edge,
                                             const uint32_t (&p0)[8], const uint32_t (&p1)[8])
 {
@@ -259,13 +211,12 @@ __device__ __forceinline__ void emit_item_p(SM &sm, int black, bool dark, bool s
     }
 }
 
-template <int METHOD, bool PACKED, int VEC, bool SPREAD>
+template <bool PACKED, int VEC, bool SPREAD>
 __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
 {
-    static_assert(METHOD == 2 || METHOD == 3 || METHOD == 5, "chroma smoothing only");
     static_assert(VEC != 0, "rows of whole 8-pixel groups");
-    constexpr bool CHAIN = METHOD == 5;
-    using Smem = SmemP<SPREAD, CHAIN>;
+    constexpr int METHOD = 5;           // (what patch_cell and strip_output are told: this kernel is the cs5x5 one)
+    using Smem = SmemP<SPREAD>;
     __shared__ Smem sm;
     constexpr int BPP = bpp_of(PACKED, VEC);
     constexpr int NEW0 = 2 * HC;
@@ -410,7 +361,7 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
     }
     __syncthreads();                           // T16 copy complete
 
-    int fb_skip = 0, fb_wait = KF_P_WAIT_MIN;  // tiles still to go to the list unseen; how many after the next uncertain tile
+    int fb_skip = 0, fb_wait = P_WAIT_MIN;  // tiles still to go to the list unseen; how many after the next uncertain tile
     bool cont = false;
     int par = 0;                               // tile parity: which of the two `unc` slots this tile uses
     int low_prev = 3;                          // (the tile before this one: conservative until there is one)
@@ -494,7 +445,7 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
                 sm.dim[par] = 1;
                 if (__any((int)lo <= a.black + 64)) sm.low[par] = 1;   // the stripes epilogue's "more than 64 above black" holds for no mask then
             }
-            emit_item_p<METHOD, Smem>(sm, a.black, dark, slow, ref_r, ref_b, p, lk, L.edge, p0, p1);
+            emit_item_p<Smem>(sm, a.black, dark, slow, ref_r, ref_b, p, lk, L.edge, p0, p1);
         };
         if (!cont) {
             // the first tile of a run (or of a column): the four plane rows above the tile's own, straight from memory -- threads
@@ -508,14 +459,10 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
                 do_item(TL, q0, q1, trw, tid_o & 15);
             }
         }
-#ifndef KFP_EXP_NOLOAD
         if (tid_o < N_ITEMS) {
             const bool l_edge = tid_o >= N_MAIN;
             do_item(item_lane<PACKED, VEC>(tid_o & 15, l_edge), r0, r1, NEW0 + (l_edge ? tid_o - N_MAIN : tid_o >> 4), tid_o & 15);
         }
-#else
-        asm volatile("" :: "v"(r0[0]), "v"(r0[1]), "v"(r0[2]), "v"(r0[3]), "v"(r1[0]), "v"(r1[1]), "v"(r1[2]), "v"(r1[3]));
-#endif
         if (tid == 0) { sm.next_tile = nt; sm.next_end = ne; }
         lds_barrier();
         if (tid == 0) { sm.unc[par ^ 1] = 0; sm.low[par ^ 1] = 0; sm.dim[par ^ 1] = 0; }          // (read by all before this barrier, written again behind the next tile's)
@@ -548,30 +495,27 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
         // ---- prefetch the next tile (and, where it starts anew, its sample) while the medians run
         Pos nxt = pos_below(cur);
         if (t_next != t + 1 || t_next >= band_end) nxt = pos_of(min(t_next, band_end - 1));
-#ifndef KFP_EXP_NOPREF
         {
             int tid_p = tid;
             asm volatile("" : "+v"(tid_p));
             issue_tile(sa, nxt, tid_p);
             if (!cont_next) issue_sample(sa, nxt, tid_p);
         }
-#endif
         // what the output stage needs of the cold arguments, in one go and early: the loads go out together, long before their first use
         const OutArgs oa = out_args(cold_args());
 
         // ---- medians + output: one thread = 4 cells = 8 px on two rows
         int tid_m = tid;
         asm volatile("" : "+v"(tid_m));
-        // lane -> (row j, strip k).  5x5: 17 consecutive lanes per tile row (16 strips and the halo group); other methods: 16
-        const int j_ = CHAIN ? (int)(__umul24((uint32_t)tid_m, 241u) >> 12) : tid_m >> 4;       // tid / 17 for tid < 256 (24-bit multiply: v_mul_lo_u32 takes twice the issue slots)
-        const int k = CHAIN ? tid_m - (int)__umul24((uint32_t)j_, 17u) : tid_m & 15;
+        // lane -> (row j, strip k): 17 consecutive lanes per tile row (16 strips and the halo group)
+        const int j_ = (int)(__umul24((uint32_t)tid_m, 241u) >> 12);       // tid / 17 for tid < 256 (24-bit multiply: v_mul_lo_u32 takes twice the issue slots)
+        const int k = tid_m - (int)__umul24((uint32_t)j_, 17u);
         const int j = min(j_, TCH - 1);
-        const bool is_strip = CHAIN ? (k < 16 && tid_m < 17 * TCH) : tid_m < N_MAIN;
-        const int y = ty0 + 2 * j, x = tx0 + 2 * STRIP * k;
+        const bool is_strip = k < 16 && tid_m < 17 * TCH;
+        const int y = ty0 + 2 * j;
         const bool smooth_row = y >= 4 && y < a.h - 5;                                    // chroma_smooth.c:25
         mlv_pk16 o[STRIP] = { { 0, 0 }, { 0, 0 }, { 0, 0 }, { 0, 0 } };
-#ifndef KFP_EXP_NOMED
-        if (CHAIN) {
+        {
             const int lane = tid_m & 63;
             const bool publishes = lane == 0 && tid_m != 0, collects = lane == 63 && tid_m < 192;
             const int wv = tid_m >> 6;
@@ -588,20 +532,10 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
             pchain_fetch_window(g, n);
             if (collects) { pchain_collect_lists(xo, n); pchain_collect_window(xo, n); }
             pchain_finish(g, n, o);
-        } else if (smooth_row) {
-            if (METHOD == 3) pstrip_median9(sm.pk, j, STRIP * k, o);
-            else pstrip_median5(sm.pk, j, STRIP * k, o);
         }
         if (is_strip && smooth_row && pk_uncertain(o)) sm.unc[par] = 1;
-#else
-        { const uint4 v = *(const uint4 *)&sm.pk[j + 2][STRIP * k]; o[0] = as_pk(v.x); o[1] = as_pk(v.y); o[2] = as_pk(v.z); o[3] = as_pk(v.w); }
-#endif
         // ---- R / B replacement, stripes, store: the medians come relative to the reference
-#ifdef KFP_EXP_NOOUT
-        if (is_strip && o[0].x == 12345 && o[1].y == 321) {
-#else
         if (is_strip) {
-#endif
             const int4 g4 = *(const int4 *)&sm.ge[j][STRIP * k];
             const int gev[STRIP] = { g4.x, g4.y, g4.z, g4.w };
             int er[STRIP], eb[STRIP];
@@ -623,11 +557,7 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
             carry = *(const int4 *)((const char *)&sm + c_at.x);
         }
         lds_barrier();
-#if defined(KFP_EXP_NOLOAD) || defined(KFP_EXP_NOPREF) || defined(KFP_EXP_NOMED) || defined(KFP_EXP_NOOUT)
-        const int unc = 0 * __builtin_amdgcn_readfirstlane(sm.unc[par]);       // (the experiments' planes hold garbage)
-#else
         const int unc = __builtin_amdgcn_readfirstlane(sm.unc[par]);
-#endif
         if (cont_next) *(int4 *)((char *)&sm + c_at.y) = carry;
         have_smp = !cont_next;
         if (unc) {
@@ -635,10 +565,10 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
             // none is skipped the next tile starts anew, with a reference of its own
             if (tid == 0) push(t, 1);
             fb_skip = fb_wait;
-            fb_wait = min(2 * fb_wait + 1, KF_P_WAIT_MAX);
+            fb_wait = min(2 * fb_wait + 1, P_WAIT_MAX);
             cont = false;
         } else {
-            fb_wait = KF_P_WAIT_MIN;
+            fb_wait = P_WAIT_MIN;
             cont = cont_next;
         }
         low_prev = low_cur;
@@ -672,7 +602,6 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
 //     chosen per row from the five rows of its window.
 // Takes long launches of 14-bit streams (rows of whole 8-pixel groups, even heights, black >= 0, stripes packed or none); everything
 // else, and every short launch, stays with k_frame_p / k_frame.
-__device__ __forceinline__ int dpp_prev_ii(int v) { return __builtin_amdgcn_mov_dpp(v, 0x138, 0xf, 0xf, true); }
 template <bool SPREAD, int VEC>
 __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols, int segs, int seg_rows, int fold, int S_OUT)
 {
@@ -685,35 +614,19 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
     __syncthreads();                                     // the only barrier
     const int lane = (int)threadIdx.x & 63;
     const int w = a.w, h = a.h, black = a.black;
-    const int rows = h >> 1, gmax = (w >> 3) - 1;
-    // fold > 1: the frame's last column is at most 64 / fold - 2 items wide and a wave takes `fold` of its segments at once, one per
-    // group of 64 / fold lanes (each with its own two halo lanes): 3584 px = 7 columns of 62 items and one of 14 -- 7.25 columns' worth
-    // of steps instead of 8
-    const int ncols_full = fold > 1 ? cols - 1 : cols, nfolded = fold > 1 ? (segs + fold - 1) / fold : 0;
-    const int per_frame = ncols_full * segs + nfolded, ntasks = cold_args()->nframes * per_frame;
+    const int rows = h >> 1;
+    const StreamGrid sg = stream_grid(cols, segs, fold);          // (the folded last column: k_stream_dev.h)
+    const int ntasks = cold_args()->nframes * sg.per_frame;
     const uint32_t pitch = (uint32_t)(w >> 3) * 14u;
     int *tickets = cold_args()->tickets;
     uint4 (*const mypark)[2][PARK_LANES] = park[threadIdx.x >> 6];
     const int plane = SPREAD ? min(max(lane - 1, 0), 61) : lane;       // the lane's slot (SPREAD: lanes 0 and 63 share their neighbours', unused)
     const bool parks = !SPREAD || (lane >= 1 && lane <= 62);
     for (;;) {
-        int task = 0;
-        if (lane == 0) task = atomicAdd(&tickets[0], 1);
-        task = __builtin_amdgcn_readfirstlane(task);
+        const int task = stream_draw(tickets, lane);
         if (task >= ntasks) break;
-        const int f = task / per_frame, rem = task - f * per_frame;
-        const bool folded = rem >= ncols_full * segs;
-        const int c = folded ? ncols_full : rem / segs, sg = folded ? (rem - ncols_full * segs) * fold : rem - c * segs;
-        const int j0 = sg * seg_rows, j1 = min(j0 + seg_rows, rows);              // (of the first group of lanes; the others lie roff rows further down)
-        const int nparts = folded ? fold : 1, P = folded ? 64 / fold : 64;
-        const int pl = lane & (P - 1), part = folded ? lane / P : 0;
-        const int roff = part * seg_rows;
-        const int g_true = c * S_OUT + pl - 1;
-        const int g = min(max(g_true, 0), gmax);
-        const bool writes = pl >= 1 && pl <= min(S_OUT, P - 2) && g_true <= gmax && j0 + roff < rows;
-        const uint32_t gbyte = (uint32_t)g * 14u;
-        const uint32_t sel = (g & 1) ? SEL_MIS : SEL_SWAP;
-        const uint32_t sel1 = VEC == 2 ? sel ^ (SEL_SWAP ^ SEL_MIS) : sel;
+        const StreamTask t = stream_task<VEC>(task, sg, segs, seg_rows, fold, S_OUT, lane, w, rows);
+        const int f = t.f, c = t.c, j0 = t.j0, j1 = t.j1, nparts = t.nparts, P = t.P, roff = t.roff;
         KArgs kt = cold_args();                          // (what a task needs once: read here, not held in scalar registers through the launch)
         const uint8_t *const frame = kt->src + (size_t)f * kt->src_stride;
         const mlv_i32x4 rs_in = frame_rsrc(frame, kt->src_bytes);
@@ -721,14 +634,7 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
         const int tx0 = 8 * (c * S_OUT - 1);
         const bool xm = c == 0 || 8 * (c * S_OUT + S_OUT) > w - 4;
         uint32_t dA0[4], dA1[4], dB0[4], dB1[4];
-        auto issue = [&](int r, uint32_t (&d0)[4], uint32_t (&d1)[4]) {
-            const int rr = min(max(r + roff, 0), rows - 1);
-            const uint32_t o0u = __umul24((uint32_t)(2 * rr), pitch) + gbyte, o0 = o0u & ~3u, o1 = (o0u + pitch) & ~3u;
-            const mlv_u32x2 a0 = mlv_rbl_x2(rs_in, (int)o0, 0, KF_SRC_AUX), b0 = mlv_rbl_x2(rs_in, (int)o0 + 8, 0, KF_SRC_AUX);
-            const mlv_u32x2 a1 = mlv_rbl_x2(rs_in, (int)o1, 0, KF_SRC_AUX), b1 = mlv_rbl_x2(rs_in, (int)o1 + 8, 0, KF_SRC_AUX);
-            d0[0] = a0.x; d0[1] = a0.y; d0[2] = b0.x; d0[3] = b0.y;
-            d1[0] = a1.x; d1[1] = a1.y; d1[2] = b1.x; d1[3] = b1.y;
-        };
+        auto issue = [&](int r, uint32_t (&d0)[4], uint32_t (&d1)[4]) { stream_issue(rs_in, r, roff, rows, pitch, t.gbyte, d0, d1); };
         issue(j0 - 2, dA0, dA1);
         issue(j0 - 1, dB0, dB1);
         // ---- the task's reference: median of five cells (no two of them neighbours) of the 16 x 4 block at its centre
@@ -810,8 +716,8 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
         int unc_r0 = 1 << 30, unc_r1 = -1;               // ... and the rows
         auto step = [&](int r, uint32_t (&d0)[4], uint32_t (&d1)[4]) {
             uint32_t p0[8], p1[8];
-            unpack8<BPP>(d0, sel, sel, sel, p0);
-            unpack8<BPP>(d1, sel1, sel1, sel1, p1);
+            unpack8<BPP>(d0, t.sel, t.sel, t.sel, p0);
+            unpack8<BPP>(d1, t.sel1, t.sel1, t.sel1, p1);
             if (r + 2 <= j1 + 1) issue(r + 2, d0, d1);
             if (n_pm) {                                   // pixel-map cells of this row: the owning lane takes the record's pixels
                 unsigned long long m = __ballot(lane < n_pm && (pm_cell >> 16) == r);
@@ -828,20 +734,10 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
                         if (mine && cc == k) { p0[2 * k] = t_ & 0xFFFFu; p0[2 * k + 1] = t_ >> 16; p1[2 * k] = b_ & 0xFFFFu; p1[2 * k + 1] = b_ >> 16; }
                 }
             }
-            uint32_t lo = min(p0[0], p1[0]);
-#pragma unroll
-            for (int i = 1; i < 8; i++) lo = min(min(lo, p0[i]), p1[i]);
-            const bool dark = __any((int)lo <= black);
-            int fl0 = 0;
-            if (__any((int)lo <= black + 255)) fl0 = __any((int)lo <= black + 64) ? 3 : 2;
+            bool dark;
+            const int fl0 = stream_row_low(p0, p1, black, dark);
             int ge[4];
             uint32_t pk[4];
-#ifdef KFP5_EXP_NOCELL
-            if (true) {
-#pragma unroll
-                for (int cc = 0; cc < 4; cc++) { ge[cc] = (int)((p0[2 * cc + 1] + p1[2 * cc]) << 12); pk[cc] = (p0[2 * cc] & 255u) | ((p1[2 * cc + 1] & 255u) << 16); }
-            } else
-#endif
             if (!dark) cell_multi_pk_fast<4, SPREAD>(p0, p1, black, t16, ref_r, ref_b, ge, pk);
             else {
 #pragma unroll
@@ -867,13 +763,6 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
                 const unsigned long long msmooth = lanes_ge(yl, 4) & lanes_lt(yl, h - 5);  // chroma_smooth.c:25
                 const bool smooth_row = y + 2 * (nparts - 1) * seg_rows >= 4 && y < h - 5; // (some group's row)
                 mlv_pk16 o[STRIP] = { { 0, 0 }, { 0, 0 }, { 0, 0 }, { 0, 0 } };
-#ifdef KFP5_EXP_NOMED
-                if (smooth_row) {
-#pragma unroll
-                    for (int cc = 0; cc < 4; cc++) o[cc] = as_pk(pkr[2][cc]);
-                    o[0] = as_pk((uint32_t)dpp_prev_ii((int)as_u(o[2])));
-                } else
-#endif
                 if (smooth_row) {
                     PGroup gq;
                     {
@@ -895,9 +784,9 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
                     pchain_finish(gq, n, oc);
                     // the chain's four medians are those of the lane's cells 2, 3 and of the NEXT lane's cells 0, 1 (its window is the lane's
                     // group and the next one): the lane's own cells 0, 1 come from the lane before
-                    o[0] = as_pk((uint32_t)dpp_prev_ii((int)as_u(oc[2]))); o[1] = as_pk((uint32_t)dpp_prev_ii((int)as_u(oc[3])));
+                    o[0] = as_pk((uint32_t)dpp_prev_i((int)as_u(oc[2]))); o[1] = as_pk((uint32_t)dpp_prev_i((int)as_u(oc[3])));
                     o[2] = oc[0]; o[3] = oc[1];
-                    const unsigned long long um = __ballot(writes && pk_uncertain(o)) & msmooth;
+                    const unsigned long long um = __ballot(t.writes && pk_uncertain(o)) & msmooth;
                     if (um) { unc_lanes |= um; unc_r0 = min(unc_r0, jr); unc_r1 = max(unc_r1, jr); }
                 }
                 int er[STRIP], eb[STRIP];
@@ -914,26 +803,8 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
                     bot[0] = b4.x; bot[1] = b4.y; bot[2] = b4.z; bot[3] = b4.w;
                 }
                 const OutArgs oa = out_args(cold_args());          // (read here, not held through the step: 39 -> 17 spilled scalars)
-                // the five rows of the window, and what smoothing makes of them (smoothed_low)
-                const int fl = fl0 | fl1 | fl2 | fl3 | fl4 | (oa.stripes && smoothed_low(er, eb) ? 1 : 0);
-#define KFP5_OUT(CLAMP, XM, BRIGHT) strip_output_t<5, true, true, CLAMP, XM, false, BRIGHT, NoSmem, true>(NoSmem(), oa, w, h, black, f, tx0, 0, jr, pl, msmooth, \
-                                                                                                          ge2, 0, er, eb, false, top, bot)
-#ifdef KFP5_EXP_NOOUT
-                if (er[0] == 0x12345 && eb[1] == 0x54321) KFP5_OUT(false, false, true);
-                else if (er[0] != 0x12345 || eb[1] != 0x54321) { top[0] ^= er[0] ^ er[1] ^ er[2] ^ er[3]; bot[0] ^= eb[0] ^ eb[1] ^ eb[2] ^ eb[3]; }
-                else
-#endif
-                if (fl & 1) { if (xm) KFP5_OUT(true, true, false); else KFP5_OUT(true, false, false); }
-                else if (xm) KFP5_OUT(false, true, false);
-                else if (fl == 0) KFP5_OUT(false, false, true);
-                else KFP5_OUT(false, false, false);
-#undef KFP5_OUT
-                if (writes) {
-                    const uint32_t vo = (__umul24((uint32_t)yl, (uint32_t)w) + (uint32_t)(8 * g)) * 2u;  // (rows below the frame: beyond the buffer's range)
-                    const mlv_u32x4 vt = { top[0], top[1], top[2], top[3] }, vb_ = { bot[0], bot[1], bot[2], bot[3] };
-                    mlv_rbs_x4(vt, rs_out, (int)vo, 0, 2);
-                    mlv_rbs_x4(vb_, rs_out, (int)vo, w * 2, 2);
-                }
+                // (the five rows of the window; stream_output adds what smoothing makes of them)
+                stream_output<5>(oa, t, tx0, xm, rs_out, w, h, black, jr, yl, msmooth, fl0 | fl1 | fl2 | fl3 | fl4, ge2, er, eb, top, bot);
             }
 #pragma unroll
             for (int cc = 0; cc < 4; cc++) { ge2[cc] = ge1[cc]; ge1[cc] = ge[cc]; }
@@ -964,20 +835,16 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
             }
         }
     }
-    if (lane == 0) {
-        const int nwaves = (int)gridDim.x * 4;
-        if (atomicAdd(&tickets[1], 1) == nwaves - 1) { tickets[0] = 0; tickets[1] = 0; }
-    }
+    stream_last_out(tickets, lane, [] {});
 }
 
-// The plan's first kernel of a cs5x5 launch (frame_plan.cpp): k_frame_p5 where it takes the launch, else k_frame_p.  (k_frame_p is
-// instantiated for cs2x2 / cs3x3 as well, which the plan never gives it: k_frame's int32 networks compile to three-input min / max /
-// med3 and the packed two-input ones save them nothing; tools/kfp_resources.sh and tools/isa_classes.py compare the two.)
+// The plan's first kernel of a cs5x5 launch (frame_plan.cpp): k_frame_p5 where it takes the launch, else k_frame_p.  (The plan gives
+// neither a cs2x2 / cs3x3 launch: k_frame's int32 networks compile to three-input min / max / med3 there and the packed two-input ones
+// save them nothing.)
 void launch_frame_p(const FramePlan &pl, int method, bool packed, int vec, bool spread, hipStream_t stream, const FrameArgs &a)
 {
-#ifdef KFP_ONLY          // (tools: two instantiations, seconds to compile)
-    if (method == 5) hipLaunchKernelGGL((k_frame_p<5, true, 1, false>), dim3(pl.first_grid), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((k_frame_p<2, true, 1, false>), dim3(pl.first_grid), dim3(256), 0, stream, a);
+#ifdef KFP_ONLY          // (tools: one instantiation, seconds to compile)
+    hipLaunchKernelGGL((k_frame_p<true, 1, false>), dim3(pl.first_grid), dim3(256), 0, stream, a);
 #else
     with_layout(method, packed, vec, spread, [&](auto M, auto P, auto V, auto S) {
         if constexpr (M.value == 5 && P.value && (V.value == 1 || V.value == 2)) {
@@ -987,14 +854,14 @@ void launch_frame_p(const FramePlan &pl, int method, bool packed, int vec, bool 
                 return;
             }
         }
-        if constexpr (M.value != 0 && V.value != 0)
-            hipLaunchKernelGGL((k_frame_p<M.value, P.value, V.value, S.value>), dim3(pl.first_grid), dim3(256), 0, stream, a);
+        if constexpr (M.value == 5 && V.value != 0)
+            hipLaunchKernelGGL((k_frame_p<P.value, V.value, S.value>), dim3(pl.first_grid), dim3(256), 0, stream, a);
     });
 #endif
 }
 
 // the code object of this file loaded when the device context is created, like the other files of the frame path (runtime.cpp:
 // get_device): without it the first clip of a process paid 1.7 ms for it at its first fused launch
-void preload_k_frame_p() { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, (const void *)k_frame_p<5, true, 1, false>); (void)hipGetLastError(); }
+void preload_k_frame_p() { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, (const void *)k_frame_p<true, 1, false>); (void)hipGetLastError(); }
 
 }  // namespace mlv

@@ -278,6 +278,14 @@ def test_fused_pass_plan(amd, monkeypatch):
     assert pick(plan(cs=2, pmap=0, held=1), "first word") == (P_NONE, 1)
     assert pick(plan(cs=3, pmap=0, held=1, s=2), "first") == (P_S,)
     assert pick(plan(cs=2, pmap=0, s=0), "first word") == (P_NONE, -1)
+    # k_frame_p and k_frame_p5 are cs5x5 kernels: whatever the stream's verdict and the launch, forcing the two-kernel path
+    # (KF_P=2, KF_P5=2) never makes one of them the first kernel of a cs2x2 / cs3x3 launch
+    for cs in (2, 3):
+        for kw in (dict(), dict(pmap=0), dict(held=1), dict(some_listed=1), dict(nframes=8), dict(nframes=50, pmap=0), dict(bpp=12, vec=3),
+                   dict(bpp=16, packed=0), dict(stripes=2), dict(s=0), dict(pmap=0, s=0)):
+            for force in (dict(p=2), dict(p=2, p5=2)):
+                p = plan(cs=cs, **kw, **force)
+                assert p["first"] in (P_NONE, P_S) and p["list_after"] == 0, (cs, kw, force)
     # no chroma smoothing: k_frame alone
     assert pick(plan(cs=0), "first list_after word grid") == (P_NONE, 0, -1, 1024)
     # 112x250: one column of 14 items, its segments folded four to a wave

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/isa_classes.py -- where the vector instructions of the headline kernel go, by ISSUE-RATE CLASS and weighted by how often
-each instruction runs per tile, from the compiler's own assembly of k_frame_p<5, true, 1, false> (METHOD, PACKED, VEC, SPREAD) --
+each instruction runs per tile, from the compiler's own assembly of k_frame_p<true, 1, false> (PACKED, VEC, SPREAD) --
 the packed-once kernel of round 5 (mlvfs_amd/csrc/k_frame_p.hip + k_frame_dev.h); rounds 2-4 analysed k_frame<5, true, 1, false>.
 
 How (no GPU needed):
@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mlvfs_amd", "csrc")
 SRC = os.path.join(CSRC, "k_frame_p.hip")
 DEV = os.path.join(CSRC, "k_frame_dev.h")
-KERNEL = "_ZN3mlv9k_frame_pILi5ELb1ELi1ELb0EEEvNS_9FrameArgsE"
+KERNEL = "_ZN3mlv9k_frame_pILb1ELi1ELb0EEEvNS_9FrameArgsE"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
          "-mllvm", "--amdgpu-sched-strategy=max-ilp", "-fno-slp-vectorize", "-DKFP_ONLY"]
 W, H, TCW, TCH5 = 3584, 1320, 64, 15
@@ -284,7 +284,7 @@ def main():
     weighted_clk = sum(c["clk"] for c in per_class.values())
     us = lambda clk_per_tile: clk_per_tile * tiles / simds / (a.clock_ghz * 1e3)
     res = {
-        "kernel": "k_frame_p<5, true, 1, false>", "same_instruction_stream_with_line_tables": same,
+        "kernel": "k_frame_p<true, 1, false>", "same_instruction_stream_with_line_tables": same,
         "static_instructions": counts["static_all"], "static_valu": counts["static_valu"],
         "tiles_per_frame": tiles, "valu_wave_instructions_per_tile": round(counts["valu"], 1),
         "valu_wave_instructions_per_frame": round(counts["valu"] * tiles),

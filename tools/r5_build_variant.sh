@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/r5_build_variant.sh NAME [extra hipcc flags] -- build/ab/NAME.so: the in-tree library with k_frame.o, k_frame_p.o and k_frame_s.o compiled with the
-# extra flags (-DKF_EXP_... switches of k_frame_dev.h); A/B on one box: tools/r5_libs_ab.sh
+# extra flags (compiler options, or a -D of an experiment of your own); A/B on one box: tools/r5_libs_ab.sh
 set -e
 cd "$(dirname "$0")/../mlvfs_amd/csrc"
 NAME=$1; shift
