@@ -28,6 +28,7 @@
 
 #define MLV_T16_N 8192
 #define MLV_U16_N 32768
+#define MLV_EV32_N 16388   // raw2ev by pixel - black + 1 (k_frame_p5's LDS table): [0] = 0, [1 + lin] = raw2ev_lin[lin], padded to whole 16-byte pieces
 
 namespace mlv {
 
@@ -47,6 +48,7 @@ struct DeviceLuts {
     const uint16_t *t16;   // [8192]   mantissa-normalised raw2ev (sparse kernels, global memory)
     const uint16_t *t16d;  // [16384]  direct raw2ev: raw2ev_lin[i] - (floor(log2 i) << 15) (LDS copy in k_frame)
     const uint16_t *u16;   // [32768]
+    const int32_t *ev32;   // [MLV_EV32_N] raw2ev itself, one entry below black in front: [0] = 0, [1 + lin] = raw2ev_lin[lin] (LDS copy in k_frame_p5)
 };
 
 struct Device {            // one per GPU, created once

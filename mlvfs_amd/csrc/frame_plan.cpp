@@ -10,7 +10,8 @@
 namespace mlv {
 
 namespace {
-constexpr int WGS_PER_CU = 4;      // every kernel of the pass: four workgroups of four waves per CU (their __launch_bounds__)
+constexpr int WGS_PER_CU = 4;      // every kernel of the pass: four workgroups of four waves per CU (their __launch_bounds__; k_frame_p5
+                                   // takes the same sixteen waves as ONE workgroup: launch_frame_p launches first_grid / 4 of them)
 constexpr int RUN_MAX = 22;        // k_frame: tiles per run at most
 constexpr int P5_SEG = 60;         // k_frame_p5: rows per task (or half as many for launches half as long)
 constexpr int S_SEG = 60;          // k_frame_s: rows per task

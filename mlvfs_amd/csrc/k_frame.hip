@@ -682,6 +682,7 @@ int launch_frame(const Device *dev, const Geom &g, bool packed, const void *src,
     a.tiles_x = frame_tiles_x(g.w);
     a.tiles_y = frame_tiles_y(g.h, frame_geo_of(method));
     a.t16 = dev->luts.t16;
+    a.ev32 = dev->luts.ev32;
     a.patch = pv && pv->n_rec > 0;
     if (a.patch) { a.cells = (const int4 *)pv->cells; a.n_rec = pv->n_rec; a.tile_off = pv->tile_off; }
     a.stripes = stripes ? 1 : 0;

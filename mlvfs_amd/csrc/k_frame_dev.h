@@ -71,6 +71,7 @@ struct FrameArgs {
     int *wl_ctl;             // [0] entries pushed, [1] entries drawn, [2] workgroups of the list-mode launch done (the last one zeroes all three), [3] tiles listed so far (statistics)
     int list_mode;
     int *wl_stat;            // page-locked host word: tiles listed so far on this stream, written by the list-mode launch when it ends
+    const int *ev32;         // k_frame_p5: raw2ev by pixel - black + 1 (common.h: MLV_EV32_N), read once per workgroup
 };
 
 // Table look-ups as buffer loads with idxen: the address unit scales the index by the descriptor's stride, no VALU address arithmetic

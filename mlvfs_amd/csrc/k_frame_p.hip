@@ -177,6 +177,60 @@ __device__ __forceinline__ void cell_multi_pk_fast(const uint32_t *p0, const uin
     }
 }
 
+// k_frame_p5's loader: the whole of raw2ev in LDS (MLV_EV32_N ints indexed by pixel - black + 1: entry 0 = 0, what raw2ev gives a pixel
+// below black, entry 1 = INT_MIN, a pixel AT black), so a pixel's EV is one address operation and one read.  koff = 4 - 4 black.
+// Common path (every pixel above black): EVs in [0, 14 << 15), nothing wraps; the green's half is a plain shift, and R's (B's) EV,
+// 1 - reference and ~green meet in one three-input add: ev - ref - green = ev + (1 - ref) + ~green.
+template <int NC>
+__device__ __forceinline__ void cell_multi_pk_tab(const uint32_t *p0, const uint32_t *p1, uint32_t koff, const int *tab, int ref_r, int ref_b,
+                                                  int (&ge)[NC], uint32_t (&pk)[NC])
+{
+    uint32_t ev[4 * NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const uint32_t px[4] = { p0[2 * c], p0[2 * c + 1], p1[2 * c], p1[2 * c + 1] };
+#pragma unroll
+        for (int i = 0; i < 4; i++) ev[4 * c + i] = *(const uint32_t *)((const char *)tab + ((px[i] << 2) + koff));
+    }
+#pragma unroll
+    for (int i = 0; i < 4 * NC; i += 8) {                // opaque uses: the reads stay unconditional and back to back
+        asm volatile("" :: "v"(ev[i]), "v"(ev[i + 1]), "v"(ev[i + 2]), "v"(ev[i + 3]), "v"(ev[i + 4]), "v"(ev[i + 5]), "v"(ev[i + 6]), "v"(ev[i + 7]));
+    }
+    uint32_t nref_r = 1u - (uint32_t)ref_r, nref_b = 1u - (uint32_t)ref_b;
+    asm("" : "+v"(nref_r), "+v"(nref_b));       // (opaque, as measured in profiles/p5_table/; without it a step is two v_mov shorter: built, not yet run)
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const uint32_t gb = (ev[4 * c + 1] + ev[4 * c + 2]) >> 1;                       // chroma_smooth.c:32,54 (both EVs >= 0: trunc == floor)
+        ge[c] = (int)gb;
+        const uint32_t ng = ~gb;
+        pk[c] = as_u(__builtin_amdgcn_cvt_pk_i16((int)add3_u32(ev[4 * c + 0], nref_r, ng), (int)add3_u32(ev[4 * c + 3], nref_b, ng)));
+    }
+}
+// Rows with a pixel at or below black: the address clamped to the table's first entry, and the reference's wrapping arithmetic on
+// what it holds there (0 and INT_MIN)
+template <int NC>
+__device__ __forceinline__ void cell_multi_pk_tab_dark(const uint32_t *p0, const uint32_t *p1, uint32_t koff, const int *tab, int ref_r, int ref_b,
+                                                       int (&ge)[NC], uint32_t (&pk)[NC])
+{
+    int ev[4 * NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const uint32_t px[4] = { p0[2 * c], p0[2 * c + 1], p1[2 * c], p1[2 * c + 1] };
+#pragma unroll
+        for (int i = 0; i < 4; i++) ev[4 * c + i] = *(const int *)((const char *)tab + max((int)((px[i] << 2) + koff), 0));
+    }
+#pragma unroll
+    for (int i = 0; i < 4 * NC; i += 8) {
+        asm volatile("" :: "v"(ev[i]), "v"(ev[i + 1]), "v"(ev[i + 2]), "v"(ev[i + 3]), "v"(ev[i + 4]), "v"(ev[i + 5]), "v"(ev[i + 6]), "v"(ev[i + 7]));
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        ge[c] = half_trunc(wadd(ev[4 * c + 1], ev[4 * c + 2]));
+        const int dr = wsub(ev[4 * c + 0], ge[c]), db = wsub(ev[4 * c + 3], ge[c]);
+        pk[c] = as_u(__builtin_amdgcn_cvt_pk_i16(__builtin_elementwise_sub_sat(dr, ref_r), __builtin_elementwise_sub_sat(db, ref_b)));   // (differences of wrapped values: saturating)
+    }
+}
+
 template <class SM>
 __device__ __forceinline__ void emit_item_p(SM &sm, int black, bool dark, bool slow, int ref_r, int ref_b, int p, int lk, bool edge,
                                             const uint32_t (&p0)[8], const uint32_t (&p1)[8])
@@ -591,7 +645,9 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
 // cell row per step, keeps the five packed rows of the window in registers, gets the right-hand group's sorted columns and rank window
 // from the next lane (v_mov_b32_dpp wave_shl, as k_frame_p's lanes do inside a row) and finishes row r - 2 when row r is in.  No
 // s_barrier after the table load, no planes in LDS (only the pixels of the three rows between load and output wait there, in the
-// wave's own 6 KiB): 113 VGPRs, 40 KiB of LDS, four workgroups per CU -- and 6.0 instead of 6.8 us per frame (profiles/r05/ab_p5.log).
+// wave's own 6 KiB): 6.0 instead of 6.8 us per frame (profiles/r05/ab_p5.log).  With no barrier to keep short, the workgroup is the
+// CU's sixteen waves, and what four small workgroups spent on four copies of the mantissa table holds raw2ev itself (MLV_EV32_N ints,
+// indexed by pixel - black + 1: cell_multi_pk_tab): 124 VGPRs, 157 KiB of LDS, one workgroup per CU (profiles/p5_table/).
 //   * Reference: one per task (a column of seg_rows rows), the median of five cells at its centre like k_frame_p's.
 //   * A strip whose packed median is not provably exact marks its lane and row; when the task ends, the tiles of k_frame's geometry
 //     that those strips lie in go on the launch's work list and the list-mode k_frame does them again (what this kernel wrote there
@@ -603,25 +659,39 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
 // Takes long launches of 14-bit streams (rows of whole 8-pixel groups, even heights, black >= 0, stripes packed or none); everything
 // else, and every short launch, stays with k_frame_p / k_frame.
 template <bool SPREAD, int VEC>
-__global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols, int segs, int seg_rows, int fold, int S_OUT)
+__global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int cols, int segs, int seg_rows, int fold, int S_OUT)
 {
+    // (SPREAD stays in the kernel's name, always false: the benchmark's result and the profiles know the kernel by it.  A directly
+    // indexed table puts neighbouring levels into neighbouring banks)
+    static_assert(!SPREAD, "one table layout");
     constexpr int BPP = 14;                              // (S_OUT: items a wave writes per row, frame_plan.h: FRAME_STREAM_COLW)
-    __shared__ __align__(16) uint16_t t16[MLV_T16_N + (SPREAD ? 64 : 0)];
-    // (the dark-clip table layout is 128 bytes longer: there only the 62 lanes that write a row park it, which keeps the workgroup at 40 KiB)
-    constexpr int PARK_LANES = SPREAD ? 62 : 64;
-    __shared__ uint4 park[4][3][2][PARK_LANES];
-    load_t16_rel<SPREAD>(t16, cold_args()->t16, (int)threadIdx.x);
+    constexpr int WAVES = 16;                            // one workgroup per CU: the CU's one copy of the table
+    // the lanes that write a row park it (1 .. 62; lanes 0 and 63 share their neighbours' slots, unused): with 64 slots a row the
+    // workgroup would need 16 bytes more than a CU has
+    constexpr int PARK_LANES = 62;
+    struct __align__(16) Smem {
+        int ev[MLV_EV32_N];                              // at offset 0: a look-up's address is its offset
+        uint4 park[WAVES][3][2][PARK_LANES];
+    };
+    static_assert(sizeof(Smem) <= 160 * 1024, "the CU's LDS");
+    __shared__ Smem sm;
+    {
+        const uint4 *s4 = (const uint4 *)cold_args()->ev32;
+        uint4 *d4 = (uint4 *)sm.ev;
+        for (int i = (int)threadIdx.x; i < MLV_EV32_N * 4 / 16; i += 64 * WAVES) d4[i] = s4[i];
+    }
     __syncthreads();                                     // the only barrier
     const int lane = (int)threadIdx.x & 63;
     const int w = a.w, h = a.h, black = a.black;
+    const uint32_t koff = 4u - 4u * (uint32_t)black;     // byte offset of a pixel's entry, less four times the pixel
     const int rows = h >> 1;
     const StreamGrid sg = stream_grid(cols, segs, fold);          // (the folded last column: k_stream_dev.h)
     const int ntasks = cold_args()->nframes * sg.per_frame;
     const uint32_t pitch = (uint32_t)(w >> 3) * 14u;
     int *tickets = cold_args()->tickets;
-    uint4 (*const mypark)[2][PARK_LANES] = park[threadIdx.x >> 6];
-    const int plane = SPREAD ? min(max(lane - 1, 0), 61) : lane;       // the lane's slot (SPREAD: lanes 0 and 63 share their neighbours', unused)
-    const bool parks = !SPREAD || (lane >= 1 && lane <= 62);
+    uint4 (*const mypark)[2][PARK_LANES] = sm.park[threadIdx.x >> 6];
+    const int plane = min(max(lane - 1, 0), PARK_LANES - 1);
+    const bool parks = lane >= 1 && lane <= PARK_LANES;
     for (;;) {
         const int task = stream_draw(tickets, lane);
         if (task >= ntasks) break;
@@ -642,9 +712,7 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
         {
             const int x0 = min(max(8 * (c * S_OUT + S_OUT / 2), 0), (w - 16) & ~1), y0 = min(j0 + j1, (h - 4) & ~1) & ~1;
             const uint32_t px = fetch_clamped<BPP>(frame, w, h, x0 + (lane & 15), y0 + (lane >> 4));
-            const int l = min(max((int)px - black, 1), 16383);
-            const int ix = ev_index(l);
-            const int ev = ev_value(l, (int)t16[SPREAD ? ix + (ix >> 7) : ix]);
+            const int ev = sm.ev[1 + min(max((int)px - black, 1), 16383)];
             constexpr int CX[5] = { 0, 3, 6, 1, 5 }, CY[5] = { 0, 0, 0, 1, 1 };
             int sdr[5], sdb[5];
 #pragma unroll
@@ -738,17 +806,8 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
             const int fl0 = stream_row_low(p0, p1, black, dark);
             int ge[4];
             uint32_t pk[4];
-            if (!dark) cell_multi_pk_fast<4, SPREAD>(p0, p1, black, t16, ref_r, ref_b, ge, pk);
-            else {
-#pragma unroll
-                for (int cc = 0; cc < 4; cc += 2) {
-                    int g2[2], r2[2], b2[2];
-                    cell_multi_ev_dark<2, SPREAD>(p0 + 2 * cc, p1 + 2 * cc, black, t16, g2, r2, b2);
-                    ge[cc] = g2[0]; ge[cc + 1] = g2[1];
-                    pk[cc] = as_u(__builtin_amdgcn_cvt_pk_i16(__builtin_elementwise_sub_sat(r2[0], ref_r), __builtin_elementwise_sub_sat(b2[0], ref_b)));
-                    pk[cc + 1] = as_u(__builtin_amdgcn_cvt_pk_i16(__builtin_elementwise_sub_sat(r2[1], ref_r), __builtin_elementwise_sub_sat(b2[1], ref_b)));
-                }
-            }
+            if (!dark) cell_multi_pk_tab<4>(p0, p1, koff, sm.ev, ref_r, ref_b, ge, pk);
+            else cell_multi_pk_tab_dark<4>(p0, p1, koff, sm.ev, ref_r, ref_b, ge, pk);
             {
                 uint4 (&slot)[2][PARK_LANES] = mypark[(unsigned)(r + 6) % 3u];
                 if (parks) {
@@ -835,7 +894,7 @@ __global__ __launch_bounds__(256, 4) void k_frame_p5(const FrameArgs a, int cols
             }
         }
     }
-    stream_last_out(tickets, lane, [] {});
+    stream_last_out(tickets, lane, WAVES, [] {});
 }
 
 // The plan's first kernel of a cs5x5 launch (frame_plan.cpp): k_frame_p5 where it takes the launch, else k_frame_p.  (The plan gives
@@ -849,7 +908,8 @@ void launch_frame_p(const FramePlan &pl, int method, bool packed, int vec, bool 
     with_layout(method, packed, vec, spread, [&](auto M, auto P, auto V, auto S) {
         if constexpr (M.value == 5 && P.value && (V.value == 1 || V.value == 2)) {
             if (pl.first == FirstKernel::p5) {
-                hipLaunchKernelGGL((k_frame_p5<S.value, V.value>), dim3(pl.first_grid), dim3(256), 0, stream, a, pl.cols, pl.segs, pl.seg_rows,
+                // (the plan counts four-wave groups; the kernel's workgroups hold sixteen waves, one workgroup per CU)
+                hipLaunchKernelGGL((k_frame_p5<false, V.value>), dim3((pl.first_grid + 3) / 4), dim3(1024), 0, stream, a, pl.cols, pl.segs, pl.seg_rows,
                                    pl.fold, FRAME_STREAM_COLW);
                 return;
             }

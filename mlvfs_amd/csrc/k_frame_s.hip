@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256, 4) void k_frame_s(const FrameArgs a, int cols,
         }
         if (lane == 0 && dark_steps) atomicAdd(&a.wl_ctl[0], dark_steps);       // (what the host's choice of kernel for this stream looks at)
     }
-    stream_last_out(tickets, lane, [&] { if (a.wl_stat) { __atomic_store_n(a.wl_stat, a.wl_ctl[0], __ATOMIC_RELAXED); __threadfence_system(); } });
+    stream_last_out(tickets, lane, 4, [&] { if (a.wl_stat) { __atomic_store_n(a.wl_stat, a.wl_ctl[0], __ATOMIC_RELAXED); __threadfence_system(); } });
 }
 
 // k_frame_s as the plan lays it out (frame_plan.cpp: which launches it takes, its grid and tasks)

@@ -125,12 +125,12 @@ __device__ __forceinline__ void stream_output(const OutArgs &oa, const StreamTas
 }
 
 // The last wave out leaves the two counters as it found them (the next launch on this stream starts from zero), then does `after`
-// (its lane 0 only).
+// (its lane 0 only).  waves_per_wg: of the kernel's workgroups (k_frame_s: 4, k_frame_p5: 16).
 template <class AFTER>
-__device__ __forceinline__ void stream_last_out(int *tickets, int lane, AFTER after)
+__device__ __forceinline__ void stream_last_out(int *tickets, int lane, int waves_per_wg, AFTER after)
 {
     if (lane == 0) {
-        const int nwaves = (int)gridDim.x * 4;
+        const int nwaves = (int)gridDim.x * waves_per_wg;
         if (atomicAdd(&tickets[1], 1) == nwaves - 1) {
             tickets[0] = 0; tickets[1] = 0;
             after();

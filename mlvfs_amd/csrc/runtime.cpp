@@ -232,8 +232,13 @@ static Device *get_device(int id)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, id) == hipSuccess) d->num_cu = prop.multiProcessorCount;
     uint16_t *t16 = nullptr, *t16d = nullptr, *u16 = nullptr;
+    int32_t *ev32 = nullptr;
+    // (k_frame_p5's table is indexed by pixel - black + 1: the same for every black level)
+    std::vector<int32_t> h_ev32(MLV_EV32_N, 0);
+    std::copy(host_raw2ev_lin(), host_raw2ev_lin() + 16384, h_ev32.begin() + 1);
     if (hipMalloc(&t16, MLV_T16_N * 2) != hipSuccess || hipMalloc(&u16, MLV_U16_N * 2) != hipSuccess ||
-        hipMalloc(&t16d, 16384 * 2) != hipSuccess ||
+        hipMalloc(&t16d, 16384 * 2) != hipSuccess || hipMalloc(&ev32, MLV_EV32_N * 4) != hipSuccess ||
+        hipMemcpy(ev32, h_ev32.data(), MLV_EV32_N * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(t16d, host_t16d(), 16384 * 2, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(t16, host_t16(), MLV_T16_N * 2, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(u16, host_u16(), MLV_U16_N * 2, hipMemcpyHostToDevice) != hipSuccess) {
@@ -244,6 +249,7 @@ static Device *get_device(int id)
     d->luts.t16 = t16;
     d->luts.t16d = t16d;
     d->luts.u16 = u16;
+    d->luts.ev32 = ev32;
     // HIP loads a file's code object at the first launch of one of its kernels: about 1 ms each for the four files of the frame
     // path, 2 ms for k_frame's 68 instantiations -- paid here, once per device, instead of inside the first frame of the first
     // clip (bench.py first_frame_split_ms; MLVFS_AMD_PRELOAD=0 leaves them lazy).  The dual-ISO, LJ92 and preview files stay lazy.
