@@ -549,6 +549,51 @@ int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out,
                                  int batch_frames, int io_threads, int *results);
 void mlvfs_amd_mount_close(void *mount);
 
+/* -- dark-frame subtraction (csrc/dark.cpp, csrc/k_dark.hip) ---- */
+/* A dark frame: a plane of width x height 16-bit values of `bpp` bits with a pedestal black_d, the black level of the clip it was
+ * averaged from.  Subtraction, per pixel in 32-bit signed arithmetic:   out = clamp(px - dark + black_d, 0, 2^bpp - 1).
+ * The plane is applied by position in the stored frame (xRes x yRes); panPosX/Y and cropPosX/Y are ignored.  The frame's own levels,
+ * its RAWI block and its DNG header do not change.  It is stage 0: after unpack / LZMA / LJ92 decode, before deflicker, pattern
+ * noise, dual ISO, pixel repair, chroma smoothing and stripes, which all see subtracted pixels.  The reference has no such stage
+ * (`mlv_dump -s` / `-a` do it a frame at a time on a host core).
+ * A handle keeps the plane on the host and uploads it once per device, on that device's first use; afterwards it is read-only: it may
+ * be shared between threads and mounts and must outlive the mounts that use it.                                                   */
+typedef struct mlvfs_amd_dark mlvfs_amd_dark_t;
+/* geom: width, height, bpp (1..16) and black (= black_d, 0..65535) are used.  Host code: needs no HIP device.  NULL on a null
+ * argument, a non-positive size (or 2^27 pixels and more), bpp or black out of range (mlvfs_amd_last_error).                      */
+mlvfs_amd_dark_t *mlvfs_amd_dark_create(const mlvfs_amd_geom_t *geom, const uint16_t *h_plane);
+/* The rounded mean of frames first .. first + count - 1 of an opened clip (plain, LZMA or LJ92 payloads), 1 <= count <= 65536:
+ *     dark[p] = (sum of px_f[p] over the frames + count / 2) / count      (integer division; 32-bit unsigned sums)
+ * summed on the GPU in batches of batch_frames frames (<= 0: 8); count = 1 gives the frame itself.  black_d is the black level of
+ * frame `first`.  NULL: frames outside the clip, count > 65536, frames of more than one geometry, a read or device failure.      */
+mlvfs_amd_dark_t *mlvfs_amd_dark_from_clip(const void *reader, int first, int count, int batch_frames, int io_threads);
+/* geom (optional): width, height, bpp, black = black_d, the rest 0; frames_averaged (optional): 0 for a plane given to
+ * mlvfs_amd_dark_create.  Host code.                                                                                              */
+int  mlvfs_amd_dark_info(const mlvfs_amd_dark_t *dark, mlvfs_amd_geom_t *geom, int *frames_averaged);
+/* the plane into h_plane[width * height]; MLVFS_AMD_ERR_ARG when cap_pixels is smaller.  Host code.                              */
+int  mlvfs_amd_dark_plane(const mlvfs_amd_dark_t *dark, uint16_t *h_plane, size_t cap_pixels);
+void mlvfs_amd_dark_destroy(mlvfs_amd_dark_t *dark);
+/* In place on nframes 16-bit device frames `stride` bytes apart (bytes between them are not touched); asynchronous on `stream`.
+ * geom's width, height and bpp must be the dark frame's: anything else is MLVFS_AMD_ERR_ARG before any device work.  width * height
+ * a multiple of 16 with d_frames and stride 16-byte aligned takes the fast form (16 pixels per lane), anything else down to 2-byte
+ * alignment one pixel per lane.                                                                                                   */
+int  mlvfs_amd_dark_subtract_dev(const mlvfs_amd_dark_t *dark, const mlvfs_amd_geom_t *geom, void *d_frames, size_t stride,
+                                 int nframes, void *stream);
+/* The mount subtracts `dark` from every frame it serves, between the read and everything else (mlvfs_amd_mount_dng and
+ * mlvfs_amd_mount_dng_lossless alike).  NULL clears.  MLVFS_AMD_ERR_ARG once the handle has served a frame, or when width, height
+ * or bpp differ from the clip's.
+ * The bad-pixel map is the process's, shared per clip GUID like cs.c's (see mlvfs_amd_mount_open), and is detected from the first
+ * frame that reaches the repair -- with a dark frame set, a subtracted one.  Mounts of one clip with different dark frames, or with
+ * and without one, in one process share whichever map was detected first: call free_focus_pixel_maps() between them where each is to
+ * behave like a fresh process (which is what the byte-for-byte equalities are stated for).                                        */
+int  mlvfs_amd_mount_set_dark(void *mount, const mlvfs_amd_dark_t *dark);
+/* mlvfs_amd_mlv_transcode with the dark frame subtracted from every frame: the same container rules, refusals, clean-up and stats.
+ * With a dark frame, plain output of a plain or LZMA clip goes through the GPU too (upload, unpack and subtract in one pass,
+ * mlvfs_amd_pack_dev).  A frame whose width, height or bpp is not the dark frame's: MLVFS_AMD_ERR_ARG before any output file
+ * exists.  dark = NULL: mlvfs_amd_mlv_transcode itself, the host-only route included.                                             */
+int  mlvfs_amd_mlv_transcode_dark(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark,
+                                  int batch_frames, int io_threads, long long stats[4]);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):

@@ -185,12 +185,32 @@ int deflicker_batch_device(const void *d_frames, size_t fstride, int nframes, in
                            uint16_t *med, hipStream_t stream);
 size_t deflicker_batch_scratch_bytes(int bpp, int nframes);
 void deflicker_bias(int target, int black_level, uint16_t median, int32_t exposure_bias[2]);
-// the mount's reader half (mlvreader.cpp): frames of one geometry from the file to 16-bit pixels in HBM; synchronises s
+// what a frame's payload is, from its chunk's videoClass (mlv.h:30-31: LZMA 0x80, LJ92 0x100; main.c:573 tests the LZMA flag first)
+enum { PAYLOAD_PLAIN = 0, PAYLOAD_LZMA = 1, PAYLOAD_LJ92 = 2 };
+inline int payload_kind(uint16_t video_class) { return (video_class & 0x80) ? PAYLOAD_LZMA : (video_class & 0x100) ? PAYLOAD_LJ92 : PAYLOAD_PLAIN; }
+// A dark FRAME (dark.cpp, k_dark.hip: a sensor's offset pattern to subtract; not the "dark clips" of dark_share and the T16 layout,
+// which are low-light footage) as the kernels take it: the plane on the current device, its pedestal, 2^bpp - 1
+struct DarkFrameDev {
+    const uint16_t *d_plane;
+    int black, top;
+};
+// the handle's plane on the calling thread's device (uploaded on the device's first use); the geometry must be the handle's
+int darkframe_on_device(const mlvfs_amd_dark_t *dark, ThreadCtx *c, int w, int h, int bpp, DarkFrameDev *out);
+bool darkframe_fits(const mlvfs_amd_dark_t *dark, int w, int h, int bpp);
+int launch_dark_sub(void *d_frames, size_t stride, uint32_t npix, int nframes, const DarkFrameDev &dark, hipStream_t stream);
+int launch_dark_unpack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int nframes,
+                       const DarkFrameDev &dark, hipStream_t stream);
+int launch_dark_accum(const void *d_frames, size_t stride, uint32_t npix, int nframes, uint32_t *d_sums, hipStream_t stream);
+int launch_dark_mean(const uint32_t *d_sums, uint16_t *d_dark, uint32_t npix, uint32_t n, hipStream_t stream);
+// the mount's reader half (mlvreader.cpp): frames of one geometry from the file to 16-bit pixels in HBM.  On return everything that
+// reads the reader's staging has ended on s; without `dark` s is drained.  dark: stage 0, the dark frame subtracted from every frame
+// as it arrives -- plain and LZMA payloads inside the unpack pass (s drained on return), LJ92 payloads in a pass behind the decoder
+// that may still be in flight on s on return: the caller goes on on s, or synchronises it
 int reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                      hipStream_t s);
+                      hipStream_t s, const DarkFrameDev *dark = nullptr);
 // the same for frames named one by one (all of one geometry and payload kind); stage_locked: the caller holds reader_stage_mutex
 int reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                     hipStream_t s, bool stage_locked);
+                     hipStream_t s, bool stage_locked, const DarkFrameDev *dark = nullptr);
 // what the transcoder (mlvwriter.cpp) asks of an opened clip: its path and chunk files, where a frame's VIDF block lies, the bytes of
 // its payload as read_frames (lj92: as the LJ92 decoder) takes it, packed payloads of plain and LZMA frames (host only), and the
 // mutex that serialises the reader's streaming calls

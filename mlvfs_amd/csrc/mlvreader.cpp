@@ -414,10 +414,11 @@ int read_frames(const Reader &r, int first, int count, uint8_t *dst, size_t stri
 
 // The mount (mount.cpp) and the transcoder (mlvwriter.cpp): `count` frames of one geometry and one payload kind, named by list[], as
 // 16-bit pixels in HBM, `dstride` bytes apart, on `s` -- payloads read by io_threads threads into the reader's page-locked staging
-// (LZMA decoded there), then uploaded and unpacked (k_unpack) or, LJ92 clips, decoded on the GPU.  Returns with the stream drained:
-// the staging is the next caller's again.  stage_locked: the caller holds the reader's staging mutex already.
+// (LZMA decoded there), then uploaded and unpacked (k_unpack) or, LJ92 clips, decoded on the GPU.  Returns with the stream drained
+// of everything that reads the staging: it is the next caller's again.  dark: the dark frame to subtract (k_dark.hip), in the unpack
+// pass or, LJ92 clips, in a pass behind the decoder that is still in flight on `s` on return.  stage_locked: the caller holds the reader's staging mutex already.
 int mlv::reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                          hipStream_t s, bool stage_locked)
+                          hipStream_t s, bool stage_locked, const DarkFrameDev *dark)
 {
     const Reader &r = *(const Reader *)reader;
     if (count <= 0) return MLVFS_AMD_OK;
@@ -441,13 +442,16 @@ int mlv::reader_load_list(const void *reader, const int *list, int count, int w,
         std::vector<const void *> ptr(count);
         std::vector<size_t> len(count);
         for (int i = 0; i < count; i++) { ptr[i] = r.stage[0] + (size_t)i * stride + 4; len[i] = sizes[i] - 4; }
-        return mlvfs_amd_lj92_decode_dev(ptr.data(), len.data(), count, w, h, d_frames, dstride, s);     // (synchronises s)
+        rc = mlvfs_amd_lj92_decode_dev(ptr.data(), len.data(), count, w, h, d_frames, dstride, s);     // (synchronises s)
+        if (rc || !dark) return rc;
+        return launch_dark_sub(d_frames, dstride, (uint32_t)w * (uint32_t)h, count, *dark, s);         // (the staging is free already)
     }
     rc = ensure_packed_dev(r, stride * count);
     if (rc) return rc;
     const mlvfs_amd_geom_t geom{ w, h, bpp, 0, 0, 0, 0 };
     MLV_HIP(hipMemcpyAsync(r.d_di_packed, r.stage[0], stride * count, hipMemcpyHostToDevice, s));
-    rc = mlvfs_amd_unpack_dev(&geom, r.d_di_packed, stride, d_frames, dstride, count, s);
+    rc = dark ? launch_dark_unpack(r.d_di_packed, stride, d_frames, dstride, (uint32_t)w * (uint32_t)h, bpp, count, *dark, s)
+              : mlvfs_amd_unpack_dev(&geom, r.d_di_packed, stride, d_frames, dstride, count, s);
     if (rc) return rc;
     MLV_HIP(hipStreamSynchronize(s));
     return MLVFS_AMD_OK;
@@ -455,12 +459,12 @@ int mlv::reader_load_list(const void *reader, const int *list, int count, int w,
 
 // frames first .. first + count - 1
 int mlv::reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                           hipStream_t s)
+                           hipStream_t s, const DarkFrameDev *dark)
 {
     if (count <= 0) return MLVFS_AMD_OK;
     std::vector<int> list(count);
     for (int k = 0; k < count; k++) list[k] = first + k;
-    return reader_load_list(reader, list.data(), count, w, h, bpp, d_frames, dstride, io_threads, s, false);
+    return reader_load_list(reader, list.data(), count, w, h, bpp, d_frames, dstride, io_threads, s, false, dark);
 }
 
 // ---- what the transcoder (mlvwriter.cpp) asks of an opened clip -------------------------------------------------------------

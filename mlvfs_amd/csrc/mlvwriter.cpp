@@ -17,6 +17,8 @@
 //                          -> k_mlv_tile -> lje_encode_batch -> lengths and streams to page-locked staging -> file
 //   plain from LJ92        GPU decode -> k_mlv_pack -> file
 //   plain from plain/LZMA  host only: the packed bytes read_frames yields are written as they are (no HIP device needed)
+// With a dark frame (mlvfs_amd_mlv_transcode_dark) reader_load_list subtracts it from every frame (stage 0: k_dark.hip), and a plain or
+// LZMA source with plain output goes upload -> unpack + subtract -> k_mlv_pack, the route of an LJ92 source.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -39,7 +41,7 @@ namespace {
 
 constexpr uint16_t CLASS_RAW = 0x01, CLASS_KIND = 0x0F, CLASS_DELTA = 0x40, CLASS_LZMA = 0x80, CLASS_LJ92 = 0x100;   // mlv.h:25-32
 constexpr size_t VIDEO_CLASS_AT = 32;                                                           // offsetof(mlv_file_hdr_t, videoClass)
-enum { SRC_PLAIN = 0, SRC_LZMA = 1, SRC_LJ92 = 2 };
+enum { SRC_PLAIN = PAYLOAD_PLAIN, SRC_LZMA = PAYLOAD_LZMA, SRC_LJ92 = PAYLOAD_LJ92 };
 
 struct Block {
     uint8_t type[4];
@@ -157,6 +159,7 @@ struct DevRoom : LjeRoom {
 
 struct Job {
     const void *reader;
+    const mlvfs_amd_dark_t *dark = nullptr;
     int payload, batch, io_threads;
     std::vector<Frame> frames;
     std::vector<std::vector<Block>> chunks;
@@ -173,7 +176,7 @@ struct Job {
 
 size_t plain_bytes(const Frame &f) { return (size_t)(((uint64_t)f.w * f.h * f.bpp + 15) / 16) * 2; }
 
-bool on_host(const Job &j, const Frame &f) { return j.payload == MLVFS_AMD_MLV_PLAIN && f.kind != SRC_LJ92; }
+bool on_host(const Job &j, const Frame &f) { return j.payload == MLVFS_AMD_MLV_PLAIN && f.kind != SRC_LJ92 && !j.dark; }
 
 bool same_batch(const Frame &a, const Frame &b) { return a.w == b.w && a.h == b.h && a.bpp == b.bpp && a.kind == b.kind; }
 
@@ -215,7 +218,10 @@ int batch_device(Job &j, const std::vector<int> &list)
     const uint32_t npix = (uint32_t)f.w * (uint32_t)f.h;
     const size_t img = (size_t)npix * 2, dstride = up(img, 256);
     if (int rc = d.frames(dstride * n)) return rc;
-    int rc = reader_load_list(j.reader, list.data(), n, f.w, f.h, f.bpp, d.d_frames, dstride, j.io_threads, s, true);
+    DarkFrameDev dark{};
+    int rc = j.dark ? darkframe_on_device(j.dark, j.ctx, f.w, f.h, f.bpp, &dark) : MLVFS_AMD_OK;
+    if (rc) return rc;
+    rc = reader_load_list(j.reader, list.data(), n, f.w, f.h, f.bpp, d.d_frames, dstride, j.io_threads, s, true, j.dark ? &dark : nullptr);
     if (rc) return rc;
     if (j.payload == MLVFS_AMD_MLV_PLAIN) {
         const size_t bytes = plain_bytes(f), pstride = up(bytes, 16);
@@ -371,7 +377,8 @@ bool list_blocks(Job &j, int nchunks, const std::map<std::pair<int, uint64_t>, i
     return ok;
 }
 
-int transcode(const void *reader, const char *out_path, int payload, int batch_frames, int io_threads, long long stats[4])
+int transcode(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark, int batch_frames, int io_threads,
+              long long stats[4])
 {
     if (!reader || !out_path || !stats) { set_error("mlv transcode: null argument"); return MLVFS_AMD_ERR_ARG; }
     for (int i = 0; i < 4; i++) stats[i] = 0;
@@ -385,6 +392,7 @@ int transcode(const void *reader, const char *out_path, int payload, int batch_f
     Job j;
     j.reader = reader;
     j.payload = payload;
+    j.dark = dark;
     j.batch = batch_frames <= 0 ? 8 : batch_frames;
     j.io_threads = io_threads;
     const int nchunks = mlvfs_amd_mlv_chunk_count(reader), nframes = mlvfs_amd_mlv_frame_count(reader);
@@ -416,10 +424,14 @@ int transcode(const void *reader, const char *out_path, int payload, int batch_f
         f.w = fh.rawi_hdr.xRes;
         f.h = fh.rawi_hdr.yRes;
         f.bpp = fh.rawi_hdr.raw_info.bits_per_pixel;
-        f.kind = (vc & CLASS_LZMA) ? SRC_LZMA : (vc & CLASS_LJ92) ? SRC_LJ92 : SRC_PLAIN;     // main.c:573 tests the LZMA flag first
+        f.kind = payload_kind(vc);
         if (f.w <= 0 || f.h <= 0 || f.bpp < 1 || f.bpp > 16 || (uint64_t)f.w * f.h >= (1u << 27)) { set_error("mlv transcode: frame %d: %dx%d at %d bits is not supported", k, f.w, f.h, f.bpp); return MLVFS_AMD_ERR_ARG; }
         if (payload == MLVFS_AMD_MLV_LJ92 && ((f.w | f.h) & 1)) {
             set_error("mlv transcode: frame %d: the quadrant tiling of an LJ92 payload takes even sizes, not %dx%d", k, f.w, f.h);
+            return MLVFS_AMD_ERR_ARG;
+        }
+        if (dark && !darkframe_fits(dark, f.w, f.h, f.bpp)) {
+            set_error("mlv transcode: frame %d: %dx%d at %d bits is not the dark frame's geometry", k, f.w, f.h, f.bpp);
             return MLVFS_AMD_ERR_ARG;
         }
         size_t bytes;
@@ -447,8 +459,15 @@ extern "C" {
 
 int mlvfs_amd_mlv_transcode(const void *reader, const char *out_path, int payload, int batch_frames, int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, batch_frames, io_threads, stats); }
+    try { return transcode(reader, out_path, payload, nullptr, batch_frames, io_threads, stats); }
     catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }    // (allocations sized from the file)
+}
+
+int mlvfs_amd_mlv_transcode_dark(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark, int batch_frames,
+                                 int io_threads, long long stats[4])
+{
+    try { return transcode(reader, out_path, payload, dark, batch_frames, io_threads, stats); }
+    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
 }
 
 int mlvfs_amd_lj92_tile_dev(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int width, int height, int nframes, void *stream)

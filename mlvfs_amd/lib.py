@@ -61,6 +61,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_mount_open", "mlvfs_amd_mount_dng", "mlvfs_amd_mount_close",
     "mlvfs_amd_lj92_encode_batch_dev", "mlvfs_amd_dng_header_lossless", "mlvfs_amd_mount_dng_lossless",
     "mlvfs_amd_lj92_tile_dev", "mlvfs_amd_pack_dev", "mlvfs_amd_mlv_transcode",
+    "mlvfs_amd_dark_create", "mlvfs_amd_dark_from_clip", "mlvfs_amd_dark_info", "mlvfs_amd_dark_plane", "mlvfs_amd_dark_destroy",
+    "mlvfs_amd_dark_subtract_dev", "mlvfs_amd_mount_set_dark", "mlvfs_amd_mlv_transcode_dark",
 ]
 
 
@@ -226,6 +228,14 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_lj92_tile_dev", i, [vp, sz, vp, sz, i, i, i, vp])
     sig("mlvfs_amd_pack_dev", i, [gp, vp, sz, vp, sz, i, vp])
     sig("mlvfs_amd_mlv_transcode", i, [vp, C.c_char_p, i, i, i, C.POINTER(C.c_longlong)])
+    sig("mlvfs_amd_dark_create", vp, [gp, vp])
+    sig("mlvfs_amd_dark_from_clip", vp, [vp, i, i, i, i])
+    sig("mlvfs_amd_dark_info", i, [vp, gp, C.POINTER(i)])
+    sig("mlvfs_amd_dark_plane", i, [vp, vp, sz])
+    sig("mlvfs_amd_dark_destroy", None, [vp])
+    sig("mlvfs_amd_dark_subtract_dev", i, [vp, gp, vp, sz, i, vp])
+    sig("mlvfs_amd_mount_set_dark", i, [vp, vp])
+    sig("mlvfs_amd_mlv_transcode_dark", i, [vp, C.c_char_p, i, vp, i, i, C.POINTER(C.c_longlong)])
     _lib = L
     return L
 

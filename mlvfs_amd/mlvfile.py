@@ -181,11 +181,16 @@ class MlvReader:
                                                        io_threads, lib.ptr(res)), "mlv_process_dualiso")
         return res
 
-    def transcode(self, out_path: str, lj92: bool = True, batch: int = 0, io_threads: int = 0) -> dict:
+    def transcode(self, out_path: str, lj92: bool = True, batch: int = 0, io_threads: int = 0, dark=None) -> dict:
         """mlvfs_amd_mlv_transcode: the clip written again as <out_path> (+ .M00 ...) with lossless-JPEG payloads (lj92=True, what
         `mlv_dump -c` writes) or plain packed ones; blocks stay in the source's file order, NULL and XREF blocks are dropped, nothing is
-        overwritten.  Plain output of a plain or LZMA clip needs no GPU.  -> {frames, bytes_in, bytes_out, files}."""
+        overwritten.  Plain output of a plain or LZMA clip needs no GPU.  dark: a mlvfs_amd.dark.Dark subtracted from every frame first
+        (mlvfs_amd_mlv_transcode_dark; every route then runs on the GPU).  -> {frames, bytes_in, bytes_out, files}."""
         stats = (C.c_longlong * 4)()
-        lib.check(self.L.mlvfs_amd_mlv_transcode(self.h, os.fsencode(out_path), lib.MLV_LJ92 if lj92 else lib.MLV_PLAIN, batch, io_threads,
-                                                 stats), "mlv_transcode")
+        payload = lib.MLV_LJ92 if lj92 else lib.MLV_PLAIN
+        if dark is None:
+            rc = self.L.mlvfs_amd_mlv_transcode(self.h, os.fsencode(out_path), payload, batch, io_threads, stats)
+        else:
+            rc = self.L.mlvfs_amd_mlv_transcode_dark(self.h, os.fsencode(out_path), payload, dark.h, batch, io_threads, stats)
+        lib.check(rc, "mlv_transcode")
         return dict(frames=int(stats[0]), bytes_in=int(stats[1]), bytes_out=int(stats[2]), files=int(stats[3]))

@@ -1,10 +1,12 @@
 """Rewrite a clip with lossless-JPEG payloads (what `mlv_dump -c` writes) or plain packed ones (--plain, `mlv_dump -d`) on the GPU:
 mlvfs_amd_mlv_transcode (csrc/mlvwriter.cpp).
 
-    python tools/mlv_transcode.py SRC.MLV DST.MLV [--plain] [--batch N] [--io-threads N]
+    python tools/mlv_transcode.py SRC.MLV DST.MLV [--plain] [--batch N] [--io-threads N] [--dark DARK.MLV [--dark-frames A:B]]
 
 Source chunks SRC.M00 ... become DST.M00 ...; blocks keep the source's file order, NULL and XREF blocks are dropped, nothing is
-overwritten and no .IDX is written.  Plain output of a plain or LZMA clip needs no GPU."""
+overwritten and no .IDX is written.  Plain output of a plain or LZMA clip needs no GPU.  --dark: the clip DARK.MLV (its frames A .. B - 1,
+default all) is averaged into a dark frame first, which is then subtracted from every frame (mlvfs_amd_dark_from_clip,
+mlvfs_amd_mlv_transcode_dark; what `mlv_dump -a` and `-s` do)."""
 import argparse
 import os
 import sys
@@ -13,6 +15,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mlvfs_amd import mlvfile
+from mlvfs_amd.dark import Dark
 
 
 def main() -> int:
@@ -22,11 +25,26 @@ def main() -> int:
     ap.add_argument("--plain", action="store_true", help="plain packed payloads instead of LJ92")
     ap.add_argument("--batch", type=int, default=0, help="frames per GPU batch (default 8)")
     ap.add_argument("--io-threads", type=int, default=0)
+    ap.add_argument("--dark", metavar="PATH", help="a clip of dark frames: averaged, then subtracted from every frame")
+    ap.add_argument("--dark-frames", metavar="A:B", help="the frames of --dark to average (default: all)")
     a = ap.parse_args()
+    if a.dark_frames and not a.dark:
+        ap.error("--dark-frames needs --dark")
+    dark = None
+    if a.dark:
+        with mlvfile.MlvReader(a.dark) as dr:
+            lo, _, hi = (a.dark_frames or ":").partition(":")
+            first = int(lo) if lo else 0
+            count = (int(hi) if hi else dr.frame_count) - first
+            t0 = time.perf_counter()
+            dark = Dark.from_clip(dr, first, count, batch=a.batch, io_threads=a.io_threads)
+            print(f"dark frame: the mean of {count} frame(s) of {a.dark} in {time.perf_counter() - t0:.3f} s, pedestal {dark.info()['black']}")
     with mlvfile.MlvReader(a.src) as r:
         t0 = time.perf_counter()
-        s = r.transcode(a.dst, lj92=not a.plain, batch=a.batch, io_threads=a.io_threads)
+        s = r.transcode(a.dst, lj92=not a.plain, batch=a.batch, io_threads=a.io_threads, dark=dark)
         dt = time.perf_counter() - t0
+    if dark is not None:
+        dark.close()
     print(f"{s['frames']} frames in {s['files']} file(s), {dt:.3f} s ({s['frames'] / dt:.1f} frames/s): payload bytes {s['bytes_in']} -> {s['bytes_out']}"
           f" ({s['bytes_out'] / max(s['bytes_in'], 1):.3f})")
     return 0
