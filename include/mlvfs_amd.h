@@ -594,6 +594,36 @@ int  mlvfs_amd_mount_set_dark(void *mount, const mlvfs_amd_dark_t *dark);
 int  mlvfs_amd_mlv_transcode_dark(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark,
                                   int batch_frames, int io_threads, long long stats[4]);
 
+/* -- a clip at another bit depth (csrc/mlvwriter.cpp, csrc/k_mlvpack.hip) -- what `mlv_dump -b` does ------------- */
+/* For a frame whose RAWI block says bpp bits and a requested out_bpp, d = out_bpp - bpp:
+ *     out = px >> -d  (d < 0: truncation; no rounding, no dither)      out = px << d  (d > 0)      out = px  (d = 0)
+ * A dark frame, if any, is subtracted first, at the source's depth (stage 0); the shift comes after it.  The reference has no such
+ * code: the definition is this project's.
+ * mlvfs_amd_rawi_set_bits applies the same rule to a RAWI block in place (host code, no HIP device): raw_info.bits_per_pixel =
+ * out_bpp; black_level and white_level shifted like pixels; pitch = raw_info.width * out_bpp / 8; frame_size = xRes * yRes *
+ * out_bpp / 8 (integer divisions); every other byte stays.  MLVFS_AMD_ERR_ARG, with the block untouched: a null pointer, out_bpp
+ * outside 8..16, a bits_per_pixel outside 1..16.                                                                                 */
+int  mlvfs_amd_rawi_set_bits(mlv_rawi_hdr_t *rawi, int out_bpp);
+/* Packed payloads of geom->bpp bits (1..16) -> packed payloads of out_bpp bits (8..16) in one pass: unpack, `dark` subtracted
+ * (NULL: none; its width, height and bpp must be geom's), shift, pack.  Input as mlvfs_amd_unpack_dev takes it, output as
+ * mlvfs_amd_pack_dev writes it: exactly ceil(width * height * out_bpp / 16) words per frame, the unused low bits of the last word
+ * zero, nothing behind it touched.  14 / 12 / 10 bits on both sides with width * height a multiple of 16 and 4-byte aligned buffers
+ * and strides take the fast form (16 pixels per lane: bpp / 2 dwords in, out_bpp / 2 dwords out), anything else down to 2-byte
+ * alignment one output word per lane.  Not in place.  Asynchronous on `stream`; every check happens before any device work.       */
+int  mlvfs_amd_repack_dev(const mlvfs_amd_geom_t *geom, int out_bpp, const mlvfs_amd_dark_t *dark, const void *d_packed,
+                          size_t packed_stride, void *d_out, size_t out_stride, int nframes, void *stream);
+/* mlvfs_amd_mlv_transcode_dark at another bit depth: every frame whose depth is not out_bpp is shifted (after the dark frame) and
+ * written at out_bpp -- a plain payload of ceil(w * h * out_bpp / 16) words, an LJ92 payload encoded at out_bpp precision --, and
+ * every RAWI block of another depth, in every chunk, is rewritten from its own content as mlvfs_amd_rawi_set_bits does.  The shift
+ * rides in a pass the route makes anyway: a plain or LZMA source to plain output is unpacked, subtracted, shifted and packed in one
+ * (as in mlvfs_amd_repack_dev), so with a conversion that route goes through the GPU, as it does with a dark frame.  Everything else
+ * -- container rules, refusals, clean-up, stats -- is mlvfs_amd_mlv_transcode's.  out_bpp = 0, or the depth every frame has already:
+ * mlvfs_amd_mlv_transcode_dark itself, byte for byte and launch for launch, the host-only route included.  out_bpp outside
+ * {0, 8..16}: MLVFS_AMD_ERR_ARG before any output file exists.  A frame that cannot be encoded at the new depth fails the call and
+ * is named in the error, as before: widening to 16 bits in particular can produce a difference of class 16.                       */
+int  mlvfs_amd_mlv_transcode_bits(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark,
+                                  int batch_frames, int io_threads, long long stats[4]);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):

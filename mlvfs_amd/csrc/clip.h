@@ -206,11 +206,19 @@ int launch_dark_mean(const uint32_t *d_sums, uint16_t *d_dark, uint32_t npix, ui
 // reads the reader's staging has ended on s; without `dark` s is drained.  dark: stage 0, the dark frame subtracted from every frame
 // as it arrives -- plain and LZMA payloads inside the unpack pass (s drained on return), LJ92 payloads in a pass behind the decoder
 // that may still be in flight on s on return: the caller goes on on s, or synchronises it
+// A change of bit depth on the way (the transcoder, mlvfs_amd_mlv_transcode_bits; k_mlvpack.hip): plain and LZMA
+// payloads leave the load at out_bpp bits, shifted after the dark frame was subtracted -- as 16-bit frames, or (packed) as packed
+// payloads `dstride` bytes apart, ceil(w * h * out_bpp / 16) words each.  LJ92 payloads are not touched by it: their pixels are
+// shifted by the pass that follows the decoder (launch_mlv_pack_shift, launch_mlv_tile_shift).
+struct LoadBits {
+    int out_bpp;
+    bool packed;
+};
 int reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
                       hipStream_t s, const DarkFrameDev *dark = nullptr);
 // the same for frames named one by one (all of one geometry and payload kind); stage_locked: the caller holds reader_stage_mutex
 int reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                     hipStream_t s, bool stage_locked, const DarkFrameDev *dark = nullptr);
+                     hipStream_t s, bool stage_locked, const DarkFrameDev *dark = nullptr, const LoadBits *bits = nullptr);
 // what the transcoder (mlvwriter.cpp) asks of an opened clip: its path and chunk files, where a frame's VIDF block lies, the bytes of
 // its payload as read_frames (lj92: as the LJ92 decoder) takes it, packed payloads of plain and LZMA frames (host only), and the
 // mutex that serialises the reader's streaming calls
@@ -227,6 +235,15 @@ std::mutex &reader_stage_mutex(const void *reader);
 int launch_mlv_tile(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int nframes, hipStream_t stream);
 int launch_mlv_pack(const void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int nframes,
                     hipStream_t stream);
+// the same passes with a change of bit depth inside (d = out_bpp - bpp; > 0: << d, < 0: >> -d), and packed -> packed in one pass
+int launch_mlv_shift(void *d_frames, size_t stride, uint32_t npix, int d, int nframes, hipStream_t stream);
+int launch_mlv_repack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
+                      const DarkFrameDev *dark, hipStream_t stream);
+int launch_mlv_unpack_shift(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp,
+                            int nframes, const DarkFrameDev *dark, hipStream_t stream);
+int launch_mlv_pack_shift(void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
+                          hipStream_t stream);
+int launch_mlv_tile_shift(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int d, int nframes, hipStream_t stream);
 void preload_k_mlvpack();
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);

@@ -17,7 +17,23 @@
 //   k_mlv_tile_generic : any even width and height; one lane = one destination pixel.
 //   k_mlv_pack_x16<14 | 12 | 10> : one lane = 16 pixels = two 128-bit loads and 7 / 6 / 5 coalesced dword stores.
 //   k_mlv_pack_generic : any bpp in 1..16, any length; one lane = one output word (the pixels that touch it: 2 at 14 bits, 16 at 1).
+//
+// A clip rewritten at another bit depth (mlvfs_amd_mlv_transcode_bits, `mlv_dump -b`).  For a frame of bpp bits and a
+// requested out_bpp, d = out_bpp - bpp:
+//     out = px >> -d   (d < 0: truncation, no rounding, no dither)        out = px << d   (d > 0)        out = px   (d = 0)
+// after the dark frame, if any, was subtracted at the source's depth (stage 0, k_dark.hip).  The shift rides inside the pass a route
+// makes anyway -- the kernels above are not touched, a call without conversion launches exactly what it launched before:
+//   k_mlv_repack_x16<IN, OUT>, IN, OUT in {14, 12, 10} : packed stream in, packed stream out; one lane = 16 pixels = IN / 2 coalesced
+//                  dword loads, unpack, the dark plane (optional: two 128-bit loads), shift, OUT / 2 coalesced dword stores.
+//                  3.25 B per pixel at 14 -> 12 where unpack + pack move 7.25.  IN == OUT is for a dark frame alone.
+//   k_mlv_repack_generic : any depths in 1..16, any length, 2-byte alignment; one lane = one output word.
+//   k_mlv_unpack_shift_x16<IN> : k_dark_unpack_x16 with the shift (plain / LZMA source to the encoder); the plane is optional.
+//   k_mlv_pack_shift_x16<OUT>  : k_mlv_pack_x16 with the shift in front of the mask (LJ92 source to plain output).
+//   k_mlv_tile_shift_x<16 | 8>, k_mlv_tile_shift_generic : the tiling with the shift (LJ92 source to LJ92 output).
+//   k_mlv_shift_generic : in place, one pixel per lane -- the extra pass of the shapes the fast forms do not take.
+// Pad bytes between frames are never touched.
 #include "clip.h"
+#include "k_unpack_dev.h"
 
 namespace mlv {
 
@@ -173,6 +189,285 @@ int launch_mlv_pack(const void *d_frames, size_t stride, void *d_packed, size_t 
         const dim3 grid(grid_x(nwords, 16384), nframes);
         hipLaunchKernelGGL(k_mlv_pack_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (uint8_t *)d_packed,
                            packed_stride, npix, nwords, bpp);
+    }
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+// ---- the same passes with a change of bit depth inside ---------------------------------------------------------
+// d > 0: << d, d < 0: >> -d; the result is kept to 16 bits (a decoded value above its depth must not reach the neighbouring pixel)
+__device__ __forceinline__ uint32_t shift_px(uint32_t v, int d) { return (d >= 0 ? v << d : v >> -d) & 0xFFFFu; }
+
+// two pixels in a dword
+__device__ __forceinline__ uint32_t shift_px2(uint32_t two, int d)
+{
+    return d >= 0 ? (two << d) & (((0xFFFFu << d) & 0xFFFFu) * 0x10001u) : (two >> -d) & ((0xFFFFu >> -d) * 0x10001u);
+}
+
+__device__ __forceinline__ uint32_t sub_dark_px(uint32_t px, uint32_t dk, int black_d, int top)
+{
+    const int v = (int)px - (int)dk + black_d;
+    return (uint32_t)min(max(v, 0), top);
+}
+
+// the lane's 16 pixels less the dark plane's (k_dark.hip's rule: clamp(px - dark + black_d, 0, 2^IN - 1))
+__device__ __forceinline__ void dark_x16(uint32_t (&px)[16], const uint4 *__restrict__ dark, size_t g, int black_d, int top)
+{
+    const uint4 da = dark[g * 2], db = dark[g * 2 + 1];
+    const uint32_t dk[8] = { da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w };
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        px[2 * i] = sub_dark_px(px[2 * i], dk[i] & 0xFFFFu, black_d, top);
+        px[2 * i + 1] = sub_dark_px(px[2 * i + 1], dk[i] >> 16, black_d, top);
+    }
+}
+
+// dark: nullptr or the plane, 16-byte aligned; a frame is `groups` runs of 16 pixels
+template <int IN, int OUT>
+__global__ __launch_bounds__(256) void k_mlv_repack_x16(const uint8_t *__restrict__ packed, size_t packed_stride, uint8_t *__restrict__ out,
+                                                        size_t out_stride, const uint4 *__restrict__ dark, uint32_t groups, int black_d)
+{
+    constexpr int NI = IN / 2, NO = OUT / 2, D = OUT - IN;
+    const uint32_t *src = (const uint32_t *)(packed + (size_t)blockIdx.y * packed_stride);
+    uint32_t *dst = (uint32_t *)(out + (size_t)blockIdx.y * out_stride);
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        uint32_t s[NI], px[16], le[NO];
+#pragma unroll
+        for (int i = 0; i < NI; i++) s[i] = stream_word(src[(size_t)g * NI + i]);
+        unpack_x16<IN>(s, px);
+        if (dark) dark_x16(px, dark, g, black_d, (1 << IN) - 1);
+#pragma unroll
+        for (int k = 0; k < 16; k++) {                                                        // IN bits at most: OUT bits at most
+            if constexpr (D >= 0) px[k] <<= D; else px[k] >>= -D;
+        }
+        pack_x16<OUT>(px, le);
+#pragma unroll
+        for (int i = 0; i < NO; i++) dst[(size_t)g * NO + i] = le[i];
+    }
+}
+
+// output word j holds output stream bits [16j, 16j + 16): every pixel that touches it is read from the input stream (its two words,
+// the second one only where the frame has it), subtracted, shifted and masked
+__global__ __launch_bounds__(256) void k_mlv_repack_generic(const uint8_t *__restrict__ packed, size_t packed_stride, uint8_t *__restrict__ out,
+                                                            size_t out_stride, const uint16_t *__restrict__ dark, uint32_t npix, uint32_t in_words,
+                                                            uint32_t out_words, int bpp, int out_bpp, int black_d)
+{
+    const uint16_t *src = (const uint16_t *)(packed + (size_t)blockIdx.y * packed_stride);
+    uint16_t *dst = (uint16_t *)(out + (size_t)blockIdx.y * out_stride);
+    const uint32_t in_mask = (1u << bpp) - 1u, out_mask = (1u << out_bpp) - 1u;
+    const int d = out_bpp - bpp;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < out_words; j += gridDim.x * blockDim.x) {
+        const uint32_t bit0 = j * 16u;
+        const uint32_t first = bit0 / (uint32_t)out_bpp;
+        uint32_t last = (bit0 + 15u) / (uint32_t)out_bpp;
+        if (last > npix - 1) last = npix - 1;
+        uint32_t word = 0;
+        for (uint32_t i = first; i <= last; i++) {
+            const uint32_t bit = i * (uint32_t)bpp, wi = bit >> 4, sh = bit & 15u;
+            const uint32_t two = ((uint32_t)src[wi] << 16) | (wi + 1 < in_words ? (uint32_t)src[wi + 1] : 0u);
+            uint32_t v = (two >> (32 - bpp - (int)sh)) & in_mask;
+            if (dark) v = sub_dark_px(v, dark[i], black_d, (int)in_mask);
+            v = shift_px(v, d) & out_mask;
+            const int pos = 15 - (int)(i * (uint32_t)out_bpp + (uint32_t)out_bpp - 1u - bit0);
+            word |= pos >= 0 ? v << pos : v >> -pos;
+        }
+        dst[j] = (uint16_t)word;
+    }
+}
+
+template <int IN>
+__global__ __launch_bounds__(256) void k_mlv_unpack_shift_x16(const uint8_t *__restrict__ packed, size_t packed_stride, uint8_t *__restrict__ out,
+                                                              size_t out_stride, const uint4 *__restrict__ dark, uint32_t groups, int black_d, int d)
+{
+    constexpr int NW = IN / 2;
+    const uint32_t *src = (const uint32_t *)(packed + (size_t)blockIdx.y * packed_stride);
+    uint4 *dst = (uint4 *)(out + (size_t)blockIdx.y * out_stride);
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        uint32_t s[NW], px[16];
+#pragma unroll
+        for (int i = 0; i < NW; i++) s[i] = stream_word(src[(size_t)g * NW + i]);
+        unpack_x16<IN>(s, px);
+        if (dark) dark_x16(px, dark, g, black_d, (1 << IN) - 1);
+#pragma unroll
+        for (int k = 0; k < 16; k++) px[k] = shift_px(px[k], d);
+        uint4 lo, hi;
+        lo.x = px[0] | (px[1] << 16);   lo.y = px[2] | (px[3] << 16);
+        lo.z = px[4] | (px[5] << 16);   lo.w = px[6] | (px[7] << 16);
+        hi.x = px[8] | (px[9] << 16);   hi.y = px[10] | (px[11] << 16);
+        hi.z = px[12] | (px[13] << 16); hi.w = px[14] | (px[15] << 16);
+        dst[(size_t)g * 2] = lo;
+        dst[(size_t)g * 2 + 1] = hi;
+    }
+}
+
+template <int OUT>
+__global__ __launch_bounds__(256) void k_mlv_pack_shift_x16(const uint8_t *__restrict__ frames, size_t stride, uint8_t *__restrict__ packed,
+                                                            size_t packed_stride, uint32_t groups, int d)
+{
+    constexpr int NW = OUT / 2;
+    const uint4 *src = (const uint4 *)(frames + (size_t)blockIdx.y * stride);
+    uint32_t *dst = (uint32_t *)(packed + (size_t)blockIdx.y * packed_stride);
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        const uint4 a = src[(size_t)g * 2], b = src[(size_t)g * 2 + 1];
+        const uint32_t in[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+        uint32_t px[16], le[NW];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { px[2 * i] = shift_px(in[i] & 0xFFFFu, d); px[2 * i + 1] = shift_px(in[i] >> 16, d); }
+        pack_x16<OUT>(px, le);
+#pragma unroll
+        for (int i = 0; i < NW; i++) dst[(size_t)g * NW + i] = le[i];
+    }
+}
+
+template <int PX>
+__global__ __launch_bounds__(256) void k_mlv_tile_shift_x(const uint8_t *__restrict__ frames, size_t stride, uint8_t *__restrict__ out,
+                                                          size_t out_stride, uint32_t groups, uint32_t groups_per_row, uint32_t w, uint32_t h, int d)
+{
+    const uint4 *src = (const uint4 *)(frames + (size_t)blockIdx.y * stride);
+    uint16_t *dst = (uint16_t *)(out + (size_t)blockIdx.y * out_stride);
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        const uint32_t sy = g / groups_per_row, gx = g - sy * groups_per_row;
+        const uint32_t dy = (sy >> 1) + (sy & 1u) * (h >> 1);
+        uint16_t *row = dst + (size_t)dy * w + (size_t)gx * (PX / 2);
+        if (PX == 16) {
+            const uint4 a = src[(size_t)g * 2], b = src[(size_t)g * 2 + 1];
+            uint4 e, o;
+            e.x = evens(a.x, a.y); e.y = evens(a.z, a.w); e.z = evens(b.x, b.y); e.w = evens(b.z, b.w);
+            o.x = odds(a.x, a.y);  o.y = odds(a.z, a.w);  o.z = odds(b.x, b.y);  o.w = odds(b.z, b.w);
+            e.x = shift_px2(e.x, d); e.y = shift_px2(e.y, d); e.z = shift_px2(e.z, d); e.w = shift_px2(e.w, d);
+            o.x = shift_px2(o.x, d); o.y = shift_px2(o.y, d); o.z = shift_px2(o.z, d); o.w = shift_px2(o.w, d);
+            *(uint4 *)row = e;
+            *(uint4 *)(row + (w >> 1)) = o;
+        } else {
+            const uint4 a = src[g];
+            uint2 e, o;
+            e.x = shift_px2(evens(a.x, a.y), d); e.y = shift_px2(evens(a.z, a.w), d);
+            o.x = shift_px2(odds(a.x, a.y), d);  o.y = shift_px2(odds(a.z, a.w), d);
+            *(uint2 *)row = e;
+            *(uint2 *)(row + (w >> 1)) = o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mlv_tile_shift_generic(const uint8_t *__restrict__ frames, size_t stride, uint8_t *__restrict__ out,
+                                                                size_t out_stride, uint32_t npix, uint32_t w, uint32_t h, int d)
+{
+    const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
+    uint16_t *dst = (uint16_t *)(out + (size_t)blockIdx.y * out_stride);
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < npix; k += gridDim.x * blockDim.x) {
+        const uint32_t y = k / w, x = k - y * w;
+        const uint32_t ty = y < (h >> 1) ? 2 * y : 2 * y - h + 1, tx = x < (w >> 1) ? 2 * x : 2 * x - w + 1;
+        dst[k] = (uint16_t)shift_px(src[(size_t)ty * w + tx], d);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mlv_shift_generic(uint8_t *__restrict__ frames, size_t stride, uint32_t npix, int d)
+{
+    uint16_t *f = (uint16_t *)(frames + (size_t)blockIdx.y * stride);
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < npix; k += gridDim.x * blockDim.x) f[k] = (uint16_t)shift_px(f[k], d);
+}
+
+static bool fast_depth(int bpp) { return bpp == 14 || bpp == 12 || bpp == 10; }
+
+int launch_mlv_shift(void *d_frames, size_t stride, uint32_t npix, int d, int nframes, hipStream_t stream)
+{
+    if (npix == 0 || nframes <= 0 || d == 0) return MLVFS_AMD_OK;
+    hipLaunchKernelGGL(k_mlv_shift_generic, dim3(grid_x(npix, 16384), nframes), dim3(256), 0, stream, (uint8_t *)d_frames, stride, npix, d);
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+// packed payloads of bpp bits -> packed payloads of out_bpp bits, the dark frame (optional) subtracted in between
+int launch_mlv_repack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
+                      const DarkFrameDev *dark, hipStream_t stream)
+{
+    if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
+    if (bpp < 1 || bpp > 16 || out_bpp < 1 || out_bpp > 16) { set_error("unsupported bits_per_pixel %d -> %d", bpp, out_bpp); return MLVFS_AMD_ERR_ARG; }
+    if (npix >= (1u << 27)) { set_error("more than 2^27 pixels"); return MLVFS_AMD_ERR_ARG; }       // bit positions are 32-bit
+    const bool fast = fast_depth(bpp) && fast_depth(out_bpp) && npix % 16 == 0 && ((uintptr_t)d_packed % 4 == 0) && ((uintptr_t)d_out % 4 == 0) &&
+                      (!dark || (dark->top == (1 << bpp) - 1 && (uintptr_t)dark->d_plane % 16 == 0)) &&
+                      (nframes == 1 || (packed_stride % 4 == 0 && out_stride % 4 == 0));
+    if (fast) {
+        using Kern = void (*)(const uint8_t *, size_t, uint8_t *, size_t, const uint4 *, uint32_t, int);
+        static const Kern table[3][3] = {
+            { k_mlv_repack_x16<14, 14>, k_mlv_repack_x16<14, 12>, k_mlv_repack_x16<14, 10> },
+            { k_mlv_repack_x16<12, 14>, k_mlv_repack_x16<12, 12>, k_mlv_repack_x16<12, 10> },
+            { k_mlv_repack_x16<10, 14>, k_mlv_repack_x16<10, 12>, k_mlv_repack_x16<10, 10> },
+        };
+        const uint32_t groups = npix / 16;
+        hipLaunchKernelGGL(table[(14 - bpp) / 2][(14 - out_bpp) / 2], dim3(grid_x(groups, 8192), nframes), dim3(256), 0, stream,
+                           (const uint8_t *)d_packed, packed_stride, (uint8_t *)d_out, out_stride, dark ? (const uint4 *)dark->d_plane : nullptr, groups,
+                           dark ? dark->black : 0);
+    } else {
+        const uint32_t in_words = (uint32_t)(((uint64_t)npix * bpp + 15) / 16), out_words = (uint32_t)(((uint64_t)npix * out_bpp + 15) / 16);
+        hipLaunchKernelGGL(k_mlv_repack_generic, dim3(grid_x(out_words, 16384), nframes), dim3(256), 0, stream, (const uint8_t *)d_packed,
+                           packed_stride, (uint8_t *)d_out, out_stride, dark ? dark->d_plane : nullptr, npix, in_words, out_words, bpp, out_bpp,
+                           dark ? dark->black : 0);
+    }
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+// packed payloads of bpp bits -> 16-bit frames of out_bpp bits, the dark frame (optional) subtracted in between: one pass where
+// k_unpack_x16 would run, else the generic unpack (and subtraction) and one in-place pass more
+int launch_mlv_unpack_shift(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp,
+                            int nframes, const DarkFrameDev *dark, hipStream_t stream)
+{
+    if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
+    if (bpp < 1 || bpp > 16 || out_bpp < 1 || out_bpp > 16) { set_error("unsupported bits_per_pixel %d -> %d", bpp, out_bpp); return MLVFS_AMD_ERR_ARG; }
+    const bool fast = fast_depth(bpp) && npix % 16 == 0 && ((uintptr_t)d_packed % 4 == 0) && ((uintptr_t)d_out % 16 == 0) &&
+                      (!dark || (dark->top == (1 << bpp) - 1 && (uintptr_t)dark->d_plane % 16 == 0)) &&
+                      (nframes == 1 || (packed_stride % 4 == 0 && out_stride % 16 == 0));
+    if (!fast) {
+        if (int rc = dark ? launch_dark_unpack(d_packed, packed_stride, d_out, out_stride, npix, bpp, nframes, *dark, stream)
+                          : launch_unpack(d_packed, packed_stride, d_out, out_stride, 0, npix, bpp, nframes, stream)) return rc;
+        return launch_mlv_shift(d_out, out_stride, npix, out_bpp - bpp, nframes, stream);
+    }
+    const uint32_t groups = npix / 16;
+    auto kern = bpp == 14 ? k_mlv_unpack_shift_x16<14> : (bpp == 12 ? k_mlv_unpack_shift_x16<12> : k_mlv_unpack_shift_x16<10>);
+    hipLaunchKernelGGL(kern, dim3(grid_x(groups, 8192), nframes), dim3(256), 0, stream, (const uint8_t *)d_packed, packed_stride, (uint8_t *)d_out,
+                       out_stride, dark ? (const uint4 *)dark->d_plane : nullptr, groups, dark ? dark->black : 0, out_bpp - bpp);
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+// 16-bit frames of bpp bits -> packed payloads of out_bpp bits; the shapes k_mlv_pack_x16 does not take: shifted in place first
+int launch_mlv_pack_shift(void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
+                          hipStream_t stream)
+{
+    if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
+    if (bpp < 1 || bpp > 16 || out_bpp < 1 || out_bpp > 16) { set_error("unsupported bits_per_pixel %d -> %d", bpp, out_bpp); return MLVFS_AMD_ERR_ARG; }
+    if (npix >= (1u << 27)) { set_error("more than 2^27 pixels"); return MLVFS_AMD_ERR_ARG; }
+    const bool fast = fast_depth(out_bpp) && npix % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && ((uintptr_t)d_packed % 4 == 0) &&
+                      (nframes == 1 || (stride % 16 == 0 && packed_stride % 4 == 0));
+    if (!fast) {
+        if (int rc = launch_mlv_shift(d_frames, stride, npix, out_bpp - bpp, nframes, stream)) return rc;
+        return launch_mlv_pack(d_frames, stride, d_packed, packed_stride, npix, out_bpp, nframes, stream);
+    }
+    const uint32_t groups = npix / 16;
+    auto kern = out_bpp == 14 ? k_mlv_pack_shift_x16<14> : (out_bpp == 12 ? k_mlv_pack_shift_x16<12> : k_mlv_pack_shift_x16<10>);
+    hipLaunchKernelGGL(kern, dim3(grid_x(groups, 8192), nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (uint8_t *)d_packed,
+                       packed_stride, groups, out_bpp - bpp);
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+// launch_mlv_tile with every pixel shifted by d bits (d > 0: left)
+int launch_mlv_tile_shift(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int d, int nframes, hipStream_t stream)
+{
+    if (nframes <= 0) return MLVFS_AMD_OK;
+    if (w <= 0 || h <= 0 || (w & 1) || (h & 1)) { set_error("quadrant tiling takes even sizes, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    if (d < -15 || d > 15) { set_error("a shift of %d bits", d); return MLVFS_AMD_ERR_ARG; }
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;
+    const bool aligned = ((uintptr_t)d_frames % 16 == 0) && ((uintptr_t)d_out % 16 == 0) && (nframes == 1 || (stride % 16 == 0 && out_stride % 16 == 0));
+    const int px = !aligned ? 0 : (w % 16 == 0 ? 16 : (w % 8 == 0 ? 8 : 0));
+    if (px) {
+        const uint32_t gpr = (uint32_t)w / px, groups = gpr * (uint32_t)h;
+        hipLaunchKernelGGL(px == 16 ? k_mlv_tile_shift_x<16> : k_mlv_tile_shift_x<8>, dim3(grid_x(groups, 8192), nframes), dim3(256), 0, stream,
+                           (const uint8_t *)d_frames, stride, (uint8_t *)d_out, out_stride, groups, gpr, (uint32_t)w, (uint32_t)h, d);
+    } else {
+        hipLaunchKernelGGL(k_mlv_tile_shift_generic, dim3(grid_x(npix, 16384), nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                           (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)h, d);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

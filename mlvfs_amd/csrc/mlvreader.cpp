@@ -417,8 +417,10 @@ int read_frames(const Reader &r, int first, int count, uint8_t *dst, size_t stri
 // (LZMA decoded there), then uploaded and unpacked (k_unpack) or, LJ92 clips, decoded on the GPU.  Returns with the stream drained
 // of everything that reads the staging: it is the next caller's again.  dark: the dark frame to subtract (k_dark.hip), in the unpack
 // pass or, LJ92 clips, in a pass behind the decoder that is still in flight on `s` on return.  stage_locked: the caller holds the reader's staging mutex already.
+// bits (the transcoder at another bit depth, clip.h: LoadBits): plain and LZMA payloads leave at bits->out_bpp bits, as 16-bit frames
+// or as packed payloads, in the one pass that reads them (k_mlvpack.hip); LJ92 payloads are left to the caller's next pass.
 int mlv::reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                          hipStream_t s, bool stage_locked, const DarkFrameDev *dark)
+                          hipStream_t s, bool stage_locked, const DarkFrameDev *dark, const LoadBits *bits)
 {
     const Reader &r = *(const Reader *)reader;
     if (count <= 0) return MLVFS_AMD_OK;
@@ -450,8 +452,11 @@ int mlv::reader_load_list(const void *reader, const int *list, int count, int w,
     if (rc) return rc;
     const mlvfs_amd_geom_t geom{ w, h, bpp, 0, 0, 0, 0 };
     MLV_HIP(hipMemcpyAsync(r.d_di_packed, r.stage[0], stride * count, hipMemcpyHostToDevice, s));
-    rc = dark ? launch_dark_unpack(r.d_di_packed, stride, d_frames, dstride, (uint32_t)w * (uint32_t)h, bpp, count, *dark, s)
-              : mlvfs_amd_unpack_dev(&geom, r.d_di_packed, stride, d_frames, dstride, count, s);
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;
+    if (bits && bits->packed) rc = launch_mlv_repack(r.d_di_packed, stride, d_frames, dstride, npix, bpp, bits->out_bpp, count, dark, s);
+    else if (bits) rc = launch_mlv_unpack_shift(r.d_di_packed, stride, d_frames, dstride, npix, bpp, bits->out_bpp, count, dark, s);
+    else rc = dark ? launch_dark_unpack(r.d_di_packed, stride, d_frames, dstride, npix, bpp, count, *dark, s)
+                   : mlvfs_amd_unpack_dev(&geom, r.d_di_packed, stride, d_frames, dstride, count, s);
     if (rc) return rc;
     MLV_HIP(hipStreamSynchronize(s));
     return MLVFS_AMD_OK;

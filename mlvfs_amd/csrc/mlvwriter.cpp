@@ -19,6 +19,14 @@
 //   plain from plain/LZMA  host only: the packed bytes read_frames yields are written as they are (no HIP device needed)
 // With a dark frame (mlvfs_amd_mlv_transcode_dark) reader_load_list subtracts it from every frame (stage 0: k_dark.hip), and a plain or
 // LZMA source with plain output goes upload -> unpack + subtract -> k_mlv_pack, the route of an LJ92 source.
+// At another bit depth (mlvfs_amd_mlv_transcode_bits, `mlv_dump -b`) every frame whose depth is not out_bpp is shifted
+// after the dark frame, inside a pass its route makes anyway (k_mlvpack.hip), and every RAWI block of another depth is rewritten
+// (mlvfs_amd_rawi_set_bits):
+//   plain / LZMA -> plain   upload -> k_mlv_repack (unpack, subtract, shift, pack in one pass) -> file
+//   plain / LZMA -> LJ92    upload -> k_mlv_unpack_shift -> k_mlv_tile -> the encoder at out_bpp
+//   LJ92 -> plain           GPU decode -> k_dark_sub if a dark frame is set -> k_mlv_pack_shift -> file
+//   LJ92 -> LJ92            GPU decode -> k_dark_sub if set -> k_mlv_tile_shift -> the encoder at out_bpp
+// Frames already at out_bpp, and every frame when out_bpp is 0, take the routes above unchanged.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -52,6 +60,7 @@ struct Block {
 
 struct Frame {
     int w, h, bpp, kind;
+    int obpp;                  // bits per pixel of the payload written: bpp, or the call's out_bpp
 };
 
 bool is(const uint8_t t[4], const char *tag) { return !memcmp(t, tag, 4); }
@@ -161,6 +170,7 @@ struct Job {
     const void *reader;
     const mlvfs_amd_dark_t *dark = nullptr;
     int payload, batch, io_threads;
+    int out_bpp = 0;                                                   // 0: every frame keeps its depth
     std::vector<Frame> frames;
     std::vector<std::vector<Block>> chunks;
     OutFiles out;
@@ -174,9 +184,9 @@ struct Job {
     long long frames_written = 0, bytes_in = 0, bytes_out = 0;
 };
 
-size_t plain_bytes(const Frame &f) { return (size_t)(((uint64_t)f.w * f.h * f.bpp + 15) / 16) * 2; }
+size_t plain_bytes(const Frame &f) { return (size_t)(((uint64_t)f.w * f.h * f.obpp + 15) / 16) * 2; }             // of the payload written
 
-bool on_host(const Job &j, const Frame &f) { return j.payload == MLVFS_AMD_MLV_PLAIN && f.kind != SRC_LJ92 && !j.dark; }
+bool on_host(const Job &j, const Frame &f) { return j.payload == MLVFS_AMD_MLV_PLAIN && f.kind != SRC_LJ92 && !j.dark && f.obpp == f.bpp; }
 
 bool same_batch(const Frame &a, const Frame &b) { return a.w == b.w && a.h == b.h && a.bpp == b.bpp && a.kind == b.kind; }
 
@@ -221,26 +231,35 @@ int batch_device(Job &j, const std::vector<int> &list)
     DarkFrameDev dark{};
     int rc = j.dark ? darkframe_on_device(j.dark, j.ctx, f.w, f.h, f.bpp, &dark) : MLVFS_AMD_OK;
     if (rc) return rc;
-    rc = reader_load_list(j.reader, list.data(), n, f.w, f.h, f.bpp, d.d_frames, dstride, j.io_threads, s, true, j.dark ? &dark : nullptr);
+    const bool conv = f.obpp != f.bpp, plain = j.payload == MLVFS_AMD_MLV_PLAIN;
+    const size_t pstride = up(plain_bytes(f), 16);                     // (<= dstride: d_aux has the room)
+    // at another depth a plain or LZMA source is shifted by the pass that reads it; to plain output that pass packs as well
+    const LoadBits bits{ f.obpp, plain };
+    const bool repacked = conv && plain && f.kind != SRC_LJ92;
+    rc = reader_load_list(j.reader, list.data(), n, f.w, f.h, f.bpp, repacked ? d.d_aux : d.d_frames, repacked ? pstride : dstride, j.io_threads, s,
+                          true, j.dark ? &dark : nullptr, conv && f.kind != SRC_LJ92 ? &bits : nullptr);
     if (rc) return rc;
-    if (j.payload == MLVFS_AMD_MLV_PLAIN) {
-        const size_t bytes = plain_bytes(f), pstride = up(bytes, 16);
+    const int shift = f.kind == SRC_LJ92 ? f.obpp - f.bpp : 0;         // what is left to do here
+    if (plain) {
+        const size_t bytes = plain_bytes(f);
         if ((rc = d.stage(pstride * n))) return rc;
-        if ((rc = launch_mlv_pack(d.d_frames, dstride, d.d_aux, pstride, npix, f.bpp, n, s))) return rc;
+        if (!repacked && (rc = shift ? launch_mlv_pack_shift(d.d_frames, dstride, d.d_aux, pstride, npix, f.bpp, f.obpp, n, s)
+                                     : launch_mlv_pack(d.d_frames, dstride, d.d_aux, pstride, npix, f.bpp, n, s))) return rc;
         MLV_HIP(hipMemcpyAsync(d.h_stage, d.d_aux, pstride * n, hipMemcpyDeviceToHost, s));
         MLV_HIP(hipStreamSynchronize(s));
         for (int k = 0; k < n; k++) j.ready[list[k]] = { d.h_stage + (size_t)k * pstride, bytes };
         return MLVFS_AMD_OK;
     }
     if ((rc = DevRoom::grow(&d.d_fixed, &d.fixed_bytes, lje_fixed_bytes(npix, n)))) return rc;
-    if ((rc = launch_mlv_tile(d.d_frames, dstride, d.d_aux, dstride, f.w, f.h, n, s))) return rc;
+    if ((rc = shift ? launch_mlv_tile_shift(d.d_frames, dstride, d.d_aux, dstride, f.w, f.h, shift, n, s)
+                    : launch_mlv_tile(d.d_frames, dstride, d.d_aux, dstride, f.w, f.h, n, s))) return rc;
     std::vector<const uint16_t *> src(n);
     for (int k = 0; k < n; k++) src[k] = (const uint16_t *)((const uint8_t *)d.d_aux + (size_t)k * dstride);
     std::vector<LjeResult> res(n);
     uint8_t *d_streams = nullptr;
     size_t sstride = 0;
     d.n = n;
-    if ((rc = lje_encode_batch(src.data(), n, f.w, f.h, f.bpp, nullptr, 0, d.d_fixed, d, &d_streams, &sstride, res.data(), s))) return rc;
+    if ((rc = lje_encode_batch(src.data(), n, f.w, f.h, f.obpp, nullptr, 0, d.d_fixed, d, &d_streams, &sstride, res.data(), s))) return rc;
     size_t longest = 0;
     for (int k = 0; k < n; k++) {
         const LjeResult &r = res[k];
@@ -268,13 +287,13 @@ int batch_device(Job &j, const std::vector<int> &list)
     return MLVFS_AMD_OK;
 }
 
-// a block as it is; MLVI: with the video class of the output
-bool copy_block(Job &j, int fd, const Block &b, std::vector<uint8_t> &buf)
+// a block as it is; MLVI: with the video class of the output; RAWI of another depth than the call's out_bpp: at out_bpp
+int copy_block(Job &j, int fd, const Block &b, std::vector<uint8_t> &buf)
 {
     buf.resize(1 << 20);
     for (uint64_t done = 0; done < b.size;) {
         const size_t n = (size_t)std::min<uint64_t>(buf.size(), b.size - done);
-        if (!read_at(fd, buf.data(), n, b.off + done)) { set_error("mlv transcode: short read in the %.4s block at 0x%llx", (const char *)b.type, (unsigned long long)b.off); return false; }
+        if (!read_at(fd, buf.data(), n, b.off + done)) { set_error("mlv transcode: short read in the %.4s block at 0x%llx", (const char *)b.type, (unsigned long long)b.off); return MLVFS_AMD_ERR_IO; }
         if (done == 0 && is(b.type, "MLVI") && n >= VIDEO_CLASS_AT + 2) {
             uint16_t vc;
             memcpy(&vc, buf.data() + VIDEO_CLASS_AT, 2);
@@ -282,10 +301,21 @@ bool copy_block(Job &j, int fd, const Block &b, std::vector<uint8_t> &buf)
             if (j.payload == MLVFS_AMD_MLV_LJ92) vc |= CLASS_LJ92;
             memcpy(buf.data() + VIDEO_CLASS_AT, &vc, 2);
         }
-        if (!write_all(j.out.fd, buf.data(), n)) { set_error("mlv transcode: write failed: %s", strerror(errno)); return false; }
+        if (done == 0 && j.out_bpp && is(b.type, "RAWI") && n >= sizeof(mlv_rawi_hdr_t)) {
+            mlv_rawi_hdr_t rawi;
+            memcpy(&rawi, buf.data(), sizeof rawi);
+            if (rawi.raw_info.bits_per_pixel != j.out_bpp) {
+                if (mlvfs_amd_rawi_set_bits(&rawi, j.out_bpp) != MLVFS_AMD_OK) {
+                    set_error("mlv transcode: the RAWI block at 0x%llx says %d bits per pixel", (unsigned long long)b.off, (int)rawi.raw_info.bits_per_pixel);
+                    return MLVFS_AMD_ERR_ARG;
+                }
+                memcpy(buf.data(), &rawi, sizeof rawi);
+            }
+        }
+        if (!write_all(j.out.fd, buf.data(), n)) { set_error("mlv transcode: write failed: %s", strerror(errno)); return MLVFS_AMD_ERR_IO; }
         done += n;
     }
-    return true;
+    return MLVFS_AMD_OK;
 }
 
 int write_chunk(Job &j, int c, const std::string &name)
@@ -297,7 +327,7 @@ int write_chunk(Job &j, int c, const std::string &name)
     for (size_t i = 0; i < blocks.size(); i++) {
         const Block &b = blocks[i];
         if (!is(b.type, "VIDF")) {
-            if (!copy_block(j, fd, b, buf)) return MLVFS_AMD_ERR_IO;
+            if (int rc = copy_block(j, fd, b, buf)) return rc;
             continue;
         }
         if (!j.ready.count(b.frame)) {
@@ -377,12 +407,13 @@ bool list_blocks(Job &j, int nchunks, const std::map<std::pair<int, uint64_t>, i
     return ok;
 }
 
-int transcode(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark, int batch_frames, int io_threads,
+int transcode(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark, int batch_frames, int io_threads,
               long long stats[4])
 {
     if (!reader || !out_path || !stats) { set_error("mlv transcode: null argument"); return MLVFS_AMD_ERR_ARG; }
     for (int i = 0; i < 4; i++) stats[i] = 0;
     if (payload != MLVFS_AMD_MLV_PLAIN && payload != MLVFS_AMD_MLV_LJ92) { set_error("mlv transcode: payload kind %d", payload); return MLVFS_AMD_ERR_ARG; }
+    if (out_bpp != 0 && (out_bpp < 8 || out_bpp > 16)) { set_error("mlv transcode: %d bits per pixel: 8 to 16, or 0 to keep the clip's", out_bpp); return MLVFS_AMD_ERR_ARG; }
     const std::string out = out_path;
     if (out.size() < 5 || (out.compare(out.size() - 4, 4, ".MLV") && out.compare(out.size() - 4, 4, ".mlv"))) {
         set_error("mlv transcode: the output path must end in .MLV");
@@ -393,6 +424,7 @@ int transcode(const void *reader, const char *out_path, int payload, const mlvfs
     j.reader = reader;
     j.payload = payload;
     j.dark = dark;
+    j.out_bpp = out_bpp;
     j.batch = batch_frames <= 0 ? 8 : batch_frames;
     j.io_threads = io_threads;
     const int nchunks = mlvfs_amd_mlv_chunk_count(reader), nframes = mlvfs_amd_mlv_frame_count(reader);
@@ -425,6 +457,7 @@ int transcode(const void *reader, const char *out_path, int payload, const mlvfs
         f.h = fh.rawi_hdr.yRes;
         f.bpp = fh.rawi_hdr.raw_info.bits_per_pixel;
         f.kind = payload_kind(vc);
+        f.obpp = out_bpp ? out_bpp : f.bpp;
         if (f.w <= 0 || f.h <= 0 || f.bpp < 1 || f.bpp > 16 || (uint64_t)f.w * f.h >= (1u << 27)) { set_error("mlv transcode: frame %d: %dx%d at %d bits is not supported", k, f.w, f.h, f.bpp); return MLVFS_AMD_ERR_ARG; }
         if (payload == MLVFS_AMD_MLV_LJ92 && ((f.w | f.h) & 1)) {
             set_error("mlv transcode: frame %d: the quadrant tiling of an LJ92 payload takes even sizes, not %dx%d", k, f.w, f.h);
@@ -459,15 +492,67 @@ extern "C" {
 
 int mlvfs_amd_mlv_transcode(const void *reader, const char *out_path, int payload, int batch_frames, int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, nullptr, batch_frames, io_threads, stats); }
+    try { return transcode(reader, out_path, payload, 0, nullptr, batch_frames, io_threads, stats); }
     catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }    // (allocations sized from the file)
 }
 
 int mlvfs_amd_mlv_transcode_dark(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark, int batch_frames,
                                  int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, dark, batch_frames, io_threads, stats); }
+    try { return transcode(reader, out_path, payload, 0, dark, batch_frames, io_threads, stats); }
     catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
+}
+
+int mlvfs_amd_mlv_transcode_bits(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark, int batch_frames,
+                                 int io_threads, long long stats[4])
+{
+    try { return transcode(reader, out_path, payload, out_bpp, dark, batch_frames, io_threads, stats); }
+    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
+}
+
+int mlvfs_amd_rawi_set_bits(mlv_rawi_hdr_t *rawi, int out_bpp)
+{
+    if (!rawi) { set_error("rawi_set_bits: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (out_bpp < 8 || out_bpp > 16) { set_error("rawi_set_bits: %d bits per pixel: 8 to 16", out_bpp); return MLVFS_AMD_ERR_ARG; }
+    struct raw_info ri;                                                // (the block is packed: its fields are copied out and back)
+    memcpy(&ri, &rawi->raw_info, sizeof ri);
+    if (ri.bits_per_pixel < 1 || ri.bits_per_pixel > 16) { set_error("rawi_set_bits: the block says %d bits per pixel", ri.bits_per_pixel); return MLVFS_AMD_ERR_ARG; }
+    const int d = out_bpp - ri.bits_per_pixel;
+    auto shifted = [d](int32_t v) { return d >= 0 ? (int32_t)((uint32_t)v << d) : v >> -d; };
+    ri.black_level = shifted(ri.black_level);
+    ri.white_level = shifted(ri.white_level);
+    ri.bits_per_pixel = out_bpp;
+    ri.pitch = (int32_t)((int64_t)ri.width * out_bpp / 8);
+    ri.frame_size = (int32_t)((uint64_t)rawi->xRes * rawi->yRes * (uint64_t)out_bpp / 8);
+    memcpy(&rawi->raw_info, &ri, sizeof ri);
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_repack_dev(const mlvfs_amd_geom_t *geom, int out_bpp, const mlvfs_amd_dark_t *dark, const void *d_packed, size_t packed_stride,
+                         void *d_out, size_t out_stride, int nframes, void *stream)
+{
+    if (!geom || !d_packed || !d_out) { set_error("repack: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("repack: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    if (geom->width <= 0 || geom->height <= 0 || (uint64_t)geom->width * geom->height >= (1u << 27)) { set_error("repack: %dx%d not supported", geom->width, geom->height); return MLVFS_AMD_ERR_ARG; }
+    if (geom->bpp < 1 || geom->bpp > 16) { set_error("repack: unsupported bits_per_pixel %d", geom->bpp); return MLVFS_AMD_ERR_ARG; }
+    if (out_bpp < 8 || out_bpp > 16) { set_error("repack: %d bits per pixel: 8 to 16", out_bpp); return MLVFS_AMD_ERR_ARG; }
+    if (dark && !darkframe_fits(dark, geom->width, geom->height, geom->bpp)) {
+        set_error("repack: %dx%d at %d bits is not the dark frame's geometry", geom->width, geom->height, geom->bpp);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    const uint32_t npix = (uint32_t)geom->width * (uint32_t)geom->height;
+    const size_t in = (size_t)(((uint64_t)npix * geom->bpp + 15) / 16) * 2, packed = (size_t)(((uint64_t)npix * out_bpp + 15) / 16) * 2;
+    if (((uintptr_t)d_packed & 1) || ((uintptr_t)d_out & 1) || (nframes > 1 && (packed_stride < in || out_stride < packed || ((packed_stride | out_stride) & 1)))) {
+        set_error("repack: strides %zu / %zu too small or odd", packed_stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (d_packed == d_out) { set_error("repack: not in place"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    DarkFrameDev dd{};
+    if (dark) if (int rc = darkframe_on_device(dark, c, geom->width, geom->height, geom->bpp, &dd)) return rc;
+    return launch_mlv_repack(d_packed, packed_stride, d_out, out_stride, npix, geom->bpp, out_bpp, nframes, dark ? &dd : nullptr, pick_stream(stream, c));
 }
 
 int mlvfs_amd_lj92_tile_dev(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int width, int height, int nframes, void *stream)

@@ -63,6 +63,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_lj92_tile_dev", "mlvfs_amd_pack_dev", "mlvfs_amd_mlv_transcode",
     "mlvfs_amd_dark_create", "mlvfs_amd_dark_from_clip", "mlvfs_amd_dark_info", "mlvfs_amd_dark_plane", "mlvfs_amd_dark_destroy",
     "mlvfs_amd_dark_subtract_dev", "mlvfs_amd_mount_set_dark", "mlvfs_amd_mlv_transcode_dark",
+    "mlvfs_amd_rawi_set_bits", "mlvfs_amd_repack_dev", "mlvfs_amd_mlv_transcode_bits",
 ]
 
 
@@ -236,6 +237,9 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_dark_subtract_dev", i, [vp, gp, vp, sz, i, vp])
     sig("mlvfs_amd_mount_set_dark", i, [vp, vp])
     sig("mlvfs_amd_mlv_transcode_dark", i, [vp, C.c_char_p, i, vp, i, i, C.POINTER(C.c_longlong)])
+    sig("mlvfs_amd_rawi_set_bits", i, [vp, i])
+    sig("mlvfs_amd_repack_dev", i, [gp, i, vp, vp, sz, vp, sz, i, vp])
+    sig("mlvfs_amd_mlv_transcode_bits", i, [vp, C.c_char_p, i, i, vp, i, i, C.POINTER(C.c_longlong)])
     _lib = L
     return L
 

@@ -156,3 +156,27 @@ def pack_frames(frames, bpp: int = 14, out=None, torch_stream=None):
     lib.check(L.mlvfs_amd_pack_dev(C.byref(geom), C.c_void_p(frames.data_ptr()), frames.stride(0) * 2, C.c_void_p(out.data_ptr()),
                                    out.stride(0) * 2, n, st), "pack_dev")
     return out
+
+
+def repack_frames(packed, w: int, h: int, bpp: int, out_bpp: int, dark=None, out=None, torch_stream=None):
+    """mlvfs_amd_repack_dev: (n, ceil(w * h * bpp / 16)) 16-bit words of packed payload per frame on the GPU (or host arrays, which
+    are uploaded) -> (n, ceil(w * h * out_bpp / 16)) words at out_bpp bits, every pixel shifted (>> when narrowing, no rounding) after
+    `dark` (a mlvfs_amd.dark.Dark of the input's geometry, optional) was subtracted: unpack, subtract, shift and pack in one pass."""
+    import torch
+    L = lib.load()
+    if not isinstance(packed, torch.Tensor):
+        packed = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(p, np.uint16) for p in packed])).view(np.int16)).cuda()
+    words_in, words = (w * h * bpp + 15) // 16, (w * h * out_bpp + 15) // 16
+    if packed.dim() != 2 or packed.element_size() != 2 or not packed.is_cuda or packed.shape[1] != words_in:
+        raise ValueError(f"packed must be an (n, {words_in}) tensor of 16-bit words on the GPU")
+    n = packed.shape[0]
+    if n and packed.stride(1) != 1:
+        raise ValueError("each payload must be contiguous")
+    if out is None:
+        out = torch.empty((n, words), dtype=torch.int16, device=packed.device)
+    _check_out(out, (n, words), packed)
+    geom = lib.Geom(w, h, bpp, 0, 0, 0, 0)
+    st = C.c_void_p(torch_stream.cuda_stream) if torch_stream is not None else None
+    lib.check(L.mlvfs_amd_repack_dev(C.byref(geom), out_bpp, None if dark is None else dark.h, C.c_void_p(packed.data_ptr()), packed.stride(0) * 2,
+                                     C.c_void_p(out.data_ptr()), out.stride(0) * 2, n, st), "repack_dev")
+    return out

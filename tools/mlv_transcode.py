@@ -1,12 +1,13 @@
 """Rewrite a clip with lossless-JPEG payloads (what `mlv_dump -c` writes) or plain packed ones (--plain, `mlv_dump -d`) on the GPU:
 mlvfs_amd_mlv_transcode (csrc/mlvwriter.cpp).
 
-    python tools/mlv_transcode.py SRC.MLV DST.MLV [--plain] [--batch N] [--io-threads N] [--dark DARK.MLV [--dark-frames A:B]]
+    python tools/mlv_transcode.py SRC.MLV DST.MLV [--plain] [--bits N] [--batch N] [--io-threads N] [--dark DARK.MLV [--dark-frames A:B]]
 
 Source chunks SRC.M00 ... become DST.M00 ...; blocks keep the source's file order, NULL and XREF blocks are dropped, nothing is
 overwritten and no .IDX is written.  Plain output of a plain or LZMA clip needs no GPU.  --dark: the clip DARK.MLV (its frames A .. B - 1,
 default all) is averaged into a dark frame first, which is then subtracted from every frame (mlvfs_amd_dark_from_clip,
-mlvfs_amd_mlv_transcode_dark; what `mlv_dump -a` and `-s` do)."""
+mlvfs_amd_mlv_transcode_dark; what `mlv_dump -a` and `-s` do).  --bits N: the clip at N bits per pixel, 8..16 (what `mlv_dump -b` does:
+pixels and levels shifted without rounding, after the dark frame; RAWI rewritten; mlvfs_amd_mlv_transcode_bits)."""
 import argparse
 import os
 import sys
@@ -23,6 +24,7 @@ def main() -> int:
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--plain", action="store_true", help="plain packed payloads instead of LJ92")
+    ap.add_argument("--bits", type=int, default=0, metavar="N", help="bits per pixel of the output, 8..16 (default: the clip's)")
     ap.add_argument("--batch", type=int, default=0, help="frames per GPU batch (default 8)")
     ap.add_argument("--io-threads", type=int, default=0)
     ap.add_argument("--dark", metavar="PATH", help="a clip of dark frames: averaged, then subtracted from every frame")
@@ -30,6 +32,8 @@ def main() -> int:
     a = ap.parse_args()
     if a.dark_frames and not a.dark:
         ap.error("--dark-frames needs --dark")
+    if a.bits and not 8 <= a.bits <= 16:
+        ap.error("--bits takes 8 to 16")
     dark = None
     if a.dark:
         with mlvfile.MlvReader(a.dark) as dr:
@@ -41,7 +45,7 @@ def main() -> int:
             print(f"dark frame: the mean of {count} frame(s) of {a.dark} in {time.perf_counter() - t0:.3f} s, pedestal {dark.info()['black']}")
     with mlvfile.MlvReader(a.src) as r:
         t0 = time.perf_counter()
-        s = r.transcode(a.dst, lj92=not a.plain, batch=a.batch, io_threads=a.io_threads, dark=dark)
+        s = r.transcode(a.dst, lj92=not a.plain, batch=a.batch, io_threads=a.io_threads, dark=dark, bits=a.bits or None)
         dt = time.perf_counter() - t0
     if dark is not None:
         dark.close()
