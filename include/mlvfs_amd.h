@@ -242,6 +242,12 @@ int mlvfs_amd_lj92_info(const void *stream, size_t size, int dims[4]);
 int mlvfs_amd_lj92_decode_dev(const void *const *streams, const size_t *sizes, int nframes, int xres, int yres,
                               void *d_out, size_t out_stride, void *stream);
 
+/* Test hook, host only: the LDS of the decoder's row kernel (csrc/lj92.h: lj_row_plan, the one rule its launcher and the kernel
+ * share) for a row of w values in a launch whose widest frame has max_w, 1 <= w <= max_w <= 65535.  out[4] = {1 if the row is staged
+ * in LDS (0: worked on in place in global memory), byte offset of the staged row behind the carries, byte offset up to which a staged
+ * row reaches, LDS bytes of the launch}.  0, or MLVFS_AMD_ERR_ARG.                                                              */
+int mlvfs_amd_test_lj92_row_plan(int w, int max_w, long long out[4]);
+
 /* The reference decoder's own three calls (lj92.h:40-58), what get_image_data makes of an LJ92 frame (main.c:626-647: lj92_open,
  * lj92_decode into a temporary buffer, then its own untiling loop): with them `lj92.o` can leave MLVFS's link too and the decode
  * runs on the GPU.  Values in the decoder's own order, width x height of the JPEG.  Only what MLVFS passes is supported:

@@ -520,19 +520,11 @@ __global__ __launch_bounds__(256) void k_lj_decode(const LjFrame *frames)
 }
 
 // ---------------------------------------------------------------- prediction
-constexpr int ROW_LDS = 8192;
 struct RowView {
     int *p;
     bool padded;
     __device__ __forceinline__ int &operator[](int i) const { return p[padded ? i + (i >> 5) : i]; }
 };
-
-// LDS of k_lj_rows for rows of up to max_w values: carries (one per block of 32 columns, + 2), the staged row when it fits
-static size_t row_lds_bytes(int max_w)
-{
-    const size_t carries = (size_t)((max_w + 31) / 32 + 2) * sizeof(long long);
-    return carries + (max_w <= ROW_LDS ? (size_t)(max_w + max_w / 32 + 2) * sizeof(int) : 0);
-}
 
 // one workgroup per row.  HALVING rows (predictor 6, r >= 1): e[c] = (e[c-1] >> 1) + d[c] in blocks of 32 columns.
 // SCAN rows (row 0 always, every row of predictor 1): inclusive prefix sum; row 0 also carries the base 2^(bits-1).
@@ -548,15 +540,18 @@ __global__ __launch_bounds__(256) void k_lj_rows(const LjFrame *frames, int max_
     if (!scan_row && f.pred != 6) return;
     int *grow = f.diff + (size_t)r * f.W;
     const int W = f.W;
-    // Dynamic LDS, sized by the launcher from the widest frame of the batch (row_lds_bytes): the carries of the row's blocks of 32
-    // columns, then the staged row.  (Sized statically for the widest possible row it was 50 KiB -- three rows in flight per CU in a
-    // kernel that is all latency: a row's load, 112 dependent carry steps, its store.)
+    // Dynamic LDS, sized by the launcher from the widest frame of the batch (lj_row_plan, lj92.h -- the launcher's rule and this
+    // kernel's are that one function): the carries of the row's blocks of 32 columns, then the staged row.  (Sized statically for the
+    // widest possible row it was 50 KiB -- three rows in flight per CU in a kernel that is all latency: a row's load, 112 dependent
+    // carry steps, its store.)
     extern __shared__ long long row_lds[];
     long long *const carry = row_lds;                   // (W + 31) / 32 + 1 entries
-    // rows up to ROW_LDS values are staged in LDS (coalesced in, coalesced out; one spare word per 32 keeps the threads,
-    // which each work on 32 consecutive values, in different banks); longer rows are worked on in place
-    int *const stage = (int *)(row_lds + ((max_w + 31) / 32 + 2));
-    const bool staged = W <= ROW_LDS;
+    // rows up to LJ_ROW_LDS values are staged in LDS (coalesced in, coalesced out; one spare word per 32 keeps the threads,
+    // which each work on 32 consecutive values, in different banks), whatever the other frames of the batch are; longer rows are
+    // worked on in place
+    const LjRowPlan plan = lj_row_plan(W, max_w);
+    int *const stage = (int *)((char *)row_lds + plan.stage_off);
+    const bool staged = plan.staged;
     if (staged) {
         for (int i = threadIdx.x; i < W; i += blockDim.x) stage[i + (i >> 5)] = grow[i];
         __syncthreads();
@@ -779,7 +774,7 @@ int lj92_launch(const LjFrame *d_frames, int nframes, uint32_t max_raw, uint32_t
     hipLaunchKernelGGL(k_lj_group_starts, dim3(max_ngrp, nframes), dim3(256), 0, s, d_frames);
     hipLaunchKernelGGL(k_lj_decode, dim3(max_nwg, nframes), dim3(256), 0, s, d_frames);
     if (preds & (1u << 5)) hipLaunchKernelGGL(k_lj_vhalve, dim3((max_w + 255) / 256, nframes), dim3(256), 0, s, d_frames);
-    hipLaunchKernelGGL(k_lj_rows, dim3(max_h, nframes), dim3(256), row_lds_bytes(max_w), s, d_frames, max_w);
+    hipLaunchKernelGGL(k_lj_rows, dim3(max_h, nframes), dim3(256), lj_row_plan(max_w, max_w).lds_bytes, s, d_frames, max_w);
     if (preds & (1u << 3)) hipLaunchKernelGGL(k_lj_diagonals, dim3((max_w + max_h + 255) / 256, nframes), dim3(256), 0, s, d_frames);
     if (preds & (1u << 7)) hipLaunchKernelGGL(k_lj_wavefront, dim3(nframes), dim3(1024), 0, s, d_frames);
     hipLaunchKernelGGL(k_lj_column_sums, dim3((max_w + 255) / 256 * COL_SEGS, nframes), dim3(256), 0, s, d_frames);

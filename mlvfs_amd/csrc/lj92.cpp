@@ -176,6 +176,16 @@ extern "C" int mlvfs_amd_lj92_info(const void *stream, size_t size, int dims[4])
     return MLVFS_AMD_OK;
 }
 
+// Test hook, host only: k_lj_rows' LDS for a row of w values in a launch whose widest frame has max_w (lj_row_plan, lj92.h -- the
+// function the launcher sizes the launch with and the kernel places the row with).
+extern "C" int mlvfs_amd_test_lj92_row_plan(int w, int max_w, long long out[4])
+{
+    if (!out || w < 1 || max_w < w || max_w > 65535) { set_error("lj92: row plan wants 1 <= w <= max_w <= 65535"); return MLVFS_AMD_ERR_ARG; }
+    const LjRowPlan p = lj_row_plan(w, max_w);
+    out[0] = p.staged ? 1 : 0; out[1] = p.stage_off; out[2] = p.stage_end; out[3] = p.lds_bytes;
+    return MLVFS_AMD_OK;
+}
+
 extern "C" int mlvfs_amd_lj92_decode_dev(const void *const *streams, const size_t *sizes, int nframes, int xres, int yres,
                                          void *d_out, size_t out_stride, void *stream)
 {

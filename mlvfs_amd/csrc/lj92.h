@@ -34,6 +34,28 @@ struct LjFrame {
 
 constexpr int LJ_WAVE_MAX_H = 8192;        // predictor 7 keeps two anti-diagonals (indexed by row) in LDS
 
+// k_lj_rows' dynamic LDS, ONE rule for the launcher (how many bytes) and the kernel (where a frame's row goes): the carries of the
+// widest frame's blocks of 32 columns (+ 2), then room for the widest row of the batch that can be staged at all -- min(max_w,
+// LJ_ROW_LDS) values, one spare word per 32 (+ 2).  A row of w <= LJ_ROW_LDS values is staged there whatever else is in its batch;
+// a longer one is worked on in place in global memory.  65535 values at most: 2050 carries + 8450 ints = 50 200 bytes.
+constexpr int LJ_ROW_LDS = 8192;
+struct LjRowPlan {
+    bool staged;                 // the row of w values goes through LDS
+    uint32_t stage_off;          // bytes from the start of the launch's LDS to the staged row (behind the carries)
+    uint32_t stage_end;          // bytes up to which a staged row of w values reaches (== stage_off when it is not staged)
+    uint32_t lds_bytes;          // what a launch for rows of up to max_w values asks for
+};
+__host__ __device__ inline LjRowPlan lj_row_plan(int w, int max_w)
+{
+    const int cap = max_w < LJ_ROW_LDS ? max_w : LJ_ROW_LDS;
+    LjRowPlan p;
+    p.staged = w <= cap;
+    p.stage_off = (uint32_t)((max_w + 31) / 32 + 2) * (uint32_t)sizeof(long long);
+    p.lds_bytes = p.stage_off + (uint32_t)(cap + cap / 32 + 2) * (uint32_t)sizeof(int);
+    p.stage_end = p.stage_off + (p.staged && w > 0 ? (uint32_t)(w + ((w - 1) >> 5)) * (uint32_t)sizeof(int) : 0u);      // value i lies at i + (i >> 5)
+    return p;
+}
+
 // preds: bit p set when some frame of the batch uses predictor p (the rarely used ones have kernels of their own)
 int lj92_launch(const LjFrame *d_frames, int nframes, uint32_t max_raw, uint32_t max_nwg, uint32_t max_ngrp, int max_w, int max_h,
                 unsigned preds, hipStream_t s);
