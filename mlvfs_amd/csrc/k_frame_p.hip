@@ -664,6 +664,9 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
     // (SPREAD stays in the kernel's name, always false: the benchmark's result and the profiles know the kernel by it.  A directly
     // indexed table puts neighbouring levels into neighbouring banks)
     static_assert(!SPREAD, "one table layout");
+    // (as a plain value, not a kernel argument the allocator may load again wherever it is used: the four ints behind FrameArgs are one
+    // 16-byte load, and a spill slot set aside for it and never used made the kernel ask for scratch memory)
+    asm volatile("" : "+s"(cols));
     constexpr int BPP = 14;                              // (S_OUT: items a wave writes per row, frame_plan.h: FRAME_STREAM_COLW)
     constexpr int WAVES = 16;                            // one workgroup per CU: the CU's one copy of the table
     // the lanes that write a row park it (1 .. 62; lanes 0 and 63 share their neighbours' slots, unused): with 64 slots a row the
@@ -700,9 +703,10 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
         KArgs kt = cold_args();                          // (what a task needs once: read here, not held in scalar registers through the launch)
         const uint8_t *const frame = kt->src + (size_t)f * kt->src_stride;
         const mlv_i32x4 rs_in = frame_rsrc(frame, kt->src_bytes);
-        const mlv_i32x4 rs_out = frame_rsrc(kt->dst + (size_t)f * kt->dst_stride, (uint32_t)w * (uint32_t)h * 2u);
-        const int tx0 = 8 * (c * S_OUT - 1);
-        const bool xm = c == 0 || 8 * (c * S_OUT + S_OUT) > w - 4;
+        // (the output stage's descriptor and its two scalars are made when the window is full: nothing before needs them)
+        mlv_i32x4 rs_out = { 0, 0, 0, 0 };
+        int tx0 = 0;
+        bool xm = false;
         uint32_t dA0[4], dA1[4], dB0[4], dB1[4];
         auto issue = [&](int r, uint32_t (&d0)[4], uint32_t (&d1)[4]) { stream_issue(rs_in, r, roff, rows, pitch, t.gbyte, d0, d1); };
         issue(j0 - 2, dA0, dA1);
@@ -782,11 +786,24 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
         int fl1 = 3, fl2 = 3, fl3 = 3, fl4 = 3;          // low / dim flags of rows r - 1 .. r - 4 (k_frame_s.hip)
         unsigned long long unc_lanes = 0;                // lanes with an uncertain strip in some row of the task
         int unc_r0 = 1 << 30, unc_r1 = -1;               // ... and the rows
-        auto step = [&](int r, uint32_t (&d0)[4], uint32_t (&d1)[4]) {
+        // One step: row r comes in (d0 / d1: its stream words, loaded two steps ago), row r - 2 goes out.  OUT and PRE say where the step
+        // stands in the task and are fixed where it is written (the loops below).  OUT: the step has an output stage.  PRE: it loads
+        // row r + 2 into the registers it has just emptied -- always, at the clamped row: as a condition of the step the registers
+        // became a merge of "loaded" and "kept", copied at the loop's edges behind a drained wait (trap 1).  A step
+        // with an output stage issues that load behind its table look-ups' wait and ahead of its stores (stream_output's hook), so
+        // the load stays in flight until the NEXT step's look-ups are waited for; n0 / n1, the other buffer, is what the next step
+        // unpacks: named as used at that point, where it has arrived, it costs the next step no wait of its own (the compiler cannot
+        // see that every path through the output stage's variants waits; its wait at the next step's head would count the stores and
+        // the load just issued as older and drain them).
+        auto step = [&](auto OUT, auto PRE, int r, uint32_t (&d0)[4], uint32_t (&d1)[4], const uint32_t (&n0)[4], const uint32_t (&n1)[4]) {
             uint32_t p0[8], p1[8];
             unpack8<BPP>(d0, t.sel, t.sel, t.sel, p0);
             unpack8<BPP>(d1, t.sel1, t.sel1, t.sel1, p1);
-            if (r + 2 <= j1 + 1) issue(r + 2, d0, d1);
+#ifdef P5_AB_EARLY_PREFETCH
+            if constexpr (PRE.value) issue(r + 2, d0, d1);
+#else
+            if constexpr (PRE.value && !OUT.value) issue(r + 2, d0, d1);
+#endif
             if (n_pm) {                                   // pixel-map cells of this row: the owning lane takes the record's pixels
                 unsigned long long m = __ballot(lane < n_pm && (pm_cell >> 16) == r);
                 while (m) {
@@ -817,8 +834,15 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) { pkr[0][i] = pkr[1][i]; pkr[1][i] = pkr[2][i]; pkr[2][i] = pkr[3][i]; pkr[3][i] = pkr[4][i]; pkr[4][i] = pk[i]; }
-            const int jr = r - 2, y = 2 * jr, yl = y + 2 * roff;
-            if (jr >= j0 && jr < j1) {
+            if constexpr (OUT.value) {
+                const int jr = r - 2, y = 2 * jr, yl = y + 2 * roff;
+#ifndef P5_AB_LATE_OUTARGS
+                // what the look-ups need of the cold arguments (their table, and `stripes`, which picks the variant): asked for a median
+                // chain ahead of them.  The rest is read where it is used (held through the chain it is what the allocator spills)
+                KArgs ke = cold_args();
+                const uint2 *const e2d_early = ke->e2d;
+                const int stripes_early = ke->stripes;
+#endif
                 const unsigned long long msmooth = lanes_ge(yl, 4) & lanes_lt(yl, h - 5);  // chroma_smooth.c:25
                 const bool smooth_row = y + 2 * (nparts - 1) * seg_rows >= 4 && y < h - 5; // (some group's row)
                 mlv_pk16 o[STRIP] = { { 0, 0 }, { 0, 0 }, { 0, 0 }, { 0, 0 } };
@@ -861,17 +885,56 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
                     top[0] = t4.x; top[1] = t4.y; top[2] = t4.z; top[3] = t4.w;
                     bot[0] = b4.x; bot[1] = b4.y; bot[2] = b4.z; bot[3] = b4.w;
                 }
-                const OutArgs oa = out_args(cold_args());          // (read here, not held through the step: 39 -> 17 spilled scalars)
+#ifndef P5_AB_LATE_OUTARGS
+                OutArgs oa = out_args(cold_args());                // (read here, not held through the step: 39 -> 17 spilled scalars)
+                oa.e2d = e2d_early; oa.stripes = stripes_early;
+#else
+                const OutArgs oa = out_args(cold_args());
+#endif
                 // (the five rows of the window; stream_output adds what smoothing makes of them)
-                stream_output<5>(oa, t, tx0, xm, rs_out, w, h, black, jr, yl, msmooth, fl0 | fl1 | fl2 | fl3 | fl4, ge2, er, eb, top, bot);
+                stream_output<5>(oa, t, tx0, xm, rs_out, w, h, black, jr, yl, msmooth, fl0 | fl1 | fl2 | fl3 | fl4, ge2, er, eb, top, bot, [&] {
+#ifndef P5_AB_EARLY_PREFETCH
+                    if constexpr (PRE.value) {
+                        asm volatile("" :: "v"(n0[0]), "v"(n0[1]), "v"(n0[2]), "v"(n0[3]), "v"(n1[0]), "v"(n1[1]), "v"(n1[2]), "v"(n1[3]));
+                        issue(r + 2, d0, d1);
+                    }
+#endif
+                });
             }
 #pragma unroll
             for (int cc = 0; cc < 4; cc++) { ge2[cc] = ge1[cc]; ge1[cc] = ge[cc]; }
             fl4 = fl3; fl3 = fl2; fl2 = fl1; fl1 = fl0;
         };
-        for (int r = j0 - 2; r <= j1 + 1; r += 2) {
-            step(r, dA0, dA1);
-            if (r + 1 <= j1 + 1) step(r + 1, dB0, dB1);
+        // The task's j1 - j0 + 4 steps, peeled so that no step tests where it stands: four that only fill the window (rows j0 - 2 ..
+        // j0 + 1), pairs with an output stage and a prefetch while the first of a pair still has a row to fetch (the second may fetch
+        // one row past the task: clamped, unused), and the last one or two, which fetch nothing, in one copy that picks its buffer.
+        constexpr std::true_type Y{};
+        constexpr std::false_type N{};
+        int r = j0 - 2;
+#pragma unroll 1
+        for (; r < j0 + 2; r += 2) {
+            step(N, Y, r, dA0, dA1, dB0, dB1);
+            step(N, Y, r + 1, dB0, dB1, dA0, dA1);
+        }
+        // (the main loop's first step finds its row arrived, as every later one does: the same state on both ways into the loop's head)
+        asm volatile("" :: "v"(dA0[0]), "v"(dA0[1]), "v"(dA0[2]), "v"(dA0[3]), "v"(dA1[0]), "v"(dA1[1]), "v"(dA1[2]), "v"(dA1[3]));
+        {
+            KArgs ko = cold_args();
+            rs_out = frame_rsrc(ko->dst + (size_t)f * ko->dst_stride, (uint32_t)w * (uint32_t)h * 2u);
+            tx0 = 8 * (c * S_OUT - 1);
+            xm = c == 0 || 8 * (c * S_OUT + S_OUT) > w - 4;
+        }
+#pragma unroll 1
+        for (; r < j1; r += 2) {
+            step(Y, Y, r, dA0, dA1, dB0, dB1);
+            step(Y, Y, r + 1, dB0, dB1, dA0, dA1);
+        }
+#pragma unroll 1
+        for (bool second = false; r <= j1 + 1; r++, second = true) {
+            uint32_t e0[4], e1[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) { e0[i] = second ? dB0[i] : dA0[i]; e1[i] = second ? dB1[i] : dA1[i]; }
+            step(Y, N, r, e0, e1, e0, e1);
         }
         // ---- what this task could not settle goes to k_frame: the tiles (64 x 15 cells) its uncertain strips lie in
         if (list_all) { unc_lanes = ~0ull; unc_r0 = j0; unc_r1 = j1 - 1; }

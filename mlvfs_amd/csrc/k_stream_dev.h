@@ -100,10 +100,11 @@ __device__ __forceinline__ int stream_row_low(const uint32_t (&p0)[8], const uin
 // 8 * (t.c * S_OUT - 1); xm: the column touches the frame's left or right margin, t.c == 0 || 8 * (t.c * S_OUT + S_OUT) > w - 4.  fl: the
 // flags of the rows of the window; what smoothing makes of them is added here (smoothed_low).  The variants of strip_output_t are
 // chosen by scalars: margins, low pixels, bright rows.
-template <int METHOD>
+struct StreamNoHook { __device__ __forceinline__ void operator()() const {} };
+template <int METHOD, class BEFORE_STORES = StreamNoHook>
 __device__ __forceinline__ void stream_output(const OutArgs &oa, const StreamTask &t, int tx0, bool xm, mlv_i32x4 rs_out, int w, int h, int black, int jr, int yl,
                                               unsigned long long msmooth, int fl, const int (&ge)[STRIP], const int (&er)[STRIP], const int (&eb)[STRIP],
-                                              uint32_t (&top)[STRIP], uint32_t (&bot)[STRIP])
+                                              uint32_t (&top)[STRIP], uint32_t (&bot)[STRIP], BEFORE_STORES before_stores = BEFORE_STORES())
 {
     fl |= oa.stripes && smoothed_low(er, eb) ? 1 : 0;
     auto out = [&](auto CLAMP, auto XM, auto BRIGHT) {
@@ -116,6 +117,7 @@ __device__ __forceinline__ void stream_output(const OutArgs &oa, const StreamTas
     else if (xm) out(N, Y, N);
     else if (fl == 0) out(N, N, Y);
     else out(N, N, N);
+    before_stores();
     if (t.writes) {
         const uint32_t vo = (__umul24((uint32_t)yl, (uint32_t)w) + (uint32_t)(8 * t.g)) * 2u;     // (rows below the frame: beyond the buffer's range)
         const mlv_u32x4 vt = { top[0], top[1], top[2], top[3] }, vb = { bot[0], bot[1], bot[2], bot[3] };
