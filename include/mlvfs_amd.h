@@ -271,6 +271,10 @@ int mlvfs_amd_lj92_decode_untiled(lj92 lj, uint16_t *dst, int xres, int yres);
 /* host-only test hook: the encoder's Huffman table for a histogram of the 17 classes; out[68] = bits[1..16], number of DHT
  * values, the 17 values, then length and code per class.  0, or -1 (error string set) where lj92_encode would refuse.          */
 int mlvfs_amd_lj92_encode_table(const uint32_t hist[17], int npix, int *out);
+/* Test hook, host only: how the encoder's kernels cut a frame of npix pixels, 1 <= npix < 2^27 (csrc/lj92enc.h, the constants the
+ * kernels are built with).  out[4] = {pixels per block, blocks of the frame, threads of the workgroup that scans a frame's block
+ * offsets, blocks each of its threads sums}.  0, or MLVFS_AMD_ERR_ARG.                                                          */
+int mlvfs_amd_test_lj92_encode_plan(long long npix, long long out[4]);
 /* The same encoder on a batch of frames that already lie in device memory: nframes frames of width x height uint16 values, `stride`
  * bytes apart, each to the COMPLETE stream (SOI .. EOI) lj92_encode writes for it with readLength = width * height, skipLength 0 and
  * no delinearisation table, at d_out + f * out_stride (device memory, 4-byte aligned, out_stride a multiple of 4).  One launch

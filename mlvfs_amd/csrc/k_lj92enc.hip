@@ -107,6 +107,7 @@ __global__ __launch_bounds__(256) void k_lje_hist(const uint16_t *const *__restr
 }
 
 // exclusive scan over the 1024 threads of a workgroup; *total = the sum
+static_assert(LJE_SCAN_THREADS == 16 * 64, "lje_scan1024 scans 16 waves of 64");
 __device__ __forceinline__ uint32_t lje_scan1024(uint32_t x, uint32_t *ws /* [16], shared */, uint32_t *total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -125,7 +126,7 @@ __device__ __forceinline__ uint32_t lje_scan1024(uint32_t x, uint32_t *ws /* [16
 __device__ __forceinline__ uint32_t lje_byte(const uint32_t *__restrict__ bits, uint32_t b) { return (bits[b >> 2] >> (24 - 8 * (b & 3))) & 0xFFu; }
 
 // off[0 .. nb]: where each block's bits begin, off[nb] = the frame's bits
-__global__ __launch_bounds__(1024) void k_lje_scan_bits(const LjeFrame *__restrict__ tabs, const uint32_t *__restrict__ blockhist, uint32_t nb,
+__global__ __launch_bounds__(LJE_SCAN_THREADS) void k_lje_scan_bits(const LjeFrame *__restrict__ tabs, const uint32_t *__restrict__ blockhist, uint32_t nb,
                                                         uint32_t *__restrict__ off, uint32_t *__restrict__ bits, LjeOut *__restrict__ res)
 {
     __shared__ uint32_t ws[16], cost[17];
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(1024) void k_lje_scan_bits(const LjeFrame *__restri
     if (t.status != LJE_OK) return;
     if (threadIdx.x < 17) cost[threadIdx.x] = t.len[threadIdx.x] + threadIdx.x;
     __syncthreads();
-    const uint32_t per = (nb + 1023) / 1024, b0 = min(nb, threadIdx.x * per), b1 = min(nb, b0 + per);
+    const uint32_t per = lje_scan_per(nb), b0 = min(nb, threadIdx.x * per), b1 = min(nb, b0 + per);
     uint32_t *o = off + (size_t)f * (nb + 1);
     uint32_t sum = 0;
     for (uint32_t b = b0; b < b1; b++) {
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(256) void k_lje_emit(const uint16_t *const *__restr
 }
 
 // ffoff[b]: 0xFF bytes before block b's bytes -- a block's bytes are those whose first bit is its own
-__global__ __launch_bounds__(1024) void k_lje_scan_ff(const LjeFrame *__restrict__ tabs, const uint32_t *__restrict__ off, uint32_t nb,
+__global__ __launch_bounds__(LJE_SCAN_THREADS) void k_lje_scan_ff(const LjeFrame *__restrict__ tabs, const uint32_t *__restrict__ off, uint32_t nb,
                                                       uint32_t *__restrict__ ffoff, const uint32_t *__restrict__ bits, uint8_t *__restrict__ out,
                                                       size_t out_stride, LjeOut *__restrict__ res)
 {
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(1024) void k_lje_scan_ff(const LjeFrame *__restrict
     const uint32_t f = blockIdx.x;
     const LjeFrame &t = tabs[f];
     if (t.status != LJE_OK) return;
-    const uint32_t per = (nb + 1023) / 1024, b0 = min(nb, threadIdx.x * per), b1 = min(nb, b0 + per);
+    const uint32_t per = lje_scan_per(nb), b0 = min(nb, threadIdx.x * per), b1 = min(nb, b0 + per);
     const uint32_t *o = off + (size_t)f * (nb + 1);
     uint32_t *fo = ffoff + (size_t)f * (nb + 1);
     const uint32_t *fb = bits + t.bits_at;
@@ -339,10 +340,10 @@ int lje_launch_pack(const uint16_t *const *d_src, const uint16_t *d_delin, int d
 {
     const uint32_t nb = lje_blocks(npix);
     const dim3 grid(nb, n);
-    hipLaunchKernelGGL(k_lje_scan_bits, dim3(n), dim3(1024), 0, s, d_tabs, d_blockhist, nb, d_off, d_bits, d_res);
+    hipLaunchKernelGGL(k_lje_scan_bits, dim3(n), dim3(LJE_SCAN_THREADS), 0, s, d_tabs, d_blockhist, nb, d_off, d_bits, d_res);
     if (d_delin) hipLaunchKernelGGL(k_lje_emit<true>, grid, dim3(256), 0, s, d_src, d_delin, delin_len, width, npix, bitdepth, d_tabs, (const uint32_t *)d_off, d_bits, d_ffoff);
     else hipLaunchKernelGGL(k_lje_emit<false>, grid, dim3(256), 0, s, d_src, d_delin, delin_len, width, npix, bitdepth, d_tabs, (const uint32_t *)d_off, d_bits, d_ffoff);
-    hipLaunchKernelGGL(k_lje_scan_ff, dim3(n), dim3(1024), 0, s, d_tabs, (const uint32_t *)d_off, nb, d_ffoff, (const uint32_t *)d_bits, d_out, out_stride, d_res);
+    hipLaunchKernelGGL(k_lje_scan_ff, dim3(n), dim3(LJE_SCAN_THREADS), 0, s, d_tabs, (const uint32_t *)d_off, nb, d_ffoff, (const uint32_t *)d_bits, d_out, out_stride, d_res);
     hipLaunchKernelGGL(k_lje_stuff, grid, dim3(256), 0, s, d_tabs, (const uint32_t *)d_off, (const uint32_t *)d_ffoff, (const uint32_t *)d_bits, d_out, out_stride, (const LjeOut *)d_res);
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

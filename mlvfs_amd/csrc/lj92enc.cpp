@@ -231,6 +231,16 @@ int mlvfs_amd_lj92_encode_table(const uint32_t hist[17], int npix, int *out)
     return 0;
 }
 
+// Test hook, host only: how the encoder's kernels cut a frame of npix pixels (lj92enc.h -- the constants the kernels and their
+// launchers are built with): pixels per block, blocks, threads of a scan workgroup, blocks per scan thread.
+int mlvfs_amd_test_lj92_encode_plan(long long npix, long long out[4])
+{
+    if (!out || npix < 1 || npix >= (1ll << 27)) { set_error("lj92_encode: encode plan wants 1 <= npix < 2^27"); return MLVFS_AMD_ERR_ARG; }
+    const uint32_t nb = lje_blocks((uint64_t)npix);
+    out[0] = LJE_BLOCK; out[1] = nb; out[2] = LJE_SCAN_THREADS; out[3] = lje_scan_per(nb);
+    return MLVFS_AMD_OK;
+}
+
 int mlvfs_amd_lj92_encode_batch_dev(const void *d_frames, size_t stride, int nframes, int width, int height, int bitdepth, void *d_out,
                                     size_t out_stride, uint32_t *lengths, int *status, int *max_class, void *stream)
 {

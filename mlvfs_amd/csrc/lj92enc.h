@@ -7,6 +7,7 @@ namespace mlv {
 
 constexpr int LJE_PER_THREAD = 16;                      // pixels (or stream bytes) per thread
 constexpr int LJE_BLOCK = 256 * LJE_PER_THREAD;         // pixels per workgroup
+constexpr int LJE_SCAN_THREADS = 1024;                  // threads of the one workgroup per frame that scans its blocks' offsets
 constexpr int LJE_HIST = 20;                            // counters per frame: 17 classes, 17-bit differences, a value beyond the
                                                         // delinearisation table, one spare
 
@@ -37,6 +38,8 @@ struct LjeResult {
 };
 
 inline uint32_t lje_blocks(uint64_t npix) { return (uint32_t)((npix + LJE_BLOCK - 1) / LJE_BLOCK); }
+// blocks a thread of the scan kernels sums before the workgroup's scan (k_lje_scan_bits, k_lje_scan_ff and the test hook)
+__host__ __device__ inline uint32_t lje_scan_per(uint32_t nb) { return (nb + LJE_SCAN_THREADS - 1) / LJE_SCAN_THREADS; }
 // the batch's fixed scratch: frame pointers, histograms, per-block class counts, bit and 0xFF offsets, frame records, results
 size_t lje_fixed_bytes(uint32_t npix, int nframes);
 

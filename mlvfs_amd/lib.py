@@ -55,7 +55,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_timer_begin", "mlvfs_amd_timer_end", "mlvfs_amd_selftest_host", "mlvfs_amd_selftest_tables", "mlvfs_amd_frame_begin", "mlvfs_amd_frame_end", "mlvfs_amd_frame_sync", "mlvfs_amd_dropin_stats", "mlvfs_amd_test_fail_next", "mlvfs_amd_dropin_transfers", "mlvfs_amd_dropin_profile",
     "mlvfs_amd_mlv_open", "mlvfs_amd_mlv_close", "mlvfs_amd_mlv_frame_count", "mlvfs_amd_mlv_chunk_count",
     "mlvfs_amd_mlv_xref", "mlvfs_amd_mlv_frame_headers", "mlvfs_amd_mlv_read_frames", "mlvfs_amd_mlv_process", "mlvfs_amd_mlv_process_dualiso",
-    "mlvfs_amd_lj92_info", "mlvfs_amd_lj92_decode_dev", "mlvfs_amd_lj92_decode_untiled", "mlvfs_amd_lj92_encode_table", "mlvfs_amd_test_rand_layout", "mlvfs_amd_test_device_order", "mlvfs_amd_test_stream_plan", "mlvfs_amd_test_lj92_row_plan", "mlvfs_amd_test_frame_plan", "mlvfs_amd_test_last_frame_plan", "mlvfs_amd_test_stream_listed", "mlvfs_amd_test_dualiso_parts", "mlvfs_amd_lzma_uncompress",
+    "mlvfs_amd_lj92_info", "mlvfs_amd_lj92_decode_dev", "mlvfs_amd_lj92_decode_untiled", "mlvfs_amd_lj92_encode_table", "mlvfs_amd_test_rand_layout", "mlvfs_amd_test_device_order", "mlvfs_amd_test_stream_plan", "mlvfs_amd_test_lj92_row_plan", "mlvfs_amd_test_lj92_encode_plan", "mlvfs_amd_test_frame_plan", "mlvfs_amd_test_last_frame_plan", "mlvfs_amd_test_stream_listed", "mlvfs_amd_test_dualiso_parts", "mlvfs_amd_lzma_uncompress",
     "mlvfs_amd_gif_size", "mlvfs_amd_gif_render", "mlvfs_amd_mlv_gif_data", "mlvfs_amd_process_unpacked_dev", "mlvfs_amd_deflicker_dev",
     "mlvfs_amd_fix_pattern_noise_dev", "mlvfs_amd_test_pn_scratch_cap", "mlvfs_amd_deflicker_batch_dev", "mlvfs_amd_hdr_preview_batch_dev",
     "mlvfs_amd_mount_open", "mlvfs_amd_mount_dng", "mlvfs_amd_mount_close",
@@ -194,6 +194,7 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_test_device_order", i, [vp, i, i, vp])
     sig("mlvfs_amd_test_stream_plan", i, [i, i, i, vp, vp, vp, vp])
     sig("mlvfs_amd_test_lj92_row_plan", i, [i, i, vp])
+    sig("mlvfs_amd_test_lj92_encode_plan", i, [C.c_longlong, vp])
     sig("mlvfs_amd_test_frame_plan", i, [vp, vp])
     sig("mlvfs_amd_test_last_frame_plan", i, [vp])
     sig("mlvfs_amd_test_stream_listed", i, [vp, vp])

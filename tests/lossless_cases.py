@@ -25,6 +25,35 @@ def fallback_frames(n=5, at=2):
     return frames
 
 
+LONG_K = 10                         # classes 1 .. 10 in long_stream_frames' staircase: class 0's code is ten one-bits or more
+
+
+def long_stream_frames(n=5, at=2):
+    """A clip in which frame `at` cannot be served compressed although every difference class is below 16: its rows alternate the two
+    halves of one staircase of 2W values, so every row of the 2W x H/2 view is that staircase and every difference below the first row
+    is zero.  The staircase uses class j Fibonacci(j) times (1, 1, 2, 3, 5 ...), j = 1 .. LONG_K, which gives class 0 -- the all-ones
+    code of the reference's table, the longest -- LONG_K bits or more: a stream of 0xFF bytes, each stuffed, longer than the pixels."""
+    frames = clip_frames("plain", n)
+    steps, a, b = [], 1, 1
+    for j in range(1, LONG_K + 1):
+        steps += [1 << (j - 1)] * a
+        a, b = b, a + b
+    row = [8192]
+    for k in range(2 * W - 1):
+        d = steps[k] if k < len(steps) else 0
+        row.append(row[-1] + d if row[-1] + d < 16384 else row[-1] - d)
+    pair = np.array(row, np.uint16).reshape(2, W)
+    frames[at] = np.ascontiguousarray(np.tile(pair, (H // 2, 1)))
+    return frames
+
+
+def mount_stream_room(w, h):
+    """(cap, stride) of csrc/mount.cpp for a w x h frame: a stream longer than the pixels (cap) is not served; the room a stream has
+    on the device is the frames' own stride there, the pixels' size rounded up to 256 bytes"""
+    img = w * h * 2
+    return img // 4 * 4, (img + 255) // 256 * 256
+
+
 def big_frames():
     return [synth.normal_frame(BIG_W, BIG_H, seed=1, frame=k) for k in range(BIG_N)]
 

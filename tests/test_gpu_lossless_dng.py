@@ -10,7 +10,8 @@ from mlvfs_amd import lj92, mlvfile, synth
 from mlvfs_amd.mount import Mount
 from mlvfs_amd.pipeline import MlvfsOptions
 
-from lossless_cases import BIG_H, BIG_W, H, W, assert_lossless_header, big_frames, fallback_frames, jpeg_view, max_class
+from lossless_cases import (BIG_H, BIG_W, H, W, assert_lossless_header, big_frames, fallback_frames, jpeg_view, long_stream_frames, max_class,
+                            mount_stream_room)
 from test_gpu_mount import dual_clip, mount_opts
 from test_gpu_ref_host import make_clip
 from test_lj92_encode import CASES as SMALL_CASES, material
@@ -193,6 +194,36 @@ def test_mount_serves_a_class_16_frame_uncompressed(gpu, reference, tmp_path):
     with r, m:
         files, flags = m.dng_lossless(0, 5, batch=3)
     assert flags[2] & 1, "the frame whose first pixel is 0 must be served uncompressed"
+    assert files[2] == plain[2].tobytes()
+    assert np.array_equal(plain[2][65536:].view(np.uint16).reshape(H, W), frames[2])
+    rest = [k for k in range(5) if k != 2]
+    _check_files(reference, [plain[k] for k in rest], [files[k] for k in rest], [flags[k] for k in rest], W, H, "neighbours")
+
+
+def test_mount_serves_a_frame_whose_stream_is_longer_than_its_pixels_uncompressed(gpu, oracle, reference, tmp_path):
+    """Frame 2's stream is all 0xFF bytes, each stuffed: longer than the frame's pixels with every class below 16
+    (tests/test_lossless_dng.py proves it on the CPU).  The refusal it takes is LJE_NOFIT on the device: the oracle's length is beyond
+    the stride the mount gives a stream there.  That stride equals the host's cap at this geometry (W * H * 2 is a multiple of 256), so
+    no length can pass k_lje_scan_ff and then fail `res.length > cap`; there is no second frame for that refusal."""
+    d = tmp_path / "card"
+    d.mkdir()
+    frames = long_stream_frames(n=5, at=2)
+    v = jpeg_view(frames[2])
+    cap, stride = mount_stream_room(W, H)
+    long = oracle.lj92_encode(v, v.shape[1], v.shape[0], 16)
+    assert max_class(long) < 16 and len(long) > stride == cap
+    pl = [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames]
+    mlvfile.write_clip(str(d / "M07-1234.MLV"), pl, W, H, chunks=2, frame_space=32, shuffle=True)
+    path = str(d / "M07-1234.MLV")
+    _fresh(gpu)
+    r, m = _open(path, {})
+    with r, m:
+        plain = m.dng(0, 5, batch=3)
+    _fresh(gpu)
+    r, m = _open(path, {})
+    with r, m:
+        files, flags = m.dng_lossless(0, 5, batch=3)
+    assert flags[2] & 1, "a stream longer than the pixels must be served uncompressed"
     assert files[2] == plain[2].tobytes()
     assert np.array_equal(plain[2][65536:].view(np.uint16).reshape(H, W), frames[2])
     rest = [k for k in range(5) if k != 2]

@@ -9,7 +9,8 @@ import pytest
 
 from mlvfs_amd import abi, lib, mlvfile, synth
 
-from lossless_cases import assert_lossless_header, big_frames, clip_frames, fallback_frames, ifd0, jpeg_view, max_class
+from lossless_cases import (H, LONG_K, W, assert_lossless_header, big_frames, clip_frames, fallback_frames, ifd0, jpeg_view, long_stream_frames,
+                            max_class, mount_stream_room)
 
 
 def _headers(L, k, length, offset=0, max_size=65536):
@@ -156,6 +157,33 @@ def test_no_frame_of_the_gpu_tests_clips_reaches_class_16(oracle, reference):
     frames = fallback_frames()
     classes = [max_class(oracle.lj92_encode(jpeg_view(f), 2 * f.shape[1], f.shape[0] // 2, 16)) for f in frames]
     assert classes[2] == 16 and all(c < 16 for i, c in enumerate(classes) if i != 2), classes
+
+
+def test_the_long_stream_frame_is_longer_than_its_pixels_below_class_16(oracle, reference):
+    """The CPU side of test_mount_serves_a_frame_whose_stream_is_longer_than_its_pixels_uncompressed: frame 2 of long_stream_frames()
+    encodes (oracle and reference agree, the reference's decoder gives the view back) to a stream longer than the frame's pixels with
+    every class below 16, and longer than the room the mount gives a stream on the device -- so the refusal it takes is LJE_NOFIT
+    from k_lje_scan_ff.  At this geometry the pixels' size is a multiple of 256, the device stride equals the host's cap, and no length
+    lies between the two: `res.length > cap` (csrc/mount.cpp) cannot be the refusal here."""
+    frames = long_stream_frames()
+    cap, stride = mount_stream_room(W, H)
+    assert cap == stride == W * H * 2
+    for k, f in enumerate(frames):
+        assert f.shape == (H, W) and int(f.max()) < 16384
+        v = jpeg_view(f)
+        s = oracle.lj92_encode(v, 2 * W, H // 2, 16)
+        assert s is not None and max_class(s) < 16, k
+        if k != 2:
+            assert len(s) <= cap, k
+            continue
+        assert (v == v[0]).all()                                        # every row the same staircase
+        longest = max(l for l in range(1, 17) if s[19 + l])           # DHT: codes per length; the longest is class 0's, all ones
+        assert longest >= LONG_K >= 9
+        assert len(s) > 65 + (W * H * longest // 8) * 2 - 4 * W         # 0xFF bytes, each stuffed, behind the first row
+        assert len(s) > stride >= cap                                   # NOFIT on the device
+        assert len(s) <= 2 * W * (H // 2) * 3 + 200 and reference.lj92_encode_tile(v, 2 * W, H // 2, 16) == s
+        st, back = reference.lj92_decode(s)
+        assert st == 0 and np.array_equal(back, v)
 
 
 def test_stream_geometry_sizes(oracle):
