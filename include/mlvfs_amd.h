@@ -634,6 +634,65 @@ int  mlvfs_amd_repack_dev(const mlvfs_amd_geom_t *geom, int out_bpp, const mlvfs
 int  mlvfs_amd_mlv_transcode_bits(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark,
                                   int batch_frames, int io_threads, long long stats[4]);
 
+/* -- flat-field correction (csrc/flat.cpp, csrc/k_flat.hip) -- what `mlv_dump -t` does -------------------------- */
+/* A flat field: a plane F of width x height 16-bit values with a pedestal black_f, the black level of the clip of an evenly lit
+ * target it was averaged from.  Integer arithmetic only.  The gain plane, one uint16 per pixel in Q14 (16384 = 1.0):
+ *     s[p]    = max(F[p] - black_f, 1)
+ *     c       = (y & 1) * 2 + (x & 1)                                 the channel, by position in the stored frame
+ *     M_c     = (sum of s[p] over channel c + n_c / 2) / n_c          n_c pixels of channel c; 64-bit sums
+ *     gain[p] = min((M_c * 16384 + s[p] / 2) / s[p], 65535)
+ * so a gain stops at 65535 / 16384, just under 4.0: a pixel whose flat value is below a quarter of its channel's mean is corrected
+ * by that cap and no more.  A channel without pixels (a width or height of 1) has no M_c and is never read.  The application:
+ *     out = clamp(black + floor(((px - black) * gain[p] + 8192) / 16384), 0, 2^bpp - 1)
+ * with the frame's own raw_info.black_level and depth; a frame value above 2^bpp - 1, which no valid frame holds but a damaged LJ92
+ * stream can decode to, is taken as 2^bpp - 1.  A gain plane has no depth: a flat shot at 14 bits corrects a 12- or 10-bit
+ * clip of the same width x height; only the size must match.  A constant flat gives gain = 16384 everywhere and leaves every frame
+ * as it is, bit for bit.  The plane is applied by position in the stored frame; panPosX/Y and cropPosX/Y are ignored.  The frame's
+ * levels, its RAWI block and its DNG header do not change.  It is stage 0b: directly after the dark frame (stage 0), before every
+ * other stage and before a change of bit depth.  The reference has no such stage.
+ * A handle keeps the gain plane on the host and uploads it once per device, on that device's first use; afterwards it is read-only: it
+ * may be shared between threads and mounts and must outlive the mounts that use it.                                               */
+typedef struct mlvfs_amd_flat mlvfs_amd_flat_t;
+/* The gain plane of h_plane[width * height], computed on the host.  geom: width, height, bpp (1..16) and black (= black_f,
+ * 0..65535) are used.  Needs no HIP device.  NULL on a null argument, a non-positive size (or 2^27 pixels and more), bpp or black
+ * out of range (mlvfs_amd_last_error).                                                                                            */
+mlvfs_amd_flat_t *mlvfs_amd_flat_create(const mlvfs_amd_geom_t *geom, const uint16_t *h_plane);
+/* The gain plane of the rounded mean of frames first .. first + count - 1 of an opened clip (mlvfs_amd_dark_from_clip's mean and
+ * limits), computed on the GPU; black_f is the black level of frame `first`.  dark (optional; its width, height and bpp must be the
+ * flat clip's) is subtracted from the mean plane first.  The plane equals mlvfs_amd_flat_create's of the same mean.  NULL as for
+ * mlvfs_amd_dark_from_clip, and for a dark frame of another geometry.                                                             */
+mlvfs_amd_flat_t *mlvfs_amd_flat_from_clip(const void *reader, int first, int count, const mlvfs_amd_dark_t *dark, int batch_frames,
+                                           int io_threads);
+/* geom (optional): width, height, the flat plane's bpp and black = black_f, the rest 0; frames_averaged (optional): 0 for a plane
+ * given to mlvfs_amd_flat_create; means (optional): M_c[4], 0 for a channel without pixels.  Host code.                           */
+int  mlvfs_amd_flat_info(const mlvfs_amd_flat_t *flat, mlvfs_amd_geom_t *geom, int *frames_averaged, uint32_t means[4]);
+/* the gain plane into h_gain[width * height]; MLVFS_AMD_ERR_ARG when cap_pixels is smaller.  Host code.                           */
+int  mlvfs_amd_flat_gain(const mlvfs_amd_flat_t *flat, uint16_t *h_gain, size_t cap_pixels);
+void mlvfs_amd_flat_destroy(mlvfs_amd_flat_t *flat);
+/* In place on nframes 16-bit device frames `stride` bytes apart (bytes between them are not touched); asynchronous on `stream`.
+ * geom: the FRAMES' width, height, bpp (1..16) and black (0..65535).  dark (optional; geom's width, height and bpp) is subtracted
+ * first, in the same pass.  A size that is not the flat field's, a dark frame of another geometry, bpp or black out of range:
+ * MLVFS_AMD_ERR_ARG before any device work.  Up to 15 bits with black <= 32767, width * height a multiple of 16 and d_frames and
+ * stride 16-byte aligned take the fast form (16 pixels per lane, 32-bit products); anything else, 16-bit frames included, one pixel
+ * per lane with 64-bit products, down to 2-byte alignment.                                                                        */
+int  mlvfs_amd_flat_apply_dev(const mlvfs_amd_flat_t *flat, const mlvfs_amd_dark_t *dark, const mlvfs_amd_geom_t *geom, void *d_frames,
+                              size_t stride, int nframes, void *stream);
+/* The mount corrects every frame it serves with `flat`, directly after the dark frame if one is set and before everything else
+ * (mlvfs_amd_mount_dng and mlvfs_amd_mount_dng_lossless alike).  NULL clears.  MLVFS_AMD_ERR_ARG once the handle has served a
+ * frame, or when width or height differ from the clip's.
+ * As for mlvfs_amd_mount_set_dark: the bad-pixel map is the process's, shared per clip GUID, and is detected from the first frame
+ * that reaches the repair -- with a flat field set, a corrected one.  Mounts of one clip with different flat fields, or with and
+ * without one, in one process share whichever map was detected first: call free_focus_pixel_maps() between them where each is to
+ * behave like a fresh process (which is what the byte-for-byte equalities are stated for).                                        */
+int  mlvfs_amd_mount_set_flat(void *mount, const mlvfs_amd_flat_t *flat);
+/* mlvfs_amd_mlv_transcode_bits with the flat field applied to every frame after the dark frame and before the change of depth.
+ * flat = NULL: mlvfs_amd_mlv_transcode_bits itself, byte for byte and launch for launch.  With a flat field the load delivers
+ * corrected 16-bit frames, and the tiling or packing pass (with the shift, if any) follows: every route goes through the GPU, plain
+ * output of a plain clip included, and plain or LZMA to plain pays one pass more than the packed-to-packed repack.  A frame whose
+ * width or height is not the flat field's: MLVFS_AMD_ERR_ARG before any output file exists.                                       */
+int  mlvfs_amd_mlv_transcode_cal(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark,
+                                 const mlvfs_amd_flat_t *flat, int batch_frames, int io_threads, long long stats[4]);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):

@@ -202,6 +202,34 @@ int launch_dark_unpack(const void *d_packed, size_t packed_stride, void *d_out, 
                        const DarkFrameDev &dark, hipStream_t stream);
 int launch_dark_accum(const void *d_frames, size_t stride, uint32_t npix, int nframes, uint32_t *d_sums, hipStream_t stream);
 int launch_dark_mean(const uint32_t *d_sums, uint16_t *d_dark, uint32_t npix, uint32_t n, hipStream_t stream);
+// what dark.cpp and flat.cpp share: a plane's geometry check (false with the error set: a non-positive size or 2^27 pixels and more,
+// bpp outside 1..16, a pedestal outside 0..65535), device memory that lives as long as its scope, and
+// what they average a clip with: the one geometry of frames first .. first + count - 1 and frame first's black
+// level (false, with the error set: frames outside the clip, count outside 1..65536, unusable headers, more than one geometry),
+// and their rounded mean as w * h 16-bit values at d_mean (16-byte aligned), summed in batches; s is drained on return
+bool plane_geometry_ok(const char *who, int w, int h, int bpp, int black);
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+bool clip_mean_geometry(const char *who, const void *reader, int first, int count, int *w, int *h, int *bpp, int *black);
+int clip_mean_dev(const void *reader, int first, int count, int w, int h, int bpp, int batch, int io_threads, uint16_t *d_mean, hipStream_t s);
+// A flat field (flat.cpp, k_flat.hip) as the kernels take it: the Q14 gain plane on the current device, and the
+// black level and 2^bpp - 1 of the FRAMES it is applied to (a gain plane has no depth of its own)
+struct FlatFieldDev {
+    const uint16_t *d_gain;
+    int black, top;
+};
+// the handle's gain plane on the calling thread's device (uploaded on the device's first use); the size must be the handle's
+int flatfield_on_device(const mlvfs_amd_flat_t *flat, ThreadCtx *c, int w, int h, const uint16_t **d_gain);
+bool flatfield_fits(const mlvfs_amd_flat_t *flat, int w, int h);
+int launch_flat_gain(const uint16_t *d_plane, uint32_t w, uint32_t h, int black_f, unsigned long long *d_sums, uint16_t *d_gain,
+                     uint32_t *d_means, hipStream_t stream);
+// stage 0b, in place; dark (optional): stage 0, subtracted first in the same pass
+int launch_flat_apply(void *d_frames, size_t stride, uint32_t npix, int nframes, const FlatFieldDev &flat, const DarkFrameDev *dark,
+                      hipStream_t stream);
+int launch_flat_unpack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int nframes,
+                       const FlatFieldDev &flat, const DarkFrameDev *dark, hipStream_t stream);
 // the mount's reader half (mlvreader.cpp): frames of one geometry from the file to 16-bit pixels in HBM.  On return everything that
 // reads the reader's staging has ended on s; without `dark` s is drained.  dark: stage 0, the dark frame subtracted from every frame
 // as it arrives -- plain and LZMA payloads inside the unpack pass (s drained on return), LJ92 payloads in a pass behind the decoder
@@ -214,11 +242,14 @@ struct LoadBits {
     int out_bpp;
     bool packed;
 };
+// flat: stage 0b, the flat field's gain, in the pass that subtracts the dark frame (or would): plain and LZMA payloads in
+// launch_flat_unpack, LJ92 payloads in one launch_flat_apply behind the decoder.  Not together with `bits`: the caller shifts afterwards.
 int reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                      hipStream_t s, const DarkFrameDev *dark = nullptr);
+                      hipStream_t s, const DarkFrameDev *dark = nullptr, const FlatFieldDev *flat = nullptr);
 // the same for frames named one by one (all of one geometry and payload kind); stage_locked: the caller holds reader_stage_mutex
 int reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                     hipStream_t s, bool stage_locked, const DarkFrameDev *dark = nullptr, const LoadBits *bits = nullptr);
+                     hipStream_t s, bool stage_locked, const DarkFrameDev *dark = nullptr, const LoadBits *bits = nullptr,
+                     const FlatFieldDev *flat = nullptr);
 // what the transcoder (mlvwriter.cpp) asks of an opened clip: its path and chunk files, where a frame's VIDF block lies, the bytes of
 // its payload as read_frames (lj92: as the LJ92 decoder) takes it, packed payloads of plain and LZMA frames (host only), and the
 // mutex that serialises the reader's streaming calls

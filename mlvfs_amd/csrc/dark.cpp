@@ -25,7 +25,28 @@ struct mlvfs_amd_dark {
 
 namespace {
 
-bool geometry_ok(const char *who, int w, int h, int bpp, int black)
+size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+int mean_of_clip(const void *reader, int first, int count, int batch, int io_threads, mlvfs_amd_dark &d)
+{
+    const uint32_t npix = (uint32_t)d.w * (uint32_t)d.h;
+    LibcRandGuard rand_guard;                           // HIP code runs: the caller's rand() stream stays out of its reach
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    hipStream_t s = c->stream;
+    DevBuf mean;
+    MLV_HIP(hipMalloc(&mean.p, (size_t)npix * 2));
+    const int rc = clip_mean_dev(reader, first, count, d.w, d.h, d.bpp, batch, io_threads, (uint16_t *)mean.p, s);
+    if (rc != MLVFS_AMD_OK) return rc;
+    d.plane.resize(npix);
+    MLV_HIP(hipMemcpyAsync(d.plane.data(), mean.p, (size_t)npix * 2, hipMemcpyDeviceToHost, s));
+    MLV_HIP(hipStreamSynchronize(s));
+    return MLVFS_AMD_OK;
+}
+
+}  // namespace
+
+bool mlv::plane_geometry_ok(const char *who, int w, int h, int bpp, int black)
 {
     if (w <= 0 || h <= 0 || (uint64_t)w * h >= (1u << 27)) { set_error("%s: %dx%d not supported", who, w, h); return false; }
     if (bpp < 1 || bpp > 16) { set_error("%s: unsupported bits_per_pixel %d", who, bpp); return false; }
@@ -33,25 +54,33 @@ bool geometry_ok(const char *who, int w, int h, int bpp, int black)
     return true;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
-int mean_of_clip(const void *reader, int first, int count, int batch, int io_threads, mlvfs_amd_dark &d)
+bool mlv::clip_mean_geometry(const char *who, const void *reader, int first, int count, int *w, int *h, int *bpp, int *black)
 {
-    const uint32_t npix = (uint32_t)d.w * (uint32_t)d.h;
+    const int frames = mlvfs_amd_mlv_frame_count(reader);
+    if (count < 1 || count > 65536) { set_error("%s: a mean of %d frames (1..65536)", who, count); return false; }
+    if (first < 0 || (long long)first + count > frames) { set_error("%s: frames %d..%lld outside the clip (%d frames)", who, first, (long long)first + count - 1, frames); return false; }
+    for (int k = 0; k < count; k++) {
+        frame_headers fh;
+        if (!mlvfs_amd_mlv_frame_headers(reader, first + k, &fh)) { set_error("%s: frame %d has no usable headers", who, first + k); return false; }
+        const int fw = fh.rawi_hdr.xRes, fhh = fh.rawi_hdr.yRes, fb = fh.rawi_hdr.raw_info.bits_per_pixel;
+        if (k == 0) {
+            if (!plane_geometry_ok(who, fw, fhh, fb, fh.rawi_hdr.raw_info.black_level)) return false;
+            *w = fw; *h = fhh; *bpp = fb; *black = fh.rawi_hdr.raw_info.black_level;
+        } else if (fw != *w || fhh != *h || fb != *bpp) {
+            set_error("%s: frames of more than one geometry (frame %d)", who, first + k);
+            return false;
+        }
+    }
+    return true;
+}
+
+int mlv::clip_mean_dev(const void *reader, int first, int count, int w, int h, int bpp, int batch, int io_threads, uint16_t *d_mean, hipStream_t s)
+{
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;
     const size_t dstride = up256((size_t)npix * 2);
-    LibcRandGuard rand_guard;                           // HIP code runs: the caller's rand() stream stays out of its reach
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    hipStream_t s = c->stream;
-    DevBuf frames, sums, mean;
+    DevBuf frames, sums;
     MLV_HIP(hipMalloc(&frames.p, dstride * (size_t)batch));
     MLV_HIP(hipMalloc(&sums.p, (size_t)npix * 4));
-    MLV_HIP(hipMalloc(&mean.p, (size_t)npix * 2));
     MLV_HIP(hipMemsetAsync(sums.p, 0, (size_t)npix * 4, s));
     int rc = MLVFS_AMD_OK;
     std::vector<int> kind(count);
@@ -62,18 +91,13 @@ int mean_of_clip(const void *reader, int first, int count, int batch, int io_thr
     }
     for (int f0 = 0, n; rc == MLVFS_AMD_OK && f0 < count; f0 += n) {
         for (n = 1; n < batch && f0 + n < count && kind[f0 + n] == kind[f0]; n++) {}
-        rc = reader_load_batch(reader, first + f0, n, d.w, d.h, d.bpp, frames.p, dstride, io_threads, s);
+        rc = reader_load_batch(reader, first + f0, n, w, h, bpp, frames.p, dstride, io_threads, s);
         if (rc == MLVFS_AMD_OK) rc = launch_dark_accum(frames.p, dstride, npix, n, (uint32_t *)sums.p, s);
     }
-    if (rc == MLVFS_AMD_OK) rc = launch_dark_mean((const uint32_t *)sums.p, (uint16_t *)mean.p, npix, (uint32_t)count, s);
-    if (rc != MLVFS_AMD_OK) { (void)hipStreamSynchronize(s); return rc; }
-    d.plane.resize(npix);
-    MLV_HIP(hipMemcpyAsync(d.plane.data(), mean.p, (size_t)npix * 2, hipMemcpyDeviceToHost, s));
-    MLV_HIP(hipStreamSynchronize(s));
-    return MLVFS_AMD_OK;
+    if (rc == MLVFS_AMD_OK) rc = launch_dark_mean((const uint32_t *)sums.p, d_mean, npix, (uint32_t)count, s);
+    (void)hipStreamSynchronize(s);                      // frames and sums go away here
+    return rc;
 }
-
-}  // namespace
 
 bool mlv::darkframe_fits(const mlvfs_amd_dark_t *dark, int w, int h, int bpp) { return dark->w == w && dark->h == h && dark->bpp == bpp; }
 
@@ -105,7 +129,7 @@ extern "C" {
 mlvfs_amd_dark_t *mlvfs_amd_dark_create(const mlvfs_amd_geom_t *geom, const uint16_t *h_plane)
 {
     if (!geom || !h_plane) { set_error("dark_create: null argument"); return nullptr; }
-    if (!geometry_ok("dark_create", geom->width, geom->height, geom->bpp, geom->black)) return nullptr;
+    if (!plane_geometry_ok("dark_create", geom->width, geom->height, geom->bpp, geom->black)) return nullptr;
     try {
         std::unique_ptr<mlvfs_amd_dark> d(new mlvfs_amd_dark);
         d->w = geom->width; d->h = geom->height; d->bpp = geom->bpp; d->black = geom->black;
@@ -117,23 +141,9 @@ mlvfs_amd_dark_t *mlvfs_amd_dark_create(const mlvfs_amd_geom_t *geom, const uint
 mlvfs_amd_dark_t *mlvfs_amd_dark_from_clip(const void *reader, int first, int count, int batch_frames, int io_threads)
 {
     if (!reader) { set_error("dark_from_clip: null argument"); return nullptr; }
-    const int frames = mlvfs_amd_mlv_frame_count(reader);
-    if (count < 1 || count > 65536) { set_error("dark_from_clip: a mean of %d frames (1..65536)", count); return nullptr; }
-    if (first < 0 || (long long)first + count > frames) { set_error("dark_from_clip: frames %d..%lld outside the clip (%d frames)", first, (long long)first + count - 1, frames); return nullptr; }
     try {
         std::unique_ptr<mlvfs_amd_dark> d(new mlvfs_amd_dark);
-        for (int k = 0; k < count; k++) {
-            frame_headers fh;
-            if (!mlvfs_amd_mlv_frame_headers(reader, first + k, &fh)) { set_error("dark_from_clip: frame %d has no usable headers", first + k); return nullptr; }
-            const int w = fh.rawi_hdr.xRes, h = fh.rawi_hdr.yRes, bpp = fh.rawi_hdr.raw_info.bits_per_pixel;
-            if (k == 0) {
-                if (!geometry_ok("dark_from_clip", w, h, bpp, fh.rawi_hdr.raw_info.black_level)) return nullptr;
-                d->w = w; d->h = h; d->bpp = bpp; d->black = fh.rawi_hdr.raw_info.black_level;
-            } else if (!darkframe_fits(d.get(), w, h, bpp)) {
-                set_error("dark_from_clip: frames of more than one geometry (frame %d)", first + k);
-                return nullptr;
-            }
-        }
+        if (!clip_mean_geometry("dark_from_clip", reader, first, count, &d->w, &d->h, &d->bpp, &d->black)) return nullptr;
         d->averaged = count;
         const int batch = std::min(batch_frames <= 0 ? 8 : batch_frames, count);
         if (mean_of_clip(reader, first, count, batch, io_threads, *d) != MLVFS_AMD_OK) return nullptr;

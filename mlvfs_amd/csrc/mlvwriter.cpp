@@ -27,6 +27,9 @@
 //   LJ92 -> plain           GPU decode -> k_dark_sub if a dark frame is set -> k_mlv_pack_shift -> file
 //   LJ92 -> LJ92            GPU decode -> k_dark_sub if set -> k_mlv_tile_shift -> the encoder at out_bpp
 // Frames already at out_bpp, and every frame when out_bpp is 0, take the routes above unchanged.
+// With a flat field (mlvfs_amd_mlv_transcode_cal) reader_load_list applies its gain after the dark frame (stage 0b:
+// k_flat.hip) and delivers corrected 16-bit frames at the source's depth; k_mlv_tile(_shift) or k_mlv_pack(_shift) follow on every
+// route, so a plain or LZMA source to plain output pays one pass more than k_mlv_repack.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -61,6 +64,7 @@ struct Block {
 struct Frame {
     int w, h, bpp, kind;
     int obpp;                  // bits per pixel of the payload written: bpp, or the call's out_bpp
+    int black;                 // raw_info.black_level: what a flat field's gain is applied around
 };
 
 bool is(const uint8_t t[4], const char *tag) { return !memcmp(t, tag, 4); }
@@ -169,6 +173,7 @@ struct DevRoom : LjeRoom {
 struct Job {
     const void *reader;
     const mlvfs_amd_dark_t *dark = nullptr;
+    const mlvfs_amd_flat_t *flat = nullptr;
     int payload, batch, io_threads;
     int out_bpp = 0;                                                   // 0: every frame keeps its depth
     std::vector<Frame> frames;
@@ -186,7 +191,7 @@ struct Job {
 
 size_t plain_bytes(const Frame &f) { return (size_t)(((uint64_t)f.w * f.h * f.obpp + 15) / 16) * 2; }             // of the payload written
 
-bool on_host(const Job &j, const Frame &f) { return j.payload == MLVFS_AMD_MLV_PLAIN && f.kind != SRC_LJ92 && !j.dark && f.obpp == f.bpp; }
+bool on_host(const Job &j, const Frame &f) { return j.payload == MLVFS_AMD_MLV_PLAIN && f.kind != SRC_LJ92 && !j.dark && !j.flat && f.obpp == f.bpp; }
 
 bool same_batch(const Frame &a, const Frame &b) { return a.w == b.w && a.h == b.h && a.bpp == b.bpp && a.kind == b.kind; }
 
@@ -231,15 +236,19 @@ int batch_device(Job &j, const std::vector<int> &list)
     DarkFrameDev dark{};
     int rc = j.dark ? darkframe_on_device(j.dark, j.ctx, f.w, f.h, f.bpp, &dark) : MLVFS_AMD_OK;
     if (rc) return rc;
+    FlatFieldDev flat{ nullptr, f.black, (1 << f.bpp) - 1 };
+    if (j.flat && (rc = flatfield_on_device(j.flat, j.ctx, f.w, f.h, &flat.d_gain))) return rc;
     const bool conv = f.obpp != f.bpp, plain = j.payload == MLVFS_AMD_MLV_PLAIN;
     const size_t pstride = up(plain_bytes(f), 16);                     // (<= dstride: d_aux has the room)
-    // at another depth a plain or LZMA source is shifted by the pass that reads it; to plain output that pass packs as well
+    // at another depth a plain or LZMA source is shifted by the pass that reads it; to plain output that pass packs as well.  Not with
+    // a flat field: the load corrects at the source's depth and the shift is left to the pass that follows, as for an LJ92 source
     const LoadBits bits{ f.obpp, plain };
-    const bool repacked = conv && plain && f.kind != SRC_LJ92;
+    const bool in_load = conv && f.kind != SRC_LJ92 && !j.flat;
+    const bool repacked = in_load && plain;
     rc = reader_load_list(j.reader, list.data(), n, f.w, f.h, f.bpp, repacked ? d.d_aux : d.d_frames, repacked ? pstride : dstride, j.io_threads, s,
-                          true, j.dark ? &dark : nullptr, conv && f.kind != SRC_LJ92 ? &bits : nullptr);
+                          true, j.dark ? &dark : nullptr, in_load ? &bits : nullptr, j.flat ? &flat : nullptr);
     if (rc) return rc;
-    const int shift = f.kind == SRC_LJ92 ? f.obpp - f.bpp : 0;         // what is left to do here
+    const int shift = in_load ? 0 : f.obpp - f.bpp;                    // what is left to do here
     if (plain) {
         const size_t bytes = plain_bytes(f);
         if ((rc = d.stage(pstride * n))) return rc;
@@ -339,7 +348,7 @@ int write_chunk(Job &j, int c, const std::string &name)
             std::vector<int> list;
             for (size_t k = i; k < blocks.size() && list.size() < cap; k++) {
                 if (!is(blocks[k].type, "VIDF")) continue;
-                if (!same_batch(j.frames[blocks[k].frame], f)) break;
+                if (!same_batch(j.frames[blocks[k].frame], f) || (j.flat && j.frames[blocks[k].frame].black != f.black)) break;
                 list.push_back(blocks[k].frame);
             }
             const int rc = on_host(j, f) ? batch_host(j, list) : batch_device(j, list);
@@ -407,8 +416,8 @@ bool list_blocks(Job &j, int nchunks, const std::map<std::pair<int, uint64_t>, i
     return ok;
 }
 
-int transcode(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark, int batch_frames, int io_threads,
-              long long stats[4])
+int transcode(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark, const mlvfs_amd_flat_t *flat,
+              int batch_frames, int io_threads, long long stats[4])
 {
     if (!reader || !out_path || !stats) { set_error("mlv transcode: null argument"); return MLVFS_AMD_ERR_ARG; }
     for (int i = 0; i < 4; i++) stats[i] = 0;
@@ -424,6 +433,7 @@ int transcode(const void *reader, const char *out_path, int payload, int out_bpp
     j.reader = reader;
     j.payload = payload;
     j.dark = dark;
+    j.flat = flat;
     j.out_bpp = out_bpp;
     j.batch = batch_frames <= 0 ? 8 : batch_frames;
     j.io_threads = io_threads;
@@ -458,6 +468,7 @@ int transcode(const void *reader, const char *out_path, int payload, int out_bpp
         f.bpp = fh.rawi_hdr.raw_info.bits_per_pixel;
         f.kind = payload_kind(vc);
         f.obpp = out_bpp ? out_bpp : f.bpp;
+        f.black = fh.rawi_hdr.raw_info.black_level;
         if (f.w <= 0 || f.h <= 0 || f.bpp < 1 || f.bpp > 16 || (uint64_t)f.w * f.h >= (1u << 27)) { set_error("mlv transcode: frame %d: %dx%d at %d bits is not supported", k, f.w, f.h, f.bpp); return MLVFS_AMD_ERR_ARG; }
         if (payload == MLVFS_AMD_MLV_LJ92 && ((f.w | f.h) & 1)) {
             set_error("mlv transcode: frame %d: the quadrant tiling of an LJ92 payload takes even sizes, not %dx%d", k, f.w, f.h);
@@ -465,6 +476,10 @@ int transcode(const void *reader, const char *out_path, int payload, int out_bpp
         }
         if (dark && !darkframe_fits(dark, f.w, f.h, f.bpp)) {
             set_error("mlv transcode: frame %d: %dx%d at %d bits is not the dark frame's geometry", k, f.w, f.h, f.bpp);
+            return MLVFS_AMD_ERR_ARG;
+        }
+        if (flat && !flatfield_fits(flat, f.w, f.h)) {
+            set_error("mlv transcode: frame %d: %dx%d is not the flat field's geometry", k, f.w, f.h);
             return MLVFS_AMD_ERR_ARG;
         }
         size_t bytes;
@@ -492,21 +507,28 @@ extern "C" {
 
 int mlvfs_amd_mlv_transcode(const void *reader, const char *out_path, int payload, int batch_frames, int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, 0, nullptr, batch_frames, io_threads, stats); }
+    try { return transcode(reader, out_path, payload, 0, nullptr, nullptr, batch_frames, io_threads, stats); }
     catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }    // (allocations sized from the file)
 }
 
 int mlvfs_amd_mlv_transcode_dark(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark, int batch_frames,
                                  int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, 0, dark, batch_frames, io_threads, stats); }
+    try { return transcode(reader, out_path, payload, 0, dark, nullptr, batch_frames, io_threads, stats); }
     catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
 }
 
 int mlvfs_amd_mlv_transcode_bits(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark, int batch_frames,
                                  int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, out_bpp, dark, batch_frames, io_threads, stats); }
+    try { return transcode(reader, out_path, payload, out_bpp, dark, nullptr, batch_frames, io_threads, stats); }
+    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
+}
+
+int mlvfs_amd_mlv_transcode_cal(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark,
+                                const mlvfs_amd_flat_t *flat, int batch_frames, int io_threads, long long stats[4])
+{
+    try { return transcode(reader, out_path, payload, out_bpp, dark, flat, batch_frames, io_threads, stats); }
     catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
 }
 

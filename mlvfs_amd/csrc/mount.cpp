@@ -1,8 +1,8 @@
 // mount.cpp -- a clip served as MLVFS serves it: process_frame (mlvfs/main.c:908-1005) and the two dng_get_header_data calls of it,
 // batch by batch, for every mount option that shapes a frame's .dng file.
 //
-// Per batch, in main.c's order: read + decode / unpack (the reader's staging, mlvreader.cpp; with a dark frame set -- which main.c does
-// not know -- its subtraction, stage 0, in the same load: k_dark.hip), deflicker (one histogram launch, one
+// Per batch, in main.c's order: read + decode / unpack (the reader's staging, mlvreader.cpp; with a dark frame or a flat field set -- which main.c does
+// not know -- the subtraction, stage 0, and the gain, stage 0b, in the same load: k_dark.hip, k_flat.hip), deflicker (one histogram launch, one
 // median launch, log2 on the host), the frame's header, pattern noise (12 launches per sub-batch), dual ISO (the batched preview,
 // or the batched full conversion), then per frame the route main.c takes: a converted frame gets the header again (x4 levels) and
 // chroma smoothing (preview only) + stripes; any other frame focus pixels, bad pixels, chroma smoothing (not under dual_iso = 2),
@@ -36,7 +36,8 @@ struct Mount {
     int stripes_needed = 0;
     int32_t coef[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     const mlvfs_amd_dark_t *dark = nullptr;  // stage 0 (mlvfs_amd_mount_set_dark): subtracted inside the reader's load
-    bool served = false;                     // a call has reached the device: the dark frame stays what it is
+    const mlvfs_amd_flat_t *flat = nullptr;  // stage 0b (mlvfs_amd_mount_set_flat): the gain, in the same pass of the load
+    bool served = false;                     // a call has reached the device: the dark frame and the flat field stay what they are
     int device = -1;
     void *d_frames = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_bits = nullptr;
     size_t frames_bytes = 0, scratch_bytes = 0, bits_bytes = 0;   // d_bits: the encoder's bit streams, sized from a batch's histograms
@@ -321,6 +322,24 @@ int mlvfs_amd_mount_set_dark(void *mount, const mlvfs_amd_dark_t *dark)
     return MLVFS_AMD_OK;
 }
 
+int mlvfs_amd_mount_set_flat(void *mount, const mlvfs_amd_flat_t *flat)
+{
+    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (m.served) { set_error("mount: the handle has served frames already: the flat field cannot change any more"); return MLVFS_AMD_ERR_ARG; }
+    frame_headers fh;
+    if (flat && mlvfs_amd_mlv_frame_count(m.reader) > 0) {
+        if (!mlvfs_amd_mlv_frame_headers(m.reader, 0, &fh)) { set_error("mount: frame 0 has no usable headers"); return MLVFS_AMD_ERR_ARG; }
+        if (!flatfield_fits(flat, fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) {
+            set_error("mount: the flat field does not have the clip's geometry (%dx%d)", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
+            return MLVFS_AMD_ERR_ARG;
+        }
+    }
+    m.flat = flat;
+    return MLVFS_AMD_OK;
+}
+
 // both entry points
 static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
                        int batch_frames, int io_threads, int *results)
@@ -348,6 +367,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     LibcRandGuard rand_guard;                      // HIP code runs: the caller's rand() stream stays out of its reach (rand_mode 0 draws from it)
     std::lock_guard<std::mutex> lk(m.mu);
     if (m.dark && !darkframe_fits(m.dark, w, h, bpp)) { set_error("mount: the dark frame does not have the geometry of frame %d (%dx%d at %d bits)", first, w, h, bpp); return MLVFS_AMD_ERR_ARG; }
+    if (m.flat && !flatfield_fits(m.flat, w, h)) { set_error("mount: the flat field does not have the geometry of frame %d (%dx%d)", first, w, h); return MLVFS_AMD_ERR_ARG; }
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
     const size_t img = (size_t)w * h * 2, dstride = up256(img);
@@ -358,6 +378,8 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     m.served = true;
     DarkFrameDev dark{};
     int rc = m.dark ? darkframe_on_device(m.dark, c, w, h, bpp, &dark) : MLVFS_AMD_OK;
+    FlatFieldDev flat{ nullptr, 0, (1 << bpp) - 1 };
+    if (rc == MLVFS_AMD_OK && m.flat) rc = flatfield_on_device(m.flat, c, w, h, &flat.d_gain);
     if (rc == MLVFS_AMD_OK) rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
     for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
         int n = std::min(batch_frames, count - f0);
@@ -365,7 +387,12 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             std::shared_ptr<Clip> known;
             if (!cached_bad_clip(&fh[f0], c, m.o.fix_bad_pixels == 2, &known)) n = 1;     // until the map exists: strictly in serve order
         }
-        rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream, m.dark ? &dark : nullptr);
+        if (m.flat) {                                                                      // the frames' own black level: one per load
+            flat.black = fh[f0].rawi_hdr.raw_info.black_level;
+            for (int k = 1; k < n; k++) if (fh[f0 + k].rawi_hdr.raw_info.black_level != flat.black) { n = k; break; }
+        }
+        rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream, m.dark ? &dark : nullptr,
+                               m.flat ? &flat : nullptr);
         if (rc == MLVFS_AMD_OK) {
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,

@@ -64,6 +64,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_dark_create", "mlvfs_amd_dark_from_clip", "mlvfs_amd_dark_info", "mlvfs_amd_dark_plane", "mlvfs_amd_dark_destroy",
     "mlvfs_amd_dark_subtract_dev", "mlvfs_amd_mount_set_dark", "mlvfs_amd_mlv_transcode_dark",
     "mlvfs_amd_rawi_set_bits", "mlvfs_amd_repack_dev", "mlvfs_amd_mlv_transcode_bits",
+    "mlvfs_amd_flat_create", "mlvfs_amd_flat_from_clip", "mlvfs_amd_flat_info", "mlvfs_amd_flat_gain", "mlvfs_amd_flat_destroy",
+    "mlvfs_amd_flat_apply_dev", "mlvfs_amd_mount_set_flat", "mlvfs_amd_mlv_transcode_cal",
 ]
 
 
@@ -242,6 +244,14 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_rawi_set_bits", i, [vp, i])
     sig("mlvfs_amd_repack_dev", i, [gp, i, vp, vp, sz, vp, sz, i, vp])
     sig("mlvfs_amd_mlv_transcode_bits", i, [vp, C.c_char_p, i, i, vp, i, i, C.POINTER(C.c_longlong)])
+    sig("mlvfs_amd_flat_create", vp, [gp, vp])
+    sig("mlvfs_amd_flat_from_clip", vp, [vp, i, i, vp, i, i])
+    sig("mlvfs_amd_flat_info", i, [vp, gp, C.POINTER(i), vp])
+    sig("mlvfs_amd_flat_gain", i, [vp, vp, sz])
+    sig("mlvfs_amd_flat_destroy", None, [vp])
+    sig("mlvfs_amd_flat_apply_dev", i, [vp, vp, gp, vp, sz, i, vp])
+    sig("mlvfs_amd_mount_set_flat", i, [vp, vp])
+    sig("mlvfs_amd_mlv_transcode_cal", i, [vp, C.c_char_p, i, i, vp, vp, i, i, C.POINTER(C.c_longlong)])
     _lib = L
     return L
 

@@ -181,16 +181,20 @@ class MlvReader:
                                                        io_threads, lib.ptr(res)), "mlv_process_dualiso")
         return res
 
-    def transcode(self, out_path: str, lj92: bool = True, batch: int = 0, io_threads: int = 0, dark=None, bits=None) -> dict:
+    def transcode(self, out_path: str, lj92: bool = True, batch: int = 0, io_threads: int = 0, dark=None, bits=None, flat=None) -> dict:
         """mlvfs_amd_mlv_transcode: the clip written again as <out_path> (+ .M00 ...) with lossless-JPEG payloads (lj92=True, what
         `mlv_dump -c` writes) or plain packed ones; blocks stay in the source's file order, NULL and XREF blocks are dropped, nothing is
         overwritten.  Plain output of a plain or LZMA clip needs no GPU.  dark: a mlvfs_amd.dark.Dark subtracted from every frame first
         (mlvfs_amd_mlv_transcode_dark; every route then runs on the GPU).  bits: the clip at another bit depth, 8..16, what
         `mlv_dump -b` writes (mlvfs_amd_mlv_transcode_bits: pixels and levels shifted, after the dark frame; RAWI rewritten); None or 0
-        keeps the clip's.  -> {frames, bytes_in, bytes_out, files}."""
+        keeps the clip's.  flat: a mlvfs_amd.flat.Flat whose gain corrects every frame after the dark frame and before the change of
+        depth (mlvfs_amd_mlv_transcode_cal).  -> {frames, bytes_in, bytes_out, files}."""
         stats = (C.c_longlong * 4)()
         payload = lib.MLV_LJ92 if lj92 else lib.MLV_PLAIN
-        if bits:
+        if flat is not None:
+            rc = self.L.mlvfs_amd_mlv_transcode_cal(self.h, os.fsencode(out_path), payload, int(bits or 0), None if dark is None else dark.h,
+                                                    flat.h, batch, io_threads, stats)
+        elif bits:
             rc = self.L.mlvfs_amd_mlv_transcode_bits(self.h, os.fsencode(out_path), payload, int(bits), None if dark is None else dark.h, batch,
                                                      io_threads, stats)
         elif dark is None:

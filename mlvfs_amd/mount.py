@@ -27,9 +27,11 @@ def mount_opts(opt: MlvfsOptions, deflicker: int = 0, fps: float = 0.0, rand_mod
 
 class Mount:
     """reader: an open mlvfile.MlvReader (or a raw mlvfs_amd_mlv_open handle); it must stay open while the Mount lives.
-    dark: a mlvfs_amd.dark.Dark to subtract from every frame (stage 0), or None."""
+    dark: a mlvfs_amd.dark.Dark to subtract from every frame (stage 0), or None.
+    flat: a mlvfs_amd.flat.Flat whose gain corrects every frame directly after that (stage 0b), or None."""
 
-    def __init__(self, reader, opt: MlvfsOptions, deflicker: int = 0, fps: float = 0.0, basename: str = "", rand_mode: int = 1, dark=None):
+    def __init__(self, reader, opt: MlvfsOptions, deflicker: int = 0, fps: float = 0.0, basename: str = "", rand_mode: int = 1, dark=None,
+                 flat=None):
         self.L = lib.load()
         self._reader = reader
         handle = getattr(reader, "h", reader)
@@ -38,19 +40,27 @@ class Mount:
         if not self.h:
             raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
         self.frame_count = self.L.mlvfs_amd_mlv_frame_count(handle)
-        self._dark = None
-        if dark is not None:
-            try:
+        self._dark = self._flat = None
+        try:
+            if dark is not None:
                 self.set_dark(dark)
-            except lib.MlvfsAmdError:
-                self.close()
-                raise
+            if flat is not None:
+                self.set_flat(flat)
+        except lib.MlvfsAmdError:
+            self.close()
+            raise
 
     def set_dark(self, dark) -> None:
         """dark: a mlvfs_amd.dark.Dark subtracted from every frame before any other stage (None clears); refused once a frame was
         served.  It must stay open while the Mount lives."""
         lib.check(self.L.mlvfs_amd_mount_set_dark(self.h, None if dark is None else dark.h), "mount_set_dark")
         self._dark = dark
+
+    def set_flat(self, flat) -> None:
+        """flat: a mlvfs_amd.flat.Flat of the clip's width and height applied to every frame after the dark frame and before any other
+        stage (None clears); refused once a frame was served.  It must stay open while the Mount lives."""
+        lib.check(self.L.mlvfs_amd_mount_set_flat(self.h, None if flat is None else flat.h), "mount_set_flat")
+        self._flat = flat
 
     def dng_size(self, index: int = 0) -> int:
         from . import abi
