@@ -693,6 +693,55 @@ int  mlvfs_amd_mount_set_flat(void *mount, const mlvfs_amd_flat_t *flat);
 int  mlvfs_amd_mlv_transcode_cal(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark,
                                  const mlvfs_amd_flat_t *flat, int batch_frames, int io_threads, long long stats[4]);
 
+/* -- half-size Bayer proxies (csrc/k_proxy.hip, csrc/mount.cpp) -------------------------------------------------- */
+/* A proxy: the frame the mount serves, binned 2x2 within each colour of the CFA, so that a quarter of the pixels remain and the file is
+ * still raw.  Integer arithmetic only; the reference has no such stage.  A W x H frame with W >= 4 and H >= 4 becomes W' x H':
+ *     W' = 2 * floor(W / 4)        H' = 2 * floor(H / 4)
+ * columns 4 * floor(W / 4) .. W - 1 and rows 4 * floor(H / 4) .. H - 1 are never read.  H' is even, so the lossless path always
+ * takes its 2W' x H'/2 form.  Output pixel (Y, X) has the CFA parity py = Y & 1, px = X & 1 and is the rounded mean of the four
+ * pixels of that parity inside its 4x4 block:
+ *     y0 = 4 * (Y >> 1) + py        x0 = 4 * (X >> 1) + px
+ *     out(Y, X) = (in(y0, x0) + in(y0, x0 + 2) + in(y0 + 2, x0) + in(y0 + 2, x0 + 2) + 2) >> 2
+ * exact for every 16-bit input (the sum takes 18 bits).  CFA pattern, black level, white level and bit depth stay the frame's.
+ * It is the LAST stage: after chroma smoothing and stripes, on the frame mlvfs_amd_mount_dng would have served; dark frame, flat
+ * field, bad-pixel map, stripe coefficients, dual ISO and deflicker all work at full size, in serve order, as without a proxy.
+ * A dual-ISO clip served unconverted (dual_iso = 0) has its two ISOs mixed: rows y0 and y0 + 2 differ in ISO.  Nothing is done
+ * about that.
+ * The proxy file's first 65536 bytes are the header mlvfs_amd_mount_dng writes for the frame in its final state (levels x4 after a
+ * conversion, exposure_bias after deflicker) but for the value fields of these tags -- all of fixed size, so every other byte keeps
+ * its offset.  With lo(v) = 2 * ceil(v / 4), hi(v, lim) = min(2 * floor(v / 4), lim) and (x1, y1, x2, y2) = raw_info.active_area as
+ * the full-size header uses it (after its own overwrite rule):
+ *     256 ImageWidth, 257 ImageLength, 278 RowsPerStrip      W', H', H'
+ *     279 StripByteCounts                                    W' * H' * 2, or the stream's length under Compression 7
+ *     50719 DefaultCropOrigin                                (lo(ox), lo(oy))
+ *     50720 DefaultCropSize                                  (max(hi(x2, W') - lo(x1), 0), max(hi(y2, H') - lo(y1), 0))
+ *     50829 ActiveArea (top, left, bottom, right)            lo(top), lo(left), hi(bottom, H'), hi(right, W')
+ *     41486 / 41487 FocalPlaneX/YResolution                  the same numerators, denominators x 2
+ * DefaultScale, the 5:3 and "x3 below 2000 columns" decisions, the levels and every other tag are the FULL-SIZE frame's.           */
+/* W', H' of a width x height frame.  Host code.  MLVFS_AMD_ERR_ARG: a null pointer, factor != 2, a size below 4, 2^27 pixels or more. */
+int    mlvfs_amd_proxy_geom(int width, int height, int factor, int *pw, int *ph);
+/* nframes frames of width x height 16-bit pixels `stride` bytes apart -> their proxies, W' x H' pixels each (rows W' * 2 bytes apart),
+ * out_stride bytes apart.  Bytes between frames and behind W' * H' * 2 are not touched.  Not in place.  Asynchronous on `stream`;
+ * every check happens before any device work: a null pointer, a size below 4 or of 2^27 pixels and more, a negative frame count,
+ * odd addresses or strides, strides smaller than a frame (with more than one frame), source and destination ranges that overlap are
+ * MLVFS_AMD_ERR_ARG.  width a multiple of 16 with both bases and both strides 16-byte aligned takes the fast form (k_bin2_x16: a lane
+ * reads 16 pixels of each of a block row's four rows and writes 8 pixels to each of two rows), anything else one output pixel per lane. */
+int    mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int height, void *d_out, size_t out_stride, int nframes,
+                          void *stream);
+/* The proxy file's header as defined above; stream_bytes = 0: uncompressed (dng_get_header_data's tags 259 and 279 rule), else
+ * mlvfs_amd_dng_header_lossless's.  Rewrites raw_info.active_area like dng_get_header_data.  Host code.  Returns 0 and writes
+ * nothing for a null pointer, factor != 2 or a frame below 4x4 (mlvfs_amd_last_error).                                           */
+size_t mlvfs_amd_dng_header_proxy(struct frame_headers *frame_headers, uint8_t *output_buffer, off_t offset, size_t max_size,
+                                  double fps_override, const char *mlv_basename, int factor, uint32_t stream_bytes);
+/* factor 2: the handle serves proxies -- mlvfs_amd_mount_dng files of 65536 + W' * H' * 2 bytes, mlvfs_amd_mount_dng_lossless the
+ * binned frames as 2W' x H'/2 streams with the sizes, the cap and the fallback of the proxy file; results[], the serve-order state
+ * and every stage in front of the binning are untouched.  out_stride of both calls may then be anything from the proxy file's size
+ * up.  factor 1: off (the default), byte for byte and launch for launch.  MLVFS_AMD_ERR_ARG: a null handle, another factor, a handle
+ * that has served a frame, a clip whose first frame is smaller than 4x4.                                                          */
+int    mlvfs_amd_mount_set_proxy(void *mount, int factor);
+/* bytes of file `index` as this handle serves it uncompressed (dng_get_size, or the proxy file's size); 0: no such frame */
+size_t mlvfs_amd_mount_dng_size(const void *mount, int index);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):

@@ -276,6 +276,15 @@ int launch_mlv_pack_shift(void *d_frames, size_t stride, void *d_packed, size_t 
                           hipStream_t stream);
 int launch_mlv_tile_shift(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int d, int nframes, hipStream_t stream);
 void preload_k_mlvpack();
+// half-size Bayer proxies (k_proxy.hip): W' x H' of a w x h frame, false below 4x4 and from 2^27 pixels on; the binning pass
+inline bool proxy_geom(int w, int h, int *pw, int *ph)
+{
+    if (w < 4 || h < 4 || (uint64_t)w * (uint64_t)h >= (1u << 27)) return false;
+    *pw = 2 * (w / 4);
+    *ph = 2 * (h / 4);
+    return true;
+}
+int launch_bin2(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int nframes, hipStream_t stream);
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

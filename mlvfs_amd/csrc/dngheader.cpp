@@ -30,6 +30,8 @@
 
 #include "mlvfs_amd.h"
 
+namespace mlv { void set_error(const char *fmt, ...); }
+
 namespace {
 
 constexpr size_t kHeaderBytes = 65536;
@@ -319,9 +321,15 @@ private:
 
 uint8_t bcd(int v) { return (uint8_t)(((v / 10) << 4) | (v % 10)); }
 
+// the proxy header's rounding of a full-size coordinate (include/mlvfs_amd.h): lo(v) = 2 * ceil(v / 4), hi(v, lim) = min(2 * floor(v / 4), lim)
+int32_t proxy_lo(int32_t v) { return 2 * ((v + 3) >> 2); }
+int32_t proxy_hi(int32_t v, int32_t lim) { const int32_t r = 2 * (v >> 2); return r < lim ? r : lim; }
+
 // compression / strip_bytes: TIFF tags 259 and 279 -- 1 and the image's size (dng.c), or 7 and the length of the lossless-JPEG stream
+// proxy: the header of the frame binned to 2 * (xRes / 4) x 2 * (yRes / 4) -- sizes, crop, active area and focal-plane resolution
+// follow the binning, every decision (pixel aspect, the x3 / x5 factors) and every other tag stays the full-size frame's
 size_t header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offset, size_t max_size, double fps_override, const char *mlv_basename,
-                   uint32_t compression, uint32_t strip_bytes)
+                   uint32_t compression, uint32_t strip_bytes, bool proxy = false)
 {
     std::vector<uint8_t> header(kHeaderBytes, 0);
     struct raw_info &ri = fh->rawi_hdr.raw_info;
@@ -352,6 +360,28 @@ size_t header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offse
     if (fh->rawi_hdr.xRes < ri.active_area.x2 || fh->rawi_hdr.yRes < ri.active_area.y2) {
         ri.active_area.x1 = 0; ri.active_area.y1 = 0;
         ri.active_area.x2 = fh->rawi_hdr.xRes; ri.active_area.y2 = fh->rawi_hdr.yRes;
+    }
+
+    // what the binning changes: fixed-size value fields only
+    int32_t img_w = fh->rawi_hdr.xRes, img_h = fh->rawi_hdr.yRes;
+    int32_t crop_origin[2] = { ri.crop.origin[0], ri.crop.origin[1] };
+    int32_t crop_size[2] = { ri.active_area.x2 - ri.active_area.x1, ri.active_area.y2 - ri.active_area.y1 };
+    int32_t active[4] = { ri.dng_active_area[0], ri.dng_active_area[1], ri.dng_active_area[2], ri.dng_active_area[3] };
+    if (proxy) {
+        img_w = 2 * (img_w / 4);
+        img_h = 2 * (img_h / 4);
+        crop_origin[0] = proxy_lo(crop_origin[0]);
+        crop_origin[1] = proxy_lo(crop_origin[1]);
+        crop_size[0] = proxy_hi(ri.active_area.x2, img_w) - proxy_lo(ri.active_area.x1);
+        crop_size[1] = proxy_hi(ri.active_area.y2, img_h) - proxy_lo(ri.active_area.y1);
+        if (crop_size[0] < 0) crop_size[0] = 0;
+        if (crop_size[1] < 0) crop_size[1] = 0;
+        active[0] = proxy_lo(active[0]);
+        active[1] = proxy_lo(active[1]);
+        active[2] = proxy_hi(active[2], img_h);
+        active[3] = proxy_hi(active[3], img_w);
+        fpx[1] *= 2;
+        fpy[1] *= 2;
     }
 
     int32_t rate[2] = { (int32_t)fh->file_hdr.sourceFpsNom, (int32_t)fh->file_hdr.sourceFpsDenom };
@@ -388,8 +418,8 @@ size_t header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offse
 
     Tiff t(header.data(), 41, 11);
     t.inl(254, LONG, 1, 0);                                             // NewSubFileType: main image
-    t.inl(256, LONG, 1, fh->rawi_hdr.xRes);                             // ImageWidth
-    t.inl(257, LONG, 1, fh->rawi_hdr.yRes);                             // ImageLength
+    t.inl(256, LONG, 1, img_w);                                         // ImageWidth
+    t.inl(257, LONG, 1, img_h);                                         // ImageLength
     t.inl(258, SHORT, 1, 16);                                           // BitsPerSample
     t.inl(259, SHORT, 1, compression);                                  // Compression: 1 none, 7 lossless JPEG
     t.inl(262, SHORT, 1, 32803);                                        // PhotometricInterpretation: CFA
@@ -399,7 +429,7 @@ size_t header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offse
     t.inl(273, LONG, 1, (uint32_t)kHeaderBytes);                        // StripOffsets
     t.inl(274, SHORT, 1, 1);                                            // Orientation
     t.inl(277, SHORT, 1, 1);                                            // SamplesPerPixel
-    t.inl(278, SHORT, 1, fh->rawi_hdr.yRes);                            // RowsPerStrip
+    t.inl(278, SHORT, 1, img_h);                                        // RowsPerStrip
     t.inl(279, LONG, 1, strip_bytes);                                   // StripByteCounts
     t.inl(284, SHORT, 1, 1);                                            // PlanarConfiguration
     t.ascii(305, "MLVFS");                                              // Software (mlvfs.h:65)
@@ -412,9 +442,8 @@ size_t header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offse
     t.inl(50714, LONG, 1, (uint32_t)ri.black_level);                    // BlackLevel
     t.inl(50717, LONG, 1, (uint32_t)ri.white_level);                    // WhiteLevel
     t.words(50718, RATIONAL, 2, scale, 4);                              // DefaultScale
-    t.inl(50719, SHORT, 2, ((uint32_t)(uint16_t)ri.crop.origin[1] << 16) | (uint16_t)ri.crop.origin[0]);       // DefaultCropOrigin
-    t.inl(50720, SHORT, 2, ((uint32_t)(uint16_t)(ri.active_area.y2 - ri.active_area.y1) << 16) |
-                               (uint16_t)(ri.active_area.x2 - ri.active_area.x1));                                  // DefaultCropSize
+    t.inl(50719, SHORT, 2, ((uint32_t)(uint16_t)crop_origin[1] << 16) | (uint16_t)crop_origin[0]);             // DefaultCropOrigin
+    t.inl(50720, SHORT, 2, ((uint32_t)(uint16_t)crop_size[1] << 16) | (uint16_t)crop_size[0]);                 // DefaultCropSize
     t.words(50721, SRATIONAL, 9, matrix[0], 18);                        // ColorMatrix1
     t.words(50722, SRATIONAL, 9, matrix[1], 18);                        // ColorMatrix2
     t.words(50728, RATIONAL, 3, neutral, 6);                            // AsShotNeutral
@@ -422,7 +451,7 @@ size_t header_data(struct frame_headers *fh, uint8_t *output_buffer, off_t offse
     t.ascii(50735, serial);                                             // CameraSerialNumber
     t.inl(50778, SHORT, 1, 17);                                         // CalibrationIlluminant1: standard light A
     t.inl(50779, SHORT, 1, 21);                                         // CalibrationIlluminant2: D65
-    t.words(50829, LONG, 4, ri.dng_active_area, 4);                     // ActiveArea
+    t.words(50829, LONG, 4, active, 4);                                 // ActiveArea
     t.words(50964, SRATIONAL, 9, matrix[2], 18);                        // ForwardMatrix1
     t.words(50965, SRATIONAL, 9, matrix[3], 18);                        // ForwardMatrix2
     t.bytes8(51043, timecode);                                          // TimeCodes (CinemaDNG)
@@ -470,4 +499,16 @@ extern "C" size_t mlvfs_amd_dng_header_lossless(struct frame_headers *fh, uint8_
                                                 double fps_override, const char *mlv_basename, uint32_t stream_bytes)
 {
     return header_data(fh, output_buffer, offset, max_size, fps_override, mlv_basename, 7, stream_bytes);
+}
+
+// The header of a frame's half-size proxy (include/mlvfs_amd.h, "half-size Bayer proxies"): the frame's own 65536 bytes but for the
+// value fields of tags 256, 257, 278, 279, 50719, 50720, 50829, 41486 and 41487 (and 259 with a stream).
+extern "C" size_t mlvfs_amd_dng_header_proxy(struct frame_headers *fh, uint8_t *output_buffer, off_t offset, size_t max_size,
+                                             double fps_override, const char *mlv_basename, int factor, uint32_t stream_bytes)
+{
+    if (!fh || !output_buffer) { mlv::set_error("dng_header_proxy: null argument"); return 0; }
+    int pw, ph;
+    if (mlvfs_amd_proxy_geom(fh->rawi_hdr.xRes, fh->rawi_hdr.yRes, factor, &pw, &ph) != MLVFS_AMD_OK) return 0;
+    return header_data(fh, output_buffer, offset, max_size, fps_override, mlv_basename, stream_bytes ? 7 : 1,
+                       stream_bytes ? stream_bytes : (uint32_t)pw * (uint32_t)ph * 2u, true);
 }

@@ -16,6 +16,10 @@
 //
 // mlvfs_amd_mount_dng_lossless serves the same frames through the same stages; only the last step differs: the batch's final frames
 // are encoded where they lie (lje_encode_batch, k_lj92enc.hip) and their streams, not their pixels, cross the link.
+//
+// mlvfs_amd_mount_set_proxy(2): one stage more behind the last, the 2x2 binning within each CFA colour (k_proxy.hip).  Each final frame
+// is binned into its other slot (O when it lies in F, and the reverse -- free by then); the download, the encoder and the headers take
+// the binned frame and its geometry.  Nothing in front of it knows.
 #include "clip.h"
 #include "lj92enc.h"
 
@@ -37,7 +41,8 @@ struct Mount {
     int32_t coef[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     const mlvfs_amd_dark_t *dark = nullptr;  // stage 0 (mlvfs_amd_mount_set_dark): subtracted inside the reader's load
     const mlvfs_amd_flat_t *flat = nullptr;  // stage 0b (mlvfs_amd_mount_set_flat): the gain, in the same pass of the load
-    bool served = false;                     // a call has reached the device: the dark frame and the flat field stay what they are
+    bool served = false;                     // a call has reached the device: the dark frame, the flat field and the proxy stay what they are
+    int proxy = 1;                           // mlvfs_amd_mount_set_proxy: 2 = the served frames are binned to half size
     int device = -1;
     void *d_frames = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_bits = nullptr;
     size_t frames_bytes = 0, scratch_bytes = 0, bits_bytes = 0;   // d_bits: the encoder's bit streams, sized from a batch's histograms
@@ -118,11 +123,11 @@ size_t o_pn_bytes(const mlvfs_amd_mount_opts_t &o, int w, int h, int batch)
 
 // The batch's final frames as lossless-JPEG streams: encoded where they lie, one copy of lengths and states, then the streams.
 // hdr_max[k]: the max_size the frame's header was last written with.  A frame that is not to be served compressed gets its pixels.
+// w x h: the frames at final_at as they are served -- the clip's size, or with a proxy set the binned one
 int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at,
-                   const std::vector<size_t> &hdr_max, uint8_t *h_out, size_t out_stride, const Lossless &ll)
+                   const std::vector<size_t> &hdr_max, uint8_t *h_out, size_t out_stride, const Lossless &ll, int w, int h)
 {
     hipStream_t s = c->stream;
-    const int w = fh[0].rawi_hdr.xRes, h = fh[0].rawi_hdr.yRes;
     const size_t img = (size_t)w * h * 2, hdr = dng_get_header_size();
     const bool pairs = !(h & 1);                                       // 2w x h/2: the row above is the same colour
     const int jw = pairs ? 2 * w : w, jh = pairs ? h / 2 : h;
@@ -148,7 +153,8 @@ int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstr
             continue;
         }
         ll.sizes[k] = hdr + res[k].length;
-        (void)mlvfs_amd_dng_header_lossless(&fh[k], file, 0, hdr_max[k], m.o.fps, m.basename.data(), res[k].length);
+        if (m.proxy == 2) (void)mlvfs_amd_dng_header_proxy(&fh[k], file, 0, hdr_max[k], m.o.fps, m.basename.data(), 2, res[k].length);
+        else (void)mlvfs_amd_dng_header_lossless(&fh[k], file, 0, hdr_max[k], m.o.fps, m.basename.data(), res[k].length);
         MLV_HIP(hipMemcpyAsync(file + hdr, d_streams + k * dstride, res[k].length, hipMemcpyDeviceToHost, s));
     }
     MLV_HIP(hipStreamSynchronize(s));
@@ -172,7 +178,12 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
         if (rc) return rc;
         for (int k = 0; k < n; k++) deflicker_bias(o.deflicker, fh[k].rawi_hdr.raw_info.black_level, med[k], fh[k].rawi_hdr.raw_info.exposure_bias);
     }
-    for (int k = 0; k < n; k++) (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, hdr, o.fps, m.basename.data());    // main.c:944
+    // the frame's header: the proxy's where one is served, with the max_size the full-size write has
+    auto write_header = [&](int k, size_t max_size) {
+        if (m.proxy == 2) (void)mlvfs_amd_dng_header_proxy(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data(), 2, 0);
+        else (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data());
+    };
+    for (int k = 0; k < n; k++) write_header(k, hdr);                  // main.c:944
     // pattern noise (main.c:946-949): runs of one white level
     if (o.fix_pattern_noise && w >= 2 && h >= 2 && !(w & 1) && !(h & 1)) {
         for (int k0 = 0, k1; k0 < n; k0 = k1) {
@@ -216,7 +227,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
         if (conv[k] != 1) continue;
         fh[k].rawi_hdr.raw_info.black_level *= 4;                      // hdr.c:223-224, 1951-1952
         fh[k].rawi_hdr.raw_info.white_level *= 4;
-        (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, img, o.fps, m.basename.data());   // main.c:962-966
+        write_header(k, img);                                          // main.c:962-966
         hdr_max[k] = img;
     }
     // frames that were not converted: focus pixels, bad pixels (main.c:967-975), in serve order
@@ -273,8 +284,22 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             if (rc) return rc;
         }
     }
-    if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll);
-    for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], img, hipMemcpyDeviceToHost, s));
+    // the proxy: the last stage, each final frame binned into its other slot, runs of frames that lie on one side in one launch
+    int sw = w, sh = h;
+    if (m.proxy == 2) {
+        if (!proxy_geom(w, h, &sw, &sh)) { set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+        for (int k0 = 0, k1; k0 < n; k0 = k1) {
+            const bool in_f = final_at[k0] == F + k0 * dstride;
+            for (k1 = k0 + 1; k1 < n && (final_at[k1] == F + k1 * dstride) == in_f; k1++) {}
+            uint8_t *dst = (in_f ? O : F) + k0 * dstride;
+            rc = launch_bin2(final_at[k0], dstride, dst, dstride, w, h, k1 - k0, s);
+            if (rc) return rc;
+            for (int k = k0; k < k1; k++) final_at[k] = dst + (size_t)(k - k0) * dstride;
+        }
+    }
+    if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll, sw, sh);
+    const size_t served = (size_t)sw * sh * 2;
+    for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
     MLV_HIP(hipStreamSynchronize(s));
     return MLVFS_AMD_OK;
 }
@@ -340,6 +365,74 @@ int mlvfs_amd_mount_set_flat(void *mount, const mlvfs_amd_flat_t *flat)
     return MLVFS_AMD_OK;
 }
 
+int mlvfs_amd_mount_set_proxy(void *mount, int factor)
+{
+    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (factor != 1 && factor != 2) { set_error("mount: a proxy factor of %d (1: off, 2: half size)", factor); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (m.served) { set_error("mount: the handle has served frames already: the proxy cannot change any more"); return MLVFS_AMD_ERR_ARG; }
+    frame_headers fh;
+    if (factor == 2 && mlvfs_amd_mlv_frame_count(m.reader) > 0) {
+        if (!mlvfs_amd_mlv_frame_headers(m.reader, 0, &fh)) { set_error("mount: frame 0 has no usable headers"); return MLVFS_AMD_ERR_ARG; }
+        int pw, ph;
+        if (!proxy_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, &pw, &ph)) {
+            set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
+            return MLVFS_AMD_ERR_ARG;
+        }
+    }
+    m.proxy = factor;
+    return MLVFS_AMD_OK;
+}
+
+size_t mlvfs_amd_mount_dng_size(const void *mount, int index)
+{
+    if (!mount) { set_error("mount: null argument"); return 0; }
+    Mount &m = *(Mount *)mount;
+    frame_headers fh;
+    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
+    int proxy;
+    {
+        std::lock_guard<std::mutex> lk(m.mu);
+        proxy = m.proxy;
+    }
+    if (proxy != 2) return dng_get_size(&fh);
+    int pw, ph;
+    if (!proxy_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, &pw, &ph)) { set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
+    return dng_get_header_size() + (size_t)pw * ph * 2;
+}
+
+int mlvfs_amd_proxy_geom(int width, int height, int factor, int *pw, int *ph)
+{
+    if (!pw || !ph) { set_error("proxy_geom: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (factor != 2) { set_error("proxy_geom: a factor of %d (only 2 is built)", factor); return MLVFS_AMD_ERR_ARG; }
+    int w2, h2;
+    if (!proxy_geom(width, height, &w2, &h2)) { set_error("proxy_geom: %dx%d not supported (4x4 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
+    *pw = w2;
+    *ph = h2;
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int height, void *d_out, size_t out_stride, int nframes, void *stream)
+{
+    if (!d_frames || !d_out) { set_error("bin2: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("bin2: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    int pw, ph;
+    if (!proxy_geom(width, height, &pw, &ph)) { set_error("bin2: %dx%d not supported (4x4 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)pw * ph * 2;
+    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_out & 1) || (nframes > 1 && (stride < img || out_stride < pimg || ((stride | out_stride) & 1)))) {
+        set_error("bin2: strides %zu / %zu too small or odd", stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
+    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
+    if (a0 < b1 && b0 < a1) { set_error("bin2: the source and the destination overlap (the binning does not work in place)"); return MLVFS_AMD_ERR_ARG; }
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    return launch_bin2(d_frames, stride, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
+}
+
 // both entry points
 static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
                        int batch_frames, int io_threads, int *results)
@@ -360,12 +453,17 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             set_error("mount: frames of more than one geometry in one call (frame %d)", first + k);
             return MLVFS_AMD_ERR_ARG;
         }
-    const size_t size = dng_get_size(&fh[0]);
-    if (out_stride < size) { set_error("mount: out_stride %zu smaller than a .dng file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     if (batch_frames <= 0) batch_frames = 8;
     batch_frames = std::min(batch_frames, count);
     LibcRandGuard rand_guard;                      // HIP code runs: the caller's rand() stream stays out of its reach (rand_mode 0 draws from it)
     std::lock_guard<std::mutex> lk(m.mu);
+    size_t size = dng_get_size(&fh[0]);
+    if (m.proxy == 2) {                                                // the proxy file: anything from its size up is room enough
+        int pw, ph;
+        if (!proxy_geom(w, h, &pw, &ph)) { set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+        size = dng_get_header_size() + (size_t)pw * ph * 2;
+    }
+    if (out_stride < size) { set_error("mount: out_stride %zu smaller than a .dng file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     if (m.dark && !darkframe_fits(m.dark, w, h, bpp)) { set_error("mount: the dark frame does not have the geometry of frame %d (%dx%d at %d bits)", first, w, h, bpp); return MLVFS_AMD_ERR_ARG; }
     if (m.flat && !flatfield_fits(m.flat, w, h)) { set_error("mount: the flat field does not have the geometry of frame %d (%dx%d)", first, w, h); return MLVFS_AMD_ERR_ARG; }
     ThreadCtx *c = thread_ctx();

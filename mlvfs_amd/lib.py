@@ -66,6 +66,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_rawi_set_bits", "mlvfs_amd_repack_dev", "mlvfs_amd_mlv_transcode_bits",
     "mlvfs_amd_flat_create", "mlvfs_amd_flat_from_clip", "mlvfs_amd_flat_info", "mlvfs_amd_flat_gain", "mlvfs_amd_flat_destroy",
     "mlvfs_amd_flat_apply_dev", "mlvfs_amd_mount_set_flat", "mlvfs_amd_mlv_transcode_cal",
+    "mlvfs_amd_proxy_geom", "mlvfs_amd_bin2_dev", "mlvfs_amd_dng_header_proxy", "mlvfs_amd_mount_set_proxy", "mlvfs_amd_mount_dng_size",
 ]
 
 
@@ -252,6 +253,11 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_flat_apply_dev", i, [vp, vp, gp, vp, sz, i, vp])
     sig("mlvfs_amd_mount_set_flat", i, [vp, vp])
     sig("mlvfs_amd_mlv_transcode_cal", i, [vp, C.c_char_p, i, i, vp, vp, i, i, C.POINTER(C.c_longlong)])
+    sig("mlvfs_amd_proxy_geom", i, [i, i, i, C.POINTER(i), C.POINTER(i)])
+    sig("mlvfs_amd_bin2_dev", i, [vp, sz, i, i, vp, sz, i, vp])
+    sig("mlvfs_amd_dng_header_proxy", sz, [fhp, vp, C.c_long, sz, C.c_double, C.c_char_p, i, C.c_uint32])
+    sig("mlvfs_amd_mount_set_proxy", i, [vp, i])
+    sig("mlvfs_amd_mount_dng_size", sz, [vp, i])
     _lib = L
     return L
 

@@ -6,6 +6,9 @@
 
         small, flags = m.dng_lossless(16, 16)   # the same files with their pixels as one lossless-JPEG stream each
 
+    Mount(r, opt, proxy=2) serves half-size Bayer proxies: the same frames after every stage, binned 2x2 within each CFA colour on the
+    GPU (include/mlvfs_amd.h, "half-size Bayer proxies"), a quarter of the bytes per file.
+
 Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
 """
 from __future__ import annotations
@@ -28,10 +31,11 @@ def mount_opts(opt: MlvfsOptions, deflicker: int = 0, fps: float = 0.0, rand_mod
 class Mount:
     """reader: an open mlvfile.MlvReader (or a raw mlvfs_amd_mlv_open handle); it must stay open while the Mount lives.
     dark: a mlvfs_amd.dark.Dark to subtract from every frame (stage 0), or None.
-    flat: a mlvfs_amd.flat.Flat whose gain corrects every frame directly after that (stage 0b), or None."""
+    flat: a mlvfs_amd.flat.Flat whose gain corrects every frame directly after that (stage 0b), or None.
+    proxy: 1 full-size files, 2 half-size Bayer proxies (the last stage)."""
 
     def __init__(self, reader, opt: MlvfsOptions, deflicker: int = 0, fps: float = 0.0, basename: str = "", rand_mode: int = 1, dark=None,
-                 flat=None):
+                 flat=None, proxy: int = 1):
         self.L = lib.load()
         self._reader = reader
         handle = getattr(reader, "h", reader)
@@ -41,11 +45,14 @@ class Mount:
             raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
         self.frame_count = self.L.mlvfs_amd_mlv_frame_count(handle)
         self._dark = self._flat = None
+        self.proxy = 1
         try:
             if dark is not None:
                 self.set_dark(dark)
             if flat is not None:
                 self.set_flat(flat)
+            if proxy != 1:
+                self.set_proxy(proxy)
         except lib.MlvfsAmdError:
             self.close()
             raise
@@ -62,12 +69,18 @@ class Mount:
         lib.check(self.L.mlvfs_amd_mount_set_flat(self.h, None if flat is None else flat.h), "mount_set_flat")
         self._flat = flat
 
+    def set_proxy(self, factor: int) -> None:
+        """factor 2: every frame is served binned to half size, 2 * (W // 4) x 2 * (H // 4), after all other stages; 1: off.  Refused
+        once a frame was served."""
+        lib.check(self.L.mlvfs_amd_mount_set_proxy(self.h, factor), "mount_set_proxy")
+        self.proxy = factor
+
     def dng_size(self, index: int = 0) -> int:
-        from . import abi
-        fh = abi.FrameHeaders()
-        if not self.L.mlvfs_amd_mlv_frame_headers(getattr(self._reader, "h", self._reader), index, C.byref(fh)):
-            raise lib.MlvfsAmdError(f"frame {index} has no usable headers")
-        return int(self.L.dng_get_size(C.byref(fh)))
+        """bytes of file `index` as this handle serves it uncompressed (the proxy file's with a proxy set)"""
+        size = int(self.L.mlvfs_amd_mount_dng_size(self.h, index))
+        if not size:
+            raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
+        return size
 
     def dng(self, first: int, count: int, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None) -> np.ndarray:
         """Frames first .. first + count - 1 as .dng files: a (count, dng_size) uint8 array."""
