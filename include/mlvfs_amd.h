@@ -742,6 +742,70 @@ int    mlvfs_amd_mount_set_proxy(void *mount, int factor);
 /* bytes of file `index` as this handle serves it uncompressed (dng_get_size, or the proxy file's size); 0: no such frame */
 size_t mlvfs_amd_mount_dng_size(const void *mount, int index);
 
+/* -- rendered half-size sRGB frames (csrc/k_render.hip, csrc/dngheader.cpp, csrc/mount.cpp) --------------------------- */
+/* A rendering: the frame the mount serves, developed to 8-bit sRGB at half size, as a TIFF any viewer opens.  The definition is this
+ * project's (the reference has no such stage), in integers only, so that it has a byte-exact oracle (mlvfs_amd/render.py).
+ * Geometry.  A W x H frame with W, H >= 2 becomes W' x H' RGB pixels, W' = floor(W / 2), H' = floor(H / 2).  An odd last column or
+ * row is never read.  The CFA is RGGB, as the header always declares it.  The whole frame is rendered: no crop to the active area.
+ * Input.  The frame mlvfs_amd_mount_dng would have served, after every stage, at full size, with the BlackLevel and WhiteLevel of the
+ * header written for that frame in its final state (the x4 levels after a dual-ISO conversion).  range = max(white - black, 1).
+ * Per output pixel (Y, X):
+ *   1. superpixel   c0 = in(2Y, 2X)    c1 = (in(2Y, 2X + 1) + in(2Y + 1, 2X) + 1) >> 1    c2 = in(2Y + 1, 2X + 1)
+ *                   c'_j = max(c_j - black, 0)
+ *   2. balance, exposure, normalisation to 16 bits
+ *                   n_j = min((c'_j * A_j + 2048) >> 12, 65535)            the product in 64 bits; the min keeps clipped highlights
+ *                                                                          neutral instead of pink
+ *   3. camera to linear sRGB
+ *                   acc_i = sum_j K[i][j] * n_j                            64 bits, signed
+ *                   t_i = clamp((acc_i + 32768) >> 16, 0, 4095)            the shift is arithmetic: floor
+ *   4. tone         out_i = LUT[t_i]                                       bytes in R, G, B order, rows top down, no padding in a row
+ * Per-frame parameters, computed on the host in exact integer arithmetic (no floating point takes part):
+ *   A_j   from the frame's AsShotNeutral num_j / den_j -- the six integers the header writes in tag 50728 -- and the caller's gain_q8,
+ *         1 .. 65535, 256 is unity:    D = 256 * num_j * range    A_j = floor((2 * 65535 * 4096 * gain_q8 * den_j + D) / (2 * D))
+ *         capped at 2^31 - 1.  If any num_j <= 0 or any den_j <= 0, all three channels take num = den = 1.
+ *   K     from the camera's ForwardMatrix2 FM, nine integers over 10000 (tag 50965; always this matrix, no interpolation between
+ *         illuminants), and the D50-XYZ -> linear-sRGB matrix as integers over 10^7
+ *             S = [[31338561, -16168667, -4906146], [-9787684, 19161415, 334540], [719453, -2289914, 14052427]]
+ *         P[i][j] = sum_k S[i][k] * FM[k][j]      K[i][j] = floor((2 * 4096 * P[i][j] + 10^11) / (2 * 10^11)), floor towards -inf
+ *   LUT   the 8-bit sRGB curve on 12 bits, LUT[t] = round(255 * oetf(t / 4095)), oetf(x) = 12.92 x for x <= 0.0031308, else
+ *         1.055 x^(1 / 2.4) - 0.055: 4096 constant bytes (csrc/srgb_lut12.h = tests/golden/srgb_lut12.bin), never computed at run time.
+ * The deflicker's exposure_bias is NOT applied: gain_q8 is the only exposure control.
+ * The file: a baseline little-endian TIFF with one strip -- ImageWidth W', ImageLength H', BitsPerSample 8 8 8, Compression 1,
+ * PhotometricInterpretation 2, StripOffsets = the header's size, Orientation 1, SamplesPerPixel 3, RowsPerStrip H', StripByteCounts
+ * 3 W' H', PlanarConfiguration 1, Software "MLVFS" -- of mlvfs_amd_rgb_header_size() + 3 W' H' bytes.                              */
+/* W', H' of a width x height frame.  Host code.  MLVFS_AMD_ERR_ARG: a null pointer, a size below 2, 2^27 pixels or more. */
+int    mlvfs_amd_rgb_geom(int width, int height, int *pw, int *ph);
+/* bytes of the file's header: fixed (256), a multiple of 16 */
+size_t mlvfs_amd_rgb_header_size(void);
+/* the tone table.  Host code. */
+int    mlvfs_amd_rgb_lut(uint8_t out[4096]);
+/* out = black, A[3], K[9] (K row by row) for a frame with these headers: the levels are raw_info's as passed in, the neutral is what
+ * dng_get_header_data writes for them, the matrix the camera's (cameraName; unknown cameras use the first row, as the header does).
+ * Host code.  MLVFS_AMD_ERR_ARG (out untouched): a null pointer, gain_q8 outside 1 .. 65535.                                        */
+int    mlvfs_amd_rgb_params(const struct frame_headers *frame_headers, int gain_q8, int32_t out[13]);
+/* the header of a pw x ph file into out[0 .. cap): returns its size, or 0 and writes nothing for a null pointer, pw or ph below 1,
+ * 2^25 pixels or more, cap below the header's size (mlvfs_amd_last_error).  Host code.                                             */
+size_t mlvfs_amd_rgb_header(int pw, int ph, uint8_t *out, size_t cap);
+/* nframes frames of width x height 16-bit pixels `stride` bytes apart -> their renderings, 3 W' H' bytes each, out_stride bytes apart,
+ * frame k with the 13 parameters d_params[13 k ..] (device memory, as mlvfs_amd_rgb_params yields them).  Bytes between frames and
+ * behind 3 W' H' are not touched.  Not in place.  Asynchronous on `stream`; every check happens before any device work: a null
+ * pointer, a size below 2 or of 2^27 pixels and more, a negative frame count, an odd source address or stride, parameters off a
+ * 4-byte boundary, strides smaller than a frame (with more than one frame), a destination that overlaps the source or the parameters
+ * are MLVFS_AMD_ERR_ARG.  width a multiple of 16 with source base and stride 16-byte and destination base and stride 8-byte aligned
+ * takes the fast form (k_render2_x16: a lane reads 16 pixels of each of a superpixel row's two rows and writes 8 pixels, 24 bytes);
+ * anything else one output pixel per lane (k_render2_generic).                                                                     */
+int    mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                             size_t out_stride, int nframes, void *stream);
+/* mlvfs_amd_mount_dng's frames first .. first + count - 1, through the same stages, the same serve-order state and the same
+ * results[], as rendered TIFF files out_stride bytes apart in h_out: header + pixels, out_stride anything from the file's size up.
+ * Each frame's parameters come from its headers in their final state.  Only the 3 W' H' bytes of a frame cross the link.  May be
+ * interleaved with mlvfs_amd_mount_dng and mlvfs_amd_mount_dng_lossless on one handle.  MLVFS_AMD_ERR_ARG besides mlvfs_amd_mount_dng's:
+ * gain_q8 outside 1 .. 65535, a handle with mlvfs_amd_mount_set_proxy(2), frames below 2x2.                                         */
+int    mlvfs_amd_mount_rgb(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int batch_frames,
+                           int io_threads, int *results);
+/* bytes of file `index` as mlvfs_amd_mount_rgb serves it; 0: no such frame, or one below 2x2 */
+size_t mlvfs_amd_mount_rgb_size(const void *mount, int index);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):

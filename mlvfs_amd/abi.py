@@ -87,6 +87,10 @@ StripesCorrection._fields_ = [("next", C.POINTER(StripesCorrection)), ("mlv_file
                               ("correction_needed", C.c_int), ("coeffficients", C.c_int * 8)]
 
 
+# mlvfs_amd_rgb_params' out[13] (include/mlvfs_amd.h, "rendered half-size sRGB frames"): black, A[3], K[9]
+RgbParams = i32 * 13
+
+
 def make_frame_headers(w, h, bpp=14, black=2048, white=15000, guid=0, pan=(0, 0), camera=0,
                        raw_size=None) -> FrameHeaders:
     """Fill the fields the hot path reads."""

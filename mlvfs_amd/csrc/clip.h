@@ -285,6 +285,17 @@ inline bool proxy_geom(int w, int h, int *pw, int *ph)
     return true;
 }
 int launch_bin2(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int nframes, hipStream_t stream);
+// rendered half-size sRGB frames (k_render.hip): W' x H' of a w x h frame, false below 2x2 and from 2^27 pixels on; the developing pass
+// (d_params: mlvfs_amd_rgb_params' 13 int32 per frame)
+inline bool rgb_geom(int w, int h, int *pw, int *ph)
+{
+    if (w < 2 || h < 2 || (uint64_t)w * (uint64_t)h >= (1u << 27)) return false;
+    *pw = w / 2;
+    *ph = h / 2;
+    return true;
+}
+int launch_render2(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
+                   hipStream_t stream);
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

@@ -23,12 +23,14 @@
 //   * the returned size is min(max_size, 65536) whatever `offset` is (dng.c:779).  The reference then copies that many
 //     bytes starting at header + offset, i.e. past the end of its buffer for offset > 0; here bytes past the
 //     header read as zero.  MLVFS itself only ever asks for offset 0 (main.c:944,964).
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "mlvfs_amd.h"
+#include "srgb_lut12.h"
 
 namespace mlv { void set_error(const char *fmt, ...); }
 
@@ -511,4 +513,89 @@ extern "C" size_t mlvfs_amd_dng_header_proxy(struct frame_headers *fh, uint8_t *
     if (mlvfs_amd_proxy_geom(fh->rawi_hdr.xRes, fh->rawi_hdr.yRes, factor, &pw, &ph) != MLVFS_AMD_OK) return 0;
     return header_data(fh, output_buffer, offset, max_size, fps_override, mlv_basename, stream_bytes ? 7 : 1,
                        stream_bytes ? stream_bytes : (uint32_t)pw * (uint32_t)ph * 2u, true);
+}
+
+// ---- rendered half-size sRGB frames (include/mlvfs_amd.h, "rendered half-size sRGB frames"): the host half ------------
+// The per-frame parameters in exact integer arithmetic (__int128: D takes up to 70 bits, the numerator 77), the table and the TIFF
+// header of the served file.  The developing pass itself is k_render.hip.
+namespace {
+
+constexpr size_t kRgbHeaderBytes = 256;
+// D50 XYZ -> linear sRGB, integers over 10^7
+const int64_t kXyzToSrgb[3][3] = { { 31338561, -16168667, -4906146 }, { -9787684, 19161415, 334540 }, { 719453, -2289914, 14052427 } };
+
+__int128 floor_div(__int128 a, __int128 b)          // b > 0; towards -inf
+{
+    const __int128 q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+}  // namespace
+
+extern "C" size_t mlvfs_amd_rgb_header_size(void) { return kRgbHeaderBytes; }
+
+extern "C" int mlvfs_amd_rgb_lut(uint8_t out[4096])
+{
+    if (!out) { mlv::set_error("rgb_lut: null argument"); return MLVFS_AMD_ERR_ARG; }
+    memcpy(out, kSrgbLut12, 4096);
+    return MLVFS_AMD_OK;
+}
+
+extern "C" int mlvfs_amd_rgb_params(const struct frame_headers *fh, int gain_q8, int32_t out[13])
+{
+    if (!fh || !out) { mlv::set_error("rgb_params: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (gain_q8 < 1 || gain_q8 > 65535) { mlv::set_error("rgb_params: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    const struct raw_info &ri = fh->rawi_hdr.raw_info;
+    const Calibration &cal = by_model(kCalibration, (const char *)fh->idnt_hdr.cameraName);
+    int32_t neutral[6];
+    as_shot_neutral(fh->wbal_hdr, cal, neutral);
+    bool usable = true;
+    for (int v : neutral) usable = usable && v > 0;
+    if (!usable)
+        for (int32_t &v : neutral) v = 1;
+    int64_t range = (int64_t)ri.white_level - (int64_t)ri.black_level;
+    if (range < 1) range = 1;
+    int32_t p[13];
+    p[0] = ri.black_level;
+    for (int j = 0; j < 3; j++) {
+        const __int128 D = (__int128)256 * neutral[2 * j] * range;
+        const __int128 a = ((__int128)2 * 65535 * 4096 * gain_q8 * neutral[2 * j + 1] + D) / (2 * D);          // all positive
+        p[1 + j] = a > INT32_MAX ? INT32_MAX : (int32_t)a;
+    }
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            int64_t P = 0;
+            for (int k = 0; k < 3; k++) P += kXyzToSrgb[i][k] * cal.m[3][3 * k + j];                              // ForwardMatrix2, always
+            p[4 + 3 * i + j] = (int32_t)floor_div((__int128)2 * 4096 * P + 100000000000LL, 200000000000LL);
+        }
+    memcpy(out, p, sizeof p);
+    return MLVFS_AMD_OK;
+}
+
+// Baseline little-endian TIFF: 12 entries behind the 8-byte header, BitsPerSample's three shorts at 158, "MLVFS" at 164, zeros up to
+// 256, where the one strip begins.
+extern "C" size_t mlvfs_amd_rgb_header(int pw, int ph, uint8_t *out, size_t cap)
+{
+    if (!out) { mlv::set_error("rgb_header: null argument"); return 0; }
+    if (pw < 1 || ph < 1 || (uint64_t)pw * (uint64_t)ph >= (1u << 25)) { mlv::set_error("rgb_header: %dx%d pixels not supported", pw, ph); return 0; }
+    if (cap < kRgbHeaderBytes) { mlv::set_error("rgb_header: room for %zu bytes, the header takes %zu", cap, kRgbHeaderBytes); return 0; }
+    uint8_t b[kRgbHeaderBytes] = { 0 };
+    const struct { uint16_t tag, type; uint32_t count, value; } e[12] = {
+        { 256, LONG, 1, (uint32_t)pw }, { 257, LONG, 1, (uint32_t)ph }, { 258, SHORT, 3, 158 }, { 259, SHORT, 1, 1 }, { 262, SHORT, 1, 2 },
+        { 273, LONG, 1, (uint32_t)kRgbHeaderBytes }, { 274, SHORT, 1, 1 }, { 277, SHORT, 1, 3 }, { 278, LONG, 1, (uint32_t)ph },
+        { 279, LONG, 1, 3u * (uint32_t)pw * (uint32_t)ph }, { 284, SHORT, 1, 1 }, { 305, ASCII, 6, 164 } };
+    const uint16_t head[5] = { 0x4949, 42, 8, 0, 12 };
+    memcpy(b, head, 10);
+    for (int i = 0; i < 12; i++) {
+        uint8_t *at = b + 10 + 12 * i;
+        memcpy(at, &e[i].tag, 2);
+        memcpy(at + 2, &e[i].type, 2);
+        memcpy(at + 4, &e[i].count, 4);
+        memcpy(at + 8, &e[i].value, 4);
+    }
+    const uint16_t bits[3] = { 8, 8, 8 };
+    memcpy(b + 158, bits, 6);
+    memcpy(b + 164, "MLVFS", 6);
+    memcpy(out, b, kRgbHeaderBytes);
+    return kRgbHeaderBytes;
 }

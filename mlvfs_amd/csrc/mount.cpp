@@ -20,6 +20,10 @@
 // mlvfs_amd_mount_set_proxy(2): one stage more behind the last, the 2x2 binning within each CFA colour (k_proxy.hip).  Each final frame
 // is binned into its other slot (O when it lies in F, and the reverse -- free by then); the download, the encoder and the headers take
 // the binned frame and its geometry.  Nothing in front of it knows.
+//
+// mlvfs_amd_mount_rgb serves the same frames through the same stages as TIFF files of 8-bit sRGB at half size: each final frame is
+// developed into its other slot (k_render.hip) with the parameters its headers give in their final state (mlvfs_amd_rgb_params), and
+// only the 3 W' H' bytes cross the link.  No .dng header is written on that route; nothing in front of the last step knows.
 #include "clip.h"
 #include "lj92enc.h"
 
@@ -45,6 +49,9 @@ struct Mount {
     int proxy = 1;                           // mlvfs_amd_mount_set_proxy: 2 = the served frames are binned to half size
     int device = -1;
     void *d_frames = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_bits = nullptr;
+    int32_t *d_rgb = nullptr;                // mlvfs_amd_mount_rgb: 13 parameters per frame of a batch
+    int rgb_frames = 0;
+    std::vector<int32_t> rgb_host;           // what the upload reads: it outlives every call
     size_t frames_bytes = 0, scratch_bytes = 0, bits_bytes = 0;   // d_bits: the encoder's bit streams, sized from a batch's histograms
 
     void release()
@@ -53,8 +60,11 @@ struct Mount {
         if (d_out) (void)hipFree(d_out);
         if (d_scratch) (void)hipFree(d_scratch);
         if (d_bits) (void)hipFree(d_bits);
+        if (d_rgb) (void)hipFree(d_rgb);
         d_frames = d_out = d_scratch = d_bits = nullptr;
+        d_rgb = nullptr;
         frames_bytes = scratch_bytes = bits_bytes = 0;
+        rgb_frames = 0;
     }
     ~Mount() { release(); }
 
@@ -77,6 +87,17 @@ struct Mount {
             MLV_HIP(hipMalloc(&d_scratch, sbytes));
             scratch_bytes = sbytes;
         }
+        return MLVFS_AMD_OK;
+    }
+
+    int ensure_rgb(int frames)               // after ensure(): the device is this handle's
+    {
+        if (rgb_frames >= frames) return MLVFS_AMD_OK;
+        if (d_rgb) (void)hipFree(d_rgb);
+        d_rgb = nullptr;
+        rgb_frames = 0;
+        MLV_HIP(hipMalloc((void **)&d_rgb, (size_t)frames * 13 * sizeof(int32_t)));
+        rgb_frames = frames;
         return MLVFS_AMD_OK;
     }
 };
@@ -161,9 +182,43 @@ int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstr
     return MLVFS_AMD_OK;
 }
 
-// frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly
+// The batch's final frames as rendered TIFF files: the parameters of every frame from its headers as they are now, one upload, runs of
+// frames that lie on one side of the slot pair developed into the other side in one launch, then header + 3 W' H' bytes per file.
+int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *h_out,
+              size_t out_stride, int gain_q8, int w, int h)
+{
+    hipStream_t s = c->stream;
+    uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
+    int pw, ph;
+    if (!rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    std::vector<int32_t> &params = m.rgb_host;
+    params.resize((size_t)n * 13);
+    for (int k = 0; k < n; k++) {
+        const int rc = mlvfs_amd_rgb_params(&fh[k], gain_q8, params.data() + (size_t)k * 13);
+        if (rc) return rc;
+    }
+    MLV_HIP(hipMemcpyAsync(m.d_rgb, params.data(), params.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    const size_t hdr = mlvfs_amd_rgb_header_size(), served = (size_t)3 * pw * ph;
+    for (int k0 = 0, k1; k0 < n; k0 = k1) {
+        const bool in_f = final_at[k0] == F + k0 * dstride;
+        for (k1 = k0 + 1; k1 < n && (final_at[k1] == F + k1 * dstride) == in_f; k1++) {}
+        uint8_t *dst = (in_f ? O : F) + k0 * dstride;
+        const int rc = launch_render2(final_at[k0], dstride, m.d_rgb + (size_t)k0 * 13, dst, dstride, w, h, k1 - k0, s);
+        if (rc) return rc;
+        for (int k = k0; k < k1; k++) {
+            uint8_t *file = h_out + k * out_stride;
+            (void)mlvfs_amd_rgb_header(pw, ph, file, hdr);
+            MLV_HIP(hipMemcpyAsync(file + hdr, dst + (size_t)(k - k0) * dstride, served, hipMemcpyDeviceToHost, s));
+        }
+    }
+    MLV_HIP(hipStreamSynchronize(s));
+    return MLVFS_AMD_OK;
+}
+
+// frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly;
+// rgb_gain != 0: served rendered (mlvfs_amd_mount_rgb), and no .dng header is written -- a file may be smaller than one
 int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results,
-                const Lossless *ll)
+                const Lossless *ll, int rgb_gain = 0)
 {
     const mlvfs_amd_mount_opts_t &o = m.o;
     hipStream_t s = c->stream;
@@ -180,6 +235,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
     }
     // the frame's header: the proxy's where one is served, with the max_size the full-size write has
     auto write_header = [&](int k, size_t max_size) {
+        if (rgb_gain) return;
         if (m.proxy == 2) (void)mlvfs_amd_dng_header_proxy(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data(), 2, 0);
         else (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data());
     };
@@ -297,6 +353,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             for (int k = k0; k < k1; k++) final_at[k] = dst + (size_t)(k - k0) * dstride;
         }
     }
+    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h);
     if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll, sw, sh);
     const size_t served = (size_t)sw * sh * 2;
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
@@ -433,9 +490,9 @@ int mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int heigh
     return launch_bin2(d_frames, stride, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
 }
 
-// both entry points
+// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb
 static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
-                       int batch_frames, int io_threads, int *results)
+                       int batch_frames, int io_threads, int *results, int rgb_gain = 0)
 {
     if (!mount || !h_out || (lossless && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
     Mount &m = *(Mount *)mount;
@@ -463,6 +520,13 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         if (!proxy_geom(w, h, &pw, &ph)) { set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         size = dng_get_header_size() + (size_t)pw * ph * 2;
     }
+    if (rgb_gain) {
+        if (m.proxy == 2) { set_error("mount: a handle that serves proxies does not render"); return MLVFS_AMD_ERR_ARG; }
+        int pw, ph;
+        if (!rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+        size = mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
+        if (out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
+    }
     if (out_stride < size) { set_error("mount: out_stride %zu smaller than a .dng file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     if (m.dark && !darkframe_fits(m.dark, w, h, bpp)) { set_error("mount: the dark frame does not have the geometry of frame %d (%dx%d at %d bits)", first, w, h, bpp); return MLVFS_AMD_ERR_ARG; }
     if (m.flat && !flatfield_fits(m.flat, w, h)) { set_error("mount: the flat field does not have the geometry of frame %d (%dx%d)", first, w, h); return MLVFS_AMD_ERR_ARG; }
@@ -479,6 +543,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     FlatFieldDev flat{ nullptr, 0, (1 << bpp) - 1 };
     if (rc == MLVFS_AMD_OK && m.flat) rc = flatfield_on_device(m.flat, c, w, h, &flat.d_gain);
     if (rc == MLVFS_AMD_OK) rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
+    if (rc == MLVFS_AMD_OK && rgb_gain) rc = m.ensure_rgb(batch_frames);
     for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
         int n = std::min(batch_frames, count - f0);
         if (m.o.dual_iso == 2 && m.o.fix_bad_pixels) {
@@ -494,7 +559,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         if (rc == MLVFS_AMD_OK) {
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
-                             lossless ? &ll : nullptr);
+                             lossless ? &ll : nullptr, rgb_gain);
         }
         f0 += n;
     }
@@ -505,6 +570,57 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
 int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results)
 {
     return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results);
+}
+
+int mlvfs_amd_mount_rgb(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int batch_frames, int io_threads,
+                        int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8);
+}
+
+size_t mlvfs_amd_mount_rgb_size(const void *mount, int index)
+{
+    if (!mount) { set_error("mount: null argument"); return 0; }
+    Mount &m = *(Mount *)mount;
+    frame_headers fh;
+    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
+    int pw, ph;
+    if (!rgb_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
+    return mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
+}
+
+int mlvfs_amd_rgb_geom(int width, int height, int *pw, int *ph)
+{
+    if (!pw || !ph) { set_error("rgb_geom: null argument"); return MLVFS_AMD_ERR_ARG; }
+    int w2, h2;
+    if (!rgb_geom(width, height, &w2, &h2)) { set_error("rgb_geom: %dx%d not supported (2x2 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
+    *pw = w2;
+    *ph = h2;
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
+                          int nframes, void *stream)
+{
+    if (!d_frames || !d_out || !d_params) { set_error("render2: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("render2: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    int pw, ph;
+    if (!rgb_geom(width, height, &pw, &ph)) { set_error("render2: %dx%d not supported (2x2 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)3 * pw * ph;
+    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render2: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
+        set_error("render2: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
+    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
+    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
+    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render2: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    return launch_render2(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
 }
 
 int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,

@@ -67,6 +67,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_flat_create", "mlvfs_amd_flat_from_clip", "mlvfs_amd_flat_info", "mlvfs_amd_flat_gain", "mlvfs_amd_flat_destroy",
     "mlvfs_amd_flat_apply_dev", "mlvfs_amd_mount_set_flat", "mlvfs_amd_mlv_transcode_cal",
     "mlvfs_amd_proxy_geom", "mlvfs_amd_bin2_dev", "mlvfs_amd_dng_header_proxy", "mlvfs_amd_mount_set_proxy", "mlvfs_amd_mount_dng_size",
+    "mlvfs_amd_rgb_geom", "mlvfs_amd_rgb_header_size", "mlvfs_amd_rgb_lut", "mlvfs_amd_rgb_params", "mlvfs_amd_rgb_header",
+    "mlvfs_amd_render2_dev", "mlvfs_amd_mount_rgb", "mlvfs_amd_mount_rgb_size",
 ]
 
 
@@ -258,6 +260,14 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_dng_header_proxy", sz, [fhp, vp, C.c_long, sz, C.c_double, C.c_char_p, i, C.c_uint32])
     sig("mlvfs_amd_mount_set_proxy", i, [vp, i])
     sig("mlvfs_amd_mount_dng_size", sz, [vp, i])
+    sig("mlvfs_amd_rgb_geom", i, [i, i, C.POINTER(i), C.POINTER(i)])
+    sig("mlvfs_amd_rgb_header_size", sz, [])
+    sig("mlvfs_amd_rgb_lut", i, [vp])
+    sig("mlvfs_amd_rgb_params", i, [fhp, i, vp])
+    sig("mlvfs_amd_rgb_header", sz, [i, i, vp, sz])
+    sig("mlvfs_amd_render2_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp])
+    sig("mlvfs_amd_mount_rgb", i, [vp, i, i, vp, sz, i, i, i, vp])
+    sig("mlvfs_amd_mount_rgb_size", sz, [vp, i])
     _lib = L
     return L
 

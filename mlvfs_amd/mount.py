@@ -9,6 +9,9 @@
     Mount(r, opt, proxy=2) serves half-size Bayer proxies: the same frames after every stage, binned 2x2 within each CFA colour on the
     GPU (include/mlvfs_amd.h, "half-size Bayer proxies"), a quarter of the bytes per file.
 
+    m.rgb(0, 16, gain=1.0) serves the same frames developed to 8-bit sRGB at half size, as TIFF files any viewer opens
+    (include/mlvfs_amd.h, "rendered half-size sRGB frames"; mlvfs_amd/render.py is the definition in numpy).
+
 Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
 """
 from __future__ import annotations
@@ -108,6 +111,28 @@ class Mount:
         lib.check(self.L.mlvfs_amd_mount_dng_lossless(self.h, first, count, lib.ptr(out), stride, lib.ptr(sizes), lib.ptr(flags), batch,
                                                       io_threads, lib.ptr(res)), "mount_dng_lossless")
         return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
+
+    def rgb_size(self, index: int = 0) -> int:
+        """bytes of file `index` as rgb() serves it: the TIFF header + 3 * (W // 2) * (H // 2)"""
+        size = int(self.L.mlvfs_amd_mount_rgb_size(self.h, index))
+        if not size:
+            raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
+        return size
+
+    def rgb(self, first: int, count: int, gain: float = 1.0, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None) -> np.ndarray:
+        """Frames first .. first + count - 1 rendered to half-size 8-bit sRGB TIFF files: a (count, rgb_size) uint8 array.  gain: the
+        exposure factor, in steps of 1 / 256 (gain_q8 = round(256 * gain), 1 .. 65535).  Not on a handle that serves proxies."""
+        gain_q8 = int(round(256 * gain))
+        if not 1 <= gain_q8 <= 65535:
+            raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
+        out = np.zeros((count, self.rgb_size(first) if count else 0), np.uint8)
+        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
+                                        and results.size >= count):
+            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
+        res = np.zeros(max(count, 1), np.int32) if results is None else results
+        lib.check(self.L.mlvfs_amd_mount_rgb(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, batch, io_threads, lib.ptr(res)),
+                  "mount_rgb")
+        return out
 
     def close(self) -> None:
         if self.h:

@@ -1,0 +1,88 @@
+"""Write a clip as a sequence of rendered half-size sRGB TIFF frames: every frame as the mount serves it with these options, developed
+to 8-bit RGB at half size on the GPU (mlvfs_amd_mount_rgb; include/mlvfs_amd.h, "rendered half-size sRGB frames").
+
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+                                             [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
+                                             [--first A] [--count N] [--batch N] [--io-threads N]
+
+OUTDIR/<clip>_000000.tif ... hold (W // 2) x (H // 2) RGB pixels behind a 256-byte baseline TIFF header: any viewer opens them, any
+editing program takes the sequence as an offline proxy.  --gain is the only exposure control (the deflicker's bias is not applied: it
+only shapes the frame through the stages in front).  Frames are served in order, as one MLVFS process would serve them.  Nothing is
+overwritten: an existing file of the sequence ends the run before any frame is served."""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mlvfs_amd import mlvfile
+from mlvfs_amd.dark import Dark
+from mlvfs_amd.flat import Flat
+from mlvfs_amd.mount import Mount
+from mlvfs_amd.pipeline import MlvfsOptions
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("src")
+    ap.add_argument("outdir")
+    ap.add_argument("--gain", type=float, default=1.0, help="exposure factor, in steps of 1 / 256 (1 / 256 .. 255.996)")
+    ap.add_argument("--cs", type=int, default=0, choices=(0, 2, 3, 5), help="chroma smoothing")
+    ap.add_argument("--bad-pix", type=int, default=0, choices=(0, 1, 2), help="bad-pixel repair (2: aggressive)")
+    ap.add_argument("--stripes", action="store_true", help="vertical stripes correction")
+    ap.add_argument("--dual-iso", type=int, default=0, choices=(0, 1, 2), help="1 preview, 2 full conversion")
+    ap.add_argument("--hdr-interp", type=int, default=0, choices=(0, 1), help="0 AMaZE + edge-directed, 1 mean23")
+    ap.add_argument("--pattern-noise", action="store_true")
+    ap.add_argument("--deflicker", type=int, default=0, metavar="T", help="target level, 0 = off")
+    ap.add_argument("--dark", metavar="PATH", help="a clip of dark frames: averaged, then subtracted from every frame")
+    ap.add_argument("--flat", metavar="PATH", help="a clip of an evenly lit target: averaged into a gain plane that corrects every frame")
+    ap.add_argument("--first", type=int, default=0)
+    ap.add_argument("--count", type=int, default=0, help="frames to write (default: to the end of the clip)")
+    ap.add_argument("--batch", type=int, default=8, help="frames per GPU batch")
+    ap.add_argument("--io-threads", type=int, default=0)
+    a = ap.parse_args()
+    if not 1 <= round(256 * a.gain) <= 65535:
+        ap.error(f"--gain {a.gain} outside 1 / 256 .. 65535 / 256")
+    stem = os.path.splitext(os.path.basename(a.src))[0]
+    opt = MlvfsOptions(chroma_smooth=a.cs, fix_bad_pixels=a.bad_pix, fix_stripes=int(a.stripes), dual_iso=a.dual_iso,
+                       hdr_interpolation_method=a.hdr_interp, fix_pattern_noise=int(a.pattern_noise))
+    dark = flat = None
+    with mlvfile.MlvReader(a.src) as r:
+        count = a.count or r.frame_count - a.first
+        if a.first < 0 or count <= 0 or a.first + count > r.frame_count:
+            ap.error(f"frames {a.first} .. {a.first + count - 1} outside the clip ({r.frame_count} frames)")
+        names = [os.path.join(a.outdir, f"{stem}_{k:06d}.tif") for k in range(a.first, a.first + count)]
+        taken = [n for n in names if os.path.exists(n)]
+        if taken:
+            print(f"{taken[0]} exists ({len(taken)} of {count} files): nothing is overwritten", file=sys.stderr)
+            return 1
+        os.makedirs(a.outdir, exist_ok=True)
+        try:
+            if a.dark:
+                with mlvfile.MlvReader(a.dark) as dr:
+                    dark = Dark.from_clip(dr, 0, dr.frame_count, batch=a.batch, io_threads=a.io_threads)
+            if a.flat:
+                with mlvfile.MlvReader(a.flat) as fr:
+                    flat = Flat.from_clip(fr, dark=dark, batch=a.batch, io_threads=a.io_threads)
+            t0, total = time.perf_counter(), 0
+            with Mount(r, opt, deflicker=a.deflicker, basename="/" + os.path.basename(a.src), dark=dark, flat=flat) as m:
+                for f0 in range(0, count, a.batch):
+                    n = min(a.batch, count - f0)
+                    files = m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads)
+                    for name, data in zip(names[f0:f0 + n], files):
+                        with open(name, "xb") as out:                       # "x": never over a file that appeared meanwhile
+                            out.write(data.tobytes())
+                        total += data.size
+            dt = time.perf_counter() - t0
+        finally:
+            if flat is not None:
+                flat.close()
+            if dark is not None:
+                dark.close()
+    print(f"{count} rendered file(s) in {a.outdir}, {dt:.3f} s ({count / dt:.1f} frames/s), {total / count:.0f} bytes per file")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
