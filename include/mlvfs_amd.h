@@ -559,7 +559,7 @@ int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out,
                                  int batch_frames, int io_threads, int *results);
 void mlvfs_amd_mount_close(void *mount);
 
-/* -- dark-frame subtraction (csrc/dark.cpp, csrc/k_dark.hip) ---- */
+/* -- dark-frame subtraction (csrc/cal.cpp, csrc/k_cal.hip) ---- */
 /* A dark frame: a plane of width x height 16-bit values of `bpp` bits with a pedestal black_d, the black level of the clip it was
  * averaged from.  Subtraction, per pixel in 32-bit signed arithmetic:   out = clamp(px - dark + black_d, 0, 2^bpp - 1).
  * The plane is applied by position in the stored frame (xRes x yRes); panPosX/Y and cropPosX/Y are ignored.  The frame's own levels,
@@ -634,7 +634,7 @@ int  mlvfs_amd_repack_dev(const mlvfs_amd_geom_t *geom, int out_bpp, const mlvfs
 int  mlvfs_amd_mlv_transcode_bits(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark,
                                   int batch_frames, int io_threads, long long stats[4]);
 
-/* -- flat-field correction (csrc/flat.cpp, csrc/k_flat.hip) -- what `mlv_dump -t` does -------------------------- */
+/* -- flat-field correction (csrc/cal.cpp, csrc/k_cal.hip) -- what `mlv_dump -t` does -------------------------- */
 /* A flat field: a plane F of width x height 16-bit values with a pedestal black_f, the black level of the clip of an evenly lit
  * target it was averaged from.  Integer arithmetic only.  The gain plane, one uint16 per pixel in Q14 (16384 = 1.0):
  *     s[p]    = max(F[p] - black_f, 1)

@@ -188,50 +188,38 @@ void deflicker_bias(int target, int black_level, uint16_t median, int32_t exposu
 // what a frame's payload is, from its chunk's videoClass (mlv.h:30-31: LZMA 0x80, LJ92 0x100; main.c:573 tests the LZMA flag first)
 enum { PAYLOAD_PLAIN = 0, PAYLOAD_LZMA = 1, PAYLOAD_LJ92 = 2 };
 inline int payload_kind(uint16_t video_class) { return (video_class & 0x80) ? PAYLOAD_LZMA : (video_class & 0x100) ? PAYLOAD_LJ92 : PAYLOAD_PLAIN; }
-// A dark FRAME (dark.cpp, k_dark.hip: a sensor's offset pattern to subtract; not the "dark clips" of dark_share and the T16 layout,
-// which are low-light footage) as the kernels take it: the plane on the current device, its pedestal, 2^bpp - 1
-struct DarkFrameDev {
-    const uint16_t *d_plane;
-    int black, top;
+// The calibration stage (cal.cpp, k_cal.hip) as the kernels take it: a dark FRAME (a sensor's offset pattern to
+// subtract, stage 0; not the "dark clips" of dark_share and the T16 layout, which are low-light footage) and a flat field's Q14 gain
+// plane (stage 0b) on the current device; a null plane: that stage is off.  black_d: the dark plane's pedestal; black, top: the black
+// level and 2^bpp - 1 of the FRAMES (a dark frame has the frames' depth; a gain plane has none of its own)
+struct Calib {
+    const uint16_t *d_dark = nullptr;
+    int black_d = 0;
+    const uint16_t *d_gain = nullptr;
+    int black = 0, top = 0;
+    bool on() const { return d_dark || d_gain; }
 };
-// the handle's plane on the calling thread's device (uploaded on the device's first use); the geometry must be the handle's
-int darkframe_on_device(const mlvfs_amd_dark_t *dark, ThreadCtx *c, int w, int h, int bpp, DarkFrameDev *out);
+// the handles' planes (either may be null) on the calling thread's device, each uploaded on the device's first use, for frames of
+// w x h at bpp bits and this black level; a handle of another geometry is refused
+int calib_on_device(const mlvfs_amd_dark_t *dark, const mlvfs_amd_flat_t *flat, ThreadCtx *c, int w, int h, int bpp, int black, Calib *out);
 bool darkframe_fits(const mlvfs_amd_dark_t *dark, int w, int h, int bpp);
-int launch_dark_sub(void *d_frames, size_t stride, uint32_t npix, int nframes, const DarkFrameDev &dark, hipStream_t stream);
-int launch_dark_unpack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int nframes,
-                       const DarkFrameDev &dark, hipStream_t stream);
+bool flatfield_fits(const mlvfs_amd_flat_t *flat, int w, int h);
+// in place, both stages in one pass; packed payloads in, corrected 16-bit frames out
+int launch_cal_apply(void *d_frames, size_t stride, uint32_t npix, int nframes, const Calib &cal, hipStream_t stream);
+int launch_cal_unpack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int nframes,
+                      const Calib &cal, hipStream_t stream);
 int launch_dark_accum(const void *d_frames, size_t stride, uint32_t npix, int nframes, uint32_t *d_sums, hipStream_t stream);
 int launch_dark_mean(const uint32_t *d_sums, uint16_t *d_dark, uint32_t npix, uint32_t n, hipStream_t stream);
-// what dark.cpp and flat.cpp share: a plane's geometry check (false with the error set: a non-positive size or 2^27 pixels and more,
-// bpp outside 1..16, a pedestal outside 0..65535), device memory that lives as long as its scope, and
-// what they average a clip with: the one geometry of frames first .. first + count - 1 and frame first's black
-// level (false, with the error set: frames outside the clip, count outside 1..65536, unusable headers, more than one geometry),
-// and their rounded mean as w * h 16-bit values at d_mean (16-byte aligned), summed in batches; s is drained on return
-bool plane_geometry_ok(const char *who, int w, int h, int bpp, int black);
+int launch_flat_gain(const uint16_t *d_plane, uint32_t w, uint32_t h, int black_f, unsigned long long *d_sums, uint16_t *d_gain,
+                     uint32_t *d_means, hipStream_t stream);
+// device memory that lives as long as its scope, and a size rounded up to the 256 bytes frames lie apart by
 struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
-bool clip_mean_geometry(const char *who, const void *reader, int first, int count, int *w, int *h, int *bpp, int *black);
-int clip_mean_dev(const void *reader, int first, int count, int w, int h, int bpp, int batch, int io_threads, uint16_t *d_mean, hipStream_t s);
-// A flat field (flat.cpp, k_flat.hip) as the kernels take it: the Q14 gain plane on the current device, and the
-// black level and 2^bpp - 1 of the FRAMES it is applied to (a gain plane has no depth of its own)
-struct FlatFieldDev {
-    const uint16_t *d_gain;
-    int black, top;
-};
-// the handle's gain plane on the calling thread's device (uploaded on the device's first use); the size must be the handle's
-int flatfield_on_device(const mlvfs_amd_flat_t *flat, ThreadCtx *c, int w, int h, const uint16_t **d_gain);
-bool flatfield_fits(const mlvfs_amd_flat_t *flat, int w, int h);
-int launch_flat_gain(const uint16_t *d_plane, uint32_t w, uint32_t h, int black_f, unsigned long long *d_sums, uint16_t *d_gain,
-                     uint32_t *d_means, hipStream_t stream);
-// stage 0b, in place; dark (optional): stage 0, subtracted first in the same pass
-int launch_flat_apply(void *d_frames, size_t stride, uint32_t npix, int nframes, const FlatFieldDev &flat, const DarkFrameDev *dark,
-                      hipStream_t stream);
-int launch_flat_unpack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int nframes,
-                       const FlatFieldDev &flat, const DarkFrameDev *dark, hipStream_t stream);
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 // the mount's reader half (mlvreader.cpp): frames of one geometry from the file to 16-bit pixels in HBM.  On return everything that
-// reads the reader's staging has ended on s; without `dark` s is drained.  dark: stage 0, the dark frame subtracted from every frame
+// reads the reader's staging has ended on s; without `cal` s is drained.  cal: the calibration stage, every frame corrected
 // as it arrives -- plain and LZMA payloads inside the unpack pass (s drained on return), LJ92 payloads in a pass behind the decoder
 // that may still be in flight on s on return: the caller goes on on s, or synchronises it
 // A change of bit depth on the way (the transcoder, mlvfs_amd_mlv_transcode_bits; k_mlvpack.hip): plain and LZMA
@@ -242,14 +230,13 @@ struct LoadBits {
     int out_bpp;
     bool packed;
 };
-// flat: stage 0b, the flat field's gain, in the pass that subtracts the dark frame (or would): plain and LZMA payloads in
-// launch_flat_unpack, LJ92 payloads in one launch_flat_apply behind the decoder.  Not together with `bits`: the caller shifts afterwards.
+// cal: the calibration stage, both of its halves in one pass: plain and LZMA payloads in launch_cal_unpack, LJ92 payloads in one
+// launch_cal_apply behind the decoder.  A gain is not combined with `bits`: the caller shifts afterwards.
 int reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                      hipStream_t s, const DarkFrameDev *dark = nullptr, const FlatFieldDev *flat = nullptr);
+                      hipStream_t s, const Calib *cal = nullptr);
 // the same for frames named one by one (all of one geometry and payload kind); stage_locked: the caller holds reader_stage_mutex
 int reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                     hipStream_t s, bool stage_locked, const DarkFrameDev *dark = nullptr, const LoadBits *bits = nullptr,
-                     const FlatFieldDev *flat = nullptr);
+                     hipStream_t s, bool stage_locked, const Calib *cal = nullptr, const LoadBits *bits = nullptr);
 // what the transcoder (mlvwriter.cpp) asks of an opened clip: its path and chunk files, where a frame's VIDF block lies, the bytes of
 // its payload as read_frames (lj92: as the LJ92 decoder) takes it, packed payloads of plain and LZMA frames (host only), and the
 // mutex that serialises the reader's streaming calls
@@ -269,9 +256,9 @@ int launch_mlv_pack(const void *d_frames, size_t stride, void *d_packed, size_t 
 // the same passes with a change of bit depth inside (d = out_bpp - bpp; > 0: << d, < 0: >> -d), and packed -> packed in one pass
 int launch_mlv_shift(void *d_frames, size_t stride, uint32_t npix, int d, int nframes, hipStream_t stream);
 int launch_mlv_repack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
-                      const DarkFrameDev *dark, hipStream_t stream);
+                      const Calib *cal, hipStream_t stream);
 int launch_mlv_unpack_shift(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp,
-                            int nframes, const DarkFrameDev *dark, hipStream_t stream);
+                            int nframes, const Calib *cal, hipStream_t stream);
 int launch_mlv_pack_shift(void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
                           hipStream_t stream);
 int launch_mlv_tile_shift(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int d, int nframes, hipStream_t stream);

@@ -21,18 +21,19 @@
 // A clip rewritten at another bit depth (mlvfs_amd_mlv_transcode_bits, `mlv_dump -b`).  For a frame of bpp bits and a
 // requested out_bpp, d = out_bpp - bpp:
 //     out = px >> -d   (d < 0: truncation, no rounding, no dither)        out = px << d   (d > 0)        out = px   (d = 0)
-// after the dark frame, if any, was subtracted at the source's depth (stage 0, k_dark.hip).  The shift rides inside the pass a route
+// after the dark frame, if any, was subtracted at the source's depth (stage 0, k_cal.hip).  The shift rides inside the pass a route
 // makes anyway -- the kernels above are not touched, a call without conversion launches exactly what it launched before:
 //   k_mlv_repack_x16<IN, OUT>, IN, OUT in {14, 12, 10} : packed stream in, packed stream out; one lane = 16 pixels = IN / 2 coalesced
 //                  dword loads, unpack, the dark plane (optional: two 128-bit loads), shift, OUT / 2 coalesced dword stores.
 //                  3.25 B per pixel at 14 -> 12 where unpack + pack move 7.25.  IN == OUT is for a dark frame alone.
 //   k_mlv_repack_generic : any depths in 1..16, any length, 2-byte alignment; one lane = one output word.
-//   k_mlv_unpack_shift_x16<IN> : k_dark_unpack_x16 with the shift (plain / LZMA source to the encoder); the plane is optional.
+//   k_mlv_unpack_shift_x16<IN> : k_cal_unpack_x16<IN, true, false> with the shift (plain / LZMA source to the encoder); the plane is optional.
 //   k_mlv_pack_shift_x16<OUT>  : k_mlv_pack_x16 with the shift in front of the mask (LJ92 source to plain output).
 //   k_mlv_tile_shift_x<16 | 8>, k_mlv_tile_shift_generic : the tiling with the shift (LJ92 source to LJ92 output).
 //   k_mlv_shift_generic : in place, one pixel per lane -- the extra pass of the shapes the fast forms do not take.
 // Pad bytes between frames are never touched.
 #include "clip.h"
+#include "k_cal_dev.h"
 #include "k_unpack_dev.h"
 
 namespace mlv {
@@ -204,21 +205,15 @@ __device__ __forceinline__ uint32_t shift_px2(uint32_t two, int d)
     return d >= 0 ? (two << d) & (((0xFFFFu << d) & 0xFFFFu) * 0x10001u) : (two >> -d) & ((0xFFFFu >> -d) * 0x10001u);
 }
 
-__device__ __forceinline__ uint32_t sub_dark_px(uint32_t px, uint32_t dk, int black_d, int top)
-{
-    const int v = (int)px - (int)dk + black_d;
-    return (uint32_t)min(max(v, 0), top);
-}
-
-// the lane's 16 pixels less the dark plane's (k_dark.hip's rule: clamp(px - dark + black_d, 0, 2^IN - 1))
+// the lane's 16 pixels less the dark plane's (k_cal_dev.h's rule: clamp(px - dark + black_d, 0, 2^IN - 1))
 __device__ __forceinline__ void dark_x16(uint32_t (&px)[16], const uint4 *__restrict__ dark, size_t g, int black_d, int top)
 {
     const uint4 da = dark[g * 2], db = dark[g * 2 + 1];
     const uint32_t dk[8] = { da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w };
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        px[2 * i] = sub_dark_px(px[2 * i], dk[i] & 0xFFFFu, black_d, top);
-        px[2 * i + 1] = sub_dark_px(px[2 * i + 1], dk[i] >> 16, black_d, top);
+        px[2 * i] = cal_px<true, false>(px[2 * i], dk[i] & 0xFFFFu, 0, black_d, 0, top);
+        px[2 * i + 1] = cal_px<true, false>(px[2 * i + 1], dk[i] >> 16, 0, black_d, 0, top);
     }
 }
 
@@ -266,7 +261,7 @@ __global__ __launch_bounds__(256) void k_mlv_repack_generic(const uint8_t *__res
             const uint32_t bit = i * (uint32_t)bpp, wi = bit >> 4, sh = bit & 15u;
             const uint32_t two = ((uint32_t)src[wi] << 16) | (wi + 1 < in_words ? (uint32_t)src[wi + 1] : 0u);
             uint32_t v = (two >> (32 - bpp - (int)sh)) & in_mask;
-            if (dark) v = sub_dark_px(v, dark[i], black_d, (int)in_mask);
+            if (dark) v = cal_px<true, false>(v, dark[i], 0, black_d, 0, (int)in_mask);
             v = shift_px(v, d) & out_mask;
             const int pos = 15 - (int)(i * (uint32_t)out_bpp + (uint32_t)out_bpp - 1u - bit0);
             word |= pos >= 0 ? v << pos : v >> -pos;
@@ -379,13 +374,14 @@ int launch_mlv_shift(void *d_frames, size_t stride, uint32_t npix, int d, int nf
 
 // packed payloads of bpp bits -> packed payloads of out_bpp bits, the dark frame (optional) subtracted in between
 int launch_mlv_repack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
-                      const DarkFrameDev *dark, hipStream_t stream)
+                      const Calib *cal, hipStream_t stream)
 {
     if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
+    const uint16_t *dark = cal ? cal->d_dark : nullptr;
     if (bpp < 1 || bpp > 16 || out_bpp < 1 || out_bpp > 16) { set_error("unsupported bits_per_pixel %d -> %d", bpp, out_bpp); return MLVFS_AMD_ERR_ARG; }
     if (npix >= (1u << 27)) { set_error("more than 2^27 pixels"); return MLVFS_AMD_ERR_ARG; }       // bit positions are 32-bit
     const bool fast = fast_depth(bpp) && fast_depth(out_bpp) && npix % 16 == 0 && ((uintptr_t)d_packed % 4 == 0) && ((uintptr_t)d_out % 4 == 0) &&
-                      (!dark || (dark->top == (1 << bpp) - 1 && (uintptr_t)dark->d_plane % 16 == 0)) &&
+                      (!dark || (cal->top == (1 << bpp) - 1 && (uintptr_t)dark % 16 == 0)) &&
                       (nframes == 1 || (packed_stride % 4 == 0 && out_stride % 4 == 0));
     if (fast) {
         using Kern = void (*)(const uint8_t *, size_t, uint8_t *, size_t, const uint4 *, uint32_t, int);
@@ -396,13 +392,12 @@ int launch_mlv_repack(const void *d_packed, size_t packed_stride, void *d_out, s
         };
         const uint32_t groups = npix / 16;
         hipLaunchKernelGGL(table[(14 - bpp) / 2][(14 - out_bpp) / 2], dim3(grid_x(groups, 8192), nframes), dim3(256), 0, stream,
-                           (const uint8_t *)d_packed, packed_stride, (uint8_t *)d_out, out_stride, dark ? (const uint4 *)dark->d_plane : nullptr, groups,
-                           dark ? dark->black : 0);
+                           (const uint8_t *)d_packed, packed_stride, (uint8_t *)d_out, out_stride, (const uint4 *)dark, groups,
+                           dark ? cal->black_d : 0);
     } else {
         const uint32_t in_words = (uint32_t)(((uint64_t)npix * bpp + 15) / 16), out_words = (uint32_t)(((uint64_t)npix * out_bpp + 15) / 16);
         hipLaunchKernelGGL(k_mlv_repack_generic, dim3(grid_x(out_words, 16384), nframes), dim3(256), 0, stream, (const uint8_t *)d_packed,
-                           packed_stride, (uint8_t *)d_out, out_stride, dark ? dark->d_plane : nullptr, npix, in_words, out_words, bpp, out_bpp,
-                           dark ? dark->black : 0);
+                           packed_stride, (uint8_t *)d_out, out_stride, dark, npix, in_words, out_words, bpp, out_bpp, dark ? cal->black_d : 0);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;
@@ -411,22 +406,23 @@ int launch_mlv_repack(const void *d_packed, size_t packed_stride, void *d_out, s
 // packed payloads of bpp bits -> 16-bit frames of out_bpp bits, the dark frame (optional) subtracted in between: one pass where
 // k_unpack_x16 would run, else the generic unpack (and subtraction) and one in-place pass more
 int launch_mlv_unpack_shift(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp,
-                            int nframes, const DarkFrameDev *dark, hipStream_t stream)
+                            int nframes, const Calib *cal, hipStream_t stream)
 {
     if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
+    const uint16_t *dark = cal ? cal->d_dark : nullptr;
     if (bpp < 1 || bpp > 16 || out_bpp < 1 || out_bpp > 16) { set_error("unsupported bits_per_pixel %d -> %d", bpp, out_bpp); return MLVFS_AMD_ERR_ARG; }
     const bool fast = fast_depth(bpp) && npix % 16 == 0 && ((uintptr_t)d_packed % 4 == 0) && ((uintptr_t)d_out % 16 == 0) &&
-                      (!dark || (dark->top == (1 << bpp) - 1 && (uintptr_t)dark->d_plane % 16 == 0)) &&
+                      (!dark || (cal->top == (1 << bpp) - 1 && (uintptr_t)dark % 16 == 0)) &&
                       (nframes == 1 || (packed_stride % 4 == 0 && out_stride % 16 == 0));
     if (!fast) {
-        if (int rc = dark ? launch_dark_unpack(d_packed, packed_stride, d_out, out_stride, npix, bpp, nframes, *dark, stream)
+        if (int rc = dark ? launch_cal_unpack(d_packed, packed_stride, d_out, out_stride, npix, bpp, nframes, *cal, stream)
                           : launch_unpack(d_packed, packed_stride, d_out, out_stride, 0, npix, bpp, nframes, stream)) return rc;
         return launch_mlv_shift(d_out, out_stride, npix, out_bpp - bpp, nframes, stream);
     }
     const uint32_t groups = npix / 16;
     auto kern = bpp == 14 ? k_mlv_unpack_shift_x16<14> : (bpp == 12 ? k_mlv_unpack_shift_x16<12> : k_mlv_unpack_shift_x16<10>);
     hipLaunchKernelGGL(kern, dim3(grid_x(groups, 8192), nframes), dim3(256), 0, stream, (const uint8_t *)d_packed, packed_stride, (uint8_t *)d_out,
-                       out_stride, dark ? (const uint4 *)dark->d_plane : nullptr, groups, dark ? dark->black : 0, out_bpp - bpp);
+                       out_stride, (const uint4 *)dark, groups, dark ? cal->black_d : 0, out_bpp - bpp);
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;
 }

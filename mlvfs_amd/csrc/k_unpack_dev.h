@@ -1,5 +1,5 @@
 // k_unpack_dev.h -- the bit-stream side of a packed MLV payload (mlvfs/raw.h:41-79), shared by the kernels that read one:
-// k_unpack.hip and k_dark.hip.  Pixel i is bits [i*bpp, (i+1)*bpp) of an MSB-first bit stream stored as little-endian 16-bit words.
+// k_unpack.hip, k_cal.hip and k_mlvpack.hip.  Pixel i is bits [i*bpp, (i+1)*bpp) of an MSB-first bit stream stored as little-endian 16-bit words.
 #pragma once
 #include "common.h"
 

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <vector>
 
+#include "clip.h"
 #include "lj92enc.h"
 
 namespace mlv {
@@ -98,9 +99,7 @@ int write_header(uint8_t *e, int width, int height, int bitdepth, const EncTable
     return w;
 }
 
-
 enum { LJ92_OK = 0, LJ92_CORRUPT = -1, LJ92_NO_MEMORY = -2 };      // lj92.h:29-35
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct FixedLayout {
     size_t src_at, hist_at, blockhist_at, off_at, ffoff_at, tabs_at, res_at, bytes;

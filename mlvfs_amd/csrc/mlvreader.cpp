@@ -415,16 +415,17 @@ int read_frames(const Reader &r, int first, int count, uint8_t *dst, size_t stri
 // The mount (mount.cpp) and the transcoder (mlvwriter.cpp): `count` frames of one geometry and one payload kind, named by list[], as
 // 16-bit pixels in HBM, `dstride` bytes apart, on `s` -- payloads read by io_threads threads into the reader's page-locked staging
 // (LZMA decoded there), then uploaded and unpacked (k_unpack) or, LJ92 clips, decoded on the GPU.  Returns with the stream drained
-// of everything that reads the staging: it is the next caller's again.  dark: the dark frame to subtract (k_dark.hip), in the unpack
-// pass or, LJ92 clips, in a pass behind the decoder that is still in flight on `s` on return.  flat: the flat field's gain
-// (k_flat.hip), applied after the dark frame in that same pass; the caller passes no `bits` with it.  stage_locked: the caller holds the reader's staging mutex already.
+// of everything that reads the staging: it is the next caller's again.  cal: the calibration stage (k_cal.hip) -- the dark frame to
+// subtract, then the flat field's gain --, in the unpack pass or, LJ92 clips, in one pass behind the decoder that is still in flight
+// on `s` on return; the caller passes no `bits` with a gain.  stage_locked: the caller holds the reader's staging mutex already.
 // bits (the transcoder at another bit depth, clip.h: LoadBits): plain and LZMA payloads leave at bits->out_bpp bits, as 16-bit frames
 // or as packed payloads, in the one pass that reads them (k_mlvpack.hip); LJ92 payloads are left to the caller's next pass.
 int mlv::reader_load_list(const void *reader, const int *list, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                          hipStream_t s, bool stage_locked, const DarkFrameDev *dark, const LoadBits *bits, const FlatFieldDev *flat)
+                          hipStream_t s, bool stage_locked, const Calib *cal, const LoadBits *bits)
 {
     const Reader &r = *(const Reader *)reader;
     if (count <= 0) return MLVFS_AMD_OK;
+    const bool on = cal && cal->on();
     frame_headers fh0;
     if (!frame_headers_of(r, list[0], &fh0)) { set_error("mlv: frame %d has no usable headers", list[0]); return MLVFS_AMD_ERR_ARG; }
     const bool lj92 = (fh0.file_hdr.videoClass & CLASS_LJ92) && !(fh0.file_hdr.videoClass & CLASS_LZMA);
@@ -446,20 +447,18 @@ int mlv::reader_load_list(const void *reader, const int *list, int count, int w,
         std::vector<size_t> len(count);
         for (int i = 0; i < count; i++) { ptr[i] = r.stage[0] + (size_t)i * stride + 4; len[i] = sizes[i] - 4; }
         rc = mlvfs_amd_lj92_decode_dev(ptr.data(), len.data(), count, w, h, d_frames, dstride, s);     // (synchronises s)
-        if (rc || (!dark && !flat)) return rc;
-        if (flat) return launch_flat_apply(d_frames, dstride, (uint32_t)w * (uint32_t)h, count, *flat, dark, s);   // dark and flat in one pass
-        return launch_dark_sub(d_frames, dstride, (uint32_t)w * (uint32_t)h, count, *dark, s);         // (the staging is free already)
+        if (rc || !on) return rc;
+        return launch_cal_apply(d_frames, dstride, (uint32_t)w * (uint32_t)h, count, *cal, s);        // (the staging is free already)
     }
     rc = ensure_packed_dev(r, stride * count);
     if (rc) return rc;
     const mlvfs_amd_geom_t geom{ w, h, bpp, 0, 0, 0, 0 };
     MLV_HIP(hipMemcpyAsync(r.d_di_packed, r.stage[0], stride * count, hipMemcpyHostToDevice, s));
     const uint32_t npix = (uint32_t)w * (uint32_t)h;
-    if (flat) rc = launch_flat_unpack(r.d_di_packed, stride, d_frames, dstride, npix, bpp, count, *flat, dark, s);
-    else if (bits && bits->packed) rc = launch_mlv_repack(r.d_di_packed, stride, d_frames, dstride, npix, bpp, bits->out_bpp, count, dark, s);
-    else if (bits) rc = launch_mlv_unpack_shift(r.d_di_packed, stride, d_frames, dstride, npix, bpp, bits->out_bpp, count, dark, s);
-    else rc = dark ? launch_dark_unpack(r.d_di_packed, stride, d_frames, dstride, npix, bpp, count, *dark, s)
-                   : mlvfs_amd_unpack_dev(&geom, r.d_di_packed, stride, d_frames, dstride, count, s);
+    if (on && (cal->d_gain || !bits)) rc = launch_cal_unpack(r.d_di_packed, stride, d_frames, dstride, npix, bpp, count, *cal, s);
+    else if (bits && bits->packed) rc = launch_mlv_repack(r.d_di_packed, stride, d_frames, dstride, npix, bpp, bits->out_bpp, count, cal, s);
+    else if (bits) rc = launch_mlv_unpack_shift(r.d_di_packed, stride, d_frames, dstride, npix, bpp, bits->out_bpp, count, cal, s);
+    else rc = mlvfs_amd_unpack_dev(&geom, r.d_di_packed, stride, d_frames, dstride, count, s);
     if (rc) return rc;
     MLV_HIP(hipStreamSynchronize(s));
     return MLVFS_AMD_OK;
@@ -467,12 +466,12 @@ int mlv::reader_load_list(const void *reader, const int *list, int count, int w,
 
 // frames first .. first + count - 1
 int mlv::reader_load_batch(const void *reader, int first, int count, int w, int h, int bpp, void *d_frames, size_t dstride, int io_threads,
-                           hipStream_t s, const DarkFrameDev *dark, const FlatFieldDev *flat)
+                           hipStream_t s, const Calib *cal)
 {
     if (count <= 0) return MLVFS_AMD_OK;
     std::vector<int> list(count);
     for (int k = 0; k < count; k++) list[k] = first + k;
-    return reader_load_list(reader, list.data(), count, w, h, bpp, d_frames, dstride, io_threads, s, false, dark, nullptr, flat);
+    return reader_load_list(reader, list.data(), count, w, h, bpp, d_frames, dstride, io_threads, s, false, cal);
 }
 
 // ---- what the transcoder (mlvwriter.cpp) asks of an opened clip -------------------------------------------------------------

@@ -17,18 +17,18 @@
 //                          -> k_mlv_tile -> lje_encode_batch -> lengths and streams to page-locked staging -> file
 //   plain from LJ92        GPU decode -> k_mlv_pack -> file
 //   plain from plain/LZMA  host only: the packed bytes read_frames yields are written as they are (no HIP device needed)
-// With a dark frame (mlvfs_amd_mlv_transcode_dark) reader_load_list subtracts it from every frame (stage 0: k_dark.hip), and a plain or
+// With a dark frame (mlvfs_amd_mlv_transcode_dark) reader_load_list subtracts it from every frame (stage 0: k_cal.hip), and a plain or
 // LZMA source with plain output goes upload -> unpack + subtract -> k_mlv_pack, the route of an LJ92 source.
 // At another bit depth (mlvfs_amd_mlv_transcode_bits, `mlv_dump -b`) every frame whose depth is not out_bpp is shifted
 // after the dark frame, inside a pass its route makes anyway (k_mlvpack.hip), and every RAWI block of another depth is rewritten
 // (mlvfs_amd_rawi_set_bits):
 //   plain / LZMA -> plain   upload -> k_mlv_repack (unpack, subtract, shift, pack in one pass) -> file
 //   plain / LZMA -> LJ92    upload -> k_mlv_unpack_shift -> k_mlv_tile -> the encoder at out_bpp
-//   LJ92 -> plain           GPU decode -> k_dark_sub if a dark frame is set -> k_mlv_pack_shift -> file
-//   LJ92 -> LJ92            GPU decode -> k_dark_sub if set -> k_mlv_tile_shift -> the encoder at out_bpp
+//   LJ92 -> plain           GPU decode -> k_cal_apply if a dark frame is set -> k_mlv_pack_shift -> file
+//   LJ92 -> LJ92            GPU decode -> k_cal_apply if set -> k_mlv_tile_shift -> the encoder at out_bpp
 // Frames already at out_bpp, and every frame when out_bpp is 0, take the routes above unchanged.
 // With a flat field (mlvfs_amd_mlv_transcode_cal) reader_load_list applies its gain after the dark frame (stage 0b:
-// k_flat.hip) and delivers corrected 16-bit frames at the source's depth; k_mlv_tile(_shift) or k_mlv_pack(_shift) follow on every
+// k_cal.hip) and delivers corrected 16-bit frames at the source's depth; k_mlv_tile(_shift) or k_mlv_pack(_shift) follow on every
 // route, so a plain or LZMA source to plain output pays one pass more than k_mlv_repack.
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -233,11 +233,9 @@ int batch_device(Job &j, const std::vector<int> &list)
     const uint32_t npix = (uint32_t)f.w * (uint32_t)f.h;
     const size_t img = (size_t)npix * 2, dstride = up(img, 256);
     if (int rc = d.frames(dstride * n)) return rc;
-    DarkFrameDev dark{};
-    int rc = j.dark ? darkframe_on_device(j.dark, j.ctx, f.w, f.h, f.bpp, &dark) : MLVFS_AMD_OK;
+    Calib cal;
+    int rc = calib_on_device(j.dark, j.flat, j.ctx, f.w, f.h, f.bpp, f.black, &cal);
     if (rc) return rc;
-    FlatFieldDev flat{ nullptr, f.black, (1 << f.bpp) - 1 };
-    if (j.flat && (rc = flatfield_on_device(j.flat, j.ctx, f.w, f.h, &flat.d_gain))) return rc;
     const bool conv = f.obpp != f.bpp, plain = j.payload == MLVFS_AMD_MLV_PLAIN;
     const size_t pstride = up(plain_bytes(f), 16);                     // (<= dstride: d_aux has the room)
     // at another depth a plain or LZMA source is shifted by the pass that reads it; to plain output that pass packs as well.  Not with
@@ -246,7 +244,7 @@ int batch_device(Job &j, const std::vector<int> &list)
     const bool in_load = conv && f.kind != SRC_LJ92 && !j.flat;
     const bool repacked = in_load && plain;
     rc = reader_load_list(j.reader, list.data(), n, f.w, f.h, f.bpp, repacked ? d.d_aux : d.d_frames, repacked ? pstride : dstride, j.io_threads, s,
-                          true, j.dark ? &dark : nullptr, in_load ? &bits : nullptr, j.flat ? &flat : nullptr);
+                          true, &cal, in_load ? &bits : nullptr);
     if (rc) return rc;
     const int shift = in_load ? 0 : f.obpp - f.bpp;                    // what is left to do here
     if (plain) {
@@ -572,9 +570,9 @@ int mlvfs_amd_repack_dev(const mlvfs_amd_geom_t *geom, int out_bpp, const mlvfs_
     if (nframes == 0) return MLVFS_AMD_OK;
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
-    DarkFrameDev dd{};
-    if (dark) if (int rc = darkframe_on_device(dark, c, geom->width, geom->height, geom->bpp, &dd)) return rc;
-    return launch_mlv_repack(d_packed, packed_stride, d_out, out_stride, npix, geom->bpp, out_bpp, nframes, dark ? &dd : nullptr, pick_stream(stream, c));
+    Calib cal;
+    if (int rc = calib_on_device(dark, nullptr, c, geom->width, geom->height, geom->bpp, geom->black, &cal)) return rc;
+    return launch_mlv_repack(d_packed, packed_stride, d_out, out_stride, npix, geom->bpp, out_bpp, nframes, &cal, pick_stream(stream, c));
 }
 
 int mlvfs_amd_lj92_tile_dev(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int width, int height, int nframes, void *stream)

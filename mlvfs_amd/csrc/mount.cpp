@@ -2,7 +2,7 @@
 // batch by batch, for every mount option that shapes a frame's .dng file.
 //
 // Per batch, in main.c's order: read + decode / unpack (the reader's staging, mlvreader.cpp; with a dark frame or a flat field set -- which main.c does
-// not know -- the subtraction, stage 0, and the gain, stage 0b, in the same load: k_dark.hip, k_flat.hip), deflicker (one histogram launch, one
+// not know -- the subtraction, stage 0, and the gain, stage 0b, in the same load: k_cal.hip), deflicker (one histogram launch, one
 // median launch, log2 on the host), the frame's header, pattern noise (12 launches per sub-batch), dual ISO (the batched preview,
 // or the batched full conversion), then per frame the route main.c takes: a converted frame gets the header again (x4 levels) and
 // chroma smoothing (preview only) + stripes; any other frame focus pixels, bad pixels, chroma smoothing (not under dual_iso = 2),
@@ -131,8 +131,6 @@ bool same_levels(const frame_headers &a, const frame_headers &b)
 {
     return a.rawi_hdr.raw_info.black_level == b.rawi_hdr.raw_info.black_level && a.rawi_hdr.raw_info.white_level == b.rawi_hdr.raw_info.white_level;
 }
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
 // pattern-noise scratch of a batch: whole frames, at most pattern_noise_scratch_cap() (sub-batches beyond that)
 size_t o_pn_bytes(const mlvfs_amd_mount_opts_t &o, int w, int h, int batch)
@@ -361,6 +359,25 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
     return MLVFS_AMD_OK;
 }
 
+// what mlvfs_amd_mount_set_dark, _set_flat and _set_proxy do alike: the handle locked and refused once it has served frames (what:
+// "the dark frame"); a setting that is switched on (wanted) checked against frame 0's headers if the clip has frames -- fits(fh):
+// false with the error set --; then taken: take(m)
+template <class Fits, class Take>
+int mount_set(void *mount, const char *what, bool wanted, Fits fits, Take take)
+{
+    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (m.served) { set_error("mount: the handle has served frames already: %s cannot change any more", what); return MLVFS_AMD_ERR_ARG; }
+    frame_headers fh;
+    if (wanted && mlvfs_amd_mlv_frame_count(m.reader) > 0) {
+        if (!mlvfs_amd_mlv_frame_headers(m.reader, 0, &fh)) { set_error("mount: frame 0 has no usable headers"); return MLVFS_AMD_ERR_ARG; }
+        if (!fits(fh)) return MLVFS_AMD_ERR_ARG;
+    }
+    take(m);
+    return MLVFS_AMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -387,59 +404,32 @@ void mlvfs_amd_mount_close(void *mount) { delete (Mount *)mount; }
 
 int mlvfs_amd_mount_set_dark(void *mount, const mlvfs_amd_dark_t *dark)
 {
-    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
-    Mount &m = *(Mount *)mount;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (m.served) { set_error("mount: the handle has served frames already: the dark frame cannot change any more"); return MLVFS_AMD_ERR_ARG; }
-    frame_headers fh;
-    if (dark && mlvfs_amd_mlv_frame_count(m.reader) > 0) {
-        if (!mlvfs_amd_mlv_frame_headers(m.reader, 0, &fh)) { set_error("mount: frame 0 has no usable headers"); return MLVFS_AMD_ERR_ARG; }
-        if (!darkframe_fits(dark, fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, fh.rawi_hdr.raw_info.bits_per_pixel)) {
-            set_error("mount: the dark frame does not have the clip's geometry (%dx%d at %d bits)", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes,
-                      fh.rawi_hdr.raw_info.bits_per_pixel);
-            return MLVFS_AMD_ERR_ARG;
-        }
-    }
-    m.dark = dark;
-    return MLVFS_AMD_OK;
+    return mount_set(mount, "the dark frame", dark != nullptr, [&](const frame_headers &fh) {
+        if (darkframe_fits(dark, fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, fh.rawi_hdr.raw_info.bits_per_pixel)) return true;
+        set_error("mount: the dark frame does not have the clip's geometry (%dx%d at %d bits)", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes,
+                  fh.rawi_hdr.raw_info.bits_per_pixel);
+        return false;
+    }, [&](Mount &m) { m.dark = dark; });
 }
 
 int mlvfs_amd_mount_set_flat(void *mount, const mlvfs_amd_flat_t *flat)
 {
-    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
-    Mount &m = *(Mount *)mount;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (m.served) { set_error("mount: the handle has served frames already: the flat field cannot change any more"); return MLVFS_AMD_ERR_ARG; }
-    frame_headers fh;
-    if (flat && mlvfs_amd_mlv_frame_count(m.reader) > 0) {
-        if (!mlvfs_amd_mlv_frame_headers(m.reader, 0, &fh)) { set_error("mount: frame 0 has no usable headers"); return MLVFS_AMD_ERR_ARG; }
-        if (!flatfield_fits(flat, fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) {
-            set_error("mount: the flat field does not have the clip's geometry (%dx%d)", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
-            return MLVFS_AMD_ERR_ARG;
-        }
-    }
-    m.flat = flat;
-    return MLVFS_AMD_OK;
+    return mount_set(mount, "the flat field", flat != nullptr, [&](const frame_headers &fh) {
+        if (flatfield_fits(flat, fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) return true;
+        set_error("mount: the flat field does not have the clip's geometry (%dx%d)", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
+        return false;
+    }, [&](Mount &m) { m.flat = flat; });
 }
 
 int mlvfs_amd_mount_set_proxy(void *mount, int factor)
 {
-    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (factor != 1 && factor != 2) { set_error("mount: a proxy factor of %d (1: off, 2: half size)", factor); return MLVFS_AMD_ERR_ARG; }
-    Mount &m = *(Mount *)mount;
-    std::lock_guard<std::mutex> lk(m.mu);
-    if (m.served) { set_error("mount: the handle has served frames already: the proxy cannot change any more"); return MLVFS_AMD_ERR_ARG; }
-    frame_headers fh;
-    if (factor == 2 && mlvfs_amd_mlv_frame_count(m.reader) > 0) {
-        if (!mlvfs_amd_mlv_frame_headers(m.reader, 0, &fh)) { set_error("mount: frame 0 has no usable headers"); return MLVFS_AMD_ERR_ARG; }
+    if (mount && factor != 1 && factor != 2) { set_error("mount: a proxy factor of %d (1: off, 2: half size)", factor); return MLVFS_AMD_ERR_ARG; }
+    return mount_set(mount, "the proxy", factor == 2, [&](const frame_headers &fh) {
         int pw, ph;
-        if (!proxy_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, &pw, &ph)) {
-            set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
-            return MLVFS_AMD_ERR_ARG;
-        }
-    }
-    m.proxy = factor;
-    return MLVFS_AMD_OK;
+        if (proxy_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, &pw, &ph)) return true;
+        set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
+        return false;
+    }, [&](Mount &m) { m.proxy = factor; });
 }
 
 size_t mlvfs_amd_mount_dng_size(const void *mount, int index)
@@ -538,10 +528,8 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
     if (lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
     m.served = true;
-    DarkFrameDev dark{};
-    int rc = m.dark ? darkframe_on_device(m.dark, c, w, h, bpp, &dark) : MLVFS_AMD_OK;
-    FlatFieldDev flat{ nullptr, 0, (1 << bpp) - 1 };
-    if (rc == MLVFS_AMD_OK && m.flat) rc = flatfield_on_device(m.flat, c, w, h, &flat.d_gain);
+    Calib cal;
+    int rc = calib_on_device(m.dark, m.flat, c, w, h, bpp, 0, &cal);
     if (rc == MLVFS_AMD_OK) rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
     if (rc == MLVFS_AMD_OK && rgb_gain) rc = m.ensure_rgb(batch_frames);
     for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
@@ -551,11 +539,10 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             if (!cached_bad_clip(&fh[f0], c, m.o.fix_bad_pixels == 2, &known)) n = 1;     // until the map exists: strictly in serve order
         }
         if (m.flat) {                                                                      // the frames' own black level: one per load
-            flat.black = fh[f0].rawi_hdr.raw_info.black_level;
-            for (int k = 1; k < n; k++) if (fh[f0 + k].rawi_hdr.raw_info.black_level != flat.black) { n = k; break; }
+            cal.black = fh[f0].rawi_hdr.raw_info.black_level;
+            for (int k = 1; k < n; k++) if (fh[f0 + k].rawi_hdr.raw_info.black_level != cal.black) { n = k; break; }
         }
-        rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream, m.dark ? &dark : nullptr,
-                               m.flat ? &flat : nullptr);
+        rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream, &cal);
         if (rc == MLVFS_AMD_OK) {
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,

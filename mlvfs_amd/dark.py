@@ -1,4 +1,4 @@
-"""Dark frames (mlvfs_amd_dark_*, csrc/dark.cpp, csrc/k_dark.hip): a sensor's fixed offset pattern, subtracted on the GPU before
+"""Dark frames (mlvfs_amd_dark_*, csrc/cal.cpp, csrc/k_cal.hip): a sensor's fixed offset pattern, subtracted on the GPU before
 any other stage looks at the pixels.
 
     out     = clamp(px - dark + black_d, 0, 2^bpp - 1)          black_d: the black level of the clip the plane was averaged from

@@ -1,4 +1,4 @@
-"""Flat fields (mlvfs_amd_flat_*, csrc/flat.cpp, csrc/k_flat.hip): gain correction against a clip of an evenly lit target -- vignetting,
+"""Flat fields (mlvfs_amd_flat_*, csrc/cal.cpp, csrc/k_cal.hip): gain correction against a clip of an evenly lit target -- vignetting,
 dust shadows, per-pixel and per-column gain -- applied on the GPU directly after the dark frame and before any other stage.
 
     s[p]    = max(F[p] - black_f, 1)                                black_f: the black level of the clip F was averaged from

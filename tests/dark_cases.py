@@ -1,4 +1,4 @@
-"""Cases and the numpy oracle of dark-frame subtraction and averaging (csrc/dark.cpp, csrc/k_dark.hip), shared by
+"""Cases and the numpy oracle of dark-frame subtraction and averaging (csrc/cal.cpp, csrc/k_cal.hip), shared by
 tests/test_dark_cases.py (CPU: the cases really test something) and tests/test_gpu_dark.py.
 
     out     = clamp(px - dark + black_d, 0, 2^bpp - 1)
@@ -126,7 +126,7 @@ def clip_case(kind="plain", n=5, w=W, h=H, black_d=BLACK):
 
 
 # Other bit depths and a size that is no multiple of 16 pixels, through the reader's load (mount, transcoder): 12 and 10 bits take
-# k_dark_unpack_x16<12 | 10>; 16 bits and 30 x 12 take the two-pass fallback of launch_dark_unpack (k_unpack_generic, then k_dark_sub)
+# k_cal_unpack_x16<12 | 10, true, false>; 16 bits and 30 x 12 take the two-pass fallback of launch_cal_unpack (k_unpack_generic, then k_cal_apply)
 DEPTH_CASES = [(W, H, 12), (W, H, 10), (64, 48, 16), (30, 12, 14), (30, 12, 12)]
 
 

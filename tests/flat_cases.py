@@ -1,4 +1,4 @@
-"""Cases and the numpy oracle of flat-field correction (csrc/flat.cpp, csrc/k_flat.hip), shared by
+"""Cases and the numpy oracle of flat-field correction (csrc/cal.cpp, csrc/k_cal.hip), shared by
 tests/test_flat_cases.py (CPU: the cases really test something), tests/test_flat_host.py and tests/test_gpu_flat.py.
 
     s[p]    = max(F[p] - black_f, 1)

@@ -56,7 +56,7 @@ def test_every_depth_case_clamps_both_ways_and_takes_the_path_it_is_there_for(w,
         assert lo > 0 and hi > 0 and mid > f.size // 2, (lo, hi, mid)
         assert int(f.max()) <= top and int(p.max()) == top and int(p.min()) == 0 and not np.array_equal(f, p)
     assert (w * h * bpp) % 16 == 0                                        # the clip's frame_size holds every pixel
-    fused = bpp in (10, 12, 14) and (w * h) % 16 == 0                      # launch_dark_unpack's choice (csrc/k_dark.hip)
+    fused = bpp in (10, 12, 14) and (w * h) % 16 == 0                      # launch_cal_unpack's choice (csrc/k_cal.hip)
     assert fused == ((w, h, bpp) in [(dc.W, dc.H, 12), (dc.W, dc.H, 10)])
     assert {b for _, _, b in dc.DEPTH_CASES if b != 14} == {10, 12, 16}
 

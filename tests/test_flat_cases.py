@@ -154,5 +154,5 @@ def test_every_depth_case_differs_and_takes_the_path_it_is_there_for(w, h, bpp, 
     for f, p in zip(frames, pre):
         assert int(f.max()) <= top and int(p.max()) == top and int(p.min()) == 0 and (f != p).mean() > 0.5
     assert (w * h * bpp) % 16 == 0
-    fused = bpp in (10, 12, 14) and (w * h) % 16 == 0                       # launch_flat_unpack's choice (csrc/k_flat.hip)
+    fused = bpp in (10, 12, 14) and (w * h) % 16 == 0                       # launch_cal_unpack's choice (csrc/k_cal.hip)
     assert fused == ((w, h, bpp) in [(dc.W, dc.H, 12), (dc.W, dc.H, 10)])

@@ -1,4 +1,4 @@
-"""Flat fields, the library's host code (csrc/flat.cpp; no GPU): mlvfs_amd_flat_create and mlvfs_amd_flat_gain against the numpy
+"""Flat fields, the library's host code (csrc/cal.cpp; no GPU): mlvfs_amd_flat_create and mlvfs_amd_flat_gain against the numpy
 oracle of tests/flat_cases.py, every refusal of the host and device entry points (before any device work), the export table and the
 Python binding -- and the same planes once more through a stand-alone C++ program (tests/flat_host_check.cpp) built with
 -fsanitize=address,undefined against the sanitizer build of the host code (`make hostcheck`, built here if it is not yet).  The GPU side: tests/test_gpu_flat.py."""

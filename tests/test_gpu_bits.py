@@ -206,6 +206,20 @@ def test_the_dark_frame_is_subtracted_before_the_shift(gpu, request, tmp_path, k
     check_output(reference, tmp_path, src, tmp_path / "out", stats, pre, 14, 12, lj92_out, ("dark", 14, 12))
 
 
+@pytest.mark.parametrize("kind", ["plain", "lj92"])
+@pytest.mark.parametrize("lj92_out", [False, True], ids=["plain", "lj92"])
+def test_a_30x12_clip_with_a_dark_frame(gpu, request, tmp_path, kind, lj92_out):
+    """no multiple of 16 pixels, the subtraction in every pixel-per-lane form: inside k_mlv_repack_generic (plain -> plain), behind the
+    generic unpack and in front of the in-place shift (plain -> lj92), and in place behind the LJ92 decoder (lj92 -> both)"""
+    reference = request.getfixturevalue("reference") if lj92_out else None
+    frames, plane, black_d, pre = dc.depth_case(30, 12, 14)
+    src = bc.write_clip(tmp_path / "card", frames, 14, kind)
+    with Dark.from_plane(plane, 14, black_d) as dark:
+        stats = transcode(src, tmp_path / "out", lj92_out, 12, 2, dark)
+    assert any(not np.array_equal(bc.convert(p, 14, 12), bc.convert(f, 14, 12)) for p, f in zip(pre, frames))
+    check_output(reference, tmp_path, src, tmp_path / "out", stats, pre, 14, 12, lj92_out, ("small dark", 14, 12))
+
+
 def files_of(d):
     return {n: open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d))}
 

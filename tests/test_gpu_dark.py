@@ -1,4 +1,4 @@
-"""Dark-frame subtraction and averaging on the GPU (csrc/dark.cpp, csrc/k_dark.hip): the kernels against numpy, and a dark frame in
+"""Dark-frame subtraction and averaging on the GPU (csrc/cal.cpp, csrc/k_cal.hip): the kernels against numpy, and a dark frame in
 the mount and in the transcoder against the reference's own process_frame text (oracle/_ref/ref_host_ref) on clips whose payloads
 were subtracted beforehand with numpy (tests/dark_cases.py; tests/test_dark_cases.py shows on the CPU that those cases clamp both
 ways, hit the rounding boundary and differ from their sources)."""
@@ -186,7 +186,7 @@ def test_the_reference_text_serves_the_output_as_it_serves_the_subtracted_clip(g
 # ---- 4b. other bit depths and the two-pass fallback, through the reader's load ------------------------------------------------
 @pytest.mark.parametrize("w,h,bpp", dc.DEPTH_CASES, ids=lambda v: str(v))
 def test_plain_output_with_a_dark_frame_at_other_depths_and_sizes(gpu, tmp_path, w, h, bpp):
-    """12 and 10 bits: k_dark_unpack_x16<12 | 10>; 16 bits and 30 x 12: k_unpack_generic, then k_dark_sub.  Every payload is the
+    """12 and 10 bits: k_cal_unpack_x16<12 | 10, true, false>; 16 bits and 30 x 12: k_unpack_generic, then k_cal_apply.  Every payload is the
     packed numpy-subtracted frame."""
     frames, plane, black_d, pre = dc.depth_case(w, h, bpp)
     src = dc.write_clip(tmp_path / "card", frames, bpp=bpp)

@@ -1,4 +1,4 @@
-"""Flat-field correction on the GPU (csrc/flat.cpp, csrc/k_flat.hip): the gain kernels and the apply kernels against
+"""Flat-field correction on the GPU (csrc/cal.cpp, csrc/k_cal.hip): the gain kernels and the apply kernels against
 numpy (tests/flat_cases.py), and a flat field -- with and without a dark frame -- in the mount and in the transcoder against the
 reference's own process_frame text (oracle/_ref/ref_host_ref) and the reference's encoder on clips whose payloads were corrected
 beforehand with numpy.  tests/test_flat_cases.py shows on the CPU that those cases reach the cap, s = 1, both roundings, both clamps,
@@ -79,8 +79,8 @@ def test_gain_of_a_clip_equals_the_host_and_numpy(gpu, request, tmp_path, w, h, 
 # ---- 2. mlvfs_amd_flat_apply_dev against numpy --------------------------------------------------------------------------------
 @pytest.mark.parametrize("w,h,bpp,n,dark", fc.APPLY_CASES, ids=lambda v: str(v))
 def test_apply_dev_equals_numpy(gpu, w, h, bpp, n, dark):
-    """Frames at a padded stride; at byte offset 0 (16 x 2, 48 x 6 and 416 x 264 up to 14 bits take k_flat_apply_x16<DARK>) and 2,
-    2 x 2, 30 x 10 and every 16-bit case (k_flat_apply_generic: 64-bit products); the flat plane is a 14-bit one whatever the
+    """Frames at a padded stride; at byte offset 0 (16 x 2, 48 x 6 and 416 x 264 up to 14 bits take k_cal_apply_x16<DARK, true>) and 2,
+    2 x 2, 30 x 10 and every 16-bit case (k_cal_apply_generic: 64-bit products); the flat plane is a 14-bit one whatever the
     frames' depth; no byte outside the frames changes."""
     import torch
     c = fc.apply_case(w, h, bpp, n, dark)
@@ -140,7 +140,7 @@ def planes_of(plane_d, bpp, black_d):
 @pytest.mark.parametrize("dark", [False, True], ids=["flat", "dark+flat"])
 @pytest.mark.parametrize("w,h,bpp", fc.DEPTH_CASES, ids=lambda v: str(v))
 def test_the_load_at_other_depths_and_sizes(gpu, tmp_path, w, h, bpp, dark):
-    """12 and 10 bits at 416 x 264: k_flat_unpack_x16<12 | 10, DARK>; 16 bits and 30 x 12: k_unpack_generic, then the apply pass.  The
+    """12 and 10 bits at 416 x 264: k_cal_unpack_x16<12 | 10, DARK, true>; 16 bits and 30 x 12: k_unpack_generic, then the apply pass.  The
     flat is a 14-bit one.  The mount without options against the reference's process_frame text on the pre-corrected clip (header and
     pixels), and the plain transcode against the packed corrected frames."""
     need_hosts()
@@ -194,6 +194,7 @@ MOUNT_CASES = [
     ("plain", "lj92", False, FULL),
     ("plain", "plain", True, FULL),
     ("plain", "lj92", True, FULL),                                           # dark and flat in ONE pass behind the decoder
+    ("plain", "lzma", True, FULL),
     ("plain", "plain", False, dict(pnoise=1, deflicker=3000)),
     ("dual_iso", "plain", False, dict(dual_iso=2)),
 ]
@@ -373,7 +374,7 @@ def test_a_batch_ends_where_the_black_level_changes(gpu, tmp_path, payload):
 # ---- 8. full size -------------------------------------------------------------------------------------------------------------
 def test_full_size_frames(gpu, tmp_path):
     """3584 x 1320, two frames, the 16-pixel forms: flat_apply_dev (with the dark frame in the same pass) against numpy, and the load
-    (k_flat_unpack_x16<14, true>) through one mount call without options against the same frames."""
+    (k_cal_unpack_x16<14, true, true>) through one mount call without options against the same frames."""
     import torch
     w, h = 3584, 1320
     frames, F, plane_d, pre = fc.clip_case("plain", n=2, w=w, h=h, dark=True)

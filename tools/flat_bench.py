@@ -1,13 +1,13 @@
-"""Flat fields at 3584x1320 (csrc/flat.cpp, csrc/k_flat.hip): the numbers of DESIGN.md 3.10.
+"""Flat fields at 3584x1320 (csrc/cal.cpp, csrc/k_cal.hip): the numbers of DESIGN.md 3.10.
 
     python tools/flat_bench.py [--frames 32] [--batch 8] [--reps 3] [--dir DIR] [--skip-kernels]
 
 1. Kernel times.  The tool starts ITSELF once more under `rocprofv3 --kernel-trace --stats` (a run of its own, no counters, the
    program behind `--`); that child runs, on 32 frames in batches of 8 and in one process,
        the mount without options: plain, with a dark frame, with a flat field, with both
-                                        k_unpack_x16<14> | k_dark_unpack_x16<14> | k_flat_unpack_x16<14, false> | k_flat_unpack_x16<14, true>
+                                        k_unpack_x16<14> | k_cal_unpack_x16<14, DARK, FLAT> for (true, false), (false, true), (true, true)
        mlvfs_amd_unpack_dev + mlvfs_amd_flat_apply_dev without and with a dark frame
-                                        k_unpack_x16<14>, k_flat_apply_x16<false | true> (the two passes the fused one replaces)
+                                        k_unpack_x16<14>, k_cal_apply_x16<false | true, true> (the two passes the fused one replaces)
        mlvfs_amd_flat_from_clip         k_unpack_x16<14>, k_dark_accum_x16, k_dark_mean, k_flat_chan_sums, k_flat_gain
    and the parent prints every kernel's time per frame side by side, with the spread of its launches, and the keep rule's verdict.
 2. The mount's frames per second with and without a flat field for cs5x5 + bad pixels + stripes, in alternating repetitions.
@@ -36,8 +36,8 @@ from mlvfs_amd.pipeline import MlvfsOptions
 
 W, H = 3584, 1320
 # (what a kernel's name in the profile starts with, launches that are one plane and not one batch)
-KERNELS = [("k_unpack_x16<14>", False), ("k_dark_unpack_x16<14>", False), ("k_flat_unpack_x16<14, false>", False), ("k_flat_unpack_x16<14, true>", False),
-           ("k_flat_apply_x16<false>", False), ("k_flat_apply_x16<true>", False), ("k_flat_chan_sums", True), ("k_flat_gain", True)]
+KERNELS = [("k_unpack_x16<14>", False), ("k_cal_unpack_x16<14, true, false>", False), ("k_cal_unpack_x16<14, false, true>", False), ("k_cal_unpack_x16<14, true, true>", False),
+           ("k_cal_apply_x16<false, true>", False), ("k_cal_apply_x16<true, true>", False), ("k_flat_chan_sums", True), ("k_flat_gain", True)]
 
 
 def dark_plane():
@@ -122,7 +122,7 @@ def kernel_report(a) -> bool:
                 print(f"  {want:30s} {calls:3d} launches   avg {avg:7.2f}   min {lo:7.2f}   max {hi:7.2f}   spread {hi - lo:6.2f}")
     if all(k in found for k, _ in KERNELS[:6]):
         u = found["k_unpack_x16<14>"]
-        for fused, apply in (("k_flat_unpack_x16<14, false>", "k_flat_apply_x16<false>"), ("k_flat_unpack_x16<14, true>", "k_flat_apply_x16<true>")):
+        for fused, apply in (("k_cal_unpack_x16<14, false, true>", "k_cal_apply_x16<false, true>"), ("k_cal_unpack_x16<14, true, true>", "k_cal_apply_x16<true, true>")):
             f, s = found[fused], found[apply]
             saved = u[0] + s[0] - f[0]
             print(f"  {fused} {f[0]:.2f} against k_unpack_x16<14> + {apply} {u[0] + s[0]:.2f} us per frame: {saved:.2f} saved;"
