@@ -225,7 +225,7 @@ inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 // A change of bit depth on the way (the transcoder, mlvfs_amd_mlv_transcode_bits; k_mlvpack.hip): plain and LZMA
 // payloads leave the load at out_bpp bits, shifted after the dark frame was subtracted -- as 16-bit frames, or (packed) as packed
 // payloads `dstride` bytes apart, ceil(w * h * out_bpp / 16) words each.  LJ92 payloads are not touched by it: their pixels are
-// shifted by the pass that follows the decoder (launch_mlv_pack_shift, launch_mlv_tile_shift).
+// shifted by the pass that follows the decoder (launch_mlv_pack, launch_mlv_tile).
 struct LoadBits {
     int out_bpp;
     bool packed;
@@ -249,19 +249,16 @@ int reader_read_list(const void *reader, const int *list, int count, uint8_t *ds
 // visit(chunk, position, tag, block size, the MLVI block's header or nullptr); false ends the walk
 void reader_walk_blocks(const void *reader, const std::function<bool(int, uint64_t, const uint8_t *, uint32_t, const mlv_file_hdr_t *)> &visit);
 std::mutex &reader_stage_mutex(const void *reader);
-// quadrant tiling and bit packing (k_mlvpack.hip)
-int launch_mlv_tile(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int nframes, hipStream_t stream);
-int launch_mlv_pack(const void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int nframes,
+// quadrant tiling and bit packing (k_mlvpack.hip), with a change of bit depth inside where one is asked for (d = out_bpp - bpp;
+// > 0: << d, < 0: >> -d, 0: none); neither writes its source
+int launch_mlv_tile(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int d, int nframes, hipStream_t stream);
+int launch_mlv_pack(const void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
                     hipStream_t stream);
-// the same passes with a change of bit depth inside (d = out_bpp - bpp; > 0: << d, < 0: >> -d), and packed -> packed in one pass
-int launch_mlv_shift(void *d_frames, size_t stride, uint32_t npix, int d, int nframes, hipStream_t stream);
+// packed payloads at one depth -> packed payloads or 16-bit frames at another, the dark frame (optional) subtracted on the way
 int launch_mlv_repack(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
                       const Calib *cal, hipStream_t stream);
 int launch_mlv_unpack_shift(const void *d_packed, size_t packed_stride, void *d_out, size_t out_stride, uint32_t npix, int bpp, int out_bpp,
                             int nframes, const Calib *cal, hipStream_t stream);
-int launch_mlv_pack_shift(void *d_frames, size_t stride, void *d_packed, size_t packed_stride, uint32_t npix, int bpp, int out_bpp, int nframes,
-                          hipStream_t stream);
-int launch_mlv_tile_shift(const void *d_frames, size_t stride, void *d_out, size_t out_stride, int w, int h, int d, int nframes, hipStream_t stream);
 void preload_k_mlvpack();
 // half-size Bayer proxies (k_proxy.hip): W' x H' of a w x h frame, false below 4x4 and from 2^27 pixels on; the binning pass
 inline bool proxy_geom(int w, int h, int *pw, int *ph)

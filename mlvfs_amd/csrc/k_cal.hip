@@ -86,10 +86,7 @@ __global__ __launch_bounds__(256) void k_cal_unpack_x16(const uint8_t *__restric
         if (DARK) { da = dark[(size_t)g * 2]; db = dark[(size_t)g * 2 + 1]; }
         unpack_x16<BPP>(s, px);
         uint4 lo, hi;
-        lo.x = px[0] | (px[1] << 16);   lo.y = px[2] | (px[3] << 16);
-        lo.z = px[4] | (px[5] << 16);   lo.w = px[6] | (px[7] << 16);
-        hi.x = px[8] | (px[9] << 16);   hi.y = px[10] | (px[11] << 16);
-        hi.z = px[12] | (px[13] << 16); hi.w = px[14] | (px[15] << 16);
+        join_x16(px, lo, hi);
         dst[(size_t)g * 2] = cal_px8<DARK, FLAT>(lo, da, ga, black_d, black, top);
         dst[(size_t)g * 2 + 1] = cal_px8<DARK, FLAT>(hi, db, gb, black_d, black, top);
     }
@@ -237,8 +234,6 @@ __global__ __launch_bounds__(256) void k_flat_gain(const uint16_t *__restrict__ 
 }
 
 // ---- the launchers ----------------------------------------------------------------------------------------------------------
-static uint32_t grid_x(uint32_t items, uint32_t cap) { return std::min<uint32_t>((items + 255) / 256, cap); }
-
 static bool aligned16(const void *p) { return (uintptr_t)p % 16 == 0; }          // (a stage that is off: nullptr)
 
 // what an x16 form asks of the descriptor: planes the library allocated itself are 16-byte aligned, and a gain's 32-bit products
@@ -281,9 +276,8 @@ int launch_cal_unpack(const void *d_packed, size_t packed_stride, void *d_out, s
                       const Calib &cal, hipStream_t stream)
 {
     if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
-    const bool fast = cal.on() && (bpp == 14 || bpp == 12 || bpp == 10) && cal.top == (1 << bpp) - 1 && npix % 16 == 0 &&
-                      ((uintptr_t)d_packed % 4 == 0) && aligned16(d_out) && planes_x16(cal) &&
-                      (nframes == 1 || (packed_stride % 4 == 0 && out_stride % 16 == 0));
+    const bool fast = cal.on() && fast_depth(bpp) && cal.top == (1 << bpp) - 1 && planes_x16(cal) &&
+                      fits_x16(npix, nframes, d_packed, packed_stride, 4, d_out, out_stride, 16);
     if (!fast) {
         if (int rc = launch_unpack(d_packed, packed_stride, d_out, out_stride, 0, npix, bpp, nframes, stream)) return rc;
         return launch_cal_apply(d_out, out_stride, npix, nframes, cal, stream);

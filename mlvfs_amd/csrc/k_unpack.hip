@@ -29,10 +29,7 @@ __global__ __launch_bounds__(256) void k_unpack_x16(const uint8_t *__restrict__ 
         for (int i = 0; i < NW; i++) s[i] = stream_word(src[(size_t)g * NW + i]);
         unpack_x16<BPP>(s, px);
         uint4 lo, hi;
-        lo.x = px[0] | (px[1] << 16);   lo.y = px[2] | (px[3] << 16);
-        lo.z = px[4] | (px[5] << 16);   lo.w = px[6] | (px[7] << 16);
-        hi.x = px[8] | (px[9] << 16);   hi.y = px[10] | (px[11] << 16);
-        hi.z = px[12] | (px[13] << 16); hi.w = px[14] | (px[15] << 16);
+        join_x16(px, lo, hi);
         dst[(size_t)g * 2] = lo;
         dst[(size_t)g * 2 + 1] = hi;
     }
@@ -60,18 +57,13 @@ int launch_unpack(const void *d_packed, size_t packed_stride, void *d_out, size_
 {
     if (npix == 0 || nframes <= 0) return MLVFS_AMD_OK;
     if (bpp < 1 || bpp > 16) { set_error("unsupported bits_per_pixel %d", bpp); return MLVFS_AMD_ERR_ARG; }
-    const bool fast = (bpp == 14 || bpp == 12 || bpp == 10) && first_px == 0 && npix % 16 == 0 && ((uintptr_t)d_packed % 4 == 0) &&
-                      ((uintptr_t)d_out % 16 == 0) && (nframes == 1 || (packed_stride % 4 == 0 && out_stride % 16 == 0));
-    if (fast) {
+    if (fast_depth(bpp) && first_px == 0 && fits_x16(npix, nframes, d_packed, packed_stride, 4, d_out, out_stride, 16)) {
         const uint32_t groups = npix / 16;
-        dim3 grid((groups + 255) / 256, nframes);
-        if (grid.x > 8192) grid.x = 8192;
         auto kern = bpp == 14 ? k_unpack_x16<14> : (bpp == 12 ? k_unpack_x16<12> : k_unpack_x16<10>);
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, (const uint8_t *)d_packed, packed_stride, (uint8_t *)d_out, out_stride, groups);
+        hipLaunchKernelGGL(kern, dim3(grid_x(groups, 8192), nframes), dim3(256), 0, stream, (const uint8_t *)d_packed, packed_stride,
+                           (uint8_t *)d_out, out_stride, groups);
     } else {
-        dim3 grid((npix + 255) / 256, nframes);
-        if (grid.x > 16384) grid.x = 16384;
-        hipLaunchKernelGGL(k_unpack_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_packed, packed_stride,
+        hipLaunchKernelGGL(k_unpack_generic, dim3(grid_x(npix, 16384), nframes), dim3(256), 0, stream, (const uint8_t *)d_packed, packed_stride,
                            (uint8_t *)d_out, out_stride, first_px, npix, bpp);
     }
     MLV_HIP(hipGetLastError());

@@ -23,13 +23,14 @@
 // after the dark frame, inside a pass its route makes anyway (k_mlvpack.hip), and every RAWI block of another depth is rewritten
 // (mlvfs_amd_rawi_set_bits):
 //   plain / LZMA -> plain   upload -> k_mlv_repack (unpack, subtract, shift, pack in one pass) -> file
-//   plain / LZMA -> LJ92    upload -> k_mlv_unpack_shift -> k_mlv_tile -> the encoder at out_bpp
-//   LJ92 -> plain           GPU decode -> k_cal_apply if a dark frame is set -> k_mlv_pack_shift -> file
-//   LJ92 -> LJ92            GPU decode -> k_cal_apply if set -> k_mlv_tile_shift -> the encoder at out_bpp
-// Frames already at out_bpp, and every frame when out_bpp is 0, take the routes above unchanged.
+//   plain / LZMA -> LJ92    upload -> k_mlv_unpack_shift -> k_mlv_tile (frames at out_bpp already: no shift) -> the encoder at out_bpp
+//   LJ92 -> plain           GPU decode -> k_cal_apply if a dark frame is set -> k_mlv_pack with the shift inside -> file
+//   LJ92 -> LJ92            GPU decode -> k_cal_apply if set -> k_mlv_tile with the shift inside -> the encoder at out_bpp
+// launch_mlv_tile and launch_mlv_pack are told the depth of the frames in HBM and the depth to write, and shift where the two differ:
+// frames already at out_bpp, and every frame when out_bpp is 0, run the instantiations without a shift.
 // With a flat field (mlvfs_amd_mlv_transcode_cal) reader_load_list applies its gain after the dark frame (stage 0b:
-// k_cal.hip) and delivers corrected 16-bit frames at the source's depth; k_mlv_tile(_shift) or k_mlv_pack(_shift) follow on every
-// route, so a plain or LZMA source to plain output pays one pass more than k_mlv_repack.
+// k_cal.hip) and delivers corrected 16-bit frames at the source's depth; k_mlv_tile or k_mlv_pack follow on every route, shifting
+// where the depth changes, so a plain or LZMA source to plain output pays one pass more than k_mlv_repack.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -246,20 +247,18 @@ int batch_device(Job &j, const std::vector<int> &list)
     rc = reader_load_list(j.reader, list.data(), n, f.w, f.h, f.bpp, repacked ? d.d_aux : d.d_frames, repacked ? pstride : dstride, j.io_threads, s,
                           true, &cal, in_load ? &bits : nullptr);
     if (rc) return rc;
-    const int shift = in_load ? 0 : f.obpp - f.bpp;                    // what is left to do here
+    const int loaded = in_load ? f.obpp : f.bpp;                       // the depth of the frames in HBM: the pass that follows does the rest
     if (plain) {
         const size_t bytes = plain_bytes(f);
         if ((rc = d.stage(pstride * n))) return rc;
-        if (!repacked && (rc = shift ? launch_mlv_pack_shift(d.d_frames, dstride, d.d_aux, pstride, npix, f.bpp, f.obpp, n, s)
-                                     : launch_mlv_pack(d.d_frames, dstride, d.d_aux, pstride, npix, f.bpp, n, s))) return rc;
+        if (!repacked && (rc = launch_mlv_pack(d.d_frames, dstride, d.d_aux, pstride, npix, loaded, f.obpp, n, s))) return rc;
         MLV_HIP(hipMemcpyAsync(d.h_stage, d.d_aux, pstride * n, hipMemcpyDeviceToHost, s));
         MLV_HIP(hipStreamSynchronize(s));
         for (int k = 0; k < n; k++) j.ready[list[k]] = { d.h_stage + (size_t)k * pstride, bytes };
         return MLVFS_AMD_OK;
     }
     if ((rc = DevRoom::grow(&d.d_fixed, &d.fixed_bytes, lje_fixed_bytes(npix, n)))) return rc;
-    if ((rc = shift ? launch_mlv_tile_shift(d.d_frames, dstride, d.d_aux, dstride, f.w, f.h, shift, n, s)
-                    : launch_mlv_tile(d.d_frames, dstride, d.d_aux, dstride, f.w, f.h, n, s))) return rc;
+    if ((rc = launch_mlv_tile(d.d_frames, dstride, d.d_aux, dstride, f.w, f.h, f.obpp - loaded, n, s))) return rc;
     std::vector<const uint16_t *> src(n);
     for (int k = 0; k < n; k++) src[k] = (const uint16_t *)((const uint8_t *)d.d_aux + (size_t)k * dstride);
     std::vector<LjeResult> res(n);
@@ -499,35 +498,39 @@ int transcode(const void *reader, const char *out_path, int payload, int out_bpp
     return MLVFS_AMD_OK;
 }
 
+// what the entry points call: an exception (allocations sized from the file) becomes an error code
+int guarded(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark, const mlvfs_amd_flat_t *flat,
+            int batch_frames, int io_threads, long long stats[4])
+{
+    try { return transcode(reader, out_path, payload, out_bpp, dark, flat, batch_frames, io_threads, stats); }
+    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
+}
+
 }  // namespace
 
 extern "C" {
 
 int mlvfs_amd_mlv_transcode(const void *reader, const char *out_path, int payload, int batch_frames, int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, 0, nullptr, nullptr, batch_frames, io_threads, stats); }
-    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }    // (allocations sized from the file)
+    return guarded(reader, out_path, payload, 0, nullptr, nullptr, batch_frames, io_threads, stats);
 }
 
 int mlvfs_amd_mlv_transcode_dark(const void *reader, const char *out_path, int payload, const mlvfs_amd_dark_t *dark, int batch_frames,
                                  int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, 0, dark, nullptr, batch_frames, io_threads, stats); }
-    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
+    return guarded(reader, out_path, payload, 0, dark, nullptr, batch_frames, io_threads, stats);
 }
 
 int mlvfs_amd_mlv_transcode_bits(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark, int batch_frames,
                                  int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, out_bpp, dark, nullptr, batch_frames, io_threads, stats); }
-    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
+    return guarded(reader, out_path, payload, out_bpp, dark, nullptr, batch_frames, io_threads, stats);
 }
 
 int mlvfs_amd_mlv_transcode_cal(const void *reader, const char *out_path, int payload, int out_bpp, const mlvfs_amd_dark_t *dark,
                                 const mlvfs_amd_flat_t *flat, int batch_frames, int io_threads, long long stats[4])
 {
-    try { return transcode(reader, out_path, payload, out_bpp, dark, flat, batch_frames, io_threads, stats); }
-    catch (const std::exception &e) { set_error("mlv transcode: %s", e.what()); return MLVFS_AMD_ERR_NOMEM; }
+    return guarded(reader, out_path, payload, out_bpp, dark, flat, batch_frames, io_threads, stats);
 }
 
 int mlvfs_amd_rawi_set_bits(mlv_rawi_hdr_t *rawi, int out_bpp)
@@ -590,7 +593,7 @@ int mlvfs_amd_lj92_tile_dev(const void *d_frames, size_t stride, void *d_out, si
     if (nframes == 0) return MLVFS_AMD_OK;
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
-    return launch_mlv_tile(d_frames, stride, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
+    return launch_mlv_tile(d_frames, stride, d_out, out_stride, width, height, 0, nframes, pick_stream(stream, c));
 }
 
 int mlvfs_amd_pack_dev(const mlvfs_amd_geom_t *geom, const void *d_frames, size_t stride, void *d_packed, size_t packed_stride, int nframes,
@@ -609,7 +612,7 @@ int mlvfs_amd_pack_dev(const mlvfs_amd_geom_t *geom, const void *d_frames, size_
     if (nframes == 0) return MLVFS_AMD_OK;
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
-    return launch_mlv_pack(d_frames, stride, d_packed, packed_stride, npix, geom->bpp, nframes, pick_stream(stream, c));
+    return launch_mlv_pack(d_frames, stride, d_packed, packed_stride, npix, geom->bpp, geom->bpp, nframes, pick_stream(stream, c));
 }
 
 }  // extern "C"

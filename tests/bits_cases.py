@@ -126,9 +126,16 @@ def repack_frames(w, h, bpp, n, seed=0):
     return [f.reshape(h, w) for f in frames]
 
 
-def small_frames(bpp=14, n=3):
-    """30 x 12: no multiple of 16 pixels (w * h a multiple of 8: a 14-, 12- or 10-bit payload ends on a whole word)"""
-    return source_frames(bpp, n, 30, 12)
+def small_frames(bpp=14, n=3, w=30, h=12):
+    """30 x 12: no multiple of 16 pixels (w * h a multiple of 8: a 14-, 12- or 10-bit payload ends on a whole word).
+    40 x 12 (SMALL_X8): whole groups of 16 pixels in rows of 8k + 8 -- the tiling's 8-pixel form and the other passes' 16-pixel forms."""
+    return source_frames(bpp, n, w, h)
+
+
+SMALL_X8 = (40, 12)
+# the 40 x 12 clips test_gpu_bits.py rewrites to LJ92: (payload kind, source depth, out_bpp) -- an LJ92 source narrowed and widened
+# (the tiling shifts, d < 0 and d > 0), and a 10-bit plain source (the one source depth CLIP_DEPTHS does not have)
+SMALL_X8_CLIPS = [("lj92", 14, 12), ("lj92", 12, 14), ("plain", 10, 12)]
 
 
 def full_size_frames():

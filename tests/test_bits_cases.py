@@ -194,6 +194,20 @@ def test_widening_cases_use_the_whole_range():
             assert int(f.max()) == (1 << bpp) - 1 and int(conv.max()) == ((1 << bpp) - 1) << (out_bpp - bpp) and int(conv.min()) == 0
 
 
+@pytest.mark.parametrize("kind,bpp,out_bpp", bc.SMALL_X8_CLIPS, ids=[f"{k}:{b}->{o}" for k, b, o in bc.SMALL_X8_CLIPS])
+def test_the_40x12_cases_truncate_or_use_the_whole_range_and_encode(kind, bpp, out_bpp):
+    """what the 416 x 264 and 30 x 12 material shows above, for the 40 x 12 frames"""
+    frames = bc.small_frames(bpp, 3, *bc.SMALL_X8)
+    assert frames[0].shape == (12, 40)
+    if out_bpp < bpp:
+        assert_narrowing_material(frames, bpp, out_bpp, "40x12")
+    for f in frames:
+        conv = bc.convert(f, bpp, out_bpp)
+        assert int(f.max()) == (1 << bpp) - 1 and int(f.min()) == 0
+        assert int(conv.max()) == bc.shift((1 << bpp) - 1, out_bpp - bpp) and int(conv.min()) == 0
+        assert class_of(quadrants(conv), out_bpp) <= 15                     # the reference's encoder gets this frame
+
+
 # ---- what the GPU file hands to the reference's encoder -----------------------------------------------------------------------
 def test_every_frame_handed_to_the_reference_encoder_is_one_it_encodes():
     for bpp, out_bpp in bc.CLIP_DEPTHS:

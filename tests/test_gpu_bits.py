@@ -163,6 +163,17 @@ def test_a_30x12_clip(gpu, request, tmp_path, kind, lj92_out):
     check_output(reference, tmp_path, src, tmp_path / "out", stats, frames, 14, 12, lj92_out, ("small", 14, 12))
 
 
+@pytest.mark.parametrize("kind,bpp,out_bpp", bc.SMALL_X8_CLIPS, ids=[f"{k}:{b}->{o}" for k, b, o in bc.SMALL_X8_CLIPS])
+def test_a_40x12_clip_to_lj92(gpu, reference, tmp_path, kind, bpp, out_bpp):
+    """whole groups of 16 pixels in rows of 8k + 8.  An LJ92 source: the tiling's 8-pixel form with the shift inside, to the right
+    (14 -> 12) and to the left (12 -> 14).  A 10-bit plain source: k_mlv_unpack_shift_x16<10>, then the 8-pixel form without a shift.
+    (the instantiations no other case selects)"""
+    frames = bc.small_frames(bpp, 3, *bc.SMALL_X8)
+    src = bc.write_clip(tmp_path / "card", frames, bpp, kind)
+    stats = transcode(src, tmp_path / "out", True, out_bpp)
+    check_output(reference, tmp_path, src, tmp_path / "out", stats, frames, bpp, out_bpp, True, ("40x12", bpp, out_bpp))
+
+
 TIES = [("plain", True, 14, 12), ("plain", False, 14, 10), ("lj92", False, 14, 12), ("plain", True, 12, 14)]
 
 

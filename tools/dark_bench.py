@@ -6,7 +6,7 @@
    program behind `--`); that child runs, on 32 frames in batches of 8 and in one process,
        the mount without options, without and with a dark frame    k_unpack_x16<14>  |  k_cal_unpack_x16<14, true, false> (the fused pass)
        mlvfs_amd_unpack_dev + mlvfs_amd_dark_subtract_dev          k_unpack_x16<14>, k_cal_apply_x16<true, false> (the two passes it replaces)
-       mlvfs_amd_lj92_tile_dev                                     k_mlv_tile_x<16>
+       mlvfs_amd_lj92_tile_dev                                     k_mlv_tile_x<16, false>
        mlvfs_amd_dark_from_clip                                    k_unpack_x16<14>, k_dark_accum_x16, k_dark_mean
    and the parent prints every kernel's time per frame side by side, with the spread of its launches.
 2. The mount's frames per second with and without a dark frame for cs5x5 + bad pixels + stripes, in alternating repetitions.
@@ -33,7 +33,7 @@ from mlvfs_amd.mount import Mount
 from mlvfs_amd.pipeline import MlvfsOptions
 
 W, H = 3584, 1320
-KERNELS = ["k_unpack_x16<14>", "k_mlv_tile_x<16>", "k_cal_unpack_x16<14, true, false>", "k_cal_apply_x16<true, false>", "k_dark_accum_x16", "k_dark_mean"]
+KERNELS = ["k_unpack_x16<14>", "k_mlv_tile_x<16, false>", "k_cal_unpack_x16<14, true, false>", "k_cal_apply_x16<true, false>", "k_dark_accum_x16", "k_dark_mean"]
 
 
 def plane():
@@ -107,7 +107,7 @@ def kernel_report(a) -> bool:
                 found[want] = [float(row[k]) / 1e3 / per for k in ("AverageNs", "MinNs", "MaxNs")] + [int(row["Calls"])]
                 avg, lo, hi, calls = found[want]
                 print(f"  {want:24s} {calls:3d} launches   avg {avg:7.2f}   min {lo:7.2f}   max {hi:7.2f}   spread {hi - lo:6.2f}")
-    if all(k in found for k in KERNELS[:4] if k != "k_mlv_tile_x<16>"):
+    if all(k in found for k in KERNELS[:4] if k != "k_mlv_tile_x<16, false>"):
         u, f, s = found["k_unpack_x16<14>"], found["k_cal_unpack_x16<14, true, false>"], found["k_cal_apply_x16<true, false>"]
         print(f"  fused {f[0]:.2f} against two passes {u[0] + s[0]:.2f} us per frame: {u[0] + s[0] - f[0]:.2f} saved; the spread of k_unpack_x16<14>'s launches is {u[2] - u[1]:.2f}")
     return True

@@ -10,11 +10,11 @@ For the time per frame of k_mlv_tile / k_mlv_pack beside k_unpack_x16<14> on the
 --bits N (8..16; several may be given): the clip at another bit depth (mlvfs_amd_mlv_transcode_bits; the numbers of DESIGN.md 3.9).
 1. Kernel times.  The tool starts ITSELF once more under `rocprofv3 --kernel-trace --stats` (a run of its own, no counters, the
    program behind `--`); that child rewrites the clip, in one process and twice each (the second round is the warm one),
-       plain -> LJ92 at 14 bits                 k_unpack_x16<14>, k_mlv_tile_x<16>           (no conversion: the routes as they were)
+       plain -> LJ92 at 14 bits                 k_unpack_x16<14>, k_mlv_tile_x<16, false>    (no conversion: the routes as they were)
        plain -> plain at the first N            k_mlv_repack_x16<14, N>                      (unpack, shift and pack in one pass)
-       plain -> LJ92 at N                       k_mlv_unpack_shift_x16<14>, k_mlv_tile_x<16>
-       that LJ92 clip (14 bits) -> plain at N   k_mlv_pack_shift_x16<N>                      (the second of the two passes k_mlv_repack replaces)
-       that LJ92 clip -> LJ92 at N              k_mlv_tile_shift_x<16>
+       plain -> LJ92 at N                       k_mlv_unpack_shift_x16<14>, k_mlv_tile_x<16, false>
+       that LJ92 clip (14 bits) -> plain at N   k_mlv_pack_x16<N, true>                      (the second of the two passes k_mlv_repack replaces)
+       that LJ92 clip -> LJ92 at N              k_mlv_tile_x<16, true>
    and the parent prints every kernel's time per frame with the spread of its launches, and the fused pass beside the two it replaces.
 2. Frames per second and payload bytes out / in, best of --loops, for plain -> LJ92 at 14 bits (no conversion) and, for every N,
    plain -> plain and plain -> LJ92 at N, all in this one call."""
@@ -106,8 +106,8 @@ def kernel_report(a) -> bool:
         print("no kernel_stats.csv under", out, [os.path.relpath(f, out) for f in glob.glob(os.path.join(out, "**", "*"), recursive=True)][:20])
         return True
     rows = list(csv.DictReader(open(stats[0])))
-    fused, second = f"k_mlv_repack_x16<14,{n}>", f"k_mlv_pack_shift_x16<{n}>"
-    kernels = ["k_unpack_x16<14>", "k_mlv_tile_x<16>", fused, "k_mlv_unpack_shift_x16<14>", second, "k_mlv_tile_shift_x<16>"]
+    fused, second = f"k_mlv_repack_x16<14,{n}>", f"k_mlv_pack_x16<{n},true>"
+    kernels = ["k_unpack_x16<14>", "k_mlv_tile_x<16,false>", fused, "k_mlv_unpack_shift_x16<14>", second, "k_mlv_tile_x<16,true>"]
     print(f"kernel times, {a.frames} frames in batches of {a.batch} (one launch = one batch; us per frame = launch / {a.batch}):")
     found = {}
     for want in kernels:
