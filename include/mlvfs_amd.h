@@ -457,8 +457,9 @@ void mlvfs_amd_dropin_transfers(long long out[4]);
  * {inside dng_get_image_data, of it the upload call, of it the wait for the upload's end, inside the recorded stage calls, inside
  * mlvfs_amd_frame_end, of it the fused launch's calls, of it the download call + the wait for it, number of frames}. */
 void mlvfs_amd_dropin_profile(double out[8]);
-/* Test hook: the calling thread's next fused launch of a bracketed frame (what = 1) or next frame download (what = 2) reports a HIP
- * error without touching the device.  What the caller then finds -- a zeroed frame and one line on stderr, never the bytes its
+/* Test hook: the calling thread's next fused launch of a bracketed frame (what = 1), next frame download (what = 2) or next growth
+ * of one of the library's device or page-locked buffers (what = 3: the old block is freed, nothing is allocated) reports a HIP
+ * error without touching the device.  What the caller of a drop-in stage then finds -- a zeroed frame and one line on stderr, never the bytes its
  * malloc returned -- is the library's failure policy ("When the device fails"; tests/test_failure_policy.py). */
 void mlvfs_amd_test_fail_next(int what);
 /* Test hook, host only: can the dither of stripes_compute_correction be taken from the application's libc generator in bulk

@@ -94,8 +94,8 @@ int clip_mean_dev(const void *reader, int first, int count, const CalPlane &p, i
     const uint32_t npix = (uint32_t)p.w * (uint32_t)p.h;
     const size_t dstride = up256((size_t)npix * 2);
     DevBuf frames, sums;
-    MLV_HIP(hipMalloc(&frames.p, dstride * (size_t)batch));
-    MLV_HIP(hipMalloc(&sums.p, (size_t)npix * 4));
+    if (const int rc0 = frames.reserve(dstride * (size_t)batch)) return rc0;
+    if (const int rc0 = sums.reserve((size_t)npix * 4)) return rc0;
     MLV_HIP(hipMemsetAsync(sums.p, 0, (size_t)npix * 4, s));
     int rc = MLVFS_AMD_OK;
     std::vector<int> kind(count);
@@ -123,7 +123,7 @@ int mean_of_clip(const void *reader, int first, int count, int batch, int io_thr
     if (!c) return MLVFS_AMD_ERR_HIP;
     hipStream_t s = c->stream;
     DevBuf mean;
-    MLV_HIP(hipMalloc(&mean.p, (size_t)npix * 2));
+    if (const int rc0 = mean.reserve((size_t)npix * 2)) return rc0;
     const int rc = clip_mean_dev(reader, first, count, d, batch, io_threads, (uint16_t *)mean.p, s);
     if (rc != MLVFS_AMD_OK) return rc;
     d.plane.resize(npix);
@@ -166,9 +166,9 @@ int gains_of_clip(const void *reader, int first, int count, const mlvfs_amd_dark
     Calib cal;
     if (int rc = calib_on_device(dark, nullptr, c, f.w, f.h, f.bpp, f.black, &cal)) return rc;
     DevBuf mean, out, sums;                             // out: [the gain plane][M_c[4]]
-    MLV_HIP(hipMalloc(&mean.p, gain_bytes));
-    MLV_HIP(hipMalloc(&out.p, gain_bytes + 16));
-    MLV_HIP(hipMalloc(&sums.p, 4 * sizeof(unsigned long long)));
+    if (const int rc0 = mean.reserve(gain_bytes)) return rc0;
+    if (const int rc0 = out.reserve(gain_bytes + 16)) return rc0;
+    if (const int rc0 = sums.reserve(4 * sizeof(unsigned long long))) return rc0;
     int rc = clip_mean_dev(reader, first, count, f, batch, io_threads, (uint16_t *)mean.p, s);
     if (rc == MLVFS_AMD_OK) rc = launch_cal_apply(mean.p, 0, npix, 1, cal, s);
     if (rc == MLVFS_AMD_OK)

@@ -56,12 +56,12 @@ struct Clip {
     std::vector<int32_t> xy;
     int rules = 0, dual_iso = 0;
     int n_entries = 0, n_levels = 0, n_level0 = 0;       // n_level0: entries without a dependency (they come first)
-    PixEntry *d_entries = nullptr;
-    int *d_level_off = nullptr;
+    DevBuf d_entries;                // PixEntry[n_entries], then {pos, kind | emit << 8} per entry
+    DevBuf d_level_off;              // int[n_levels + 1]
     // per tile geometry: the cells with repaired pixels, listed tile by tile (a cell in the halo of a neighbouring tile is
     // listed there too)
-    int *d_tile_off[FRAME_GEOS] = { nullptr, nullptr };
-    CellRec *d_tile_rec[FRAME_GEOS] = { nullptr, nullptr };
+    DevBuf d_tile_off[FRAME_GEOS];   // int
+    DevBuf d_tile_rec[FRAME_GEOS];   // CellRec
     int n_rec[FRAME_GEOS] = { 0, 0 };
     // One buffer per call holds the patch list {position, value} of every frame and, behind it, the cell values of every
     // frame for the tile geometry in use
@@ -77,20 +77,12 @@ struct Clip {
     {
         return PatchView{ cells_of(patches, n_entries, nframes), n_rec[geo], d_tile_off[geo] };
     }
-    void *d_patches = nullptr;
-    size_t patch_bytes = 0;
-    void *d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    DevBuf d_patches, d_scratch;
     // T16 layout of the fused kernel: 0 = not decided yet (from the first frame the clip processes), 1 = plain, 2 = spread
     int t16_layout = 0;
-    void *d_unpacked = nullptr;      // 10 / 12-bit clips: frames unpacked to 16 bits before the fused kernel
-    size_t unpacked_bytes = 0;
+    DevBuf d_unpacked;               // 10 / 12-bit clips: frames unpacked to 16 bits before the fused kernel
 
-    ~Clip();
     int set_pixel_map(const int32_t *xy, size_t count, int rules, int dual_iso);
-    int ensure_patches(int nframes);
-    int ensure_scratch(size_t bytes);
-    int ensure_unpacked(size_t bytes);
     int detect_bad_pixels(const void *d_frame, int aggressive, int dual_iso, hipStream_t stream);
     int fix_pixels(void *d_frames, size_t stride, int nframes, hipStream_t stream);
     // one frame, for callers that SHARE this clip between host threads (drop-in path): nothing of the clip is written --
@@ -212,12 +204,6 @@ int launch_dark_accum(const void *d_frames, size_t stride, uint32_t npix, int nf
 int launch_dark_mean(const uint32_t *d_sums, uint16_t *d_dark, uint32_t npix, uint32_t n, hipStream_t stream);
 int launch_flat_gain(const uint16_t *d_plane, uint32_t w, uint32_t h, int black_f, unsigned long long *d_sums, uint16_t *d_gain,
                      uint32_t *d_means, hipStream_t stream);
-// device memory that lives as long as its scope, and a size rounded up to the 256 bytes frames lie apart by
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 // the mount's reader half (mlvreader.cpp): frames of one geometry from the file to 16-bit pixels in HBM.  On return everything that
 // reads the reader's staging has ended on s; without `cal` s is drained.  cal: the calibration stage, every frame corrected
 // as it arrives -- plain and LZMA payloads inside the unpack pass (s drained on return), LJ92 payloads in a pass behind the decoder

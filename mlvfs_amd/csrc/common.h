@@ -43,6 +43,32 @@ void set_error(const char *fmt, ...);
         }                                                                               \
     } while (0)
 
+// ---------------------------------------------------------------- grow-only buffers
+// The one owner of device memory that grows on demand.  reserve(need) does nothing while the block holds `need` bytes;
+// otherwise it frees the old block FIRST (the peak stays at one block) and allocates exactly `need`.  A failed allocation leaves the
+// buffer empty (p == nullptr, bytes == 0): the next reserve allocates again, whatever its size, and no stale pointer survives.
+// What has to happen before the old block may go (a flush, a synchronise) is the caller's, in front of reserve.  Buffers that grow
+// as a group are reserved one by one in a loop, each with its own capacity.  PinBuf: the same over page-locked host memory.
+// Converts to any pointer type, so it stands where the raw pointer stood.
+template <bool Pinned>
+struct GrowBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    ~GrowBuf() { release(); }
+    int reserve(size_t need);          // runtime.cpp (mlvfs_amd_test_fail_next(3) fails the calling thread's next one that has to grow)
+    void release();
+    template <class T> operator T *() const { return (T *)p; }
+};
+using DevBuf = GrowBuf<false>;
+using PinBuf = GrowBuf<true>;
+// test hook (mlvfs_amd_test_fail_next; dropin.cpp): [what] != 0: the calling thread's next such step fails without touching the device
+extern thread_local int t_fail_next[4];
+// a size rounded up to the 256 bytes frames lie apart by
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
 // ---------------------------------------------------------------- device state
 struct DeviceLuts {
     const uint16_t *t16;   // [8192]   mantissa-normalised raw2ev (sparse kernels, global memory)
@@ -96,18 +122,13 @@ struct ThreadCtx {         // one per (host thread, device)
     Device *dev = nullptr;
     hipStream_t stream = nullptr;
     // grow-only staging buffers for the host-memory (drop-in) entry points
-    void *d_a = nullptr, *d_b = nullptr;
-    size_t cap_a = 0, cap_b = 0;
-    void *h_pin = nullptr;
-    size_t cap_pin = 0;
-    void *d_patch = nullptr;             // this thread's patch list for pixel maps shared between threads (Clip::fix_pixels_shared)
-    size_t cap_patch = 0;
+    DevBuf d_a, d_b;
+    DevBuf d_patch;                      // this thread's patch list for pixel maps shared between threads (Clip::fix_pixels_shared)
     // The 16-bit frame the drop-in stages work on: two buffers (a stage reads one and writes the other, or works in place), and --
     // MLVFS_AMD_RESIDENT=1 -- which host buffer the current one mirrors, so that the next stage called on the same host pointer
     // need not upload it again (dropin.cpp)
     static constexpr int RES_SAMPLES = 64;
-    void *d_res[2] = { nullptr, nullptr };
-    size_t cap_res = 0;
+    DevBuf d_res[2];
     const void *res_host = nullptr;
     size_t res_bytes = 0;
     int res_cur = 0;

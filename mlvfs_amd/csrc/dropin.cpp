@@ -23,6 +23,11 @@
 
 using namespace mlv;
 
+// test hook (mlvfs_amd_test_fail_next): the calling thread's next fused launch of a bracketed frame [1] / next frame download [2] /
+// next growth of a DevBuf or PinBuf [3] (runtime.cpp) reports a HIP error without touching the device -- how
+// tests/test_failure_policy.py and tests/test_gpu_devbuf.py show what is served when the device is lost or full
+thread_local int mlv::t_fail_next[4] = { 0, 0, 0, 0 };
+
 namespace {
 
 struct FrameView {
@@ -158,9 +163,6 @@ void unfilled_frame(void *host, size_t bytes, const char *where)
 // batch) when the frame is fetched -- or earlier, when a call arrives that is not the next stage of process_frame's order or
 // needs the pixels (first frame of a clip: bad-pixel detection, stripe histogram; focus-pixel maps; pattern noise; dual ISO).
 std::atomic<long long> g_lazy_fused{ 0 }, g_lazy_early{ 0 };
-// test hook (mlvfs_amd_test_fail_next): the calling thread's next fused launch of a bracketed frame [1] / next frame download [2]
-// reports a HIP error without touching the device -- how tests/test_failure_policy.py shows what MLVFS serves when the device is lost
-thread_local int t_fail_next[3] = { 0, 0, 0 };
 // where the wall time of a bracketed frame goes, per process, in ns (MLVFS_AMD_DROPIN_PROFILE=1; mlvfs_amd_dropin_profile):
 // [0] inside dng_get_image_data, [1] of it the upload call, [2] of it the wait for the upload's end, [3] inside the recorded stage
 // calls, [4] inside mlvfs_amd_frame_end, [5] of it the fused launch's calls, [6] of it the download call + the wait for it, [7] frames
@@ -491,8 +493,9 @@ void mlvfs_amd_dropin_profile(double out[8]) { for (int i = 0; i < 8; i++) out[i
 // whole-frame transfers of the drop-in stages since the process started: {uploads, downloads, bytes up, bytes down}
 void mlvfs_amd_dropin_transfers(long long out[4]) { for (int i = 0; i < 4; i++) out[i] = g_xfer[i].load(); }
 
-// test hook: see t_fail_next (1: the next fused launch of a bracketed frame, 2: the next frame download, on the calling thread)
-void mlvfs_amd_test_fail_next(int what) { if (what == 1 || what == 2) t_fail_next[what] = 1; }
+// test hook: see t_fail_next (1: the next fused launch of a bracketed frame, 2: the next frame download, 3: the next growth of a
+// device or page-locked buffer, on the calling thread)
+void mlvfs_amd_test_fail_next(int what) { if (what >= 1 && what <= 3) t_fail_next[what] = 1; }
 
 // how often this process ran recorded stages as one fused launch at the fetch [0], and how often earlier because a call could not
 // be recorded [1] (for tests and tuning)

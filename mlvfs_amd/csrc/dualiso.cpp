@@ -227,57 +227,24 @@ static int prepare_tables(int device, int black, int white, int interp_method, D
 static thread_local double t_last_scalars[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
 
 // ------------------------------------------------------------------ per-thread work buffers
-struct DiWork {
-    void *base = nullptr;
-    size_t cap = 0;
-    DiWork() = default;
-    DiWork(const DiWork &) = delete;
-    ~DiWork() { if (base) (void)hipFree(base); }             // with the host thread that owned it
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return MLVFS_AMD_OK;
-        if (base) (void)hipFree(base);
-        base = nullptr; cap = 0;
-        void *grown = nullptr;
-        MLV_HIP(hipMalloc(&grown, bytes));
-        base = grown;
-        cap = bytes;
-        return MLVFS_AMD_OK;
-    }
-};
-static thread_local std::map<int, DiWork> t_work;
-struct PinnedWork {              // page-locked host landing zone for the summaries the host decisions read
-    void *base = nullptr;
-    size_t cap = 0;
-    PinnedWork() = default;
-    PinnedWork(const PinnedWork &) = delete;
-    ~PinnedWork() { if (base) (void)hipHostFree(base); }
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return MLVFS_AMD_OK;
-        if (base) (void)hipHostFree(base);
-        base = nullptr; cap = 0;
-        MLV_HIP(hipHostMalloc(&base, bytes, hipHostMallocDefault));
-        cap = bytes;
-        return MLVFS_AMD_OK;
-    }
-};
-static thread_local std::map<int, PinnedWork> t_pinned;
+// (each goes with the host thread that owned it)
+static thread_local std::map<int, DevBuf> t_work;
+static thread_local std::map<int, PinBuf> t_pinned;     // page-locked host landing zone for the summaries the host decisions read
 // AMaZE tile planes: zeroed when (re)allocated or when the plane geometry changes, like the reference's calloc per call
 // (for one geometry every tile rewrites exactly what it wrote before, so what must read as zero stays zero)
-struct AmazeWork : DiWork { int w = 0, h = 0; };
+struct AmazeWork { DevBuf buf; int w = 0, h = 0; };
 static thread_local std::map<int, AmazeWork> t_amaze;
 static int amaze_scratch_for(int device, int w, int h, hipStream_t s, float **out)
 {
     AmazeWork &aw = t_amaze[device];
     const size_t need = amaze_scratch_bytes(w, h);
-    if (need > aw.cap || aw.w != w || aw.h != h) {
-        int rc = aw.ensure(need);
+    if (need > aw.buf.bytes || aw.w != w || aw.h != h) {
+        int rc = aw.buf.reserve(need);
         if (rc) return rc;
-        MLV_HIP(hipMemsetAsync(aw.base, 0, aw.cap, s));
+        MLV_HIP(hipMemsetAsync(aw.buf, 0, aw.buf.bytes, s));
         aw.w = w; aw.h = h;
     }
-    *out = (float *)aw.base;
+    *out = aw.buf;
     return MLVFS_AMD_OK;
 }
 
@@ -451,7 +418,7 @@ static bool dualiso_parts(int w, int H, int nframes, std::vector<DiPart> &parts)
 
 // AMaZE tile planes of a batch: frame f's blocks at f * stride; a slot is zeroed when it is (re)allocated or when the rows of the
 // frame in it change (RGGB and GBRG frames of one clip differ by a row), like the reference's calloc per call
-struct AmazeSlots : DiWork { int w = 0, H = 0; std::vector<int> slot_h; size_t stride = 0; };
+struct AmazeSlots { DevBuf buf; int w = 0, H = 0; std::vector<int> slot_h; size_t stride = 0; };
 static thread_local std::map<int, AmazeSlots> t_amaze_slots;
 
 // ------------------------------------------------------------------ the conversion of a batch of device frames
@@ -499,19 +466,19 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
     const bool amaze = o.interp_method == 0;
     const size_t o_cfa = take(amaze ? NF * S * 4 : 0), o_ev = take(amaze ? NF * S * 12 : NF * S * 4), o_gray = take(amaze ? NF * S * 4 : 0),
                  o_dir = take(amaze ? NF * S : 0), o_sq = take(amaze ? NF * (size_t)H * 12 : 0), o_stats = take(NF * 16 * DI_STAT_SLOTS);
-    DiWork &wk = t_work[c->dev->id];
-    rc = wk.ensure(off);
+    DevBuf &wk = t_work[c->dev->id];
+    rc = wk.reserve(off);
     if (rc) return rc;
-    uint8_t *B = (uint8_t *)wk.base;
+    uint8_t *B = wk;
 
     // page-locked landing zone: every copy of this path starts or ends here (a copy from or to pageable memory waits inside the
     // runtime for the stream to reach it, and the calls of the other host threads wait with it)
     const size_t ph_dd = 0, ph_pp = ph_dd + up(NF * sizeof(DiDecide)), ph_sq = ph_pp + up(NF * sizeof(DiParams)),
                  ph_st = ph_sq + up(NF * (size_t)H * 12), ph_check = ph_st + up(NF * 16 * DI_STAT_SLOTS), ph_end = ph_check + up(NF * 16);
-    PinnedWork &pw = t_pinned[c->dev->id];
-    rc = pw.ensure(ph_end);
+    PinBuf &pw = t_pinned[c->dev->id];
+    rc = pw.reserve(ph_end);
     if (rc) return rc;
-    uint8_t *PH = (uint8_t *)pw.base;
+    uint8_t *PH = pw;
     DiDecide *dd = (DiDecide *)(PH + ph_dd);
     DiParams *pp = (DiParams *)(PH + ph_pp);
 
@@ -624,24 +591,25 @@ int cr2hdr20_batch(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_
         // AMaZE's tile planes
         AmazeSlots &as = t_amaze_slots[c->dev->id];
         const size_t a_stride = amaze_scratch_bytes(w, H) / sizeof(float);
-        if (as.w != w || as.H != H || as.slot_h.size() < NF) {
-            rc = as.ensure(a_stride * sizeof(float) * NF);
+        const size_t a_bytes = a_stride * sizeof(float) * NF;
+        if (as.w != w || as.H != H || as.slot_h.size() < NF || as.buf.bytes < a_bytes) {       // (the last: a growth that failed)
+            rc = as.buf.reserve(a_bytes);
             if (rc) return rc;
-            MLV_HIP(hipMemsetAsync(as.base, 0, a_stride * sizeof(float) * NF, stream));
+            MLV_HIP(hipMemsetAsync(as.buf, 0, a_bytes, stream));
             as.w = w; as.H = H; as.stride = a_stride;
             as.slot_h.assign(NF, 0);
         }
         for (int f = 0; f < nframes; f++) {
             if (results[f] != 1) continue;
             if (as.slot_h[f] != 0 && as.slot_h[f] != pp[f].h)
-                MLV_HIP(hipMemsetAsync((float *)as.base + (size_t)f * a_stride, 0, a_stride * sizeof(float), stream));
+                MLV_HIP(hipMemsetAsync((float *)as.buf + (size_t)f * a_stride, 0, a_stride * sizeof(float), stream));
             as.slot_h[f] = pp[f].h;
         }
         P.cfa = (float *)(B + o_cfa);
         P.ev_red = (int *)(B + o_ev); P.ev_green = P.ev_red + NF * S; P.ev_blue = P.ev_green + NF * S;
         P.gray_ev = (int *)(B + o_gray); P.dir = (uint8_t *)(B + o_dir);
         P.sq_dst = (const int *)(B + o_sq); P.sq_row = P.sq_dst + H;
-        P.stats = (unsigned *)(B + o_stats); P.amaze_scratch = (float *)as.base; P.amaze_scratch_stride = a_stride;
+        P.stats = (unsigned *)(B + o_stats); P.amaze_scratch = (float *)as.buf; P.amaze_scratch_stride = a_stride;
         // the parts' AMaZE one after the other on the caller's stream, the rest of each part on the second stream (dualiso_parts).
         // (The first form alternated the PARTS between the two streams.  Same dependencies for two parts, yet its speed depended on
         // the order in which the process had created its streams -- 8.5 or 9.2 ms per batch of 8, each reproducible: the tail then
@@ -882,10 +850,10 @@ void mlvfs_amd_dualiso_last_scalars(double out[8]) { for (int i = 0; i < 8; i++)
 // page-locked landing zone: ~0.93 GB per frame of its largest batch at 3584x1320); the next conversion allocates again
 void mlvfs_amd_dualiso_trim(void)
 {
-    for (auto &kv : t_work) { if (kv.second.base) { (void)hipDeviceSynchronize(); (void)hipFree(kv.second.base); } kv.second.base = nullptr; kv.second.cap = 0; }
-    for (auto &kv : t_amaze_slots) { if (kv.second.base) (void)hipFree(kv.second.base); kv.second.base = nullptr; kv.second.cap = 0; kv.second.w = kv.second.H = 0; kv.second.slot_h.clear(); }
-    for (auto &kv : t_amaze) { if (kv.second.base) (void)hipFree(kv.second.base); kv.second.base = nullptr; kv.second.cap = 0; kv.second.w = kv.second.h = 0; }
-    for (auto &kv : t_pinned) { if (kv.second.base) (void)hipHostFree(kv.second.base); kv.second.base = nullptr; kv.second.cap = 0; }
+    for (auto &kv : t_work) { if (kv.second.p) (void)hipDeviceSynchronize(); kv.second.release(); }
+    for (auto &kv : t_amaze_slots) { kv.second.buf.release(); kv.second.w = kv.second.H = 0; kv.second.slot_h.clear(); }
+    for (auto &kv : t_amaze) { kv.second.buf.release(); kv.second.w = kv.second.h = 0; }
+    for (auto &kv : t_pinned) kv.second.release();
 }
 
 // test hook: forget the per-black table caches, as a fresh process would

@@ -110,8 +110,8 @@ int build_lut(const Parsed &h, uint16_t *lut)
 }
 
 struct Work {                              // per host thread and device, grow-only
-    uint8_t *d_arena = nullptr, *h_stage = nullptr;
-    size_t cap_arena = 0, cap_stage = 0;
+    DevBuf d_arena;
+    PinBuf h_stage;
     hipStream_t sub[2] = { nullptr, nullptr };          // sub-batches alternate between two streams: uploads overlap kernels
     hipEvent_t ready = nullptr, done[2] = { nullptr, nullptr };
     hipStream_t up = nullptr;                            // every sub-batch's upload, in order, on ONE stream (see the call)
@@ -130,8 +130,6 @@ struct Work {                              // per host thread and device, grow-o
         if (ready) (void)hipEventDestroy(ready);
         if (up) { (void)hipStreamSynchronize(up); (void)hipStreamDestroy(up); }
         for (hipEvent_t e : uploaded) (void)hipEventDestroy(e);
-        if (d_arena) (void)hipFree(d_arena);
-        if (h_stage) (void)hipHostFree(h_stage);
     }
     int ensure(size_t arena, size_t stage)
     {
@@ -143,24 +141,11 @@ struct Work {                              // per host thread and device, grow-o
             MLV_HIP(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
             MLV_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
         }
-        if (arena > cap_arena) {
-            if (d_arena) (void)hipFree(d_arena);
-            d_arena = nullptr; cap_arena = 0;
-            MLV_HIP(hipMalloc(&d_arena, arena));
-            cap_arena = arena;
-        }
-        if (stage > cap_stage) {
-            if (h_stage) (void)hipHostFree(h_stage);
-            h_stage = nullptr; cap_stage = 0;
-            MLV_HIP(hipHostMalloc(&h_stage, stage, hipHostMallocDefault));
-            cap_stage = stage;
-        }
-        return MLVFS_AMD_OK;
+        if (const int rc = d_arena.reserve(arena)) return rc;
+        return h_stage.reserve(stage);
     }
 };
 thread_local std::map<int, Work> t_work;
-
-size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 }  // namespace mlv
@@ -219,28 +204,28 @@ extern "C" int mlvfs_amd_lj92_decode_dev(const void *const *streams, const size_
         o.nwg = (o.raw_len + 8191) / 8192;
         if (o.nwg == 0) o.nwg = 1;
         o.ngrp = (o.nwg + 31) / 32;
-        o.lut = stage; stage += up(sizeof(uint16_t) * LJ_LUT_MAX, 256);
+        o.lut = stage; stage += up256(sizeof(uint16_t) * LJ_LUT_MAX);
         max_raw = std::max(max_raw, o.raw_len); max_nwg = std::max(max_nwg, o.nwg); max_ngrp = std::max(max_ngrp, o.ngrp);
         max_w = std::max(max_w, h.width); max_h = std::max(max_h, h.height);
     }
     const size_t frames_at = stage;
-    stage += up(sizeof(LjFrame) * nframes, 256);
+    stage += up256(sizeof(LjFrame) * nframes);
     arena = stage;                                           // the staging block (tables, frame records) is mirrored at the start of the arena
     for (int i = 0; i < nframes; i++) {
         Off &o = off[i];
         const Parsed &h = hdr[i];
-        o.raw = arena; arena += up(o.raw_len + 16, 256);
-        o.ust = arena; arena += up((size_t)o.nwg * 8192 + 8192, 256);
+        o.raw = arena; arena += up256(o.raw_len + 16);
+        o.ust = arena; arena += up256((size_t)o.nwg * 8192 + 8192);
         o.ust_len = arena; arena += 256;
-        o.blk = arena; arena += up(((size_t)o.raw_len / 4096 + 2) * 4, 256);
+        o.blk = arena; arena += up256(((size_t)o.raw_len / 4096 + 2) * 4);
         o.cmap = arena; arena += (size_t)o.nwg * 256 * 32 * 2;
         o.smap = arena; arena += (size_t)o.nwg * 16 * 32 * 8;
-        o.wmap = arena; arena += up((size_t)o.nwg * 32 * 8, 256);
-        o.gmap = arena; arena += up((size_t)o.ngrp * 32 * 8, 256);
-        o.wstart = arena; arena += up((size_t)o.nwg * 8, 256);
-        o.gstart = arena; arena += up((size_t)o.ngrp * 8, 256);
-        o.diff = arena; arena += up((size_t)h.width * h.height * 4, 256);
-        o.colsum = arena; arena += up((size_t)h.width * 16 * 4, 256);
+        o.wmap = arena; arena += up256((size_t)o.nwg * 32 * 8);
+        o.gmap = arena; arena += up256((size_t)o.ngrp * 32 * 8);
+        o.wstart = arena; arena += up256((size_t)o.nwg * 8);
+        o.gstart = arena; arena += up256((size_t)o.ngrp * 8);
+        o.diff = arena; arena += up256((size_t)h.width * h.height * 4);
+        o.colsum = arena; arena += up256((size_t)h.width * 16 * 4);
         o.err = arena; arena += 256;
     }
     Work &w = t_work[c->dev->id];
@@ -252,14 +237,15 @@ extern "C" int mlvfs_amd_lj92_decode_dev(const void *const *streams, const size_
         w.same_as_before = key == w.last_key && arena == w.last_arena;
         w.last_key.swap(key); w.last_arena = arena;
     }
-    LjFrame *fr = (LjFrame *)(w.h_stage + frames_at);
+    uint8_t *const d_arena = w.d_arena, *const h_stage = w.h_stage;
+    LjFrame *fr = (LjFrame *)(h_stage + frames_at);
     for (int i = 0; i < nframes; i++) {
         const Off &o = off[i];
         const Parsed &h = hdr[i];
-        const int lut_n = build_lut(h, (uint16_t *)(w.h_stage + o.lut));
+        const int lut_n = build_lut(h, (uint16_t *)(h_stage + o.lut));
         if (lut_n < 0) { set_error("lj92: frame %d: Huffman table with more than %d long-code prefixes", i, (LJ_LUT_MAX - (1 << LJ_L1_BITS)) / 32); return MLVFS_AMD_ERR_ARG; }
         LjFrame &f = fr[i];
-        uint8_t *A = w.d_arena;
+        uint8_t *A = d_arena;
         f.raw = A + o.raw; f.raw_len = o.raw_len;
         f.ust = A + o.ust; f.ust_len = (uint32_t *)(A + o.ust_len); f.blk_drop = (uint32_t *)(A + o.blk);
         f.lut = (const uint16_t *)(A + o.lut); f.huffbits = h.huffbits; f.lut_entries = lut_n;
@@ -273,7 +259,7 @@ extern "C" int mlvfs_amd_lj92_decode_dev(const void *const *streams, const size_
         f.err = (int *)(A + o.err);
     }
     MLV_HIP(hipMemcpyAsync(w.d_arena, w.h_stage, stage, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < nframes; i++) MLV_HIP(hipMemsetAsync(w.d_arena + off[i].err, 0, sizeof(int), s));
+    for (int i = 0; i < nframes; i++) MLV_HIP(hipMemsetAsync(d_arena + off[i].err, 0, sizeof(int), s));
     MLV_HIP(hipEventRecord(w.ready, s));
     // Sub-batches of frames alternate between two streams, so that the upload of one overlaps the kernels of the other.  The
     // entropy-coded bytes go straight from the caller's memory (page-locked when they come from the reader's staging).
@@ -299,7 +285,7 @@ extern "C" int mlvfs_amd_lj92_decode_dev(const void *const *streams, const size_
         }();
         if (!(no_upload && w.same_as_before))
         for (int i = j0; i < j0 + n; i++)
-            MLV_HIP(hipMemcpyAsync(w.d_arena + off[i].raw, (const uint8_t *)streams[i] + hdr[i].scan, off[i].raw_len, hipMemcpyHostToDevice, su));
+            MLV_HIP(hipMemcpyAsync(d_arena + off[i].raw, (const uint8_t *)streams[i] + hdr[i].scan, off[i].raw_len, hipMemcpyHostToDevice, su));
         if (one_up) {
             while ((int)w.uploaded.size() <= j) { hipEvent_t e; MLV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); w.uploaded.push_back(e); }
             MLV_HIP(hipEventRecord(w.uploaded[j], w.up));
@@ -307,15 +293,15 @@ extern "C" int mlvfs_amd_lj92_decode_dev(const void *const *streams, const size_
         }
         unsigned preds = 0;
         for (int i = j0; i < j0 + n; i++) preds |= 1u << hdr[i].pred;
-        rc = lj92_launch((const LjFrame *)(w.d_arena + frames_at) + j0, n, max_raw, max_nwg, max_ngrp, max_w, max_h, preds, sj);
+        rc = lj92_launch((const LjFrame *)(d_arena + frames_at) + j0, n, max_raw, max_nwg, max_ngrp, max_w, max_h, preds, sj);
         if (rc) return rc;
     }
     for (int k = 0; k < 2; k++) {
         MLV_HIP(hipEventRecord(w.done[k], w.sub[k]));
         MLV_HIP(hipStreamWaitEvent(s, w.done[k], 0));
     }
-    int *errs = (int *)(w.h_stage + stage);
-    for (int i = 0; i < nframes; i++) MLV_HIP(hipMemcpyAsync(&errs[i], w.d_arena + off[i].err, sizeof(int), hipMemcpyDeviceToHost, s));
+    int *errs = (int *)(h_stage + stage);
+    for (int i = 0; i < nframes; i++) MLV_HIP(hipMemcpyAsync(&errs[i], d_arena + off[i].err, sizeof(int), hipMemcpyDeviceToHost, s));
     MLV_HIP(hipStreamSynchronize(s));                        // the staging block is reused by the next call
     for (int i = 0; i < nframes; i++)
         if (errs[i]) {

@@ -203,7 +203,7 @@ struct ThreadRoom : LjeRoom {
     int get(size_t bits_bytes, size_t stream_bytes, void **d_bits, uint8_t **d_out, size_t *out_stride) override
     {
         const size_t bits = up256(bits_bytes);
-        if (c->ensure(c->cap_a, bits + (own_out ? stream_bytes : 0))) return MLVFS_AMD_ERR_NOMEM;
+        if (c->ensure(c->d_a.bytes, bits + (own_out ? stream_bytes : 0))) return MLVFS_AMD_ERR_NOMEM;
         *d_bits = c->d_b;
         if (own_out) { *d_out = (uint8_t *)c->d_b + bits; *out_stride = stream_bytes; }
         return MLVFS_AMD_OK;

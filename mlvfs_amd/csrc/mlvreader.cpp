@@ -35,7 +35,9 @@
 
 namespace {
 
+using mlv::DevBuf;
 using mlv::set_error;
+using mlv::up256;
 
 #pragma pack(push, 1)
 struct BlockHead { uint8_t type[4]; uint32_t size; uint64_t timestamp; };                       // mlv.h:42-46
@@ -74,25 +76,19 @@ struct Reader {
     mutable size_t stage_bytes = 0;
     // LJ92 clips: decoded frames of one batch and two buffers of finished frames in HBM; the download of one batch runs on
     // its own stream while the next batch is decoded
-    mutable void *d_dec = nullptr, *d_fin[2] = { nullptr, nullptr };
-    mutable size_t dev_bytes = 0;
+    mutable DevBuf d_dec, d_fin[2];
     mutable hipStream_t s_run = nullptr, s_down = nullptr;
     mutable hipEvent_t fin_done[2] = { nullptr, nullptr }, down_done[2] = { nullptr, nullptr };
     mutable std::mutex stage_mu;
     // dual-ISO clips (mlvfs_amd_mlv_process_dualiso): packed payloads of one batch and two buffers of 16-bit frames in HBM
-    mutable void *d_di_packed = nullptr, *d_di_frames[2] = { nullptr, nullptr };
-    mutable size_t di_packed_bytes = 0, di_frames_bytes = 0;
+    mutable DevBuf d_di_packed, d_di_frames[2];
 
     ~Reader()
     {
-        if (d_di_packed) (void)hipFree(d_di_packed);
-        for (int k = 0; k < 2; k++) if (d_di_frames[k]) (void)hipFree(d_di_frames[k]);
         for (int fd : fds) if (fd >= 0) close(fd);
         mlvfs_amd_host_free(stage[0]);
         mlvfs_amd_host_free(stage[1]);
-        if (d_dec) (void)hipFree(d_dec);
         for (int k = 0; k < 2; k++) {
-            if (d_fin[k]) (void)hipFree(d_fin[k]);
             if (fin_done[k]) (void)hipEventDestroy(fin_done[k]);
             if (down_done[k]) (void)hipEventDestroy(down_done[k]);
         }
@@ -112,17 +108,6 @@ bool ensure_stage(const Reader &r, size_t bytes)
     r.stage[1] = (uint8_t *)mlvfs_amd_host_alloc(bytes);
     r.stage_bytes = (r.stage[0] && r.stage[1]) ? bytes : 0;
     return r.stage_bytes != 0;
-}
-
-// the device buffer packed payloads are uploaded to before the unpack
-int ensure_packed_dev(const Reader &r, size_t bytes)
-{
-    if (r.di_packed_bytes >= bytes) return MLVFS_AMD_OK;
-    if (r.d_di_packed) (void)hipFree(r.d_di_packed);
-    r.d_di_packed = nullptr; r.di_packed_bytes = 0;
-    MLV_HIP(hipMalloc(&r.d_di_packed, bytes));
-    r.di_packed_bytes = bytes;
-    return MLVFS_AMD_OK;
 }
 
 // ---- chunks ---------------------------------------------------------------------------------------------------------
@@ -450,7 +435,7 @@ int mlv::reader_load_list(const void *reader, const int *list, int count, int w,
         if (rc || !on) return rc;
         return launch_cal_apply(d_frames, dstride, (uint32_t)w * (uint32_t)h, count, *cal, s);        // (the staging is free already)
     }
-    rc = ensure_packed_dev(r, stride * count);
+    rc = r.d_di_packed.reserve(stride * count);                       // packed payloads are uploaded here before the unpack
     if (rc) return rc;
     const mlvfs_amd_geom_t geom{ w, h, bpp, 0, 0, 0, 0 };
     MLV_HIP(hipMemcpyAsync(r.d_di_packed, r.stage[0], stride * count, hipMemcpyHostToDevice, s));
@@ -595,18 +580,11 @@ int mlvfs_amd_mlv_process(const void *reader, mlvfs_amd_clip_t *clip, int first,
     uint8_t *const *stage = r.stage;
     int rc = ensure_stage(r, stride * batch_frames) ? MLVFS_AMD_OK : MLVFS_AMD_ERR_NOMEM;
     std::vector<size_t> sizes[2] = { std::vector<size_t>(batch_frames), std::vector<size_t>(batch_frames) };
-    const size_t px_bytes = (size_t)fh0.rawi_hdr.xRes * fh0.rawi_hdr.yRes * 2, dstride = (px_bytes + 255) / 256 * 256;
-    if (rc == MLVFS_AMD_OK && lj92 && r.dev_bytes < dstride * batch_frames) {
+    const size_t px_bytes = (size_t)fh0.rawi_hdr.xRes * fh0.rawi_hdr.yRes * 2, dstride = up256(px_bytes);
+    if (rc == MLVFS_AMD_OK && lj92) {
         if (!mlv::thread_ctx()) return MLVFS_AMD_ERR_HIP;
-        if (r.d_dec) (void)hipFree(r.d_dec);
-        r.d_dec = nullptr; r.dev_bytes = 0;
-        MLV_HIP(hipMalloc(&r.d_dec, dstride * batch_frames));
-        for (int k = 0; k < 2; k++) {
-            if (r.d_fin[k]) (void)hipFree(r.d_fin[k]);
-            r.d_fin[k] = nullptr;
-            MLV_HIP(hipMalloc(&r.d_fin[k], dstride * batch_frames));
-        }
-        r.dev_bytes = dstride * batch_frames;
+        for (DevBuf *b : { &r.d_dec, &r.d_fin[0], &r.d_fin[1] })
+            if (const int rc1 = b->reserve(dstride * batch_frames)) return rc1;
     }
     if (rc == MLVFS_AMD_OK && lj92 && !r.s_run) {
         MLV_HIP(hipStreamCreateWithFlags(&r.s_run, hipStreamNonBlocking));
@@ -683,21 +661,14 @@ int mlvfs_amd_mlv_process_dualiso(const void *reader, int first, int count, void
     batch_frames = std::min(batch_frames, count);
     Span s0;
     if (!payload_span(r, first, &s0)) return MLVFS_AMD_ERR_ARG;
-    const size_t stride = (s0.bytes + 2 + 15) / 16 * 16, dstride = (px_bytes + 255) / 256 * 256;
+    const size_t stride = (s0.bytes + 2 + 15) / 16 * 16, dstride = up256(px_bytes);
     mlv::ThreadCtx *c = mlv::thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
     std::lock_guard<std::mutex> lk(r.stage_mu);                     // one streaming call per reader at a time
     if (!ensure_stage(r, stride * batch_frames)) return MLVFS_AMD_ERR_NOMEM;
-    if (int rc0 = ensure_packed_dev(r, stride * batch_frames)) return rc0;
-    if (r.di_frames_bytes < dstride * batch_frames) {
-        for (int k = 0; k < 2; k++) {
-            if (r.d_di_frames[k]) (void)hipFree(r.d_di_frames[k]);
-            r.d_di_frames[k] = nullptr;
-        }
-        r.di_frames_bytes = 0;
-        for (int k = 0; k < 2; k++) MLV_HIP(hipMalloc(&r.d_di_frames[k], dstride * batch_frames));
-        r.di_frames_bytes = dstride * batch_frames;
-    }
+    if (const int rc0 = r.d_di_packed.reserve(stride * batch_frames)) return rc0;
+    for (DevBuf &b : r.d_di_frames)
+        if (const int rc0 = b.reserve(dstride * batch_frames)) return rc0;
     if (!r.s_down) {
         MLV_HIP(hipStreamCreateWithFlags(&r.s_run, hipStreamNonBlocking));
         MLV_HIP(hipStreamCreateWithFlags(&r.s_down, hipStreamNonBlocking));
@@ -774,7 +745,7 @@ static size_t gif_data(const void *reader, uint8_t *output_buffer, off_t offset,
         }
         mlv::ThreadCtx *c = mlv::thread_ctx();
         if (!c) return 0;
-        const size_t fbytes = (size_t)xres * yres * 2, dstride = (fbytes + 255) / 256 * 256;
+        const size_t fbytes = (size_t)xres * yres * 2, dstride = up256(fbytes);
         void *d = nullptr;
         if (hipMalloc(&d, dstride * NF) != hipSuccess) { set_error("mlv: out of device memory"); return 0; }
         std::vector<uint8_t> frames(dstride * NF);

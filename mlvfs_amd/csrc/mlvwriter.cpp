@@ -123,25 +123,15 @@ size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // device memory and page-locked staging of one call
 struct DevRoom : LjeRoom {
-    void *d_frames = nullptr, *d_aux = nullptr, *d_fixed = nullptr, *d_bits = nullptr, *d_streams = nullptr;
-    size_t frames_bytes = 0, aux_bytes = 0, fixed_bytes = 0, bits_bytes = 0, streams_bytes = 0;
+    DevBuf d_frames, d_aux, d_fixed, d_bits, d_streams;
     uint8_t *h_stage = nullptr;
     size_t stage_bytes = 0;
     int n = 0;                                                         // frames of the batch being encoded
 
-    static int grow(void **p, size_t *have, size_t want)
-    {
-        if (*have >= want) return MLVFS_AMD_OK;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr; *have = 0;
-        MLV_HIP(hipMalloc(p, want));
-        *have = want;
-        return MLVFS_AMD_OK;
-    }
     int frames(size_t bytes)
     {
-        if (int rc = grow(&d_frames, &frames_bytes, bytes)) return rc;
-        return grow(&d_aux, &aux_bytes, bytes);
+        if (int rc = d_frames.reserve(bytes)) return rc;
+        return d_aux.reserve(bytes);
     }
     int stage(size_t bytes)
     {
@@ -156,19 +146,15 @@ struct DevRoom : LjeRoom {
     // the encoder's room: the batch's bit streams and one stream slot per frame
     int get(size_t bits, size_t stream_bytes, void **bits_out, uint8_t **d_out, size_t *out_stride) override
     {
-        if (int rc = grow(&d_bits, &bits_bytes, up(bits, 256))) return rc;
-        const size_t slot = up(stream_bytes, 256);
-        if (int rc = grow(&d_streams, &streams_bytes, slot * (size_t)n)) return rc;
+        if (int rc = d_bits.reserve(up256(bits))) return rc;
+        const size_t slot = up256(stream_bytes);
+        if (int rc = d_streams.reserve(slot * (size_t)n)) return rc;
         *bits_out = d_bits;
         *d_out = (uint8_t *)d_streams;
         *out_stride = slot;
         return MLVFS_AMD_OK;
     }
-    ~DevRoom() override
-    {
-        for (void *p : { d_frames, d_aux, d_fixed, d_bits, d_streams }) if (p) (void)hipFree(p);
-        mlvfs_amd_host_free(h_stage);
-    }
+    ~DevRoom() override { mlvfs_amd_host_free(h_stage); }
 };
 
 struct Job {
@@ -232,7 +218,7 @@ int batch_device(Job &j, const std::vector<int> &list)
     const Frame &f = j.frames[list[0]];
     const int n = (int)list.size();
     const uint32_t npix = (uint32_t)f.w * (uint32_t)f.h;
-    const size_t img = (size_t)npix * 2, dstride = up(img, 256);
+    const size_t img = (size_t)npix * 2, dstride = up256(img);
     if (int rc = d.frames(dstride * n)) return rc;
     Calib cal;
     int rc = calib_on_device(j.dark, j.flat, j.ctx, f.w, f.h, f.bpp, f.black, &cal);
@@ -257,7 +243,7 @@ int batch_device(Job &j, const std::vector<int> &list)
         for (int k = 0; k < n; k++) j.ready[list[k]] = { d.h_stage + (size_t)k * pstride, bytes };
         return MLVFS_AMD_OK;
     }
-    if ((rc = DevRoom::grow(&d.d_fixed, &d.fixed_bytes, lje_fixed_bytes(npix, n)))) return rc;
+    if ((rc = d.d_fixed.reserve(lje_fixed_bytes(npix, n)))) return rc;
     if ((rc = launch_mlv_tile(d.d_frames, dstride, d.d_aux, dstride, f.w, f.h, f.obpp - loaded, n, s))) return rc;
     std::vector<const uint16_t *> src(n);
     for (int k = 0; k < n; k++) src[k] = (const uint16_t *)((const uint8_t *)d.d_aux + (size_t)k * dstride);

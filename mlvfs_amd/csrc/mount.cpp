@@ -48,58 +48,22 @@ struct Mount {
     bool served = false;                     // a call has reached the device: the dark frame, the flat field and the proxy stay what they are
     int proxy = 1;                           // mlvfs_amd_mount_set_proxy: 2 = the served frames are binned to half size
     int device = -1;
-    void *d_frames = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_bits = nullptr;
-    int32_t *d_rgb = nullptr;                // mlvfs_amd_mount_rgb: 13 parameters per frame of a batch
-    int rgb_frames = 0;
+    DevBuf d_frames, d_out, d_scratch;
+    DevBuf d_bits;                           // the encoder's bit streams, sized from a batch's histograms
+    DevBuf d_rgb;                            // mlvfs_amd_mount_rgb: 13 int32 parameters per frame of a batch
     std::vector<int32_t> rgb_host;           // what the upload reads: it outlives every call
-    size_t frames_bytes = 0, scratch_bytes = 0, bits_bytes = 0;   // d_bits: the encoder's bit streams, sized from a batch's histograms
 
-    void release()
-    {
-        if (d_frames) (void)hipFree(d_frames);
-        if (d_out) (void)hipFree(d_out);
-        if (d_scratch) (void)hipFree(d_scratch);
-        if (d_bits) (void)hipFree(d_bits);
-        if (d_rgb) (void)hipFree(d_rgb);
-        d_frames = d_out = d_scratch = d_bits = nullptr;
-        d_rgb = nullptr;
-        frames_bytes = scratch_bytes = bits_bytes = 0;
-        rgb_frames = 0;
-    }
-    ~Mount() { release(); }
+    void release() { for (DevBuf *b : { &d_frames, &d_out, &d_scratch, &d_bits, &d_rgb }) b->release(); }
 
     int ensure(int dev, size_t fbytes, size_t sbytes)
     {
         if (dev != device) { release(); device = dev; }
-        if (frames_bytes < fbytes) {
-            if (d_frames) (void)hipFree(d_frames);
-            if (d_out) (void)hipFree(d_out);
-            d_frames = d_out = nullptr;
-            frames_bytes = 0;
-            MLV_HIP(hipMalloc(&d_frames, fbytes));
-            MLV_HIP(hipMalloc(&d_out, fbytes));
-            frames_bytes = fbytes;
-        }
-        if (scratch_bytes < sbytes) {
-            if (d_scratch) (void)hipFree(d_scratch);
-            d_scratch = nullptr;
-            scratch_bytes = 0;
-            MLV_HIP(hipMalloc(&d_scratch, sbytes));
-            scratch_bytes = sbytes;
-        }
-        return MLVFS_AMD_OK;
+        for (DevBuf *b : { &d_frames, &d_out })
+            if (const int rc = b->reserve(fbytes)) return rc;
+        return d_scratch.reserve(sbytes);
     }
-
-    int ensure_rgb(int frames)               // after ensure(): the device is this handle's
-    {
-        if (rgb_frames >= frames) return MLVFS_AMD_OK;
-        if (d_rgb) (void)hipFree(d_rgb);
-        d_rgb = nullptr;
-        rgb_frames = 0;
-        MLV_HIP(hipMalloc((void **)&d_rgb, (size_t)frames * 13 * sizeof(int32_t)));
-        rgb_frames = frames;
-        return MLVFS_AMD_OK;
-    }
+    // after ensure(): the device is this handle's
+    int ensure_rgb(int frames) { return d_rgb.reserve((size_t)frames * 13 * sizeof(int32_t)); }
 };
 
 // where a lossless call wants its answers (frame 0 of the batch first)
@@ -115,13 +79,7 @@ struct MountRoom : LjeRoom {
     explicit MountRoom(Mount &m_) : m(m_) {}
     int get(size_t bits_bytes, size_t, void **d_bits, uint8_t **, size_t *) override
     {
-        if (m.bits_bytes < bits_bytes) {
-            if (m.d_bits) (void)hipFree(m.d_bits);
-            m.d_bits = nullptr;
-            m.bits_bytes = 0;
-            MLV_HIP(hipMalloc(&m.d_bits, bits_bytes));
-            m.bits_bytes = bits_bytes;
-        }
+        if (const int rc = m.d_bits.reserve(bits_bytes)) return rc;
         *d_bits = m.d_bits;
         return MLVFS_AMD_OK;
     }
@@ -201,7 +159,7 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         const bool in_f = final_at[k0] == F + k0 * dstride;
         for (k1 = k0 + 1; k1 < n && (final_at[k1] == F + k1 * dstride) == in_f; k1++) {}
         uint8_t *dst = (in_f ? O : F) + k0 * dstride;
-        const int rc = launch_render2(final_at[k0], dstride, m.d_rgb + (size_t)k0 * 13, dst, dstride, w, h, k1 - k0, s);
+        const int rc = launch_render2(final_at[k0], dstride, (const int32_t *)m.d_rgb + (size_t)k0 * 13, dst, dstride, w, h, k1 - k0, s);
         if (rc) return rc;
         for (int k = k0; k < k1; k++) {
             uint8_t *file = h_out + k * out_stride;
@@ -227,7 +185,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
     // deflicker (main.c:943): before the header, which writes exposure_bias as BaselineExposure
     if (o.deflicker) {
         std::vector<uint16_t> med(n);
-        rc = deflicker_batch_device(F, dstride, n, bpp, img, m.d_scratch, m.scratch_bytes, med.data(), s);
+        rc = deflicker_batch_device(F, dstride, n, bpp, img, m.d_scratch, m.d_scratch.bytes, med.data(), s);
         if (rc) return rc;
         for (int k = 0; k < n; k++) deflicker_bias(o.deflicker, fh[k].rawi_hdr.raw_info.black_level, med[k], fh[k].rawi_hdr.raw_info.exposure_bias);
     }
@@ -243,7 +201,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
         for (int k0 = 0, k1; k0 < n; k0 = k1) {
             for (k1 = k0 + 1; k1 < n && fh[k1].rawi_hdr.raw_info.white_level == fh[k0].rawi_hdr.raw_info.white_level; k1++) {}
             rc = launch_pattern_noise_batch(F + k0 * dstride, dstride, k1 - k0, w, h, fh[k0].rawi_hdr.raw_info.white_level, m.d_scratch,
-                                            m.scratch_bytes, s);
+                                            m.d_scratch.bytes, s);
             if (rc) return rc;
         }
     }

@@ -277,14 +277,30 @@ ThreadCtx::~ThreadCtx()
         release_stream_state(dev ? dev->id : 0, stream);
         (void)hipStreamDestroy(stream);
     }
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (d_patch) (void)hipFree(d_patch);
-    if (d_res[0]) (void)hipFree(d_res[0]);
-    if (d_res[1]) (void)hipFree(d_res[1]);
-    if (h_pin) (void)hipHostFree(h_pin);
     if (ev_up) (void)hipEventDestroy(ev_up);
 }
+
+// ------------------------------------------------------------------ grow-only buffers (common.h)
+template <bool Pinned>
+void GrowBuf<Pinned>::release()
+{
+    if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    bytes = 0;
+}
+
+template <bool Pinned>
+int GrowBuf<Pinned>::reserve(size_t need)
+{
+    if (need <= bytes) return MLVFS_AMD_OK;
+    release();
+    if (t_fail_next[3]) { t_fail_next[3] = 0; set_error("injected failure of a device allocation (test hook)"); return MLVFS_AMD_ERR_HIP; }
+    MLV_HIP(Pinned ? hipHostMalloc(&p, need, hipHostMallocDefault) : hipMalloc(&p, need));
+    bytes = need;
+    return MLVFS_AMD_OK;
+}
+template struct GrowBuf<false>;
+template struct GrowBuf<true>;
 
 static int visible_devices()
 {
@@ -396,24 +412,13 @@ int ThreadCtx::ensure(size_t need_a, size_t need_b)
         const int rc = flush_pending(this);
         if (rc) return rc;
     }
-    if (need_a > cap_a) {
-        if (d_a) (void)hipFree(d_a);
-        d_a = nullptr; cap_a = 0;
-        MLV_HIP(hipMalloc(&d_a, need_a));
-        cap_a = need_a;
-    }
-    if (need_b > cap_b) {
-        if (d_b) (void)hipFree(d_b);
-        d_b = nullptr; cap_b = 0;
-        MLV_HIP(hipMalloc(&d_b, need_b));
-        cap_b = need_b;
-    }
-    return MLVFS_AMD_OK;
+    if (const int rc = d_a.reserve(need_a)) return rc;
+    return d_b.reserve(need_b);
 }
 
 int ThreadCtx::ensure_res(size_t bytes)
 {
-    if (bytes <= cap_res) return MLVFS_AMD_OK;
+    if (bytes <= d_res[0].bytes && bytes <= d_res[1].bytes) return MLVFS_AMD_OK;
     if (lazy.active || res_dirty) {                  // the buffers about to be freed hold a frame the host has not got yet
         const int rc = flush_pending(this);
         if (rc) return rc;
@@ -421,25 +426,15 @@ int ThreadCtx::ensure_res(size_t bytes)
     (void)hipStreamSynchronize(stream);
     res_host = nullptr;
     res_dirty = false;
-    for (int k = 0; k < 2; k++) {
-        if (d_res[k]) (void)hipFree(d_res[k]);
-        d_res[k] = nullptr;
-    }
-    cap_res = 0;
-    for (int k = 0; k < 2; k++) MLV_HIP(hipMalloc(&d_res[k], bytes));
-    cap_res = bytes;
+    for (DevBuf &b : d_res)
+        if (const int rc = b.reserve(bytes)) return rc;
     return MLVFS_AMD_OK;
 }
 
 int ThreadCtx::ensure_patch(size_t need)
 {
-    if (need > cap_patch) {
-        if (d_patch) { (void)hipStreamSynchronize(stream); (void)hipFree(d_patch); }
-        d_patch = nullptr; cap_patch = 0;
-        MLV_HIP(hipMalloc(&d_patch, need));
-        cap_patch = need;
-    }
-    return MLVFS_AMD_OK;
+    if (need > d_patch.bytes && d_patch.p) (void)hipStreamSynchronize(stream);
+    return d_patch.reserve(need);
 }
 
 }  // namespace mlv
