@@ -807,6 +807,65 @@ int    mlvfs_amd_mount_rgb(void *mount, int first, int count, void *h_out, size_
 /* bytes of file `index` as mlvfs_amd_mount_rgb serves it; 0: no such frame, or one below 2x2 */
 size_t mlvfs_amd_mount_rgb_size(const void *mount, int index);
 
+/* -- rendered frames as baseline JPEG files (csrc/k_jpeg.hip, csrc/jpeg.cpp, csrc/mount.cpp) -------------------------- */
+/* A rendering as an ordinary baseline (DCT, Huffman) JFIF file that any decoder opens, a tenth of the TIFF's bytes.  The definition is
+ * this project's (the reference has no such stage), in integers only, so that it has a byte-exact oracle (mlvfs_amd/jpeg.py).
+ * Input.   W' x H' RGB bytes exactly as mlvfs_amd_render2_dev writes them: rows top down, no padding in a row.  W', H' 1 .. 65535,
+ *          W' H' < 2^25.
+ * Colour.  JFIF full-range YCbCr per pixel, 32 bits signed, arithmetic (floor) shifts:
+ *            Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *            Cb = clamp(((-11058 R - 21710 G + 32768 B + 32768) >> 16) + 128, 0, 255)      (R = G = 0, B = 255 gives 256 before the clamp)
+ *            Cr = clamp(((32768 R - 27439 G - 5329 B + 32768) >> 16) + 128, 0, 255)
+ * MCUs.    4:2:0, MCUs of 16 x 16 pixels, mw = ceil(W' / 16), mh = ceil(H' / 16).  The three planes are extended to 16 mw x 16 mh by
+ *          repeating the last column and the last row; then Cb and Cr are halved:
+ *            c(y, x) = (p(2y, 2x) + p(2y, 2x + 1) + p(2y + 1, 2x) + p(2y + 1, 2x + 1) + 2) >> 2
+ * DCT.     Of each 8 x 8 block of p - 128, with the integer matrix T[u][x] = round(8192 s(u) cos((2x + 1) u pi / 16)), s(0) = sqrt(1 / 8),
+ *          s(u > 0) = 1 / 2 -- 64 constants (row 1: 4017 3406 2276 799 -799 -2276 -3406 -4017), never computed by the library:
+ *            rows     A[y][u] = (sum_x T[u][x] (p[y][x] - 128) + 128) >> 8          |A| < 2^14
+ *            columns  B[v][u] = sum_y T[v][y] A[y][u]                               |B| < 2^29: the coefficient times 2^18
+ * Tables.  The IJG rule for quality 1 .. 100: scale = 5000 / quality below 50, else 200 - 2 quality;
+ *          Q[k] = clamp((base[k] scale + 50) / 100, 1, 255), integer divisions, base the two example tables of Annex K of the standard.
+ * Quantisation.  q = sgn(B) floor((|B| + Q 2^17) / (Q 2^18)) (round half away from zero) = sgn(B) floor(((|B| + (Q << 17)) >> 18) / Q);
+ *          the 63 AC values are then clamped to +-1023 (DC lies in -1024 .. 1016).
+ * Entropy coding.  Baseline sequential, the zigzag order of the standard, the four "typical" Huffman tables of Annex K.3 - K.6, never
+ *          others.  One interleaved scan, blocks of an MCU in the order Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr.  DC: the difference to the
+ *          block of the same component before; category = bit length of |d|; value bits d for d >= 0, else d + 2^cat - 1.  AC: (run,
+ *          category) symbols, ZRL (0xF0) for each 16 zeros in front of a non-zero value, EOB (0x00) if and only if the last non-zero
+ *          coefficient lies before position 63.
+ * Restart intervals.  One MCU row each (DRI = mw): every row starts with the three DC predictors at 0, ends padded with 1-bits to a
+ *          byte, and every row but the last is followed by FF D0 + (r mod 8), r from 0.  Every 0xFF byte of entropy-coded data, one
+ *          that the padding completes included, is followed by 0x00.
+ * The file.  SOI; APP0 FF E0 00 10 'JFIF\0' 01 01 00 00 01 00 01 00 00; two DQT segments (ids 0 and 1, zigzag order); SOF0 (precision 8,
+ *          H', W', components 01 22 00, 02 11 01, 03 11 01); four DHT segments (DC0 AC0 DC1 AC1); DRI; SOS (01 00, 02 11, 03 11, 00 3F 00)
+ *          -- mlvfs_amd_jpeg_header_size() = 629 bytes --; the rows with their RST markers; EOI.                                      */
+size_t mlvfs_amd_jpeg_header_size(void);
+/* the file's bytes in front of the entropy-coded data into out[0 .. cap): returns their number, or 0 and writes nothing for a null
+ * pointer, a size outside the input's, a quality outside 1 .. 100, cap below 629 (mlvfs_amd_last_error).  Host code.                */
+size_t mlvfs_amd_jpeg_header(int pw, int ph, int quality, uint8_t *out, size_t cap);
+/* the two quantisation tables of a quality, natural (row-major) order, luminance then chrominance.  Host code.  MLVFS_AMD_ERR_ARG (out
+ * untouched): a null pointer, a quality outside 1 .. 100.                                                                            */
+int    mlvfs_amd_jpeg_qtables(int quality, uint8_t out[128]);
+/* bytes of device scratch mlvfs_amd_jpeg_encode_dev takes for nframes renderings of pw x ph; 0: a size outside the input's.  Host code. */
+size_t mlvfs_amd_jpeg_scratch_bytes(int pw, int ph, int nframes);
+/* nframes renderings of pw x ph RGB bytes `stride` apart -> per frame the entropy-coded data followed by EOI at d_out + k out_stride.
+ * h_lengths[k]: that length, known on return (the call synchronises `stream`).  h_status[k] = 1 where it exceeds `room`: then no byte
+ * at or behind `room` is touched and the frame's content is unspecified; otherwise 0, and bytes behind the stream and between frames
+ * are not touched.  The streams may begin at any address.  Every check happens before any device work: a null pointer, a size outside
+ * the input's, a quality outside 1 .. 100, a frame count outside 0 .. 65535, strides smaller than a rendering or than `room` (with more
+ * than one frame), a scratch off a 16-byte boundary or smaller than mlvfs_amd_jpeg_scratch_bytes, renderings, streams and scratch that
+ * overlap are MLVFS_AMD_ERR_ARG.                                                                                                     */
+int    mlvfs_amd_jpeg_encode_dev(const void *d_rgb, size_t stride, int pw, int ph, int quality, void *d_out, size_t out_stride, size_t room,
+                                 void *d_scratch, size_t scratch_bytes, uint32_t *h_lengths, int *h_status, int nframes, void *stream);
+/* mlvfs_amd_mount_rgb's frames, through the same stages, the same serve-order state, the same results[] and the same rendering, as
+ * JPEG files of `quality`: each rendering is encoded on the device where it lies, the header is written on the host and only the
+ * stream crosses the link.  sizes[k]: the bytes of file k.  flags[k] bit 0: the JPEG file would be larger than the TIFF
+ * (629 + stream > 256 + 3 W' H'), and the frame is served as mlvfs_amd_mount_rgb's TIFF, byte for byte.  out_stride: anything from
+ * mlvfs_amd_mount_rgb_size up.  May be interleaved with the other three serving calls on one handle; a handle that never calls it
+ * serves what it served before, launch for launch.  MLVFS_AMD_ERR_ARG besides mlvfs_amd_mount_rgb's: null sizes or flags, a quality
+ * outside 1 .. 100.                                                                                                                  */
+int    mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes,
+                            int *flags, int batch_frames, int io_threads, int *results);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):

@@ -24,8 +24,13 @@
 // mlvfs_amd_mount_rgb serves the same frames through the same stages as TIFF files of 8-bit sRGB at half size: each final frame is
 // developed into its other slot (k_render.hip) with the parameters its headers give in their final state (mlvfs_amd_rgb_params), and
 // only the 3 W' H' bytes cross the link.  No .dng header is written on that route; nothing in front of the last step knows.
+//
+// mlvfs_amd_mount_jpeg renders in the same way and then encodes each rendering where it lies (jpg_encode_batch, k_jpeg.hip): the stream
+// goes into the slot the frame was developed from, which is free by then, and only the stream crosses the link.  A file that would be
+// larger than the TIFF is served as the TIFF.
 #include "clip.h"
 #include "lj92enc.h"
+#include "jpeg.h"
 
 #include <cstring>
 #include <string>
@@ -138,10 +143,28 @@ int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstr
     return MLVFS_AMD_OK;
 }
 
+// where a JPEG call wants its answers (frame 0 of the batch first), and its quality
+struct Jpeg {
+    size_t *sizes;
+    int *flags;
+    int quality;
+};
+
+// what the encoder's row buffer has to hold for streams of at most `room` bytes: the rows unstuffed, each begun on a dword
+size_t jpg_rowcap(size_t room, int ph) { return room + 4 * (((size_t)ph + 15) / 16) + 4; }
+// the stream's room in a JPEG file that is to be no larger than the TIFF (0: there is none)
+size_t jpg_room(int pw, int ph)
+{
+    const size_t tiff = mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
+    return tiff > (size_t)JPG_HEADER_BYTES + 2 ? tiff - JPG_HEADER_BYTES : 0;
+}
+
 // The batch's final frames as rendered TIFF files: the parameters of every frame from its headers as they are now, one upload, runs of
 // frames that lie on one side of the slot pair developed into the other side in one launch, then header + 3 W' H' bytes per file.
+// jp: as JPEG files -- the run's renderings encoded into the slots they were developed from, then header + stream per file, or the
+// TIFF where that is the smaller file.
 int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *h_out,
-              size_t out_stride, int gain_q8, int w, int h)
+              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp)
 {
     hipStream_t s = c->stream;
     uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
@@ -161,8 +184,25 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         uint8_t *dst = (in_f ? O : F) + k0 * dstride;
         const int rc = launch_render2(final_at[k0], dstride, (const int32_t *)m.d_rgb + (size_t)k0 * 13, dst, dstride, w, h, k1 - k0, s);
         if (rc) return rc;
+        std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
+        const size_t room = jp ? std::min(jpg_room(pw, ph), dstride) : 0;
+        if (room) {
+            const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap(room, ph));
+            const int rj = jpg_encode_batch(dst, dstride, pw, ph, jp->quality, final_at[k0], dstride, room, m.d_scratch, l, res.data(), k1 - k0, s);
+            if (rj) return rj;
+        }
         for (int k = k0; k < k1; k++) {
             uint8_t *file = h_out + k * out_stride;
+            if (jp) {
+                const JpgOut &r = res[k - k0];
+                jp->flags[k] = r.status ? 1 : 0;
+                jp->sizes[k] = r.status ? hdr + served : (size_t)JPG_HEADER_BYTES + r.length;
+                if (!r.status) {
+                    (void)mlvfs_amd_jpeg_header(pw, ph, jp->quality, file, JPG_HEADER_BYTES);
+                    MLV_HIP(hipMemcpyAsync(file + JPG_HEADER_BYTES, final_at[k0] + (size_t)(k - k0) * dstride, r.length, hipMemcpyDeviceToHost, s));
+                    continue;
+                }
+            }
             (void)mlvfs_amd_rgb_header(pw, ph, file, hdr);
             MLV_HIP(hipMemcpyAsync(file + hdr, dst + (size_t)(k - k0) * dstride, served, hipMemcpyDeviceToHost, s));
         }
@@ -174,7 +214,7 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
 // frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly;
 // rgb_gain != 0: served rendered (mlvfs_amd_mount_rgb), and no .dng header is written -- a file may be smaller than one
 int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results,
-                const Lossless *ll, int rgb_gain = 0)
+                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr)
 {
     const mlvfs_amd_mount_opts_t &o = m.o;
     hipStream_t s = c->stream;
@@ -309,7 +349,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             for (int k = k0; k < k1; k++) final_at[k] = dst + (size_t)(k - k0) * dstride;
         }
     }
-    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h);
+    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp);
     if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll, sw, sh);
     const size_t served = (size_t)sw * sh * 2;
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
@@ -438,11 +478,11 @@ int mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int heigh
     return launch_bin2(d_frames, stride, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
 }
 
-// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb
+// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb, with jpeg_quality != 0 mlvfs_amd_mount_jpeg
 static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
-                       int batch_frames, int io_threads, int *results, int rgb_gain = 0)
+                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0)
 {
-    if (!mount || !h_out || (lossless && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!mount || !h_out || ((lossless || jpeg_quality) && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
     Mount &m = *(Mount *)mount;
     if (count < 0) { set_error("mount: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     if (count == 0) return MLVFS_AMD_OK;
@@ -485,6 +525,13 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
     scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
     if (lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
+    if (jpeg_quality) {
+        int pw, ph;
+        (void)rgb_geom(w, h, &pw, &ph);
+        if (pw > 65535 || ph > 65535) { set_error("mount: a JPEG file takes renderings of up to 65535 a side, not %dx%d", pw, ph); return MLVFS_AMD_ERR_ARG; }
+        if (const size_t room = std::min(jpg_room(pw, ph), dstride))
+            scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph)), batch_frames));
+    }
     m.served = true;
     Calib cal;
     int rc = calib_on_device(m.dark, m.flat, c, w, h, bpp, 0, &cal);
@@ -503,8 +550,9 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream, &cal);
         if (rc == MLVFS_AMD_OK) {
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
+            const Jpeg jp{ jpeg_quality ? sizes + f0 : nullptr, jpeg_quality ? flags + f0 : nullptr, jpeg_quality };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
-                             lossless ? &ll : nullptr, rgb_gain);
+                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr);
         }
         f0 += n;
     }
@@ -522,6 +570,14 @@ int mlvfs_amd_mount_rgb(void *mount, int first, int count, void *h_out, size_t o
 {
     if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
     return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8);
+}
+
+int mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes, int *flags,
+                         int batch_frames, int io_threads, int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality);
 }
 
 size_t mlvfs_amd_mount_rgb_size(const void *mount, int index)

@@ -69,6 +69,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_proxy_geom", "mlvfs_amd_bin2_dev", "mlvfs_amd_dng_header_proxy", "mlvfs_amd_mount_set_proxy", "mlvfs_amd_mount_dng_size",
     "mlvfs_amd_rgb_geom", "mlvfs_amd_rgb_header_size", "mlvfs_amd_rgb_lut", "mlvfs_amd_rgb_params", "mlvfs_amd_rgb_header",
     "mlvfs_amd_render2_dev", "mlvfs_amd_mount_rgb", "mlvfs_amd_mount_rgb_size",
+    "mlvfs_amd_jpeg_header_size", "mlvfs_amd_jpeg_header", "mlvfs_amd_jpeg_qtables", "mlvfs_amd_jpeg_scratch_bytes",
+    "mlvfs_amd_jpeg_encode_dev", "mlvfs_amd_mount_jpeg",
 ]
 
 
@@ -268,6 +270,12 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_render2_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp])
     sig("mlvfs_amd_mount_rgb", i, [vp, i, i, vp, sz, i, i, i, vp])
     sig("mlvfs_amd_mount_rgb_size", sz, [vp, i])
+    sig("mlvfs_amd_jpeg_header_size", sz, [])
+    sig("mlvfs_amd_jpeg_header", sz, [i, i, i, vp, sz])
+    sig("mlvfs_amd_jpeg_qtables", i, [i, vp])
+    sig("mlvfs_amd_jpeg_scratch_bytes", sz, [i, i, i])
+    sig("mlvfs_amd_jpeg_encode_dev", i, [vp, sz, i, i, i, vp, sz, sz, vp, sz, vp, vp, i, vp])
+    sig("mlvfs_amd_mount_jpeg", i, [vp, i, i, vp, sz, i, i, vp, vp, i, i, vp])
     _lib = L
     return L
 

@@ -12,6 +12,9 @@
     m.rgb(0, 16, gain=1.0) serves the same frames developed to 8-bit sRGB at half size, as TIFF files any viewer opens
     (include/mlvfs_amd.h, "rendered half-size sRGB frames"; mlvfs_amd/render.py is the definition in numpy).
 
+    files, flags = m.jpeg(0, 16, gain=1.0, quality=90) serves the same renderings as baseline JPEG files encoded on the GPU, a tenth
+    of the bytes (include/mlvfs_amd.h, "rendered frames as baseline JPEG files"; mlvfs_amd/jpeg.py is the definition in numpy).
+
 Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
 """
 from __future__ import annotations
@@ -133,6 +136,28 @@ class Mount:
         lib.check(self.L.mlvfs_amd_mount_rgb(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, batch, io_threads, lib.ptr(res)),
                   "mount_rgb")
         return out
+
+    def jpeg(self, first: int, count: int, gain: float = 1.0, quality: int = 90, batch: int = 8, io_threads: int = 0,
+             results: np.ndarray | None = None):
+        """The renderings of rgb() as baseline JPEG files of `quality` (1 .. 100), encoded on the GPU:
+        -> (files, flags): files[k] the bytes of file k, flags[k] bit 0 set where the JPEG file would be larger than the TIFF and the
+        frame is served as rgb()'s TIFF, byte for byte."""
+        gain_q8 = int(round(256 * gain))
+        if not 1 <= gain_q8 <= 65535:
+            raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
+        if not 1 <= quality <= 100:
+            raise ValueError(f"quality {quality} outside 1 .. 100")
+        stride = self.rgb_size(first) if count else 0
+        out = np.zeros((count, stride), np.uint8)
+        sizes = np.zeros(max(count, 1), np.uintp)
+        flags = np.zeros(max(count, 1), np.int32)
+        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
+                                        and results.size >= count):
+            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
+        res = np.zeros(max(count, 1), np.int32) if results is None else results
+        lib.check(self.L.mlvfs_amd_mount_jpeg(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, lib.ptr(sizes), lib.ptr(flags),
+                                              batch, io_threads, lib.ptr(res)), "mount_jpeg")
+        return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
 
     def close(self) -> None:
         if self.h:

@@ -1,14 +1,16 @@
 """Write a clip as a sequence of rendered half-size sRGB TIFF frames: every frame as the mount serves it with these options, developed
-to 8-bit RGB at half size on the GPU (mlvfs_amd_mount_rgb; include/mlvfs_amd.h, "rendered half-size sRGB frames").
+to 8-bit RGB at half size on the GPU (mlvfs_amd_mount_rgb; include/mlvfs_amd.h, "rendered half-size sRGB frames") -- or, with --jpeg,
+as baseline JPEG files encoded on the GPU (mlvfs_amd_mount_jpeg; "rendered frames as baseline JPEG files").
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--jpeg [QUALITY]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
 OUTDIR/<clip>_000000.tif ... hold (W // 2) x (H // 2) RGB pixels behind a 256-byte baseline TIFF header: any viewer opens them, any
 editing program takes the sequence as an offline proxy.  --gain is the only exposure control (the deflicker's bias is not applied: it
 only shapes the frame through the stages in front).  Frames are served in order, as one MLVFS process would serve them.  Nothing is
-overwritten: an existing file of the sequence ends the run before any frame is served."""
+overwritten: an existing file of the sequence ends the run before any frame is served.  --jpeg writes OUTDIR/<clip>_000000.jpg ...
+(quality 1 .. 100, 90 if none is given); a frame whose JPEG file would be larger than its TIFF is written as the .tif."""
 import argparse
 import os
 import sys
@@ -28,6 +30,7 @@ def main() -> int:
     ap.add_argument("src")
     ap.add_argument("outdir")
     ap.add_argument("--gain", type=float, default=1.0, help="exposure factor, in steps of 1 / 256 (1 / 256 .. 255.996)")
+    ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
     ap.add_argument("--cs", type=int, default=0, choices=(0, 2, 3, 5), help="chroma smoothing")
     ap.add_argument("--bad-pix", type=int, default=0, choices=(0, 1, 2), help="bad-pixel repair (2: aggressive)")
     ap.add_argument("--stripes", action="store_true", help="vertical stripes correction")
@@ -44,6 +47,8 @@ def main() -> int:
     a = ap.parse_args()
     if not 1 <= round(256 * a.gain) <= 65535:
         ap.error(f"--gain {a.gain} outside 1 / 256 .. 65535 / 256")
+    if a.jpeg and not 1 <= a.jpeg <= 100:
+        ap.error(f"--jpeg {a.jpeg} outside 1 .. 100")
     stem = os.path.splitext(os.path.basename(a.src))[0]
     opt = MlvfsOptions(chroma_smooth=a.cs, fix_bad_pixels=a.bad_pix, fix_stripes=int(a.stripes), dual_iso=a.dual_iso,
                        hdr_interpolation_method=a.hdr_interp, fix_pattern_noise=int(a.pattern_noise))
@@ -53,7 +58,8 @@ def main() -> int:
         if a.first < 0 or count <= 0 or a.first + count > r.frame_count:
             ap.error(f"frames {a.first} .. {a.first + count - 1} outside the clip ({r.frame_count} frames)")
         names = [os.path.join(a.outdir, f"{stem}_{k:06d}.tif") for k in range(a.first, a.first + count)]
-        taken = [n for n in names if os.path.exists(n)]
+        jpgs = [n[:-4] + ".jpg" for n in names]
+        taken = [n for n in names + (jpgs if a.jpeg else []) if os.path.exists(n)]
         if taken:
             print(f"{taken[0]} exists ({len(taken)} of {count} files): nothing is overwritten", file=sys.stderr)
             return 1
@@ -69,11 +75,16 @@ def main() -> int:
             with Mount(r, opt, deflicker=a.deflicker, basename="/" + os.path.basename(a.src), dark=dark, flat=flat) as m:
                 for f0 in range(0, count, a.batch):
                     n = min(a.batch, count - f0)
-                    files = m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads)
-                    for name, data in zip(names[f0:f0 + n], files):
+                    if a.jpeg:
+                        files, flags = m.jpeg(a.first + f0, n, gain=a.gain, quality=a.jpeg, batch=a.batch, io_threads=a.io_threads)
+                        targets = [names[f0 + k] if flags[k] & 1 else jpgs[f0 + k] for k in range(n)]
+                    else:
+                        files = [f.tobytes() for f in m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads)]
+                        targets = names[f0:f0 + n]
+                    for name, data in zip(targets, files):
                         with open(name, "xb") as out:                       # "x": never over a file that appeared meanwhile
-                            out.write(data.tobytes())
-                        total += data.size
+                            out.write(data)
+                        total += len(data)
             dt = time.perf_counter() - t0
         finally:
             if flat is not None:
