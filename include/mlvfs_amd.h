@@ -868,6 +868,9 @@ int    mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
+/* Test hook, host only: the two selection networks of k_frame_p5's pair step (csrc/median_nets.h) on the caller's values, n sets at a
+ * time.  net 4: mlv_sort4, in[4] -> out[4] per set; net 5: mlv_insert4, in[0..3] (sorted) and in[4] -> the sorted five, out[5] per set. */
+int mlvfs_amd_test_median_net(int net, int n, const int32_t *in, int32_t *out);
 /* the library's host EV tables against raw2ev_lin[16384] (index = pixel - black) and ev2raw[24 * 32768] (index 0 = EV -10 * 32768):
  * 0 = identical (main.c:128-196; no GPU needed) */
 int mlvfs_amd_selftest_tables(const int32_t *raw2ev_lin, const int32_t *ev2raw);

@@ -197,7 +197,6 @@ __device__ __forceinline__ void cell_multi_pk_tab(const uint32_t *p0, const uint
         asm volatile("" :: "v"(ev[i]), "v"(ev[i + 1]), "v"(ev[i + 2]), "v"(ev[i + 3]), "v"(ev[i + 4]), "v"(ev[i + 5]), "v"(ev[i + 6]), "v"(ev[i + 7]));
     }
     uint32_t nref_r = 1u - (uint32_t)ref_r, nref_b = 1u - (uint32_t)ref_b;
-    asm("" : "+v"(nref_r), "+v"(nref_b));       // (opaque, as measured in profiles/p5_table/; without it a step is two v_mov shorter: built, not yet run)
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         const uint32_t gb = (ev[4 * c + 1] + ev[4 * c + 2]) >> 1;                       // chroma_smooth.c:32,54 (both EVs >= 0: trunc == floor)
@@ -643,11 +642,12 @@ __global__ __launch_bounds__(256, 4) void k_frame_p(const FrameArgs a)
 // ================================================================ k_frame_p5: the packed-once pass as a streaming kernel (round 5, end)
 // k_frame_s's form (k_frame_s.hip) for cs5x5: a WAVE owns a column of the frame 62 items wide (lanes 0 / 63: the halo items), walks down it a
 // cell row per step, keeps the five packed rows of the window in registers, gets the right-hand group's sorted columns and rank window
-// from the next lane (v_mov_b32_dpp wave_shl, as k_frame_p's lanes do inside a row) and finishes row r - 2 when row r is in.  No
+// from the next lane (v_mov_b32_dpp wave_shl, as k_frame_p's lanes do inside a row) and finishes row r - 2 when row r is in -- two
+// rows per step, whose windows share four rows: sorted once, each window inserts its fifth (pair_step below).  No
 // s_barrier after the table load, no planes in LDS (only the pixels of the three rows between load and output wait there, in the
 // wave's own 6 KiB): 6.0 instead of 6.8 us per frame (profiles/r05/ab_p5.log).  With no barrier to keep short, the workgroup is the
 // CU's sixteen waves, and what four small workgroups spent on four copies of the mantissa table holds raw2ev itself (MLV_EV32_N ints,
-// indexed by pixel - black + 1: cell_multi_pk_tab): 124 VGPRs, 157 KiB of LDS, one workgroup per CU (profiles/p5_table/).
+// indexed by pixel - black + 1: cell_multi_pk_tab): 126 VGPRs, 157 KiB of LDS, one workgroup per CU (profiles/p5_table/, profiles/p5_pair/).
 //   * Reference: one per task (a column of seg_rows rows), the median of five cells at its centre like k_frame_p's.
 //   * A strip whose packed median is not provably exact marks its lane and row; when the task ends, the tiles of k_frame's geometry
 //     that those strips lie in go on the launch's work list and the list-mode k_frame does them again (what this kernel wrote there
@@ -669,12 +669,13 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
     asm volatile("" : "+s"(cols));
     constexpr int BPP = 14;                              // (S_OUT: items a wave writes per row, frame_plan.h: FRAME_STREAM_COLW)
     constexpr int WAVES = 16;                            // one workgroup per CU: the CU's one copy of the table
+    constexpr int SLOTS = 3;                             // rows of parked pixels per wave
     // the lanes that write a row park it (1 .. 62; lanes 0 and 63 share their neighbours' slots, unused): with 64 slots a row the
     // workgroup would need 16 bytes more than a CU has
     constexpr int PARK_LANES = 62;
     struct __align__(16) Smem {
         int ev[MLV_EV32_N];                              // at offset 0: a look-up's address is its offset
-        uint4 park[WAVES][3][2][PARK_LANES];
+        uint4 park[WAVES][SLOTS][2][PARK_LANES];
     };
     static_assert(sizeof(Smem) <= 160 * 1024, "the CU's LDS");
     __shared__ Smem sm;
@@ -781,29 +782,18 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
                 }
             }
         }
-        uint32_t pkr[5][4] = {};                          // packed rows r - 4 .. r
-        int ge2[4] = { 0, 0, 0, 0 }, ge1[4] = { 0, 0, 0, 0 };
+        uint32_t pkr[4][4] = {};                          // packed rows r - 4 .. r - 1
+        int geA[4] = { 0, 0, 0, 0 }, geB[4] = { 0, 0, 0, 0 };      // green EVs of rows r - 2 and r - 1
         int fl1 = 3, fl2 = 3, fl3 = 3, fl4 = 3;          // low / dim flags of rows r - 1 .. r - 4 (k_frame_s.hip)
         unsigned long long unc_lanes = 0;                // lanes with an uncertain strip in some row of the task
         int unc_r0 = 1 << 30, unc_r1 = -1;               // ... and the rows
-        // One step: row r comes in (d0 / d1: its stream words, loaded two steps ago), row r - 2 goes out.  OUT and PRE say where the step
-        // stands in the task and are fixed where it is written (the loops below).  OUT: the step has an output stage.  PRE: it loads
-        // row r + 2 into the registers it has just emptied -- always, at the clamped row: as a condition of the step the registers
-        // became a merge of "loaded" and "kept", copied at the loop's edges behind a drained wait (trap 1).  A step
-        // with an output stage issues that load behind its table look-ups' wait and ahead of its stores (stream_output's hook), so
-        // the load stays in flight until the NEXT step's look-ups are waited for; n0 / n1, the other buffer, is what the next step
-        // unpacks: named as used at that point, where it has arrived, it costs the next step no wait of its own (the compiler cannot
-        // see that every path through the output stage's variants waits; its wait at the next step's head would count the stores and
-        // the load just issued as older and drain them).
-        auto step = [&](auto OUT, auto PRE, int r, uint32_t (&d0)[4], uint32_t (&d1)[4], const uint32_t (&n0)[4], const uint32_t (&n1)[4]) {
+        // Row r comes in (d0 / d1: its stream words, loaded a pair step ago): unpacked, its pixel-map cells replaced, converted, parked.
+        // after_unpack: where a step without an output stage re-issues the registers just emptied.  Returns the row's low / dim flags.
+        auto load_row = [&](int r, const uint32_t (&d0)[4], const uint32_t (&d1)[4], auto after_unpack, int (&ge)[4], uint32_t (&pk)[4]) {
             uint32_t p0[8], p1[8];
             unpack8<BPP>(d0, t.sel, t.sel, t.sel, p0);
             unpack8<BPP>(d1, t.sel1, t.sel1, t.sel1, p1);
-#ifdef P5_AB_EARLY_PREFETCH
-            if constexpr (PRE.value) issue(r + 2, d0, d1);
-#else
-            if constexpr (PRE.value && !OUT.value) issue(r + 2, d0, d1);
-#endif
+            after_unpack();
             if (n_pm) {                                   // pixel-map cells of this row: the owning lane takes the record's pixels
                 unsigned long long m = __ballot(lane < n_pm && (pm_cell >> 16) == r);
                 while (m) {
@@ -821,103 +811,136 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
             }
             bool dark;
             const int fl0 = stream_row_low(p0, p1, black, dark);
-            int ge[4];
-            uint32_t pk[4];
             if (!dark) cell_multi_pk_tab<4>(p0, p1, koff, sm.ev, ref_r, ref_b, ge, pk);
             else cell_multi_pk_tab_dark<4>(p0, p1, koff, sm.ev, ref_r, ref_b, ge, pk);
             {
-                uint4 (&slot)[2][PARK_LANES] = mypark[(unsigned)(r + 6) % 3u];
+                uint4 (&slot)[2][PARK_LANES] = mypark[(unsigned)(r + 2 * SLOTS) % (unsigned)SLOTS];
                 if (parks) {
                     slot[0][plane] = make_uint4(p0[0] | (p0[1] << 16), p0[2] | (p0[3] << 16), p0[4] | (p0[5] << 16), p0[6] | (p0[7] << 16));
                     slot[1][plane] = make_uint4(p1[0] | (p1[1] << 16), p1[2] | (p1[3] << 16), p1[4] | (p1[5] << 16), p1[6] | (p1[7] << 16));
                 }
             }
-#pragma unroll
-            for (int i = 0; i < 4; i++) { pkr[0][i] = pkr[1][i]; pkr[1][i] = pkr[2][i]; pkr[2][i] = pkr[3][i]; pkr[3][i] = pkr[4][i]; pkr[4][i] = pk[i]; }
-            if constexpr (OUT.value) {
-                const int jr = r - 2, y = 2 * jr, yl = y + 2 * roff;
-#ifndef P5_AB_LATE_OUTARGS
-                // what the look-ups need of the cold arguments (their table, and `stripes`, which picks the variant): asked for a median
-                // chain ahead of them.  The rest is read where it is used (held through the chain it is what the allocator spills)
-                KArgs ke = cold_args();
-                const uint2 *const e2d_early = ke->e2d;
-                const int stripes_early = ke->stripes;
-#endif
-                const unsigned long long msmooth = lanes_ge(yl, 4) & lanes_lt(yl, h - 5);  // chroma_smooth.c:25
-                const bool smooth_row = y + 2 * (nparts - 1) * seg_rows >= 4 && y < h - 5; // (some group's row)
-                mlv_pk16 o[STRIP] = { { 0, 0 }, { 0, 0 }, { 0, 0 }, { 0, 0 } };
-                if (smooth_row) {
-                    PGroup gq;
-                    {
-                        mlv_pk16 col[4][5];
-#pragma unroll
-                        for (int rr = 0; rr < 5; rr++)
-#pragma unroll
-                            for (int cc = 0; cc < 4; cc++) col[cc][rr] = as_pk(pkr[rr][cc]);
-#pragma unroll
-                        for (int cc = 0; cc < 4; cc++) mlv_sort5(col[cc], gq.s[cc]);
-                        mlv_merge55(gq.s[0], gq.s[1], gq.p0);
-                        mlv_merge55(gq.s[2], gq.s[3], gq.p1);
-                    }
-                    mlv_quad_mid6(gq.p0, gq.p1, gq.q);
-                    PNext n;
-                    pchain_fetch_lists(gq, n);
-                    pchain_fetch_window(gq, n);
-                    mlv_pk16 oc[STRIP];
-                    pchain_finish(gq, n, oc);
-                    // the chain's four medians are those of the lane's cells 2, 3 and of the NEXT lane's cells 0, 1 (its window is the lane's
-                    // group and the next one): the lane's own cells 0, 1 come from the lane before
-                    o[0] = as_pk((uint32_t)dpp_prev_i((int)as_u(oc[2]))); o[1] = as_pk((uint32_t)dpp_prev_i((int)as_u(oc[3])));
-                    o[2] = oc[0]; o[3] = oc[1];
-                    const unsigned long long um = __ballot(t.writes && pk_uncertain(o)) & msmooth;
-                    if (um) { unc_lanes |= um; unc_r0 = min(unc_r0, jr); unc_r1 = max(unc_r1, jr); }
-                }
-                int er[STRIP], eb[STRIP];
-#pragma unroll
-                for (int cc = 0; cc < STRIP; cc++) {
-                    er[cc] = wadd(wadd(ge2[cc], ref_r), (int)o[cc].x);
-                    eb[cc] = wadd(wadd(ge2[cc], ref_b), (int)o[cc].y);
-                }
-                uint32_t top[STRIP], bot[STRIP];
-                {
-                    const uint4 (&slot)[2][PARK_LANES] = mypark[(unsigned)(jr + 6) % 3u];
-                    const uint4 t4 = slot[0][plane], b4 = slot[1][plane];
-                    top[0] = t4.x; top[1] = t4.y; top[2] = t4.z; top[3] = t4.w;
-                    bot[0] = b4.x; bot[1] = b4.y; bot[2] = b4.z; bot[3] = b4.w;
-                }
-#ifndef P5_AB_LATE_OUTARGS
-                OutArgs oa = out_args(cold_args());                // (read here, not held through the step: 39 -> 17 spilled scalars)
-                oa.e2d = e2d_early; oa.stripes = stripes_early;
-#else
-                const OutArgs oa = out_args(cold_args());
-#endif
-                // (the five rows of the window; stream_output adds what smoothing makes of them)
-                stream_output<5>(oa, t, tx0, xm, rs_out, w, h, black, jr, yl, msmooth, fl0 | fl1 | fl2 | fl3 | fl4, ge2, er, eb, top, bot, [&] {
-#ifndef P5_AB_EARLY_PREFETCH
-                    if constexpr (PRE.value) {
-                        asm volatile("" :: "v"(n0[0]), "v"(n0[1]), "v"(n0[2]), "v"(n0[3]), "v"(n1[0]), "v"(n1[1]), "v"(n1[2]), "v"(n1[3]));
-                        issue(r + 2, d0, d1);
-                    }
-#endif
-                });
-            }
-#pragma unroll
-            for (int cc = 0; cc < 4; cc++) { ge2[cc] = ge1[cc]; ge1[cc] = ge[cc]; }
-            fl4 = fl3; fl3 = fl2; fl2 = fl1; fl1 = fl0;
+            return fl0;
         };
-        // The task's j1 - j0 + 4 steps, peeled so that no step tests where it stands: four that only fill the window (rows j0 - 2 ..
-        // j0 + 1), pairs with an output stage and a prefetch while the first of a pair still has a row to fetch (the second may fetch
-        // one row past the task: clamped, unused), and the last one or two, which fetch nothing, in one copy that picks its buffer.
+        // the four rows that the windows of rows jr and jr + 1 share (jr - 1 .. jr + 2), sorted column by column
+        auto sort_common = [&](const uint32_t (&ra)[4], const uint32_t (&rb)[4], const uint32_t (&rc)[4], const uint32_t (&rd)[4], mlv_pk16 (&c4)[4][4]) {
+#pragma unroll
+            for (int cc = 0; cc < 4; cc++) {
+                const mlv_pk16 v[4] = { as_pk(ra[cc]), as_pk(rb[cc]), as_pk(rc[cc]), as_pk(rd[cc]) };
+                mlv_sort4(v, c4[cc]);
+            }
+        };
+        // Row jr goes out: the window's fifth row (x: row jr - 2 or jr + 2) is inserted into the sorted four, and from the sorted
+        // columns on the chain and the output stage are what they were.  fl: the flags of the window's five rows; gej: the row's green
+        // EVs.  hook: what stream_output runs behind its look-ups' wait and ahead of its stores (the prefetch).
+        auto finish_row = [&](int jr, const mlv_pk16 (&c4)[4][4], const uint32_t (&x)[4], int fl, const int (&gej)[4], auto hook) {
+            const int y = 2 * jr, yl = y + 2 * roff;
+            // what the look-ups need of the cold arguments (their table, and `stripes`, which picks the variant): asked for a median
+            // chain ahead of them.  The rest is read where it is used (held through the chain it is what the allocator spills)
+            KArgs ke = cold_args();
+            const uint2 *const e2d_early = ke->e2d;
+            const int stripes_early = ke->stripes;
+            const unsigned long long msmooth = lanes_ge(yl, 4) & lanes_lt(yl, h - 5);  // chroma_smooth.c:25
+            const bool smooth_row = y + 2 * (nparts - 1) * seg_rows >= 4 && y < h - 5; // (some group's row)
+            mlv_pk16 o[STRIP] = { { 0, 0 }, { 0, 0 }, { 0, 0 }, { 0, 0 } };
+            if (smooth_row) {
+                PGroup gq;
+#pragma unroll
+                for (int cc = 0; cc < 4; cc++) {
+                    const mlv_pk16 xv[1] = { as_pk(x[cc]) };
+                    mlv_insert4(c4[cc], xv, gq.s[cc]);
+                }
+                mlv_merge55(gq.s[0], gq.s[1], gq.p0);
+                mlv_merge55(gq.s[2], gq.s[3], gq.p1);
+                mlv_quad_mid6(gq.p0, gq.p1, gq.q);
+                PNext n;
+                pchain_fetch_lists(gq, n);
+                pchain_fetch_window(gq, n);
+                mlv_pk16 oc[STRIP];
+                pchain_finish(gq, n, oc);
+                // the chain's four medians are those of the lane's cells 2, 3 and of the NEXT lane's cells 0, 1 (its window is the lane's
+                // group and the next one): the lane's own cells 0, 1 come from the lane before
+                o[0] = as_pk((uint32_t)dpp_prev_i((int)as_u(oc[2]))); o[1] = as_pk((uint32_t)dpp_prev_i((int)as_u(oc[3])));
+                o[2] = oc[0]; o[3] = oc[1];
+                const unsigned long long um = __ballot(t.writes && pk_uncertain(o)) & msmooth;
+                if (um) { unc_lanes |= um; unc_r0 = min(unc_r0, jr); unc_r1 = max(unc_r1, jr); }
+            }
+            int er[STRIP], eb[STRIP];
+#pragma unroll
+            for (int cc = 0; cc < STRIP; cc++) {
+                er[cc] = wadd(wadd(gej[cc], ref_r), (int)o[cc].x);
+                eb[cc] = wadd(wadd(gej[cc], ref_b), (int)o[cc].y);
+            }
+            uint32_t top[STRIP], bot[STRIP];
+            {
+                const uint4 (&slot)[2][PARK_LANES] = mypark[(unsigned)(jr + 2 * SLOTS) % (unsigned)SLOTS];
+                const uint4 t4 = slot[0][plane], b4 = slot[1][plane];
+                top[0] = t4.x; top[1] = t4.y; top[2] = t4.z; top[3] = t4.w;
+                bot[0] = b4.x; bot[1] = b4.y; bot[2] = b4.z; bot[3] = b4.w;
+            }
+            OutArgs oa = out_args(cold_args());                // (read here, not held through the step: 39 -> 17 spilled scalars)
+            oa.e2d = e2d_early; oa.stripes = stripes_early;
+            // (the five rows of the window; stream_output adds what smoothing makes of them)
+            stream_output<5>(oa, t, tx0, xm, rs_out, w, h, black, jr, yl, msmooth, fl, gej, er, eb, top, bot, hook);
+        };
+        auto named_as_used = [](const uint32_t (&n0)[4], const uint32_t (&n1)[4]) {
+            asm volatile("" :: "v"(n0[0]), "v"(n0[1]), "v"(n0[2]), "v"(n0[3]), "v"(n1[0]), "v"(n1[1]), "v"(n1[2]), "v"(n1[3]));
+        };
+        // One pair step: rows r and r + 1 come in (buffers A and B), rows r - 2 and r - 1 go out.  The two windows share rows r - 3 .. r:
+        // sorted once per column; window A adds row r - 4, window B row r + 1.  Window A's chain and output stage run before row r + 1 is
+        // converted: its temporaries are dead by then, and row r + 1 is parked in the slot that row r - 2 has just left (three slots:
+        // rows r - 2, r - 1, r.  Four slots and both rows converted ahead of both chains need twelve waves and 134 VGPRs: slower than
+        // the single-row step).  OUT: the step has its two
+        // output stages (the warm-up has none).  The prefetch of rows r + 2 and r + 3 goes into the registers just emptied -- always, at
+        // the clamped row: as a condition of the step the registers became a merge of "loaded" and "kept", copied at the loop's edges
+        // behind a drained wait (trap 1).  A step with output stages issues each behind that stage's look-ups' wait and
+        // ahead of its stores (stream_output's hook), so a row's loads stay in flight for two chains; the OTHER buffer is what is
+        // unpacked next: named as used at that point, where it has arrived (the look-ups were issued behind it, the counter is in
+        // order), it costs no wait of its own (the compiler cannot see that every path through the output stage's variants waits; its
+        // wait at the next unpack would count the stores and the load just issued as older and drain them).
+        auto pair_step = [&](auto OUT, int r) {
+            int ge0[4], ge1[4];
+            uint32_t pk0[4], pk1[4];
+            mlv_pk16 c4[4][4];
+            auto early_a = [&] { if constexpr (!OUT.value) issue(r + 2, dA0, dA1); };
+            auto early_b = [&] { if constexpr (!OUT.value) issue(r + 3, dB0, dB1); };
+            auto late_a = [&] { named_as_used(dB0, dB1); issue(r + 2, dA0, dA1); };
+            auto late_b = [&] { named_as_used(dA0, dA1); issue(r + 3, dB0, dB1); };
+            const int f0 = load_row(r, dA0, dA1, early_a, ge0, pk0);
+            if constexpr (OUT.value) {
+                sort_common(pkr[1], pkr[2], pkr[3], pk0, c4);
+                finish_row(r - 2, c4, pkr[0], f0 | fl1 | fl2 | fl3 | fl4, geA, late_a);
+            }
+            const int f1 = load_row(r + 1, dB0, dB1, early_b, ge1, pk1);
+            if constexpr (OUT.value) finish_row(r - 1, c4, pk1, f1 | f0 | fl1 | fl2 | fl3, geB, late_b);
+#pragma unroll
+            for (int i = 0; i < 4; i++) { pkr[0][i] = pkr[2][i]; pkr[1][i] = pkr[3][i]; pkr[2][i] = pk0[i]; pkr[3][i] = pk1[i]; geA[i] = ge0[i]; geB[i] = ge1[i]; }
+            fl4 = fl2; fl3 = fl1; fl2 = f0; fl1 = f1;
+        };
+        // The single-row step that ends a task: row r comes in, row r - 2 goes out, nothing is fetched.  Sorting four rows and inserting
+        // the fifth costs what mlv_sort5 did (10 + 8 min / max)
+        auto single_step = [&](int r, const uint32_t (&d0)[4], const uint32_t (&d1)[4]) {
+            int ge0[4];
+            uint32_t pk0[4];
+            mlv_pk16 c4[4][4];
+            const int f0 = load_row(r, d0, d1, [] {}, ge0, pk0);
+            sort_common(pkr[1], pkr[2], pkr[3], pk0, c4);
+            finish_row(r - 2, c4, pkr[0], f0 | fl1 | fl2 | fl3 | fl4, geA, StreamNoHook());
+#pragma unroll
+            for (int i = 0; i < 4; i++) { pkr[0][i] = pkr[1][i]; pkr[1][i] = pkr[2][i]; pkr[2][i] = pkr[3][i]; pkr[3][i] = pk0[i]; geA[i] = geB[i]; geB[i] = ge0[i]; }
+            fl4 = fl3; fl3 = fl2; fl2 = fl1; fl1 = f0;
+        };
+        // The task's j1 - j0 + 4 rows, peeled so that no step tests where it stands: two pair steps that only fill the window (rows
+        // j0 - 2 .. j0 + 1), pair steps with output stages and prefetch while the first row of a pair still has a row to fetch (the
+        // second may fetch one row past the task: clamped, unused), and the last one or two rows (a task of an odd number of rows
+        // leaves one), single steps that fetch nothing, in one copy that picks its buffer.
         constexpr std::true_type Y{};
         constexpr std::false_type N{};
         int r = j0 - 2;
 #pragma unroll 1
-        for (; r < j0 + 2; r += 2) {
-            step(N, Y, r, dA0, dA1, dB0, dB1);
-            step(N, Y, r + 1, dB0, dB1, dA0, dA1);
-        }
+        for (; r < j0 + 2; r += 2) pair_step(N, r);
         // (the main loop's first step finds its row arrived, as every later one does: the same state on both ways into the loop's head)
-        asm volatile("" :: "v"(dA0[0]), "v"(dA0[1]), "v"(dA0[2]), "v"(dA0[3]), "v"(dA1[0]), "v"(dA1[1]), "v"(dA1[2]), "v"(dA1[3]));
+        named_as_used(dA0, dA1);
         {
             KArgs ko = cold_args();
             rs_out = frame_rsrc(ko->dst + (size_t)f * ko->dst_stride, (uint32_t)w * (uint32_t)h * 2u);
@@ -925,16 +948,13 @@ __global__ __launch_bounds__(1024, 1) void k_frame_p5(const FrameArgs a, int col
             xm = c == 0 || 8 * (c * S_OUT + S_OUT) > w - 4;
         }
 #pragma unroll 1
-        for (; r < j1; r += 2) {
-            step(Y, Y, r, dA0, dA1, dB0, dB1);
-            step(Y, Y, r + 1, dB0, dB1, dA0, dA1);
-        }
+        for (; r < j1; r += 2) pair_step(Y, r);
 #pragma unroll 1
         for (bool second = false; r <= j1 + 1; r++, second = true) {
             uint32_t e0[4], e1[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) { e0[i] = second ? dB0[i] : dA0[i]; e1[i] = second ? dB1[i] : dA1[i]; }
-            step(Y, N, r, e0, e1, e0, e1);
+            single_step(r, e0, e1);
         }
         // ---- what this task could not settle goes to k_frame: the tiles (64 x 15 cells) its uncertain strips lie in
         if (list_all) { unc_lanes = ~0ull; unc_r0 = j0; unc_r1 = j1 - 1; }

@@ -65,6 +65,18 @@ extern "C" int mlvfs_amd_selftest_host(void)
             s.assign(v5, v5 + 5); std::sort(s.begin(), s.end());
             mlv_median5(v5, o); if (o[0] != s[2]) fails++;
         }
+        for (int it = 0; it < 20000; it++) {                 // k_frame_p5's pair step: four shared rows sorted once, a fifth inserted twice
+            int v[4], s4[4], x[1], s5[5], w5[5];
+            for (int &e : v) e = value(mode);
+            x[0] = value(mode);
+            mlv_sort4(v, s4);
+            mlv_insert4(s4, x, s5);
+            std::sort(v, v + 4);
+            for (int i = 0; i < 4; i++) { if (s4[i] != v[i]) fails++; w5[i] = v[i]; }
+            w5[4] = x[0];
+            std::sort(w5, w5 + 5);
+            for (int i = 0; i < 5; i++) if (s5[i] != w5[i]) fails++;
+        }
         for (int it = 0; it < 5000; it++) {
             int plane[5][12], med[8];
             for (auto &row : plane) for (int &x : row) x = value(mode);
@@ -79,6 +91,28 @@ extern "C" int mlvfs_amd_selftest_host(void)
     }
     if (!mlv::luts_ok()) fails += 1000000;
     return fails;
+}
+
+// The two networks of k_frame_p5's pair step on the caller's values, n sets at a time.  net 4: mlv_sort4, in[4] -> out[4] per set;
+// net 5: mlv_insert4, in[0..3] (sorted) and in[4] -> out[5] per set.
+extern "C" int mlvfs_amd_test_median_net(int net, int n, const int32_t *in, int32_t *out)
+{
+    if ((net != 4 && net != 5) || n < 0 || !in || !out) return MLVFS_AMD_ERR_ARG;
+    for (int k = 0; k < n; k++) {
+        if (net == 4) {
+            int v[4], o[4];
+            for (int i = 0; i < 4; i++) v[i] = in[4 * k + i];
+            mlv_sort4(v, o);
+            for (int i = 0; i < 4; i++) out[4 * k + i] = o[i];
+        } else {
+            int a[4], x[1], o[5];
+            for (int i = 0; i < 4; i++) a[i] = in[5 * k + i];
+            x[0] = in[5 * k + 4];
+            mlv_insert4(a, x, o);
+            for (int i = 0; i < 5; i++) out[5 * k + i] = o[i];
+        }
+    }
+    return 0;
 }
 
 // The library's host EV tables (its own formulas, or the caller's get_raw2ev / get_ev2raw when the caller exports them) against

@@ -52,7 +52,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_rand_stream", "mlvfs_amd_rand_stream_dev", "mlvfs_amd_process_frames_dev", "mlvfs_amd_process_frames_host",
     "mlvfs_amd_host_alloc", "mlvfs_amd_host_free", "mlvfs_amd_host_owns", "mlvfs_amd_host_size", "mlvfs_amd_host_knows", "mlvfs_amd_host_trim", "mlvfs_amd_hdr_preview_dev",
     "mlvfs_amd_cr2hdr20_dev", "mlvfs_amd_cr2hdr20_batch_dev", "mlvfs_amd_dualiso_reset", "mlvfs_amd_dualiso_trim", "mlvfs_amd_dualiso_last_scalars", "mlvfs_amd_amaze_demosaic_dev", "mlvfs_amd_amaze_debug", "mlvfs_amd_amaze_rows_extent", "mlvfs_amd_amaze_rows_extra_mode",
-    "mlvfs_amd_timer_begin", "mlvfs_amd_timer_end", "mlvfs_amd_selftest_host", "mlvfs_amd_selftest_tables", "mlvfs_amd_frame_begin", "mlvfs_amd_frame_end", "mlvfs_amd_frame_sync", "mlvfs_amd_dropin_stats", "mlvfs_amd_test_fail_next", "mlvfs_amd_dropin_transfers", "mlvfs_amd_dropin_profile",
+    "mlvfs_amd_timer_begin", "mlvfs_amd_timer_end", "mlvfs_amd_selftest_host", "mlvfs_amd_selftest_tables", "mlvfs_amd_test_median_net", "mlvfs_amd_frame_begin", "mlvfs_amd_frame_end", "mlvfs_amd_frame_sync", "mlvfs_amd_dropin_stats", "mlvfs_amd_test_fail_next", "mlvfs_amd_dropin_transfers", "mlvfs_amd_dropin_profile",
     "mlvfs_amd_mlv_open", "mlvfs_amd_mlv_close", "mlvfs_amd_mlv_frame_count", "mlvfs_amd_mlv_chunk_count",
     "mlvfs_amd_mlv_xref", "mlvfs_amd_mlv_frame_headers", "mlvfs_amd_mlv_read_frames", "mlvfs_amd_mlv_process", "mlvfs_amd_mlv_process_dualiso",
     "mlvfs_amd_lj92_info", "mlvfs_amd_lj92_decode_dev", "mlvfs_amd_lj92_decode_untiled", "mlvfs_amd_lj92_encode_table", "mlvfs_amd_test_rand_layout", "mlvfs_amd_test_device_order", "mlvfs_amd_test_stream_plan", "mlvfs_amd_test_lj92_row_plan", "mlvfs_amd_test_lj92_encode_plan", "mlvfs_amd_test_frame_plan", "mlvfs_amd_test_last_frame_plan", "mlvfs_amd_test_stream_listed", "mlvfs_amd_test_dualiso_parts", "mlvfs_amd_lzma_uncompress",
@@ -193,6 +193,7 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_timer_end", i, [vp, i])
     sig("mlvfs_amd_selftest_host", i, [])
     sig("mlvfs_amd_selftest_tables", i, [vp, vp])
+    sig("mlvfs_amd_test_median_net", i, [i, i, vp, vp])
     sig("mlvfs_amd_frame_begin", i, [])
     sig("mlvfs_amd_frame_end", i, [])
     sig("mlvfs_amd_frame_sync", i, [vp])

@@ -10,6 +10,8 @@ Design (sliding 5x5 window on a plane, one thread produces a horizontal strip):
      -- the only ranks of a 4-column group that can still be the median of 25
   4. median of 25 = 6th smallest of {6 quad candidates} U {5th column} (final)
   Steps 1-3 are shared by neighbouring outputs of the strip.
+  k_frame_p5 finishes two rows per step: their windows share four rows, sorted
+  once (sort4); each window then inserts its fifth row (insert4).
 
 The networks are built functionally (Batcher odd-even merge for arbitrary
 lengths), dead nodes are removed for the requested outputs, every network is
@@ -195,6 +197,27 @@ def main():
     code, ops = n.emit("mlv_sort5", [("v", 5)], res)
     parts.append(code)
     summary.append(("mlv_sort5", ops))
+
+    # k_frame_p5's pair step: two windows that share four of their five rows sort those four once ...
+    n = Net(4)
+    res = n.sort(list(range(4)))
+    check_select(n, 4, res, list(range(4)))
+    code, ops = n.emit("mlv_sort4", [("v", 4)], res)
+    assert ops == 10                         # 5 compare-exchanges
+    parts.append(code)
+    summary.append(("mlv_sort4", ops))
+
+    # ... and each inserts its own fifth row: o[i] = min(a[i], max(a[i - 1], x)) -- eight operations (four compare-exchanges' worth),
+    # two deep where a chain of compare-exchanges is four deep
+    n = Net(5)
+    a, x = [0, 1, 2, 3], 4
+    up = [n.mx(a[i], x) for i in range(4)]
+    res = [n.mn(a[0], x)] + [n.mn(a[i], up[i - 1]) for i in range(1, 4)] + [up[3]]
+    check_merge(n, 4, 1, res, list(range(5)))
+    code, ops = n.emit("mlv_insert4", [("a", 4), ("x", 1)], res)
+    assert ops == 8
+    parts.append(code)
+    summary.append(("mlv_insert4", ops))
 
     # plain selection networks (used for the 5- and 9-element windows, and as the
     # 25-element cross-check in the self test)
