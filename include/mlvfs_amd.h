@@ -866,6 +866,62 @@ int    mlvfs_amd_jpeg_encode_dev(const void *d_rgb, size_t stride, int pw, int p
 int    mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes,
                             int *flags, int batch_frames, int io_threads, int *results);
 
+/* -- rendered full-size sRGB frames (csrc/k_demosaic.hip, csrc/mount.cpp) --------------------------------------------- */
+/* The rendering at the size the frame was shot: three channels per sensor pixel.  The definition is this project's, in integers only,
+ * so that it has a byte-exact oracle (mlvfs_amd/demosaic.py): a fixed linear demosaic, the Malvar-He-Cutler 5x5 filter, whose
+ * coefficients are eighths and sixteenths, between the half-size rendering's balance and its matrix.
+ * Geometry.  A W x H frame with W, H >= 4 and W H < 2^25 becomes W x H RGB pixels; odd sizes are allowed.  The CFA is RGGB.  No crop.
+ * Input.  The frame mlvfs_amd_mount_dng would have served, and the 13 parameters black, A[3], K[9] exactly as mlvfs_amd_rgb_params
+ * yields them for the half-size rendering.
+ *   1. balance every sensor pixel at its own site: the site's colour is j(y, x) = (y & 1) + (x & 1) (0 R, 1 G, 2 B) and
+ *                   b(y, x) = min((max(in(y, x) - black, 0) * A_j + 2048) >> 12, 65535)        the product in 64 bits
+ *      (steps 1's clamp and 2 of the half-size definition per pixel).  Balancing before interpolating keeps clipped highlights
+ *      neutral -- every channel stops at 65535 first -- and gives the filter's cross-channel terms channels of equal scale.
+ *      Border.  b outside the frame is b reflected about the edge pixel: index i < 0 stands for -i, i >= n for 2 (n - 1) - i
+ *      (-1 -> 1, -2 -> 2, n -> n - 2, n + 1 -> n - 3).  The reflection keeps the CFA parity and needs n >= 3.
+ *   2. interpolate, in sixteenths.  With c = b(y, x),
+ *                   h1 = b(y, x - 1) + b(y, x + 1)      v1 = b(y - 1, x) + b(y + 1, x)      d1 = the four diagonal neighbours
+ *                   h2 = b(y, x - 2) + b(y, x + 2)      v2 = b(y - 2, x) + b(y + 2, x)
+ *                   sG = 8 c + 4 (h1 + v1) - 2 (h2 + v2)                green at an R or B site
+ *                   sH = 10 c + 8 h1 - 2 d1 - 2 h2 + v2                 the colour whose samples lie left and right of a green site
+ *                   sV = 10 c + 8 v1 - 2 d1 - 2 v2 + h2                 the colour whose samples lie above and below a green site
+ *                   sD = 12 c + 4 d1 - 3 (h2 + v2)                      B at an R site, R at a B site
+ *                   site                          R     G     B
+ *                   R (even row, even column)     c     sG    sD
+ *                   G (even row, odd column)      sH    c     sV
+ *                   G (odd row, even column)      sV    c     sH
+ *                   B (odd row, odd column)       sD    sG    c
+ *      An interpolated channel is m = clamp((s + 8) >> 4, 0, 65535), the shift arithmetic (floor); the site's own channel is m = c.
+ *      |s| < 2^22: 32 bits signed hold every sum.
+ *   3., 4.  the half-size definition's, with n = (m_R, m_G, m_B): t_i = clamp((sum_j K[i][j] n_j + 32768) >> 16, 0, 4095) in 64 bits,
+ *      out_i = LUT[t_i]; bytes in R, G, B order, rows top down, no padding in a row.
+ * The file: mlvfs_amd_rgb_header(W, H, ...) followed by 3 W H bytes -- the same 256-byte TIFF header at full size.
+ * Not built: an adaptive demosaic, a crop to the active area, 16-bit output, highlight recovery, other CFA orders.               */
+/* *pw = width, *ph = height.  Host code.  MLVFS_AMD_ERR_ARG: a null pointer, a size below 4, 2^25 pixels or more. */
+int    mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph);
+/* mlvfs_amd_render2_dev at full size: nframes frames of width x height 16-bit pixels `stride` bytes apart -> their renderings, 3 W H
+ * bytes each, out_stride bytes apart, frame k with the 13 parameters d_params[13 k ..].  Bytes between frames and behind 3 W H are not
+ * touched.  Not in place.  Asynchronous on `stream`; every check happens before any device work, and the checks are
+ * mlvfs_amd_render2_dev's but for the size: below 4x4 or of 2^25 pixels and more is MLVFS_AMD_ERR_ARG.  width a multiple of 16 with
+ * source base and stride 16-byte and destination base and stride 8-byte aligned takes the fast form (k_render1_x16: a workgroup walks
+ * down a strip of 512 columns with the balanced rows in a ring in LDS, a lane writes 8 pixels, 24 bytes); anything else one output
+ * pixel per lane with its taps from global memory (k_render1_generic).                                                          */
+int    mlvfs_amd_render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                             size_t out_stride, int nframes, void *stream);
+/* mlvfs_amd_mount_rgb and mlvfs_amd_mount_jpeg at full size: the same arguments, the same stages, the same serve-order state and the
+ * same results[]; each file is the full-size TIFF (256 + 3 W H bytes) or the JPEG file of that rendering.  flags[k] bit 0: the JPEG
+ * file would be larger than the TIFF (629 + stream > 256 + 3 W H), and the frame is served as mlvfs_amd_mount_rgb_full's TIFF.
+ * out_stride: anything from mlvfs_amd_mount_rgb_full_size up.  The renderings (and a JPEG call's streams behind them) lie in a device
+ * buffer of their own, which the first full-size call allocates for its batch; a handle that never makes a full-size call serves what
+ * it served before, byte for byte and launch for launch.  May be interleaved with the other serving calls on one handle.
+ * MLVFS_AMD_ERR_ARG besides the half-size calls': frames below 4x4 or of 2^25 pixels and more.                                      */
+int    mlvfs_amd_mount_rgb_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int batch_frames,
+                                int io_threads, int *results);
+int    mlvfs_amd_mount_jpeg_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes,
+                                 int *flags, int batch_frames, int io_threads, int *results);
+/* bytes of file `index` as mlvfs_amd_mount_rgb_full serves it; 0: no such frame, or one below 4x4 or of 2^25 pixels and more */
+size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* Test hook, host only: the two selection networks of k_frame_p5's pair step (csrc/median_nets.h) on the caller's values, n sets at a

@@ -266,6 +266,11 @@ inline bool rgb_geom(int w, int h, int *pw, int *ph)
 }
 int launch_render2(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
                    hipStream_t stream);
+// rendered full-size sRGB frames (k_demosaic.hip): W x H pixels of a w x h frame, false below 4x4 and from 2^25 pixels on (what
+// mlvfs_amd_rgb_header writes); the demosaicing pass, with the same parameters
+inline bool rgb_full_geom(int w, int h) { return w >= 4 && h >= 4 && (uint64_t)w * (uint64_t)h < (1u << 25); }
+int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
+                   hipStream_t stream);
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

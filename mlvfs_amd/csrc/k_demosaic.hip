@@ -1,0 +1,291 @@
+// k_demosaic.hip -- rendered full-size sRGB frames: the frames the mount serves, developed to 8-bit RGB at the size they were shot
+// (include/mlvfs_amd.h, "rendered full-size sRGB frames").  A W x H RGGB frame becomes W x H pixels of 3 bytes:
+//     b(y, x) = min((max(in(y, x) - black, 0) * A_j + 2048) >> 12, 65535)     j = (y & 1) + (x & 1)      (the product in 64 bits)
+//     b outside the frame: reflected about the edge pixel (-1 -> 1, n -> n - 2)
+//     the Malvar-He-Cutler 5x5 filter in sixteenths, c = b(y, x), h1 / v1 / d1 the neighbours at distance 1, h2 / v2 at distance 2:
+//         sG = 8c + 4(h1 + v1) - 2(h2 + v2)     sH = 10c + 8 h1 - 2 d1 - 2 h2 + v2     sV = 10c + 8 v1 - 2 d1 - 2 v2 + h2
+//         sD = 12c + 4 d1 - 3(h2 + v2)          m = clamp((s + 8) >> 4, 0, 65535), or c for the site's own channel
+//     t_i = clamp((sum_j K[i][j] * m_j + 32768) >> 16, 0, 4095)     out_i = LUT[t_i]
+// black, A[3], K[9]: the half-size rendering's 13 int32 per frame (mlvfs_amd_rgb_params), uniform in a workgroup.
+//
+// The first stencil of the rendered routes.  Frames are batched in grid.y, never in place, no scratch, the 4 KiB LUT in LDS.
+//   k_render1_x16     : W % 16 == 0, source base and stride 16-byte, destination base and stride 8-byte aligned.  A workgroup of four
+//                       waves owns a strip of R1_STRIP columns and walks down R1_RUN rows of it, four rows a step, one row per wave.
+//                       Every source pixel it loads is balanced once (the 64-bit multiply) and kept as 16 bits in a ring of R1_RING
+//                       rows in LDS with a 2-pixel halo at both sides; a step's loads are issued before its arithmetic and stored
+//                       behind it, one barrier a step.  A lane produces an even-aligned group of 8 pixels of its wave's row -- the
+//                       CFA site of each is a compile-time fact, the row's parity is uniform in the wave -- = 24 bytes: three 64-bit
+//                       stores; a wave reads 1 KiB contiguous of a source row and writes 1.5 KiB contiguous.  Source bytes read:
+//                       (R1_RUN + 4) / R1_RUN rows of (R1_STRIP + 4) / R1_STRIP columns = 1.13 frames.
+//                       Where sum_j |K[i][j]| * 65535 + 32768 < 2^31 for every i (uniform: taken per frame from the parameters) step 3
+//                       runs in 24-bit multiplies and 32-bit sums, otherwise in 64 bits; the results are the same.
+//   k_render1_generic : any W, H >= 4, 2-byte source alignment, 1-byte destination alignment; one lane = one output pixel, the 13
+//                       taps straight from global memory with the reflection applied to the indices.
+// Bytes between frames and behind 3 * W * H are never touched.
+#include "clip.h"
+
+#define MLV_SRGB_LUT12_ATTR __device__ __attribute__((aligned(16)))          // stage_lut reads it in 16-byte pieces
+#include "srgb_lut12.h"
+
+namespace mlv {
+
+struct RenderParams {          // mlvfs_amd_rgb_params' out[13]
+    int32_t black, A[3], K[9];
+};
+static_assert(sizeof(RenderParams) == 13 * sizeof(int32_t), "mlvfs_amd_rgb_params' layout");
+
+namespace {                    // this file's device helpers
+
+constexpr int R1_STRIP = 512;                         // columns of a workgroup's strip: 64 lanes x 8 pixels
+constexpr int R1_RUN = 32;                            // rows a workgroup walks down
+constexpr int R1_RING = 16;                           // rows of the ring: the 12 a step has live (8 read, 4 written), as a power of two
+constexpr int R1_PITCH = 8 + R1_STRIP + 8;            // uint16 per ring row: the strip from [8] on, the halos at [6], [7] and behind it
+
+// 256 lanes x 16 bytes
+__device__ __forceinline__ void stage_lut(uint8_t *lut)
+{
+    ((uint4 *)lut)[threadIdx.x] = ((const uint4 *)kSrgbLut12)[threadIdx.x];
+    __syncthreads();
+}
+
+// what max(c - black, 0) needs for any int32 black with c < 2^16: c' = sat(c + lift - drop) in 32 bits unsigned
+struct Black {
+    uint32_t lift, drop;
+    __device__ explicit Black(int32_t black) : lift(black < 0 ? 0u - (uint32_t)black : 0u), drop(black > 0 ? (uint32_t)black : 0u) {}
+    __device__ __forceinline__ uint32_t operator()(uint32_t c) const { const uint32_t v = c + lift; return v > drop ? v - drop : 0u; }
+};
+
+__device__ __forceinline__ uint32_t balance(uint32_t c, int32_t A)
+{
+    const uint64_t v = ((uint64_t)c * (uint32_t)A + 2048u) >> 12;
+    return v < 65535u ? (uint32_t)v : 65535u;
+}
+
+// the index inside 0 .. n - 1 that stands for i in -2 .. n + 1 (n >= 3)
+__device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; }
+
+__device__ __forceinline__ uint32_t sixteenths(int s)
+{
+    const int m = (s + 8) >> 4;
+    return (uint32_t)(m < 0 ? 0 : m > 65535 ? 65535 : m);
+}
+
+// step 3 in 64 bits, and in 32 where the frame's K allows it (fits32: every |K| < 2^15, every sum below 2^31)
+template <bool K32>
+__device__ __forceinline__ uint32_t tone_index(const int32_t *K, uint32_t n0, uint32_t n1, uint32_t n2)
+{
+    if constexpr (K32) {
+        const int acc = __mul24(K[0], (int)n0) + __mul24(K[1], (int)n1) + __mul24(K[2], (int)n2) + 32768;
+        const int t = acc >> 16;
+        return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
+    }
+    const int64_t acc = (int64_t)K[0] * (int32_t)n0 + (int64_t)K[1] * (int32_t)n1 + (int64_t)K[2] * (int32_t)n2 + 32768;
+    const int64_t t = acc >> 16;
+    return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
+}
+
+__device__ __forceinline__ bool fits32(const RenderParams &p)
+{
+    bool ok = true;
+    for (int i = 0; i < 3; i++) {
+        uint64_t sum = 0;
+        for (int j = 0; j < 3; j++) { const int64_t k = p.K[3 * i + j]; sum += (uint64_t)(k < 0 ? -k : k); }
+        ok = ok && sum * 65535u + 32768u < (1ull << 31);
+    }
+    return ok;
+}
+
+// the three bytes of one output pixel in bits 0 .. 23: R, G, B from the low byte up
+template <bool K32>
+__device__ __forceinline__ uint32_t tone(const RenderParams &p, const uint8_t *lut, uint32_t m0, uint32_t m1, uint32_t m2)
+{
+    const uint32_t r = lut[tone_index<K32>(p.K, m0, m1, m2)], g = lut[tone_index<K32>(p.K + 3, m0, m1, m2)], b = lut[tone_index<K32>(p.K + 6, m0, m1, m2)];
+    return r | (g << 8) | (b << 16);
+}
+
+// ---- k_render1_x16
+// one source row of the strip as a wave loads it: 8 pixels per lane, and in lanes 0 .. 3 one halo pixel each
+struct RowLoad {
+    uint4 main;
+    uint32_t halo;
+};
+
+// row r of the frame (-2 .. h + 1 are reflected); rows behind rmax -- the frame's last row + 2, the run's last row + 2 -- are not needed
+// and not read; x0: the strip's first column, sw its width
+__device__ __forceinline__ void load_row(RowLoad &v, const uint16_t *src, int w, int h, int r, int rmax, int x0, int sw, int lane)
+{
+    if (r > rmax) return;
+    const uint16_t *row = src + (size_t)reflect(r, h) * w;
+    if (8 * lane < sw) v.main = *(const uint4 *)(row + x0 + 8 * lane);
+    if (lane < 4) v.halo = row[reflect(lane < 2 ? x0 - 2 + lane : x0 + sw + lane - 2, w)];
+}
+
+__device__ __forceinline__ uint32_t balance2(uint32_t d, const Black &bl, int32_t a_even, int32_t a_odd)
+{
+    return balance(bl(d & 0xFFFFu), a_even) | (balance(bl(d >> 16), a_odd) << 16);
+}
+
+// balanced once, into slot `slot` of the ring
+__device__ __forceinline__ void store_row(const RowLoad &v, uint16_t *ring, int slot, int r, int rmax, int sw, int lane, const Black &bl, const RenderParams &p)
+{
+    if (r > rmax) return;
+    const bool odd = r & 1;                                   // the reflection keeps the parity
+    const int32_t a_even = odd ? p.A[1] : p.A[0], a_odd = odd ? p.A[2] : p.A[1];
+    uint16_t *row = ring + slot * R1_PITCH;
+    if (8 * lane < sw)
+        *(uint4 *)(row + 8 + 8 * lane) = make_uint4(balance2(v.main.x, bl, a_even, a_odd), balance2(v.main.y, bl, a_even, a_odd),
+                                                    balance2(v.main.z, bl, a_even, a_odd), balance2(v.main.w, bl, a_even, a_odd));
+    if (lane < 4) row[lane < 2 ? 6 + lane : 8 + sw + lane - 2] = (uint16_t)balance(bl(v.halo), (lane & 1) ? a_odd : a_even);
+}
+
+__device__ __forceinline__ void unpack8(int *o, const uint4 &v)
+{
+    o[0] = v.x & 0xFFFFu; o[1] = v.x >> 16; o[2] = v.y & 0xFFFFu; o[3] = v.y >> 16;
+    o[4] = v.z & 0xFFFFu; o[5] = v.z >> 16; o[6] = v.w & 0xFFFFu; o[7] = v.w >> 16;
+}
+
+// the 8 pixels of one lane: rows y - 2 .. y + 2 of the ring at m2, m1, c0, p1, p2 (each at the lane's first pixel).  ODD: the row's parity
+template <bool ODD, bool K32>
+__device__ __forceinline__ void develop8(const uint16_t *m2, const uint16_t *m1, const uint16_t *c0, const uint16_t *p1, const uint16_t *p2,
+                                         const RenderParams &p, const uint8_t *lut, uint2 *o)
+{
+    int a[8], b[10], c[12], d[10], e[8];                      // a, e: columns 0 .. 7; b, d: -1 .. 8; c: -2 .. 9
+    unpack8(a, *(const uint4 *)m2);
+    unpack8(e, *(const uint4 *)p2);
+    unpack8(b + 1, *(const uint4 *)m1);
+    unpack8(d + 1, *(const uint4 *)p1);
+    unpack8(c + 2, *(const uint4 *)c0);
+    b[0] = m1[-1]; b[9] = m1[8];
+    d[0] = p1[-1]; d[9] = p1[8];
+    const uint32_t cl = *(const uint32_t *)(c0 - 2), cr = *(const uint32_t *)(c0 + 8);
+    c[0] = cl & 0xFFFFu; c[1] = cl >> 16; c[10] = cr & 0xFFFFu; c[11] = cr >> 16;
+    uint32_t px[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int cc = c[i + 2], h1 = c[i + 1] + c[i + 3], h2 = c[i] + c[i + 4], v1 = b[i + 1] + d[i + 1], v2 = a[i] + e[i];
+        const int d1 = b[i] + b[i + 2] + d[i] + d[i + 2];
+        uint32_t m0, mg, mb;
+        if ((i & 1) == (ODD ? 1 : 0)) {                       // an R site (even row) or a B site (odd row): green and the other colour
+            const uint32_t g = sixteenths(8 * cc + 4 * (h1 + v1) - 2 * (h2 + v2)), x = sixteenths(12 * cc + 4 * d1 - 3 * (h2 + v2));
+            m0 = ODD ? x : (uint32_t)cc; mg = g; mb = ODD ? (uint32_t)cc : x;
+        } else {                                              // a green site: the colour of its row and the colour of its column
+            const uint32_t sh = sixteenths(10 * cc + 8 * h1 - 2 * d1 - 2 * h2 + v2), sv = sixteenths(10 * cc + 8 * v1 - 2 * d1 - 2 * v2 + h2);
+            m0 = ODD ? sv : sh; mg = (uint32_t)cc; mb = ODD ? sh : sv;
+        }
+        px[i] = tone<K32>(p, lut, m0, mg, mb);
+    }
+    // four pixels of 24 bits are three dwords
+    o[0] = make_uint2(px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16));
+    o[1] = make_uint2((px[2] >> 16) | (px[3] << 8), px[4] | (px[5] << 24));
+    o[2] = make_uint2((px[5] >> 8) | (px[6] << 16), (px[6] >> 16) | (px[7] << 8));
+}
+
+// rows y0 .. y0 + R1_RUN - 1 of columns x0 .. x0 + sw - 1.  The ring's slot of row r: (r - y0 + 2) & (R1_RING - 1).
+template <bool K32>
+__device__ __forceinline__ void walk_strip(const uint16_t *src, uint8_t *dst, int w, int h, int x0, int sw, int y0, const RenderParams &p,
+                                           const Black &bl, uint16_t *ring, const uint8_t *lut)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rmax = min(h, y0 + R1_RUN) + 1;
+    RowLoad v = {};
+    // rows y0 - 2 .. y0 + 5: what the first step reads
+    for (int k = 0; k < 2; k++) {
+        const int r = y0 - 2 + 4 * k + wave;
+        load_row(v, src, w, h, r, rmax, x0, sw, lane);
+        store_row(v, ring, 4 * k + wave, r, rmax, sw, lane, bl, p);
+    }
+    __syncthreads();
+    for (int y = y0 + wave; y < y0 + R1_RUN; y += 4) {        // y - wave is uniform in the workgroup: every wave meets every barrier
+        const int rn = y + 6;                                 // the row this wave fetches for the next step
+        load_row(v, src, w, h, rn, rmax, x0, sw, lane);
+        if (y < h && 8 * lane < sw) {
+            const int s = y - y0 + 2;
+            const uint16_t *at = ring + 8 + 8 * lane;
+            const uint16_t *m2 = at + ((s - 2) & (R1_RING - 1)) * R1_PITCH, *m1 = at + ((s - 1) & (R1_RING - 1)) * R1_PITCH;
+            const uint16_t *c0 = at + (s & (R1_RING - 1)) * R1_PITCH;
+            const uint16_t *p1 = at + ((s + 1) & (R1_RING - 1)) * R1_PITCH, *p2 = at + ((s + 2) & (R1_RING - 1)) * R1_PITCH;
+            uint2 *o = (uint2 *)(dst + ((size_t)y * w + x0 + 8 * lane) * 3);
+            if (y & 1) develop8<true, K32>(m2, m1, c0, p1, p2, p, lut, o);
+            else develop8<false, K32>(m2, m1, c0, p1, p2, p, lut, o);
+        }
+        store_row(v, ring, (rn - y0 + 2) & (R1_RING - 1), rn, rmax, sw, lane, bl, p);
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+// grid.x = strips * runs, strips side by side first
+__global__ __launch_bounds__(256) void k_render1_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                     uint8_t *__restrict__ out, size_t out_stride, int w, int h, uint32_t strips)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[4096];
+    __shared__ __attribute__((aligned(16))) uint16_t ring[R1_RING * R1_PITCH];
+    stage_lut(lut);
+    const RenderParams p = params[blockIdx.y];
+    const Black bl(p.black);
+    const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
+    uint8_t *dst = out + (size_t)blockIdx.y * out_stride;
+    const int run = blockIdx.x / strips, x0 = (int)(blockIdx.x - run * strips) * R1_STRIP, sw = min(w - x0, R1_STRIP);
+    if (fits32(p)) walk_strip<true>(src, dst, w, h, x0, sw, run * R1_RUN, p, bl, ring, lut);
+    else walk_strip<false>(src, dst, w, h, x0, sw, run * R1_RUN, p, bl, ring, lut);
+}
+
+// ---- k_render1_generic
+// npix = W * H output pixels per frame
+__global__ __launch_bounds__(256) void k_render1_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                         uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, int w, int h)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[4096];
+    stage_lut(lut);
+    const RenderParams p = params[blockIdx.y];
+    const Black bl(p.black);
+    const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
+    uint8_t *dst = out + (size_t)blockIdx.y * out_stride;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < npix; k += gridDim.x * blockDim.x) {
+        const int y = (int)(k / (uint32_t)w), x = (int)(k - (uint32_t)y * (uint32_t)w);
+        // the balanced sample at (y + dy, x + dx): its site's colour is that of the reflected position too
+        auto tap = [&](int dy, int dx) -> int {
+            const int yy = reflect(y + dy, h), xx = reflect(x + dx, w);
+            const int j = (yy & 1) + (xx & 1);
+            return (int)balance(bl(src[(size_t)yy * w + xx]), j == 0 ? p.A[0] : j == 1 ? p.A[1] : p.A[2]);
+        };
+        const int c = tap(0, 0), h1 = tap(0, -1) + tap(0, 1), v1 = tap(-1, 0) + tap(1, 0), h2 = tap(0, -2) + tap(0, 2), v2 = tap(-2, 0) + tap(2, 0);
+        const int d1 = tap(-1, -1) + tap(-1, 1) + tap(1, -1) + tap(1, 1);
+        const uint32_t sg = sixteenths(8 * c + 4 * (h1 + v1) - 2 * (h2 + v2)), sd = sixteenths(12 * c + 4 * d1 - 3 * (h2 + v2));
+        const uint32_t sh = sixteenths(10 * c + 8 * h1 - 2 * d1 - 2 * h2 + v2), sv = sixteenths(10 * c + 8 * v1 - 2 * d1 - 2 * v2 + h2);
+        const bool yo = y & 1, xo = x & 1;
+        const uint32_t m0 = yo ? (xo ? sd : sv) : (xo ? sh : (uint32_t)c);
+        const uint32_t m1 = yo == xo ? sg : (uint32_t)c;
+        const uint32_t m2 = yo ? (xo ? (uint32_t)c : sh) : (xo ? sv : sd);
+        const uint32_t v = tone<false>(p, lut, m0, m1, m2);
+        uint8_t *o = dst + (size_t)k * 3;
+        o[0] = (uint8_t)v;
+        o[1] = (uint8_t)(v >> 8);
+        o[2] = (uint8_t)(v >> 16);
+    }
+}
+
+// d_out apart from d_frames (the callers check); w, h >= 4, w * h < 2^25; d_params: 13 int32 per frame, 4-byte aligned
+int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
+                   hipStream_t stream)
+{
+    if (nframes <= 0) return MLVFS_AMD_OK;
+    if (!rgb_full_geom(w, h)) { set_error("a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    const bool fast = w % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && ((uintptr_t)d_out % 8 == 0) &&
+                      (nframes == 1 || (stride % 16 == 0 && out_stride % 8 == 0));
+    if (fast) {
+        const uint32_t strips = ((uint32_t)w + R1_STRIP - 1) / R1_STRIP, runs = ((uint32_t)h + R1_RUN - 1) / R1_RUN;
+        hipLaunchKernelGGL(k_render1_x16, dim3(strips * runs, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                           (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips);
+    } else {
+        // the workgroups of a launch share the machine: each of them stages the table once, and the lanes stride over the rest
+        const uint32_t npix = (uint32_t)w * (uint32_t)h, cap = 4 * std::max(2048u / (uint32_t)nframes, 64u);
+        hipLaunchKernelGGL(k_render1_generic, dim3(std::min<uint32_t>((npix + 255) / 256, cap), nframes), dim3(256), 0, stream,
+                           (const uint8_t *)d_frames, stride, (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, npix, w, h);
+    }
+    MLV_HIP(hipGetLastError());
+    return MLVFS_AMD_OK;
+}
+
+}  // namespace mlv

@@ -28,6 +28,10 @@
 // mlvfs_amd_mount_jpeg renders in the same way and then encodes each rendering where it lies (jpg_encode_batch, k_jpeg.hip): the stream
 // goes into the slot the frame was developed from, which is free by then, and only the stream crosses the link.  A file that would be
 // larger than the TIFF is served as the TIFF.
+//
+// mlvfs_amd_mount_rgb_full and mlvfs_amd_mount_jpeg_full are the same two routes at the frame's own size: each final frame is demosaiced
+// (k_demosaic.hip, the same parameters) into a buffer of its own, d_full -- 3 W H bytes do not fit the frame's other slot --, and a
+// JPEG call's streams lie in that buffer behind the batch's renderings.  A handle that never makes a full-size call never allocates it.
 #include "clip.h"
 #include "lj92enc.h"
 #include "jpeg.h"
@@ -57,8 +61,9 @@ struct Mount {
     DevBuf d_bits;                           // the encoder's bit streams, sized from a batch's histograms
     DevBuf d_rgb;                            // mlvfs_amd_mount_rgb: 13 int32 parameters per frame of a batch
     std::vector<int32_t> rgb_host;           // what the upload reads: it outlives every call
+    DevBuf d_full;                           // the full-size calls: a batch's renderings of 3 W H bytes, a JPEG call's streams behind them
 
-    void release() { for (DevBuf *b : { &d_frames, &d_out, &d_scratch, &d_bits, &d_rgb }) b->release(); }
+    void release() { for (DevBuf *b : { &d_frames, &d_out, &d_scratch, &d_bits, &d_rgb, &d_full }) b->release(); }
 
     int ensure(int dev, size_t fbytes, size_t sbytes)
     {
@@ -159,17 +164,23 @@ size_t jpg_room(int pw, int ph)
     return tiff > (size_t)JPG_HEADER_BYTES + 2 ? tiff - JPG_HEADER_BYTES : 0;
 }
 
+// from one full-size rendering to the next in d_full
+size_t full_stride(int w, int h) { return up256((size_t)3 * w * h); }
+
 // The batch's final frames as rendered TIFF files: the parameters of every frame from its headers as they are now, one upload, runs of
 // frames that lie on one side of the slot pair developed into the other side in one launch, then header + 3 W' H' bytes per file.
 // jp: as JPEG files -- the run's renderings encoded into the slots they were developed from, then header + stream per file, or the
 // TIFF where that is the smaller file.
+// full: at the frame's own size -- the renderings go into d_full, full_stride(w, h) apart, and their streams behind the batch's renderings
 int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *h_out,
-              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp)
+              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp, bool full)
 {
     hipStream_t s = c->stream;
     uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
-    int pw, ph;
-    if (!rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    int pw = w, ph = h;
+    if (full ? !rgb_full_geom(w, h) : !rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering does not take frames of %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    const size_t rstride = full ? full_stride(w, h) : dstride;                          // from one rendering to the next
+    const size_t sstride = full ? up256(jpg_room(w, h)) : dstride;                      // from one stream to the next
     std::vector<int32_t> &params = m.rgb_host;
     params.resize((size_t)n * 13);
     for (int k = 0; k < n; k++) {
@@ -181,14 +192,17 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
     for (int k0 = 0, k1; k0 < n; k0 = k1) {
         const bool in_f = final_at[k0] == F + k0 * dstride;
         for (k1 = k0 + 1; k1 < n && (final_at[k1] == F + k1 * dstride) == in_f; k1++) {}
-        uint8_t *dst = (in_f ? O : F) + k0 * dstride;
-        const int rc = launch_render2(final_at[k0], dstride, (const int32_t *)m.d_rgb + (size_t)k0 * 13, dst, dstride, w, h, k1 - k0, s);
+        uint8_t *dst = full ? (uint8_t *)m.d_full + k0 * rstride : (in_f ? O : F) + k0 * dstride;
+        uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
+        const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
+        const int rc = full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s)
+                            : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s);
         if (rc) return rc;
         std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
-        const size_t room = jp ? std::min(jpg_room(pw, ph), dstride) : 0;
+        const size_t room = jp ? std::min(jpg_room(pw, ph), sstride) : 0;
         if (room) {
             const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap(room, ph));
-            const int rj = jpg_encode_batch(dst, dstride, pw, ph, jp->quality, final_at[k0], dstride, room, m.d_scratch, l, res.data(), k1 - k0, s);
+            const int rj = jpg_encode_batch(dst, rstride, pw, ph, jp->quality, streams, sstride, room, m.d_scratch, l, res.data(), k1 - k0, s);
             if (rj) return rj;
         }
         for (int k = k0; k < k1; k++) {
@@ -199,12 +213,12 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
                 jp->sizes[k] = r.status ? hdr + served : (size_t)JPG_HEADER_BYTES + r.length;
                 if (!r.status) {
                     (void)mlvfs_amd_jpeg_header(pw, ph, jp->quality, file, JPG_HEADER_BYTES);
-                    MLV_HIP(hipMemcpyAsync(file + JPG_HEADER_BYTES, final_at[k0] + (size_t)(k - k0) * dstride, r.length, hipMemcpyDeviceToHost, s));
+                    MLV_HIP(hipMemcpyAsync(file + JPG_HEADER_BYTES, streams + (size_t)(k - k0) * sstride, r.length, hipMemcpyDeviceToHost, s));
                     continue;
                 }
             }
             (void)mlvfs_amd_rgb_header(pw, ph, file, hdr);
-            MLV_HIP(hipMemcpyAsync(file + hdr, dst + (size_t)(k - k0) * dstride, served, hipMemcpyDeviceToHost, s));
+            MLV_HIP(hipMemcpyAsync(file + hdr, dst + (size_t)(k - k0) * rstride, served, hipMemcpyDeviceToHost, s));
         }
     }
     MLV_HIP(hipStreamSynchronize(s));
@@ -214,7 +228,7 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
 // frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly;
 // rgb_gain != 0: served rendered (mlvfs_amd_mount_rgb), and no .dng header is written -- a file may be smaller than one
 int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results,
-                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr)
+                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr, bool full = false)
 {
     const mlvfs_amd_mount_opts_t &o = m.o;
     hipStream_t s = c->stream;
@@ -349,7 +363,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             for (int k = k0; k < k1; k++) final_at[k] = dst + (size_t)(k - k0) * dstride;
         }
     }
-    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp);
+    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp, full);
     if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll, sw, sh);
     const size_t served = (size_t)sw * sh * 2;
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
@@ -478,9 +492,9 @@ int mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int heigh
     return launch_bin2(d_frames, stride, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
 }
 
-// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb, with jpeg_quality != 0 mlvfs_amd_mount_jpeg
+// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb, with jpeg_quality != 0 mlvfs_amd_mount_jpeg; full: their full-size forms
 static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
-                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0)
+                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0, bool full = false)
 {
     if (!mount || !h_out || ((lossless || jpeg_quality) && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
     Mount &m = *(Mount *)mount;
@@ -510,8 +524,9 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     }
     if (rgb_gain) {
         if (m.proxy == 2) { set_error("mount: a handle that serves proxies does not render"); return MLVFS_AMD_ERR_ARG; }
-        int pw, ph;
-        if (!rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+        int pw = w, ph = h;
+        if (full && !rgb_full_geom(w, h)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+        if (!full && !rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         size = mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
         if (out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     }
@@ -525,18 +540,21 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
     scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
     if (lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
+    size_t full_bytes = full ? full_stride(w, h) * batch_frames : 0;                     // d_full: the batch's renderings ...
     if (jpeg_quality) {
-        int pw, ph;
-        (void)rgb_geom(w, h, &pw, &ph);
+        int pw = w, ph = h;
+        if (!full) (void)rgb_geom(w, h, &pw, &ph);
         if (pw > 65535 || ph > 65535) { set_error("mount: a JPEG file takes renderings of up to 65535 a side, not %dx%d", pw, ph); return MLVFS_AMD_ERR_ARG; }
-        if (const size_t room = std::min(jpg_room(pw, ph), dstride))
+        if (const size_t room = full ? jpg_room(pw, ph) : std::min(jpg_room(pw, ph), dstride))
             scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph)), batch_frames));
+        if (full) full_bytes += up256(jpg_room(pw, ph)) * batch_frames;                  // ... and their streams behind them
     }
     m.served = true;
     Calib cal;
     int rc = calib_on_device(m.dark, m.flat, c, w, h, bpp, 0, &cal);
     if (rc == MLVFS_AMD_OK) rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
     if (rc == MLVFS_AMD_OK && rgb_gain) rc = m.ensure_rgb(batch_frames);
+    if (rc == MLVFS_AMD_OK && full) rc = m.d_full.reserve(full_bytes);
     for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
         int n = std::min(batch_frames, count - f0);
         if (m.o.dual_iso == 2 && m.o.fix_bad_pixels) {
@@ -552,7 +570,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
             const Jpeg jp{ jpeg_quality ? sizes + f0 : nullptr, jpeg_quality ? flags + f0 : nullptr, jpeg_quality };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
-                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr);
+                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr, full);
         }
         f0 += n;
     }
@@ -578,6 +596,31 @@ int mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size_t 
     if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
     if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
     return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality);
+}
+
+int mlvfs_amd_mount_rgb_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int batch_frames, int io_threads,
+                             int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0, true);
+}
+
+int mlvfs_amd_mount_jpeg_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes,
+                              int *flags, int batch_frames, int io_threads, int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality, true);
+}
+
+size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index)
+{
+    if (!mount) { set_error("mount: null argument"); return 0; }
+    Mount &m = *(Mount *)mount;
+    frame_headers fh;
+    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
+    if (!rgb_full_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
+    return mlvfs_amd_rgb_header_size() + (size_t)3 * fh.rawi_hdr.xRes * fh.rawi_hdr.yRes;
 }
 
 size_t mlvfs_amd_mount_rgb_size(const void *mount, int index)
@@ -622,6 +665,37 @@ int mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int he
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
     return launch_render2(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
+}
+
+int mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph)
+{
+    if (!pw || !ph) { set_error("rgb_full_geom: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_full_geom(width, height)) { set_error("rgb_full_geom: %dx%d not supported (4x4 up to 2^25 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
+    *pw = width;
+    *ph = height;
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
+                          int nframes, void *stream)
+{
+    if (!d_frames || !d_out || !d_params) { set_error("render1: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("render1: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_full_geom(width, height)) { set_error("render1: %dx%d not supported (4x4 up to 2^25 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)3 * width * height;
+    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render1: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
+        set_error("render1: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
+    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
+    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
+    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render1: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    return launch_render1(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
 }
 
 int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,

@@ -71,6 +71,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_render2_dev", "mlvfs_amd_mount_rgb", "mlvfs_amd_mount_rgb_size",
     "mlvfs_amd_jpeg_header_size", "mlvfs_amd_jpeg_header", "mlvfs_amd_jpeg_qtables", "mlvfs_amd_jpeg_scratch_bytes",
     "mlvfs_amd_jpeg_encode_dev", "mlvfs_amd_mount_jpeg",
+    "mlvfs_amd_rgb_full_geom", "mlvfs_amd_render1_dev", "mlvfs_amd_mount_rgb_full", "mlvfs_amd_mount_jpeg_full", "mlvfs_amd_mount_rgb_full_size",
 ]
 
 
@@ -277,6 +278,11 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_jpeg_scratch_bytes", sz, [i, i, i])
     sig("mlvfs_amd_jpeg_encode_dev", i, [vp, sz, i, i, i, vp, sz, sz, vp, sz, vp, vp, i, vp])
     sig("mlvfs_amd_mount_jpeg", i, [vp, i, i, vp, sz, i, i, vp, vp, i, i, vp])
+    sig("mlvfs_amd_rgb_full_geom", i, [i, i, C.POINTER(i), C.POINTER(i)])
+    sig("mlvfs_amd_render1_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp])
+    sig("mlvfs_amd_mount_rgb_full", i, [vp, i, i, vp, sz, i, i, i, vp])
+    sig("mlvfs_amd_mount_jpeg_full", i, [vp, i, i, vp, sz, i, i, vp, vp, i, i, vp])
+    sig("mlvfs_amd_mount_rgb_full_size", sz, [vp, i])
     _lib = L
     return L
 

@@ -1,12 +1,13 @@
 """Write a clip as a sequence of rendered half-size sRGB TIFF frames: every frame as the mount serves it with these options, developed
 to 8-bit RGB at half size on the GPU (mlvfs_amd_mount_rgb; include/mlvfs_amd.h, "rendered half-size sRGB frames") -- or, with --jpeg,
-as baseline JPEG files encoded on the GPU (mlvfs_amd_mount_jpeg; "rendered frames as baseline JPEG files").
+as baseline JPEG files encoded on the GPU (mlvfs_amd_mount_jpeg; "rendered frames as baseline JPEG files").  --full renders at the size
+the clip was shot, demosaiced on the GPU (mlvfs_amd_mount_rgb_full, mlvfs_amd_mount_jpeg_full; "rendered full-size sRGB frames").
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--jpeg [QUALITY]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full] [--jpeg [QUALITY]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
-OUTDIR/<clip>_000000.tif ... hold (W // 2) x (H // 2) RGB pixels behind a 256-byte baseline TIFF header: any viewer opens them, any
+OUTDIR/<clip>_000000.tif ... hold (W // 2) x (H // 2) RGB pixels (W x H with --full) behind a 256-byte baseline TIFF header: any viewer opens them, any
 editing program takes the sequence as an offline proxy.  --gain is the only exposure control (the deflicker's bias is not applied: it
 only shapes the frame through the stages in front).  Frames are served in order, as one MLVFS process would serve them.  Nothing is
 overwritten: an existing file of the sequence ends the run before any frame is served.  --jpeg writes OUTDIR/<clip>_000000.jpg ...
@@ -30,6 +31,7 @@ def main() -> int:
     ap.add_argument("src")
     ap.add_argument("outdir")
     ap.add_argument("--gain", type=float, default=1.0, help="exposure factor, in steps of 1 / 256 (1 / 256 .. 255.996)")
+    ap.add_argument("--full", action="store_true", help="render at full size (a fixed 5x5 linear demosaic) instead of half size")
     ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
     ap.add_argument("--cs", type=int, default=0, choices=(0, 2, 3, 5), help="chroma smoothing")
     ap.add_argument("--bad-pix", type=int, default=0, choices=(0, 1, 2), help="bad-pixel repair (2: aggressive)")
@@ -76,10 +78,10 @@ def main() -> int:
                 for f0 in range(0, count, a.batch):
                     n = min(a.batch, count - f0)
                     if a.jpeg:
-                        files, flags = m.jpeg(a.first + f0, n, gain=a.gain, quality=a.jpeg, batch=a.batch, io_threads=a.io_threads)
+                        files, flags = m.jpeg(a.first + f0, n, gain=a.gain, quality=a.jpeg, batch=a.batch, io_threads=a.io_threads, full=a.full)
                         targets = [names[f0 + k] if flags[k] & 1 else jpgs[f0 + k] for k in range(n)]
                     else:
-                        files = [f.tobytes() for f in m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads)]
+                        files = [f.tobytes() for f in m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads, full=a.full)]
                         targets = names[f0:f0 + n]
                     for name, data in zip(targets, files):
                         with open(name, "xb") as out:                       # "x": never over a file that appeared meanwhile
