@@ -896,7 +896,8 @@ int    mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size
  *   3., 4.  the half-size definition's, with n = (m_R, m_G, m_B): t_i = clamp((sum_j K[i][j] n_j + 32768) >> 16, 0, 4095) in 64 bits,
  *      out_i = LUT[t_i]; bytes in R, G, B order, rows top down, no padding in a row.
  * The file: mlvfs_amd_rgb_header(W, H, ...) followed by 3 W H bytes -- the same 256-byte TIFF header at full size.
- * Not built: an adaptive demosaic, a crop to the active area, 16-bit output, highlight recovery, other CFA orders.               */
+ * Not built: an adaptive demosaic, a crop to the active area, 16-bit output, highlight recovery, other CFA orders, sizes between half
+ * and full size (smaller ones: "rendered frames at any smaller size" below).                                                      */
 /* *pw = width, *ph = height.  Host code.  MLVFS_AMD_ERR_ARG: a null pointer, a size below 4, 2^25 pixels or more. */
 int    mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph);
 /* mlvfs_amd_render2_dev at full size: nframes frames of width x height 16-bit pixels `stride` bytes apart -> their renderings, 3 W H
@@ -921,6 +922,67 @@ int    mlvfs_amd_mount_jpeg_full(void *mount, int first, int count, void *h_out,
                                  int *flags, int batch_frames, int io_threads, int *results);
 /* bytes of file `index` as mlvfs_amd_mount_rgb_full serves it; 0: no such frame, or one below 4x4 or of 2^25 pixels and more */
 size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index);
+
+/* -- rendered frames at any smaller size (csrc/k_scale.hip, csrc/mount.cpp) -------------------------------------------- */
+/* The rendering at any size up to half the frame's -- a daily, a thumbnail --, area-averaged in linear light between the half-size
+ * rendering's balance and its matrix.  The definition is this project's (the reference has no such stage), in integers only, so that
+ * it has a byte-exact oracle (mlvfs_amd/scale.py).
+ * Geometry.  W' = floor(W / 2), H' = floor(H / 2) as in the half-size rendering.  The caller names an output size ow x oh with
+ *   1 <= ow <= W', 1 <= oh <= H': the scaling never enlarges.  W' <= 65535, H' <= 65535 and W H < 2^27.  Anything else is
+ *   MLVFS_AMD_ERR_ARG.
+ * Source.  The three balanced superpixel channels n_j(Y, X), j = 0 .. 2, on the W' x H' grid: exactly steps 1 and 2 of the half-size
+ *   definition, 16 bits each.
+ * Weights.  In units of 1 / ow of a source pixel, source column X covers [X ow, (X + 1) ow) and output column u covers
+ *   [u W', (u + 1) W'):
+ *                   wx(u, X) = max(0, min((X + 1) ow, (u + 1) W') - max(X ow, u W'))
+ *   The weights of one output column sum to W'; the weights of one source column over all outputs sum to ow.  wy(v, Y) is defined
+ *   likewise with H' and oh.  The products stay below 2^32.
+ * Horizontal pass.
+ *                   hm_j(Y, u) = floor((sum_X wx(u, X) n_j(Y, X) + (W' >> 1)) / W')
+ *   The sum is at most 65535^2, so it fits in 32 bits unsigned with the rounding term.
+ * Vertical pass.
+ *                   m_j(v, u) = floor((sum_Y wy(v, Y) hm_j(Y, u) + (H' >> 1)) / H')              the bound is the same
+ * Steps 3 and 4 are the half-size definition's with n = m: matrix K, clamp to 12 bits, LUT; bytes in R, G, B order, rows top down,
+ *   no padding in a row.
+ * Consequences the tests use: ow = W', oh = H' gives the half-size rendering byte for byte; a constant frame renders to the same
+ *   constant at every size; two source values a and a + 1 averaged 1 : 1 give a + 1, because a half rounds up.
+ * The file: mlvfs_amd_rgb_header(ow, oh, ...) followed by 3 ow oh bytes, or the JPEG file of that rendering; the flag rule is the
+ *   half-size JPEG call's: bit 0 is set and the TIFF is served when 629 + stream > 256 + 3 ow oh.
+ * Not applied, as before: the deflicker's exposure bias, and any crop.
+ * Not built: sizes between half and full size (they would resample the demosaiced rendering), enlarging, other filters than the area
+ *   average, contact sheets.                                                                                                         */
+/* the largest size inside a box of box_w x box_h at the frame's aspect.  Host code.  With W', H' as above: box_w >= W' and
+ * box_h >= H' gives (W', H'); otherwise, if box_w H' <= box_h W' (in 64 bits), the width limits: ow = min(box_w, W'),
+ * oh = max(1, (2 ow H' + W') / (2 W')); otherwise the height limits: oh = min(box_h, H'), ow = max(1, (2 oh W' + H') / (2 H')).
+ * MLVFS_AMD_ERR_ARG, with the outputs untouched: a null pointer, a box side below 1, a frame that the scaled rendering does not take. */
+int    mlvfs_amd_rgb_fit(int width, int height, int box_w, int box_h, int *ow, int *oh);
+/* mlvfs_amd_render2_dev at ow x oh: nframes frames of width x height 16-bit pixels `stride` bytes apart -> their renderings, 3 ow oh
+ * bytes each, out_stride bytes apart, frame k with the 13 parameters d_params[13 k ..].  Bytes between renderings and behind 3 ow oh
+ * are not touched.  Not in place.  Asynchronous on `stream`; every check happens before any device work, and the checks are
+ * mlvfs_amd_render2_dev's plus the geometry above.  width a multiple of 16 with source base and stride 16-byte aligned takes the fast
+ * form (k_scale_x16: a workgroup walks the source rows of a band of output rows of one strip of columns, the balanced row in LDS;
+ * one pass, nothing in between in device memory); anything else one output pixel per lane with its footprint from global memory
+ * (k_scale_generic).                                                                                                               */
+int    mlvfs_amd_render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                   void *d_out, size_t out_stride, int nframes, void *stream);
+/* mlvfs_amd_mount_rgb and mlvfs_amd_mount_jpeg at ow x oh: the same stages, the same serve-order state and the same results[]; each
+ * file is the TIFF of 256 + 3 ow oh bytes or the JPEG file of that rendering.  Only 3 ow oh bytes, or the stream, cross the link.
+ * out_stride: anything from mlvfs_amd_mount_rgb_scaled_size up.  The renderings are developed into the frames' other slots, as the
+ * half-size ones are; a handle that never makes a scaled call serves what it served before, byte for byte and launch for launch.
+ * May be interleaved with the other serving calls on one handle.  MLVFS_AMD_ERR_ARG besides the half-size calls' (a handle with
+ * mlvfs_amd_mount_set_proxy(2) among them): a size outside the geometry above.                                                      */
+int    mlvfs_amd_mount_rgb_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
+                                  int batch_frames, int io_threads, int *results);
+int    mlvfs_amd_mount_jpeg_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, int ow,
+                                   int oh, size_t *sizes, int *flags, int batch_frames, int io_threads, int *results);
+/* bytes of file `index` as mlvfs_amd_mount_rgb_scaled serves it; 0: no such frame, or a size the frame does not allow */
+size_t mlvfs_amd_mount_rgb_scaled_size(const void *mount, int index, int ow, int oh);
+/* Test hooks, host only.  mlvfs_amd_test_scale_div: out[k] = floor(in[k] / d) by the multiplication k_scale_x16 divides with, d >= 1.
+ * mlvfs_amd_test_scale_plan: how a launch of nframes frames is divided among k_scale_x16's workgroups -- out = { width % 16 == 0, the
+ * superpixels a step stages, the most output columns of a strip, the output columns of a strip, the strips, the output rows of a
+ * band, the bands, the source rows a band covers at least }.                                                                       */
+int    mlvfs_amd_test_scale_div(uint32_t d, int n, const uint32_t *in, uint32_t *out);
+int    mlvfs_amd_test_scale_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8]);
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);

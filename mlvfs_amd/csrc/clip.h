@@ -271,6 +271,53 @@ int launch_render2(const void *d_frames, size_t stride, const int32_t *d_params,
 inline bool rgb_full_geom(int w, int h) { return w >= 4 && h >= 4 && (uint64_t)w * (uint64_t)h < (1u << 25); }
 int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
                    hipStream_t stream);
+// rendered frames at any smaller size (k_scale.hip): W' x H' of a w x h frame as rgb_geom gives them, false where a side of that grid
+// exceeds 65535 or ow x oh is not 1x1 up to W' x H'; the scaling pass, with the same parameters
+inline bool scale_geom(int w, int h, int ow, int oh, int *pw, int *ph)
+{
+    return rgb_geom(w, h, pw, ph) && *pw <= 65535 && *ph <= 65535 && ow >= 1 && ow <= *pw && oh >= 1 && oh <= *ph;
+}
+// floor(n / d) = (t + ((n - t) >> s1)) >> s2 with t = the high 32 bits of n m, for every n below 2^32 and any d >= 1: division by an
+// invariant with a 33-bit multiplier, rounded up (Granlund and Montgomery, PLDI 1994, figure 4.1), l = ceil(log2 d)
+struct ScDiv {
+    uint32_t m, s1, s2;
+};
+inline ScDiv scdiv_make(uint32_t d)
+{
+    uint32_t l = 0;
+    while ((1ull << l) < d) l++;
+    return { (uint32_t)((((1ull << l) - d) << 32) / d + 1), l ? 1u : 0u, l ? l - 1 : 0u };
+}
+inline uint32_t scdiv_host(uint32_t n, const ScDiv &d)
+{
+    const uint32_t t = (uint32_t)(((uint64_t)n * d.m) >> 32);
+    return (t + ((n - t) >> d.s1)) >> d.s2;
+}
+// how k_scale_x16 divides a frame among workgroups: strips of uo output columns, bands of bo output rows
+constexpr int SC_CHUNK = 1024;                        // superpixels of a source row a step stages: 256 lanes x 4
+constexpr int SC_STRIP = 1024;                        // most output columns of a strip: 256 lanes x 4
+constexpr int SC_BAND_ROWS = 8;                       // source rows a band covers at least: a seam costs one row read twice
+struct ScalePlan {
+    uint32_t uo, nstrips, bo, nbands;
+};
+inline ScalePlan scale_plan(int pw, int ph, int ow, int oh, int nframes)
+{
+    ScalePlan p;
+    // a strip's source columns, floor(us0 W' / ow) rounded down to 4 up to ceil(us1 W' / ow), fit one chunk where one column's do
+    p.uo = (uint32_t)((uint64_t)(SC_CHUNK - 8) * ow / pw);
+    p.uo = std::min(std::min(std::max(p.uo, 1u), (uint32_t)SC_STRIP), (uint32_t)ow);
+    p.nstrips = ((uint32_t)ow + p.uo - 1) / p.uo;
+    // as many workgroups in a launch as the machine holds at once (256 CUs x 4 of them at 4 waves per SIMD): a launch of a few more
+    // would run the last of them alone; and bands that are not all seam
+    const uint32_t budget = std::max(1024u / (uint32_t)std::max(nframes, 1), 32u);
+    const uint32_t nb = std::min(std::max(budget / p.nstrips, 1u), (uint32_t)oh);
+    const uint32_t least = (uint32_t)(((uint64_t)SC_BAND_ROWS * oh + ph - 1) / ph);
+    p.bo = std::min(std::max(((uint32_t)oh + nb - 1) / nb, least), (uint32_t)oh);
+    p.nbands = ((uint32_t)oh + p.bo - 1) / p.bo;
+    return p;
+}
+int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
+                         int oh, int nframes, hipStream_t stream);
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

@@ -32,6 +32,10 @@
 // mlvfs_amd_mount_rgb_full and mlvfs_amd_mount_jpeg_full are the same two routes at the frame's own size: each final frame is demosaiced
 // (k_demosaic.hip, the same parameters) into a buffer of its own, d_full -- 3 W H bytes do not fit the frame's other slot --, and a
 // JPEG call's streams lie in that buffer behind the batch's renderings.  A handle that never makes a full-size call never allocates it.
+//
+// mlvfs_amd_mount_rgb_scaled and mlvfs_amd_mount_jpeg_scaled are the half-size routes at ow x oh, at most the half size: each final frame
+// is balanced, area-averaged and developed in one pass (k_scale.hip, the same parameters) into its other slot, exactly where the
+// half-size rendering would lie, and only 3 ow oh bytes or the stream cross the link.  Nothing is allocated for it.
 #include "clip.h"
 #include "lj92enc.h"
 #include "jpeg.h"
@@ -148,6 +152,12 @@ int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstr
     return MLVFS_AMD_OK;
 }
 
+// which rendering a call serves: half size, the frame's own size, or ow x oh area-averaged from the half-size grid
+struct RgbMode {
+    enum Kind { HALF, FULL, SCALED } kind = HALF;
+    int ow = 0, oh = 0;
+};
+
 // where a JPEG call wants its answers (frame 0 of the batch first), and its quality
 struct Jpeg {
     size_t *sizes;
@@ -171,14 +181,20 @@ size_t full_stride(int w, int h) { return up256((size_t)3 * w * h); }
 // frames that lie on one side of the slot pair developed into the other side in one launch, then header + 3 W' H' bytes per file.
 // jp: as JPEG files -- the run's renderings encoded into the slots they were developed from, then header + stream per file, or the
 // TIFF where that is the smaller file.
-// full: at the frame's own size -- the renderings go into d_full, full_stride(w, h) apart, and their streams behind the batch's renderings
+// FULL: at the frame's own size -- the renderings go into d_full, full_stride(w, h) apart, and their streams behind the batch's renderings
+// SCALED: at ow x oh -- developed into the other slots as the half-size ones are, which are never smaller
 int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *h_out,
-              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp, bool full)
+              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp, const RgbMode &mode)
 {
     hipStream_t s = c->stream;
     uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
+    const bool full = mode.kind == RgbMode::FULL, scaled = mode.kind == RgbMode::SCALED;
     int pw = w, ph = h;
-    if (full ? !rgb_full_geom(w, h) : !rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering does not take frames of %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    if (full ? !rgb_full_geom(w, h) : scaled ? !scale_geom(w, h, mode.ow, mode.oh, &pw, &ph) : !rgb_geom(w, h, &pw, &ph)) {
+        set_error("mount: a rendering does not take frames of %dx%d", w, h);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (scaled) { pw = mode.ow; ph = mode.oh; }
     const size_t rstride = full ? full_stride(w, h) : dstride;                          // from one rendering to the next
     const size_t sstride = full ? up256(jpg_room(w, h)) : dstride;                      // from one stream to the next
     std::vector<int32_t> &params = m.rgb_host;
@@ -196,7 +212,8 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
         const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
         const int rc = full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s)
-                            : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s);
+                 : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s)
+                          : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s);
         if (rc) return rc;
         std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
         const size_t room = jp ? std::min(jpg_room(pw, ph), sstride) : 0;
@@ -228,7 +245,7 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
 // frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly;
 // rgb_gain != 0: served rendered (mlvfs_amd_mount_rgb), and no .dng header is written -- a file may be smaller than one
 int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results,
-                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr, bool full = false)
+                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr, const RgbMode &mode = RgbMode())
 {
     const mlvfs_amd_mount_opts_t &o = m.o;
     hipStream_t s = c->stream;
@@ -363,7 +380,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             for (int k = k0; k < k1; k++) final_at[k] = dst + (size_t)(k - k0) * dstride;
         }
     }
-    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp, full);
+    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp, mode);
     if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll, sw, sh);
     const size_t served = (size_t)sw * sh * 2;
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
@@ -492,10 +509,12 @@ int mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int heigh
     return launch_bin2(d_frames, stride, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
 }
 
-// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb, with jpeg_quality != 0 mlvfs_amd_mount_jpeg; full: their full-size forms
+// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb, with jpeg_quality != 0 mlvfs_amd_mount_jpeg; mode: their full-size and
+// scaled forms
 static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
-                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0, bool full = false)
+                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0, const RgbMode &mode = RgbMode())
 {
+    const bool full = mode.kind == RgbMode::FULL, scaled = mode.kind == RgbMode::SCALED;
     if (!mount || !h_out || ((lossless || jpeg_quality) && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
     Mount &m = *(Mount *)mount;
     if (count < 0) { set_error("mount: negative frame count"); return MLVFS_AMD_ERR_ARG; }
@@ -527,6 +546,11 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         int pw = w, ph = h;
         if (full && !rgb_full_geom(w, h)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         if (!full && !rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+        if (scaled) {
+            if (!scale_geom(w, h, mode.ow, mode.oh, &pw, &ph)) { set_error("mount: a scaled rendering of a %dx%d frame is 1x1 up to its half size, 65535 a side at most, not %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
+            pw = mode.ow;
+            ph = mode.oh;
+        }
         size = mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
         if (out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     }
@@ -544,6 +568,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     if (jpeg_quality) {
         int pw = w, ph = h;
         if (!full) (void)rgb_geom(w, h, &pw, &ph);
+        if (scaled) { pw = mode.ow; ph = mode.oh; }
         if (pw > 65535 || ph > 65535) { set_error("mount: a JPEG file takes renderings of up to 65535 a side, not %dx%d", pw, ph); return MLVFS_AMD_ERR_ARG; }
         if (const size_t room = full ? jpg_room(pw, ph) : std::min(jpg_room(pw, ph), dstride))
             scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph)), batch_frames));
@@ -570,7 +595,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
             const Jpeg jp{ jpeg_quality ? sizes + f0 : nullptr, jpeg_quality ? flags + f0 : nullptr, jpeg_quality };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
-                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr, full);
+                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr, mode);
         }
         f0 += n;
     }
@@ -602,7 +627,7 @@ int mlvfs_amd_mount_rgb_full(void *mount, int first, int count, void *h_out, siz
                              int *results)
 {
     if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0, true);
+    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0, RgbMode{ RgbMode::FULL });
 }
 
 int mlvfs_amd_mount_jpeg_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes,
@@ -610,7 +635,108 @@ int mlvfs_amd_mount_jpeg_full(void *mount, int first, int count, void *h_out, si
 {
     if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
     if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality, true);
+    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality, RgbMode{ RgbMode::FULL });
+}
+
+int mlvfs_amd_mount_rgb_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh, int batch_frames,
+                               int io_threads, int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    if (ow < 1 || oh < 1) { set_error("mount: a scaled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0,
+                       RgbMode{ RgbMode::SCALED, ow, oh });
+}
+
+int mlvfs_amd_mount_jpeg_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, int ow, int oh,
+                                size_t *sizes, int *flags, int batch_frames, int io_threads, int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
+    if (ow < 1 || oh < 1) { set_error("mount: a scaled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality,
+                       RgbMode{ RgbMode::SCALED, ow, oh });
+}
+
+size_t mlvfs_amd_mount_rgb_scaled_size(const void *mount, int index, int ow, int oh)
+{
+    if (!mount) { set_error("mount: null argument"); return 0; }
+    Mount &m = *(Mount *)mount;
+    frame_headers fh;
+    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
+    int pw, ph;
+    if (!scale_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh, &pw, &ph)) {
+        set_error("mount: a scaled rendering of a %dx%d frame is 1x1 up to its half size, 65535 a side at most, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh);
+        return 0;
+    }
+    return mlvfs_amd_rgb_header_size() + (size_t)3 * ow * oh;
+}
+
+int mlvfs_amd_rgb_fit(int width, int height, int box_w, int box_h, int *ow, int *oh)
+{
+    if (!ow || !oh) { set_error("rgb_fit: null argument"); return MLVFS_AMD_ERR_ARG; }
+    int pw, ph;
+    if (box_w < 1 || box_h < 1 || !scale_geom(width, height, 1, 1, &pw, &ph)) {
+        set_error("rgb_fit: a box of %dx%d, or a %dx%d frame that the scaled rendering does not take", box_w, box_h, width, height);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    int64_t fw = pw, fh = ph;
+    if (box_w < pw || box_h < ph) {
+        if ((int64_t)box_w * ph <= (int64_t)box_h * pw) {                // the width limits
+            fw = std::min(box_w, pw);
+            fh = std::max<int64_t>(1, (2 * fw * ph + pw) / (2 * (int64_t)pw));
+        } else {
+            fh = std::min(box_h, ph);
+            fw = std::max<int64_t>(1, (2 * fh * pw + ph) / (2 * (int64_t)ph));
+        }
+    }
+    *ow = (int)fw;
+    *oh = (int)fh;
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
+                                size_t out_stride, int nframes, void *stream)
+{
+    if (!d_frames || !d_out || !d_params) { set_error("render_scaled: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("render_scaled: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    int pw, ph;
+    if (!scale_geom(width, height, ow, oh, &pw, &ph)) {
+        set_error("render_scaled: %dx%d to %dx%d not supported (2x2 up to 2^27 pixels, 65535 a side at half size; 1x1 up to the half size)", width, height, ow, oh);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)3 * ow * oh;
+    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render_scaled: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
+        set_error("render_scaled: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
+    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
+    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
+    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render_scaled: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    return launch_render_scaled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c));
+}
+
+/* test hooks, host only: floor(in[k] / d) as k_scale_x16 computes it; how launch_render_scaled would divide a launch among workgroups */
+int mlvfs_amd_test_scale_div(uint32_t d, int n, const uint32_t *in, uint32_t *out)
+{
+    if (!d || n < 0 || !in || !out) { set_error("test_scale_div: bad argument"); return MLVFS_AMD_ERR_ARG; }
+    const ScDiv dv = scdiv_make(d);
+    for (int k = 0; k < n; k++) out[k] = scdiv_host(in[k], dv);
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_test_scale_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8])
+{
+    int pw, ph;
+    if (!out || nframes < 1 || !scale_geom(width, height, ow, oh, &pw, &ph)) { set_error("test_scale_plan: bad argument"); return MLVFS_AMD_ERR_ARG; }
+    const ScalePlan p = scale_plan(pw, ph, ow, oh, nframes);
+    const int32_t v[8] = { width % 16 == 0, SC_CHUNK, SC_STRIP, (int32_t)p.uo, (int32_t)p.nstrips, (int32_t)p.bo, (int32_t)p.nbands, SC_BAND_ROWS };
+    std::copy(v, v + 8, out);
+    return MLVFS_AMD_OK;
 }
 
 size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index)

@@ -72,6 +72,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_jpeg_header_size", "mlvfs_amd_jpeg_header", "mlvfs_amd_jpeg_qtables", "mlvfs_amd_jpeg_scratch_bytes",
     "mlvfs_amd_jpeg_encode_dev", "mlvfs_amd_mount_jpeg",
     "mlvfs_amd_rgb_full_geom", "mlvfs_amd_render1_dev", "mlvfs_amd_mount_rgb_full", "mlvfs_amd_mount_jpeg_full", "mlvfs_amd_mount_rgb_full_size",
+    "mlvfs_amd_rgb_fit", "mlvfs_amd_render_scaled_dev", "mlvfs_amd_mount_rgb_scaled", "mlvfs_amd_mount_jpeg_scaled",
+    "mlvfs_amd_mount_rgb_scaled_size", "mlvfs_amd_test_scale_div", "mlvfs_amd_test_scale_plan",
 ]
 
 
@@ -283,6 +285,13 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_mount_rgb_full", i, [vp, i, i, vp, sz, i, i, i, vp])
     sig("mlvfs_amd_mount_jpeg_full", i, [vp, i, i, vp, sz, i, i, vp, vp, i, i, vp])
     sig("mlvfs_amd_mount_rgb_full_size", sz, [vp, i])
+    sig("mlvfs_amd_rgb_fit", i, [i, i, i, i, C.POINTER(i), C.POINTER(i)])
+    sig("mlvfs_amd_render_scaled_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp])
+    sig("mlvfs_amd_mount_rgb_scaled", i, [vp, i, i, vp, sz, i, i, i, i, i, vp])
+    sig("mlvfs_amd_mount_jpeg_scaled", i, [vp, i, i, vp, sz, i, i, i, i, vp, vp, i, i, vp])
+    sig("mlvfs_amd_mount_rgb_scaled_size", sz, [vp, i, i, i])
+    sig("mlvfs_amd_test_scale_div", i, [C.c_uint32, i, vp, vp])
+    sig("mlvfs_amd_test_scale_plan", i, [i, i, i, i, i, vp])
     _lib = L
     return L
 

@@ -115,42 +115,65 @@ class Mount:
                                                       io_threads, lib.ptr(res)), "mount_dng_lossless")
         return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
 
-    def rgb_size(self, index: int = 0, full: bool = False) -> int:
-        """bytes of file `index` as rgb() serves it: the TIFF header + 3 * (W // 2) * (H // 2); full: + 3 * W * H"""
-        size = int((self.L.mlvfs_amd_mount_rgb_full_size if full else self.L.mlvfs_amd_mount_rgb_size)(self.h, index))
+    @staticmethod
+    def _size_arg(size, full: bool):
+        """(ow, oh) of a size= argument, or None"""
+        if size is None:
+            return None
+        if full:
+            raise ValueError("size= and full=True exclude each other")
+        ow, oh = size
+        return int(ow), int(oh)
+
+    def rgb_size(self, index: int = 0, full: bool = False, size=None) -> int:
+        """bytes of file `index` as rgb() serves it: the TIFF header + 3 * (W // 2) * (H // 2); full: + 3 * W * H; size=(ow, oh):
+        + 3 * ow * oh"""
+        size = self._size_arg(size, full)
+        if size is not None:
+            size = int(self.L.mlvfs_amd_mount_rgb_scaled_size(self.h, index, *size))
+        else:
+            size = int((self.L.mlvfs_amd_mount_rgb_full_size if full else self.L.mlvfs_amd_mount_rgb_size)(self.h, index))
         if not size:
             raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
         return size
 
     def rgb(self, first: int, count: int, gain: float = 1.0, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None,
-            full: bool = False) -> np.ndarray:
+            full: bool = False, size=None) -> np.ndarray:
         """Frames first .. first + count - 1 rendered to half-size 8-bit sRGB TIFF files: a (count, rgb_size) uint8 array.  gain: the
         exposure factor, in steps of 1 / 256 (gain_q8 = round(256 * gain), 1 .. 65535).  Not on a handle that serves proxies.
-        full: at the frame's own size, demosaiced on the GPU (mlvfs_amd/demosaic.py): a (count, rgb_size(full=True)) array."""
+        full: at the frame's own size, demosaiced on the GPU (mlvfs_amd/demosaic.py): a (count, rgb_size(full=True)) array.
+        size=(ow, oh): at any size up to half the frame's, area-averaged in linear light on the GPU (mlvfs_amd/scale.py): a
+        (count, rgb_size(size=size)) array.  Not together with full=True."""
+        size = self._size_arg(size, full)
         gain_q8 = int(round(256 * gain))
         if not 1 <= gain_q8 <= 65535:
             raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
-        out = np.zeros((count, self.rgb_size(first, full) if count else 0), np.uint8)
+        out = np.zeros((count, self.rgb_size(first, full, size) if count else 0), np.uint8)
         if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
                                         and results.size >= count):
             raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
         res = np.zeros(max(count, 1), np.int32) if results is None else results
+        if size is not None:
+            lib.check(self.L.mlvfs_amd_mount_rgb_scaled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1], batch,
+                                                        io_threads, lib.ptr(res)), "mount_rgb_scaled")
+            return out
         call = self.L.mlvfs_amd_mount_rgb_full if full else self.L.mlvfs_amd_mount_rgb
         lib.check(call(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, batch, io_threads, lib.ptr(res)),
                   "mount_rgb_full" if full else "mount_rgb")
         return out
 
     def jpeg(self, first: int, count: int, gain: float = 1.0, quality: int = 90, batch: int = 8, io_threads: int = 0,
-             results: np.ndarray | None = None, full: bool = False):
+             results: np.ndarray | None = None, full: bool = False, size=None):
         """The renderings of rgb() as baseline JPEG files of `quality` (1 .. 100), encoded on the GPU:
         -> (files, flags): files[k] the bytes of file k, flags[k] bit 0 set where the JPEG file would be larger than the TIFF and the
-        frame is served as rgb()'s TIFF, byte for byte.  full: the renderings of rgb(full=True)."""
+        frame is served as rgb()'s TIFF, byte for byte.  full: the renderings of rgb(full=True); size=(ow, oh): those of rgb(size=size)."""
+        size = self._size_arg(size, full)
         gain_q8 = int(round(256 * gain))
         if not 1 <= gain_q8 <= 65535:
             raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
         if not 1 <= quality <= 100:
             raise ValueError(f"quality {quality} outside 1 .. 100")
-        stride = self.rgb_size(first, full) if count else 0
+        stride = self.rgb_size(first, full, size) if count else 0
         out = np.zeros((count, stride), np.uint8)
         sizes = np.zeros(max(count, 1), np.uintp)
         flags = np.zeros(max(count, 1), np.int32)
@@ -158,9 +181,13 @@ class Mount:
                                         and results.size >= count):
             raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
         res = np.zeros(max(count, 1), np.int32) if results is None else results
-        call = self.L.mlvfs_amd_mount_jpeg_full if full else self.L.mlvfs_amd_mount_jpeg
-        lib.check(call(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, lib.ptr(sizes), lib.ptr(flags), batch, io_threads,
-                       lib.ptr(res)), "mount_jpeg_full" if full else "mount_jpeg")
+        if size is not None:
+            lib.check(self.L.mlvfs_amd_mount_jpeg_scaled(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, size[0], size[1],
+                                                         lib.ptr(sizes), lib.ptr(flags), batch, io_threads, lib.ptr(res)), "mount_jpeg_scaled")
+        else:
+            call = self.L.mlvfs_amd_mount_jpeg_full if full else self.L.mlvfs_amd_mount_jpeg
+            lib.check(call(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, lib.ptr(sizes), lib.ptr(flags), batch, io_threads,
+                           lib.ptr(res)), "mount_jpeg_full" if full else "mount_jpeg")
         return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
 
     def close(self) -> None:

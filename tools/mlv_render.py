@@ -1,13 +1,15 @@
 """Write a clip as a sequence of rendered half-size sRGB TIFF frames: every frame as the mount serves it with these options, developed
 to 8-bit RGB at half size on the GPU (mlvfs_amd_mount_rgb; include/mlvfs_amd.h, "rendered half-size sRGB frames") -- or, with --jpeg,
 as baseline JPEG files encoded on the GPU (mlvfs_amd_mount_jpeg; "rendered frames as baseline JPEG files").  --full renders at the size
-the clip was shot, demosaiced on the GPU (mlvfs_amd_mount_rgb_full, mlvfs_amd_mount_jpeg_full; "rendered full-size sRGB frames").
+the clip was shot, demosaiced on the GPU (mlvfs_amd_mount_rgb_full, mlvfs_amd_mount_jpeg_full; "rendered full-size sRGB frames");
+--size WxH at any size up to the half size, and --fit WxH at the largest such size inside that box at the frame's aspect, area-averaged in
+linear light on the GPU (mlvfs_amd_mount_rgb_scaled, mlvfs_amd_mount_jpeg_scaled; "rendered frames at any smaller size").
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full] [--jpeg [QUALITY]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--jpeg [QUALITY]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
-OUTDIR/<clip>_000000.tif ... hold (W // 2) x (H // 2) RGB pixels (W x H with --full) behind a 256-byte baseline TIFF header: any viewer opens them, any
+OUTDIR/<clip>_000000.tif ... hold (W // 2) x (H // 2) RGB pixels (W x H with --full, the size asked for with --size or --fit) behind a 256-byte baseline TIFF header: any viewer opens them, any
 editing program takes the sequence as an offline proxy.  --gain is the only exposure control (the deflicker's bias is not applied: it
 only shapes the frame through the stages in front).  Frames are served in order, as one MLVFS process would serve them.  Nothing is
 overwritten: an existing file of the sequence ends the run before any frame is served.  --jpeg writes OUTDIR/<clip>_000000.jpg ...
@@ -19,11 +21,18 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mlvfs_amd import mlvfile
+from mlvfs_amd import mlvfile, scale
 from mlvfs_amd.dark import Dark
 from mlvfs_amd.flat import Flat
 from mlvfs_amd.mount import Mount
 from mlvfs_amd.pipeline import MlvfsOptions
+
+
+def wxh(text: str) -> tuple[int, int]:
+    w, x, h = text.lower().partition("x")
+    if not (x and w.isdigit() and h.isdigit() and int(w) >= 1 and int(h) >= 1):
+        raise argparse.ArgumentTypeError(f"{text!r} is not WxH")
+    return int(w), int(h)
 
 
 def main() -> int:
@@ -31,7 +40,10 @@ def main() -> int:
     ap.add_argument("src")
     ap.add_argument("outdir")
     ap.add_argument("--gain", type=float, default=1.0, help="exposure factor, in steps of 1 / 256 (1 / 256 .. 255.996)")
-    ap.add_argument("--full", action="store_true", help="render at full size (a fixed 5x5 linear demosaic) instead of half size")
+    how = ap.add_mutually_exclusive_group()
+    how.add_argument("--full", action="store_true", help="render at full size (a fixed 5x5 linear demosaic) instead of half size")
+    how.add_argument("--size", type=wxh, metavar="WxH", help="render at W x H, at most half the frame's size a side (an area average in linear light)")
+    how.add_argument("--fit", type=wxh, metavar="WxH", help="render at the largest size inside a box of W x H at the frame's aspect")
     ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
     ap.add_argument("--cs", type=int, default=0, choices=(0, 2, 3, 5), help="chroma smoothing")
     ap.add_argument("--bad-pix", type=int, default=0, choices=(0, 1, 2), help="bad-pixel repair (2: aggressive)")
@@ -59,6 +71,17 @@ def main() -> int:
         count = a.count or r.frame_count - a.first
         if a.first < 0 or count <= 0 or a.first + count > r.frame_count:
             ap.error(f"frames {a.first} .. {a.first + count - 1} outside the clip ({r.frame_count} frames)")
+        size = a.size
+        if a.size or a.fit:
+            ok, fh = r.frame_headers(a.first)
+            if not ok:
+                ap.error(f"frame {a.first} has no usable headers")
+            try:
+                if a.fit:
+                    size = scale.fit(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *a.fit)
+                scale.geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *size)
+            except ValueError as e:
+                ap.error(str(e))
         names = [os.path.join(a.outdir, f"{stem}_{k:06d}.tif") for k in range(a.first, a.first + count)]
         jpgs = [n[:-4] + ".jpg" for n in names]
         taken = [n for n in names + (jpgs if a.jpeg else []) if os.path.exists(n)]
@@ -78,10 +101,12 @@ def main() -> int:
                 for f0 in range(0, count, a.batch):
                     n = min(a.batch, count - f0)
                     if a.jpeg:
-                        files, flags = m.jpeg(a.first + f0, n, gain=a.gain, quality=a.jpeg, batch=a.batch, io_threads=a.io_threads, full=a.full)
+                        files, flags = m.jpeg(a.first + f0, n, gain=a.gain, quality=a.jpeg, batch=a.batch, io_threads=a.io_threads, full=a.full,
+                                              size=size)
                         targets = [names[f0 + k] if flags[k] & 1 else jpgs[f0 + k] for k in range(n)]
                     else:
-                        files = [f.tobytes() for f in m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads, full=a.full)]
+                        files = [f.tobytes() for f in m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads, full=a.full,
+                                                            size=size)]
                         targets = names[f0:f0 + n]
                     for name, data in zip(targets, files):
                         with open(name, "xb") as out:                       # "x": never over a file that appeared meanwhile
