@@ -570,6 +570,7 @@ void mlvfs_amd_mount_close(void *mount);
  * A handle keeps the plane on the host and uploads it once per device, on that device's first use; afterwards it is read-only: it may
  * be shared between threads and mounts and must outlive the mounts that use it.                                                   */
 typedef struct mlvfs_amd_dark mlvfs_amd_dark_t;
+typedef struct mlvfs_amd_look mlvfs_amd_look_t;   /* "a look for the rendered frames" below */
 /* geom: width, height, bpp (1..16) and black (= black_d, 0..65535) are used.  Host code: needs no HIP device.  NULL on a null
  * argument, a non-positive size (or 2^27 pixels and more), bpp or black out of range (mlvfs_amd_last_error).                      */
 mlvfs_amd_dark_t *mlvfs_amd_dark_create(const mlvfs_amd_geom_t *geom, const uint16_t *h_plane);
@@ -983,6 +984,65 @@ size_t mlvfs_amd_mount_rgb_scaled_size(const void *mount, int index, int ow, int
  * band, the bands, the source rows a band covers at least }.                                                                       */
 int    mlvfs_amd_test_scale_div(uint32_t d, int n, const uint32_t *in, uint32_t *out);
 int    mlvfs_amd_test_scale_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8]);
+
+/* -- a look for the rendered frames (csrc/k_tone_dev.h, csrc/look.cpp, csrc/mount.cpp) --------------------------------- */
+/* Step 4 of the three renderings is one fixed sRGB curve.  A look replaces that step, and only that step, by a per-channel shaper table
+ * followed by a 3D table with tetrahedral interpolation -- "with our LUT on it": a .cube file from the grade, a log curve for the editor.
+ * The definition is this project's, in integers only, so that it has a byte-exact oracle (mlvfs_amd/look.py).
+ * A look is (S, N, T):
+ *   S   4096 unsigned 16-bit values, any values (it need not be monotone)
+ *   N   2 .. 65
+ *   T   N^3 entries of three unsigned 16-bit values (R, G, B out), indexed T[(b N + g) N + r]: red fastest, the order of a .cube file
+ * Steps 1 - 3 of the half-size, the full-size and the scaled definition are unchanged: three 12-bit linear-sRGB indices t_r, t_g, t_b per
+ * output pixel.  With a look, step 4 is
+ *   4a. u_c = S[t_c]                                               c = r, g, b
+ *   4b. p_c = u_c (N - 1)     i_c = p_c >> 16     f_c = p_c & 65535
+ *       u_c <= 65535, so i_c <= N - 2 always: the cell i .. i + 1 exists on every axis.
+ *   4c. tetrahedral interpolation.  Let a, b, c be the three axes ordered so that f_a >= f_b >= f_c.
+ *         V0 = T[i]     V1 = T[i + e_a]     V2 = T[i + e_a + e_b]     V3 = T[i + (1, 1, 1)]
+ *         w0 = 65536 - f_a     w1 = f_a - f_b     w2 = f_b - f_c     w3 = f_c                        they sum to 65536
+ *         v_k = (sum_j w_j V_j[k] + 32768) >> 16                                                     per output channel k
+ *       The sum with its rounding term is below 2^32 (65536 * 65535 + 32768): 32 bits unsigned suffice, and v_k <= 65535.  The order
+ *       among equal fractions does not matter -- the vertex two orders disagree on has weight 0 --, so there is no tie rule.
+ *   4d. out_k = floor((v_k + 128) / 257), 0 .. 255: v_k / 257 rounded, a half up.
+ * Bytes, rows and files are as before.
+ * Consequences the tests use: with S[t] = 257 LUT[t] and the identity table T[g] = floor((2 * 65535 g + (N - 1)) / (2 (N - 1))) per axis
+ *   the output is the plain rendering's, byte for byte, at every N (v differs from u by at most 1); a table of 65535 throughout behind
+ *   S = 65535 throughout gives v = 65535.
+ * Limits.  The table is fed from the 12-bit linear t, so a log shaper has coarse steps in the deepest shadows; for 8-bit output that is
+ *   accepted.  No floating point takes part: S and T arrive as integers (mlvfs_amd/look.py converts a .cube file's decimals in exact
+ *   rational arithmetic).
+ * Not built: a 16-bit t or 16-bit output, vendor log curves by name, 1D-only .cube files and domains other than 0 .. 1, more than one
+ *   look per launch, a table kept in LDS, a look on the .dng or proxy routes.                                                          */
+/* bytes of the device image of a look with a table of n a side: 8192 + 8 n^3; 0 for n outside 2 .. 65.  Host code. */
+size_t mlvfs_amd_look_image_size(int n);
+/* the device image into image[0 .. cap): S as it is, then the N^3 entries in the table's order as four uint16 each, R, G, B, 0 (with the
+ * image 16-byte aligned every entry is one aligned 64-bit load).  Host code.  MLVFS_AMD_ERR_ARG, with the image untouched: a null
+ * pointer, n outside 2 .. 65, cap below mlvfs_amd_look_image_size(n).                                                                  */
+int    mlvfs_amd_look_pack(const uint16_t shaper[4096], int n, const uint16_t *table, void *image, size_t cap);
+/* a look on the calling thread's device: packed, uploaded once, independent of any mount.  NULL (mlvfs_amd_last_error): a null pointer,
+ * n outside 2 .. 65, no device, no memory (nothing is held then).  Calls that run on another device refuse the handle.                 */
+mlvfs_amd_look_t *mlvfs_amd_look_create(const uint16_t shaper[4096], int n, const uint16_t *table);
+void   mlvfs_amd_look_destroy(mlvfs_amd_look_t *look);
+/* mlvfs_amd_render2_dev, mlvfs_amd_render1_dev and mlvfs_amd_render_scaled_dev with the look as step 4: the same arguments, the same
+ * checks before any device work (a null look is MLVFS_AMD_ERR_ARG too), the same rule for the fast form; the kernels are
+ * k_render2_look_x16 / _generic, k_render1_look_x16 / _generic and k_scale_look_x16 / _generic.  One look per launch.                  */
+int    mlvfs_amd_render2_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                                  size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream);
+int    mlvfs_amd_render1_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                                  size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream);
+int    mlvfs_amd_render_scaled_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                        void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream);
+/* step 4 alone: n triples t_r, t_g, t_b of 16-bit values at d_t (each is masked to 12 bits) -> n triples of bytes at d_out, device
+ * memory both.  Asynchronous on `stream`.  MLVFS_AMD_ERR_ARG: a null pointer, indices at an odd address, more than 2^40 triples, a
+ * destination that overlaps the indices.                                                                                               */
+int    mlvfs_amd_look_apply_dev(const mlvfs_amd_look_t *look, const uint16_t *d_t, size_t n, uint8_t *d_out, void *stream);
+/* every later mlvfs_amd_mount_rgb* and mlvfs_amd_mount_jpeg* call of the handle, at all three sizes, renders with the look; NULL
+ * clears.  Allowed at any time between serving calls: it touches no serve-order state, so unlike mlvfs_amd_mount_set_dark it is not
+ * refused after the first frame.  The .dng, lossless and proxy routes never see it; the JPEG routes encode the rendering where it lies,
+ * so flags, sizes and results[] keep their rules.  The look must outlive its use.  A handle that never sets a look serves byte for
+ * byte and launch for launch what it served before.  MLVFS_AMD_ERR_ARG: a null handle.                                                 */
+int    mlvfs_amd_mount_set_look(void *mount, const mlvfs_amd_look_t *look);
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);

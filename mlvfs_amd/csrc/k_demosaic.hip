@@ -22,17 +22,10 @@
 //   k_render1_generic : any W, H >= 4, 2-byte source alignment, 1-byte destination alignment; one lane = one output pixel, the 13
 //                       taps straight from global memory with the reflection applied to the indices.
 // Bytes between frames and behind 3 * W * H are never touched.
-#include "clip.h"
-
-#define MLV_SRGB_LUT12_ATTR __device__ __attribute__((aligned(16)))          // stage_lut reads it in 16-byte pieces
-#include "srgb_lut12.h"
+// k_render1_look_x16, k_render1_look_generic: the same bodies with a look as step 4 (k_tone_dev.h).
+#include "k_tone_dev.h"
 
 namespace mlv {
-
-struct RenderParams {          // mlvfs_amd_rgb_params' out[13]
-    int32_t black, A[3], K[9];
-};
-static_assert(sizeof(RenderParams) == 13 * sizeof(int32_t), "mlvfs_amd_rgb_params' layout");
 
 namespace {                    // this file's device helpers
 
@@ -41,26 +34,6 @@ constexpr int R1_RUN = 32;                            // rows a workgroup walks 
 constexpr int R1_RING = 16;                           // rows of the ring: the 12 a step has live (8 read, 4 written), as a power of two
 constexpr int R1_PITCH = 8 + R1_STRIP + 8;            // uint16 per ring row: the strip from [8] on, the halos at [6], [7] and behind it
 
-// 256 lanes x 16 bytes
-__device__ __forceinline__ void stage_lut(uint8_t *lut)
-{
-    ((uint4 *)lut)[threadIdx.x] = ((const uint4 *)kSrgbLut12)[threadIdx.x];
-    __syncthreads();
-}
-
-// what max(c - black, 0) needs for any int32 black with c < 2^16: c' = sat(c + lift - drop) in 32 bits unsigned
-struct Black {
-    uint32_t lift, drop;
-    __device__ explicit Black(int32_t black) : lift(black < 0 ? 0u - (uint32_t)black : 0u), drop(black > 0 ? (uint32_t)black : 0u) {}
-    __device__ __forceinline__ uint32_t operator()(uint32_t c) const { const uint32_t v = c + lift; return v > drop ? v - drop : 0u; }
-};
-
-__device__ __forceinline__ uint32_t balance(uint32_t c, int32_t A)
-{
-    const uint64_t v = ((uint64_t)c * (uint32_t)A + 2048u) >> 12;
-    return v < 65535u ? (uint32_t)v : 65535u;
-}
-
 // the index inside 0 .. n - 1 that stands for i in -2 .. n + 1 (n >= 3)
 __device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; }
 
@@ -68,39 +41,6 @@ __device__ __forceinline__ uint32_t sixteenths(int s)
 {
     const int m = (s + 8) >> 4;
     return (uint32_t)(m < 0 ? 0 : m > 65535 ? 65535 : m);
-}
-
-// step 3 in 64 bits, and in 32 where the frame's K allows it (fits32: every |K| < 2^15, every sum below 2^31)
-template <bool K32>
-__device__ __forceinline__ uint32_t tone_index(const int32_t *K, uint32_t n0, uint32_t n1, uint32_t n2)
-{
-    if constexpr (K32) {
-        const int acc = __mul24(K[0], (int)n0) + __mul24(K[1], (int)n1) + __mul24(K[2], (int)n2) + 32768;
-        const int t = acc >> 16;
-        return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
-    }
-    const int64_t acc = (int64_t)K[0] * (int32_t)n0 + (int64_t)K[1] * (int32_t)n1 + (int64_t)K[2] * (int32_t)n2 + 32768;
-    const int64_t t = acc >> 16;
-    return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
-}
-
-__device__ __forceinline__ bool fits32(const RenderParams &p)
-{
-    bool ok = true;
-    for (int i = 0; i < 3; i++) {
-        uint64_t sum = 0;
-        for (int j = 0; j < 3; j++) { const int64_t k = p.K[3 * i + j]; sum += (uint64_t)(k < 0 ? -k : k); }
-        ok = ok && sum * 65535u + 32768u < (1ull << 31);
-    }
-    return ok;
-}
-
-// the three bytes of one output pixel in bits 0 .. 23: R, G, B from the low byte up
-template <bool K32>
-__device__ __forceinline__ uint32_t tone(const RenderParams &p, const uint8_t *lut, uint32_t m0, uint32_t m1, uint32_t m2)
-{
-    const uint32_t r = lut[tone_index<K32>(p.K, m0, m1, m2)], g = lut[tone_index<K32>(p.K + 3, m0, m1, m2)], b = lut[tone_index<K32>(p.K + 6, m0, m1, m2)];
-    return r | (g << 8) | (b << 16);
 }
 
 // ---- k_render1_x16
@@ -145,9 +85,9 @@ __device__ __forceinline__ void unpack8(int *o, const uint4 &v)
 }
 
 // the 8 pixels of one lane: rows y - 2 .. y + 2 of the ring at m2, m1, c0, p1, p2 (each at the lane's first pixel).  ODD: the row's parity
-template <bool ODD, bool K32>
+template <bool ODD, bool K32, bool LOOK>
 __device__ __forceinline__ void develop8(const uint16_t *m2, const uint16_t *m1, const uint16_t *c0, const uint16_t *p1, const uint16_t *p2,
-                                         const RenderParams &p, const uint8_t *lut, uint2 *o)
+                                         const RenderParams &p, const uint8_t *lut, const LookArg &lk, uint2 *o)
 {
     int a[8], b[10], c[12], d[10], e[8];                      // a, e: columns 0 .. 7; b, d: -1 .. 8; c: -2 .. 9
     unpack8(a, *(const uint4 *)m2);
@@ -172,7 +112,7 @@ __device__ __forceinline__ void develop8(const uint16_t *m2, const uint16_t *m1,
             const uint32_t sh = sixteenths(10 * cc + 8 * h1 - 2 * d1 - 2 * h2 + v2), sv = sixteenths(10 * cc + 8 * v1 - 2 * d1 - 2 * v2 + h2);
             m0 = ODD ? sv : sh; mg = (uint32_t)cc; mb = ODD ? sh : sv;
         }
-        px[i] = tone<K32>(p, lut, m0, mg, mb);
+        px[i] = tone<K32, LOOK>(p, lut, lk, m0, mg, mb);
     }
     // four pixels of 24 bits are three dwords
     o[0] = make_uint2(px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16));
@@ -181,9 +121,9 @@ __device__ __forceinline__ void develop8(const uint16_t *m2, const uint16_t *m1,
 }
 
 // rows y0 .. y0 + R1_RUN - 1 of columns x0 .. x0 + sw - 1.  The ring's slot of row r: (r - y0 + 2) & (R1_RING - 1).
-template <bool K32>
+template <bool K32, bool LOOK>
 __device__ __forceinline__ void walk_strip(const uint16_t *src, uint8_t *dst, int w, int h, int x0, int sw, int y0, const RenderParams &p,
-                                           const Black &bl, uint16_t *ring, const uint8_t *lut)
+                                           const Black &bl, uint16_t *ring, const uint8_t *lut, const LookArg &lk)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rmax = min(h, y0 + R1_RUN) + 1;
@@ -205,49 +145,55 @@ __device__ __forceinline__ void walk_strip(const uint16_t *src, uint8_t *dst, in
             const uint16_t *c0 = at + (s & (R1_RING - 1)) * R1_PITCH;
             const uint16_t *p1 = at + ((s + 1) & (R1_RING - 1)) * R1_PITCH, *p2 = at + ((s + 2) & (R1_RING - 1)) * R1_PITCH;
             uint2 *o = (uint2 *)(dst + ((size_t)y * w + x0 + 8 * lane) * 3);
-            if (y & 1) develop8<true, K32>(m2, m1, c0, p1, p2, p, lut, o);
-            else develop8<false, K32>(m2, m1, c0, p1, p2, p, lut, o);
+            if (y & 1) develop8<true, K32, LOOK>(m2, m1, c0, p1, p2, p, lut, lk, o);
+            else develop8<false, K32, LOOK>(m2, m1, c0, p1, p2, p, lut, lk, o);
         }
         store_row(v, ring, (rn - y0 + 2) & (R1_RING - 1), rn, rmax, sw, lane, bl, p);
         __syncthreads();
     }
 }
 
-}  // namespace
-
 // grid.x = strips * runs, strips side by side first
-__global__ __launch_bounds__(256) void k_render1_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
-                                                     uint8_t *__restrict__ out, size_t out_stride, int w, int h, uint32_t strips)
+template <bool LOOK>
+__device__ __forceinline__ void render1_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                            uint8_t *__restrict__ out, size_t out_stride, int w, int h, uint32_t strips, uint8_t *lut, uint16_t *ring,
+                                            const LookArg &lk)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[4096];
-    __shared__ __attribute__((aligned(16))) uint16_t ring[R1_RING * R1_PITCH];
-    stage_lut(lut);
+    stage_lut<LOOK>(lut, lk);
     const RenderParams p = params[blockIdx.y];
     const Black bl(p.black);
     const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
     uint8_t *dst = out + (size_t)blockIdx.y * out_stride;
     const int run = blockIdx.x / strips, x0 = (int)(blockIdx.x - run * strips) * R1_STRIP, sw = min(w - x0, R1_STRIP);
-    if (fits32(p)) walk_strip<true>(src, dst, w, h, x0, sw, run * R1_RUN, p, bl, ring, lut);
-    else walk_strip<false>(src, dst, w, h, x0, sw, run * R1_RUN, p, bl, ring, lut);
+    if (fits32(p)) walk_strip<true, LOOK>(src, dst, w, h, x0, sw, run * R1_RUN, p, bl, ring, lut, lk);
+    else walk_strip<false, LOOK>(src, dst, w, h, x0, sw, run * R1_RUN, p, bl, ring, lut, lk);
 }
 
 // ---- k_render1_generic
 // npix = W * H output pixels per frame
-__global__ __launch_bounds__(256) void k_render1_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
-                                                         uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, int w, int h)
+template <bool LOOK>
+__device__ __forceinline__ void render1_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, int w, int h, uint8_t *lut,
+                                                const LookArg &lk, uint32_t first, uint32_t step, int32_t *site_a)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[4096];
-    stage_lut(lut);
+    stage_lut<LOOK>(lut, lk);
     const RenderParams p = params[blockIdx.y];
     const Black bl(p.black);
     const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
     uint8_t *dst = out + (size_t)blockIdx.y * out_stride;
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < npix; k += gridDim.x * blockDim.x) {
+    if constexpr (LOOK) {
+        if (threadIdx.x == 0) { site_a[0] = p.A[0]; site_a[1] = site_a[2] = p.A[1]; site_a[3] = p.A[2]; }
+        __syncthreads();
+    }
+    for (uint32_t k = first; k < npix; k += step) {
         const int y = (int)(k / (uint32_t)w), x = (int)(k - (uint32_t)y * (uint32_t)w);
-        // the balanced sample at (y + dy, x + dx): its site's colour is that of the reflected position too
-        auto tap = [&](int dy, int dx) -> int {
+        // the balanced sample at (y + dy, x + dx): its site's colour is that of the reflected position too.  (The compiler turns the
+        // three-way choice among p.A into a table per lane: in LDS in the plain kernel, as ever, but in scratch in the look kernel, which
+        // therefore reads A by site from a table of its own in LDS)
+        auto tap = [&](int dy, int dx) __attribute__((always_inline)) -> int {
             const int yy = reflect(y + dy, h), xx = reflect(x + dx, w);
             const int j = (yy & 1) + (xx & 1);
+            if constexpr (LOOK) return (int)balance(bl(src[(size_t)yy * w + xx]), site_a[2 * (yy & 1) + (xx & 1)]);
             return (int)balance(bl(src[(size_t)yy * w + xx]), j == 0 ? p.A[0] : j == 1 ? p.A[1] : p.A[2]);
         };
         const int c = tap(0, 0), h1 = tap(0, -1) + tap(0, 1), v1 = tap(-1, 0) + tap(1, 0), h2 = tap(0, -2) + tap(0, 2), v2 = tap(-2, 0) + tap(2, 0);
@@ -258,7 +204,7 @@ __global__ __launch_bounds__(256) void k_render1_generic(const uint8_t *__restri
         const uint32_t m0 = yo ? (xo ? sd : sv) : (xo ? sh : (uint32_t)c);
         const uint32_t m1 = yo == xo ? sg : (uint32_t)c;
         const uint32_t m2 = yo ? (xo ? (uint32_t)c : sh) : (xo ? sv : sd);
-        const uint32_t v = tone<false>(p, lut, m0, m1, m2);
+        const uint32_t v = tone<false, LOOK>(p, lut, lk, m0, m1, m2);
         uint8_t *o = dst + (size_t)k * 3;
         o[0] = (uint8_t)v;
         o[1] = (uint8_t)(v >> 8);
@@ -266,9 +212,42 @@ __global__ __launch_bounds__(256) void k_render1_generic(const uint8_t *__restri
     }
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_render1_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                     uint8_t *__restrict__ out, size_t out_stride, int w, int h, uint32_t strips)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<false>];
+    __shared__ __attribute__((aligned(16))) uint16_t ring[R1_RING * R1_PITCH];
+    render1_x16<false>(frames, stride, params, out, out_stride, w, h, strips, lut, ring, LookArg());
+}
+
+__global__ __launch_bounds__(256) void k_render1_look_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                          uint8_t *__restrict__ out, size_t out_stride, int w, int h, uint32_t strips, const LookArg lk)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<true>];
+    __shared__ __attribute__((aligned(16))) uint16_t ring[R1_RING * R1_PITCH];
+    render1_x16<true>(frames, stride, params, out, out_stride, w, h, strips, lut, ring, lk);
+}
+
+__global__ __launch_bounds__(256) void k_render1_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                         uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, int w, int h)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<false>];
+    render1_generic<false>(frames, stride, params, out, out_stride, npix, w, h, lut, LookArg(), MLV_GRID_STRIDE, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_render1_look_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                              uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, int w, int h, const LookArg lk)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<true>];
+    __shared__ int32_t site_a[4];                             // A of the four CFA sites, [2 * (y & 1) + (x & 1)]
+    render1_generic<true>(frames, stride, params, out, out_stride, npix, w, h, lut, lk, MLV_GRID_STRIDE, site_a);
+}
+
 // d_out apart from d_frames (the callers check); w, h >= 4, w * h < 2^25; d_params: 13 int32 per frame, 4-byte aligned
 int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
-                   hipStream_t stream)
+                   hipStream_t stream, const LookArg *lk)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
     if (!rgb_full_geom(w, h)) { set_error("a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
@@ -276,13 +255,22 @@ int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params,
                       (nframes == 1 || (stride % 16 == 0 && out_stride % 8 == 0));
     if (fast) {
         const uint32_t strips = ((uint32_t)w + R1_STRIP - 1) / R1_STRIP, runs = ((uint32_t)h + R1_RUN - 1) / R1_RUN;
-        hipLaunchKernelGGL(k_render1_x16, dim3(strips * runs, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                           (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips);
+        if (lk)
+            hipLaunchKernelGGL(k_render1_look_x16, dim3(strips * runs, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips, *lk);
+        else
+            hipLaunchKernelGGL(k_render1_x16, dim3(strips * runs, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips);
     } else {
         // the workgroups of a launch share the machine: each of them stages the table once, and the lanes stride over the rest
         const uint32_t npix = (uint32_t)w * (uint32_t)h, cap = 4 * std::max(2048u / (uint32_t)nframes, 64u);
-        hipLaunchKernelGGL(k_render1_generic, dim3(std::min<uint32_t>((npix + 255) / 256, cap), nframes), dim3(256), 0, stream,
-                           (const uint8_t *)d_frames, stride, (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, npix, w, h);
+        const dim3 grid(std::min<uint32_t>((npix + 255) / 256, cap), nframes);
+        if (lk)
+            hipLaunchKernelGGL(k_render1_look_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
+                               (uint8_t *)d_out, out_stride, npix, w, h, *lk);
+        else
+            hipLaunchKernelGGL(k_render1_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
+                               (uint8_t *)d_out, out_stride, npix, w, h);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

@@ -26,17 +26,10 @@
 //   k_scale_generic : any W, H >= 2, 2-byte source alignment; one lane = one output pixel, its footprint straight from global memory,
 //                     both divisions with the plain operator.
 // Bytes between renderings and behind 3 * ow * oh are never touched.
-#include "clip.h"
-
-#define MLV_SRGB_LUT12_ATTR __device__ __attribute__((aligned(16)))          // stage_lut reads it in 16-byte pieces
-#include "srgb_lut12.h"
+// k_scale_look_x16, k_scale_look_generic: the same bodies with a look as step 4 (k_tone_dev.h).
+#include "k_tone_dev.h"
 
 namespace mlv {
-
-struct RenderParams {          // mlvfs_amd_rgb_params' out[13]
-    int32_t black, A[3], K[9];
-};
-static_assert(sizeof(RenderParams) == 13 * sizeof(int32_t), "mlvfs_amd_rgb_params' layout");
 
 struct ScaleArgs {             // uniform in a launch
     uint32_t pw, ph, ow, oh;                          // W', H' and the output size
@@ -48,59 +41,6 @@ struct ScaleArgs {             // uniform in a launch
 namespace {                    // this file's device helpers
 
 constexpr int SC_NOUT = SC_STRIP / 256;               // output columns of a lane
-
-// 256 lanes x 16 bytes
-__device__ __forceinline__ void stage_lut(uint8_t *lut)
-{
-    ((uint4 *)lut)[threadIdx.x] = ((const uint4 *)kSrgbLut12)[threadIdx.x];
-    __syncthreads();
-}
-
-// what max(c - black, 0) needs for any int32 black with c < 2^16: c' = sat(c + lift - drop) in 32 bits unsigned
-struct Black {
-    uint32_t lift, drop;
-    __device__ explicit Black(int32_t black) : lift(black < 0 ? 0u - (uint32_t)black : 0u), drop(black > 0 ? (uint32_t)black : 0u) {}
-    __device__ __forceinline__ uint32_t operator()(uint32_t c) const { const uint32_t v = c + lift; return v > drop ? v - drop : 0u; }
-};
-
-__device__ __forceinline__ uint32_t balance(uint32_t c, int32_t A)
-{
-    const uint64_t v = ((uint64_t)c * (uint32_t)A + 2048u) >> 12;
-    return v < 65535u ? (uint32_t)v : 65535u;
-}
-
-// step 3 in 64 bits, and in 32 where the frame's K allows it (fits32: every |K| < 2^15, every sum below 2^31)
-template <bool K32>
-__device__ __forceinline__ uint32_t tone_index(const int32_t *K, uint32_t n0, uint32_t n1, uint32_t n2)
-{
-    if constexpr (K32) {
-        const int acc = __mul24(K[0], (int)n0) + __mul24(K[1], (int)n1) + __mul24(K[2], (int)n2) + 32768;
-        const int t = acc >> 16;
-        return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
-    }
-    const int64_t acc = (int64_t)K[0] * (int32_t)n0 + (int64_t)K[1] * (int32_t)n1 + (int64_t)K[2] * (int32_t)n2 + 32768;
-    const int64_t t = acc >> 16;
-    return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
-}
-
-__device__ __forceinline__ bool fits32(const RenderParams &p)
-{
-    bool ok = true;
-    for (int i = 0; i < 3; i++) {
-        uint64_t sum = 0;
-        for (int j = 0; j < 3; j++) { const int64_t k = p.K[3 * i + j]; sum += (uint64_t)(k < 0 ? -k : k); }
-        ok = ok && sum * 65535u + 32768u < (1ull << 31);
-    }
-    return ok;
-}
-
-// the three bytes of one output pixel in bits 0 .. 23: R, G, B from the low byte up
-template <bool K32>
-__device__ __forceinline__ uint32_t pixel(const RenderParams &p, const uint8_t *lut, uint32_t m0, uint32_t m1, uint32_t m2)
-{
-    const uint32_t r = lut[tone_index<K32>(p.K, m0, m1, m2)], g = lut[tone_index<K32>(p.K + 3, m0, m1, m2)], b = lut[tone_index<K32>(p.K + 6, m0, m1, m2)];
-    return r | (g << 8) | (b << 16);
-}
 
 // floor(n / d) for every n below 2^32 (scdiv_make, clip.h)
 __device__ __forceinline__ uint32_t sc_div(uint32_t n, const ScDiv &d)
@@ -117,14 +57,12 @@ __device__ __forceinline__ void balance3(uint32_t top, uint32_t bot, const Black
     n[2] = balance(bl(bot >> 16), p.A[2]);
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(256) void k_scale_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
-                                                   uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs a)
+template <bool LOOK>
+__device__ __forceinline__ void scale_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                          uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs &a, uint8_t *lut,
+                                          uint16_t (*planes)[3][SC_CHUNK], const LookArg &lk)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[4096];
-    __shared__ __attribute__((aligned(16))) uint16_t planes[2][3][SC_CHUNK];
-    stage_lut(lut);
+    stage_lut<LOOK>(lut, lk);
     const RenderParams p = params[blockIdx.y];
     const Black bl(p.black);
     const bool k32 = fits32(p);                                                              // uniform: the matrix in 24-bit multiplies
@@ -212,7 +150,7 @@ __global__ __launch_bounds__(256) void k_scale_x16(const uint8_t *__restrict__ f
                     if (last) {
                         const uint32_t m0 = sc_div(vacc[i][0] + (a.ph >> 1), a.dh), m1 = sc_div(vacc[i][1] + (a.ph >> 1), a.dh);
                         const uint32_t m2 = sc_div(vacc[i][2] + (a.ph >> 1), a.dh);
-                        const uint32_t px = k32 ? pixel<true>(p, lut, m0, m1, m2) : pixel<false>(p, lut, m0, m1, m2);
+                        const uint32_t px = k32 ? tone<true, LOOK>(p, lut, lk, m0, m1, m2) : tone<false, LOOK>(p, lut, lk, m0, m1, m2);
                         uint8_t *o = dst + ((size_t)v * a.ow + u) * 3;
                         o[0] = (uint8_t)px;
                         o[1] = (uint8_t)(px >> 8);
@@ -230,17 +168,17 @@ __global__ __launch_bounds__(256) void k_scale_x16(const uint8_t *__restrict__ f
 }
 
 // npix = ow * oh output pixels per frame
-__global__ __launch_bounds__(256) void k_scale_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
-                                                       uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw,
-                                                       uint32_t ph, uint32_t ow, uint32_t oh)
+template <bool LOOK>
+__device__ __forceinline__ void scale_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                              uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw, uint32_t ph,
+                                              uint32_t ow, uint32_t oh, uint8_t *lut, const LookArg &lk, uint32_t first, uint32_t step)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[4096];
-    stage_lut(lut);
+    stage_lut<LOOK>(lut, lk);
     const RenderParams p = params[blockIdx.y];
     const Black bl(p.black);
     const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
     uint8_t *dst = out + (size_t)blockIdx.y * out_stride;
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < npix; k += gridDim.x * blockDim.x) {
+    for (uint32_t k = first; k < npix; k += step) {
         const uint32_t v = k / ow, u = k - v * ow;
         const uint32_t ulo = u * pw, uhi = ulo + pw, vlo = v * ph, vhi = vlo + ph;
         const uint32_t xlo = ulo / ow, xhi = (uhi - 1u) / ow, ylo = vlo / oh, yhi = (vhi - 1u) / oh;
@@ -257,7 +195,7 @@ __global__ __launch_bounds__(256) void k_scale_generic(const uint8_t *__restrict
             }
             for (int j = 0; j < 3; j++) m[j] += wy * ((s[j] + (pw >> 1)) / pw);
         }
-        const uint32_t px = pixel<false>(p, lut, (m[0] + (ph >> 1)) / ph, (m[1] + (ph >> 1)) / ph, (m[2] + (ph >> 1)) / ph);
+        const uint32_t px = tone<false, LOOK>(p, lut, lk, (m[0] + (ph >> 1)) / ph, (m[1] + (ph >> 1)) / ph, (m[2] + (ph >> 1)) / ph);
         uint8_t *o = dst + (size_t)k * 3;
         o[0] = (uint8_t)px;
         o[1] = (uint8_t)(px >> 8);
@@ -265,9 +203,43 @@ __global__ __launch_bounds__(256) void k_scale_generic(const uint8_t *__restrict
     }
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_scale_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                   uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<false>];
+    __shared__ __attribute__((aligned(16))) uint16_t planes[2][3][SC_CHUNK];
+    scale_x16<false>(frames, stride, params, out, out_stride, a, lut, planes, LookArg());
+}
+
+__global__ __launch_bounds__(256) void k_scale_look_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                        uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs a, const LookArg lk)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<true>];
+    __shared__ __attribute__((aligned(16))) uint16_t planes[2][3][SC_CHUNK];
+    scale_x16<true>(frames, stride, params, out, out_stride, a, lut, planes, lk);
+}
+
+__global__ __launch_bounds__(256) void k_scale_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                       uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw,
+                                                       uint32_t ph, uint32_t ow, uint32_t oh)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<false>];
+    scale_generic<false>(frames, stride, params, out, out_stride, npix, w, pw, ph, ow, oh, lut, LookArg(), MLV_GRID_STRIDE);
+}
+
+__global__ __launch_bounds__(256) void k_scale_look_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                            uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw,
+                                                            uint32_t ph, uint32_t ow, uint32_t oh, const LookArg lk)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<true>];
+    scale_generic<true>(frames, stride, params, out, out_stride, npix, w, pw, ph, ow, oh, lut, lk, MLV_GRID_STRIDE);
+}
+
 // d_out apart from d_frames (the callers check); d_params: 13 int32 per frame, 4-byte aligned
 int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
-                         int oh, int nframes, hipStream_t stream)
+                         int oh, int nframes, hipStream_t stream, const LookArg *lk)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
     int pw, ph;
@@ -280,13 +252,21 @@ int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_p
         const ScalePlan pl = scale_plan(pw, ph, ow, oh, nframes);
         const ScaleArgs a{ (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, pl.uo, pl.nstrips, pl.bo, (uint32_t)w / 8,
                            scdiv_make((uint32_t)pw), scdiv_make((uint32_t)ph) };
-        hipLaunchKernelGGL(k_scale_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                           (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a);
+        if (lk)
+            hipLaunchKernelGGL(k_scale_look_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a, *lk);
+        else
+            hipLaunchKernelGGL(k_scale_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a);
     } else {
         const uint32_t npix = (uint32_t)ow * (uint32_t)oh, cap = std::max(2048u / (uint32_t)nframes, 64u);
-        hipLaunchKernelGGL(k_scale_generic, dim3(std::min<uint32_t>((npix + 255) / 256, 4 * cap), nframes), dim3(256), 0, stream,
-                           (const uint8_t *)d_frames, stride, (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, npix, (uint32_t)w,
-                           (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh);
+        const dim3 grid(std::min<uint32_t>((npix + 255) / 256, 4 * cap), nframes);
+        if (lk)
+            hipLaunchKernelGGL(k_scale_look_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
+                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, *lk);
+        else
+            hipLaunchKernelGGL(k_scale_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
+                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

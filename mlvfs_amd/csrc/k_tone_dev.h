@@ -1,0 +1,126 @@
+// k_tone_dev.h -- what the render kernels share (k_render.hip, k_demosaic.hip, k_scale.hip): the per-frame parameters, the black
+// level, the balance (step 2), the matrix (step 3) in its 64-bit and its 32-bit form, and step 4 once, as a template on LOOK:
+//     plain   out_i = LUT[t_i]                       the 4 KiB sRGB table in LDS, three byte reads
+//     look    4a .. 4d of include/mlvfs_amd.h, "a look for the rendered frames": the shaper S (8 KiB) in LDS INSTEAD of the sRGB table,
+//             the cube T in global memory as padded 8-byte entries (R | G << 16, B), one 64-bit gather per vertex, four per pixel.
+//             The tetrahedron is found without a branch: maximum, minimum and median of the three fractions by compares and selects;
+//             the step from V0 to V1 is the stride of the axis that holds the maximum (priorities r, g, b), the step from V3 back to V2
+//             that of the axis that holds the minimum (priorities b, g, r), so the two axes differ even where fractions are equal.
+//             i_c <= N - 2 for every 16-bit shaper value, so every gather lies inside the N^3 entries whatever S and t hold.
+// A kernel body is a template on LOOK; its plain __global__ form passes an empty LookArg that no instruction reads.
+#pragma once
+#include "clip.h"
+
+#define MLV_SRGB_LUT12_ATTR __device__ __attribute__((aligned(16)))          // stage_lut reads it in 16-byte pieces
+#include "srgb_lut12.h"
+
+// a grid-stride loop's first index and step, for the bodies that take them as arguments.  A kernel reads blockDim itself: read inside
+// a device function that is inlined into it, the compiler takes the general form of the work-group size (a load and a select) where
+// the kernel's own read folds to the launch's uniform size
+#define MLV_GRID_STRIDE blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x
+
+namespace mlv {
+
+struct RenderParams {          // mlvfs_amd_rgb_params' out[13]
+    int32_t black, A[3], K[9];
+};
+static_assert(sizeof(RenderParams) == 13 * sizeof(int32_t), "mlvfs_amd_rgb_params' layout");
+
+namespace {                    // every including file's own copy
+
+// bytes of the table a workgroup stages: the sRGB bytes, or the look's shaper
+template <bool LOOK> constexpr int TONE_LDS = LOOK ? LOOK_SHAPER_BYTES : 4096;
+
+// 256 lanes x 16 bytes, or x 32
+template <bool LOOK>
+__device__ __forceinline__ void stage_lut(uint8_t *lut, const LookArg &lk)
+{
+    if constexpr (LOOK) {
+        ((uint4 *)lut)[threadIdx.x] = ((const uint4 *)lk.image)[threadIdx.x];
+        ((uint4 *)lut)[threadIdx.x + 256] = ((const uint4 *)lk.image)[threadIdx.x + 256];
+    } else {
+        ((uint4 *)lut)[threadIdx.x] = ((const uint4 *)kSrgbLut12)[threadIdx.x];
+    }
+    __syncthreads();
+}
+
+// what max(c - black, 0) needs for any int32 black with c < 2^16: c' = sat(c + lift - drop) in 32 bits unsigned
+struct Black {
+    uint32_t lift, drop;
+    __device__ explicit Black(int32_t black) : lift(black < 0 ? 0u - (uint32_t)black : 0u), drop(black > 0 ? (uint32_t)black : 0u) {}
+    __device__ __forceinline__ uint32_t operator()(uint32_t c) const { const uint32_t v = c + lift; return v > drop ? v - drop : 0u; }
+};
+
+__device__ __forceinline__ uint32_t balance(uint32_t c, int32_t A)
+{
+    const uint64_t v = ((uint64_t)c * (uint32_t)A + 2048u) >> 12;
+    return v < 65535u ? (uint32_t)v : 65535u;
+}
+
+// step 3 in 64 bits, and in 32 where the frame's K allows it (fits32: every |K| < 2^15, every sum below 2^31)
+template <bool K32>
+__device__ __forceinline__ uint32_t tone_index(const int32_t *K, uint32_t n0, uint32_t n1, uint32_t n2)
+{
+    if constexpr (K32) {
+        const int acc = __mul24(K[0], (int)n0) + __mul24(K[1], (int)n1) + __mul24(K[2], (int)n2) + 32768;
+        const int t = acc >> 16;
+        return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
+    }
+    const int64_t acc = (int64_t)K[0] * (int32_t)n0 + (int64_t)K[1] * (int32_t)n1 + (int64_t)K[2] * (int32_t)n2 + 32768;
+    const int64_t t = acc >> 16;
+    return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
+}
+
+__device__ __forceinline__ bool fits32(const RenderParams &p)
+{
+    bool ok = true;
+    for (int i = 0; i < 3; i++) {
+        uint64_t sum = 0;
+        for (int j = 0; j < 3; j++) { const int64_t k = p.K[3 * i + j]; sum += (uint64_t)(k < 0 ? -k : k); }
+        ok = ok && sum * 65535u + 32768u < (1ull << 31);
+    }
+    return ok;
+}
+
+// 4c and 4d for one output channel: the four vertices' values of it, the weights; every factor is below 2^24 and the sum below 2^32
+__device__ __forceinline__ uint32_t look_channel(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3)
+{
+    const uint32_t v = (__umul24(w0, v0) + __umul24(w1, v1) + __umul24(w2, v2) + __umul24(w3, v3) + 32768u) >> 16;
+    return (v + 128u) / 257u;
+}
+
+// step 4 with a look: the three bytes of one output pixel in bits 0 .. 23, R, G, B from the low byte up, from its three 12-bit indices
+__device__ __forceinline__ uint32_t look_out(const uint8_t *lut, const LookArg &lk, uint32_t tr, uint32_t tg, uint32_t tb)
+{
+    const uint16_t *S = (const uint16_t *)lut;
+    const uint32_t N = lk.n, NN = N * N, n1 = N - 1u;
+    const uint32_t pr = S[tr] * n1, pg = S[tg] * n1, pb = S[tb] * n1;                    // 4a, 4b: below 2^16 * 64
+    const uint32_t ir = pr >> 16, ig = pg >> 16, ib = pb >> 16, fr = pr & 65535u, fg = pg & 65535u, fb = pb & 65535u;
+    const uint32_t fmax = max(fr, max(fg, fb)), fmin = min(fr, min(fg, fb)), fmed = max(min(fr, fg), min(max(fr, fg), fb));
+    const uint32_t up = fr == fmax ? 1u : fg == fmax ? N : NN;                            // V0 -> V1
+    const uint32_t down = fb == fmin ? NN : fg == fmin ? N : 1u;                          // V3 -> V2
+    const uint2 *T = (const uint2 *)(lk.image + LOOK_SHAPER_BYTES) + ((ib * N + ig) * N + ir);
+    const uint32_t far = NN + N + 1u;
+    const uint2 v0 = T[0], v1 = T[up], v2 = T[far - down], v3 = T[far];
+    const uint32_t w0 = 65536u - fmax, w1 = fmax - fmed, w2 = fmed - fmin, w3 = fmin;
+    const uint32_t r = look_channel(v0.x & 0xFFFFu, v1.x & 0xFFFFu, v2.x & 0xFFFFu, v3.x & 0xFFFFu, w0, w1, w2, w3);
+    const uint32_t g = look_channel(v0.x >> 16, v1.x >> 16, v2.x >> 16, v3.x >> 16, w0, w1, w2, w3);
+    const uint32_t b = look_channel(v0.y & 0xFFFFu, v1.y & 0xFFFFu, v2.y & 0xFFFFu, v3.y & 0xFFFFu, w0, w1, w2, w3);
+    return r | (g << 8) | (b << 16);
+}
+
+// steps 3 and 4 of one output pixel from its three 16-bit channels: bits 0 .. 23, R, G, B from the low byte up.  Plain: three byte reads
+// from the sRGB table, each behind its index (the order the plain kernels always had); look: the three indices, then look_out
+template <bool K32, bool LOOK>
+__device__ __forceinline__ uint32_t tone(const RenderParams &p, const uint8_t *lut, const LookArg &lk, uint32_t m0, uint32_t m1, uint32_t m2)
+{
+    if constexpr (!LOOK) {
+        const uint32_t r = lut[tone_index<K32>(p.K, m0, m1, m2)], g = lut[tone_index<K32>(p.K + 3, m0, m1, m2)], b = lut[tone_index<K32>(p.K + 6, m0, m1, m2)];
+        return r | (g << 8) | (b << 16);
+    } else {
+        return look_out(lut, lk, tone_index<K32>(p.K, m0, m1, m2), tone_index<K32>(p.K + 3, m0, m1, m2), tone_index<K32>(p.K + 6, m0, m1, m2));
+    }
+}
+
+}  // namespace
+}  // namespace mlv

@@ -58,6 +58,7 @@ struct Mount {
     int32_t coef[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     const mlvfs_amd_dark_t *dark = nullptr;  // stage 0 (mlvfs_amd_mount_set_dark): subtracted inside the reader's load
     const mlvfs_amd_flat_t *flat = nullptr;  // stage 0b (mlvfs_amd_mount_set_flat): the gain, in the same pass of the load
+    const mlvfs_amd_look_t *look = nullptr;  // step 4 of every rendering (mlvfs_amd_mount_set_look); no serve-order state: it may change between calls
     bool served = false;                     // a call has reached the device: the dark frame, the flat field and the proxy stay what they are
     int proxy = 1;                           // mlvfs_amd_mount_set_proxy: 2 = the served frames are binned to half size
     int device = -1;
@@ -179,6 +180,7 @@ size_t full_stride(int w, int h) { return up256((size_t)3 * w * h); }
 
 // The batch's final frames as rendered TIFF files: the parameters of every frame from its headers as they are now, one upload, runs of
 // frames that lie on one side of the slot pair developed into the other side in one launch, then header + 3 W' H' bytes per file.
+// With a look set (m.look) the launchers take the look kernels; nothing else differs.
 // jp: as JPEG files -- the run's renderings encoded into the slots they were developed from, then header + stream per file, or the
 // TIFF where that is the smaller file.
 // FULL: at the frame's own size -- the renderings go into d_full, full_stride(w, h) apart, and their streams behind the batch's renderings
@@ -204,6 +206,9 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         if (rc) return rc;
     }
     MLV_HIP(hipMemcpyAsync(m.d_rgb, params.data(), params.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LookArg look;
+    if (m.look) if (const int rc = look_on_device(m.look, c, &look)) return rc;
+    const LookArg *lk = m.look ? &look : nullptr;
     const size_t hdr = mlvfs_amd_rgb_header_size(), served = (size_t)3 * pw * ph;
     for (int k0 = 0, k1; k0 < n; k0 = k1) {
         const bool in_f = final_at[k0] == F + k0 * dstride;
@@ -211,9 +216,9 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         uint8_t *dst = full ? (uint8_t *)m.d_full + k0 * rstride : (in_f ? O : F) + k0 * dstride;
         uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
         const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
-        const int rc = full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s)
-                 : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s)
-                          : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s);
+        const int rc = full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk)
+                 : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s, lk)
+                          : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s, lk);
         if (rc) return rc;
         std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
         const size_t room = jp ? std::min(jpg_room(pw, ph), sstride) : 0;
@@ -461,6 +466,15 @@ int mlvfs_amd_mount_set_proxy(void *mount, int factor)
     }, [&](Mount &m) { m.proxy = factor; });
 }
 
+int mlvfs_amd_mount_set_look(void *mount, const mlvfs_amd_look_t *look)
+{
+    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    std::lock_guard<std::mutex> lk(m.mu);                // between serving calls: a call in flight holds the mutex
+    m.look = look;
+    return MLVFS_AMD_OK;
+}
+
 size_t mlvfs_amd_mount_dng_size(const void *mount, int index)
 {
     if (!mount) { set_error("mount: null argument"); return 0; }
@@ -694,10 +708,11 @@ int mlvfs_amd_rgb_fit(int width, int height, int box_w, int box_h, int *ow, int 
     return MLVFS_AMD_OK;
 }
 
-int mlvfs_amd_render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
-                                size_t out_stride, int nframes, void *stream)
+// mlvfs_amd_render_scaled_dev and mlvfs_amd_render_scaled_look_dev: the same checks before any device work
+static int render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
+                             size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream)
 {
-    if (!d_frames || !d_out || !d_params) { set_error("render_scaled: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!d_frames || !d_out || !d_params || (with_look && !look)) { set_error("render_scaled: null argument"); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0) { set_error("render_scaled: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     int pw, ph;
     if (!scale_geom(width, height, ow, oh, &pw, &ph)) {
@@ -717,7 +732,21 @@ int mlvfs_amd_render_scaled_dev(const void *d_frames, size_t stride, int width, 
     if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render_scaled: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
-    return launch_render_scaled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c));
+    LookArg lk;
+    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
+    return launch_render_scaled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c), with_look ? &lk : nullptr);
+}
+
+int mlvfs_amd_render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
+                                size_t out_stride, int nframes, void *stream)
+{
+    return render_scaled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream);
+}
+
+int mlvfs_amd_render_scaled_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                     void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
+{
+    return render_scaled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, look, true, stream);
 }
 
 /* test hooks, host only: floor(in[k] / d) as k_scale_x16 computes it; how launch_render_scaled would divide a launch among workgroups */
@@ -770,10 +799,11 @@ int mlvfs_amd_rgb_geom(int width, int height, int *pw, int *ph)
     return MLVFS_AMD_OK;
 }
 
-int mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                          int nframes, void *stream)
+// mlvfs_amd_render2_dev and mlvfs_amd_render2_look_dev: the same checks before any device work
+static int render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
+                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream)
 {
-    if (!d_frames || !d_out || !d_params) { set_error("render2: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!d_frames || !d_out || !d_params || (with_look && !look)) { set_error("render2: null argument"); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0) { set_error("render2: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     int pw, ph;
     if (!rgb_geom(width, height, &pw, &ph)) { set_error("render2: %dx%d not supported (2x2 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
@@ -790,7 +820,21 @@ int mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int he
     if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render2: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
-    return launch_render2(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
+    LookArg lk;
+    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
+    return launch_render2(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c), with_look ? &lk : nullptr);
+}
+
+int mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
+                          int nframes, void *stream)
+{
+    return render2_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream);
+}
+
+int mlvfs_amd_render2_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                               size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
+{
+    return render2_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, look, true, stream);
 }
 
 int mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph)
@@ -802,10 +846,11 @@ int mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph)
     return MLVFS_AMD_OK;
 }
 
-int mlvfs_amd_render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                          int nframes, void *stream)
+// mlvfs_amd_render1_dev and mlvfs_amd_render1_look_dev: the same checks before any device work
+static int render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
+                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream)
 {
-    if (!d_frames || !d_out || !d_params) { set_error("render1: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!d_frames || !d_out || !d_params || (with_look && !look)) { set_error("render1: null argument"); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0) { set_error("render1: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     if (!rgb_full_geom(width, height)) { set_error("render1: %dx%d not supported (4x4 up to 2^25 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
     const size_t img = (size_t)width * height * 2, pimg = (size_t)3 * width * height;
@@ -821,7 +866,21 @@ int mlvfs_amd_render1_dev(const void *d_frames, size_t stride, int width, int he
     if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render1: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
-    return launch_render1(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
+    LookArg lk;
+    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
+    return launch_render1(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c), with_look ? &lk : nullptr);
+}
+
+int mlvfs_amd_render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
+                          int nframes, void *stream)
+{
+    return render1_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream);
+}
+
+int mlvfs_amd_render1_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                               size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
+{
+    return render1_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, look, true, stream);
 }
 
 int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,

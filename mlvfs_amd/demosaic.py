@@ -84,10 +84,9 @@ def stages(frame, p, border: str = "reflect") -> dict:
     return dict(b=b, sums=sums, which=which, s=s, n=n, acc=acc, t=t, below=q < black, site=j)
 
 
-def render(frame, p, lut=None, border: str = "reflect") -> np.ndarray:
-    """(H, W, 3) uint8, R G B"""
-    lut = _render.srgb_lut12() if lut is None else np.asarray(lut, np.uint8)
-    return np.ascontiguousarray(lut[stages(frame, p, border)["t"]].transpose(1, 2, 0))
+def render(frame, p, lut=None, border: str = "reflect", look=None) -> np.ndarray:
+    """(H, W, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table"""
+    return _render.tone(stages(frame, p, border)["t"], lut, look)
 
 
 def split_file(file, w: int, h: int) -> np.ndarray:

@@ -74,6 +74,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_rgb_full_geom", "mlvfs_amd_render1_dev", "mlvfs_amd_mount_rgb_full", "mlvfs_amd_mount_jpeg_full", "mlvfs_amd_mount_rgb_full_size",
     "mlvfs_amd_rgb_fit", "mlvfs_amd_render_scaled_dev", "mlvfs_amd_mount_rgb_scaled", "mlvfs_amd_mount_jpeg_scaled",
     "mlvfs_amd_mount_rgb_scaled_size", "mlvfs_amd_test_scale_div", "mlvfs_amd_test_scale_plan",
+    "mlvfs_amd_look_image_size", "mlvfs_amd_look_pack", "mlvfs_amd_look_create", "mlvfs_amd_look_destroy", "mlvfs_amd_look_apply_dev",
+    "mlvfs_amd_render2_look_dev", "mlvfs_amd_render1_look_dev", "mlvfs_amd_render_scaled_look_dev", "mlvfs_amd_mount_set_look",
 ]
 
 
@@ -292,6 +294,15 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_mount_rgb_scaled_size", sz, [vp, i, i, i])
     sig("mlvfs_amd_test_scale_div", i, [C.c_uint32, i, vp, vp])
     sig("mlvfs_amd_test_scale_plan", i, [i, i, i, i, i, vp])
+    sig("mlvfs_amd_look_image_size", sz, [i])
+    sig("mlvfs_amd_look_pack", i, [vp, i, vp, vp, sz])
+    sig("mlvfs_amd_look_create", vp, [vp, i, vp])
+    sig("mlvfs_amd_look_destroy", None, [vp])
+    sig("mlvfs_amd_look_apply_dev", i, [vp, vp, sz, vp, vp])
+    sig("mlvfs_amd_render2_look_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_render1_look_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_render_scaled_look_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_mount_set_look", i, [vp, vp])
     _lib = L
     return L
 

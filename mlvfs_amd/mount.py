@@ -12,6 +12,9 @@
     m.rgb(0, 16, gain=1.0) serves the same frames developed to 8-bit sRGB at half size, as TIFF files any viewer opens
     (include/mlvfs_amd.h, "rendered half-size sRGB frames"; mlvfs_amd/render.py is the definition in numpy).
 
+    m.set_look(look.Look(S, n, T)) puts a shaper and a 3D table -- a .cube file -- in the place of the sRGB curve in every later rgb() and
+    jpeg() call (include/mlvfs_amd.h, "a look for the rendered frames"; mlvfs_amd/look.py is the definition in numpy).
+
     files, flags = m.jpeg(0, 16, gain=1.0, quality=90) serves the same renderings as baseline JPEG files encoded on the GPU, a tenth
     of the bytes (include/mlvfs_amd.h, "rendered frames as baseline JPEG files"; mlvfs_amd/jpeg.py is the definition in numpy).
 
@@ -50,7 +53,7 @@ class Mount:
         if not self.h:
             raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
         self.frame_count = self.L.mlvfs_amd_mlv_frame_count(handle)
-        self._dark = self._flat = None
+        self._dark = self._flat = self._look = None
         self.proxy = 1
         try:
             if dark is not None:
@@ -74,6 +77,12 @@ class Mount:
         stage (None clears); refused once a frame was served.  It must stay open while the Mount lives."""
         lib.check(self.L.mlvfs_amd_mount_set_flat(self.h, None if flat is None else flat.h), "mount_set_flat")
         self._flat = flat
+
+    def set_look(self, look) -> None:
+        """look: a mlvfs_amd.look.Look that every later rgb() and jpeg() call renders with, at all three sizes (None clears).  Allowed at
+        any time between calls; dng(), dng_lossless() and the proxies never see it.  It must stay open while it is set."""
+        lib.check(self.L.mlvfs_amd_mount_set_look(self.h, None if look is None else look.h), "mount_set_look")
+        self._look = look
 
     def set_proxy(self, factor: int) -> None:
         """factor 2: every frame is served binned to half size, 2 * (W // 4) x 2 * (H // 4), after all other stages; 1: off.  Refused

@@ -97,10 +97,18 @@ def stages(frame, p) -> dict:
     return dict(c=c, n=n, acc=acc, t=t, green_sum=g)
 
 
-def render(frame, p, lut=None) -> np.ndarray:
-    """(H // 2, W // 2, 3) uint8, R G B"""
+def tone(t, lut=None, look=None) -> np.ndarray:
+    """step 4 on t (3, H, W) -> (H, W, 3) uint8: the table, or with look = (S, n, T) or a look.Look the definition of mlvfs_amd/look.py"""
+    if look is not None:
+        from . import look as _look
+        return np.ascontiguousarray(_look.apply(t, *_look.as_tuple(look)).transpose(1, 2, 0))
     lut = srgb_lut12() if lut is None else np.asarray(lut, np.uint8)
-    return np.ascontiguousarray(lut[stages(frame, p)["t"]].transpose(1, 2, 0))
+    return np.ascontiguousarray(lut[t].transpose(1, 2, 0))
+
+
+def render(frame, p, lut=None, look=None) -> np.ndarray:
+    """(H // 2, W // 2, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table"""
+    return tone(stages(frame, p)["t"], lut, look)
 
 
 def tiff_header(pw: int, ph: int) -> bytes:

@@ -89,10 +89,9 @@ def stages(frame, p, ow: int, oh: int) -> dict:
     return dict(n=n, hm=hm, m=m, acc=acc, t=t)
 
 
-def render(frame, p, ow: int, oh: int, lut=None) -> np.ndarray:
-    """(oh, ow, 3) uint8, R G B"""
-    lut = _render.srgb_lut12() if lut is None else np.asarray(lut, np.uint8)
-    return np.ascontiguousarray(lut[stages(frame, p, ow, oh)["t"]].transpose(1, 2, 0))
+def render(frame, p, ow: int, oh: int, lut=None, look=None) -> np.ndarray:
+    """(oh, ow, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table"""
+    return _render.tone(stages(frame, p, ow, oh)["t"], lut, look)
 
 
 def split_file(file, ow: int, oh: int) -> np.ndarray:

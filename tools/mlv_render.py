@@ -4,8 +4,11 @@ as baseline JPEG files encoded on the GPU (mlvfs_amd_mount_jpeg; "rendered frame
 the clip was shot, demosaiced on the GPU (mlvfs_amd_mount_rgb_full, mlvfs_amd_mount_jpeg_full; "rendered full-size sRGB frames");
 --size WxH at any size up to the half size, and --fit WxH at the largest such size inside that box at the frame's aspect, area-averaged in
 linear light on the GPU (mlvfs_amd_mount_rgb_scaled, mlvfs_amd_mount_jpeg_scaled; "rendered frames at any smaller size").
+--lut FILE.cube puts a 3D table, interpolated tetrahedrally on the GPU, in the place of the sRGB curve of every one of these routes
+(mlvfs_amd_mount_set_look; "a look for the rendered frames"); --lut-input says what the table's input axis means: the sRGB value the
+plain rendering would write (the default), linear light, or log2:STOPS -- a pure log curve over that many stops below white.
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--jpeg [QUALITY]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--jpeg [QUALITY]] [--lut FILE.cube [--lut-input srgb|linear|log2:STOPS]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
@@ -21,7 +24,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mlvfs_amd import mlvfile, scale
+from mlvfs_amd import look, mlvfile, scale
 from mlvfs_amd.dark import Dark
 from mlvfs_amd.flat import Flat
 from mlvfs_amd.mount import Mount
@@ -45,6 +48,8 @@ def main() -> int:
     how.add_argument("--size", type=wxh, metavar="WxH", help="render at W x H, at most half the frame's size a side (an area average in linear light)")
     how.add_argument("--fit", type=wxh, metavar="WxH", help="render at the largest size inside a box of W x H at the frame's aspect")
     ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
+    ap.add_argument("--lut", metavar="FILE.cube", help="a 3D .cube table (domain 0 .. 1, up to 65 a side) applied to every rendering")
+    ap.add_argument("--lut-input", default="srgb", metavar="srgb|linear|log2:STOPS", help="what the table's input axis means (default srgb)")
     ap.add_argument("--cs", type=int, default=0, choices=(0, 2, 3, 5), help="chroma smoothing")
     ap.add_argument("--bad-pix", type=int, default=0, choices=(0, 1, 2), help="bad-pixel repair (2: aggressive)")
     ap.add_argument("--stripes", action="store_true", help="vertical stripes correction")
@@ -63,10 +68,16 @@ def main() -> int:
         ap.error(f"--gain {a.gain} outside 1 / 256 .. 65535 / 256")
     if a.jpeg and not 1 <= a.jpeg <= 100:
         ap.error(f"--jpeg {a.jpeg} outside 1 .. 100")
+    cube = None
+    if a.lut:
+        try:
+            cube = (look.shaper(a.lut_input),) + look.read_cube(a.lut)
+        except (OSError, ValueError) as e:
+            ap.error(f"--lut {a.lut}: {e}")
     stem = os.path.splitext(os.path.basename(a.src))[0]
     opt = MlvfsOptions(chroma_smooth=a.cs, fix_bad_pixels=a.bad_pix, fix_stripes=int(a.stripes), dual_iso=a.dual_iso,
                        hdr_interpolation_method=a.hdr_interp, fix_pattern_noise=int(a.pattern_noise))
-    dark = flat = None
+    dark = flat = lk = None
     with mlvfile.MlvReader(a.src) as r:
         count = a.count or r.frame_count - a.first
         if a.first < 0 or count <= 0 or a.first + count > r.frame_count:
@@ -96,8 +107,12 @@ def main() -> int:
             if a.flat:
                 with mlvfile.MlvReader(a.flat) as fr:
                     flat = Flat.from_clip(fr, dark=dark, batch=a.batch, io_threads=a.io_threads)
+            if cube:
+                lk = look.Look(*cube)
             t0, total = time.perf_counter(), 0
             with Mount(r, opt, deflicker=a.deflicker, basename="/" + os.path.basename(a.src), dark=dark, flat=flat) as m:
+                if lk is not None:
+                    m.set_look(lk)
                 for f0 in range(0, count, a.batch):
                     n = min(a.batch, count - f0)
                     if a.jpeg:
@@ -114,6 +129,8 @@ def main() -> int:
                         total += len(data)
             dt = time.perf_counter() - t0
         finally:
+            if lk is not None:
+                lk.close()
             if flat is not None:
                 flat.close()
             if dark is not None:
