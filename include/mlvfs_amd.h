@@ -571,6 +571,7 @@ void mlvfs_amd_mount_close(void *mount);
  * be shared between threads and mounts and must outlive the mounts that use it.                                                   */
 typedef struct mlvfs_amd_dark mlvfs_amd_dark_t;
 typedef struct mlvfs_amd_look mlvfs_amd_look_t;   /* "a look for the rendered frames" below */
+typedef struct mlvfs_amd_look16 mlvfs_amd_look16_t;   /* "rendered frames at 16 bits" below */
 /* geom: width, height, bpp (1..16) and black (= black_d, 0..65535) are used.  Host code: needs no HIP device.  NULL on a null
  * argument, a non-positive size (or 2^27 pixels and more), bpp or black out of range (mlvfs_amd_last_error).                      */
 mlvfs_amd_dark_t *mlvfs_amd_dark_create(const mlvfs_amd_geom_t *geom, const uint16_t *h_plane);
@@ -1010,9 +1011,9 @@ int    mlvfs_amd_test_scale_plan(int width, int height, int ow, int oh, int nfra
  *   the output is the plain rendering's, byte for byte, at every N (v differs from u by at most 1); a table of 65535 throughout behind
  *   S = 65535 throughout gives v = 65535.
  * Limits.  The table is fed from the 12-bit linear t, so a log shaper has coarse steps in the deepest shadows; for 8-bit output that is
- *   accepted.  No floating point takes part: S and T arrive as integers (mlvfs_amd/look.py converts a .cube file's decimals in exact
- *   rational arithmetic).
- * Not built: a 16-bit t or 16-bit output, vendor log curves by name, 1D-only .cube files and domains other than 0 .. 1, more than one
+ *   accepted, and "rendered frames at 16 bits" below feeds a deep look from a 16-bit t.  No floating point takes part: S and T arrive
+ *   as integers (mlvfs_amd/look.py converts a .cube file's decimals in exact rational arithmetic).
+ * Not built: vendor log curves by name, 1D-only .cube files and domains other than 0 .. 1, more than one
  *   look per launch, a table kept in LDS, a look on the .dng or proxy routes.                                                          */
 /* bytes of the device image of a look with a table of n a side: 8192 + 8 n^3; 0 for n outside 2 .. 65.  Host code. */
 size_t mlvfs_amd_look_image_size(int n);
@@ -1037,12 +1038,79 @@ int    mlvfs_amd_render_scaled_look_dev(const void *d_frames, size_t stride, int
  * memory both.  Asynchronous on `stream`.  MLVFS_AMD_ERR_ARG: a null pointer, indices at an odd address, more than 2^40 triples, a
  * destination that overlaps the indices.                                                                                               */
 int    mlvfs_amd_look_apply_dev(const mlvfs_amd_look_t *look, const uint16_t *d_t, size_t n, uint8_t *d_out, void *stream);
-/* every later mlvfs_amd_mount_rgb* and mlvfs_amd_mount_jpeg* call of the handle, at all three sizes, renders with the look; NULL
- * clears.  Allowed at any time between serving calls: it touches no serve-order state, so unlike mlvfs_amd_mount_set_dark it is not
- * refused after the first frame.  The .dng, lossless and proxy routes never see it; the JPEG routes encode the rendering where it lies,
- * so flags, sizes and results[] keep their rules.  The look must outlive its use.  A handle that never sets a look serves byte for
- * byte and launch for launch what it served before.  MLVFS_AMD_ERR_ARG: a null handle.                                                 */
+/* every later mlvfs_amd_mount_rgb* and mlvfs_amd_mount_jpeg* call of the handle, at all three sizes, renders with the look (the
+ * mlvfs_amd_mount_rgb16* calls below do not: they take a deep look of their own per call); NULL clears.  Allowed at any time between
+ * serving calls: it touches no serve-order state, so unlike mlvfs_amd_mount_set_dark it is not refused after the first frame.  The
+ * .dng, lossless and proxy routes never see it; the JPEG routes encode the rendering where it lies, so flags, sizes and results[] keep
+ * their rules.  The look must outlive its use.  A handle that never sets a look serves byte for byte and launch for launch what it
+ * served before.  MLVFS_AMD_ERR_ARG: a null handle.                                                                                    */
 int    mlvfs_amd_mount_set_look(void *mount, const mlvfs_amd_look_t *look);
+
+/* -- rendered frames at 16 bits (csrc/k_tone_dev.h, csrc/look.cpp, csrc/mount.cpp) ------------------------------------- */
+/* The routes above end in 8 bits and quantise linear light to a 12-bit index before the tone step: enough for a daily, not for a grade.
+ * The 16-bit routes serve the same three renderings as 16-bit TIFF files, toned from a 16-bit linear index.  Integers only; the numpy
+ * restatement is mlvfs_amd/look.py (stages16, apply16) with render.py, demosaic.py and scale.py (look16=).
+ * A deep look is (S16, N, T):
+ *   S16 65536 unsigned 16-bit values, any values (it need not be monotone)
+ *   N   0, or 2 .. 65; 0: there is no table
+ *   T   N^3 entries of three unsigned 16-bit values, T[(b N + g) N + r], exactly as in the 8-bit look; absent when N = 0
+ * Steps 1 and 2 of the half-size definition, the demosaic of the full-size definition and the two averaging passes of the scaled
+ * definition are unchanged: three 16-bit channels n_j (m_j) per output pixel and the 13 parameters of mlvfs_amd_rgb_params.  Then
+ *   3d. acc_i = sum_j K[i][j] n_j as before     t_i = clamp((acc_i + 2048) >> 12, 0, 65535)           (signed; an arithmetic shift)
+ *       K is Q12 and n has 16 bits: the same sum read four bits further down.  Where the matrix fits 32 bits for the 8-bit routes
+ *       (sum_j |K[i][j]| * 65535 + 32768 < 2^31) it does here, the rounding term being the smaller one.
+ *   4a. u_c = S16[t_c]
+ *   N = 0:  out_c = u_c
+ *   N >= 2: 4b and 4c of the 8-bit look, word for word: the cell, the fractions, the tetrahedron, v_k = (sum_j w_j V_j[k] + 32768) >> 16;
+ *           out_k = v_k.  There is no step 4d.
+ *   Samples: unsigned 16 bits, little-endian, R, G, B; a pixel is 6 bytes; rows top down, no padding.
+ * The file: the 256 bytes of mlvfs_amd_rgb_header with BitsPerSample 16 16 16 and StripByteCounts 6 pw ph -- the same tags, order and
+ * offsets otherwise --, then 6 pw ph bytes.
+ * Consequences the tests use: S16[t] = t and N = 0 give a file of t itself, a linear 16-bit TIFF; a constant S16 with N = 0 gives a
+ *   constant file; the scaled route at W' x H' gives the half-size route's bytes; t >> 4 is not always the 8-bit routes' t (the
+ *   roundings differ).
+ * The library ships no default curve (a 16-bit sRGB curve would be 128 KiB of constant, and the library computes nothing in floating
+ *   point): every 16-bit call takes a deep look; mlvfs_amd/look.py gives shaper16_linear, shaper16_srgb and shaper16_log2.
+ * Not built: 16-bit JPEG files, more than one deep look per launch, S16 or the table kept in LDS.                                       */
+/* bytes of the device image of a deep look: 131072 + 8 n^3; 0 for n outside {0, 2 .. 65}.  Host code. */
+size_t mlvfs_amd_look16_image_size(int n);
+/* the device image into image[0 .. cap): S16 as it is, then the N^3 entries as four uint16 each, R, G, B, 0 (16-byte aligned, every entry
+ * is one aligned 64-bit load; every gather is in bounds whatever S16 and a frame hold, t and u being at most 65535).  Host code.
+ * MLVFS_AMD_ERR_ARG, with the image untouched: a null shaper or image, a null table with n != 0, n outside {0, 2 .. 65}, a short cap. */
+int    mlvfs_amd_look16_pack(const uint16_t shaper[65536], int n, const uint16_t *table, void *image, size_t cap);
+/* a deep look on the calling thread's device, with the lifetime rules of mlvfs_amd_look_create.  table may be NULL only when n = 0.     */
+mlvfs_amd_look16_t *mlvfs_amd_look16_create(const uint16_t shaper[65536], int n, const uint16_t *table);
+void   mlvfs_amd_look16_destroy(mlvfs_amd_look16_t *look);
+/* the 256-byte header of a 16-bit file; everything else as mlvfs_amd_rgb_header.  Host code. */
+size_t mlvfs_amd_rgb16_header(int pw, int ph, uint8_t *out, size_t cap);
+/* mlvfs_amd_render2_look_dev, mlvfs_amd_render1_look_dev and mlvfs_amd_render_scaled_look_dev at 16 bits: the same arguments with a deep
+ * look, 6 bytes per pixel written, all checks before any device work, the stride checks with 6 bytes per pixel.  The fast forms
+ * (k_render2_deep_x16, k_render1_deep_x16) write a lane's 8 pixels as three 16-byte stores and need the destination base and stride
+ * 16-byte aligned -- a destination that is only 8-byte aligned takes the generic kernel --; k_scale_deep_x16 needs them 2-byte aligned;
+ * the rules for the source are the 8-bit calls'.  One deep look per launch.                                                            */
+int    mlvfs_amd_render2_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                                  size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream);
+int    mlvfs_amd_render1_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                                  size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream);
+int    mlvfs_amd_render_scaled_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                        void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream);
+/* step 4 alone: n triples of raw 16-bit t at d_t -> n triples of 16-bit samples at d_out, device memory both, 2-byte aligned.
+ * Asynchronous on `stream`.  MLVFS_AMD_ERR_ARG: a null pointer, an odd address, more than 2^40 triples, an overlap.                   */
+int    mlvfs_amd_look16_apply_dev(const mlvfs_amd_look16_t *look, const uint16_t *d_t, size_t n, uint16_t *d_out, void *stream);
+/* mlvfs_amd_mount_rgb, mlvfs_amd_mount_rgb_full and mlvfs_amd_mount_rgb_scaled as 16-bit TIFF files: the same arguments plus a non-null
+ * deep look, passed per call.  The same stages, the same serve-order state, the same results[]; they may be interleaved with every other
+ * serving call.  They refuse a handle with mlvfs_amd_mount_set_proxy(2) and ignore mlvfs_amd_mount_set_look, which belongs to the 8-bit
+ * routes.  A handle that never makes such a call serves byte for byte and launch for launch what it served before.                     */
+int    mlvfs_amd_mount_rgb16(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
+                             int batch_frames, int io_threads, int *results);
+int    mlvfs_amd_mount_rgb16_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8,
+                                  const mlvfs_amd_look16_t *look, int batch_frames, int io_threads, int *results);
+int    mlvfs_amd_mount_rgb16_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
+                                    const mlvfs_amd_look16_t *look, int batch_frames, int io_threads, int *results);
+/* bytes of file `index` as those calls serve it: 256 + 6 pw ph; 0 where the 8-bit size call gives 0 */
+size_t mlvfs_amd_mount_rgb16_size(const void *mount, int index);
+size_t mlvfs_amd_mount_rgb16_full_size(const void *mount, int index);
+size_t mlvfs_amd_mount_rgb16_scaled_size(const void *mount, int index, int ow, int oh);
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);

@@ -267,6 +267,9 @@ inline bool rgb_geom(int w, int h, int *pw, int *ph)
 // a look for the rendered frames (look.cpp; k_tone_dev.h): the device image mlvfs_amd_look_pack writes -- the shaper's 4096 uint16, then
 // n^3 entries of 8 bytes (R, G, B, 0 as uint16), red fastest -- as the look kernels take it; lk == nullptr below: the plain kernels
 constexpr size_t LOOK_SHAPER_BYTES = 4096 * sizeof(uint16_t);
+// a deep look for the 16-bit routes (look.cpp; k_tone_dev.h): S16's 65536 uint16, then the same entries; n == 0: no table.  The deep
+// kernels take it as a LookArg too (deep == true below, with lk set)
+constexpr size_t LOOK16_SHAPER_BYTES = 65536 * sizeof(uint16_t);
 struct LookArg {
     const uint8_t *image = nullptr;
     uint32_t n = 0;
@@ -275,13 +278,16 @@ struct LookArg {
 int look_on_device(const mlvfs_amd_look_t *look, ThreadCtx *c, LookArg *out);
 // n triples of 12-bit indices (masked) -> n triples of bytes through step 4 with the look (k_render.hip)
 int launch_look_apply(const LookArg &lk, const uint16_t *d_t, size_t n, uint8_t *d_out, hipStream_t stream);
+int look16_on_device(const mlvfs_amd_look16_t *look, ThreadCtx *c, LookArg *out);
+// n triples of 16-bit indices -> n triples of 16-bit samples through step 4 of the 16-bit routes (k_render.hip)
+int launch_look16_apply(const LookArg &lk, const uint16_t *d_t, size_t n, uint16_t *d_out, hipStream_t stream);
 int launch_render2(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
-                   hipStream_t stream, const LookArg *lk = nullptr);
+                   hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
 // rendered full-size sRGB frames (k_demosaic.hip): W x H pixels of a w x h frame, false below 4x4 and from 2^25 pixels on (what
 // mlvfs_amd_rgb_header writes); the demosaicing pass, with the same parameters
 inline bool rgb_full_geom(int w, int h) { return w >= 4 && h >= 4 && (uint64_t)w * (uint64_t)h < (1u << 25); }
 int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
-                   hipStream_t stream, const LookArg *lk = nullptr);
+                   hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
 // rendered frames at any smaller size (k_scale.hip): W' x H' of a w x h frame as rgb_geom gives them, false where a side of that grid
 // exceeds 65535 or ow x oh is not 1x1 up to W' x H'; the scaling pass, with the same parameters
 inline bool scale_geom(int w, int h, int ow, int oh, int *pw, int *ph)
@@ -328,7 +334,7 @@ inline ScalePlan scale_plan(int pw, int ph, int ow, int oh, int nframes)
     return p;
 }
 int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
-                         int oh, int nframes, hipStream_t stream, const LookArg *lk = nullptr);
+                         int oh, int nframes, hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

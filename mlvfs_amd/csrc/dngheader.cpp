@@ -573,17 +573,17 @@ extern "C" int mlvfs_amd_rgb_params(const struct frame_headers *fh, int gain_q8,
 }
 
 // Baseline little-endian TIFF: 12 entries behind the 8-byte header, BitsPerSample's three shorts at 158, "MLVFS" at 164, zeros up to
-// 256, where the one strip begins.
-extern "C" size_t mlvfs_amd_rgb_header(int pw, int ph, uint8_t *out, size_t cap)
+// 256, where the one strip begins.  bits: 8 or 16 per sample -- BitsPerSample and StripByteCounts follow it, nothing else does.
+static size_t rgb_header(const char *who, uint16_t bits_per_sample, int pw, int ph, uint8_t *out, size_t cap)
 {
-    if (!out) { mlv::set_error("rgb_header: null argument"); return 0; }
-    if (pw < 1 || ph < 1 || (uint64_t)pw * (uint64_t)ph >= (1u << 25)) { mlv::set_error("rgb_header: %dx%d pixels not supported", pw, ph); return 0; }
-    if (cap < kRgbHeaderBytes) { mlv::set_error("rgb_header: room for %zu bytes, the header takes %zu", cap, kRgbHeaderBytes); return 0; }
+    if (!out) { mlv::set_error("%s: null argument", who); return 0; }
+    if (pw < 1 || ph < 1 || (uint64_t)pw * (uint64_t)ph >= (1u << 25)) { mlv::set_error("%s: %dx%d pixels not supported", who, pw, ph); return 0; }
+    if (cap < kRgbHeaderBytes) { mlv::set_error("%s: room for %zu bytes, the header takes %zu", who, cap, kRgbHeaderBytes); return 0; }
     uint8_t b[kRgbHeaderBytes] = { 0 };
     const struct { uint16_t tag, type; uint32_t count, value; } e[12] = {
         { 256, LONG, 1, (uint32_t)pw }, { 257, LONG, 1, (uint32_t)ph }, { 258, SHORT, 3, 158 }, { 259, SHORT, 1, 1 }, { 262, SHORT, 1, 2 },
         { 273, LONG, 1, (uint32_t)kRgbHeaderBytes }, { 274, SHORT, 1, 1 }, { 277, SHORT, 1, 3 }, { 278, LONG, 1, (uint32_t)ph },
-        { 279, LONG, 1, 3u * (uint32_t)pw * (uint32_t)ph }, { 284, SHORT, 1, 1 }, { 305, ASCII, 6, 164 } };
+        { 279, LONG, 1, (3u * bits_per_sample / 8u) * (uint32_t)pw * (uint32_t)ph }, { 284, SHORT, 1, 1 }, { 305, ASCII, 6, 164 } };
     const uint16_t head[5] = { 0x4949, 42, 8, 0, 12 };
     memcpy(b, head, 10);
     for (int i = 0; i < 12; i++) {
@@ -593,9 +593,12 @@ extern "C" size_t mlvfs_amd_rgb_header(int pw, int ph, uint8_t *out, size_t cap)
         memcpy(at + 4, &e[i].count, 4);
         memcpy(at + 8, &e[i].value, 4);
     }
-    const uint16_t bits[3] = { 8, 8, 8 };
+    const uint16_t bits[3] = { bits_per_sample, bits_per_sample, bits_per_sample };
     memcpy(b + 158, bits, 6);
     memcpy(b + 164, "MLVFS", 6);
     memcpy(out, b, kRgbHeaderBytes);
     return kRgbHeaderBytes;
 }
+
+extern "C" size_t mlvfs_amd_rgb_header(int pw, int ph, uint8_t *out, size_t cap) { return rgb_header("rgb_header", 8, pw, ph, out, cap); }
+extern "C" size_t mlvfs_amd_rgb16_header(int pw, int ph, uint8_t *out, size_t cap) { return rgb_header("rgb16_header", 16, pw, ph, out, cap); }

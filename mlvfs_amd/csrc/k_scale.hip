@@ -27,6 +27,9 @@
 //                     both divisions with the plain operator.
 // Bytes between renderings and behind 3 * ow * oh are never touched.
 // k_scale_look_x16, k_scale_look_generic: the same bodies with a look as step 4 (k_tone_dev.h).
+// k_scale_deep_x16, k_scale_deep_generic: the same bodies with the 16-bit form of steps 3 and 4 and 6 bytes per pixel -- a lane of the
+// x16 form keeps its output columns and writes three 16-bit values where it wrote three bytes, so its destination base and stride are
+// 2-byte aligned (an odd one takes the generic kernel); no table in LDS.
 #include "k_tone_dev.h"
 
 namespace mlv {
@@ -57,12 +60,12 @@ __device__ __forceinline__ void balance3(uint32_t top, uint32_t bot, const Black
     n[2] = balance(bl(bot >> 16), p.A[2]);
 }
 
-template <bool LOOK>
+template <Tone TN>
 __device__ __forceinline__ void scale_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
                                           uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs &a, uint8_t *lut,
                                           uint16_t (*planes)[3][SC_CHUNK], const LookArg &lk)
 {
-    stage_lut<LOOK>(lut, lk);
+    stage_lut<TN>(lut, lk);
     const RenderParams p = params[blockIdx.y];
     const Black bl(p.black);
     const bool k32 = fits32(p);                                                              // uniform: the matrix in 24-bit multiplies
@@ -150,11 +153,15 @@ __device__ __forceinline__ void scale_x16(const uint8_t *__restrict__ frames, si
                     if (last) {
                         const uint32_t m0 = sc_div(vacc[i][0] + (a.ph >> 1), a.dh), m1 = sc_div(vacc[i][1] + (a.ph >> 1), a.dh);
                         const uint32_t m2 = sc_div(vacc[i][2] + (a.ph >> 1), a.dh);
-                        const uint32_t px = k32 ? tone<true, LOOK>(p, lut, lk, m0, m1, m2) : tone<false, LOOK>(p, lut, lk, m0, m1, m2);
-                        uint8_t *o = dst + ((size_t)v * a.ow + u) * 3;
-                        o[0] = (uint8_t)px;
-                        o[1] = (uint8_t)(px >> 8);
-                        o[2] = (uint8_t)(px >> 16);
+                        const auto px = k32 ? tone<true, TN>(p, lut, lk, m0, m1, m2) : tone<false, TN>(p, lut, lk, m0, m1, m2);
+                        if constexpr (TN == DEEP) {                                       // the same columns, stores twice as wide
+                            uint16_t *o = (uint16_t *)(dst + ((size_t)v * a.ow + u) * 6);
+                            o[0] = (uint16_t)px.x;
+                            o[1] = (uint16_t)(px.x >> 16);
+                            o[2] = (uint16_t)px.y;
+                        } else {
+                            put_pixel(dst + ((size_t)v * a.ow + u) * 3, px);
+                        }
 #pragma unroll
                         for (int j = 0; j < 3; j++) vacc[i][j] = __umul24(wnext, hm[j]);
                     }
@@ -168,12 +175,12 @@ __device__ __forceinline__ void scale_x16(const uint8_t *__restrict__ frames, si
 }
 
 // npix = ow * oh output pixels per frame
-template <bool LOOK>
+template <Tone TN>
 __device__ __forceinline__ void scale_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
                                               uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw, uint32_t ph,
                                               uint32_t ow, uint32_t oh, uint8_t *lut, const LookArg &lk, uint32_t first, uint32_t step)
 {
-    stage_lut<LOOK>(lut, lk);
+    stage_lut<TN>(lut, lk);
     const RenderParams p = params[blockIdx.y];
     const Black bl(p.black);
     const uint16_t *src = (const uint16_t *)(frames + (size_t)blockIdx.y * stride);
@@ -195,11 +202,8 @@ __device__ __forceinline__ void scale_generic(const uint8_t *__restrict__ frames
             }
             for (int j = 0; j < 3; j++) m[j] += wy * ((s[j] + (pw >> 1)) / pw);
         }
-        const uint32_t px = tone<false, LOOK>(p, lut, lk, (m[0] + (ph >> 1)) / ph, (m[1] + (ph >> 1)) / ph, (m[2] + (ph >> 1)) / ph);
-        uint8_t *o = dst + (size_t)k * 3;
-        o[0] = (uint8_t)px;
-        o[1] = (uint8_t)(px >> 8);
-        o[2] = (uint8_t)(px >> 16);
+        put_pixel(dst + (size_t)k * (TN == DEEP ? 6 : 3),
+                  tone<false, TN>(p, lut, lk, (m[0] + (ph >> 1)) / ph, (m[1] + (ph >> 1)) / ph, (m[2] + (ph >> 1)) / ph));
     }
 }
 
@@ -208,38 +212,53 @@ __device__ __forceinline__ void scale_generic(const uint8_t *__restrict__ frames
 __global__ __launch_bounds__(256) void k_scale_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
                                                    uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs a)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<false>];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<PLAIN>];
     __shared__ __attribute__((aligned(16))) uint16_t planes[2][3][SC_CHUNK];
-    scale_x16<false>(frames, stride, params, out, out_stride, a, lut, planes, LookArg());
+    scale_x16<PLAIN>(frames, stride, params, out, out_stride, a, lut, planes, LookArg());
 }
 
 __global__ __launch_bounds__(256) void k_scale_look_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
                                                         uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs a, const LookArg lk)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<true>];
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<LOOK>];
     __shared__ __attribute__((aligned(16))) uint16_t planes[2][3][SC_CHUNK];
-    scale_x16<true>(frames, stride, params, out, out_stride, a, lut, planes, lk);
+    scale_x16<LOOK>(frames, stride, params, out, out_stride, a, lut, planes, lk);
+}
+
+// the 16-bit form: the planes alone in LDS; the destination base and stride 2-byte aligned
+__global__ __launch_bounds__(256) void k_scale_deep_x16(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                        uint8_t *__restrict__ out, size_t out_stride, const ScaleArgs a, const LookArg lk)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t planes[2][3][SC_CHUNK];
+    scale_x16<DEEP>(frames, stride, params, out, out_stride, a, nullptr, planes, lk);
 }
 
 __global__ __launch_bounds__(256) void k_scale_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
                                                        uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw,
                                                        uint32_t ph, uint32_t ow, uint32_t oh)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<false>];
-    scale_generic<false>(frames, stride, params, out, out_stride, npix, w, pw, ph, ow, oh, lut, LookArg(), MLV_GRID_STRIDE);
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<PLAIN>];
+    scale_generic<PLAIN>(frames, stride, params, out, out_stride, npix, w, pw, ph, ow, oh, lut, LookArg(), MLV_GRID_STRIDE);
 }
 
 __global__ __launch_bounds__(256) void k_scale_look_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
                                                             uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw,
                                                             uint32_t ph, uint32_t ow, uint32_t oh, const LookArg lk)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<true>];
-    scale_generic<true>(frames, stride, params, out, out_stride, npix, w, pw, ph, ow, oh, lut, lk, MLV_GRID_STRIDE);
+    __shared__ __attribute__((aligned(16))) uint8_t lut[TONE_LDS<LOOK>];
+    scale_generic<LOOK>(frames, stride, params, out, out_stride, npix, w, pw, ph, ow, oh, lut, lk, MLV_GRID_STRIDE);
+}
+
+__global__ __launch_bounds__(256) void k_scale_deep_generic(const uint8_t *__restrict__ frames, size_t stride, const RenderParams *__restrict__ params,
+                                                            uint8_t *__restrict__ out, size_t out_stride, uint32_t npix, uint32_t w, uint32_t pw,
+                                                            uint32_t ph, uint32_t ow, uint32_t oh, const LookArg lk)
+{
+    scale_generic<DEEP>(frames, stride, params, out, out_stride, npix, w, pw, ph, ow, oh, nullptr, lk, MLV_GRID_STRIDE);
 }
 
 // d_out apart from d_frames (the callers check); d_params: 13 int32 per frame, 4-byte aligned
 int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
-                         int oh, int nframes, hipStream_t stream, const LookArg *lk)
+                         int oh, int nframes, hipStream_t stream, const LookArg *lk, bool deep)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
     int pw, ph;
@@ -247,12 +266,16 @@ int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_p
         set_error("a scaled rendering takes frames of 2x2 up to 2^27 pixels and 131071 a side and a size of 1x1 up to half the frame's, not %dx%d to %dx%d", w, h, ow, oh);
         return MLVFS_AMD_ERR_ARG;
     }
-    const bool fast = w % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && (nframes == 1 || stride % 16 == 0);
+    const bool fast = w % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && (nframes == 1 || stride % 16 == 0) &&
+                      (!deep || ((uintptr_t)d_out % 2 == 0 && (nframes == 1 || out_stride % 2 == 0)));      // 16-bit stores
     if (fast) {
         const ScalePlan pl = scale_plan(pw, ph, ow, oh, nframes);
         const ScaleArgs a{ (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, pl.uo, pl.nstrips, pl.bo, (uint32_t)w / 8,
                            scdiv_make((uint32_t)pw), scdiv_make((uint32_t)ph) };
-        if (lk)
+        if (deep)
+            hipLaunchKernelGGL(k_scale_deep_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
+                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a, *lk);
+        else if (lk)
             hipLaunchKernelGGL(k_scale_look_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
                                (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a, *lk);
         else
@@ -261,7 +284,10 @@ int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_p
     } else {
         const uint32_t npix = (uint32_t)ow * (uint32_t)oh, cap = std::max(2048u / (uint32_t)nframes, 64u);
         const dim3 grid(std::min<uint32_t>((npix + 255) / 256, 4 * cap), nframes);
-        if (lk)
+        if (deep)
+            hipLaunchKernelGGL(k_scale_deep_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
+                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, *lk);
+        else if (lk)
             hipLaunchKernelGGL(k_scale_look_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
                                (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, *lk);
         else

@@ -7,7 +7,11 @@
 //             the step from V0 to V1 is the stride of the axis that holds the maximum (priorities r, g, b), the step from V3 back to V2
 //             that of the axis that holds the minimum (priorities b, g, r), so the two axes differ even where fractions are equal.
 //             i_c <= N - 2 for every 16-bit shaper value, so every gather lies inside the N^3 entries whatever S and t hold.
-// A kernel body is a template on LOOK; its plain __global__ form passes an empty LookArg that no instruction reads.
+//     deep    the 16-bit routes (include/mlvfs_amd.h, "rendered frames at 16 bits"): step 3d's 16-bit index, 4a from the deep look's
+//             S16 -- 128 KiB, which stays in global memory and is read through the cache as 2-byte gathers: a deep kernel stages
+//             nothing in LDS and has no barrier at entry --, then 4b and 4c as above, or nothing where N = 0 (uniform in a launch);
+//             no 4d: three 16-bit samples per pixel.  t <= 65535 and u <= 65535, so every gather is in bounds whatever S16 holds.
+// A kernel body is a template on the form (Tone); its plain __global__ form passes an empty LookArg that no instruction reads.
 #pragma once
 #include "clip.h"
 
@@ -21,6 +25,8 @@
 
 namespace mlv {
 
+enum Tone { PLAIN, LOOK, DEEP };           // the three forms of steps 3 and 4
+
 struct RenderParams {          // mlvfs_amd_rgb_params' out[13]
     int32_t black, A[3], K[9];
 };
@@ -28,14 +34,16 @@ static_assert(sizeof(RenderParams) == 13 * sizeof(int32_t), "mlvfs_amd_rgb_param
 
 namespace {                    // every including file's own copy
 
-// bytes of the table a workgroup stages: the sRGB bytes, or the look's shaper
-template <bool LOOK> constexpr int TONE_LDS = LOOK ? LOOK_SHAPER_BYTES : 4096;
+// bytes of the table a workgroup stages: the sRGB bytes, or the look's shaper (a deep kernel stages none and declares none)
+template <Tone TN> constexpr int TONE_LDS = TN == LOOK ? LOOK_SHAPER_BYTES : 4096;
 
-// 256 lanes x 16 bytes, or x 32
-template <bool LOOK>
+// 256 lanes x 16 bytes, or x 32; deep: nothing, and no barrier
+template <Tone TN>
 __device__ __forceinline__ void stage_lut(uint8_t *lut, const LookArg &lk)
 {
-    if constexpr (LOOK) {
+    if constexpr (TN == DEEP) {
+        return;
+    } else if constexpr (TN == LOOK) {
         ((uint4 *)lut)[threadIdx.x] = ((const uint4 *)lk.image)[threadIdx.x];
         ((uint4 *)lut)[threadIdx.x + 256] = ((const uint4 *)lk.image)[threadIdx.x + 256];
     } else {
@@ -71,6 +79,20 @@ __device__ __forceinline__ uint32_t tone_index(const int32_t *K, uint32_t n0, ui
     return t < 0 ? 0u : t > 4095 ? 4095u : (uint32_t)t;
 }
 
+// step 3d: the same sum read four bits further down; the 32-bit form stays valid, its rounding term is the smaller one
+template <bool K32>
+__device__ __forceinline__ uint32_t tone_index16(const int32_t *K, uint32_t n0, uint32_t n1, uint32_t n2)
+{
+    if constexpr (K32) {
+        const int acc = __mul24(K[0], (int)n0) + __mul24(K[1], (int)n1) + __mul24(K[2], (int)n2) + 2048;
+        const int t = acc >> 12;
+        return t < 0 ? 0u : t > 65535 ? 65535u : (uint32_t)t;
+    }
+    const int64_t acc = (int64_t)K[0] * (int32_t)n0 + (int64_t)K[1] * (int32_t)n1 + (int64_t)K[2] * (int32_t)n2 + 2048;
+    const int64_t t = acc >> 12;
+    return t < 0 ? 0u : t > 65535 ? 65535u : (uint32_t)t;
+}
+
 __device__ __forceinline__ bool fits32(const RenderParams &p)
 {
     bool ok = true;
@@ -82,10 +104,16 @@ __device__ __forceinline__ bool fits32(const RenderParams &p)
     return ok;
 }
 
-// 4c and 4d for one output channel: the four vertices' values of it, the weights; every factor is below 2^24 and the sum below 2^32
+// 4c for one output channel: the four vertices' values of it, the weights; every factor is below 2^24 and the sum below 2^32
+__device__ __forceinline__ uint32_t look_vertex_sum(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3)
+{
+    return (__umul24(w0, v0) + __umul24(w1, v1) + __umul24(w2, v2) + __umul24(w3, v3) + 32768u) >> 16;
+}
+
+// 4c and 4d for one output channel
 __device__ __forceinline__ uint32_t look_channel(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3)
 {
-    const uint32_t v = (__umul24(w0, v0) + __umul24(w1, v1) + __umul24(w2, v2) + __umul24(w3, v3) + 32768u) >> 16;
+    const uint32_t v = look_vertex_sum(v0, v1, v2, v3, w0, w1, w2, w3);
     return (v + 128u) / 257u;
 }
 
@@ -109,17 +137,75 @@ __device__ __forceinline__ uint32_t look_out(const uint8_t *lut, const LookArg &
     return r | (g << 8) | (b << 16);
 }
 
-// steps 3 and 4 of one output pixel from its three 16-bit channels: bits 0 .. 23, R, G, B from the low byte up.  Plain: three byte reads
-// from the sRGB table, each behind its index (the order the plain kernels always had); look: the three indices, then look_out
-template <bool K32, bool LOOK>
-__device__ __forceinline__ uint32_t tone(const RenderParams &p, const uint8_t *lut, const LookArg &lk, uint32_t m0, uint32_t m1, uint32_t m2)
+// step 4 with a deep look: the three 16-bit samples of one output pixel, R | G << 16 and B, from its three 16-bit indices.  S16 is read
+// where it lies: 2-byte gathers through the cache.  lk.n == 0: no table (uniform in a launch).  4b and 4c are look_out's, stated once more
+// and not shared with it: look_out routed through a common function -- by reference, by value, with the loads inside or outside -- cost
+// k_render1_look_x16 18 VGPRs and an occupancy step
+__device__ __forceinline__ uint2 deep_out(const LookArg &lk, uint32_t tr, uint32_t tg, uint32_t tb)
 {
-    if constexpr (!LOOK) {
+    const uint16_t *S = (const uint16_t *)lk.image;
+    const uint32_t N = lk.n, NN = N * N, n1 = N - 1u;
+    const uint32_t ur = S[tr], ug = S[tg], ub = S[tb];                                    // 4a
+    if (!N) return make_uint2(ur | (ug << 16), ub);
+    const uint32_t pr = ur * n1, pg = ug * n1, pb = ub * n1;                              // 4b
+    const uint32_t ir = pr >> 16, ig = pg >> 16, ib = pb >> 16, fr = pr & 65535u, fg = pg & 65535u, fb = pb & 65535u;
+    const uint32_t fmax = max(fr, max(fg, fb)), fmin = min(fr, min(fg, fb)), fmed = max(min(fr, fg), min(max(fr, fg), fb));
+    const uint32_t up = fr == fmax ? 1u : fg == fmax ? N : NN;
+    const uint32_t down = fb == fmin ? NN : fg == fmin ? N : 1u;
+    const uint2 *T = (const uint2 *)(lk.image + LOOK16_SHAPER_BYTES) + ((ib * N + ig) * N + ir);
+    const uint32_t far = NN + N + 1u;
+    const uint2 v0 = T[0], v1 = T[up], v2 = T[far - down], v3 = T[far];
+    const uint32_t w0 = 65536u - fmax, w1 = fmax - fmed, w2 = fmed - fmin, w3 = fmin;
+    const uint32_t r = look_vertex_sum(v0.x & 0xFFFFu, v1.x & 0xFFFFu, v2.x & 0xFFFFu, v3.x & 0xFFFFu, w0, w1, w2, w3);
+    const uint32_t g = look_vertex_sum(v0.x >> 16, v1.x >> 16, v2.x >> 16, v3.x >> 16, w0, w1, w2, w3);
+    const uint32_t b = look_vertex_sum(v0.y & 0xFFFFu, v1.y & 0xFFFFu, v2.y & 0xFFFFu, v3.y & 0xFFFFu, w0, w1, w2, w3);
+    return make_uint2(r | (g << 16), b);
+}
+
+// steps 3 and 4 of one output pixel from its three 16-bit channels.  Plain and look: bits 0 .. 23, R, G, B from the low byte up -- plain
+// three byte reads from the sRGB table, each behind its index (the order the plain kernels always had); look the three indices, then
+// look_out.  Deep: deep_out's uint2
+template <bool K32, Tone TN>
+__device__ __forceinline__ auto tone(const RenderParams &p, const uint8_t *lut, const LookArg &lk, uint32_t m0, uint32_t m1, uint32_t m2)
+{
+    if constexpr (TN == PLAIN) {
         const uint32_t r = lut[tone_index<K32>(p.K, m0, m1, m2)], g = lut[tone_index<K32>(p.K + 3, m0, m1, m2)], b = lut[tone_index<K32>(p.K + 6, m0, m1, m2)];
         return r | (g << 8) | (b << 16);
-    } else {
+    } else if constexpr (TN == LOOK) {
         return look_out(lut, lk, tone_index<K32>(p.K, m0, m1, m2), tone_index<K32>(p.K + 3, m0, m1, m2), tone_index<K32>(p.K + 6, m0, m1, m2));
+    } else {
+        return deep_out(lk, tone_index16<K32>(p.K, m0, m1, m2), tone_index16<K32>(p.K + 3, m0, m1, m2), tone_index16<K32>(p.K + 6, m0, m1, m2));
     }
+}
+
+// ---- how a pixel is written.  8 bits: three bytes; 16 bits: six, little-endian
+__device__ __forceinline__ void put_pixel(uint8_t *o, uint32_t v)
+{
+    o[0] = (uint8_t)v;
+    o[1] = (uint8_t)(v >> 8);
+    o[2] = (uint8_t)(v >> 16);
+}
+// any alignment: the generic kernels
+__device__ __forceinline__ void put_pixel(uint8_t *o, uint2 v)
+{
+    o[0] = (uint8_t)v.x; o[1] = (uint8_t)(v.x >> 8); o[2] = (uint8_t)(v.x >> 16); o[3] = (uint8_t)(v.x >> 24);
+    o[4] = (uint8_t)v.y; o[5] = (uint8_t)(v.y >> 8);
+}
+// 8 pixels of a lane of an x16 kernel.  8 bits: 24 bytes as three 64-bit stores (four pixels of 24 bits are three dwords); 16 bits: 48
+// bytes as three aligned 128-bit stores (two pixels of 48 bits are three dwords), contiguous across the wave
+__device__ __forceinline__ void put_pixels8(void *at, uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t p4, uint32_t p5, uint32_t p6, uint32_t p7)
+{
+    uint2 *o = (uint2 *)at;
+    o[0] = make_uint2(p0 | (p1 << 24), (p1 >> 8) | (p2 << 16));
+    o[1] = make_uint2((p2 >> 16) | (p3 << 8), p4 | (p5 << 24));
+    o[2] = make_uint2((p5 >> 8) | (p6 << 16), (p6 >> 16) | (p7 << 8));
+}
+__device__ __forceinline__ void put_pixels8(void *at, uint2 p0, uint2 p1, uint2 p2, uint2 p3, uint2 p4, uint2 p5, uint2 p6, uint2 p7)
+{
+    uint4 *o = (uint4 *)at;
+    o[0] = make_uint4(p0.x, p0.y | (p1.x << 16), (p1.x >> 16) | (p1.y << 16), p2.x);
+    o[1] = make_uint4(p2.y | (p3.x << 16), (p3.x >> 16) | (p3.y << 16), p4.x, p4.y | (p5.x << 16));
+    o[2] = make_uint4((p5.x >> 16) | (p5.y << 16), p6.x, p6.y | (p7.x << 16), (p7.x >> 16) | (p7.y << 16));
 }
 
 }  // namespace

@@ -66,7 +66,8 @@ struct Mount {
     DevBuf d_bits;                           // the encoder's bit streams, sized from a batch's histograms
     DevBuf d_rgb;                            // mlvfs_amd_mount_rgb: 13 int32 parameters per frame of a batch
     std::vector<int32_t> rgb_host;           // what the upload reads: it outlives every call
-    DevBuf d_full;                           // the full-size calls: a batch's renderings of 3 W H bytes, a JPEG call's streams behind them
+    DevBuf d_full;                           // the full-size calls: a batch's renderings of 3 W H bytes (6 W H once a 16-bit call needs
+                                             // them), a JPEG call's streams behind them
 
     void release() { for (DevBuf *b : { &d_frames, &d_out, &d_scratch, &d_bits, &d_rgb, &d_full }) b->release(); }
 
@@ -175,8 +176,8 @@ size_t jpg_room(int pw, int ph)
     return tiff > (size_t)JPG_HEADER_BYTES + 2 ? tiff - JPG_HEADER_BYTES : 0;
 }
 
-// from one full-size rendering to the next in d_full
-size_t full_stride(int w, int h) { return up256((size_t)3 * w * h); }
+// from one full-size rendering to the next in d_full; bpx: 3 bytes per pixel, or 6 in a 16-bit call
+size_t full_stride(int w, int h, size_t bpx = 3) { return up256(bpx * w * h); }
 
 // The batch's final frames as rendered TIFF files: the parameters of every frame from its headers as they are now, one upload, runs of
 // frames that lie on one side of the slot pair developed into the other side in one launch, then header + 3 W' H' bytes per file.
@@ -185,8 +186,10 @@ size_t full_stride(int w, int h) { return up256((size_t)3 * w * h); }
 // TIFF where that is the smaller file.
 // FULL: at the frame's own size -- the renderings go into d_full, full_stride(w, h) apart, and their streams behind the batch's renderings
 // SCALED: at ow x oh -- developed into the other slots as the half-size ones are, which are never smaller
+// deep: as 16-bit TIFF files through the call's deep look (never m.look, never jp) -- 6 bytes per pixel; 6 W' H' <= 1.5 W H still fits the
+// other slot, and d_full has grown to 6 W H
 int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *h_out,
-              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp, const RgbMode &mode)
+              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp, const RgbMode &mode, const mlvfs_amd_look16_t *deep)
 {
     hipStream_t s = c->stream;
     uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
@@ -197,7 +200,8 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         return MLVFS_AMD_ERR_ARG;
     }
     if (scaled) { pw = mode.ow; ph = mode.oh; }
-    const size_t rstride = full ? full_stride(w, h) : dstride;                          // from one rendering to the next
+    const size_t bpx = deep ? 6 : 3;
+    const size_t rstride = full ? full_stride(w, h, bpx) : dstride;                     // from one rendering to the next
     const size_t sstride = full ? up256(jpg_room(w, h)) : dstride;                      // from one stream to the next
     std::vector<int32_t> &params = m.rgb_host;
     params.resize((size_t)n * 13);
@@ -207,18 +211,19 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
     }
     MLV_HIP(hipMemcpyAsync(m.d_rgb, params.data(), params.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     LookArg look;
-    if (m.look) if (const int rc = look_on_device(m.look, c, &look)) return rc;
-    const LookArg *lk = m.look ? &look : nullptr;
-    const size_t hdr = mlvfs_amd_rgb_header_size(), served = (size_t)3 * pw * ph;
+    if (deep) { if (const int rc = look16_on_device(deep, c, &look)) return rc; }
+    else if (m.look) if (const int rc = look_on_device(m.look, c, &look)) return rc;
+    const LookArg *lk = deep || m.look ? &look : nullptr;
+    const size_t hdr = mlvfs_amd_rgb_header_size(), served = bpx * pw * ph;
     for (int k0 = 0, k1; k0 < n; k0 = k1) {
         const bool in_f = final_at[k0] == F + k0 * dstride;
         for (k1 = k0 + 1; k1 < n && (final_at[k1] == F + k1 * dstride) == in_f; k1++) {}
         uint8_t *dst = full ? (uint8_t *)m.d_full + k0 * rstride : (in_f ? O : F) + k0 * dstride;
         uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
         const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
-        const int rc = full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk)
-                 : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s, lk)
-                          : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s, lk);
+        const int rc = full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
+                 : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
+                          : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s, lk, deep != nullptr);
         if (rc) return rc;
         std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
         const size_t room = jp ? std::min(jpg_room(pw, ph), sstride) : 0;
@@ -239,7 +244,8 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
                     continue;
                 }
             }
-            (void)mlvfs_amd_rgb_header(pw, ph, file, hdr);
+            if (deep) (void)mlvfs_amd_rgb16_header(pw, ph, file, hdr);
+            else (void)mlvfs_amd_rgb_header(pw, ph, file, hdr);
             MLV_HIP(hipMemcpyAsync(file + hdr, dst + (size_t)(k - k0) * rstride, served, hipMemcpyDeviceToHost, s));
         }
     }
@@ -250,7 +256,8 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
 // frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly;
 // rgb_gain != 0: served rendered (mlvfs_amd_mount_rgb), and no .dng header is written -- a file may be smaller than one
 int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results,
-                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr, const RgbMode &mode = RgbMode())
+                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr, const RgbMode &mode = RgbMode(),
+                const mlvfs_amd_look16_t *deep = nullptr)
 {
     const mlvfs_amd_mount_opts_t &o = m.o;
     hipStream_t s = c->stream;
@@ -385,7 +392,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             for (int k = k0; k < k1; k++) final_at[k] = dst + (size_t)(k - k0) * dstride;
         }
     }
-    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp, mode);
+    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp, mode, deep);
     if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll, sw, sh);
     const size_t served = (size_t)sw * sh * 2;
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
@@ -524,9 +531,10 @@ int mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int heigh
 }
 
 // every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb, with jpeg_quality != 0 mlvfs_amd_mount_jpeg; mode: their full-size and
-// scaled forms
+// scaled forms; deep: mlvfs_amd_mount_rgb16 and its forms, with the call's deep look
 static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
-                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0, const RgbMode &mode = RgbMode())
+                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0, const RgbMode &mode = RgbMode(),
+                       const mlvfs_amd_look16_t *deep = nullptr)
 {
     const bool full = mode.kind == RgbMode::FULL, scaled = mode.kind == RgbMode::SCALED;
     if (!mount || !h_out || ((lossless || jpeg_quality) && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
@@ -565,7 +573,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             pw = mode.ow;
             ph = mode.oh;
         }
-        size = mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
+        size = mlvfs_amd_rgb_header_size() + (size_t)(deep ? 6 : 3) * pw * ph;
         if (out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     }
     if (out_stride < size) { set_error("mount: out_stride %zu smaller than a .dng file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
@@ -578,7 +586,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
     scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
     if (lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
-    size_t full_bytes = full ? full_stride(w, h) * batch_frames : 0;                     // d_full: the batch's renderings ...
+    size_t full_bytes = full ? full_stride(w, h, deep ? 6 : 3) * batch_frames : 0;       // d_full: the batch's renderings ...
     if (jpeg_quality) {
         int pw = w, ph = h;
         if (!full) (void)rgb_geom(w, h, &pw, &ph);
@@ -609,7 +617,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
             const Jpeg jp{ jpeg_quality ? sizes + f0 : nullptr, jpeg_quality ? flags + f0 : nullptr, jpeg_quality };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
-                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr, mode);
+                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr, mode, deep);
         }
         f0 += n;
     }
@@ -671,6 +679,43 @@ int mlvfs_amd_mount_jpeg_scaled(void *mount, int first, int count, void *h_out, 
                        RgbMode{ RgbMode::SCALED, ow, oh });
 }
 
+// the three 16-bit TIFF calls: what the 8-bit ones check, and the call's deep look
+static int mount_rgb16(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
+                       int batch_frames, int io_threads, int *results, const RgbMode &mode)
+{
+    if (!look) { set_error("mount: null argument (a 16-bit rendering takes a deep look)"); return MLVFS_AMD_ERR_ARG; }
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    if (mode.kind == RgbMode::SCALED && (mode.ow < 1 || mode.oh < 1)) { set_error("mount: a scaled rendering of %dx%d", mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0, mode, look);
+}
+
+int mlvfs_amd_mount_rgb16(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
+                          int batch_frames, int io_threads, int *results)
+{
+    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode());
+}
+
+int mlvfs_amd_mount_rgb16_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
+                               int batch_frames, int io_threads, int *results)
+{
+    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode{ RgbMode::FULL });
+}
+
+int mlvfs_amd_mount_rgb16_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
+                                 const mlvfs_amd_look16_t *look, int batch_frames, int io_threads, int *results)
+{
+    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode{ RgbMode::SCALED, ow, oh });
+}
+
+// a 16-bit file has the 8-bit file's header and twice its pixel bytes
+static size_t twice_the_pixels(size_t size8) { return size8 ? 2 * size8 - mlvfs_amd_rgb_header_size() : 0; }
+size_t mlvfs_amd_mount_rgb16_size(const void *mount, int index) { return twice_the_pixels(mlvfs_amd_mount_rgb_size(mount, index)); }
+size_t mlvfs_amd_mount_rgb16_full_size(const void *mount, int index) { return twice_the_pixels(mlvfs_amd_mount_rgb_full_size(mount, index)); }
+size_t mlvfs_amd_mount_rgb16_scaled_size(const void *mount, int index, int ow, int oh)
+{
+    return twice_the_pixels(mlvfs_amd_mount_rgb_scaled_size(mount, index, ow, oh));
+}
+
 size_t mlvfs_amd_mount_rgb_scaled_size(const void *mount, int index, int ow, int oh)
 {
     if (!mount) { set_error("mount: null argument"); return 0; }
@@ -710,16 +755,17 @@ int mlvfs_amd_rgb_fit(int width, int height, int box_w, int box_h, int *ow, int 
 
 // mlvfs_amd_render_scaled_dev and mlvfs_amd_render_scaled_look_dev: the same checks before any device work
 static int render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
-                             size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream)
+                             size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream,
+                             const mlvfs_amd_look16_t *deep = nullptr, bool with_deep = false)
 {
-    if (!d_frames || !d_out || !d_params || (with_look && !look)) { set_error("render_scaled: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render_scaled: null argument"); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0) { set_error("render_scaled: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     int pw, ph;
     if (!scale_geom(width, height, ow, oh, &pw, &ph)) {
         set_error("render_scaled: %dx%d to %dx%d not supported (2x2 up to 2^27 pixels, 65535 a side at half size; 1x1 up to the half size)", width, height, ow, oh);
         return MLVFS_AMD_ERR_ARG;
     }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)3 * ow * oh;
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * ow * oh;
     if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render_scaled: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
     if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
         set_error("render_scaled: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
@@ -734,7 +780,9 @@ static int render_scaled_dev(const void *d_frames, size_t stride, int width, int
     if (!c) return MLVFS_AMD_ERR_HIP;
     LookArg lk;
     if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    return launch_render_scaled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c), with_look ? &lk : nullptr);
+    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
+    return launch_render_scaled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c),
+                                with_look || with_deep ? &lk : nullptr, with_deep);
 }
 
 int mlvfs_amd_render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
@@ -747,6 +795,12 @@ int mlvfs_amd_render_scaled_look_dev(const void *d_frames, size_t stride, int wi
                                      void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
 {
     return render_scaled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, look, true, stream);
+}
+
+int mlvfs_amd_render_scaled_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                     void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
+{
+    return render_scaled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream, look, true);
 }
 
 /* test hooks, host only: floor(in[k] / d) as k_scale_x16 computes it; how launch_render_scaled would divide a launch among workgroups */
@@ -801,13 +855,14 @@ int mlvfs_amd_rgb_geom(int width, int height, int *pw, int *ph)
 
 // mlvfs_amd_render2_dev and mlvfs_amd_render2_look_dev: the same checks before any device work
 static int render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream)
+                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream, const mlvfs_amd_look16_t *deep = nullptr,
+                       bool with_deep = false)
 {
-    if (!d_frames || !d_out || !d_params || (with_look && !look)) { set_error("render2: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render2: null argument"); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0) { set_error("render2: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     int pw, ph;
     if (!rgb_geom(width, height, &pw, &ph)) { set_error("render2: %dx%d not supported (2x2 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)3 * pw * ph;
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * pw * ph;
     if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render2: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
     if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
         set_error("render2: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
@@ -822,7 +877,9 @@ static int render2_dev(const void *d_frames, size_t stride, int width, int heigh
     if (!c) return MLVFS_AMD_ERR_HIP;
     LookArg lk;
     if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    return launch_render2(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c), with_look ? &lk : nullptr);
+    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
+    return launch_render2(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c),
+                          with_look || with_deep ? &lk : nullptr, with_deep);
 }
 
 int mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
@@ -837,6 +894,12 @@ int mlvfs_amd_render2_look_dev(const void *d_frames, size_t stride, int width, i
     return render2_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, look, true, stream);
 }
 
+int mlvfs_amd_render2_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                               size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
+{
+    return render2_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream, look, true);
+}
+
 int mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph)
 {
     if (!pw || !ph) { set_error("rgb_full_geom: null argument"); return MLVFS_AMD_ERR_ARG; }
@@ -848,12 +911,13 @@ int mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph)
 
 // mlvfs_amd_render1_dev and mlvfs_amd_render1_look_dev: the same checks before any device work
 static int render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream)
+                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream, const mlvfs_amd_look16_t *deep = nullptr,
+                       bool with_deep = false)
 {
-    if (!d_frames || !d_out || !d_params || (with_look && !look)) { set_error("render1: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render1: null argument"); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0) { set_error("render1: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     if (!rgb_full_geom(width, height)) { set_error("render1: %dx%d not supported (4x4 up to 2^25 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)3 * width * height;
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * width * height;
     if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render1: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
     if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
         set_error("render1: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
@@ -868,7 +932,9 @@ static int render1_dev(const void *d_frames, size_t stride, int width, int heigh
     if (!c) return MLVFS_AMD_ERR_HIP;
     LookArg lk;
     if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    return launch_render1(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c), with_look ? &lk : nullptr);
+    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
+    return launch_render1(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c),
+                          with_look || with_deep ? &lk : nullptr, with_deep);
 }
 
 int mlvfs_amd_render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
@@ -881,6 +947,12 @@ int mlvfs_amd_render1_look_dev(const void *d_frames, size_t stride, int width, i
                                size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
 {
     return render1_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, look, true, stream);
+}
+
+int mlvfs_amd_render1_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                               size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
+{
+    return render1_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream, look, true);
 }
 
 int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,

@@ -81,12 +81,13 @@ def stages(frame, p, border: str = "reflect") -> dict:
     n = np.clip((s + 8) >> 4, 0, 65535)
     acc = np.stack([sum(np.int64(K[3 * i + k]) * n[k] for k in range(3)) for i in range(3)])
     t = np.clip((acc + 32768) >> 16, 0, 4095)
-    return dict(b=b, sums=sums, which=which, s=s, n=n, acc=acc, t=t, below=q < black, site=j)
+    return dict(b=b, sums=sums, which=which, s=s, n=n, acc=acc, t=t, t16=_render.index16(acc), below=q < black, site=j)
 
 
-def render(frame, p, lut=None, border: str = "reflect", look=None) -> np.ndarray:
-    """(H, W, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table"""
-    return _render.tone(stages(frame, p, border)["t"], lut, look)
+def render(frame, p, lut=None, border: str = "reflect", look=None, look16=None) -> np.ndarray:
+    """(H, W, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table; look16: the 16-bit rendering through
+    a deep look, uint16"""
+    return _render.develop(stages(frame, p, border), lut, look, look16)
 
 
 def split_file(file, w: int, h: int) -> np.ndarray:

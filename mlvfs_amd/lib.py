@@ -76,6 +76,10 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_mount_rgb_scaled_size", "mlvfs_amd_test_scale_div", "mlvfs_amd_test_scale_plan",
     "mlvfs_amd_look_image_size", "mlvfs_amd_look_pack", "mlvfs_amd_look_create", "mlvfs_amd_look_destroy", "mlvfs_amd_look_apply_dev",
     "mlvfs_amd_render2_look_dev", "mlvfs_amd_render1_look_dev", "mlvfs_amd_render_scaled_look_dev", "mlvfs_amd_mount_set_look",
+    "mlvfs_amd_look16_image_size", "mlvfs_amd_look16_pack", "mlvfs_amd_look16_create", "mlvfs_amd_look16_destroy", "mlvfs_amd_look16_apply_dev",
+    "mlvfs_amd_rgb16_header", "mlvfs_amd_render2_deep_dev", "mlvfs_amd_render1_deep_dev", "mlvfs_amd_render_scaled_deep_dev",
+    "mlvfs_amd_mount_rgb16", "mlvfs_amd_mount_rgb16_full", "mlvfs_amd_mount_rgb16_scaled",
+    "mlvfs_amd_mount_rgb16_size", "mlvfs_amd_mount_rgb16_full_size", "mlvfs_amd_mount_rgb16_scaled_size",
 ]
 
 
@@ -303,6 +307,21 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_render1_look_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
     sig("mlvfs_amd_render_scaled_look_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
     sig("mlvfs_amd_mount_set_look", i, [vp, vp])
+    sig("mlvfs_amd_look16_image_size", sz, [i])
+    sig("mlvfs_amd_look16_pack", i, [vp, i, vp, vp, sz])
+    sig("mlvfs_amd_look16_create", vp, [vp, i, vp])
+    sig("mlvfs_amd_look16_destroy", None, [vp])
+    sig("mlvfs_amd_look16_apply_dev", i, [vp, vp, sz, vp, vp])
+    sig("mlvfs_amd_rgb16_header", sz, [i, i, vp, sz])
+    sig("mlvfs_amd_render2_deep_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_render1_deep_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_render_scaled_deep_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_mount_rgb16", i, [vp, i, i, vp, sz, i, vp, i, i, vp])
+    sig("mlvfs_amd_mount_rgb16_full", i, [vp, i, i, vp, sz, i, vp, i, i, vp])
+    sig("mlvfs_amd_mount_rgb16_scaled", i, [vp, i, i, vp, sz, i, i, i, vp, i, i, vp])
+    sig("mlvfs_amd_mount_rgb16_size", sz, [vp, i])
+    sig("mlvfs_amd_mount_rgb16_full_size", sz, [vp, i])
+    sig("mlvfs_amd_mount_rgb16_scaled_size", sz, [vp, i, i, i])
     _lib = L
     return L
 

@@ -15,6 +15,9 @@
     m.set_look(look.Look(S, n, T)) puts a shaper and a 3D table -- a .cube file -- in the place of the sRGB curve in every later rgb() and
     jpeg() call (include/mlvfs_amd.h, "a look for the rendered frames"; mlvfs_amd/look.py is the definition in numpy).
 
+    m.rgb(0, 16, look16=look.Look16(S16, n, T)) serves them as 16-bit TIFF files toned from 16-bit linear light through a deep look that
+    is passed per call (include/mlvfs_amd.h, "rendered frames at 16 bits").
+
     files, flags = m.jpeg(0, 16, gain=1.0, quality=90) serves the same renderings as baseline JPEG files encoded on the GPU, a tenth
     of the bytes (include/mlvfs_amd.h, "rendered frames as baseline JPEG files"; mlvfs_amd/jpeg.py is the definition in numpy).
 
@@ -80,7 +83,7 @@ class Mount:
 
     def set_look(self, look) -> None:
         """look: a mlvfs_amd.look.Look that every later rgb() and jpeg() call renders with, at all three sizes (None clears).  Allowed at
-        any time between calls; dng(), dng_lossless() and the proxies never see it.  It must stay open while it is set."""
+        any time between calls; dng(), dng_lossless(), the proxies and rgb(look16=...) never see it.  It must stay open while it is set."""
         lib.check(self.L.mlvfs_amd_mount_set_look(self.h, None if look is None else look.h), "mount_set_look")
         self._look = look
 
@@ -134,34 +137,50 @@ class Mount:
         ow, oh = size
         return int(ow), int(oh)
 
-    def rgb_size(self, index: int = 0, full: bool = False, size=None) -> int:
+    def rgb_size(self, index: int = 0, full: bool = False, size=None, bits: int = 8) -> int:
         """bytes of file `index` as rgb() serves it: the TIFF header + 3 * (W // 2) * (H // 2); full: + 3 * W * H; size=(ow, oh):
-        + 3 * ow * oh"""
+        + 3 * ow * oh; bits=16: as rgb(look16=...) serves it, twice the pixel bytes"""
+        if bits not in (8, 16):
+            raise ValueError(f"{bits} bits per sample (8 or 16)")
         size = self._size_arg(size, full)
+        L, deep = self.L, bits == 16
         if size is not None:
-            size = int(self.L.mlvfs_amd_mount_rgb_scaled_size(self.h, index, *size))
+            size = int((L.mlvfs_amd_mount_rgb16_scaled_size if deep else L.mlvfs_amd_mount_rgb_scaled_size)(self.h, index, *size))
+        elif full:
+            size = int((L.mlvfs_amd_mount_rgb16_full_size if deep else L.mlvfs_amd_mount_rgb_full_size)(self.h, index))
         else:
-            size = int((self.L.mlvfs_amd_mount_rgb_full_size if full else self.L.mlvfs_amd_mount_rgb_size)(self.h, index))
+            size = int((L.mlvfs_amd_mount_rgb16_size if deep else L.mlvfs_amd_mount_rgb_size)(self.h, index))
         if not size:
             raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
         return size
 
     def rgb(self, first: int, count: int, gain: float = 1.0, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None,
-            full: bool = False, size=None) -> np.ndarray:
+            full: bool = False, size=None, look16=None) -> np.ndarray:
         """Frames first .. first + count - 1 rendered to half-size 8-bit sRGB TIFF files: a (count, rgb_size) uint8 array.  gain: the
         exposure factor, in steps of 1 / 256 (gain_q8 = round(256 * gain), 1 .. 65535).  Not on a handle that serves proxies.
         full: at the frame's own size, demosaiced on the GPU (mlvfs_amd/demosaic.py): a (count, rgb_size(full=True)) array.
         size=(ow, oh): at any size up to half the frame's, area-averaged in linear light on the GPU (mlvfs_amd/scale.py): a
-        (count, rgb_size(size=size)) array.  Not together with full=True."""
+        (count, rgb_size(size=size)) array.  Not together with full=True.
+        look16: a mlvfs_amd.look.Look16 -- the same renderings as 16-bit TIFF files toned from 16-bit linear light through that deep look
+        (rgb_size(..., bits=16) bytes each).  It is passed per call; set_look() does not touch these files."""
         size = self._size_arg(size, full)
         gain_q8 = int(round(256 * gain))
         if not 1 <= gain_q8 <= 65535:
             raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
-        out = np.zeros((count, self.rgb_size(first, full, size) if count else 0), np.uint8)
+        out = np.zeros((count, self.rgb_size(first, full, size, 16 if look16 is not None else 8) if count else 0), np.uint8)
         if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
                                         and results.size >= count):
             raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
         res = np.zeros(max(count, 1), np.int32) if results is None else results
+        if look16 is not None:
+            if size is not None:
+                lib.check(self.L.mlvfs_amd_mount_rgb16_scaled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1],
+                                                              look16.h, batch, io_threads, lib.ptr(res)), "mount_rgb16_scaled")
+                return out
+            call = self.L.mlvfs_amd_mount_rgb16_full if full else self.L.mlvfs_amd_mount_rgb16
+            lib.check(call(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, look16.h, batch, io_threads, lib.ptr(res)),
+                      "mount_rgb16_full" if full else "mount_rgb16")
+            return out
         if size is not None:
             lib.check(self.L.mlvfs_amd_mount_rgb_scaled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1], batch,
                                                         io_threads, lib.ptr(res)), "mount_rgb_scaled")

@@ -94,7 +94,27 @@ def stages(frame, p) -> dict:
     n = np.stack([np.minimum((c[j] * np.int64(A[j]) + 2048) >> 12, 65535) for j in range(3)])
     acc = np.stack([sum(np.int64(K[3 * i + j]) * n[j] for j in range(3)) for i in range(3)])
     t = np.clip((acc + 32768) >> 16, 0, 4095)
-    return dict(c=c, n=n, acc=acc, t=t, green_sum=g)
+    return dict(c=c, n=n, acc=acc, t=t, t16=index16(acc), green_sum=g)
+
+
+def index16(acc) -> np.ndarray:
+    """step 3d of the 16-bit routes: clamp((acc + 2048) >> 12, 0, 65535)"""
+    return np.clip((np.asarray(acc, np.int64) + 2048) >> 12, 0, 65535)
+
+
+def tone16(t16, look16) -> np.ndarray:
+    """step 4 of the 16-bit routes on t16 (3, H, W) -> (H, W, 3) uint16; look16 = (S16, n, T) or a look.Look16"""
+    from . import look as _look
+    return np.ascontiguousarray(_look.apply16(t16, *_look.as_tuple16(look16)).transpose(1, 2, 0))
+
+
+def develop(st: dict, lut=None, look=None, look16=None) -> np.ndarray:
+    """steps 3d / 4 of a stages() result: the 8-bit rendering, or with look16 the 16-bit one"""
+    if look16 is not None:
+        if look is not None or lut is not None:
+            raise ValueError("look16= excludes look= and lut=")
+        return tone16(st["t16"], look16)
+    return tone(st["t"], lut, look)
 
 
 def tone(t, lut=None, look=None) -> np.ndarray:
@@ -106,19 +126,29 @@ def tone(t, lut=None, look=None) -> np.ndarray:
     return np.ascontiguousarray(lut[t].transpose(1, 2, 0))
 
 
-def render(frame, p, lut=None, look=None) -> np.ndarray:
-    """(H // 2, W // 2, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table"""
-    return tone(stages(frame, p)["t"], lut, look)
+def render(frame, p, lut=None, look=None, look16=None) -> np.ndarray:
+    """(H // 2, W // 2, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table; look16: the 16-bit
+    rendering through a deep look, uint16"""
+    return develop(stages(frame, p), lut, look, look16)
 
 
-def tiff_header(pw: int, ph: int) -> bytes:
-    """the file's first HEADER_BYTES bytes: a baseline little-endian TIFF, one strip of 8-bit RGB behind the header"""
+def tiff_header(pw: int, ph: int, bits: int = 8) -> bytes:
+    """the file's first HEADER_BYTES bytes: a baseline little-endian TIFF, one strip of 8-bit (or 16-bit) RGB behind the header"""
+    if bits not in (8, 16):
+        raise ValueError(f"{bits} bits per sample (8 or 16)")
     entries = [(256, 4, 1, pw), (257, 4, 1, ph), (258, 3, 3, 158), (259, 3, 1, 1), (262, 3, 1, 2), (273, 4, 1, HEADER_BYTES), (274, 3, 1, 1),
-               (277, 3, 1, 3), (278, 4, 1, ph), (279, 4, 1, 3 * pw * ph), (284, 3, 1, 1), (305, 2, 6, 164)]
+               (277, 3, 1, 3), (278, 4, 1, ph), (279, 4, 1, 3 * (bits // 8) * pw * ph), (284, 3, 1, 1), (305, 2, 6, 164)]
     buf = struct.pack("<HHIH", 0x4949, 42, 8, len(entries)) + b"".join(struct.pack("<HHII", *e) for e in entries) + struct.pack("<I", 0)
     assert len(buf) == 158
-    buf += struct.pack("<3H", 8, 8, 8) + b"MLVFS\0"
+    buf += struct.pack("<3H", bits, bits, bits) + b"MLVFS\0"
     return buf + bytes(HEADER_BYTES - len(buf))
+
+
+def split_file16(file, pw: int, ph: int) -> np.ndarray:
+    """the samples of one served 16-bit file"""
+    b = bytes(file)
+    assert len(b) == HEADER_BYTES + 6 * pw * ph
+    return np.frombuffer(b, "<u2", offset=HEADER_BYTES).reshape(ph, pw, 3)
 
 
 def split_file(file, pw: int, ph: int) -> np.ndarray:

@@ -86,12 +86,13 @@ def stages(frame, p, ow: int, oh: int) -> dict:
     K = p[4:13]
     acc = np.stack([sum(np.int64(K[3 * i + j]) * m[j] for j in range(3)) for i in range(3)])
     t = np.clip((acc + 32768) >> 16, 0, 4095)
-    return dict(n=n, hm=hm, m=m, acc=acc, t=t)
+    return dict(n=n, hm=hm, m=m, acc=acc, t=t, t16=_render.index16(acc))
 
 
-def render(frame, p, ow: int, oh: int, lut=None, look=None) -> np.ndarray:
-    """(oh, ow, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table"""
-    return _render.tone(stages(frame, p, ow, oh)["t"], lut, look)
+def render(frame, p, ow: int, oh: int, lut=None, look=None, look16=None) -> np.ndarray:
+    """(oh, ow, 3) uint8, R G B; look: step 4 with a look (mlvfs_amd/look.py) instead of the table; look16: the 16-bit rendering
+    through a deep look, uint16"""
+    return _render.develop(stages(frame, p, ow, oh), lut, look, look16)
 
 
 def split_file(file, ow: int, oh: int) -> np.ndarray:

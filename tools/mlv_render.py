@@ -7,8 +7,10 @@ linear light on the GPU (mlvfs_amd_mount_rgb_scaled, mlvfs_amd_mount_jpeg_scaled
 --lut FILE.cube puts a 3D table, interpolated tetrahedrally on the GPU, in the place of the sRGB curve of every one of these routes
 (mlvfs_amd_mount_set_look; "a look for the rendered frames"); --lut-input says what the table's input axis means: the sRGB value the
 plain rendering would write (the default), linear light, or log2:STOPS -- a pure log curve over that many stops below white.
+--bits 16 writes 16-bit TIFF files toned from 16-bit linear light (mlvfs_amd_mount_rgb16 and its forms; "rendered frames at 16 bits"):
+--lut-input's curve on the 16-bit index (linear: the file holds linear light itself), --lut's table behind it if one is given.
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--jpeg [QUALITY]] [--lut FILE.cube [--lut-input srgb|linear|log2:STOPS]] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--jpeg [QUALITY]] [--bits 16] [--lut FILE.cube] [--lut-input srgb|linear|log2:STOPS] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
@@ -48,8 +50,11 @@ def main() -> int:
     how.add_argument("--size", type=wxh, metavar="WxH", help="render at W x H, at most half the frame's size a side (an area average in linear light)")
     how.add_argument("--fit", type=wxh, metavar="WxH", help="render at the largest size inside a box of W x H at the frame's aspect")
     ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
+    ap.add_argument("--bits", type=int, default=8, choices=(8, 16), help="16: 16-bit TIFF files toned from 16-bit linear light through --lut-input's "
+                    "curve (and --lut's table behind it, if given); not with --jpeg")
     ap.add_argument("--lut", metavar="FILE.cube", help="a 3D .cube table (domain 0 .. 1, up to 65 a side) applied to every rendering")
-    ap.add_argument("--lut-input", default="srgb", metavar="srgb|linear|log2:STOPS", help="what the table's input axis means (default srgb)")
+    ap.add_argument("--lut-input", default="srgb", metavar="srgb|linear|log2:STOPS", help="what the table's input axis means (default srgb); "
+                    "with --bits 16 and no --lut: the curve the files carry")
     ap.add_argument("--cs", type=int, default=0, choices=(0, 2, 3, 5), help="chroma smoothing")
     ap.add_argument("--bad-pix", type=int, default=0, choices=(0, 1, 2), help="bad-pixel repair (2: aggressive)")
     ap.add_argument("--stripes", action="store_true", help="vertical stripes correction")
@@ -68,16 +73,22 @@ def main() -> int:
         ap.error(f"--gain {a.gain} outside 1 / 256 .. 65535 / 256")
     if a.jpeg and not 1 <= a.jpeg <= 100:
         ap.error(f"--jpeg {a.jpeg} outside 1 .. 100")
-    cube = None
-    if a.lut:
+    if a.bits == 16 and a.jpeg:
+        ap.error("--bits 16 --jpeg: there are no 16-bit JPEG files")
+    cube = deep = None
+    if a.lut or a.bits == 16:
         try:
-            cube = (look.shaper(a.lut_input),) + look.read_cube(a.lut)
+            table = look.read_cube(a.lut) if a.lut else (0, None)
+            if a.bits == 16:
+                deep = (look.shaper16(a.lut_input),) + table
+            else:
+                cube = (look.shaper(a.lut_input),) + table
         except (OSError, ValueError) as e:
-            ap.error(f"--lut {a.lut}: {e}")
+            ap.error(f"--lut {a.lut}: {e}" if a.lut else f"--lut-input: {e}")
     stem = os.path.splitext(os.path.basename(a.src))[0]
     opt = MlvfsOptions(chroma_smooth=a.cs, fix_bad_pixels=a.bad_pix, fix_stripes=int(a.stripes), dual_iso=a.dual_iso,
                        hdr_interpolation_method=a.hdr_interp, fix_pattern_noise=int(a.pattern_noise))
-    dark = flat = lk = None
+    dark = flat = lk = lk16 = None
     with mlvfile.MlvReader(a.src) as r:
         count = a.count or r.frame_count - a.first
         if a.first < 0 or count <= 0 or a.first + count > r.frame_count:
@@ -109,6 +120,8 @@ def main() -> int:
                     flat = Flat.from_clip(fr, dark=dark, batch=a.batch, io_threads=a.io_threads)
             if cube:
                 lk = look.Look(*cube)
+            if deep:
+                lk16 = look.Look16(*deep)
             t0, total = time.perf_counter(), 0
             with Mount(r, opt, deflicker=a.deflicker, basename="/" + os.path.basename(a.src), dark=dark, flat=flat) as m:
                 if lk is not None:
@@ -121,7 +134,7 @@ def main() -> int:
                         targets = [names[f0 + k] if flags[k] & 1 else jpgs[f0 + k] for k in range(n)]
                     else:
                         files = [f.tobytes() for f in m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads, full=a.full,
-                                                            size=size)]
+                                                            size=size, look16=lk16)]
                         targets = names[f0:f0 + n]
                     for name, data in zip(targets, files):
                         with open(name, "xb") as out:                       # "x": never over a file that appeared meanwhile
@@ -131,6 +144,8 @@ def main() -> int:
         finally:
             if lk is not None:
                 lk.close()
+            if lk16 is not None:
+                lk16.close()
             if flat is not None:
                 flat.close()
             if dark is not None:
