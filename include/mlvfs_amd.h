@@ -898,8 +898,8 @@ int    mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size
  *   3., 4.  the half-size definition's, with n = (m_R, m_G, m_B): t_i = clamp((sum_j K[i][j] n_j + 32768) >> 16, 0, 4095) in 64 bits,
  *      out_i = LUT[t_i]; bytes in R, G, B order, rows top down, no padding in a row.
  * The file: mlvfs_amd_rgb_header(W, H, ...) followed by 3 W H bytes -- the same 256-byte TIFF header at full size.
- * Not built: an adaptive demosaic, a crop to the active area, 16-bit output, highlight recovery, other CFA orders, sizes between half
- * and full size (smaller ones: "rendered frames at any smaller size" below).                                                      */
+ * Not built: an adaptive demosaic, a crop to the active area, 16-bit output, highlight recovery, other CFA orders, enlarging (smaller
+ * sizes: "rendered frames at any smaller size" and "rendered frames resampled from the full-size rendering" below).               */
 /* *pw = width, *ph = height.  Host code.  MLVFS_AMD_ERR_ARG: a null pointer, a size below 4, 2^25 pixels or more. */
 int    mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph);
 /* mlvfs_amd_render2_dev at full size: nframes frames of width x height 16-bit pixels `stride` bytes apart -> their renderings, 3 W H
@@ -951,8 +951,8 @@ size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index);
  * The file: mlvfs_amd_rgb_header(ow, oh, ...) followed by 3 ow oh bytes, or the JPEG file of that rendering; the flag rule is the
  *   half-size JPEG call's: bit 0 is set and the TIFF is served when 629 + stream > 256 + 3 ow oh.
  * Not applied, as before: the deflicker's exposure bias, and any crop.
- * Not built: sizes between half and full size (they would resample the demosaiced rendering), enlarging, other filters than the area
- *   average, contact sheets.                                                                                                         */
+ * Not built: enlarging, other filters than the area average, contact sheets.  Sizes between half and full size: "rendered frames
+ *   resampled from the full-size rendering" below.                                                                                   */
 /* the largest size inside a box of box_w x box_h at the frame's aspect.  Host code.  With W', H' as above: box_w >= W' and
  * box_h >= H' gives (W', H'); otherwise, if box_w H' <= box_h W' (in 64 bits), the width limits: ow = min(box_w, W'),
  * oh = max(1, (2 ow H' + W') / (2 W')); otherwise the height limits: oh = min(box_h, H'), ow = max(1, (2 oh W' + H') / (2 H')).
@@ -1111,6 +1111,74 @@ int    mlvfs_amd_mount_rgb16_scaled(void *mount, int first, int count, void *h_o
 size_t mlvfs_amd_mount_rgb16_size(const void *mount, int index);
 size_t mlvfs_amd_mount_rgb16_full_size(const void *mount, int index);
 size_t mlvfs_amd_mount_rgb16_scaled_size(const void *mount, int index, int ow, int oh);
+
+/* -- rendered frames resampled from the full-size rendering (csrc/k_resample.hip, csrc/mount.cpp) ---------------------- */
+/* The rendering at any size up to the frame's own -- a 1920 x 1080 delivery of a 3.5K clip, a 1 x 3 binning mode squeezed back --,
+ * area-averaged in linear light between the full-size rendering's demosaic and its matrix.  The definition is this project's, in
+ * integers only, so that it has a byte-exact oracle (mlvfs_amd/resample.py).
+ * Geometry.  W, H >= 4, W <= 65535, H <= 65535 and W H < 2^25: the full-size rendering's rule and a limit on the sides.  The caller
+ *   names an output size ow x oh with 1 <= ow <= W, 1 <= oh <= H: the resampling never enlarges, and the two factors are independent
+ *   (ow = W, oh = H / 3 is allowed).  Anything else is MLVFS_AMD_ERR_ARG before any device work.
+ * Source.  The three demosaiced 16-bit channels d_c(y, x), c = R, G, B, of the full-size definition after its steps 1 and 2: the pixel
+ *   balanced at its own site, the border reflected about the edge pixel, the Malvar-He-Cutler sums in sixteenths, an interpolated
+ *   channel clamp((s + 8) >> 4, 0, 65535), the site's own channel untouched.
+ * Weights.  The scaled definition's with W and H in the place of W' and H':
+ *                   wx(u, x) = max(0, min((x + 1) ow, (u + 1) W) - max(x ow, u W))              wy(v, y) likewise with H and oh
+ * Horizontal pass.
+ *                   hd_c(y, u) = floor((sum_x wx(u, x) d_c(y, x) + (W >> 1)) / W)
+ * Vertical pass.
+ *                   m_c(v, u) = floor((sum_y wy(v, y) hd_c(y, u) + (H >> 1)) / H)
+ *   Every sum is at most 65535^2 and fits 32 bits unsigned with its rounding term.
+ * Steps 3 and 4 are the half-size definition's with n = m, in each of the three tone forms: the sRGB table, a look, a deep look with
+ *   16-bit samples.
+ * Consequences the tests use: ow = W, oh = H is the full-size rendering byte for byte, in all three tone forms; a frame that is flat per
+ *   CFA colour renders to the half-size definition's pixel at every size.
+ * This is NOT the scaled route at the sizes both accept (1x1 up to W' x H'): this one averages interpolated samples, that one
+ *   averages superpixels, and their bytes differ.  Neither chooses the other by itself.
+ * The file: mlvfs_amd_rgb_header(ow, oh, ...) followed by 3 ow oh bytes; at 16 bits mlvfs_amd_rgb16_header and 6 ow oh bytes; or the
+ *   JPEG file of the 8-bit rendering with the half-size JPEG call's flag rule.
+ * Not applied, as before: the deflicker's exposure bias, and any crop.
+ * Not built: enlarging, other filters than the area average, an adaptive demosaic as the source.                                      */
+/* mlvfs_amd_rgb_fit's rule on the W x H grid: if box_w H <= box_h W (in 64 bits) the width limits: ow = min(box_w, W),
+ * oh = max(1, (2 ow H + W) / (2 W)); otherwise the height limits: oh = min(box_h, H), ow = max(1, (2 oh W + H) / (2 H)).  3584 x 1320
+ * in 1920 x 1080 gives 1920 x 707.  Host code.  MLVFS_AMD_ERR_ARG, with the outputs untouched: a null pointer, a box side below 1, a
+ * frame that the resampled rendering does not take.                                                                                  */
+int    mlvfs_amd_rgb_fit_full(int width, int height, int box_w, int box_h, int *ow, int *oh);
+/* mlvfs_amd_render1_dev at ow x oh: nframes frames of width x height 16-bit pixels `stride` bytes apart -> their renderings, 3 ow oh
+ * bytes each (6 ow oh in the deep form), out_stride bytes apart, frame k with the 13 parameters d_params[13 k ..].  Bytes between
+ * renderings and behind a rendering are not touched.  Not in place.  Asynchronous on `stream`; every check happens before any device
+ * work, and the checks are mlvfs_amd_render1_dev's plus the geometry above; the look and deep forms take what their render1
+ * counterparts take.  width a multiple of 16 with source base and stride 16-byte aligned and 2 ow >= width takes the fast form
+ * (k_resample_x16: a workgroup walks the source rows of a band of output rows of one strip of columns, the balanced rows in
+ * k_render1_x16's ring, the demosaiced row in LDS; one pass, nothing in between in device memory; the deep form needs a 2-byte aligned
+ * destination); anything else one output pixel per lane with its footprint demosaiced from global memory (k_resample_generic).     */
+int    mlvfs_amd_render_resampled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                      void *d_out, size_t out_stride, int nframes, void *stream);
+int    mlvfs_amd_render_resampled_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                           void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream);
+int    mlvfs_amd_render_resampled_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                           void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream);
+/* mlvfs_amd_mount_rgb_full, mlvfs_amd_mount_jpeg_full and mlvfs_amd_mount_rgb16_full at ow x oh: the same stages, the same serve-order
+ * state, the same results[], the handle's look on the 8-bit calls.  A resampled rendering can exceed a frame's other slot, so the
+ * renderings (and a JPEG call's streams behind them) lie in the full-size calls' device buffer, sized for ow x oh; it grows and fails
+ * as it does for them.  out_stride: anything from the size call's answer up.  A handle that never makes a resampled call serves byte
+ * for byte and launch for launch what it served before.  May be interleaved with the other serving calls on one handle.
+ * MLVFS_AMD_ERR_ARG besides the full-size calls' (a handle with mlvfs_amd_mount_set_proxy(2) among them): a size outside the geometry. */
+int    mlvfs_amd_mount_rgb_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
+                                     int batch_frames, int io_threads, int *results);
+int    mlvfs_amd_mount_jpeg_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, int ow,
+                                      int oh, size_t *sizes, int *flags, int batch_frames, int io_threads, int *results);
+int    mlvfs_amd_mount_rgb16_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
+                                       const mlvfs_amd_look16_t *look, int batch_frames, int io_threads, int *results);
+/* bytes of file `index` as those calls serve it (256 + 3 ow oh, 256 + 6 ow oh); 0: no such frame, or a size the frame does not allow */
+size_t mlvfs_amd_mount_rgb_resampled_size(const void *mount, int index, int ow, int oh);
+size_t mlvfs_amd_mount_rgb16_resampled_size(const void *mount, int index, int ow, int oh);
+/* Test hook, host only: how a launch of nframes frames is divided among k_resample_x16's workgroups -- out = { 1 where the sizes allow
+ * the fast form (width % 16 == 0 and 2 ow >= width; the alignment is the caller's), the most source columns of a strip, the output
+ * columns of a strip, the strips, the output rows of a band, the bands, the source rows a band covers at least, the source rows of
+ * a step }; the four numbers of the plan are 0 where the first is.  A strip's source columns run from floor(us0 W / ow) rounded down
+ * to 8 up to ceil(us1 W / ow) rounded up to 8; a band's source rows from floor(v0 H / oh) up to ceil(v1 H / oh).                  */
+int    mlvfs_amd_test_resample_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8]);
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);

@@ -335,6 +335,42 @@ inline ScalePlan scale_plan(int pw, int ph, int ow, int oh, int nframes)
 }
 int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
                          int oh, int nframes, hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
+// rendered frames resampled from the full-size rendering (k_resample.hip): the full-size rendering's frames with both sides up to
+// 65535, and ow x oh from 1x1 up to the frame's own size; the resampling pass, with the same parameters
+inline bool resample_geom(int w, int h, int ow, int oh)
+{
+    return rgb_full_geom(w, h) && w <= 65535 && h <= 65535 && ow >= 1 && ow <= w && oh >= 1 && oh <= h;
+}
+// what k_resample_x16 asks of the sizes: whole 16-pixel groups, and output columns that span at most three source pixels
+inline bool resample_fast_geom(int w, int ow) { return w % 16 == 0 && 2 * (int64_t)ow >= w; }
+// how k_resample_x16 divides a frame among workgroups: strips of uo output columns whose source columns, from a multiple of 8 to a
+// multiple of 8, fit the RS_STRIP columns of the ring (k_demosaic_dev.h), and bands of bo output rows
+constexpr int RS_STRIP = 512;                         // source columns a workgroup demosaics at most
+constexpr int RS_ROWS = 4;                            // source rows a step demosaics: one per wave
+constexpr int RS_BAND_ROWS = 32;                      // source rows a band covers at least: a seam costs five rows balanced twice
+struct ResamplePlan {
+    uint32_t uo, nstrips, bo, nbands;
+};
+inline ResamplePlan resample_plan(int w, int h, int ow, int oh, int nframes)
+{
+    ResamplePlan p;
+    // uo output columns cover at most ceil(uo w / ow) + 1 source columns, and the rounding to 8 adds at most 7 at each side
+    p.uo = (uint32_t)((uint64_t)(RS_STRIP - 16) * ow / w);
+    // a lane takes the columns l and l + 256 of its strip: a strip of a few more than 256 would make one wave walk twice for them
+    // while the others wait, so a strip is 256 columns unless it fills at least half of the second round
+    if (p.uo > 256 && p.uo < 384) p.uo = 256;
+    p.uo = std::min(std::max(p.uo, 1u), (uint32_t)ow);
+    p.nstrips = ((uint32_t)ow + p.uo - 1) / p.uo;
+    // as many workgroups in a launch as the machine holds at once (256 CUs x 4 of them by their LDS), and bands that are not all seam
+    const uint32_t budget = std::max(1024u / (uint32_t)std::max(nframes, 1), 32u);
+    const uint32_t nb = std::min(std::max(budget / p.nstrips, 1u), (uint32_t)oh);
+    const uint32_t least = (uint32_t)(((uint64_t)RS_BAND_ROWS * oh + h - 1) / h);
+    p.bo = std::min(std::max(((uint32_t)oh + nb - 1) / nb, least), (uint32_t)oh);
+    p.nbands = ((uint32_t)oh + p.bo - 1) / p.bo;
+    return p;
+}
+int launch_render_resampled(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
+                            int oh, int nframes, hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

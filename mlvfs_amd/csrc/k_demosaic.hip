@@ -26,68 +26,17 @@
 // k_render1_deep_x16, k_render1_deep_generic: the same bodies with the 16-bit form of steps 3 and 4 and 6 bytes per pixel -- a lane of
 // the x16 form writes 48 bytes as three 128-bit stores, so its destination base and stride are 16-byte aligned (one that is only 8-byte
 // aligned takes the generic kernel); no table in LDS.
-#include "k_tone_dev.h"
+#include "k_demosaic_dev.h"
 
 namespace mlv {
 
 namespace {                    // this file's device helpers
 
-constexpr int R1_STRIP = 512;                         // columns of a workgroup's strip: 64 lanes x 8 pixels
 constexpr int R1_RUN = 32;                            // rows a workgroup walks down
-constexpr int R1_RING = 16;                           // rows of the ring: the 12 a step has live (8 read, 4 written), as a power of two
-constexpr int R1_PITCH = 8 + R1_STRIP + 8;            // uint16 per ring row: the strip from [8] on, the halos at [6], [7] and behind it
 
-// the index inside 0 .. n - 1 that stands for i in -2 .. n + 1 (n >= 3)
-__device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; }
-
-__device__ __forceinline__ uint32_t sixteenths(int s)
-{
-    const int m = (s + 8) >> 4;
-    return (uint32_t)(m < 0 ? 0 : m > 65535 ? 65535 : m);
-}
-
-// ---- k_render1_x16
-// one source row of the strip as a wave loads it: 8 pixels per lane, and in lanes 0 .. 3 one halo pixel each
-struct RowLoad {
-    uint4 main;
-    uint32_t halo;
-};
-
-// row r of the frame (-2 .. h + 1 are reflected); rows behind rmax -- the frame's last row + 2, the run's last row + 2 -- are not needed
-// and not read; x0: the strip's first column, sw its width
-__device__ __forceinline__ void load_row(RowLoad &v, const uint16_t *src, int w, int h, int r, int rmax, int x0, int sw, int lane)
-{
-    if (r > rmax) return;
-    const uint16_t *row = src + (size_t)reflect(r, h) * w;
-    if (8 * lane < sw) v.main = *(const uint4 *)(row + x0 + 8 * lane);
-    if (lane < 4) v.halo = row[reflect(lane < 2 ? x0 - 2 + lane : x0 + sw + lane - 2, w)];
-}
-
-__device__ __forceinline__ uint32_t balance2(uint32_t d, const Black &bl, int32_t a_even, int32_t a_odd)
-{
-    return balance(bl(d & 0xFFFFu), a_even) | (balance(bl(d >> 16), a_odd) << 16);
-}
-
-// balanced once, into slot `slot` of the ring
-__device__ __forceinline__ void store_row(const RowLoad &v, uint16_t *ring, int slot, int r, int rmax, int sw, int lane, const Black &bl, const RenderParams &p)
-{
-    if (r > rmax) return;
-    const bool odd = r & 1;                                   // the reflection keeps the parity
-    const int32_t a_even = odd ? p.A[1] : p.A[0], a_odd = odd ? p.A[2] : p.A[1];
-    uint16_t *row = ring + slot * R1_PITCH;
-    if (8 * lane < sw)
-        *(uint4 *)(row + 8 + 8 * lane) = make_uint4(balance2(v.main.x, bl, a_even, a_odd), balance2(v.main.y, bl, a_even, a_odd),
-                                                    balance2(v.main.z, bl, a_even, a_odd), balance2(v.main.w, bl, a_even, a_odd));
-    if (lane < 4) row[lane < 2 ? 6 + lane : 8 + sw + lane - 2] = (uint16_t)balance(bl(v.halo), (lane & 1) ? a_odd : a_even);
-}
-
-__device__ __forceinline__ void unpack8(int *o, const uint4 &v)
-{
-    o[0] = v.x & 0xFFFFu; o[1] = v.x >> 16; o[2] = v.y & 0xFFFFu; o[3] = v.y >> 16;
-    o[4] = v.z & 0xFFFFu; o[5] = v.z >> 16; o[6] = v.w & 0xFFFFu; o[7] = v.w >> 16;
-}
-
-// the 8 pixels of one lane: rows y - 2 .. y + 2 of the ring at m2, m1, c0, p1, p2 (each at the lane's first pixel).  ODD: the row's parity
+// ---- k_render1_x16 (the ring and the filter: k_demosaic_dev.h)
+// the 8 pixels of one lane: rows y - 2 .. y + 2 of the ring at m2, m1, c0, p1, p2 (each at the lane's first pixel).  ODD: the row's parity.
+// (demosaic8 of k_demosaic_dev.h is the same filter handing its channels on; routed through it this kernel's registers change)
 template <bool ODD, bool K32, Tone TN>
 __device__ __forceinline__ void develop8(const uint16_t *m2, const uint16_t *m1, const uint16_t *c0, const uint16_t *p1, const uint16_t *p2,
                                          const RenderParams &p, const uint8_t *lut, const LookArg &lk, uint8_t *o)

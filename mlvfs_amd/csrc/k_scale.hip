@@ -31,6 +31,7 @@
 // x16 form keeps its output columns and writes three 16-bit values where it wrote three bytes, so its destination base and stride are
 // 2-byte aligned (an odd one takes the generic kernel); no table in LDS.
 #include "k_tone_dev.h"
+#include "k_scale_dev.h"
 
 namespace mlv {
 
@@ -44,13 +45,6 @@ struct ScaleArgs {             // uniform in a launch
 namespace {                    // this file's device helpers
 
 constexpr int SC_NOUT = SC_STRIP / 256;               // output columns of a lane
-
-// floor(n / d) for every n below 2^32 (scdiv_make, clip.h)
-__device__ __forceinline__ uint32_t sc_div(uint32_t n, const ScDiv &d)
-{
-    const uint32_t t = __umulhi(n, d.m);
-    return (t + ((n - t) >> d.s1)) >> d.s2;
-}
 
 // the three balanced channels of the superpixel in a dword of row 2Y (R low, G high) and the one below it (G low, B high)
 __device__ __forceinline__ void balance3(uint32_t top, uint32_t bot, const Black &bl, const RenderParams &p, uint32_t n[3])

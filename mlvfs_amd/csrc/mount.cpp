@@ -36,6 +36,10 @@
 // mlvfs_amd_mount_rgb_scaled and mlvfs_amd_mount_jpeg_scaled are the half-size routes at ow x oh, at most the half size: each final frame
 // is balanced, area-averaged and developed in one pass (k_scale.hip, the same parameters) into its other slot, exactly where the
 // half-size rendering would lie, and only 3 ow oh bytes or the stream cross the link.  Nothing is allocated for it.
+//
+// mlvfs_amd_mount_rgb_resampled and mlvfs_amd_mount_jpeg_resampled serve ow x oh up to the frame's own size: each final frame is demosaiced,
+// area-averaged and developed in one pass (k_resample.hip, the same parameters).  Such a rendering can exceed the frame's other slot, so
+// it goes into d_full as the full-size ones do, sized for ow x oh.
 #include "clip.h"
 #include "lj92enc.h"
 #include "jpeg.h"
@@ -154,9 +158,10 @@ int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstr
     return MLVFS_AMD_OK;
 }
 
-// which rendering a call serves: half size, the frame's own size, or ow x oh area-averaged from the half-size grid
+// which rendering a call serves: half size, the frame's own size, ow x oh area-averaged from the half-size grid, or ow x oh
+// area-averaged from the full-size rendering
 struct RgbMode {
-    enum Kind { HALF, FULL, SCALED } kind = HALF;
+    enum Kind { HALF, FULL, SCALED, RESAMPLED } kind = HALF;
     int ow = 0, oh = 0;
 };
 
@@ -186,6 +191,7 @@ size_t full_stride(int w, int h, size_t bpx = 3) { return up256(bpx * w * h); }
 // TIFF where that is the smaller file.
 // FULL: at the frame's own size -- the renderings go into d_full, full_stride(w, h) apart, and their streams behind the batch's renderings
 // SCALED: at ow x oh -- developed into the other slots as the half-size ones are, which are never smaller
+// RESAMPLED: at ow x oh up to the frame's size -- into d_full as the full-size ones, full_stride(ow, oh) apart
 // deep: as 16-bit TIFF files through the call's deep look (never m.look, never jp) -- 6 bytes per pixel; 6 W' H' <= 1.5 W H still fits the
 // other slot, and d_full has grown to 6 W H
 int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *h_out,
@@ -193,16 +199,17 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
 {
     hipStream_t s = c->stream;
     uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
-    const bool full = mode.kind == RgbMode::FULL, scaled = mode.kind == RgbMode::SCALED;
+    const bool resampled = mode.kind == RgbMode::RESAMPLED, scaled = mode.kind == RgbMode::SCALED;
+    const bool full = mode.kind == RgbMode::FULL || resampled;                          // the renderings lie in d_full
     int pw = w, ph = h;
-    if (full ? !rgb_full_geom(w, h) : scaled ? !scale_geom(w, h, mode.ow, mode.oh, &pw, &ph) : !rgb_geom(w, h, &pw, &ph)) {
+    if (resampled ? !resample_geom(w, h, mode.ow, mode.oh) : full ? !rgb_full_geom(w, h) : scaled ? !scale_geom(w, h, mode.ow, mode.oh, &pw, &ph) : !rgb_geom(w, h, &pw, &ph)) {
         set_error("mount: a rendering does not take frames of %dx%d", w, h);
         return MLVFS_AMD_ERR_ARG;
     }
-    if (scaled) { pw = mode.ow; ph = mode.oh; }
+    if (scaled || resampled) { pw = mode.ow; ph = mode.oh; }
     const size_t bpx = deep ? 6 : 3;
-    const size_t rstride = full ? full_stride(w, h, bpx) : dstride;                     // from one rendering to the next
-    const size_t sstride = full ? up256(jpg_room(w, h)) : dstride;                      // from one stream to the next
+    const size_t rstride = full ? full_stride(pw, ph, bpx) : dstride;                   // from one rendering to the next
+    const size_t sstride = full ? up256(jpg_room(pw, ph)) : dstride;                    // from one stream to the next
     std::vector<int32_t> &params = m.rgb_host;
     params.resize((size_t)n * 13);
     for (int k = 0; k < n; k++) {
@@ -221,7 +228,8 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         uint8_t *dst = full ? (uint8_t *)m.d_full + k0 * rstride : (in_f ? O : F) + k0 * dstride;
         uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
         const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
-        const int rc = full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
+        const int rc = resampled ? launch_render_resampled(final_at[k0], dstride, par, dst, rstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
+                 : full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
                  : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
                           : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s, lk, deep != nullptr);
         if (rc) return rc;
@@ -536,7 +544,8 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
                        int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0, const RgbMode &mode = RgbMode(),
                        const mlvfs_amd_look16_t *deep = nullptr)
 {
-    const bool full = mode.kind == RgbMode::FULL, scaled = mode.kind == RgbMode::SCALED;
+    const bool resampled = mode.kind == RgbMode::RESAMPLED, scaled = mode.kind == RgbMode::SCALED;
+    const bool full = mode.kind == RgbMode::FULL || resampled;                          // the renderings lie in d_full
     if (!mount || !h_out || ((lossless || jpeg_quality) && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
     Mount &m = *(Mount *)mount;
     if (count < 0) { set_error("mount: negative frame count"); return MLVFS_AMD_ERR_ARG; }
@@ -573,6 +582,11 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             pw = mode.ow;
             ph = mode.oh;
         }
+        if (resampled) {
+            if (!resample_geom(w, h, mode.ow, mode.oh)) { set_error("mount: a resampled rendering of a %dx%d frame is 1x1 up to its own size, 65535 a side at most, not %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
+            pw = mode.ow;
+            ph = mode.oh;
+        }
         size = mlvfs_amd_rgb_header_size() + (size_t)(deep ? 6 : 3) * pw * ph;
         if (out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     }
@@ -586,11 +600,11 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
     scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
     if (lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
-    size_t full_bytes = full ? full_stride(w, h, deep ? 6 : 3) * batch_frames : 0;       // d_full: the batch's renderings ...
+    size_t full_bytes = full ? full_stride(resampled ? mode.ow : w, resampled ? mode.oh : h, deep ? 6 : 3) * batch_frames : 0;   // d_full: the batch's renderings ...
     if (jpeg_quality) {
         int pw = w, ph = h;
         if (!full) (void)rgb_geom(w, h, &pw, &ph);
-        if (scaled) { pw = mode.ow; ph = mode.oh; }
+        if (scaled || resampled) { pw = mode.ow; ph = mode.oh; }
         if (pw > 65535 || ph > 65535) { set_error("mount: a JPEG file takes renderings of up to 65535 a side, not %dx%d", pw, ph); return MLVFS_AMD_ERR_ARG; }
         if (const size_t room = full ? jpg_room(pw, ph) : std::min(jpg_room(pw, ph), dstride))
             scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph)), batch_frames));
@@ -679,6 +693,25 @@ int mlvfs_amd_mount_jpeg_scaled(void *mount, int first, int count, void *h_out, 
                        RgbMode{ RgbMode::SCALED, ow, oh });
 }
 
+int mlvfs_amd_mount_rgb_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh, int batch_frames,
+                                  int io_threads, int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    if (ow < 1 || oh < 1) { set_error("mount: a resampled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0,
+                       RgbMode{ RgbMode::RESAMPLED, ow, oh });
+}
+
+int mlvfs_amd_mount_jpeg_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, int ow, int oh,
+                                   size_t *sizes, int *flags, int batch_frames, int io_threads, int *results)
+{
+    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
+    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
+    if (ow < 1 || oh < 1) { set_error("mount: a resampled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
+    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality,
+                       RgbMode{ RgbMode::RESAMPLED, ow, oh });
+}
+
 // the three 16-bit TIFF calls: what the 8-bit ones check, and the call's deep look
 static int mount_rgb16(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
                        int batch_frames, int io_threads, int *results, const RgbMode &mode)
@@ -686,6 +719,7 @@ static int mount_rgb16(void *mount, int first, int count, void *h_out, size_t ou
     if (!look) { set_error("mount: null argument (a 16-bit rendering takes a deep look)"); return MLVFS_AMD_ERR_ARG; }
     if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
     if (mode.kind == RgbMode::SCALED && (mode.ow < 1 || mode.oh < 1)) { set_error("mount: a scaled rendering of %dx%d", mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
+    if (mode.kind == RgbMode::RESAMPLED && (mode.ow < 1 || mode.oh < 1)) { set_error("mount: a resampled rendering of %dx%d", mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
     return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0, mode, look);
 }
 
@@ -707,6 +741,12 @@ int mlvfs_amd_mount_rgb16_scaled(void *mount, int first, int count, void *h_out,
     return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode{ RgbMode::SCALED, ow, oh });
 }
 
+int mlvfs_amd_mount_rgb16_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
+                                    const mlvfs_amd_look16_t *look, int batch_frames, int io_threads, int *results)
+{
+    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode{ RgbMode::RESAMPLED, ow, oh });
+}
+
 // a 16-bit file has the 8-bit file's header and twice its pixel bytes
 static size_t twice_the_pixels(size_t size8) { return size8 ? 2 * size8 - mlvfs_amd_rgb_header_size() : 0; }
 size_t mlvfs_amd_mount_rgb16_size(const void *mount, int index) { return twice_the_pixels(mlvfs_amd_mount_rgb_size(mount, index)); }
@@ -714,6 +754,24 @@ size_t mlvfs_amd_mount_rgb16_full_size(const void *mount, int index) { return tw
 size_t mlvfs_amd_mount_rgb16_scaled_size(const void *mount, int index, int ow, int oh)
 {
     return twice_the_pixels(mlvfs_amd_mount_rgb_scaled_size(mount, index, ow, oh));
+}
+
+size_t mlvfs_amd_mount_rgb16_resampled_size(const void *mount, int index, int ow, int oh)
+{
+    return twice_the_pixels(mlvfs_amd_mount_rgb_resampled_size(mount, index, ow, oh));
+}
+
+size_t mlvfs_amd_mount_rgb_resampled_size(const void *mount, int index, int ow, int oh)
+{
+    if (!mount) { set_error("mount: null argument"); return 0; }
+    Mount &m = *(Mount *)mount;
+    frame_headers fh;
+    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
+    if (!resample_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh)) {
+        set_error("mount: a resampled rendering of a %dx%d frame is 1x1 up to its own size, 65535 a side at most, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh);
+        return 0;
+    }
+    return mlvfs_amd_rgb_header_size() + (size_t)3 * ow * oh;
 }
 
 size_t mlvfs_amd_mount_rgb_scaled_size(const void *mount, int index, int ow, int oh)
@@ -818,6 +876,88 @@ int mlvfs_amd_test_scale_plan(int width, int height, int ow, int oh, int nframes
     if (!out || nframes < 1 || !scale_geom(width, height, ow, oh, &pw, &ph)) { set_error("test_scale_plan: bad argument"); return MLVFS_AMD_ERR_ARG; }
     const ScalePlan p = scale_plan(pw, ph, ow, oh, nframes);
     const int32_t v[8] = { width % 16 == 0, SC_CHUNK, SC_STRIP, (int32_t)p.uo, (int32_t)p.nstrips, (int32_t)p.bo, (int32_t)p.nbands, SC_BAND_ROWS };
+    std::copy(v, v + 8, out);
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_rgb_fit_full(int width, int height, int box_w, int box_h, int *ow, int *oh)
+{
+    if (!ow || !oh) { set_error("rgb_fit_full: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (box_w < 1 || box_h < 1 || !resample_geom(width, height, 1, 1)) {
+        set_error("rgb_fit_full: a box of %dx%d, or a %dx%d frame that the resampled rendering does not take", box_w, box_h, width, height);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    int64_t fw, fh;
+    if ((int64_t)box_w * height <= (int64_t)box_h * width) {             // the width limits
+        fw = std::min(box_w, width);
+        fh = std::max<int64_t>(1, (2 * fw * height + width) / (2 * (int64_t)width));
+    } else {
+        fh = std::min(box_h, height);
+        fw = std::max<int64_t>(1, (2 * fh * width + height) / (2 * (int64_t)height));
+    }
+    *ow = (int)fw;
+    *oh = (int)fh;
+    return MLVFS_AMD_OK;
+}
+
+// mlvfs_amd_render_resampled_dev and its look and deep forms: render1's checks and the geometry, before any device work
+static int render_resampled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
+                                size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream,
+                                const mlvfs_amd_look16_t *deep = nullptr, bool with_deep = false)
+{
+    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render_resampled: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("render_resampled: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    if (!resample_geom(width, height, ow, oh)) {
+        set_error("render_resampled: %dx%d to %dx%d not supported (4x4 up to 2^25 pixels, 65535 a side; 1x1 up to the frame's size)", width, height, ow, oh);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * ow * oh;
+    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render_resampled: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
+        set_error("render_resampled: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
+    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
+    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
+    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render_resampled: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    LookArg lk;
+    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
+    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
+    return launch_render_resampled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c),
+                                   with_look || with_deep ? &lk : nullptr, with_deep);
+}
+
+int mlvfs_amd_render_resampled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                   void *d_out, size_t out_stride, int nframes, void *stream)
+{
+    return render_resampled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream);
+}
+
+int mlvfs_amd_render_resampled_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                        void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
+{
+    return render_resampled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, look, true, stream);
+}
+
+int mlvfs_amd_render_resampled_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                        void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
+{
+    return render_resampled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream, look, true);
+}
+
+/* test hook, host only: how launch_render_resampled would divide a launch among workgroups */
+int mlvfs_amd_test_resample_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8])
+{
+    if (!out || nframes < 1 || !resample_geom(width, height, ow, oh)) { set_error("test_resample_plan: bad argument"); return MLVFS_AMD_ERR_ARG; }
+    int32_t v[8] = { 0, RS_STRIP, 0, 0, 0, 0, RS_BAND_ROWS, RS_ROWS };
+    if (resample_fast_geom(width, ow)) {
+        const ResamplePlan p = resample_plan(width, height, ow, oh, nframes);
+        v[0] = 1; v[2] = (int32_t)p.uo; v[3] = (int32_t)p.nstrips; v[4] = (int32_t)p.bo; v[5] = (int32_t)p.nbands;
+    }
     std::copy(v, v + 8, out);
     return MLVFS_AMD_OK;
 }

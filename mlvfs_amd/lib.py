@@ -80,6 +80,9 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_rgb16_header", "mlvfs_amd_render2_deep_dev", "mlvfs_amd_render1_deep_dev", "mlvfs_amd_render_scaled_deep_dev",
     "mlvfs_amd_mount_rgb16", "mlvfs_amd_mount_rgb16_full", "mlvfs_amd_mount_rgb16_scaled",
     "mlvfs_amd_mount_rgb16_size", "mlvfs_amd_mount_rgb16_full_size", "mlvfs_amd_mount_rgb16_scaled_size",
+    "mlvfs_amd_rgb_fit_full", "mlvfs_amd_render_resampled_dev", "mlvfs_amd_render_resampled_look_dev", "mlvfs_amd_render_resampled_deep_dev",
+    "mlvfs_amd_mount_rgb_resampled", "mlvfs_amd_mount_jpeg_resampled", "mlvfs_amd_mount_rgb16_resampled",
+    "mlvfs_amd_mount_rgb_resampled_size", "mlvfs_amd_mount_rgb16_resampled_size", "mlvfs_amd_test_resample_plan",
 ]
 
 
@@ -322,6 +325,16 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_mount_rgb16_size", sz, [vp, i])
     sig("mlvfs_amd_mount_rgb16_full_size", sz, [vp, i])
     sig("mlvfs_amd_mount_rgb16_scaled_size", sz, [vp, i, i, i])
+    sig("mlvfs_amd_rgb_fit_full", i, [i, i, i, i, C.POINTER(i), C.POINTER(i)])
+    sig("mlvfs_amd_render_resampled_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp])
+    sig("mlvfs_amd_render_resampled_look_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_render_resampled_deep_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_mount_rgb_resampled", i, [vp, i, i, vp, sz, i, i, i, i, i, vp])
+    sig("mlvfs_amd_mount_jpeg_resampled", i, [vp, i, i, vp, sz, i, i, i, i, vp, vp, i, i, vp])
+    sig("mlvfs_amd_mount_rgb16_resampled", i, [vp, i, i, vp, sz, i, i, i, vp, i, i, vp])
+    sig("mlvfs_amd_mount_rgb_resampled_size", sz, [vp, i, i, i])
+    sig("mlvfs_amd_mount_rgb16_resampled_size", sz, [vp, i, i, i])
+    sig("mlvfs_amd_test_resample_plan", i, [i, i, i, i, i, vp])
     _lib = L
     return L
 

@@ -128,8 +128,10 @@ class Mount:
         return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
 
     @staticmethod
-    def _size_arg(size, full: bool):
+    def _size_arg(size, full: bool, resample: bool = False):
         """(ow, oh) of a size= argument, or None"""
+        if resample and (size is None or full):
+            raise ValueError("resample=True takes a size= and no full=True")
         if size is None:
             return None
         if full:
@@ -137,14 +139,17 @@ class Mount:
         ow, oh = size
         return int(ow), int(oh)
 
-    def rgb_size(self, index: int = 0, full: bool = False, size=None, bits: int = 8) -> int:
+    def rgb_size(self, index: int = 0, full: bool = False, size=None, bits: int = 8, resample: bool = False) -> int:
         """bytes of file `index` as rgb() serves it: the TIFF header + 3 * (W // 2) * (H // 2); full: + 3 * W * H; size=(ow, oh):
-        + 3 * ow * oh; bits=16: as rgb(look16=...) serves it, twice the pixel bytes"""
+        + 3 * ow * oh, up to the half size, or with resample=True up to the frame's; bits=16: as rgb(look16=...) serves it, twice the
+        pixel bytes"""
         if bits not in (8, 16):
             raise ValueError(f"{bits} bits per sample (8 or 16)")
-        size = self._size_arg(size, full)
+        size = self._size_arg(size, full, resample)
         L, deep = self.L, bits == 16
-        if size is not None:
+        if resample:
+            size = int((L.mlvfs_amd_mount_rgb16_resampled_size if deep else L.mlvfs_amd_mount_rgb_resampled_size)(self.h, index, *size))
+        elif size is not None:
             size = int((L.mlvfs_amd_mount_rgb16_scaled_size if deep else L.mlvfs_amd_mount_rgb_scaled_size)(self.h, index, *size))
         elif full:
             size = int((L.mlvfs_amd_mount_rgb16_full_size if deep else L.mlvfs_amd_mount_rgb_full_size)(self.h, index))
@@ -155,31 +160,41 @@ class Mount:
         return size
 
     def rgb(self, first: int, count: int, gain: float = 1.0, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None,
-            full: bool = False, size=None, look16=None) -> np.ndarray:
+            full: bool = False, size=None, look16=None, resample: bool = False) -> np.ndarray:
         """Frames first .. first + count - 1 rendered to half-size 8-bit sRGB TIFF files: a (count, rgb_size) uint8 array.  gain: the
         exposure factor, in steps of 1 / 256 (gain_q8 = round(256 * gain), 1 .. 65535).  Not on a handle that serves proxies.
         full: at the frame's own size, demosaiced on the GPU (mlvfs_amd/demosaic.py): a (count, rgb_size(full=True)) array.
         size=(ow, oh): at any size up to half the frame's, area-averaged in linear light on the GPU (mlvfs_amd/scale.py): a
         (count, rgb_size(size=size)) array.  Not together with full=True.
+        resample=True with size=(ow, oh): at any size up to the frame's own, area-averaged from the full-size rendering's demosaiced
+        channels (mlvfs_amd/resample.py) -- another rendering than size= alone gives, also where both take the size.
         look16: a mlvfs_amd.look.Look16 -- the same renderings as 16-bit TIFF files toned from 16-bit linear light through that deep look
         (rgb_size(..., bits=16) bytes each).  It is passed per call; set_look() does not touch these files."""
-        size = self._size_arg(size, full)
+        size = self._size_arg(size, full, resample)
         gain_q8 = int(round(256 * gain))
         if not 1 <= gain_q8 <= 65535:
             raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
-        out = np.zeros((count, self.rgb_size(first, full, size, 16 if look16 is not None else 8) if count else 0), np.uint8)
+        out = np.zeros((count, self.rgb_size(first, full, size, 16 if look16 is not None else 8, resample) if count else 0), np.uint8)
         if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
                                         and results.size >= count):
             raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
         res = np.zeros(max(count, 1), np.int32) if results is None else results
         if look16 is not None:
             if size is not None:
+                if resample:
+                    lib.check(self.L.mlvfs_amd_mount_rgb16_resampled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1],
+                                                                     look16.h, batch, io_threads, lib.ptr(res)), "mount_rgb16_resampled")
+                    return out
                 lib.check(self.L.mlvfs_amd_mount_rgb16_scaled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1],
                                                               look16.h, batch, io_threads, lib.ptr(res)), "mount_rgb16_scaled")
                 return out
             call = self.L.mlvfs_amd_mount_rgb16_full if full else self.L.mlvfs_amd_mount_rgb16
             lib.check(call(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, look16.h, batch, io_threads, lib.ptr(res)),
                       "mount_rgb16_full" if full else "mount_rgb16")
+            return out
+        if resample:
+            lib.check(self.L.mlvfs_amd_mount_rgb_resampled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1], batch,
+                                                           io_threads, lib.ptr(res)), "mount_rgb_resampled")
             return out
         if size is not None:
             lib.check(self.L.mlvfs_amd_mount_rgb_scaled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1], batch,
@@ -191,17 +206,18 @@ class Mount:
         return out
 
     def jpeg(self, first: int, count: int, gain: float = 1.0, quality: int = 90, batch: int = 8, io_threads: int = 0,
-             results: np.ndarray | None = None, full: bool = False, size=None):
+             results: np.ndarray | None = None, full: bool = False, size=None, resample: bool = False):
         """The renderings of rgb() as baseline JPEG files of `quality` (1 .. 100), encoded on the GPU:
         -> (files, flags): files[k] the bytes of file k, flags[k] bit 0 set where the JPEG file would be larger than the TIFF and the
-        frame is served as rgb()'s TIFF, byte for byte.  full: the renderings of rgb(full=True); size=(ow, oh): those of rgb(size=size)."""
-        size = self._size_arg(size, full)
+        frame is served as rgb()'s TIFF, byte for byte.  full: the renderings of rgb(full=True); size=(ow, oh): those of rgb(size=size);
+        with resample=True those of rgb(size=size, resample=True)."""
+        size = self._size_arg(size, full, resample)
         gain_q8 = int(round(256 * gain))
         if not 1 <= gain_q8 <= 65535:
             raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
         if not 1 <= quality <= 100:
             raise ValueError(f"quality {quality} outside 1 .. 100")
-        stride = self.rgb_size(first, full, size) if count else 0
+        stride = self.rgb_size(first, full, size, 8, resample) if count else 0
         out = np.zeros((count, stride), np.uint8)
         sizes = np.zeros(max(count, 1), np.uintp)
         flags = np.zeros(max(count, 1), np.int32)
@@ -209,7 +225,10 @@ class Mount:
                                         and results.size >= count):
             raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
         res = np.zeros(max(count, 1), np.int32) if results is None else results
-        if size is not None:
+        if resample:
+            lib.check(self.L.mlvfs_amd_mount_jpeg_resampled(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, size[0], size[1],
+                                                            lib.ptr(sizes), lib.ptr(flags), batch, io_threads, lib.ptr(res)), "mount_jpeg_resampled")
+        elif size is not None:
             lib.check(self.L.mlvfs_amd_mount_jpeg_scaled(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, size[0], size[1],
                                                          lib.ptr(sizes), lib.ptr(flags), batch, io_threads, lib.ptr(res)), "mount_jpeg_scaled")
         else:

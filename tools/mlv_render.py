@@ -4,13 +4,16 @@ as baseline JPEG files encoded on the GPU (mlvfs_amd_mount_jpeg; "rendered frame
 the clip was shot, demosaiced on the GPU (mlvfs_amd_mount_rgb_full, mlvfs_amd_mount_jpeg_full; "rendered full-size sRGB frames");
 --size WxH at any size up to the half size, and --fit WxH at the largest such size inside that box at the frame's aspect, area-averaged in
 linear light on the GPU (mlvfs_amd_mount_rgb_scaled, mlvfs_amd_mount_jpeg_scaled; "rendered frames at any smaller size").
+--resample makes --size and --fit mean the frame's own W x H grid: any size up to the full size, area-averaged from the full-size
+rendering's demosaiced channels (mlvfs_amd_mount_rgb_resampled, mlvfs_amd_mount_jpeg_resampled; "rendered frames resampled from the
+full-size rendering") -- 3584 x 1320 --resample --fit 1920x1080 writes 1920 x 707.
 --lut FILE.cube puts a 3D table, interpolated tetrahedrally on the GPU, in the place of the sRGB curve of every one of these routes
 (mlvfs_amd_mount_set_look; "a look for the rendered frames"); --lut-input says what the table's input axis means: the sRGB value the
 plain rendering would write (the default), linear light, or log2:STOPS -- a pure log curve over that many stops below white.
 --bits 16 writes 16-bit TIFF files toned from 16-bit linear light (mlvfs_amd_mount_rgb16 and its forms; "rendered frames at 16 bits"):
 --lut-input's curve on the 16-bit index (linear: the file holds linear light itself), --lut's table behind it if one is given.
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--jpeg [QUALITY]] [--bits 16] [--lut FILE.cube] [--lut-input srgb|linear|log2:STOPS] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--resample] [--jpeg [QUALITY]] [--bits 16] [--lut FILE.cube] [--lut-input srgb|linear|log2:STOPS] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
@@ -26,7 +29,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mlvfs_amd import look, mlvfile, scale
+from mlvfs_amd import look, mlvfile, resample, scale
 from mlvfs_amd.dark import Dark
 from mlvfs_amd.flat import Flat
 from mlvfs_amd.mount import Mount
@@ -49,6 +52,8 @@ def main() -> int:
     how.add_argument("--full", action="store_true", help="render at full size (a fixed 5x5 linear demosaic) instead of half size")
     how.add_argument("--size", type=wxh, metavar="WxH", help="render at W x H, at most half the frame's size a side (an area average in linear light)")
     how.add_argument("--fit", type=wxh, metavar="WxH", help="render at the largest size inside a box of W x H at the frame's aspect")
+    ap.add_argument("--resample", action="store_true", help="with --size or --fit: any size up to the frame's own, resampled from the full-size "
+                    "rendering (not with --full)")
     ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
     ap.add_argument("--bits", type=int, default=8, choices=(8, 16), help="16: 16-bit TIFF files toned from 16-bit linear light through --lut-input's "
                     "curve (and --lut's table behind it, if given); not with --jpeg")
@@ -75,6 +80,8 @@ def main() -> int:
         ap.error(f"--jpeg {a.jpeg} outside 1 .. 100")
     if a.bits == 16 and a.jpeg:
         ap.error("--bits 16 --jpeg: there are no 16-bit JPEG files")
+    if a.resample and (a.full or not (a.size or a.fit)):
+        ap.error("--resample takes --size or --fit, and no --full")
     cube = deep = None
     if a.lut or a.bits == 16:
         try:
@@ -99,9 +106,10 @@ def main() -> int:
             if not ok:
                 ap.error(f"frame {a.first} has no usable headers")
             try:
+                route = resample if a.resample else scale
                 if a.fit:
-                    size = scale.fit(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *a.fit)
-                scale.geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *size)
+                    size = route.fit(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *a.fit)
+                route.geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *size)
             except ValueError as e:
                 ap.error(str(e))
         names = [os.path.join(a.outdir, f"{stem}_{k:06d}.tif") for k in range(a.first, a.first + count)]
@@ -130,11 +138,11 @@ def main() -> int:
                     n = min(a.batch, count - f0)
                     if a.jpeg:
                         files, flags = m.jpeg(a.first + f0, n, gain=a.gain, quality=a.jpeg, batch=a.batch, io_threads=a.io_threads, full=a.full,
-                                              size=size)
+                                              size=size, resample=a.resample)
                         targets = [names[f0 + k] if flags[k] & 1 else jpgs[f0 + k] for k in range(n)]
                     else:
                         files = [f.tobytes() for f in m.rgb(a.first + f0, n, gain=a.gain, batch=a.batch, io_threads=a.io_threads, full=a.full,
-                                                            size=size, look16=lk16)]
+                                                            size=size, look16=lk16, resample=a.resample)]
                         targets = names[f0:f0 + n]
                     for name, data in zip(targets, files):
                         with open(name, "xb") as out:                       # "x": never over a file that appeared meanwhile
