@@ -398,7 +398,7 @@ int mlvfs_amd_cr2hdr20_batch_dev(const mlvfs_amd_geom_t *geom, void *d_frames, s
                                  int fullres, int use_alias_map, int chroma_smooth, int *results, void *stream);
 void mlvfs_amd_dualiso_reset(void);
 /* gives back the dual-ISO work memory the calling thread holds (it grows with the largest batch and is otherwise kept until the
- * thread ends) */
+ * thread ends), and the work memory of its AMaZE renderings (mlvfs_amd_render1_amaze_dev) */
 void mlvfs_amd_dualiso_trim(void);
 /* the global decisions of the calling thread's last conversion: {RGGB?, is_bright[0..3] as bits 3..0, white, white of the bright
  * rows (20 bit), a, b of the exposure fit (hdr.c:638-823), ISO difference in EV, darkened white} */
@@ -1179,6 +1179,65 @@ size_t mlvfs_amd_mount_rgb16_resampled_size(const void *mount, int index, int ow
  * a step }; the four numbers of the plan are 0 where the first is.  A strip's source columns run from floor(us0 W / ow) rounded down
  * to 8 up to ceil(us1 W / ow) rounded up to 8; a band's source rows from floor(v0 H / oh) up to ceil(v1 H / oh).                  */
 int    mlvfs_amd_test_resample_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8]);
+
+/* -- rendered full-size frames demosaiced by AMaZE (csrc/k_amaze_render.hip, csrc/amaze_render.cpp) -------------------- */
+/* The full-size rendering with the library's AMaZE (csrc/k_amaze.hip, csrc/k_amaze_rows.hip: amaze_demosaic_RT.c bit for bit) in the
+ * place of the Malvar-He-Cutler filter.  The definition is this project's, integers but for AMaZE itself (mlvfs_amd/amaze_render.py):
+ * Geometry.  W a multiple of 4, W >= 36, H >= 36 (what mlvfs_amd_amaze_demosaic_dev takes) and W H < 2^25.  Anything else is
+ *   MLVFS_AMD_ERR_ARG before any device work; no such frame is ever served by the linear filter instead.
+ * 1. b(y, x) = min((max(in(y, x) - black, 0) A_j + 2048) >> 12, 65535), j = (y & 1) + (x & 1): the full-size definition's step 1.
+ *    raw(y, x) = b(y, x) as binary32, which is exact.
+ * 2. (R, G, B) = AMaZE(raw): amaze_demosaic_RT.c:113 as hdr.c calls it, winx = winy = 0, the 65535 scale, output planes zero beforehand.
+ * 3. n_c = (int)floor(clampf(v_c) + 0.5f) in binary32, c = R, G, B; clampf(v) = 0 for NaN and v <= 0, 65535 for v >= 65535, v otherwise.
+ * 4. The half-size definition's steps 3 and 4 on n, in each of the three tone forms: the sRGB table, a look, a deep look with 16-bit
+ *    samples; both forms of the matrix give the same result.
+ * The file: the full-size routes', byte for byte in its header.  Not applied, as before: the deflicker's exposure bias, and any crop.
+ * Not built: AMaZE behind the half-size, scaled or resampled routes, other CFA orders, highlight recovery.                          */
+/* *pw = width, *ph = height for a frame the route takes.  Host code.  MLVFS_AMD_ERR_ARG, with the outputs untouched: a null pointer,
+ * a frame outside the geometry above.                                                                                              */
+int    mlvfs_amd_rgb_amaze_geom(int width, int height, int *pw, int *ph);
+/* Step 1: nframes frames of width x height 16-bit pixels `stride` bytes apart -> their float planes, plane_stride floats apart, frame k
+ * with the 13 parameters d_params[13 k ..] (of which black and A are read).  Floats between planes are not touched.  Asynchronous on
+ * `stream`; every check happens before any device work: null pointers, the geometry, an odd source address or stride, parameters or
+ * planes off a 4-byte boundary, strides smaller than a frame or a plane, planes that overlap the source or the parameters.  width a
+ * multiple of 16 with source base and stride and plane base and stride 16-byte aligned takes the fast form (k_amz_balance_x16: 8
+ * pixels per lane, one 16-byte load, two 16-byte stores), anything else one pixel per lane (k_amz_balance_generic).                    */
+int    mlvfs_amd_amaze_balance_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, float *d_planes,
+                                   size_t plane_stride, int nframes, void *stream);
+/* Steps 3 and 4: three batches of nframes float planes, plane_stride floats apart -> interleaved RGB, 3 W H bytes per frame, out_stride
+ * bytes apart; with look16 set 6 W H bytes of 16-bit samples.  look and look16 may each be null (both null: the sRGB table), never both
+ * set.  Bytes between renderings and behind a rendering are not touched.  Asynchronous on `stream`; every check happens before any
+ * device work: null planes, parameters or destination, the geometry, planes or parameters off a 4-byte boundary, strides too small, a
+ * destination that overlaps a plane or the parameters.  width a multiple of 16 with plane bases and stride 16-byte aligned and the
+ * destination base and stride 8-byte aligned (16-byte with look16) takes the fast form (k_amz_tone_x16 and its look and deep forms:
+ * 8 pixels per lane, 24 bytes as three 8-byte stores or 48 as three 16-byte stores), anything else one pixel per lane.               */
+int    mlvfs_amd_amaze_tone_dev(const float *d_red, const float *d_green, const float *d_blue, size_t plane_stride, int width, int height,
+                                const int32_t *d_params, void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look,
+                                const mlvfs_amd_look16_t *look16, void *stream);
+/* mlvfs_amd_render1_dev, mlvfs_amd_render1_look_dev and mlvfs_amd_render1_deep_dev with AMaZE as the demosaic: the same arguments and
+ * the same checks with this route's geometry.  Each runs step 1, the library's AMaZE for the batch, then steps 3 and 4.  Work memory:
+ * four float planes and AMaZE's tile planes per frame, 0.71 GB per frame at 3584 x 1320, held per host thread and device, grown on
+ * demand, given back by mlvfs_amd_dualiso_trim.  A batch that would need more than 6 GiB, or more than can be allocated, runs in
+ * sub-batches; a call fails with MLVFS_AMD_ERR_HIP only where one frame's work memory cannot be had.  The tile planes are this
+ * route's own and are zeroed when they are allocated anew or serve another geometry: a dual-ISO conversion and an AMaZE rendering on
+ * one thread never see each other's.  Calls of one thread on different streams are the caller's to order: they share that memory.   */
+int    mlvfs_amd_render1_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                                   size_t out_stride, int nframes, void *stream);
+int    mlvfs_amd_render1_amaze_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                                        size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream);
+int    mlvfs_amd_render1_amaze_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
+                                        size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream);
+/* Which demosaic mlvfs_amd_mount_rgb_full, mlvfs_amd_mount_jpeg_full and mlvfs_amd_mount_rgb16_full use: 0 the linear filter (the
+ * default), 1 AMaZE.  No serve-order state: it may change between serving calls, as the look may.  The same stages, results[], flags and
+ * look handling; the renderings lie where the linear ones lie and the JPEG encoder takes them there.  With 1 set:
+ * mlvfs_amd_mount_rgb_full_size is 0 for a frame outside the geometry above and the three calls refuse it; the _resampled calls are
+ * refused with MLVFS_AMD_ERR_ARG; every other call serves what it served.  A handle that never calls this serves byte for byte and
+ * launch for launch what it served before.  MLVFS_AMD_ERR_ARG: a null handle, another value.                                          */
+int    mlvfs_amd_mount_set_demosaic(void *mount, int which);
+/* Test hook, host only: how a batch of nframes frames is cut to fit cap_bytes of work memory (0: the library's 6 GiB) -- out = { floats
+ * from one plane to the next, floats of a frame's tile planes, bytes of work memory per frame, frames of a sub-batch (at least 1, at
+ * most nframes) }.  MLVFS_AMD_ERR_ARG: null, nframes below 1, a frame outside the geometry.                                          */
+int    mlvfs_amd_test_amaze_render_plan(int width, int height, int nframes, size_t cap_bytes, int64_t out[4]);
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);

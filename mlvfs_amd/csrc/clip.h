@@ -288,6 +288,16 @@ int launch_render2(const void *d_frames, size_t stride, const int32_t *d_params,
 inline bool rgb_full_geom(int w, int h) { return w >= 4 && h >= 4 && (uint64_t)w * (uint64_t)h < (1u << 25); }
 int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int nframes,
                    hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
+// rendered full-size frames demosaiced by AMaZE (k_amaze_render.hip, amaze_render.cpp): the frames AMaZE takes -- a width that is a
+// multiple of 4, 36 x 36 and more -- below 2^25 pixels; the two element-wise passes around amaze_launch; the three passes for a batch,
+// in sub-batches that fit the calling thread's work memory (lk, deep: launch_render1's)
+inline bool rgb_amaze_geom(int w, int h) { return (w & 3) == 0 && w >= 36 && h >= 36 && (uint64_t)w * (uint64_t)h < (1u << 25); }
+int launch_amz_balance(const void *d_frames, size_t stride, const int32_t *d_params, float *d_planes, size_t plane_stride, int w, int h,
+                       int nframes, hipStream_t stream);
+int launch_amz_tone(const float *d_red, const float *d_green, const float *d_blue, size_t plane_stride, const int32_t *d_params, void *d_out,
+                    size_t out_stride, int w, int h, int nframes, hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
+int launch_render1_amaze(ThreadCtx *c, const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h,
+                         int nframes, hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
 // rendered frames at any smaller size (k_scale.hip): W' x H' of a w x h frame as rgb_geom gives them, false where a side of that grid
 // exceeds 65535 or ow x oh is not 1x1 up to W' x H'; the scaling pass, with the same parameters
 inline bool scale_geom(int w, int h, int ow, int oh, int *pw, int *ph)

@@ -854,6 +854,7 @@ void mlvfs_amd_dualiso_trim(void)
     for (auto &kv : t_amaze_slots) { kv.second.buf.release(); kv.second.w = kv.second.H = 0; kv.second.slot_h.clear(); }
     for (auto &kv : t_amaze) { kv.second.buf.release(); kv.second.w = kv.second.h = 0; }
     for (auto &kv : t_pinned) kv.second.release();
+    amaze_render_trim();
 }
 
 // test hook: forget the per-black table caches, as a fresh process would

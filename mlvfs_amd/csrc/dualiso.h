@@ -105,6 +105,16 @@ int amaze_launch(const float *d_raw, int w, int h, float *d_red, float *d_green,
 // d_r2e: the three plane pointers are INT planes and take interp_raw2ev of the clamped plane values, d_gray that of the gray value
 // (amaze_math.h, ev_of_planes)
 size_t amaze_scratch_bytes(int w, int h);
+// the tiles amaze_scratch_bytes counts, AMAZE_TILE_FLOATS each, for host code that sizes work memory without the kernel files
+// (amaze_render.cpp, which checks the two against each other before it launches)
+inline size_t amaze_tiles(int w, int h)
+{
+    const size_t step = AMAZE_TS - 32;
+    return ((size_t)w + 16 + step - 1) / step * (((size_t)h + 16 + step - 1) / step);
+}
+// the AMaZE renderings' work memory (amaze_render.cpp): the calling thread's planes and tile planes on every device, a buffer pair of
+// its own that no dual-ISO conversion reads or writes; mlvfs_amd_dualiso_trim gives it back too
+void amaze_render_trim();
 // k_amaze_rows.hip: the complete tiles (the first nfx x nfy of the tile grid), row-streamed through LDS
 extern int g_amaze_rows_mode;
 extern int g_amaze_rows_extra_mode;

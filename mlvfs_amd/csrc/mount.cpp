@@ -40,6 +40,10 @@
 // mlvfs_amd_mount_rgb_resampled and mlvfs_amd_mount_jpeg_resampled serve ow x oh up to the frame's own size: each final frame is demosaiced,
 // area-averaged and developed in one pass (k_resample.hip, the same parameters).  Such a rendering can exceed the frame's other slot, so
 // it goes into d_full as the full-size ones do, sized for ow x oh.
+//
+// mlvfs_amd_mount_set_demosaic(1): the three full-size calls demosaic with AMaZE (amaze_render.cpp: balance, amaze_launch, tone, in the
+// calling thread's work memory) instead of k_demosaic.hip's linear filter; the renderings lie in d_full as before and everything behind
+// them -- the JPEG encoder, the headers, the copies -- is the same.  No other call knows.
 #include "clip.h"
 #include "lj92enc.h"
 #include "jpeg.h"
@@ -65,6 +69,7 @@ struct Mount {
     const mlvfs_amd_look_t *look = nullptr;  // step 4 of every rendering (mlvfs_amd_mount_set_look); no serve-order state: it may change between calls
     bool served = false;                     // a call has reached the device: the dark frame, the flat field and the proxy stay what they are
     int proxy = 1;                           // mlvfs_amd_mount_set_proxy: 2 = the served frames are binned to half size
+    int demosaic = 0;                        // mlvfs_amd_mount_set_demosaic: 1 = the full-size calls demosaic with AMaZE; no serve-order state
     int device = -1;
     DevBuf d_frames, d_out, d_scratch;
     DevBuf d_bits;                           // the encoder's bit streams, sized from a batch's histograms
@@ -201,7 +206,9 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
     uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
     const bool resampled = mode.kind == RgbMode::RESAMPLED, scaled = mode.kind == RgbMode::SCALED;
     const bool full = mode.kind == RgbMode::FULL || resampled;                          // the renderings lie in d_full
+    const bool amaze = m.demosaic == 1 && mode.kind == RgbMode::FULL;
     int pw = w, ph = h;
+    if (amaze && !rgb_amaze_geom(w, h)) { set_error("mount: an AMaZE rendering does not take frames of %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
     if (resampled ? !resample_geom(w, h, mode.ow, mode.oh) : full ? !rgb_full_geom(w, h) : scaled ? !scale_geom(w, h, mode.ow, mode.oh, &pw, &ph) : !rgb_geom(w, h, &pw, &ph)) {
         set_error("mount: a rendering does not take frames of %dx%d", w, h);
         return MLVFS_AMD_ERR_ARG;
@@ -229,6 +236,7 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
         const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
         const int rc = resampled ? launch_render_resampled(final_at[k0], dstride, par, dst, rstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
+                 : amaze ? launch_render1_amaze(c, final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
                  : full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
                  : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
                           : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s, lk, deep != nullptr);
@@ -490,6 +498,16 @@ int mlvfs_amd_mount_set_look(void *mount, const mlvfs_amd_look_t *look)
     return MLVFS_AMD_OK;
 }
 
+int mlvfs_amd_mount_set_demosaic(void *mount, int which)
+{
+    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (which != 0 && which != 1) { set_error("mount: a demosaic of %d (0: the linear filter, 1: AMaZE)", which); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    std::lock_guard<std::mutex> lk(m.mu);                // between serving calls: a call in flight holds the mutex
+    m.demosaic = which;
+    return MLVFS_AMD_OK;
+}
+
 size_t mlvfs_amd_mount_dng_size(const void *mount, int index)
 {
     if (!mount) { set_error("mount: null argument"); return 0; }
@@ -576,6 +594,8 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         if (m.proxy == 2) { set_error("mount: a handle that serves proxies does not render"); return MLVFS_AMD_ERR_ARG; }
         int pw = w, ph = h;
         if (full && !rgb_full_geom(w, h)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+        if (m.demosaic == 1 && resampled) { set_error("mount: with AMaZE set (mlvfs_amd_mount_set_demosaic) the resampled calls are not served"); return MLVFS_AMD_ERR_ARG; }
+        if (m.demosaic == 1 && full && !rgb_amaze_geom(w, h)) { set_error("mount: an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         if (!full && !rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         if (scaled) {
             if (!scale_geom(w, h, mode.ow, mode.oh, &pw, &ph)) { set_error("mount: a scaled rendering of a %dx%d frame is 1x1 up to its half size, 65535 a side at most, not %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
@@ -969,6 +989,12 @@ size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index)
     frame_headers fh;
     if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
     if (!rgb_full_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
+    int demosaic;
+    {
+        std::lock_guard<std::mutex> lk(m.mu);
+        demosaic = m.demosaic;
+    }
+    if (demosaic == 1 && !rgb_amaze_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) { set_error("mount: an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
     return mlvfs_amd_rgb_header_size() + (size_t)3 * fh.rawi_hdr.xRes * fh.rawi_hdr.yRes;
 }
 

@@ -83,6 +83,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_rgb_fit_full", "mlvfs_amd_render_resampled_dev", "mlvfs_amd_render_resampled_look_dev", "mlvfs_amd_render_resampled_deep_dev",
     "mlvfs_amd_mount_rgb_resampled", "mlvfs_amd_mount_jpeg_resampled", "mlvfs_amd_mount_rgb16_resampled",
     "mlvfs_amd_mount_rgb_resampled_size", "mlvfs_amd_mount_rgb16_resampled_size", "mlvfs_amd_test_resample_plan",
+    "mlvfs_amd_rgb_amaze_geom", "mlvfs_amd_amaze_balance_dev", "mlvfs_amd_amaze_tone_dev", "mlvfs_amd_render1_amaze_dev",
+    "mlvfs_amd_render1_amaze_look_dev", "mlvfs_amd_render1_amaze_deep_dev", "mlvfs_amd_mount_set_demosaic", "mlvfs_amd_test_amaze_render_plan",
 ]
 
 
@@ -335,6 +337,14 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_mount_rgb_resampled_size", sz, [vp, i, i, i])
     sig("mlvfs_amd_mount_rgb16_resampled_size", sz, [vp, i, i, i])
     sig("mlvfs_amd_test_resample_plan", i, [i, i, i, i, i, vp])
+    sig("mlvfs_amd_rgb_amaze_geom", i, [i, i, C.POINTER(i), C.POINTER(i)])
+    sig("mlvfs_amd_amaze_balance_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp])
+    sig("mlvfs_amd_amaze_tone_dev", i, [vp, vp, vp, sz, i, i, vp, vp, sz, i, vp, vp, vp])
+    sig("mlvfs_amd_render1_amaze_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp])
+    sig("mlvfs_amd_render1_amaze_look_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_render1_amaze_deep_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_mount_set_demosaic", i, [vp, i])
+    sig("mlvfs_amd_test_amaze_render_plan", i, [i, i, i, sz, vp])
     _lib = L
     return L
 

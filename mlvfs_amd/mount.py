@@ -21,6 +21,9 @@
     files, flags = m.jpeg(0, 16, gain=1.0, quality=90) serves the same renderings as baseline JPEG files encoded on the GPU, a tenth
     of the bytes (include/mlvfs_amd.h, "rendered frames as baseline JPEG files"; mlvfs_amd/jpeg.py is the definition in numpy).
 
+    m.set_demosaic("amaze") makes the full-size calls demosaic with AMaZE instead of the linear filter (include/mlvfs_amd.h, "rendered
+    full-size frames demosaiced by AMaZE"; mlvfs_amd/amaze_render.py is the definition).
+
 Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
 """
 from __future__ import annotations
@@ -58,6 +61,7 @@ class Mount:
         self.frame_count = self.L.mlvfs_amd_mlv_frame_count(handle)
         self._dark = self._flat = self._look = None
         self.proxy = 1
+        self.demosaic = "linear"
         try:
             if dark is not None:
                 self.set_dark(dark)
@@ -86,6 +90,18 @@ class Mount:
         any time between calls; dng(), dng_lossless(), the proxies and rgb(look16=...) never see it.  It must stay open while it is set."""
         lib.check(self.L.mlvfs_amd_mount_set_look(self.h, None if look is None else look.h), "mount_set_look")
         self._look = look
+
+    DEMOSAICS = {"linear": 0, "amaze": 1}
+
+    def set_demosaic(self, which: str) -> None:
+        """which: "linear", the Malvar-He-Cutler filter (the default), or "amaze", the AMaZE demosaic (mlvfs_amd/amaze_render.py), in
+        every later rgb(full=True), jpeg(full=True) and rgb(full=True, look16=...) call.  Allowed at any time between calls; no other
+        call sees it, but with "amaze" set the resample=True calls are refused, and so are frames AMaZE does not take (a width that is
+        no multiple of 4, a side below 36)."""
+        if which not in self.DEMOSAICS:
+            raise ValueError(f'demosaic {which!r} ("linear" or "amaze")')
+        lib.check(self.L.mlvfs_amd_mount_set_demosaic(self.h, self.DEMOSAICS[which]), "mount_set_demosaic")
+        self.demosaic = which
 
     def set_proxy(self, factor: int) -> None:
         """factor 2: every frame is served binned to half size, 2 * (W // 4) x 2 * (H // 4), after all other stages; 1: off.  Refused
