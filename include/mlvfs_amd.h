@@ -1192,7 +1192,8 @@ int    mlvfs_amd_test_resample_plan(int width, int height, int ow, int oh, int n
  * 4. The half-size definition's steps 3 and 4 on n, in each of the three tone forms: the sRGB table, a look, a deep look with 16-bit
  *    samples; both forms of the matrix give the same result.
  * The file: the full-size routes', byte for byte in its header.  Not applied, as before: the deflicker's exposure bias, and any crop.
- * Not built: AMaZE behind the half-size, scaled or resampled routes, other CFA orders, highlight recovery.                          */
+ * Not built: AMaZE behind the half-size or scaled routes, other CFA orders, highlight recovery.  AMaZE behind the resampled route is
+ * the next section's.                                                                                                              */
 /* *pw = width, *ph = height for a frame the route takes.  Host code.  MLVFS_AMD_ERR_ARG, with the outputs untouched: a null pointer,
  * a frame outside the geometry above.                                                                                              */
 int    mlvfs_amd_rgb_amaze_geom(int width, int height, int *pw, int *ph);
@@ -1231,13 +1232,63 @@ int    mlvfs_amd_render1_amaze_deep_dev(const void *d_frames, size_t stride, int
  * default), 1 AMaZE.  No serve-order state: it may change between serving calls, as the look may.  The same stages, results[], flags and
  * look handling; the renderings lie where the linear ones lie and the JPEG encoder takes them there.  With 1 set:
  * mlvfs_amd_mount_rgb_full_size is 0 for a frame outside the geometry above and the three calls refuse it; the _resampled calls are
- * refused with MLVFS_AMD_ERR_ARG; every other call serves what it served.  A handle that never calls this serves byte for byte and
+ * refused with MLVFS_AMD_ERR_ARG unless mlvfs_amd_mount_set_resample_demosaic(mount, 1) has given them AMaZE of their own (the next
+ * section); every other call serves what it served.  A handle that never calls this serves byte for byte and
  * launch for launch what it served before.  MLVFS_AMD_ERR_ARG: a null handle, another value.                                          */
 int    mlvfs_amd_mount_set_demosaic(void *mount, int which);
 /* Test hook, host only: how a batch of nframes frames is cut to fit cap_bytes of work memory (0: the library's 6 GiB) -- out = { floats
  * from one plane to the next, floats of a frame's tile planes, bytes of work memory per frame, frames of a sub-batch (at least 1, at
  * most nframes) }.  MLVFS_AMD_ERR_ARG: null, nframes below 1, a frame outside the geometry.                                          */
 int    mlvfs_amd_test_amaze_render_plan(int width, int height, int nframes, size_t cap_bytes, int64_t out[4]);
+
+/* -- resampled rendered frames demosaiced by AMaZE (csrc/k_amaze_resample.hip, csrc/amaze_render.cpp) ----------------- */
+/* The resampled rendering with AMaZE as its source: the two definitions above composed, with no arithmetic of its own
+ * (mlvfs_amd/amaze_resample.py):
+ * Geometry.  W a multiple of 4, W >= 36, H >= 36, W H < 2^25 (the AMaZE rendering's) and W, H <= 65535; 1 <= ow <= W, 1 <= oh <= H, the
+ *   two factors independent, never larger than the frame.  Anything else is MLVFS_AMD_ERR_ARG before any device work; no such frame is
+ *   ever served by the linear filter instead.
+ * 1. - 3. The AMaZE rendering's: every site balanced, raw = float32(b), (R, G, B) = AMaZE(raw), n_c = (int)floor(clampf(v_c) + 0.5f).
+ * 4. The resampled rendering's average on n in the place of d, horizontally first, each pass rounded on its own:
+ *    hd_c(y, u) = floor((sum_x wx(u, x) n_c(y, x) + (W >> 1)) / W), m_c(v, u) = floor((sum_y wy(v, y) hd_c(y, u) + (H >> 1)) / H).
+ * 5. The half-size definition's steps 3 and 4 on m, in each of the three tone forms.
+ * The file: mlvfs_amd_rgb_header(ow, oh) or its 16-bit form.  ow = W, oh = H is the AMaZE full-size rendering byte for byte.
+ * Not built: AMaZE behind the half-size and scaled routes (they average superpixels and have no demosaic), enlarging.              */
+/* MLVFS_AMD_OK for a frame and a size the route takes, MLVFS_AMD_ERR_ARG otherwise.  Host code.  mlvfs_amd_rgb_fit_full gives the
+ * fitted size.                                                                                                                     */
+int    mlvfs_amd_rgb_amaze_resample_geom(int width, int height, int ow, int oh);
+/* Steps 3 to 5 alone, on a caller's planes: mlvfs_amd_amaze_tone_dev's arguments and checks plus the size, 3 ow oh bytes per frame (6
+ * with look16).  Every check happens before any device work and follows no pointer.  width a multiple of 8 with 2 ow >= width, plane
+ * bases and stride 16-byte aligned and, with look16, a 2-byte aligned destination base and stride takes the fast form
+ * (k_amz_resample_x16 and its look and deep forms: strips and bands as mlvfs_amd_test_amz_resample_plan reports them), anything else
+ * one output pixel per lane (k_amz_resample_generic and its forms).                                                                 */
+int    mlvfs_amd_amaze_resample_dev(const float *d_red, const float *d_green, const float *d_blue, size_t plane_stride, int width, int height,
+                                    const int32_t *d_params, int ow, int oh, void *d_out, size_t out_stride, int nframes,
+                                    const mlvfs_amd_look_t *look, const mlvfs_amd_look16_t *look16, void *stream);
+/* mlvfs_amd_render_resampled_dev, _look_dev and _deep_dev with AMaZE as the demosaic: the same arguments, mlvfs_amd_render1_amaze_dev's
+ * checks with this route's geometry, its work memory with its zeroing rule, its sub-batches and its halving on a failed reservation.
+ * Each runs step 1, the library's AMaZE for the batch, then steps 3 to 5 in one pass.                                               */
+int    mlvfs_amd_render_resampled_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                            void *d_out, size_t out_stride, int nframes, void *stream);
+int    mlvfs_amd_render_resampled_amaze_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow,
+                                                 int oh, void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream);
+int    mlvfs_amd_render_resampled_amaze_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow,
+                                                 int oh, void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look,
+                                                 void *stream);
+/* Which demosaic mlvfs_amd_mount_rgb_resampled, mlvfs_amd_mount_jpeg_resampled and mlvfs_amd_mount_rgb16_resampled use: 0 the linear
+ * filter (the default), 1 AMaZE.  No serve-order state: it may change between serving calls.  With 1 set, whatever
+ * mlvfs_amd_mount_set_demosaic says: the three calls render through this section's route, with the resampled route's placement,
+ * growth, JPEG encoding, fallback flag, results[], sizes[] and look handling; mlvfs_amd_mount_rgb_resampled_size and
+ * mlvfs_amd_mount_rgb16_resampled_size are 0 for a frame AMaZE does not take and the three calls refuse it.  With 0 nothing changes,
+ * the refusal of the three calls under mlvfs_amd_mount_set_demosaic(mount, 1) included.  A handle that never calls this serves byte
+ * for byte and launch for launch what it served before.  MLVFS_AMD_ERR_ARG: a null handle, another value.                            */
+int    mlvfs_amd_mount_set_resample_demosaic(void *mount, int which);
+/* Test hook, host only: how a launch of nframes frames is divided among k_amz_resample_x16's workgroups -- out = { 1 where the sizes
+ * allow the fast form (width % 8 == 0 and 2 ow >= width; the alignment is the caller's), the most source columns of a strip, uo: the
+ * output columns of a strip, the strips, bo: the output rows of a band, the bands, the source rows a band covers at least, the source
+ * rows of a step }; the four numbers of the plan are 0 where the first is.  Strip k begins at output column k uo, band k at output row
+ * k bo: those are the seams.  A strip's source columns run from floor(us0 W / ow) rounded down to 8 up to ceil(us1 W / ow) rounded up
+ * to 8; a band's source rows from floor(v0 H / oh) up to ceil(v1 H / oh), walked a step at a time from the first.                   */
+int    mlvfs_amd_test_amz_resample_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8]);
 
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);

@@ -1,6 +1,8 @@
 // amaze_render.cpp -- rendered full-size frames with AMaZE as the demosaic (include/mlvfs_amd.h, "rendered full-size frames demosaiced
 // by AMaZE"): the geometry, the work memory and its sub-batches, the three passes of a batch (k_amaze_render.hip's balance,
 // amaze_launch of k_amaze.hip / k_amaze_rows.hip as it is, k_amaze_render.hip's tone) and the device entry points with their checks.
+// The resampled form ("resampled rendered frames demosaiced by AMaZE") is the same loop with k_amaze_resample.hip's
+// pass in the place of the tone pass, and has its entry points here too.
 //
 // Work memory, per (host thread, device), grown on demand: four float planes per frame of a sub-batch (raw, red, green, blue, each kind
 // as one batch of planes plane_stride floats apart) and AMaZE's tile planes, amaze_scratch_bytes per frame.  The tile planes are this
@@ -67,13 +69,14 @@ void amaze_render_trim()
     }
 }
 
-// balance -> AMaZE -> tone for nframes frames, `sub` at a time.  A sub-batch that cannot be reserved is halved until one frame is left:
-// a batch fails only where a single frame's work memory cannot be had
-int launch_render1_amaze(ThreadCtx *c, const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h,
-                         int nframes, hipStream_t stream, const LookArg *lk, bool deep)
+namespace {
+
+// balance -> AMaZE -> the last pass for nframes frames, `sub` at a time: the tone pass (ow == 0, the full-size rendering) or the
+// resampling pass to ow x oh.  A sub-batch that cannot be reserved is halved until one frame is left: a batch fails only where a single
+// frame's work memory cannot be had.  The callers check the geometry
+int amaze_batches(ThreadCtx *c, const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
+                  int oh, int nframes, hipStream_t stream, const LookArg *lk, bool deep)
 {
-    if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!rgb_amaze_geom(w, h)) { set_error("an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
     const AmzPlan p = amz_plan(w, h, nframes, AMZ_WORK_CAP);
     if (p.tile_stride * sizeof(float) != amaze_scratch_bytes(w, h)) { set_error("amaze_render: the tile planes of %dx%d are sized wrongly", w, h); return MLVFS_AMD_ERR_ARG; }
     AmzWork &wk = t_amz[c->dev->id];
@@ -90,10 +93,34 @@ int launch_render1_amaze(ThreadCtx *c, const void *d_frames, size_t stride, cons
         const int32_t *par = d_params + (size_t)f0 * 13;
         int rc = launch_amz_balance((const uint8_t *)d_frames + (size_t)f0 * stride, stride, par, raw, p.plane_stride, w, h, n, stream);
         if (!rc) rc = amaze_launch(raw, w, h, red, green, blue, wk.tiles, stream, n, p.plane_stride, p.tile_stride);
-        if (!rc) rc = launch_amz_tone(red, green, blue, p.plane_stride, par, (uint8_t *)d_out + (size_t)f0 * out_stride, out_stride, w, h, n, stream, lk, deep);
+        uint8_t *dst = (uint8_t *)d_out + (size_t)f0 * out_stride;
+        if (!rc) rc = ow ? launch_amz_resample(red, green, blue, p.plane_stride, par, dst, out_stride, w, h, ow, oh, n, stream, lk, deep)
+                         : launch_amz_tone(red, green, blue, p.plane_stride, par, dst, out_stride, w, h, n, stream, lk, deep);
         if (rc) return rc;
     }
     return MLVFS_AMD_OK;
+}
+
+}  // namespace
+
+int launch_render1_amaze(ThreadCtx *c, const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h,
+                         int nframes, hipStream_t stream, const LookArg *lk, bool deep)
+{
+    if (nframes <= 0) return MLVFS_AMD_OK;
+    if (!rgb_amaze_geom(w, h)) { set_error("an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    return amaze_batches(c, d_frames, stride, d_params, d_out, out_stride, w, h, 0, 0, nframes, stream, lk, deep);
+}
+
+// the same loop with the resampling pass behind AMaZE (k_amaze_resample.hip) in the place of the tone pass
+int launch_render_resampled_amaze(ThreadCtx *c, const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w,
+                                  int h, int ow, int oh, int nframes, hipStream_t stream, const LookArg *lk, bool deep)
+{
+    if (nframes <= 0) return MLVFS_AMD_OK;
+    if (!amz_resample_geom(w, h, ow, oh)) {
+        set_error("a resampled AMaZE rendering takes frames of 36x36 up to 2^25 pixels and 65535 a side, the width a multiple of 4, and a size of 1x1 up to the frame's, not %dx%d to %dx%d", w, h, ow, oh);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    return amaze_batches(c, d_frames, stride, d_params, d_out, out_stride, w, h, ow, oh, nframes, stream, lk, deep);
 }
 
 }  // namespace mlv
@@ -132,6 +159,39 @@ int render1_amaze_dev(const void *d_frames, size_t stride, int width, int height
     if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
     return launch_render1_amaze(c, d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c),
                                 with_look || with_deep ? &lk : nullptr, with_deep);
+}
+
+// mlvfs_amd_render_resampled_amaze_dev and its look and deep forms: render1_amaze's checks with this route's geometry, before any device work
+int render_resampled_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
+                               size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream,
+                               const mlvfs_amd_look16_t *deep = nullptr, bool with_deep = false)
+{
+    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render_resampled_amaze: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("render_resampled_amaze: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    if (!amz_resample_geom(width, height, ow, oh)) {
+        set_error("render_resampled_amaze: %dx%d to %dx%d not supported (36x36 up to 2^25 pixels, 65535 a side, the width a multiple of 4; 1x1 up to the frame's size)", width, height, ow, oh);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * ow * oh;
+    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render_resampled_amaze: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
+        set_error("render_resampled_amaze: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    const uintptr_t b0 = (uintptr_t)d_out;
+    const size_t bn = (size_t)(nframes - 1) * out_stride + pimg;
+    if (overlap((uintptr_t)d_frames, (size_t)(nframes - 1) * stride + img, b0, bn) || overlap((uintptr_t)d_params, (size_t)nframes * 13 * sizeof(int32_t), b0, bn)) {
+        set_error("render_resampled_amaze: the destination overlaps the source or the parameters (the rendering does not work in place)");
+        return MLVFS_AMD_ERR_ARG;
+    }
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    LookArg lk;
+    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
+    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
+    return launch_render_resampled_amaze(c, d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c),
+                                         with_look || with_deep ? &lk : nullptr, with_deep);
 }
 
 }  // namespace
@@ -218,6 +278,83 @@ int mlvfs_amd_render1_amaze_deep_dev(const void *d_frames, size_t stride, int wi
                                      size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
 {
     return render1_amaze_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream, look, true);
+}
+
+int mlvfs_amd_rgb_amaze_resample_geom(int width, int height, int ow, int oh)
+{
+    if (!amz_resample_geom(width, height, ow, oh)) {
+        set_error("rgb_amaze_resample_geom: %dx%d to %dx%d not supported (36x36 up to 2^25 pixels, 65535 a side, the width a multiple of 4; 1x1 up to the frame's size)", width, height, ow, oh);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    return MLVFS_AMD_OK;
+}
+
+int mlvfs_amd_amaze_resample_dev(const float *d_red, const float *d_green, const float *d_blue, size_t plane_stride, int width, int height,
+                                 const int32_t *d_params, int ow, int oh, void *d_out, size_t out_stride, int nframes,
+                                 const mlvfs_amd_look_t *look, const mlvfs_amd_look16_t *look16, void *stream)
+{
+    if (!d_red || !d_green || !d_blue || !d_params || !d_out) { set_error("amaze_resample: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (look && look16) { set_error("amaze_resample: a look and a deep look in one call"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("amaze_resample: negative frame count"); return MLVFS_AMD_ERR_ARG; }
+    if (!amz_resample_geom(width, height, ow, oh)) {
+        set_error("amaze_resample: %dx%d to %dx%d not supported (36x36 up to 2^25 pixels, 65535 a side, the width a multiple of 4; 1x1 up to the frame's size)", width, height, ow, oh);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    const size_t npix = (size_t)width * height, pimg = (size_t)(look16 ? 6 : 3) * ow * oh;
+    if ((((uintptr_t)d_red | (uintptr_t)d_green | (uintptr_t)d_blue | (uintptr_t)d_params) & 3)) { set_error("amaze_resample: planes or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
+    if (nframes > 1 && (plane_stride < npix || out_stride < pimg)) {
+        set_error("amaze_resample: strides %zu / %zu too small", plane_stride, out_stride);
+        return MLVFS_AMD_ERR_ARG;
+    }
+    if (nframes == 0) return MLVFS_AMD_OK;
+    const uintptr_t b0 = (uintptr_t)d_out;
+    const size_t bn = (size_t)(nframes - 1) * out_stride + pimg, an = ((size_t)(nframes - 1) * plane_stride + npix) * sizeof(float);
+    if (overlap((uintptr_t)d_red, an, b0, bn) || overlap((uintptr_t)d_green, an, b0, bn) || overlap((uintptr_t)d_blue, an, b0, bn) ||
+        overlap((uintptr_t)d_params, (size_t)nframes * 13 * sizeof(int32_t), b0, bn)) {
+        set_error("amaze_resample: the destination overlaps a plane or the parameters");
+        return MLVFS_AMD_ERR_ARG;
+    }
+    ThreadCtx *c = thread_ctx();
+    if (!c) return MLVFS_AMD_ERR_HIP;
+    LookArg lk;
+    if (look) if (const int rc = look_on_device(look, c, &lk)) return rc;
+    if (look16) if (const int rc = look16_on_device(look16, c, &lk)) return rc;
+    return launch_amz_resample(d_red, d_green, d_blue, plane_stride, d_params, d_out, out_stride, width, height, ow, oh, nframes,
+                               pick_stream(stream, c), look || look16 ? &lk : nullptr, look16 != nullptr);
+}
+
+int mlvfs_amd_render_resampled_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                         void *d_out, size_t out_stride, int nframes, void *stream)
+{
+    return render_resampled_amaze_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream);
+}
+
+int mlvfs_amd_render_resampled_amaze_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                              void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
+{
+    return render_resampled_amaze_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, look, true, stream);
+}
+
+int mlvfs_amd_render_resampled_amaze_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
+                                              void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
+{
+    return render_resampled_amaze_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream, look, true);
+}
+
+/* test hook, host only: how launch_amz_resample would divide a launch among workgroups.  out[0]: 1 the x16 form (for aligned planes), 0
+   the generic one; [1] the most source columns of a strip; [2] uo, the output columns of a strip: strip k begins at column k uo; [3] the
+   strips; [4] bo, the output rows of a band: band k begins at row k bo; [5] the bands; [6] the source rows a band covers at least;
+   [7] the source rows of a step */
+int mlvfs_amd_test_amz_resample_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8])
+{
+    if (!out || nframes < 1 || !amz_resample_geom(width, height, ow, oh)) { set_error("test_amz_resample_plan: bad argument"); return MLVFS_AMD_ERR_ARG; }
+    int32_t v[8] = { 0, RS_STRIP, 0, 0, 0, 0, RS_BAND_ROWS, RS_ROWS };
+    if (amz_resample_fast_geom(width, ow)) {
+        const ResamplePlan p = resample_plan(width, height, ow, oh, nframes);
+        v[0] = 1; v[2] = (int32_t)p.uo; v[3] = (int32_t)p.nstrips; v[4] = (int32_t)p.bo; v[5] = (int32_t)p.nbands;
+    }
+    std::copy(v, v + 8, out);
+    return MLVFS_AMD_OK;
 }
 
 /* test hook, host only: how a batch of nframes frames is cut into sub-batches that fit cap_bytes of work memory (0: the library's own cap) */

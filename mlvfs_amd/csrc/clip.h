@@ -381,6 +381,21 @@ inline ResamplePlan resample_plan(int w, int h, int ow, int oh, int nframes)
 }
 int launch_render_resampled(const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w, int h, int ow,
                             int oh, int nframes, hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
+// resampled rendered frames demosaiced by AMaZE (k_amaze_resample.hip, amaze_render.cpp): the frames the AMaZE rendering takes with
+// both sides up to 65535, and ow x oh from 1x1 up to the frame's own size; the pass behind amaze_launch; balance, AMaZE and that pass
+// for a batch, in launch_render1_amaze's work memory and sub-batches
+inline bool amz_resample_geom(int w, int h, int ow, int oh)
+{
+    return rgb_amaze_geom(w, h) && w <= 65535 && h <= 65535 && ow >= 1 && ow <= w && oh >= 1 && oh <= h;
+}
+// what k_amz_resample_x16 asks of the sizes: whole 8-pixel groups, and output columns that span at most three source pixels.  It
+// divides a frame among workgroups as k_resample_x16 does (resample_plan), which asks no more of the width than that
+inline bool amz_resample_fast_geom(int w, int ow) { return w % 8 == 0 && 2 * (int64_t)ow >= w; }
+int launch_amz_resample(const float *d_red, const float *d_green, const float *d_blue, size_t plane_stride, const int32_t *d_params, void *d_out,
+                        size_t out_stride, int w, int h, int ow, int oh, int nframes, hipStream_t stream, const LookArg *lk = nullptr,
+                        bool deep = false);
+int launch_render_resampled_amaze(ThreadCtx *c, const void *d_frames, size_t stride, const int32_t *d_params, void *d_out, size_t out_stride, int w,
+                                  int h, int ow, int oh, int nframes, hipStream_t stream, const LookArg *lk = nullptr, bool deep = false);
 // the clip's bad-pixel map if it has been detected already (dropin.cpp)
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out);
 int cr2hdr20_batch_fh(ThreadCtx *c, struct frame_headers *fh, void *d_frames, size_t img_stride, int nframes, int w, int H, int black14,

@@ -44,6 +44,10 @@
 // mlvfs_amd_mount_set_demosaic(1): the three full-size calls demosaic with AMaZE (amaze_render.cpp: balance, amaze_launch, tone, in the
 // calling thread's work memory) instead of k_demosaic.hip's linear filter; the renderings lie in d_full as before and everything behind
 // them -- the JPEG encoder, the headers, the copies -- is the same.  No other call knows.
+//
+// mlvfs_amd_mount_set_resample_demosaic(1): the three resampled calls render through balance, amaze_launch and the resampling pass behind
+// it (amaze_render.cpp, k_amaze_resample.hip) instead of k_resample.hip, whatever set_demosaic says; placement, growth and everything
+// behind the renderings are the resampled route's.  At 0 (the default) the resampled calls are what they were, refused under set_demosaic(1).
 #include "clip.h"
 #include "lj92enc.h"
 #include "jpeg.h"
@@ -70,6 +74,7 @@ struct Mount {
     bool served = false;                     // a call has reached the device: the dark frame, the flat field and the proxy stay what they are
     int proxy = 1;                           // mlvfs_amd_mount_set_proxy: 2 = the served frames are binned to half size
     int demosaic = 0;                        // mlvfs_amd_mount_set_demosaic: 1 = the full-size calls demosaic with AMaZE; no serve-order state
+    int resample_demosaic = 0;               // mlvfs_amd_mount_set_resample_demosaic: 1 = the resampled calls demosaic with AMaZE; no serve-order state
     int device = -1;
     DevBuf d_frames, d_out, d_scratch;
     DevBuf d_bits;                           // the encoder's bit streams, sized from a batch's histograms
@@ -207,7 +212,9 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
     const bool resampled = mode.kind == RgbMode::RESAMPLED, scaled = mode.kind == RgbMode::SCALED;
     const bool full = mode.kind == RgbMode::FULL || resampled;                          // the renderings lie in d_full
     const bool amaze = m.demosaic == 1 && mode.kind == RgbMode::FULL;
+    const bool amaze_rs = m.resample_demosaic == 1 && resampled;
     int pw = w, ph = h;
+    if (amaze_rs && !amz_resample_geom(w, h, mode.ow, mode.oh)) { set_error("mount: a resampled AMaZE rendering does not take frames of %dx%d to %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
     if (amaze && !rgb_amaze_geom(w, h)) { set_error("mount: an AMaZE rendering does not take frames of %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
     if (resampled ? !resample_geom(w, h, mode.ow, mode.oh) : full ? !rgb_full_geom(w, h) : scaled ? !scale_geom(w, h, mode.ow, mode.oh, &pw, &ph) : !rgb_geom(w, h, &pw, &ph)) {
         set_error("mount: a rendering does not take frames of %dx%d", w, h);
@@ -235,7 +242,8 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         uint8_t *dst = full ? (uint8_t *)m.d_full + k0 * rstride : (in_f ? O : F) + k0 * dstride;
         uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
         const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
-        const int rc = resampled ? launch_render_resampled(final_at[k0], dstride, par, dst, rstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
+        const int rc = amaze_rs ? launch_render_resampled_amaze(c, final_at[k0], dstride, par, dst, rstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
+                 : resampled ? launch_render_resampled(final_at[k0], dstride, par, dst, rstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
                  : amaze ? launch_render1_amaze(c, final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
                  : full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
                  : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
@@ -508,6 +516,16 @@ int mlvfs_amd_mount_set_demosaic(void *mount, int which)
     return MLVFS_AMD_OK;
 }
 
+int mlvfs_amd_mount_set_resample_demosaic(void *mount, int which)
+{
+    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (which != 0 && which != 1) { set_error("mount: a resample demosaic of %d (0: the linear filter, 1: AMaZE)", which); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    std::lock_guard<std::mutex> lk(m.mu);                // between serving calls: a call in flight holds the mutex
+    m.resample_demosaic = which;
+    return MLVFS_AMD_OK;
+}
+
 size_t mlvfs_amd_mount_dng_size(const void *mount, int index)
 {
     if (!mount) { set_error("mount: null argument"); return 0; }
@@ -594,7 +612,9 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         if (m.proxy == 2) { set_error("mount: a handle that serves proxies does not render"); return MLVFS_AMD_ERR_ARG; }
         int pw = w, ph = h;
         if (full && !rgb_full_geom(w, h)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
-        if (m.demosaic == 1 && resampled) { set_error("mount: with AMaZE set (mlvfs_amd_mount_set_demosaic) the resampled calls are not served"); return MLVFS_AMD_ERR_ARG; }
+        if (m.resample_demosaic == 1 && resampled) {
+            if (!amz_resample_geom(w, h, mode.ow, mode.oh)) { set_error("mount: a resampled AMaZE rendering takes frames of 36x36 up to 2^25 pixels and 65535 a side, the width a multiple of 4, and a size of 1x1 up to the frame's, not %dx%d to %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
+        } else if (m.demosaic == 1 && resampled) { set_error("mount: with AMaZE set (mlvfs_amd_mount_set_demosaic) the resampled calls are not served"); return MLVFS_AMD_ERR_ARG; }
         if (m.demosaic == 1 && full && !rgb_amaze_geom(w, h)) { set_error("mount: an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         if (!full && !rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         if (scaled) {
@@ -789,6 +809,15 @@ size_t mlvfs_amd_mount_rgb_resampled_size(const void *mount, int index, int ow, 
     if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
     if (!resample_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh)) {
         set_error("mount: a resampled rendering of a %dx%d frame is 1x1 up to its own size, 65535 a side at most, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh);
+        return 0;
+    }
+    int resample_demosaic;
+    {
+        std::lock_guard<std::mutex> lk(m.mu);
+        resample_demosaic = m.resample_demosaic;
+    }
+    if (resample_demosaic == 1 && !amz_resample_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh)) {
+        set_error("mount: a resampled AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
         return 0;
     }
     return mlvfs_amd_rgb_header_size() + (size_t)3 * ow * oh;

@@ -85,6 +85,9 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_mount_rgb_resampled_size", "mlvfs_amd_mount_rgb16_resampled_size", "mlvfs_amd_test_resample_plan",
     "mlvfs_amd_rgb_amaze_geom", "mlvfs_amd_amaze_balance_dev", "mlvfs_amd_amaze_tone_dev", "mlvfs_amd_render1_amaze_dev",
     "mlvfs_amd_render1_amaze_look_dev", "mlvfs_amd_render1_amaze_deep_dev", "mlvfs_amd_mount_set_demosaic", "mlvfs_amd_test_amaze_render_plan",
+    "mlvfs_amd_rgb_amaze_resample_geom", "mlvfs_amd_amaze_resample_dev", "mlvfs_amd_render_resampled_amaze_dev",
+    "mlvfs_amd_render_resampled_amaze_look_dev", "mlvfs_amd_render_resampled_amaze_deep_dev", "mlvfs_amd_mount_set_resample_demosaic",
+    "mlvfs_amd_test_amz_resample_plan",
 ]
 
 
@@ -345,6 +348,13 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_render1_amaze_deep_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp, vp])
     sig("mlvfs_amd_mount_set_demosaic", i, [vp, i])
     sig("mlvfs_amd_test_amaze_render_plan", i, [i, i, i, sz, vp])
+    sig("mlvfs_amd_rgb_amaze_resample_geom", i, [i, i, i, i])
+    sig("mlvfs_amd_amaze_resample_dev", i, [vp, vp, vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp, vp])
+    sig("mlvfs_amd_render_resampled_amaze_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp])
+    sig("mlvfs_amd_render_resampled_amaze_look_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_render_resampled_amaze_deep_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
+    sig("mlvfs_amd_mount_set_resample_demosaic", i, [vp, i])
+    sig("mlvfs_amd_test_amz_resample_plan", i, [i, i, i, i, i, vp])
     _lib = L
     return L
 

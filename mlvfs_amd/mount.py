@@ -24,6 +24,9 @@
     m.set_demosaic("amaze") makes the full-size calls demosaic with AMaZE instead of the linear filter (include/mlvfs_amd.h, "rendered
     full-size frames demosaiced by AMaZE"; mlvfs_amd/amaze_render.py is the definition).
 
+    m.set_resample_demosaic("amaze") makes the resample=True calls demosaic with AMaZE (include/mlvfs_amd.h, "resampled rendered frames
+    demosaiced by AMaZE"; mlvfs_amd/amaze_resample.py is the definition).
+
 Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
 """
 from __future__ import annotations
@@ -62,6 +65,7 @@ class Mount:
         self._dark = self._flat = self._look = None
         self.proxy = 1
         self.demosaic = "linear"
+        self.resample_demosaic = "linear"
         try:
             if dark is not None:
                 self.set_dark(dark)
@@ -96,12 +100,21 @@ class Mount:
     def set_demosaic(self, which: str) -> None:
         """which: "linear", the Malvar-He-Cutler filter (the default), or "amaze", the AMaZE demosaic (mlvfs_amd/amaze_render.py), in
         every later rgb(full=True), jpeg(full=True) and rgb(full=True, look16=...) call.  Allowed at any time between calls; no other
-        call sees it, but with "amaze" set the resample=True calls are refused, and so are frames AMaZE does not take (a width that is
-        no multiple of 4, a side below 36)."""
+        call sees it, but with "amaze" set the resample=True calls are refused -- unless set_resample_demosaic("amaze") has given them
+        AMaZE of their own -- and so are frames AMaZE does not take (a width that is no multiple of 4, a side below 36)."""
         if which not in self.DEMOSAICS:
             raise ValueError(f'demosaic {which!r} ("linear" or "amaze")')
         lib.check(self.L.mlvfs_amd_mount_set_demosaic(self.h, self.DEMOSAICS[which]), "mount_set_demosaic")
         self.demosaic = which
+
+    def set_resample_demosaic(self, which: str) -> None:
+        """which: "linear" (the default) or "amaze", the AMaZE demosaic (mlvfs_amd/amaze_resample.py), in every later
+        rgb(resample=True), jpeg(resample=True) and rgb(resample=True, look16=...) call, whatever set_demosaic says.  Allowed at any
+        time between calls; no other call sees it.  With "amaze" set, frames AMaZE does not take are refused."""
+        if which not in self.DEMOSAICS:
+            raise ValueError(f'resample demosaic {which!r} ("linear" or "amaze")')
+        lib.check(self.L.mlvfs_amd_mount_set_resample_demosaic(self.h, self.DEMOSAICS[which]), "mount_set_resample_demosaic")
+        self.resample_demosaic = which
 
     def set_proxy(self, factor: int) -> None:
         """factor 2: every frame is served binned to half size, 2 * (W // 4) x 2 * (H // 4), after all other stages; 1: off.  Refused

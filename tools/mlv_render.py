@@ -11,11 +11,12 @@ full-size rendering") -- 3584 x 1320 --resample --fit 1920x1080 writes 1920 x 70
 (mlvfs_amd_mount_set_look; "a look for the rendered frames"); --lut-input says what the table's input axis means: the sRGB value the
 plain rendering would write (the default), linear light, or log2:STOPS -- a pure log curve over that many stops below white.
 --full --demosaic amaze demosaics with AMaZE instead of the linear filter (mlvfs_amd_mount_set_demosaic; "rendered full-size frames
-demosaiced by AMaZE"), with TIFF, --jpeg, --bits 16 and --lut alike.
+demosaiced by AMaZE"), with TIFF, --jpeg, --bits 16 and --lut alike.  --resample (--size WxH | --fit WxH) --demosaic amaze resamples
+that AMaZE rendering instead of the linear one (mlvfs_amd_mount_set_resample_demosaic; "resampled rendered frames demosaiced by AMaZE").
 --bits 16 writes 16-bit TIFF files toned from 16-bit linear light (mlvfs_amd_mount_rgb16 and its forms; "rendered frames at 16 bits"):
 --lut-input's curve on the 16-bit index (linear: the file holds linear light itself), --lut's table behind it if one is given.
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full [--demosaic amaze] | --size WxH | --fit WxH] [--resample] [--jpeg [QUALITY]] [--bits 16] [--lut FILE.cube] [--lut-input srgb|linear|log2:STOPS] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--resample] [--demosaic amaze] [--jpeg [QUALITY]] [--bits 16] [--lut FILE.cube] [--lut-input srgb|linear|log2:STOPS] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
@@ -31,7 +32,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mlvfs_amd import look, mlvfile, resample, scale
+from mlvfs_amd import amaze_resample, look, mlvfile, resample, scale
 from mlvfs_amd.dark import Dark
 from mlvfs_amd.flat import Flat
 from mlvfs_amd.mount import Mount
@@ -54,8 +55,8 @@ def main() -> int:
     how.add_argument("--full", action="store_true", help="render at full size (a fixed 5x5 linear demosaic) instead of half size")
     how.add_argument("--size", type=wxh, metavar="WxH", help="render at W x H, at most half the frame's size a side (an area average in linear light)")
     how.add_argument("--fit", type=wxh, metavar="WxH", help="render at the largest size inside a box of W x H at the frame's aspect")
-    ap.add_argument("--demosaic", default="linear", choices=("linear", "amaze"), help="with --full: the demosaic -- the fixed 5x5 linear filter "
-                    "(default) or AMaZE (frames of 36x36 and more whose width is a multiple of 4)")
+    ap.add_argument("--demosaic", default="linear", choices=("linear", "amaze"), help="with --full or --resample: the demosaic -- the fixed 5x5 "
+                    "linear filter (default) or AMaZE (frames of 36x36 and more whose width is a multiple of 4)")
     ap.add_argument("--resample", action="store_true", help="with --size or --fit: any size up to the frame's own, resampled from the full-size "
                     "rendering (not with --full)")
     ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
@@ -86,8 +87,8 @@ def main() -> int:
         ap.error("--bits 16 --jpeg: there are no 16-bit JPEG files")
     if a.resample and (a.full or not (a.size or a.fit)):
         ap.error("--resample takes --size or --fit, and no --full")
-    if a.demosaic != "linear" and not a.full:
-        ap.error("--demosaic amaze takes --full: only the full-size rendering has a demosaic to choose")
+    if a.demosaic != "linear" and not (a.full or a.resample):
+        ap.error("--demosaic amaze takes --full or --resample: only the full-size rendering and what is resampled from it have a demosaic to choose")
     cube = deep = None
     if a.lut or a.bits == 16:
         try:
@@ -112,7 +113,7 @@ def main() -> int:
             if not ok:
                 ap.error(f"frame {a.first} has no usable headers")
             try:
-                route = resample if a.resample else scale
+                route = (amaze_resample if a.demosaic == "amaze" else resample) if a.resample else scale
                 if a.fit:
                     size = route.fit(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *a.fit)
                 route.geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, *size)
@@ -140,7 +141,9 @@ def main() -> int:
             with Mount(r, opt, deflicker=a.deflicker, basename="/" + os.path.basename(a.src), dark=dark, flat=flat) as m:
                 if lk is not None:
                     m.set_look(lk)
-                if a.demosaic != "linear":
+                if a.demosaic != "linear" and a.resample:
+                    m.set_resample_demosaic(a.demosaic)
+                elif a.demosaic != "linear":
                     m.set_demosaic(a.demosaic)
                 for f0 in range(0, count, a.batch):
                     n = min(a.batch, count - f0)
