@@ -818,8 +818,9 @@ size_t mlvfs_amd_mount_rgb_size(const void *mount, int index);
  *            Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
  *            Cb = clamp(((-11058 R - 21710 G + 32768 B + 32768) >> 16) + 128, 0, 255)      (R = G = 0, B = 255 gives 256 before the clamp)
  *            Cr = clamp(((32768 R - 27439 G - 5329 B + 32768) >> 16) + 128, 0, 255)
- * MCUs.    4:2:0, MCUs of 16 x 16 pixels, mw = ceil(W' / 16), mh = ceil(H' / 16).  The three planes are extended to 16 mw x 16 mh by
- *          repeating the last column and the last row; then Cb and Cr are halved:
+ * MCUs.    4:2:0 (the default; 4:2:2 and 4:4:4: "the chroma sampling of the JPEG files" below), MCUs of 16 x 16 pixels, mw = ceil(W' / 16),
+ *          mh = ceil(H' / 16).  The three planes are extended to 16 mw x 16 mh by repeating the last column and the last row; then Cb
+ *          and Cr are halved:
  *            c(y, x) = (p(2y, 2x) + p(2y, 2x + 1) + p(2y + 1, 2x) + p(2y + 1, 2x + 1) + 2) >> 2
  * DCT.     Of each 8 x 8 block of p - 128, with the integer matrix T[u][x] = round(8192 s(u) cos((2x + 1) u pi / 16)), s(0) = sqrt(1 / 8),
  *          s(u > 0) = 1 / 2 -- 64 constants (row 1: 4017 3406 2276 799 -799 -2276 -3406 -4017), never computed by the library:
@@ -867,6 +868,43 @@ int    mlvfs_amd_jpeg_encode_dev(const void *d_rgb, size_t stride, int pw, int p
  * outside 1 .. 100.                                                                                                                  */
 int    mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes,
                             int *flags, int batch_frames, int io_threads, int *results);
+
+/* -- the chroma sampling of the JPEG files (csrc/k_jpeg.hip, csrc/jpeg.cpp, csrc/mount.cpp) ------------------------------ */
+/* Everything above describes MLVFS_AMD_JPEG_420, the default.  A sampling s changes four things of the definition and nothing else
+ * (colour, DCT, tables, quantisation, Huffman tables, stuffing, EOI are as above; the oracle takes it as `sampling`: mlvfs_amd/jpeg.py):
+ * MCUs.    (mcw, mch) = (16, 16) at 4:2:0, (16, 8) at 4:2:2, (8, 8) at 4:4:4; mw = ceil(W' / mcw), mh = ceil(H' / mch); the three planes
+ *          are extended to mcw mw x mch mh by repeating the last column and the last row.
+ * Chroma.  4:2:0 as above;  4:2:2: c(y, x) = (p(y, 2x) + p(y, 2x + 1) + 1) >> 1;  4:4:4: c = p.
+ * Blocks.  Of an MCU: its luminance blocks from left to right (4:2:0: the top row first; 4:2:2: Y0 Y1; 4:4:4: Y), then Cb, Cr.  DC
+ *          prediction is per component and starts at 0 in every MCU row: the first Y block of an MCU from the last Y block of the MCU
+ *          before, later Y blocks from the block before them, Cb and Cr from the MCU before.
+ * Restart intervals.  One MCU row of the sampling each: DRI = mw, RST index = MCU row mod 8.
+ * The file.  629 bytes of header at every sampling; three bytes differ: byte 169, the sampling factors of component 1 (22, 21, 11), and
+ *          bytes 613 - 614, the DRI count.                                                                                              */
+#define MLVFS_AMD_JPEG_420 0     /* H2V2: six blocks per MCU */
+#define MLVFS_AMD_JPEG_422 1     /* H2V1: four */
+#define MLVFS_AMD_JPEG_444 2     /* H1V1: three */
+/* mlvfs_amd_jpeg_header at a sampling: besides its refusals, a sampling that is none of the three returns 0 and writes nothing.  Host code. */
+size_t mlvfs_amd_jpeg_header_sampled(int pw, int ph, int quality, int sampling, uint8_t *out, size_t cap);
+/* mlvfs_amd_jpeg_scratch_bytes at a sampling (what mlvfs_amd_jpeg_encode_sampled_dev takes); 0 also for a sampling that is none of the
+ * three.  4:4:4 has twice the MCU rows and twice the coefficient bytes per pixel of 4:2:0.  Host code.                               */
+size_t mlvfs_amd_jpeg_scratch_bytes_sampled(int pw, int ph, int sampling, int nframes);
+/* the MCU grid of pw x ph at a sampling into *mw, *mh.  Host code.  MLVFS_AMD_ERR_ARG (nothing written): a null pointer, a sampling that
+ * is none of the three, a size outside the input's.                                                                                   */
+int    mlvfs_amd_jpeg_mcus(int pw, int ph, int sampling, int *mw, int *mh);
+/* mlvfs_amd_jpeg_encode_dev at a sampling: the same contract -- checks before any device work, `room`, h_lengths, h_status, untouched
+ * bytes -- and one refusal more, MLVFS_AMD_ERR_ARG for a sampling that is none of the three.  mlvfs_amd_jpeg_encode_dev is this call
+ * with MLVFS_AMD_JPEG_420.                                                                                                            */
+int    mlvfs_amd_jpeg_encode_sampled_dev(const void *d_rgb, size_t stride, int pw, int ph, int quality, int sampling, void *d_out,
+                                         size_t out_stride, size_t room, void *d_scratch, size_t scratch_bytes, uint32_t *h_lengths,
+                                         int *h_status, int nframes, void *stream);
+/* The sampling of every later mlvfs_amd_mount_jpeg, _full, _scaled and _resampled call of the handle, their AMaZE forms included.  It
+ * holds no serve-order state and may change between calls; the rendering, the flag rule (the TIFF where 629 + stream > 256 + 3 W' H'),
+ * sizes[] and results[] are unchanged.  A handle that never calls it serves 4:2:0, launch for launch what it served before.
+ * MLVFS_AMD_ERR_ARG: a null handle, a sampling that is none of the three.
+ * Not built: 4:1:1 and 4:4:0, greyscale files, per-frame Huffman tables, progressive coding, a sampling chosen from the quality
+ * (DESIGN.md 3.21).                                                                                                                   */
+int    mlvfs_amd_mount_set_jpeg_sampling(void *mount, int sampling);
 
 /* -- rendered full-size sRGB frames (csrc/k_demosaic.hip, csrc/mount.cpp) --------------------------------------------- */
 /* The rendering at the size the frame was shot: three channels per sensor pixel.  The definition is this project's, in integers only,

@@ -96,26 +96,28 @@ void jpg_quant(int quality, JpgQuant *out)
     for (int k = 0; k < 128; k++) (&out->recip[0][0])[k] = (1u << 20) / (&out->q[0][0])[k] + 1u;
 }
 
-size_t jpg_rowcap_max(int pw, int ph)
+size_t jpg_rowcap_max(int pw, int ph, int sampling)
 {
-    const size_t mw = ((size_t)pw + 15) / 16, mh = ((size_t)ph + 15) / 16;
-    return mh * ((mw * JPG_MCU_BYTES + 3) / 4 * 4);
+    const JpgMode &md = kJpgModes[sampling];
+    const size_t mw = ((size_t)pw + md.mcw - 1) / md.mcw, mh = ((size_t)ph + md.mch - 1) / md.mch;
+    return mh * ((mw * md.mcu_bytes() + 3) / 4 * 4);
 }
 
-JpgLayout jpg_layout(int pw, int ph, size_t rowcap_bytes)
+JpgLayout jpg_layout(int pw, int ph, size_t rowcap_bytes, int sampling)
 {
+    const JpgMode &md = kJpgModes[sampling];
     JpgLayout l{};
     l.pw = (uint32_t)pw;
     l.ph = (uint32_t)ph;
-    l.mw = ((uint32_t)pw + 15) / 16;
-    l.mh = ((uint32_t)ph + 15) / 16;
+    l.mw = ((uint32_t)pw + md.mcw - 1) / md.mcw;
+    l.mh = ((uint32_t)ph + md.mch - 1) / md.mch;
     const size_t nm = (size_t)l.mw * l.mh;
-    l.rowcap_dw = (uint32_t)((std::min(rowcap_bytes, jpg_rowcap_max(pw, ph)) + 3) / 4);
+    l.rowcap_dw = (uint32_t)((std::min(rowcap_bytes, jpg_rowcap_max(pw, ph, sampling)) + 3) / 4);
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t here = at; at += up256(bytes); return here; };
-    l.coef = take(nm * 384 * sizeof(int16_t));
-    l.dcv = take(nm * 6 * sizeof(int16_t));
-    l.bbits = take(nm * 6 * sizeof(uint16_t));
+    l.coef = take(nm * md.nb * 64 * sizeof(int16_t));
+    l.dcv = take(nm * md.nb * sizeof(int16_t));
+    l.bbits = take(nm * md.nb * sizeof(uint16_t));
     l.off = take(nm * sizeof(uint32_t));
     l.rowbits = take(l.mh * sizeof(uint32_t));
     l.rowat = take(l.mh * sizeof(uint32_t));
@@ -127,13 +129,13 @@ JpgLayout jpg_layout(int pw, int ph, size_t rowcap_bytes)
 }
 
 int jpg_encode_batch(const void *d_rgb, size_t stride, int pw, int ph, int quality, void *d_out, size_t out_stride, size_t room, void *d_scratch,
-                     const JpgLayout &l, JpgOut *res, int nframes, hipStream_t s)
+                     const JpgLayout &l, JpgOut *res, int nframes, hipStream_t s, int sampling)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
     JpgQuant q;
     jpg_quant(quality, &q);
     const uint32_t room32 = (uint32_t)std::min<size_t>(room, 0xFFFFFFFFu);
-    const int rc = jpg_launch((const uint8_t *)d_rgb, stride, l, q, jpg_huff(), (uint8_t *)d_out, out_stride, room32, (uint8_t *)d_scratch, nframes, s);
+    const int rc = jpg_launch((const uint8_t *)d_rgb, stride, l, q, jpg_huff(), (uint8_t *)d_out, out_stride, room32, (uint8_t *)d_scratch, nframes, s, sampling);
     if (rc) return rc;
     MLV_HIP(hipMemcpyAsync(res, d_scratch, sizeof(JpgOut) * (size_t)nframes, hipMemcpyDeviceToHost, s));
     MLV_HIP(hipStreamSynchronize(s));
@@ -158,12 +160,19 @@ int mlvfs_amd_jpeg_qtables(int quality, uint8_t out[128])
 
 size_t mlvfs_amd_jpeg_header(int pw, int ph, int quality, uint8_t *out, size_t cap)
 {
+    return mlvfs_amd_jpeg_header_sampled(pw, ph, quality, MLVFS_AMD_JPEG_420, out, cap);
+}
+
+size_t mlvfs_amd_jpeg_header_sampled(int pw, int ph, int quality, int sampling, uint8_t *out, size_t cap)
+{
     if (!out) { set_error("jpeg_header: null argument"); return 0; }
+    if (!jpg_sampling_ok(sampling)) { set_error("jpeg_header: a sampling of %d (0: 4:2:0, 1: 4:2:2, 2: 4:4:4)", sampling); return 0; }
     if (!jpg_size_ok(pw, ph)) { set_error("jpeg_header: %dx%d pixels not supported", pw, ph); return 0; }
     if (quality < 1 || quality > 100) { set_error("jpeg_header: a quality of %d (1 .. 100)", quality); return 0; }
     if (cap < (size_t)JPG_HEADER_BYTES) { set_error("jpeg_header: room for %zu bytes, the header takes %d", cap, JPG_HEADER_BYTES); return 0; }
     static const uint8_t soi_app0[] = { 0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00 };
-    static const uint8_t sof_tail[] = { 0x03, 0x01, 0x22, 0x00, 0x02, 0x11, 0x01, 0x03, 0x11, 0x01 };
+    static const uint8_t factors[3] = { 0x22, 0x21, 0x11 };
+    const uint8_t sof_tail[] = { 0x03, 0x01, factors[sampling], 0x00, 0x02, 0x11, 0x01, 0x03, 0x11, 0x01 };
     static const uint8_t sos[] = { 0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00 };
     uint8_t head[JPG_HEADER_BYTES], q[128];
     uint8_t *p = head;
@@ -191,23 +200,45 @@ size_t mlvfs_amd_jpeg_header(int pw, int ph, int quality, uint8_t *out, size_t c
     }
     put16(p, 0xFFDD);
     put16(p, 4);
-    put16(p, ((unsigned)pw + 15) / 16);
+    put16(p, ((unsigned)pw + kJpgModes[sampling].mcw - 1) / kJpgModes[sampling].mcw);
     put(p, sos, sizeof sos);
     if (p - head != JPG_HEADER_BYTES) { set_error("jpeg_header: %d bytes built, not %d", (int)(p - head), JPG_HEADER_BYTES); return 0; }
     memcpy(out, head, sizeof head);
     return JPG_HEADER_BYTES;
 }
 
-size_t mlvfs_amd_jpeg_scratch_bytes(int pw, int ph, int nframes)
+size_t mlvfs_amd_jpeg_scratch_bytes(int pw, int ph, int nframes) { return mlvfs_amd_jpeg_scratch_bytes_sampled(pw, ph, MLVFS_AMD_JPEG_420, nframes); }
+
+size_t mlvfs_amd_jpeg_scratch_bytes_sampled(int pw, int ph, int sampling, int nframes)
 {
+    if (!jpg_sampling_ok(sampling)) { set_error("jpeg_scratch_bytes: a sampling of %d (0: 4:2:0, 1: 4:2:2, 2: 4:4:4)", sampling); return 0; }
     if (!jpg_size_ok(pw, ph) || nframes < 0) { set_error("jpeg_scratch_bytes: %d frames of %dx%d pixels not supported", nframes, pw, ph); return 0; }
-    return jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap_max(pw, ph)), nframes);
+    return jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap_max(pw, ph, sampling), sampling), nframes);
+}
+
+int mlvfs_amd_jpeg_mcus(int pw, int ph, int sampling, int *mw, int *mh)
+{
+    if (!mw || !mh) { set_error("jpeg_mcus: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!jpg_sampling_ok(sampling)) { set_error("jpeg_mcus: a sampling of %d (0: 4:2:0, 1: 4:2:2, 2: 4:4:4)", sampling); return MLVFS_AMD_ERR_ARG; }
+    if (!jpg_size_ok(pw, ph)) { set_error("jpeg_mcus: %dx%d pixels not supported", pw, ph); return MLVFS_AMD_ERR_ARG; }
+    *mw = (pw + kJpgModes[sampling].mcw - 1) / kJpgModes[sampling].mcw;
+    *mh = (ph + kJpgModes[sampling].mch - 1) / kJpgModes[sampling].mch;
+    return MLVFS_AMD_OK;
 }
 
 int mlvfs_amd_jpeg_encode_dev(const void *d_rgb, size_t stride, int pw, int ph, int quality, void *d_out, size_t out_stride, size_t room,
                               void *d_scratch, size_t scratch_bytes, uint32_t *h_lengths, int *h_status, int nframes, void *stream)
 {
+    return mlvfs_amd_jpeg_encode_sampled_dev(d_rgb, stride, pw, ph, quality, MLVFS_AMD_JPEG_420, d_out, out_stride, room, d_scratch, scratch_bytes,
+                                             h_lengths, h_status, nframes, stream);
+}
+
+int mlvfs_amd_jpeg_encode_sampled_dev(const void *d_rgb, size_t stride, int pw, int ph, int quality, int sampling, void *d_out, size_t out_stride,
+                                      size_t room, void *d_scratch, size_t scratch_bytes, uint32_t *h_lengths, int *h_status, int nframes,
+                                      void *stream)
+{
     if (!d_rgb || !d_out || !d_scratch || !h_lengths || !h_status) { set_error("jpeg_encode: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!jpg_sampling_ok(sampling)) { set_error("jpeg_encode: a sampling of %d (0: 4:2:0, 1: 4:2:2, 2: 4:4:4)", sampling); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0 || nframes > 65535) { set_error("jpeg_encode: %d frames (0 .. 65535)", nframes); return MLVFS_AMD_ERR_ARG; }
     if (!jpg_size_ok(pw, ph)) { set_error("jpeg_encode: %dx%d pixels not supported (1x1 up to 65535 a side, below 2^25 pixels)", pw, ph); return MLVFS_AMD_ERR_ARG; }
     if (quality < 1 || quality > 100) { set_error("jpeg_encode: a quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
@@ -217,7 +248,7 @@ int mlvfs_amd_jpeg_encode_dev(const void *d_rgb, size_t stride, int pw, int ph, 
         return MLVFS_AMD_ERR_ARG;
     }
     if ((uintptr_t)d_scratch & 15) { set_error("jpeg_encode: the scratch is not 16-byte aligned"); return MLVFS_AMD_ERR_ARG; }
-    const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap_max(pw, ph));
+    const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap_max(pw, ph, sampling), sampling);
     const size_t need = jpg_scratch_bytes(l, nframes);
     if (scratch_bytes < need) { set_error("jpeg_encode: %zu bytes of scratch, %d frames of %dx%d take %zu", scratch_bytes, nframes, pw, ph, need); return MLVFS_AMD_ERR_ARG; }
     if (nframes == 0) return MLVFS_AMD_OK;
@@ -231,7 +262,7 @@ int mlvfs_amd_jpeg_encode_dev(const void *d_rgb, size_t stride, int pw, int ph, 
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
     std::vector<JpgOut> res((size_t)nframes);
-    const int rc = jpg_encode_batch(d_rgb, stride, pw, ph, quality, d_out, out_stride, room, d_scratch, l, res.data(), nframes, pick_stream(stream, c));
+    const int rc = jpg_encode_batch(d_rgb, stride, pw, ph, quality, d_out, out_stride, room, d_scratch, l, res.data(), nframes, pick_stream(stream, c), sampling);
     if (rc) return rc;
     for (int k = 0; k < nframes; k++) {
         h_status[k] = res[k].status ? 1 : 0;

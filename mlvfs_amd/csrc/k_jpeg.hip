@@ -18,6 +18,13 @@
 //                     RST marker or, after the last row, EOI
 // Coefficients go through HBM (1.5 x 256 int16 per MCU, written once, read once by k_jpg_emit): recomputing them in the emit pass
 // would run the transform twice to save 1.5 bytes per pixel each way of a stage that is far from the machine's bandwidth.
+//
+// The chroma sampling is a constant S of the three kernels that see blocks (k_jpg_transform, k_jpg_scan_bits,
+// k_jpg_emit), S indexing kJpgModes (jpeg.h): 4:2:0 as above; 4:2:2, MCUs of 16 x 8 pixels and 4 blocks; 4:4:4, MCUs of 8 x 8 pixels
+// and 3 blocks.  Their text (k_jpeg_blocks.inc) is compiled once per sampling: k_jpg_transform (4:2:0, the kernel as it was),
+// k_jpg_transform_422, k_jpg_transform_444, and so on.  At the two new samplings a workgroup of k_jpg_transform_* takes a tile of
+// 64 x 8 pixels (16 or 24 blocks), one of k_jpg_emit_* 96 blocks as at 4:2:0.  The other four kernels see MCU rows only and take
+// everything from the layout; k_jpg_rows is told how many MCUs a workgroup of the emit kernel takes.
 #include "jpeg.h"
 #include "k_bits_dev.h"
 
@@ -72,11 +79,12 @@ __device__ __forceinline__ uint32_t jpg_scan256(uint32_t x, uint32_t *ws /* [4],
 }
 
 // the DC value block bj of MCU m (mx-th of its row) is predicted from: the block of the same component before it in the row
-__device__ __forceinline__ int jpg_pred(const int16_t *__restrict__ dcv, uint32_t m, uint32_t mx, int bj)
+template <int S> __device__ __forceinline__ int jpg_pred(const int16_t *__restrict__ dcv, uint32_t m, uint32_t mx, int bj)
 {
-    if (bj >= 1 && bj <= 3) return dcv[(size_t)m * 6 + bj - 1];
+    constexpr int NB = kJpgModes[S].nb, NY = kJpgModes[S].ny;
+    if (bj >= 1 && bj <= NY - 1) return dcv[(size_t)m * NB + bj - 1];
     if (mx == 0) return 0;
-    return dcv[(size_t)(m - 1) * 6 + (bj == 0 ? 3 : bj)];
+    return dcv[(size_t)(m - 1) * NB + (bj == 0 ? NY - 1 : bj)];
 }
 
 struct JpgFrame {
@@ -102,157 +110,19 @@ __device__ __forceinline__ uint32_t jpg_row_dwords(uint32_t bits) { return (((bi
 
 }  // namespace
 
-// grid.x = ceil(mw / 4) * mh
-__global__ __launch_bounds__(256) void k_jpg_transform(const uint8_t *__restrict__ rgb, size_t stride, const JpgLayout l, const JpgQuant qt, const JpgHuff hf,
-                                                       uint8_t *__restrict__ scratch)
+// `len` bits (1 .. 64) of v, the first one at bit `pos` of the MSB-first stream in LDS
+__device__ __forceinline__ void jpg_put(uint32_t *lds, uint32_t pos, uint64_t v, uint32_t len)
 {
-    __shared__ uint32_t ys[16][18];                      // a row: 64 samples in 16 dwords, 2 dwords of padding
-    __shared__ uint32_t cbs[16][17], crs[16][17];        // a row: 32 sums of two neighbours, 16 bits each, 1 dword of padding
-    __shared__ int ab[JPG_GROUP * 6][8][9];              // after the row pass; a row of 8 in 9 dwords: the column pass reads down
-    __shared__ __attribute__((aligned(16))) int16_t zz[JPG_GROUP * 6][64];
-    __shared__ uint32_t s_recip[128], sb[JPG_GROUP * 6];
-    __shared__ uint8_t s_q[128], s_izig[64], s_aclen[512];
-    const uint32_t t = threadIdx.x, f = blockIdx.y;
-    const uint32_t gx = (l.mw + JPG_GROUP - 1) / JPG_GROUP, r = blockIdx.x / gx, g = blockIdx.x - r * gx;
-    if (t < 128) { s_recip[t] = (&qt.recip[0][0])[t]; s_q[t] = (&qt.q[0][0])[t]; }
-    if (t < 64) s_izig[t] = kIzig[t];
-    s_aclen[t] = (&hf.ac_len[0][0])[t];
-    s_aclen[t + 256] = (&hf.ac_len[0][0])[t + 256];
-    // 1. colour: a thread takes 4 pixels of one of the 16 rows
-    {
-        const uint32_t y = t >> 4, xg = t & 15, X = 64 * g + 4 * xg, Y = min(16 * r + y, l.ph - 1);
-        const uint8_t *row = rgb + (size_t)f * stride + (size_t)Y * l.pw * 3;
-        uint32_t px[4];
-        if (X + 3 < l.pw) {
-            const uintptr_t p = (uintptr_t)(row + (size_t)X * 3);
-            const uint32_t *a = (const uint32_t *)(p & ~(uintptr_t)3);
-            const uint32_t sh = 8 * (uint32_t)(p & 3);
-            uint32_t w0 = a[0], w1 = a[1], w2 = a[2];
-            if (sh) {                                    // the twelve bytes lie in four dwords
-                const uint32_t w3 = a[3];
-                w0 = (w0 >> sh) | (w1 << (32 - sh));
-                w1 = (w1 >> sh) | (w2 << (32 - sh));
-                w2 = (w2 >> sh) | (w3 << (32 - sh));
-            }
-            px[0] = w0 & 0xFFFFFFu;
-            px[1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
-            px[2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
-            px[3] = w2 >> 8;
-        } else {                                         // the last column repeats
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint8_t *q = row + (size_t)min(X + k, l.pw - 1) * 3;
-                px[k] = q[0] | (q[1] << 8) | (q[2] << 16);
-            }
-        }
-        uint32_t yy[4], cb[4], cr[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) jpg_ycc(px[k], &yy[k], &cb[k], &cr[k]);
-        ys[y][xg] = yy[0] | (yy[1] << 8) | (yy[2] << 16) | (yy[3] << 24);
-        cbs[y][xg] = (cb[0] + cb[1]) | ((cb[2] + cb[3]) << 16);
-        crs[y][xg] = (cr[0] + cr[1]) | ((cr[2] + cr[3]) << 16);
-    }
-    __syncthreads();
-    // 2. rows: a thread takes one row of one of the 24 blocks
-    if (t < JPG_GROUP * 48) {
-        const uint32_t i = t / 48, rem = t - i * 48, blk = rem >> 3, y = rem & 7;
-        int s[8], o[8];
-        if (blk < 4) {
-            const uint32_t yr = (blk >> 1) * 8 + y, c = i * 4 + (blk & 1) * 2;
-            const uint32_t a = ys[yr][c], b = ys[yr][c + 1];
-#pragma unroll
-            for (int k = 0; k < 4; k++) { s[k] = (int)((a >> (8 * k)) & 0xFF) - 128; s[4 + k] = (int)((b >> (8 * k)) & 0xFF) - 128; }
-        } else {
-            const uint32_t(*cs)[17] = blk == 4 ? cbs : crs;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t a = cs[2 * y][i * 4 + k], b = cs[2 * y + 1][i * 4 + k];
-                s[2 * k] = (int)(((a & 0xFFFF) + (b & 0xFFFF) + 2) >> 2) - 128;
-                s[2 * k + 1] = (int)(((a >> 16) + (b >> 16) + 2) >> 2) - 128;
-            }
-        }
-        jpg_dct8(s, o);
-#pragma unroll
-        for (int u = 0; u < 8; u++) ab[i * 6 + blk][y][u] = (o[u] + 128) >> 8;
-    }
-    __syncthreads();
-    // 3. columns, quantisation, scan order: a thread takes one column of one block
-    if (t < JPG_GROUP * 48) {
-        const uint32_t b = t >> 3, u = t & 7, tab = (b % 6) >= 4 ? 64 : 0;
-        int s[8], o[8];
-#pragma unroll
-        for (int y = 0; y < 8; y++) s[y] = ab[b][y][u];
-        jpg_dct8(s, o);
-#pragma unroll
-        for (int v = 0; v < 8; v++) {
-            const uint32_t n = v * 8 + u, Q = s_q[tab + n];
-            const uint32_t dividend = ((uint32_t)abs(o[v]) + (Q << 17)) >> 18;            // below 2^12
-            int q = (int)((dividend * s_recip[tab + n]) >> 20);
-            if (n) q = min(q, 1023);
-            zz[b][s_izig[n]] = (int16_t)(o[v] < 0 ? -q : q);
-        }
-    }
-    __syncthreads();
-    // 4. the bits of each block's AC symbols: a wave takes a block, a lane a coefficient
-    {
-        const uint32_t lane = t & 63, wave = t >> 6;
-        for (uint32_t b = wave; b < JPG_GROUP * 6; b += 4) {
-            const int v = zz[b][lane];
-            const uint8_t *al = s_aclen + ((b % 6) >= 4 ? 256 : 0);
-            const unsigned long long mask = __ballot(v != 0);
-            uint32_t bits = 0;
-            if (lane && v) {
-                const unsigned long long below = mask & ((1ull << lane) - 1ull) & ~1ull;
-                const uint32_t prev = below ? 63u - (uint32_t)__clzll((long long)below) : 0u, run = lane - prev - 1u;
-                const uint32_t cat = (uint32_t)jpg_category(v);
-                bits = (run >> 4) * al[0xF0] + al[((run & 15) << 4) | cat] + cat;
-            } else if (lane == 63) bits = al[0];
-            for (int o = 32; o; o >>= 1) bits += __shfl_xor(bits, o);
-            if (lane == 0) sb[b] = bits;
-        }
-    }
-    __syncthreads();
-    // 5. out: the group's MCUs lie side by side in HBM as well
-    const JpgFrame fr(l, scratch, gridDim.y, f);
-    const uint32_t m0 = r * l.mw + g * JPG_GROUP, nm = min((uint32_t)JPG_GROUP, l.mw - g * JPG_GROUP);
-    uint32_t *dst = (uint32_t *)(fr.coef + (size_t)m0 * 384);
-    for (uint32_t k = t; k < nm * 192; k += 256) dst[k] = ((const uint32_t *)&zz[0][0])[k];
-    if (t < nm * 6) {
-        fr.dcv[(size_t)m0 * 6 + t] = zz[t][0];
-        fr.bbits[(size_t)m0 * 6 + t] = (uint16_t)sb[t];
-    }
+    const uint64_t x = v << (64 - len);
+    const uint32_t i = pos >> 5, s = pos & 31;
+    const uint32_t p0 = (uint32_t)(x >> (32 + s)), p1 = (uint32_t)(x >> s), p2 = s ? (uint32_t)x << (32 - s) : 0u;
+    if (p0) atomicOr(&lds[i], p0);
+    if (p1) atomicOr(&lds[i + 1], p1);
+    if (p2) atomicOr(&lds[i + 2], p2);
 }
 
-// grid.x = mh
-__global__ __launch_bounds__(256) void k_jpg_scan_bits(const JpgLayout l, const JpgHuff hf, uint8_t *__restrict__ scratch)
-{
-    __shared__ uint32_t ws[4];
-    __shared__ uint8_t s_dclen[24];
-    const uint32_t t = threadIdx.x, f = blockIdx.y, r = blockIdx.x;
-    if (t < 24) s_dclen[t] = (&hf.dc_len[0][0])[t];
-    __syncthreads();
-    const JpgFrame fr(l, scratch, gridDim.y, f);
-    uint32_t carry = 0;
-    for (uint32_t x0 = 0; x0 < l.mw; x0 += 256) {
-        const uint32_t mx = x0 + t, m = r * l.mw + mx;
-        uint32_t bits = 0;
-        if (mx < l.mw) {
-#pragma unroll
-            for (int bj = 0; bj < 6; bj++) {
-                const int cat = jpg_category(fr.dcv[(size_t)m * 6 + bj] - jpg_pred(fr.dcv, m, mx, bj));
-                bits += fr.bbits[(size_t)m * 6 + bj] + s_dclen[(bj >= 4 ? 12 : 0) + cat] + cat;
-            }
-        }
-        uint32_t total;
-        const uint32_t at = jpg_scan256(bits, ws, &total);
-        if (mx < l.mw) fr.off[m] = carry + at;
-        carry += total;
-    }
-    if (t == 0) fr.rowbits[r] = carry;
-}
-
-// grid.x = frames
-__global__ __launch_bounds__(LJE_SCAN_THREADS) void k_jpg_rows(const JpgLayout l, uint8_t *__restrict__ scratch, uint32_t nframes)
+// grid.x = frames; chunk: the MCUs a workgroup of the sampling's emit kernel takes, nch = ceil(mw / chunk) of them a row
+__global__ __launch_bounds__(LJE_SCAN_THREADS) void k_jpg_rows(const JpgLayout l, uint8_t *__restrict__ scratch, uint32_t nframes, uint32_t chunk, uint32_t nch)
 {
     __shared__ uint32_t ws[16];
     const uint32_t f = blockIdx.x;
@@ -269,108 +139,28 @@ __global__ __launch_bounds__(LJE_SCAN_THREADS) void k_jpg_rows(const JpgLayout l
     if (!fits) return;
     __syncthreads();
     // the dword in which a workgroup of k_jpg_emit begins is the one the workgroup before it ends in
-    const uint32_t nch = (l.mw + JPG_CHUNK - 1) / JPG_CHUNK;
     for (uint32_t k = threadIdx.x; k < l.mh * nch; k += LJE_SCAN_THREADS) {
         const uint32_t r = k / nch, ch = k - r * nch;
-        if (ch) fr.rowbuf[fr.rowat[r] + (fr.off[r * l.mw + ch * JPG_CHUNK] >> 5)] = 0;
+        if (ch) fr.rowbuf[fr.rowat[r] + (fr.off[r * l.mw + ch * chunk] >> 5)] = 0;
     }
 }
 
-// `len` bits (1 .. 64) of v, the first one at bit `pos` of the MSB-first stream in LDS
-__device__ __forceinline__ void jpg_put(uint32_t *lds, uint32_t pos, uint64_t v, uint32_t len)
-{
-    const uint64_t x = v << (64 - len);
-    const uint32_t i = pos >> 5, s = pos & 31;
-    const uint32_t p0 = (uint32_t)(x >> (32 + s)), p1 = (uint32_t)(x >> s), p2 = s ? (uint32_t)x << (32 - s) : 0u;
-    if (p0) atomicOr(&lds[i], p0);
-    if (p1) atomicOr(&lds[i + 1], p1);
-    if (p2) atomicOr(&lds[i + 2], p2);
-}
-
-// grid.x = ceil(mw / 16) * mh
-__global__ __launch_bounds__(256) void k_jpg_emit(const JpgLayout l, const JpgHuff hf, uint8_t *__restrict__ scratch)
-{
-    constexpr int NB = JPG_CHUNK * 6;
-    __shared__ uint32_t lbits[(NB * JPG_BLOCK_BITS + 31) / 32 + 3];
-    __shared__ __attribute__((aligned(16))) int16_t lc[NB * 64];
-    __shared__ uint16_t s_accode[512], s_dccode[24];
-    __shared__ uint8_t s_aclen[512], s_dclen[24];
-    __shared__ uint32_t boff[NB], ws[4];
-    __shared__ int16_t sd[NB];
-    const uint32_t t = threadIdx.x, f = blockIdx.y;
-    if (((const JpgOut *)scratch)[f].status) return;
-    const JpgFrame fr(l, scratch, gridDim.y, f);
-    const uint32_t nch = (l.mw + JPG_CHUNK - 1) / JPG_CHUNK, r = blockIdx.x / nch, ch = blockIdx.x - r * nch;
-    const uint32_t mx0 = ch * JPG_CHUNK, nm = min((uint32_t)JPG_CHUNK, l.mw - mx0), nblk = nm * 6, m0 = r * l.mw + mx0;
-    s_accode[t] = (&hf.ac_code[0][0])[t];
-    s_accode[t + 256] = (&hf.ac_code[0][0])[t + 256];
-    s_aclen[t] = (&hf.ac_len[0][0])[t];
-    s_aclen[t + 256] = (&hf.ac_len[0][0])[t + 256];
-    if (t < 24) { s_dccode[t] = (&hf.dc_code[0][0])[t]; s_dclen[t] = (&hf.dc_len[0][0])[t]; }
-    {
-        const uint32_t *src = (const uint32_t *)(fr.coef + (size_t)m0 * 384);
-        for (uint32_t k = t; k < nm * 192; k += 256) ((uint32_t *)lc)[k] = src[k];
-    }
-    __syncthreads();
-    uint32_t x = 0;
-    if (t < nblk) {
-        const uint32_t mi = t / 6, bj = t - mi * 6;
-        const int d = fr.dcv[(size_t)m0 * 6 + t] - jpg_pred(fr.dcv, m0 + mi, mx0 + mi, (int)bj), cat = jpg_category(d);
-        sd[t] = (int16_t)d;
-        x = fr.bbits[(size_t)m0 * 6 + t] + s_dclen[(bj >= 4 ? 12 : 0) + cat] + cat;
-    }
-    uint32_t nb;
-    const uint32_t at = jpg_scan256(x, ws, &nb);
-    if (t < nblk) boff[t] = at;
-    const uint32_t begin = fr.off[m0], lead = begin & 31;
-    const bool last = ch == nch - 1;
-    const uint32_t pad = last ? (0u - (begin + nb)) & 7u : 0u, ndw = (lead + nb + pad + 31) >> 5;
-    for (uint32_t k = t; k < ndw + 2; k += 256) lbits[k] = 0;
-    __syncthreads();
-    const uint32_t lane = t & 63, wave = t >> 6;
-    for (uint32_t j = wave; j < nblk; j += 4) {
-        const int v = lc[j * 64 + lane];
-        const uint32_t tab = (j % 6) >= 4 ? 1 : 0;
-        const uint8_t *al = s_aclen + 256 * tab;
-        const uint16_t *ac = s_accode + 256 * tab;
-        const unsigned long long mask = __ballot(v != 0);
-        uint64_t V = 0;
-        uint32_t L = 0;
-        if (lane == 0) {
-            const int d = sd[j];
-            const uint32_t cat = (uint32_t)jpg_category(d);
-            const uint32_t vb = (uint32_t)(d >= 0 ? d : d + (1 << cat) - 1) & ((1u << cat) - 1u);
-            L = s_dclen[12 * tab + cat] + cat;
-            V = ((uint64_t)s_dccode[12 * tab + cat] << cat) | vb;
-        } else if (v) {
-            const unsigned long long below = mask & ((1ull << lane) - 1ull) & ~1ull;
-            const uint32_t prev = below ? 63u - (uint32_t)__clzll((long long)below) : 0u, run = lane - prev - 1u;
-            const uint32_t cat = (uint32_t)jpg_category(v);
-            const uint32_t vb = (uint32_t)(v >= 0 ? v : v + (1 << cat) - 1) & ((1u << cat) - 1u);
-            for (uint32_t z = 0; z < (run >> 4); z++) { V = (V << al[0xF0]) | ac[0xF0]; L += al[0xF0]; }
-            const uint32_t sym = ((run & 15) << 4) | cat, sl = al[sym];
-            V = (V << (sl + cat)) | ((uint64_t)ac[sym] << cat) | vb;
-            L += sl + cat;
-        } else if (lane == 63) {
-            L = al[0];
-            V = ac[0];
-        }
-        uint32_t inc = L;
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += u; }
-        if (L) jpg_put(lbits, lead + boff[j] + inc - L, V, L);
-    }
-    if (t == 0 && pad) jpg_put(lbits, lead + nb, (1u << pad) - 1u, pad);
-    __syncthreads();
-    // the workgroup's dwords: whole ones stored, the two it may share with its neighbours in the row ORed into the zero that
-    // k_jpg_rows put there
-    uint32_t *g = fr.rowbuf + fr.rowat[r] + (begin >> 5);
-    const bool shared_end = !last && ((lead + nb) & 31);
-    for (uint32_t k = t; k < ndw; k += 256) {
-        const uint32_t w = lbits[k];
-        if ((k == 0 && lead) || (k == ndw - 1 && shared_end)) atomicOr(&g[k], w);
-        else g[k] = w;
-    }
-}
+// the three kernels that see blocks, once per sampling
+#define JPG_S MLVFS_AMD_JPEG_420
+#define JPG_K(name) name
+#include "k_jpeg_blocks.inc"
+#undef JPG_S
+#undef JPG_K
+#define JPG_S MLVFS_AMD_JPEG_422
+#define JPG_K(name) name##_422
+#include "k_jpeg_blocks.inc"
+#undef JPG_S
+#undef JPG_K
+#define JPG_S MLVFS_AMD_JPEG_444
+#define JPG_K(name) name##_444
+#include "k_jpeg_blocks.inc"
+#undef JPG_S
+#undef JPG_K
 
 // grid.x = mh
 __global__ __launch_bounds__(256) void k_jpg_count_ff(const JpgLayout l, uint8_t *__restrict__ scratch)
@@ -430,15 +220,22 @@ __global__ __launch_bounds__(256) void k_jpg_stuff(const JpgLayout l, uint8_t *_
     }
 }
 
+// l: jpg_layout() of `sampling`
 int jpg_launch(const uint8_t *d_rgb, size_t stride, const JpgLayout &l, const JpgQuant &q, const JpgHuff &h, uint8_t *d_out, size_t out_stride,
-               uint32_t room, uint8_t *d_scratch, int nframes, hipStream_t s)
+               uint32_t room, uint8_t *d_scratch, int nframes, hipStream_t s, int sampling)
 {
+    if (!jpg_sampling_ok(sampling)) { set_error("jpeg: a sampling of %d", sampling); return MLVFS_AMD_ERR_ARG; }
     if (nframes <= 0) return MLVFS_AMD_OK;
-    const uint32_t n = (uint32_t)nframes, gx = (l.mw + JPG_GROUP - 1) / JPG_GROUP, nch = (l.mw + JPG_CHUNK - 1) / JPG_CHUNK;
-    hipLaunchKernelGGL(k_jpg_transform, dim3(gx * l.mh, n), dim3(256), 0, s, d_rgb, stride, l, q, h, d_scratch);
-    hipLaunchKernelGGL(k_jpg_scan_bits, dim3(l.mh, n), dim3(256), 0, s, l, h, d_scratch);
-    hipLaunchKernelGGL(k_jpg_rows, dim3(n), dim3(LJE_SCAN_THREADS), 0, s, l, d_scratch, n);
-    hipLaunchKernelGGL(k_jpg_emit, dim3(nch * l.mh, n), dim3(256), 0, s, l, h, d_scratch);
+    const uint32_t n = (uint32_t)nframes;
+    const uint32_t gx = (l.mw + kJpgModes[sampling].group - 1) / kJpgModes[sampling].group, nch = (l.mw + kJpgModes[sampling].chunk - 1) / kJpgModes[sampling].chunk;
+    // the three kernels that see blocks, per sampling
+    static constexpr decltype(&k_jpg_transform) transform[3] = { k_jpg_transform, k_jpg_transform_422, k_jpg_transform_444 };
+    static constexpr decltype(&k_jpg_scan_bits) scan_bits[3] = { k_jpg_scan_bits, k_jpg_scan_bits_422, k_jpg_scan_bits_444 };
+    static constexpr decltype(&k_jpg_emit) emit[3] = { k_jpg_emit, k_jpg_emit_422, k_jpg_emit_444 };
+    hipLaunchKernelGGL(transform[sampling], dim3(gx * l.mh, n), dim3(256), 0, s, d_rgb, stride, l, q, h, d_scratch);
+    hipLaunchKernelGGL(scan_bits[sampling], dim3(l.mh, n), dim3(256), 0, s, l, h, d_scratch);
+    hipLaunchKernelGGL(k_jpg_rows, dim3(n), dim3(LJE_SCAN_THREADS), 0, s, l, d_scratch, n, (uint32_t)kJpgModes[sampling].chunk, nch);
+    hipLaunchKernelGGL(emit[sampling], dim3(nch * l.mh, n), dim3(256), 0, s, l, h, d_scratch);
     hipLaunchKernelGGL(k_jpg_count_ff, dim3(l.mh, n), dim3(256), 0, s, l, d_scratch);
     hipLaunchKernelGGL(k_jpg_place, dim3(n), dim3(LJE_SCAN_THREADS), 0, s, l, d_scratch, n, room);
     hipLaunchKernelGGL(k_jpg_stuff, dim3(l.mh, n), dim3(256), 0, s, l, d_scratch, d_out, out_stride);

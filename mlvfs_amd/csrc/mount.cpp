@@ -75,6 +75,7 @@ struct Mount {
     int proxy = 1;                           // mlvfs_amd_mount_set_proxy: 2 = the served frames are binned to half size
     int demosaic = 0;                        // mlvfs_amd_mount_set_demosaic: 1 = the full-size calls demosaic with AMaZE; no serve-order state
     int resample_demosaic = 0;               // mlvfs_amd_mount_set_resample_demosaic: 1 = the resampled calls demosaic with AMaZE; no serve-order state
+    int jpeg_sampling = MLVFS_AMD_JPEG_420;  // mlvfs_amd_mount_set_jpeg_sampling: the chroma sampling of every JPEG call; no serve-order state
     int device = -1;
     DevBuf d_frames, d_out, d_scratch;
     DevBuf d_bits;                           // the encoder's bit streams, sized from a batch's histograms
@@ -175,15 +176,16 @@ struct RgbMode {
     int ow = 0, oh = 0;
 };
 
-// where a JPEG call wants its answers (frame 0 of the batch first), and its quality
+// where a JPEG call wants its answers (frame 0 of the batch first), its quality and its chroma sampling
 struct Jpeg {
     size_t *sizes;
     int *flags;
     int quality;
+    int sampling;
 };
 
 // what the encoder's row buffer has to hold for streams of at most `room` bytes: the rows unstuffed, each begun on a dword
-size_t jpg_rowcap(size_t room, int ph) { return room + 4 * (((size_t)ph + 15) / 16) + 4; }
+size_t jpg_rowcap(size_t room, int ph, int sampling) { return room + 4 * (((size_t)ph + kJpgModes[sampling].mch - 1) / kJpgModes[sampling].mch) + 4; }
 // the stream's room in a JPEG file that is to be no larger than the TIFF (0: there is none)
 size_t jpg_room(int pw, int ph)
 {
@@ -252,8 +254,8 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
         const size_t room = jp ? std::min(jpg_room(pw, ph), sstride) : 0;
         if (room) {
-            const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap(room, ph));
-            const int rj = jpg_encode_batch(dst, rstride, pw, ph, jp->quality, streams, sstride, room, m.d_scratch, l, res.data(), k1 - k0, s);
+            const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap(room, ph, jp->sampling), jp->sampling);
+            const int rj = jpg_encode_batch(dst, rstride, pw, ph, jp->quality, streams, sstride, room, m.d_scratch, l, res.data(), k1 - k0, s, jp->sampling);
             if (rj) return rj;
         }
         for (int k = k0; k < k1; k++) {
@@ -263,7 +265,7 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
                 jp->flags[k] = r.status ? 1 : 0;
                 jp->sizes[k] = r.status ? hdr + served : (size_t)JPG_HEADER_BYTES + r.length;
                 if (!r.status) {
-                    (void)mlvfs_amd_jpeg_header(pw, ph, jp->quality, file, JPG_HEADER_BYTES);
+                    (void)mlvfs_amd_jpeg_header_sampled(pw, ph, jp->quality, jp->sampling, file, JPG_HEADER_BYTES);
                     MLV_HIP(hipMemcpyAsync(file + JPG_HEADER_BYTES, streams + (size_t)(k - k0) * sstride, r.length, hipMemcpyDeviceToHost, s));
                     continue;
                 }
@@ -526,6 +528,16 @@ int mlvfs_amd_mount_set_resample_demosaic(void *mount, int which)
     return MLVFS_AMD_OK;
 }
 
+int mlvfs_amd_mount_set_jpeg_sampling(void *mount, int sampling)
+{
+    if (!mount) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!jpg_sampling_ok(sampling)) { set_error("mount: a JPEG sampling of %d (0: 4:2:0, 1: 4:2:2, 2: 4:4:4)", sampling); return MLVFS_AMD_ERR_ARG; }
+    Mount &m = *(Mount *)mount;
+    std::lock_guard<std::mutex> lk(m.mu);                // between serving calls: a call in flight holds the mutex
+    m.jpeg_sampling = sampling;
+    return MLVFS_AMD_OK;
+}
+
 size_t mlvfs_amd_mount_dng_size(const void *mount, int index)
 {
     if (!mount) { set_error("mount: null argument"); return 0; }
@@ -647,7 +659,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         if (scaled || resampled) { pw = mode.ow; ph = mode.oh; }
         if (pw > 65535 || ph > 65535) { set_error("mount: a JPEG file takes renderings of up to 65535 a side, not %dx%d", pw, ph); return MLVFS_AMD_ERR_ARG; }
         if (const size_t room = full ? jpg_room(pw, ph) : std::min(jpg_room(pw, ph), dstride))
-            scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph)), batch_frames));
+            scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph, m.jpeg_sampling), m.jpeg_sampling), batch_frames));
         if (full) full_bytes += up256(jpg_room(pw, ph)) * batch_frames;                  // ... and their streams behind them
     }
     m.served = true;
@@ -669,7 +681,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream, &cal);
         if (rc == MLVFS_AMD_OK) {
             const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
-            const Jpeg jp{ jpeg_quality ? sizes + f0 : nullptr, jpeg_quality ? flags + f0 : nullptr, jpeg_quality };
+            const Jpeg jp{ jpeg_quality ? sizes + f0 : nullptr, jpeg_quality ? flags + f0 : nullptr, jpeg_quality, m.jpeg_sampling };
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
                              lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr, mode, deep);
         }

@@ -5,14 +5,26 @@ yardstick for csrc/jpeg.cpp and csrc/k_jpeg.hip.  Integers only, so the GPU's st
     header(pw, ph, quality)   -> the 629 bytes in front of the entropy-coded data
     encode(rgb, quality)      -> the entropy-coded data with its RST markers, then EOI
     split_file(data)          -> (header bytes, stream bytes) of a file as served
+    file_sampling(data)       -> the sampling of a file as served: 420, 422 or 444
 
-header + encode is a JFIF file any decoder opens: 4:2:0, the Annex K Huffman tables, one restart interval per MCU row.
+header + encode is a JFIF file any decoder opens: the Annex K Huffman tables, one restart interval per MCU row.  mcus, header,
+coefficients and encode take the chroma sampling as an optional last argument: 420 (the default: MCUs of 16 x 16
+pixels, blocks Y00 Y01 Y10 Y11 Cb Cr), 422 (16 x 8, Y0 Y1 Cb Cr, chroma halved along the row only) or 444 (8 x 8, Y Cb Cr).
 """
 from __future__ import annotations
 
 import numpy as np
 
 HEADER_BYTES = 629                       # mlvfs_amd_jpeg_header_size()
+
+# sampling -> (MCU width, MCU height, luminance blocks per MCU, the sampling factors of component 1 in SOF0, the C interface's number)
+SAMPLINGS = {420: (16, 16, 4, 0x22, 0), 422: (16, 8, 2, 0x21, 1), 444: (8, 8, 1, 0x11, 2)}
+
+
+def _sampling(sampling: int):
+    if sampling not in SAMPLINGS:
+        raise ValueError(f"sampling {sampling!r} is none of 420, 422, 444")
+    return SAMPLINGS[sampling]
 
 BASE_LUMA = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
                       14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
@@ -73,21 +85,22 @@ def qtables(quality: int) -> np.ndarray:
     return np.stack([np.clip((b * scale + 50) // 100, 1, 255) for b in (BASE_LUMA, BASE_CHROMA)]).astype(np.uint8)
 
 
-def mcus(pw: int, ph: int):
-    return (pw + 15) // 16, (ph + 15) // 16
+def mcus(pw: int, ph: int, sampling: int = 420):
+    mcw, mch = _sampling(sampling)[:2]
+    return (pw + mcw - 1) // mcw, (ph + mch - 1) // mch
 
 
-def header(pw: int, ph: int, quality: int) -> bytes:
+def header(pw: int, ph: int, quality: int, sampling: int = 420) -> bytes:
     if pw < 1 or ph < 1 or pw > 65535 or ph > 65535 or pw * ph >= 1 << 25:
         raise ValueError(f"{pw}x{ph} pixels not supported")
     q = qtables(quality)
     out = bytearray(b"\xFF\xD8" b"\xFF\xE0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
     for t in range(2):
         out += b"\xFF\xDB\x00\x43" + bytes([t]) + q[t][ZIGZAG].tobytes()
-    out += b"\xFF\xC0\x00\x11\x08" + ph.to_bytes(2, "big") + pw.to_bytes(2, "big") + b"\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01"
+    out += b"\xFF\xC0\x00\x11\x08" + ph.to_bytes(2, "big") + pw.to_bytes(2, "big") + b"\x03\x01" + bytes([_sampling(sampling)[3]]) + b"\x00\x02\x11\x01\x03\x11\x01"
     for tc_th, spec in zip((0x00, 0x10, 0x01, 0x11), HUFFMAN):
         out += b"\xFF\xC4" + (3 + len(spec)).to_bytes(2, "big") + bytes([tc_th]) + spec
-    out += b"\xFF\xDD\x00\x04" + mcus(pw, ph)[0].to_bytes(2, "big")
+    out += b"\xFF\xDD\x00\x04" + mcus(pw, ph, sampling)[0].to_bytes(2, "big")
     out += b"\xFF\xDA\x00\x0C\x03\x01\x00\x02\x11\x03\x11\x00\x3F\x00"
     assert len(out) == HEADER_BYTES
     return bytes(out)
@@ -114,26 +127,34 @@ def fdct_quantise(blocks: np.ndarray, q: np.ndarray) -> np.ndarray:
     return v
 
 
-def coefficients(rgb: np.ndarray, quality: int, trace: dict | None = None) -> np.ndarray:
-    """(mh, mw, 6, 64): the quantised coefficients in scan (zigzag) order, blocks Y00 Y01 Y10 Y11 Cb Cr"""
+def coefficients(rgb: np.ndarray, quality: int, trace: dict | None = None, sampling: int = 420) -> np.ndarray:
+    """(mh, mw, ny + 2, 64): the quantised coefficients in scan (zigzag) order; the ny luminance blocks of an MCU from left to right (at
+    420 the top row first: Y00 Y01 Y10 Y11), then Cb, Cr"""
     rgb = np.asarray(rgb)
     if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.dtype != np.uint8:
         raise ValueError("a rendering is (H', W', 3) uint8")
+    mcw, mch, ny = _sampling(sampling)[:3]
     ph, pw = rgb.shape[:2]
-    mw, mh = mcus(pw, ph)
+    mw, mh = mcus(pw, ph, sampling)
     q = qtables(quality)
     y, cb, cr, cb0, cr0 = ycbcr(rgb)
     if trace is not None:
         trace.update(cb_range=(int(cb0.min()), int(cb0.max())), cr_range=(int(cr0.min()), int(cr0.max())))     # before the clamps
-    pad = ((0, 16 * mh - ph), (0, 16 * mw - pw))
+    pad = ((0, mch * mh - ph), (0, mcw * mw - pw))
     y, cb, cr = (np.pad(p, pad, mode="edge") for p in (y, cb, cr))
-    half = lambda p: (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + 2) >> 2
-    yb = y.reshape(mh, 2, 8, mw, 2, 8).transpose(0, 3, 1, 4, 2, 5).reshape(mh, mw, 4, 8, 8)
+    if sampling == 420:
+        half = lambda p: (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + 2) >> 2
+    elif sampling == 422:
+        half = lambda p: (p[:, 0::2] + p[:, 1::2] + 1) >> 1
+    else:
+        half = lambda p: p
+    by, bx = mch // 8, mcw // 8                             # luminance blocks down and across an MCU
+    yb = y.reshape(mh, by, 8, mw, bx, 8).transpose(0, 3, 1, 4, 2, 5).reshape(mh, mw, ny, 8, 8)
     cbb, crb = (half(p).reshape(mh, 8, mw, 8).transpose(0, 2, 1, 3) for p in (cb, cr))
-    out = np.empty((mh, mw, 6, 64), np.int64)
-    out[:, :, :4] = fdct_quantise(yb, q[0])
-    out[:, :, 4] = fdct_quantise(cbb, q[1])
-    out[:, :, 5] = fdct_quantise(crb, q[1])
+    out = np.empty((mh, mw, ny + 2, 64), np.int64)
+    out[:, :, :ny] = fdct_quantise(yb, q[0])
+    out[:, :, ny] = fdct_quantise(cbb, q[1])
+    out[:, :, ny + 1] = fdct_quantise(crb, q[1])
     return out[..., ZIGZAG]
 
 
@@ -145,25 +166,26 @@ def _category(v: np.ndarray) -> np.ndarray:
     return cat
 
 
-def encode(rgb: np.ndarray, quality: int, trace: dict | None = None) -> bytes:
+def encode(rgb: np.ndarray, quality: int, trace: dict | None = None, sampling: int = 420) -> bytes:
     """the entropy-coded data of the rendering rgb, (H', W', 3) uint8, with its RST markers, then EOI.  trace: a dict that receives
     what the stream exercised (for the tests)"""
-    co = coefficients(rgb, quality, trace)
+    co = coefficients(rgb, quality, trace, sampling)
     mh, mw = co.shape[:2]
+    ny = co.shape[2] - 2
     tabs = [huffman_codes(s) for s in HUFFMAN]
     # per coefficient: L bits with the value V, in scan order
     L = np.zeros(co.shape, np.int64)
     V = np.zeros(co.shape, np.uint64)
     dc = co[..., 0]
     pred = np.zeros_like(dc)
-    pred[:, :, 1:4] = dc[:, :, 0:3]
-    pred[:, 1:, 0] = dc[:, :-1, 3]
-    pred[:, 1:, 4:] = dc[:, :-1, 4:]
+    pred[:, :, 1:ny] = dc[:, :, 0:ny - 1]
+    pred[:, 1:, 0] = dc[:, :-1, ny - 1]
+    pred[:, 1:, ny:] = dc[:, :-1, ny:]
     d = dc - pred
     dcat = _category(d)
     dbits = np.where(d >= 0, d, d + (1 << dcat) - 1)
     zrl_count = 0
-    for comp, blocks in ((0, slice(0, 4)), (1, slice(4, 6))):
+    for comp, blocks in ((0, slice(0, ny)), (1, slice(ny, ny + 2))):
         dl, dcode = tabs[2 * comp]
         al, acode = tabs[2 * comp + 1]
         c = co[:, :, blocks]
@@ -195,6 +217,7 @@ def encode(rgb: np.ndarray, quality: int, trace: dict | None = None) -> bytes:
         zrl_count += int((zrls * nz).sum())
         if trace is not None:
             trace.setdefault("ac_categories", set()).update(int(x) for x in np.unique(cat[nz]))
+            trace.setdefault("ac_categories_chroma" if comp else "ac_categories_luma", set()).update(int(x) for x in np.unique(cat[nz]))
             trace["ac_clamped"] = trace.get("ac_clamped", False) or bool((np.abs(ac) == 1023).any())
             trace["eob"] = trace.get("eob", False) or bool(eob.any())
             trace["no_eob"] = trace.get("no_eob", False) or bool((~eob).any())
@@ -220,13 +243,13 @@ def encode(rgb: np.ndarray, quality: int, trace: dict | None = None) -> bytes:
         out += flat.tobytes()
         out += bytes([0xFF, 0xD0 + r % 8]) if r + 1 < mh else b"\xFF\xD9"
     if trace is not None:
-        trace.update(dc_categories=set(int(x) for x in np.unique(dcat)), zrl=zrl_count, pads=pads, stuffed=stuffed,
+        trace.update(dc_categories=set(int(x) for x in np.unique(dcat)), dc_categories_luma=set(int(x) for x in np.unique(dcat[:, :, :ny])),
+                     dc_categories_chroma=set(int(x) for x in np.unique(dcat[:, :, ny:])), zrl=zrl_count, pads=pads, stuffed=stuffed,
                      pad_stuffed=pad_stuffed, rows=mh)
     return bytes(out)
 
 
-def split_file(data: bytes):
-    """a file as served -> (header, stream); the header is checked to be the one this module writes for the size it declares"""
+def _split(data: bytes):
     data = bytes(data)
     if len(data) < HEADER_BYTES + 2 or data[:2] != b"\xFF\xD8" or data[-2:] != b"\xFF\xD9":
         raise ValueError("not a file of this module")
@@ -234,6 +257,19 @@ def split_file(data: bytes):
     ph, pw = int.from_bytes(head[163:165], "big"), int.from_bytes(head[165:167], "big")
     q = np.frombuffer(head[25:89], np.uint8)
     for quality in range(1, 101):
-        if np.array_equal(qtables(quality)[0][ZIGZAG], q) and header(pw, ph, quality) == head:
-            return head, data[HEADER_BYTES:]
+        if np.array_equal(qtables(quality)[0][ZIGZAG], q):
+            for sampling in SAMPLINGS:
+                if header(pw, ph, quality, sampling) == head:
+                    return head, data[HEADER_BYTES:], sampling
     raise ValueError("the header is not one of this module's")
+
+
+def split_file(data: bytes):
+    """a file as served -> (header, stream); the header is checked to be the one this module writes for the size it declares, at any of
+    the three samplings (which one: file_sampling)"""
+    return _split(data)[:2]
+
+
+def file_sampling(data: bytes) -> int:
+    """the sampling of a file as served: 420, 422 or 444; ValueError as split_file"""
+    return _split(data)[2]

@@ -88,6 +88,8 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_rgb_amaze_resample_geom", "mlvfs_amd_amaze_resample_dev", "mlvfs_amd_render_resampled_amaze_dev",
     "mlvfs_amd_render_resampled_amaze_look_dev", "mlvfs_amd_render_resampled_amaze_deep_dev", "mlvfs_amd_mount_set_resample_demosaic",
     "mlvfs_amd_test_amz_resample_plan",
+    "mlvfs_amd_jpeg_header_sampled", "mlvfs_amd_jpeg_scratch_bytes_sampled", "mlvfs_amd_jpeg_mcus", "mlvfs_amd_jpeg_encode_sampled_dev",
+    "mlvfs_amd_mount_set_jpeg_sampling",
 ]
 
 
@@ -294,6 +296,11 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_jpeg_scratch_bytes", sz, [i, i, i])
     sig("mlvfs_amd_jpeg_encode_dev", i, [vp, sz, i, i, i, vp, sz, sz, vp, sz, vp, vp, i, vp])
     sig("mlvfs_amd_mount_jpeg", i, [vp, i, i, vp, sz, i, i, vp, vp, i, i, vp])
+    sig("mlvfs_amd_jpeg_header_sampled", sz, [i, i, i, i, vp, sz])
+    sig("mlvfs_amd_jpeg_scratch_bytes_sampled", sz, [i, i, i, i])
+    sig("mlvfs_amd_jpeg_mcus", i, [i, i, i, vp, vp])
+    sig("mlvfs_amd_jpeg_encode_sampled_dev", i, [vp, sz, i, i, i, i, vp, sz, sz, vp, sz, vp, vp, i, vp])
+    sig("mlvfs_amd_mount_set_jpeg_sampling", i, [vp, i])
     sig("mlvfs_amd_rgb_full_geom", i, [i, i, C.POINTER(i), C.POINTER(i)])
     sig("mlvfs_amd_render1_dev", i, [vp, sz, i, i, vp, vp, sz, i, vp])
     sig("mlvfs_amd_mount_rgb_full", i, [vp, i, i, vp, sz, i, i, i, vp])

@@ -66,6 +66,7 @@ class Mount:
         self.proxy = 1
         self.demosaic = "linear"
         self.resample_demosaic = "linear"
+        self.jpeg_sampling = "4:2:0"
         try:
             if dark is not None:
                 self.set_dark(dark)
@@ -115,6 +116,16 @@ class Mount:
             raise ValueError(f'resample demosaic {which!r} ("linear" or "amaze")')
         lib.check(self.L.mlvfs_amd_mount_set_resample_demosaic(self.h, self.DEMOSAICS[which]), "mount_set_resample_demosaic")
         self.resample_demosaic = which
+
+    SAMPLINGS = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}
+
+    def set_jpeg_sampling(self, which: str) -> None:
+        """which: "4:2:0" (the default), "4:2:2" or "4:4:4", the chroma sampling of every later jpeg() call at every size and with either
+        demosaic (mlvfs_amd/jpeg.py: sampling 420, 422, 444).  Allowed at any time between calls; no other call sees it."""
+        if which not in self.SAMPLINGS:
+            raise ValueError(f'JPEG sampling {which!r} ("4:2:0", "4:2:2" or "4:4:4")')
+        lib.check(self.L.mlvfs_amd_mount_set_jpeg_sampling(self.h, self.SAMPLINGS[which]), "mount_set_jpeg_sampling")
+        self.jpeg_sampling = which
 
     def set_proxy(self, factor: int) -> None:
         """factor 2: every frame is served binned to half size, 2 * (W // 4) x 2 * (H // 4), after all other stages; 1: off.  Refused
@@ -235,11 +246,13 @@ class Mount:
         return out
 
     def jpeg(self, first: int, count: int, gain: float = 1.0, quality: int = 90, batch: int = 8, io_threads: int = 0,
-             results: np.ndarray | None = None, full: bool = False, size=None, resample: bool = False):
+             results: np.ndarray | None = None, sampling: str | None = None, full: bool = False, size=None, resample: bool = False):
         """The renderings of rgb() as baseline JPEG files of `quality` (1 .. 100), encoded on the GPU:
         -> (files, flags): files[k] the bytes of file k, flags[k] bit 0 set where the JPEG file would be larger than the TIFF and the
         frame is served as rgb()'s TIFF, byte for byte.  full: the renderings of rgb(full=True); size=(ow, oh): those of rgb(size=size);
-        with resample=True those of rgb(size=size, resample=True)."""
+        with resample=True those of rgb(size=size, resample=True).  sampling: set_jpeg_sampling(sampling) first, which stays set."""
+        if sampling is not None:
+            self.set_jpeg_sampling(sampling)
         size = self._size_arg(size, full, resample)
         gain_q8 = int(round(256 * gain))
         if not 1 <= gain_q8 <= 65535:

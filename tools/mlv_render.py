@@ -16,7 +16,7 @@ that AMaZE rendering instead of the linear one (mlvfs_amd_mount_set_resample_dem
 --bits 16 writes 16-bit TIFF files toned from 16-bit linear light (mlvfs_amd_mount_rgb16 and its forms; "rendered frames at 16 bits"):
 --lut-input's curve on the 16-bit index (linear: the file holds linear light itself), --lut's table behind it if one is given.
 
-    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--resample] [--demosaic amaze] [--jpeg [QUALITY]] [--bits 16] [--lut FILE.cube] [--lut-input srgb|linear|log2:STOPS] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
+    python tools/mlv_render.py SRC.MLV OUTDIR [--gain G] [--full | --size WxH | --fit WxH] [--resample] [--demosaic amaze] [--jpeg [QUALITY]] [--sampling 444|422|420] [--bits 16] [--lut FILE.cube] [--lut-input srgb|linear|log2:STOPS] [--cs N] [--bad-pix N] [--stripes] [--dual-iso N] [--hdr-interp N]
                                              [--pattern-noise] [--deflicker T] [--dark DARK.MLV] [--flat FLAT.MLV]
                                              [--first A] [--count N] [--batch N] [--io-threads N]
 
@@ -24,7 +24,9 @@ OUTDIR/<clip>_000000.tif ... hold (W // 2) x (H // 2) RGB pixels (W x H with --f
 editing program takes the sequence as an offline proxy.  --gain is the only exposure control (the deflicker's bias is not applied: it
 only shapes the frame through the stages in front).  Frames are served in order, as one MLVFS process would serve them.  Nothing is
 overwritten: an existing file of the sequence ends the run before any frame is served.  --jpeg writes OUTDIR/<clip>_000000.jpg ...
-(quality 1 .. 100, 90 if none is given); a frame whose JPEG file would be larger than its TIFF is written as the .tif."""
+(quality 1 .. 100, 90 if none is given); a frame whose JPEG file would be larger than its TIFF is written as the .tif.  --sampling
+chooses their chroma sampling (mlvfs_amd_mount_set_jpeg_sampling; "the chroma sampling of the JPEG files"): 420, the default, halves
+chroma both ways, 422 along the row only, 444 keeps it whole."""
 import argparse
 import os
 import sys
@@ -60,6 +62,7 @@ def main() -> int:
     ap.add_argument("--resample", action="store_true", help="with --size or --fit: any size up to the frame's own, resampled from the full-size "
                     "rendering (not with --full)")
     ap.add_argument("--jpeg", type=int, nargs="?", const=90, default=0, metavar="QUALITY", help="write baseline JPEG files (default quality 90)")
+    ap.add_argument("--sampling", default=None, choices=("444", "422", "420"), help="with --jpeg: the chroma sampling, 4:4:4, 4:2:2 or 4:2:0 (default)")
     ap.add_argument("--bits", type=int, default=8, choices=(8, 16), help="16: 16-bit TIFF files toned from 16-bit linear light through --lut-input's "
                     "curve (and --lut's table behind it, if given); not with --jpeg")
     ap.add_argument("--lut", metavar="FILE.cube", help="a 3D .cube table (domain 0 .. 1, up to 65 a side) applied to every rendering")
@@ -83,6 +86,8 @@ def main() -> int:
         ap.error(f"--gain {a.gain} outside 1 / 256 .. 65535 / 256")
     if a.jpeg and not 1 <= a.jpeg <= 100:
         ap.error(f"--jpeg {a.jpeg} outside 1 .. 100")
+    if a.sampling and not a.jpeg:
+        ap.error("--sampling takes --jpeg: only JPEG files have a chroma sampling")
     if a.bits == 16 and a.jpeg:
         ap.error("--bits 16 --jpeg: there are no 16-bit JPEG files")
     if a.resample and (a.full or not (a.size or a.fit)):
@@ -145,6 +150,8 @@ def main() -> int:
                     m.set_resample_demosaic(a.demosaic)
                 elif a.demosaic != "linear":
                     m.set_demosaic(a.demosaic)
+                if a.sampling:
+                    m.set_jpeg_sampling(":".join(a.sampling))
                 for f0 in range(0, count, a.batch):
                     n = min(a.batch, count - f0)
                     if a.jpeg:
