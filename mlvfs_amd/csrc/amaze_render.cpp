@@ -1,8 +1,9 @@
 // amaze_render.cpp -- rendered full-size frames with AMaZE as the demosaic (include/mlvfs_amd.h, "rendered full-size frames demosaiced
 // by AMaZE"): the geometry, the work memory and its sub-batches, the three passes of a batch (k_amaze_render.hip's balance,
-// amaze_launch of k_amaze.hip / k_amaze_rows.hip as it is, k_amaze_render.hip's tone) and the device entry points with their checks.
-// The resampled form ("resampled rendered frames demosaiced by AMaZE") is the same loop with k_amaze_resample.hip's
-// pass in the place of the tone pass, and has its entry points here too.
+// amaze_launch of k_amaze.hip / k_amaze_rows.hip as it is, k_amaze_render.hip's tone) and the entry points of the passes alone: the
+// balance, and the last pass from three float planes.  The resampled form ("resampled rendered frames demosaiced by AMaZE")
+// is the same loop with k_amaze_resample.hip's pass in the place of the tone pass.  The two routes' own entry points, with every other
+// route's, are in render_route.cpp.
 //
 // Work memory, per (host thread, device), grown on demand: four float planes per frame of a sub-batch (raw, red, green, blue, each kind
 // as one batch of planes plane_stride floats apart) and AMaZE's tile planes, amaze_scratch_bytes per frame.  The tile planes are this
@@ -11,6 +12,7 @@
 // on planes that read as zero where a tile never writes, and for one geometry every tile rewrites exactly what it wrote before.
 #include "clip.h"
 #include "dualiso.h"
+#include "render_route.h"
 
 #include <algorithm>
 #include <map>
@@ -90,7 +92,7 @@ int amaze_batches(ThreadCtx *c, const void *d_frames, size_t stride, const int32
     float *raw = wk.planes, *red = raw + (size_t)sub * p.plane_stride, *green = red + (size_t)sub * p.plane_stride, *blue = green + (size_t)sub * p.plane_stride;
     for (int f0 = 0; f0 < nframes; f0 += sub) {
         const int n = std::min(sub, nframes - f0);
-        const int32_t *par = d_params + (size_t)f0 * 13;
+        const int32_t *par = d_params + (size_t)f0 * RGB_PARAMS;
         int rc = launch_amz_balance((const uint8_t *)d_frames + (size_t)f0 * stride, stride, par, raw, p.plane_stride, w, h, n, stream);
         if (!rc) rc = amaze_launch(raw, w, h, red, green, blue, wk.tiles, stream, n, p.plane_stride, p.tile_stride);
         uint8_t *dst = (uint8_t *)d_out + (size_t)f0 * out_stride;
@@ -107,7 +109,7 @@ int launch_render1_amaze(ThreadCtx *c, const void *d_frames, size_t stride, cons
                          int nframes, hipStream_t stream, const LookArg *lk, bool deep)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!rgb_amaze_geom(w, h)) { set_error("an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_amaze_geom(w, h)) return route_refuse("launch_render1_amaze", { RenderRoute::FULL, true }, w, h);
     return amaze_batches(c, d_frames, stride, d_params, d_out, out_stride, w, h, 0, 0, nframes, stream, lk, deep);
 }
 
@@ -116,10 +118,7 @@ int launch_render_resampled_amaze(ThreadCtx *c, const void *d_frames, size_t str
                                   int h, int ow, int oh, int nframes, hipStream_t stream, const LookArg *lk, bool deep)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!amz_resample_geom(w, h, ow, oh)) {
-        set_error("a resampled AMaZE rendering takes frames of 36x36 up to 2^25 pixels and 65535 a side, the width a multiple of 4, and a size of 1x1 up to the frame's, not %dx%d to %dx%d", w, h, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
+    if (!amz_resample_geom(w, h, ow, oh)) return route_refuse("launch_render_resampled_amaze", { RenderRoute::RESAMPLED, true, ow, oh }, w, h);
     return amaze_batches(c, d_frames, stride, d_params, d_out, out_stride, w, h, ow, oh, nframes, stream, lk, deep);
 }
 
@@ -131,88 +130,52 @@ namespace {
 
 bool overlap(uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return a0 < b0 + bn && b0 < a0 + an; }
 
-// mlvfs_amd_render1_amaze_dev and its look and deep forms: render1's checks with this route's geometry, before any device work
-int render1_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                      int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream, const mlvfs_amd_look16_t *deep = nullptr,
-                      bool with_deep = false)
+// mlvfs_amd_amaze_tone_dev (r: the full-size AMaZE route) and mlvfs_amd_amaze_resample_dev (r: the resampled one): the last pass alone,
+// from three float planes; every check before any device work
+int amaze_plane_dev(const char *who, const RenderRoute &r, const float *d_red, const float *d_green, const float *d_blue, size_t plane_stride,
+                    int width, int height, const int32_t *d_params, void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look,
+                    const mlvfs_amd_look16_t *look16, void *stream)
 {
-    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render1_amaze: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("render1_amaze: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    if (!rgb_amaze_geom(width, height)) { set_error("render1_amaze: %dx%d not supported (36x36 up to 2^25 pixels, the width a multiple of 4)", width, height); return MLVFS_AMD_ERR_ARG; }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * width * height;
-    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render1_amaze: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
-        set_error("render1_amaze: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
+    if (!d_red || !d_green || !d_blue || !d_params || !d_out) { set_error("%s: null argument", who); return MLVFS_AMD_ERR_ARG; }
+    if (look && look16) { set_error("%s: a look and a deep look in one call", who); return MLVFS_AMD_ERR_ARG; }
+    if (nframes < 0) { set_error("%s: negative frame count", who); return MLVFS_AMD_ERR_ARG; }
+    int pw, ph;
+    if (!route_geom(r, width, height, &pw, &ph)) return route_refuse(who, r, width, height);
+    const size_t npix = (size_t)width * height, pimg = (size_t)(look16 ? 6 : 3) * pw * ph;
+    if ((((uintptr_t)d_red | (uintptr_t)d_green | (uintptr_t)d_blue | (uintptr_t)d_params) & 3)) { set_error("%s: planes or parameters off a 4-byte boundary", who); return MLVFS_AMD_ERR_ARG; }
+    if (nframes > 1 && (plane_stride < npix || out_stride < pimg)) {
+        set_error("%s: strides %zu / %zu too small", who, plane_stride, out_stride);
         return MLVFS_AMD_ERR_ARG;
     }
     if (nframes == 0) return MLVFS_AMD_OK;
     const uintptr_t b0 = (uintptr_t)d_out;
-    const size_t bn = (size_t)(nframes - 1) * out_stride + pimg;
-    if (overlap((uintptr_t)d_frames, (size_t)(nframes - 1) * stride + img, b0, bn) || overlap((uintptr_t)d_params, (size_t)nframes * 13 * sizeof(int32_t), b0, bn)) {
-        set_error("render1_amaze: the destination overlaps the source or the parameters (the rendering does not work in place)");
+    const size_t bn = (size_t)(nframes - 1) * out_stride + pimg, an = ((size_t)(nframes - 1) * plane_stride + npix) * sizeof(float);
+    if (overlap((uintptr_t)d_red, an, b0, bn) || overlap((uintptr_t)d_green, an, b0, bn) || overlap((uintptr_t)d_blue, an, b0, bn) ||
+        overlap((uintptr_t)d_params, (size_t)nframes * RGB_PARAMS * sizeof(int32_t), b0, bn)) {
+        set_error("%s: the destination overlaps a plane or the parameters", who);
         return MLVFS_AMD_ERR_ARG;
     }
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
     LookArg lk;
-    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
-    return launch_render1_amaze(c, d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c),
-                                with_look || with_deep ? &lk : nullptr, with_deep);
-}
-
-// mlvfs_amd_render_resampled_amaze_dev and its look and deep forms: render1_amaze's checks with this route's geometry, before any device work
-int render_resampled_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
-                               size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream,
-                               const mlvfs_amd_look16_t *deep = nullptr, bool with_deep = false)
-{
-    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render_resampled_amaze: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("render_resampled_amaze: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    if (!amz_resample_geom(width, height, ow, oh)) {
-        set_error("render_resampled_amaze: %dx%d to %dx%d not supported (36x36 up to 2^25 pixels, 65535 a side, the width a multiple of 4; 1x1 up to the frame's size)", width, height, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * ow * oh;
-    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render_resampled_amaze: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
-        set_error("render_resampled_amaze: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (nframes == 0) return MLVFS_AMD_OK;
-    const uintptr_t b0 = (uintptr_t)d_out;
-    const size_t bn = (size_t)(nframes - 1) * out_stride + pimg;
-    if (overlap((uintptr_t)d_frames, (size_t)(nframes - 1) * stride + img, b0, bn) || overlap((uintptr_t)d_params, (size_t)nframes * 13 * sizeof(int32_t), b0, bn)) {
-        set_error("render_resampled_amaze: the destination overlaps the source or the parameters (the rendering does not work in place)");
-        return MLVFS_AMD_ERR_ARG;
-    }
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    LookArg lk;
-    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
-    return launch_render_resampled_amaze(c, d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c),
-                                         with_look || with_deep ? &lk : nullptr, with_deep);
+    if (look) if (const int rc = look_on_device(look, c, &lk)) return rc;
+    if (look16) if (const int rc = look16_on_device(look16, c, &lk)) return rc;
+    const LookArg *lkp = look || look16 ? &lk : nullptr;
+    hipStream_t s = pick_stream(stream, c);
+    return r.sized() ? launch_amz_resample(d_red, d_green, d_blue, plane_stride, d_params, d_out, out_stride, width, height, pw, ph, nframes, s, lkp, look16 != nullptr)
+                     : launch_amz_tone(d_red, d_green, d_blue, plane_stride, d_params, d_out, out_stride, width, height, nframes, s, lkp, look16 != nullptr);
 }
 
 }  // namespace
 
 extern "C" {
 
-int mlvfs_amd_rgb_amaze_geom(int width, int height, int *pw, int *ph)
-{
-    if (!pw || !ph) { set_error("rgb_amaze_geom: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (!rgb_amaze_geom(width, height)) { set_error("rgb_amaze_geom: %dx%d not supported (36x36 up to 2^25 pixels, the width a multiple of 4)", width, height); return MLVFS_AMD_ERR_ARG; }
-    *pw = width;
-    *ph = height;
-    return MLVFS_AMD_OK;
-}
-
 int mlvfs_amd_amaze_balance_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, float *d_planes,
                                 size_t plane_stride, int nframes, void *stream)
 {
     if (!d_frames || !d_planes || !d_params) { set_error("amaze_balance: null argument"); return MLVFS_AMD_ERR_ARG; }
     if (nframes < 0) { set_error("amaze_balance: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    if (!rgb_amaze_geom(width, height)) { set_error("amaze_balance: %dx%d not supported (36x36 up to 2^25 pixels, the width a multiple of 4)", width, height); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_amaze_geom(width, height)) return route_refuse("amaze_balance", { RenderRoute::FULL, true }, width, height);
     const size_t npix = (size_t)width * height, img = npix * 2;
     if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3) || ((uintptr_t)d_planes & 3)) { set_error("amaze_balance: an odd source address, or parameters or planes off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
     if (nframes > 1 && (stride < img || plane_stride < npix || (stride & 1))) {
@@ -222,7 +185,7 @@ int mlvfs_amd_amaze_balance_dev(const void *d_frames, size_t stride, int width, 
     if (nframes == 0) return MLVFS_AMD_OK;
     const uintptr_t b0 = (uintptr_t)d_planes;
     const size_t bn = ((size_t)(nframes - 1) * plane_stride + npix) * sizeof(float);
-    if (overlap((uintptr_t)d_frames, (size_t)(nframes - 1) * stride + img, b0, bn) || overlap((uintptr_t)d_params, (size_t)nframes * 13 * sizeof(int32_t), b0, bn)) {
+    if (overlap((uintptr_t)d_frames, (size_t)(nframes - 1) * stride + img, b0, bn) || overlap((uintptr_t)d_params, (size_t)nframes * RGB_PARAMS * sizeof(int32_t), b0, bn)) {
         set_error("amaze_balance: the planes overlap the source or the parameters");
         return MLVFS_AMD_ERR_ARG;
     }
@@ -235,110 +198,16 @@ int mlvfs_amd_amaze_tone_dev(const float *d_red, const float *d_green, const flo
                              const int32_t *d_params, void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look,
                              const mlvfs_amd_look16_t *look16, void *stream)
 {
-    if (!d_red || !d_green || !d_blue || !d_params || !d_out) { set_error("amaze_tone: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (look && look16) { set_error("amaze_tone: a look and a deep look in one call"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("amaze_tone: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    if (!rgb_amaze_geom(width, height)) { set_error("amaze_tone: %dx%d not supported (36x36 up to 2^25 pixels, the width a multiple of 4)", width, height); return MLVFS_AMD_ERR_ARG; }
-    const size_t npix = (size_t)width * height, pimg = (size_t)(look16 ? 6 : 3) * npix;
-    if ((((uintptr_t)d_red | (uintptr_t)d_green | (uintptr_t)d_blue | (uintptr_t)d_params) & 3)) { set_error("amaze_tone: planes or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (plane_stride < npix || out_stride < pimg)) {
-        set_error("amaze_tone: strides %zu / %zu too small", plane_stride, out_stride);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (nframes == 0) return MLVFS_AMD_OK;
-    const uintptr_t b0 = (uintptr_t)d_out;
-    const size_t bn = (size_t)(nframes - 1) * out_stride + pimg, an = ((size_t)(nframes - 1) * plane_stride + npix) * sizeof(float);
-    if (overlap((uintptr_t)d_red, an, b0, bn) || overlap((uintptr_t)d_green, an, b0, bn) || overlap((uintptr_t)d_blue, an, b0, bn) ||
-        overlap((uintptr_t)d_params, (size_t)nframes * 13 * sizeof(int32_t), b0, bn)) {
-        set_error("amaze_tone: the destination overlaps a plane or the parameters");
-        return MLVFS_AMD_ERR_ARG;
-    }
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    LookArg lk;
-    if (look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (look16) if (const int rc = look16_on_device(look16, c, &lk)) return rc;
-    return launch_amz_tone(d_red, d_green, d_blue, plane_stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c),
-                           look || look16 ? &lk : nullptr, look16 != nullptr);
-}
-
-int mlvfs_amd_render1_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
-                                size_t out_stride, int nframes, void *stream)
-{
-    return render1_amaze_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream);
-}
-
-int mlvfs_amd_render1_amaze_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
-                                     size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
-{
-    return render1_amaze_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, look, true, stream);
-}
-
-int mlvfs_amd_render1_amaze_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
-                                     size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
-{
-    return render1_amaze_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream, look, true);
-}
-
-int mlvfs_amd_rgb_amaze_resample_geom(int width, int height, int ow, int oh)
-{
-    if (!amz_resample_geom(width, height, ow, oh)) {
-        set_error("rgb_amaze_resample_geom: %dx%d to %dx%d not supported (36x36 up to 2^25 pixels, 65535 a side, the width a multiple of 4; 1x1 up to the frame's size)", width, height, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    return MLVFS_AMD_OK;
+    return amaze_plane_dev("amaze_tone", { RenderRoute::FULL, true }, d_red, d_green, d_blue, plane_stride, width, height, d_params, d_out, out_stride,
+                           nframes, look, look16, stream);
 }
 
 int mlvfs_amd_amaze_resample_dev(const float *d_red, const float *d_green, const float *d_blue, size_t plane_stride, int width, int height,
                                  const int32_t *d_params, int ow, int oh, void *d_out, size_t out_stride, int nframes,
                                  const mlvfs_amd_look_t *look, const mlvfs_amd_look16_t *look16, void *stream)
 {
-    if (!d_red || !d_green || !d_blue || !d_params || !d_out) { set_error("amaze_resample: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (look && look16) { set_error("amaze_resample: a look and a deep look in one call"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("amaze_resample: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    if (!amz_resample_geom(width, height, ow, oh)) {
-        set_error("amaze_resample: %dx%d to %dx%d not supported (36x36 up to 2^25 pixels, 65535 a side, the width a multiple of 4; 1x1 up to the frame's size)", width, height, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    const size_t npix = (size_t)width * height, pimg = (size_t)(look16 ? 6 : 3) * ow * oh;
-    if ((((uintptr_t)d_red | (uintptr_t)d_green | (uintptr_t)d_blue | (uintptr_t)d_params) & 3)) { set_error("amaze_resample: planes or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (plane_stride < npix || out_stride < pimg)) {
-        set_error("amaze_resample: strides %zu / %zu too small", plane_stride, out_stride);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (nframes == 0) return MLVFS_AMD_OK;
-    const uintptr_t b0 = (uintptr_t)d_out;
-    const size_t bn = (size_t)(nframes - 1) * out_stride + pimg, an = ((size_t)(nframes - 1) * plane_stride + npix) * sizeof(float);
-    if (overlap((uintptr_t)d_red, an, b0, bn) || overlap((uintptr_t)d_green, an, b0, bn) || overlap((uintptr_t)d_blue, an, b0, bn) ||
-        overlap((uintptr_t)d_params, (size_t)nframes * 13 * sizeof(int32_t), b0, bn)) {
-        set_error("amaze_resample: the destination overlaps a plane or the parameters");
-        return MLVFS_AMD_ERR_ARG;
-    }
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    LookArg lk;
-    if (look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (look16) if (const int rc = look16_on_device(look16, c, &lk)) return rc;
-    return launch_amz_resample(d_red, d_green, d_blue, plane_stride, d_params, d_out, out_stride, width, height, ow, oh, nframes,
-                               pick_stream(stream, c), look || look16 ? &lk : nullptr, look16 != nullptr);
-}
-
-int mlvfs_amd_render_resampled_amaze_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                         void *d_out, size_t out_stride, int nframes, void *stream)
-{
-    return render_resampled_amaze_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream);
-}
-
-int mlvfs_amd_render_resampled_amaze_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                              void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
-{
-    return render_resampled_amaze_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, look, true, stream);
-}
-
-int mlvfs_amd_render_resampled_amaze_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                              void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
-{
-    return render_resampled_amaze_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream, look, true);
+    return amaze_plane_dev("amaze_resample", { RenderRoute::RESAMPLED, true, ow, oh }, d_red, d_green, d_blue, plane_stride, width, height, d_params, d_out,
+                           out_stride, nframes, look, look16, stream);
 }
 
 /* test hook, host only: how launch_amz_resample would divide a launch among workgroups.  out[0]: 1 the x16 form (for aligned planes), 0

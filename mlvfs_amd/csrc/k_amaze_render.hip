@@ -183,7 +183,7 @@ int launch_amz_balance(const void *d_frames, size_t stride, const int32_t *d_par
                        int nframes, hipStream_t stream)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!rgb_amaze_geom(w, h)) { set_error("an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_amaze_geom(w, h)) return route_refuse("launch_amz", { RenderRoute::FULL, true }, w, h);
     const uint32_t npix = (uint32_t)w * (uint32_t)h;
     const bool fast = w % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && ((uintptr_t)d_planes % 16 == 0) &&
                       (nframes == 1 || (stride % 16 == 0 && plane_stride % 4 == 0));
@@ -202,7 +202,7 @@ int launch_amz_tone(const float *d_red, const float *d_green, const float *d_blu
                     size_t out_stride, int w, int h, int nframes, hipStream_t stream, const LookArg *lk, bool deep)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!rgb_amaze_geom(w, h)) { set_error("an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_amaze_geom(w, h)) return route_refuse("launch_amz", { RenderRoute::FULL, true }, w, h);
     const uint32_t npix = (uint32_t)w * (uint32_t)h;
     const size_t oa = deep ? 16 : 8;                                                     // what the fast form's stores need
     const bool fast = w % 16 == 0 && (((uintptr_t)d_red | (uintptr_t)d_green | (uintptr_t)d_blue) % 16 == 0) && ((uintptr_t)d_out % oa == 0) &&
@@ -210,15 +210,11 @@ int launch_amz_tone(const float *d_red, const float *d_green, const float *d_blu
     const RenderParams *par = (const RenderParams *)d_params;
     uint8_t *out = (uint8_t *)d_out;
     if (fast) {
-        const dim3 grid = amz_grid(npix / 8, nframes);
-        if (deep) hipLaunchKernelGGL(k_amz_tone_deep_x16, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix / 8, *lk);
-        else if (lk) hipLaunchKernelGGL(k_amz_tone_look_x16, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix / 8, *lk);
-        else hipLaunchKernelGGL(k_amz_tone_x16, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix / 8);
+        launch_tone(k_amz_tone_deep_x16, k_amz_tone_look_x16, k_amz_tone_x16, amz_grid(npix / 8, nframes), stream, lk, deep, d_red, d_green, d_blue,
+                    plane_stride, par, out, out_stride, npix / 8);
     } else {
-        const dim3 grid = amz_grid(npix, nframes);
-        if (deep) hipLaunchKernelGGL(k_amz_tone_deep_generic, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix, *lk);
-        else if (lk) hipLaunchKernelGGL(k_amz_tone_look_generic, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix, *lk);
-        else hipLaunchKernelGGL(k_amz_tone_generic, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix);
+        launch_tone(k_amz_tone_deep_generic, k_amz_tone_look_generic, k_amz_tone_generic, amz_grid(npix, nframes), stream, lk, deep, d_red, d_green,
+                    d_blue, plane_stride, par, out, out_stride, npix);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

@@ -258,10 +258,7 @@ int launch_amz_resample(const float *d_red, const float *d_green, const float *d
                         size_t out_stride, int w, int h, int ow, int oh, int nframes, hipStream_t stream, const LookArg *lk, bool deep)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!amz_resample_geom(w, h, ow, oh)) {
-        set_error("a resampled AMaZE rendering takes frames of 36x36 up to 2^25 pixels and 65535 a side, the width a multiple of 4, and a size of 1x1 up to the frame's, not %dx%d to %dx%d", w, h, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
+    if (!amz_resample_geom(w, h, ow, oh)) return route_refuse("launch_amz_resample", { RenderRoute::RESAMPLED, true, ow, oh }, w, h);
     const bool fast = amz_resample_fast_geom(w, ow) && (((uintptr_t)d_red | (uintptr_t)d_green | (uintptr_t)d_blue) % 16 == 0) &&
                       (nframes == 1 || plane_stride % 4 == 0) &&
                       (!deep || ((uintptr_t)d_out % 2 == 0 && (nframes == 1 || out_stride % 2 == 0)));      // 16-bit stores
@@ -271,16 +268,14 @@ int launch_amz_resample(const float *d_red, const float *d_green, const float *d
         const ResamplePlan pl = resample_plan(w, h, ow, oh, nframes);
         const AmzResampleArgs a{ (uint32_t)w, (uint32_t)h, (uint32_t)ow, (uint32_t)oh, pl.uo, pl.nstrips, pl.bo, scdiv_make((uint32_t)w), scdiv_make((uint32_t)h) };
         const dim3 grid(pl.nstrips * pl.nbands, nframes);
-        if (deep) hipLaunchKernelGGL(k_amz_resample_deep_x16, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, a, *lk);
-        else if (lk) hipLaunchKernelGGL(k_amz_resample_look_x16, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, a, *lk);
-        else hipLaunchKernelGGL(k_amz_resample_x16, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, a);
+        launch_tone(k_amz_resample_deep_x16, k_amz_resample_look_x16, k_amz_resample_x16, grid, stream, lk, deep, d_red, d_green, d_blue, plane_stride,
+                    par, out, out_stride, a);
     } else {
         const uint32_t npix = (uint32_t)ow * (uint32_t)oh, cap = std::max(2048u / (uint32_t)nframes, 64u);
         const dim3 grid(std::min<uint32_t>((npix + 255) / 256, 4 * cap), nframes);
         const uint32_t uw = (uint32_t)w, uh = (uint32_t)h, uow = (uint32_t)ow, uoh = (uint32_t)oh;
-        if (deep) hipLaunchKernelGGL(k_amz_resample_deep_generic, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix, uw, uh, uow, uoh, *lk);
-        else if (lk) hipLaunchKernelGGL(k_amz_resample_look_generic, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix, uw, uh, uow, uoh, *lk);
-        else hipLaunchKernelGGL(k_amz_resample_generic, grid, dim3(256), 0, stream, d_red, d_green, d_blue, plane_stride, par, out, out_stride, npix, uw, uh, uow, uoh);
+        launch_tone(k_amz_resample_deep_generic, k_amz_resample_look_generic, k_amz_resample_generic, grid, stream, lk, deep, d_red, d_green, d_blue,
+                    plane_stride, par, out, out_stride, npix, uw, uh, uow, uoh);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

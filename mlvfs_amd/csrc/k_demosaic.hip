@@ -210,34 +210,20 @@ int launch_render1(const void *d_frames, size_t stride, const int32_t *d_params,
                    hipStream_t stream, const LookArg *lk, bool deep)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!rgb_full_geom(w, h)) { set_error("a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_full_geom(w, h)) return route_refuse("launch_render1", { RenderRoute::FULL }, w, h);
     const size_t oa = deep ? 16 : 8;                                                     // what the fast form's stores need
     const bool fast = w % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && ((uintptr_t)d_out % oa == 0) &&
                       (nframes == 1 || (stride % 16 == 0 && out_stride % oa == 0));
     if (fast) {
         const uint32_t strips = ((uint32_t)w + R1_STRIP - 1) / R1_STRIP, runs = ((uint32_t)h + R1_RUN - 1) / R1_RUN;
-        if (deep)
-            hipLaunchKernelGGL(k_render1_deep_x16, dim3(strips * runs, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_render1_look_x16, dim3(strips * runs, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips, *lk);
-        else
-            hipLaunchKernelGGL(k_render1_x16, dim3(strips * runs, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips);
+        launch_tone(k_render1_deep_x16, k_render1_look_x16, k_render1_x16, dim3(strips * runs, nframes), stream, lk, deep, (const uint8_t *)d_frames,
+                    stride, (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, w, h, strips);
     } else {
         // the workgroups of a launch share the machine: each of them stages the table once, and the lanes stride over the rest
         const uint32_t npix = (uint32_t)w * (uint32_t)h, cap = 4 * std::max(2048u / (uint32_t)nframes, 64u);
         const dim3 grid(std::min<uint32_t>((npix + 255) / 256, cap), nframes);
-        if (deep)
-            hipLaunchKernelGGL(k_render1_deep_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, w, h, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_render1_look_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, w, h, *lk);
-        else
-            hipLaunchKernelGGL(k_render1_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, w, h);
+        launch_tone(k_render1_deep_generic, k_render1_look_generic, k_render1_generic, grid, stream, lk, deep, (const uint8_t *)d_frames, stride,
+                    (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, npix, w, h);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

@@ -173,7 +173,7 @@ int launch_render2(const void *d_frames, size_t stride, const int32_t *d_params,
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
     int pw, ph;
-    if (!rgb_geom(w, h, &pw, &ph)) { set_error("a rendering takes frames of 2x2 up to 2^27 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+    if (!rgb_geom(w, h, &pw, &ph)) return route_refuse("launch_render2", { RenderRoute::HALF }, w, h);
     const size_t oa = deep ? 16 : 8;                                                     // what the fast form's stores need
     const bool fast = w % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && ((uintptr_t)d_out % oa == 0) &&
                       (nframes == 1 || (stride % 16 == 0 && out_stride % oa == 0));
@@ -182,27 +182,13 @@ int launch_render2(const void *d_frames, size_t stride, const int32_t *d_params,
     if (fast) {
         const uint32_t gpr = (uint32_t)w / 16, groups = gpr * (uint32_t)ph;
         const dim3 grid(std::min<uint32_t>((groups + 255) / 256, cap), nframes);
-        if (deep)
-            hipLaunchKernelGGL(k_render2_deep_x16, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, groups, gpr, (uint32_t)w / 8, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_render2_look_x16, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, groups, gpr, (uint32_t)w / 8, *lk);
-        else
-            hipLaunchKernelGGL(k_render2_x16, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, groups, gpr, (uint32_t)w / 8);
+        launch_tone(k_render2_deep_x16, k_render2_look_x16, k_render2_x16, grid, stream, lk, deep, (const uint8_t *)d_frames, stride,
+                    (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, groups, gpr, (uint32_t)w / 8);
     } else {
         const uint32_t npix = (uint32_t)pw * (uint32_t)ph;
         const dim3 grid(std::min<uint32_t>((npix + 255) / 256, 4 * cap), nframes);
-        if (deep)
-            hipLaunchKernelGGL(k_render2_deep_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_render2_look_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, *lk);
-        else
-            hipLaunchKernelGGL(k_render2_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw);
+        launch_tone(k_render2_deep_generic, k_render2_look_generic, k_render2_generic, grid, stream, lk, deep, (const uint8_t *)d_frames, stride,
+                    (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

@@ -269,37 +269,20 @@ int launch_render_resampled(const void *d_frames, size_t stride, const int32_t *
                             int oh, int nframes, hipStream_t stream, const LookArg *lk, bool deep)
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
-    if (!resample_geom(w, h, ow, oh)) {
-        set_error("a resampled rendering takes frames of 4x4 up to 2^25 pixels and 65535 a side and a size of 1x1 up to the frame's, not %dx%d to %dx%d", w, h, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
+    if (!resample_geom(w, h, ow, oh)) return route_refuse("launch_render_resampled", { RenderRoute::RESAMPLED, false, ow, oh }, w, h);
     const bool fast = resample_fast_geom(w, ow) && ((uintptr_t)d_frames % 16 == 0) && (nframes == 1 || stride % 16 == 0) &&
                       (!deep || ((uintptr_t)d_out % 2 == 0 && (nframes == 1 || out_stride % 2 == 0)));      // 16-bit stores
     if (fast) {
         const ResamplePlan pl = resample_plan(w, h, ow, oh, nframes);
         const ResampleArgs a{ (uint32_t)w, (uint32_t)h, (uint32_t)ow, (uint32_t)oh, pl.uo, pl.nstrips, pl.bo, scdiv_make((uint32_t)w), scdiv_make((uint32_t)h) };
         const dim3 grid(pl.nstrips * pl.nbands, nframes);
-        if (deep)
-            hipLaunchKernelGGL(k_resample_deep_x16, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, a, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_resample_look_x16, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, a, *lk);
-        else
-            hipLaunchKernelGGL(k_resample_x16, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, a);
+        launch_tone(k_resample_deep_x16, k_resample_look_x16, k_resample_x16, grid, stream, lk, deep, (const uint8_t *)d_frames, stride,
+                    (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a);
     } else {
         const uint32_t npix = (uint32_t)ow * (uint32_t)oh, cap = std::max(2048u / (uint32_t)nframes, 64u);
         const dim3 grid(std::min<uint32_t>((npix + 255) / 256, 4 * cap), nframes);
-        if (deep)
-            hipLaunchKernelGGL(k_resample_deep_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, w, h, (uint32_t)ow, (uint32_t)oh, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_resample_look_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, w, h, (uint32_t)ow, (uint32_t)oh, *lk);
-        else
-            hipLaunchKernelGGL(k_resample_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, w, h, (uint32_t)ow, (uint32_t)oh);
+        launch_tone(k_resample_deep_generic, k_resample_look_generic, k_resample_generic, grid, stream, lk, deep, (const uint8_t *)d_frames, stride,
+                    (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, npix, w, h, (uint32_t)ow, (uint32_t)oh);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

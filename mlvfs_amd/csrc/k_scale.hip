@@ -256,37 +256,20 @@ int launch_render_scaled(const void *d_frames, size_t stride, const int32_t *d_p
 {
     if (nframes <= 0) return MLVFS_AMD_OK;
     int pw, ph;
-    if (!scale_geom(w, h, ow, oh, &pw, &ph)) {
-        set_error("a scaled rendering takes frames of 2x2 up to 2^27 pixels and 131071 a side and a size of 1x1 up to half the frame's, not %dx%d to %dx%d", w, h, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
+    if (!scale_geom(w, h, ow, oh, &pw, &ph)) return route_refuse("launch_render_scaled", { RenderRoute::SCALED, false, ow, oh }, w, h);
     const bool fast = w % 16 == 0 && ((uintptr_t)d_frames % 16 == 0) && (nframes == 1 || stride % 16 == 0) &&
                       (!deep || ((uintptr_t)d_out % 2 == 0 && (nframes == 1 || out_stride % 2 == 0)));      // 16-bit stores
     if (fast) {
         const ScalePlan pl = scale_plan(pw, ph, ow, oh, nframes);
         const ScaleArgs a{ (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, pl.uo, pl.nstrips, pl.bo, (uint32_t)w / 8,
                            scdiv_make((uint32_t)pw), scdiv_make((uint32_t)ph) };
-        if (deep)
-            hipLaunchKernelGGL(k_scale_deep_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_scale_look_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a, *lk);
-        else
-            hipLaunchKernelGGL(k_scale_x16, dim3(pl.nstrips * pl.nbands, nframes), dim3(256), 0, stream, (const uint8_t *)d_frames, stride,
-                               (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a);
+        launch_tone(k_scale_deep_x16, k_scale_look_x16, k_scale_x16, dim3(pl.nstrips * pl.nbands, nframes), stream, lk, deep, (const uint8_t *)d_frames,
+                    stride, (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, a);
     } else {
         const uint32_t npix = (uint32_t)ow * (uint32_t)oh, cap = std::max(2048u / (uint32_t)nframes, 64u);
         const dim3 grid(std::min<uint32_t>((npix + 255) / 256, 4 * cap), nframes);
-        if (deep)
-            hipLaunchKernelGGL(k_scale_deep_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, *lk);
-        else if (lk)
-            hipLaunchKernelGGL(k_scale_look_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh, *lk);
-        else
-            hipLaunchKernelGGL(k_scale_generic, grid, dim3(256), 0, stream, (const uint8_t *)d_frames, stride, (const RenderParams *)d_params,
-                               (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh);
+        launch_tone(k_scale_deep_generic, k_scale_look_generic, k_scale_generic, grid, stream, lk, deep, (const uint8_t *)d_frames, stride,
+                    (const RenderParams *)d_params, (uint8_t *)d_out, out_stride, npix, (uint32_t)w, (uint32_t)pw, (uint32_t)ph, (uint32_t)ow, (uint32_t)oh);
     }
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;

@@ -2,6 +2,7 @@
 // multiplication (ScDiv, scdiv_make: clip.h).
 #pragma once
 #include "clip.h"
+#include "render_route.h"
 
 namespace mlv {
 namespace {                    // every including file's own copy

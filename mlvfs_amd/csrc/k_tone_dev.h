@@ -12,8 +12,10 @@
 //             nothing in LDS and has no barrier at entry --, then 4b and 4c as above, or nothing where N = 0 (uniform in a launch);
 //             no 4d: three 16-bit samples per pixel.  t <= 65535 and u <= 65535, so every gather is in bounds whatever S16 holds.
 // A kernel body is a template on the form (Tone); its plain __global__ form passes an empty LookArg that no instruction reads.
+// The host side picks among a kernel's three __global__ forms in one place, launch_tone.
 #pragma once
 #include "clip.h"
+#include "render_route.h"
 
 #define MLV_SRGB_LUT12_ATTR __device__ __attribute__((aligned(16)))          // stage_lut reads it in 16-byte pieces
 #include "srgb_lut12.h"
@@ -27,12 +29,22 @@ namespace mlv {
 
 enum Tone { PLAIN, LOOK, DEEP };           // the three forms of steps 3 and 4
 
-struct RenderParams {          // mlvfs_amd_rgb_params' out[13]
+struct RenderParams {          // mlvfs_amd_rgb_params' out[RGB_PARAMS]
     int32_t black, A[3], K[9];
 };
-static_assert(sizeof(RenderParams) == 13 * sizeof(int32_t), "mlvfs_amd_rgb_params' layout");
+static_assert(sizeof(RenderParams) == RGB_PARAMS * sizeof(int32_t), "mlvfs_amd_rgb_params' layout");
 
 namespace {                    // every including file's own copy
+
+// host side: one of a kernel's three forms launched with 256 lanes a workgroup -- the deep form with *lk, the look form with *lk, or
+// the plain form, which takes no look -- and otherwise the same arguments
+template <class KDeep, class KLook, class KPlain, class... Args>
+void launch_tone(KDeep k_deep, KLook k_look, KPlain k_plain, const dim3 &grid, hipStream_t stream, const LookArg *lk, bool deep, Args... args)
+{
+    if (deep) hipLaunchKernelGGL(k_deep, grid, dim3(256), 0, stream, args..., *lk);
+    else if (lk) hipLaunchKernelGGL(k_look, grid, dim3(256), 0, stream, args..., *lk);
+    else hipLaunchKernelGGL(k_plain, grid, dim3(256), 0, stream, args...);
+}
 
 // bytes of the table a workgroup stages: the sRGB bytes, or the look's shaper (a deep kernel stages none and declares none)
 template <Tone TN> constexpr int TONE_LDS = TN == LOOK ? LOOK_SHAPER_BYTES : 4096;

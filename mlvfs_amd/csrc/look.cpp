@@ -7,6 +7,7 @@
 // A deep look (include/mlvfs_amd.h, "rendered frames at 16 bits") is the same with a shaper of 65536 uint16 on the 16-bit
 // index -- [0, 131072) S16, then the entries -- and n = 0 for no table at all; mlvfs_amd_look16_*.
 #include "clip.h"
+#include "render_route.h"
 
 #include <cstring>
 #include <vector>

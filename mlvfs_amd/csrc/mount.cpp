@@ -1,5 +1,12 @@
 // mount.cpp -- a clip served as MLVFS serves it: process_frame (mlvfs/main.c:908-1005) and the two dng_get_header_data calls of it,
-// batch by batch, for every mount option that shapes a frame's .dng file.
+// batch by batch, for every mount option that shapes a frame's .dng file -- and, behind the last of those stages, what MLVFS does not
+// serve: the frames losslessly compressed, binned to proxies, or rendered to TIFF and JPEG files.
+//
+// The file holds the handle, its setters and size calls, and one path for every serving call: an exported call states what it asks for
+// (Serve), mount_serve checks it and settles under the handle's lock what the handle decides -- for a rendering its route (mount_route:
+// the size kind of the call and the handle's two demosaic settings) and from the route's geometry the size that comes out, once --,
+// and serve_batch runs the stages and hands the final frames to the plain copy, fetch_lossless or fetch_rgb.  What a route takes, how it
+// words a refusal and which launcher it has is render_route.h's; the device entry points that render without a mount are there too.
 //
 // Per batch, in main.c's order: read + decode / unpack (the reader's staging, mlvreader.cpp; with a dark frame or a flat field set -- which main.c does
 // not know -- the subtraction, stage 0, and the gain, stage 0b, in the same load: k_cal.hip), deflicker (one histogram launch, one
@@ -51,6 +58,7 @@
 #include "clip.h"
 #include "lj92enc.h"
 #include "jpeg.h"
+#include "render_route.h"
 
 #include <cstring>
 #include <string>
@@ -79,7 +87,7 @@ struct Mount {
     int device = -1;
     DevBuf d_frames, d_out, d_scratch;
     DevBuf d_bits;                           // the encoder's bit streams, sized from a batch's histograms
-    DevBuf d_rgb;                            // mlvfs_amd_mount_rgb: 13 int32 parameters per frame of a batch
+    DevBuf d_rgb;                            // mlvfs_amd_mount_rgb: RGB_PARAMS int32 per frame of a batch
     std::vector<int32_t> rgb_host;           // what the upload reads: it outlives every call
     DevBuf d_full;                           // the full-size calls: a batch's renderings of 3 W H bytes (6 W H once a 16-bit call needs
                                              // them), a JPEG call's streams behind them
@@ -94,13 +102,30 @@ struct Mount {
         return d_scratch.reserve(sbytes);
     }
     // after ensure(): the device is this handle's
-    int ensure_rgb(int frames) { return d_rgb.reserve((size_t)frames * 13 * sizeof(int32_t)); }
+    int ensure_rgb(int frames) { return d_rgb.reserve((size_t)frames * RGB_PARAMS * sizeof(int32_t)); }
 };
 
-// where a lossless call wants its answers (frame 0 of the batch first)
-struct Lossless {
-    size_t *sizes;
-    int *flags;
+// what a serving call asks for, beyond its frames and its room.  mount_serve fills in what the handle decides (the route's demosaic,
+// the chroma sampling) and the size of a rendering, once; a batch gets a copy whose sizes and flags begin at its own frame 0
+struct Serve {
+    bool lossless = false;                   // mlvfs_amd_mount_dng_lossless: sizes and flags are the encoder's answers
+    int gain_q8 = 0;                         // != 0: served rendered, and no .dng header is written -- a file may be smaller than one
+    int quality = 0;                         // != 0: as JPEG files; sizes and flags are that encoder's answers
+    RenderRoute route{};                     // which rendering
+    const mlvfs_amd_look16_t *deep = nullptr;    // as 16-bit TIFF files through this deep look (never m.look, never JPEG)
+    size_t *sizes = nullptr;
+    int *flags = nullptr;
+    int sampling = MLVFS_AMD_JPEG_420;       // the handle's, as the call found it
+    int pw = 0, ph = 0;                      // the rendering's size
+
+    bool in_full() const { return route.size == RenderRoute::FULL || route.size == RenderRoute::RESAMPLED; }     // the renderings lie in d_full
+    size_t bpx() const { return deep ? 6 : 3; }
+    Serve from(int f0) const
+    {
+        Serve b = *this;
+        if (sizes) { b.sizes += f0; b.flags += f0; }
+        return b;
+    }
 };
 
 // the encoder's room in a mount: the bit streams in a buffer of their own that grows with what a batch needs, the streams
@@ -133,7 +158,7 @@ size_t o_pn_bytes(const mlvfs_amd_mount_opts_t &o, int w, int h, int batch)
 // hdr_max[k]: the max_size the frame's header was last written with.  A frame that is not to be served compressed gets its pixels.
 // w x h: the frames at final_at as they are served -- the clip's size, or with a proxy set the binned one
 int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at,
-                   const std::vector<size_t> &hdr_max, uint8_t *h_out, size_t out_stride, const Lossless &ll, int w, int h)
+                   const std::vector<size_t> &hdr_max, uint8_t *h_out, size_t out_stride, const Serve &ll, int w, int h)
 {
     hipStream_t s = c->stream;
     const size_t img = (size_t)w * h * 2, hdr = dng_get_header_size();
@@ -169,20 +194,15 @@ int fetch_lossless(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstr
     return MLVFS_AMD_OK;
 }
 
-// which rendering a call serves: half size, the frame's own size, ow x oh area-averaged from the half-size grid, or ow x oh
-// area-averaged from the full-size rendering
-struct RgbMode {
-    enum Kind { HALF, FULL, SCALED, RESAMPLED } kind = HALF;
-    int ow = 0, oh = 0;
-};
-
-// where a JPEG call wants its answers (frame 0 of the batch first), its quality and its chroma sampling
-struct Jpeg {
-    size_t *sizes;
-    int *flags;
-    int quality;
-    int sampling;
-};
+// the route a call of size kind `size` takes on a handle with these two demosaic settings, and the only place that knows how they
+// apply: set_demosaic's AMaZE is for the full-size calls, the resampled calls have set_resample_demosaic's own, the others neither.
+// *unserved (where asked for): AMaZE is set for the full-size calls alone, which leaves the resampled calls refused
+RenderRoute mount_route(RenderRoute::Size size, int ow, int oh, int demosaic, int resample_demosaic, bool *unserved = nullptr)
+{
+    const bool resampled = size == RenderRoute::RESAMPLED;
+    if (unserved) *unserved = resampled && demosaic == 1 && resample_demosaic != 1;
+    return { size, resampled ? resample_demosaic == 1 : size == RenderRoute::FULL && demosaic == 1, ow, oh };
+}
 
 // what the encoder's row buffer has to hold for streams of at most `room` bytes: the rows unstuffed, each begun on a dword
 size_t jpg_rowcap(size_t room, int ph, int sampling) { return room + 4 * (((size_t)ph + kJpgModes[sampling].mch - 1) / kJpgModes[sampling].mch) + 4; }
@@ -193,79 +213,61 @@ size_t jpg_room(int pw, int ph)
     return tiff > (size_t)JPG_HEADER_BYTES + 2 ? tiff - JPG_HEADER_BYTES : 0;
 }
 
-// from one full-size rendering to the next in d_full; bpx: 3 bytes per pixel, or 6 in a 16-bit call
-size_t full_stride(int w, int h, size_t bpx = 3) { return up256(bpx * w * h); }
+// from one rendering to the next in d_full; bpx: 3 bytes per pixel, or 6 in a 16-bit call
+size_t full_stride(int pw, int ph, size_t bpx) { return up256(bpx * pw * ph); }
 
 // The batch's final frames as rendered TIFF files: the parameters of every frame from its headers as they are now, one upload, runs of
-// frames that lie on one side of the slot pair developed into the other side in one launch, then header + 3 W' H' bytes per file.
+// frames that lie on one side of the slot pair developed into the other side in one launch, then header + bpx W' H' bytes per file.
 // With a look set (m.look) the launchers take the look kernels; nothing else differs.
-// jp: as JPEG files -- the run's renderings encoded into the slots they were developed from, then header + stream per file, or the
-// TIFF where that is the smaller file.
-// FULL: at the frame's own size -- the renderings go into d_full, full_stride(w, h) apart, and their streams behind the batch's renderings
-// SCALED: at ow x oh -- developed into the other slots as the half-size ones are, which are never smaller
-// RESAMPLED: at ow x oh up to the frame's size -- into d_full as the full-size ones, full_stride(ow, oh) apart
-// deep: as 16-bit TIFF files through the call's deep look (never m.look, never jp) -- 6 bytes per pixel; 6 W' H' <= 1.5 W H still fits the
-// other slot, and d_full has grown to 6 W H
+// sv.quality: as JPEG files -- the run's renderings encoded into the slots they were developed from, then header + stream per file, or
+// the TIFF where that is the smaller file.
+// HALF, SCALED: developed into the other slots, which a rendering of at most the half size always fits -- at 6 bytes per pixel too:
+// 6 W' H' <= 1.5 W H
+// FULL, RESAMPLED: the renderings go into d_full, full_stride(pw, ph) apart, and their streams behind the batch's renderings
 int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *h_out,
-              size_t out_stride, int gain_q8, int w, int h, const Jpeg *jp, const RgbMode &mode, const mlvfs_amd_look16_t *deep)
+              size_t out_stride, int w, int h, const Serve &sv)
 {
     hipStream_t s = c->stream;
     uint8_t *const F = (uint8_t *)m.d_frames, *const O = (uint8_t *)m.d_out;
-    const bool resampled = mode.kind == RgbMode::RESAMPLED, scaled = mode.kind == RgbMode::SCALED;
-    const bool full = mode.kind == RgbMode::FULL || resampled;                          // the renderings lie in d_full
-    const bool amaze = m.demosaic == 1 && mode.kind == RgbMode::FULL;
-    const bool amaze_rs = m.resample_demosaic == 1 && resampled;
-    int pw = w, ph = h;
-    if (amaze_rs && !amz_resample_geom(w, h, mode.ow, mode.oh)) { set_error("mount: a resampled AMaZE rendering does not take frames of %dx%d to %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
-    if (amaze && !rgb_amaze_geom(w, h)) { set_error("mount: an AMaZE rendering does not take frames of %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
-    if (resampled ? !resample_geom(w, h, mode.ow, mode.oh) : full ? !rgb_full_geom(w, h) : scaled ? !scale_geom(w, h, mode.ow, mode.oh, &pw, &ph) : !rgb_geom(w, h, &pw, &ph)) {
-        set_error("mount: a rendering does not take frames of %dx%d", w, h);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (scaled || resampled) { pw = mode.ow; ph = mode.oh; }
-    const size_t bpx = deep ? 6 : 3;
-    const size_t rstride = full ? full_stride(pw, ph, bpx) : dstride;                   // from one rendering to the next
+    const bool full = sv.in_full(), deep = sv.deep != nullptr;
+    const int pw = sv.pw, ph = sv.ph;
+    const size_t rstride = full ? full_stride(pw, ph, sv.bpx()) : dstride;              // from one rendering to the next
     const size_t sstride = full ? up256(jpg_room(pw, ph)) : dstride;                    // from one stream to the next
     std::vector<int32_t> &params = m.rgb_host;
-    params.resize((size_t)n * 13);
+    params.resize((size_t)n * RGB_PARAMS);
     for (int k = 0; k < n; k++) {
-        const int rc = mlvfs_amd_rgb_params(&fh[k], gain_q8, params.data() + (size_t)k * 13);
+        const int rc = mlvfs_amd_rgb_params(&fh[k], sv.gain_q8, params.data() + (size_t)k * RGB_PARAMS);
         if (rc) return rc;
     }
     MLV_HIP(hipMemcpyAsync(m.d_rgb, params.data(), params.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     LookArg look;
-    if (deep) { if (const int rc = look16_on_device(deep, c, &look)) return rc; }
+    if (deep) { if (const int rc = look16_on_device(sv.deep, c, &look)) return rc; }
     else if (m.look) if (const int rc = look_on_device(m.look, c, &look)) return rc;
     const LookArg *lk = deep || m.look ? &look : nullptr;
-    const size_t hdr = mlvfs_amd_rgb_header_size(), served = bpx * pw * ph;
+    const size_t hdr = mlvfs_amd_rgb_header_size(), served = sv.bpx() * pw * ph;
     for (int k0 = 0, k1; k0 < n; k0 = k1) {
         const bool in_f = final_at[k0] == F + k0 * dstride;
         for (k1 = k0 + 1; k1 < n && (final_at[k1] == F + k1 * dstride) == in_f; k1++) {}
         uint8_t *dst = full ? (uint8_t *)m.d_full + k0 * rstride : (in_f ? O : F) + k0 * dstride;
         uint8_t *streams = full ? (uint8_t *)m.d_full + n * rstride + k0 * sstride : final_at[k0];
-        const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * 13;
-        const int rc = amaze_rs ? launch_render_resampled_amaze(c, final_at[k0], dstride, par, dst, rstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
-                 : resampled ? launch_render_resampled(final_at[k0], dstride, par, dst, rstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
-                 : amaze ? launch_render1_amaze(c, final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
-                 : full ? launch_render1(final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep != nullptr)
-                 : scaled ? launch_render_scaled(final_at[k0], dstride, par, dst, dstride, w, h, pw, ph, k1 - k0, s, lk, deep != nullptr)
-                          : launch_render2(final_at[k0], dstride, par, dst, dstride, w, h, k1 - k0, s, lk, deep != nullptr);
+        const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * RGB_PARAMS;
+        const int rc = route_launch(sv.route, c, final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep);
         if (rc) return rc;
         std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
-        const size_t room = jp ? std::min(jpg_room(pw, ph), sstride) : 0;
+        const size_t room = sv.quality ? std::min(jpg_room(pw, ph), sstride) : 0;
         if (room) {
-            const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap(room, ph, jp->sampling), jp->sampling);
-            const int rj = jpg_encode_batch(dst, rstride, pw, ph, jp->quality, streams, sstride, room, m.d_scratch, l, res.data(), k1 - k0, s, jp->sampling);
+            const JpgLayout l = jpg_layout(pw, ph, jpg_rowcap(room, ph, sv.sampling), sv.sampling);
+            const int rj = jpg_encode_batch(dst, rstride, pw, ph, sv.quality, streams, sstride, room, m.d_scratch, l, res.data(), k1 - k0, s, sv.sampling);
             if (rj) return rj;
         }
         for (int k = k0; k < k1; k++) {
             uint8_t *file = h_out + k * out_stride;
-            if (jp) {
+            if (sv.quality) {
                 const JpgOut &r = res[k - k0];
-                jp->flags[k] = r.status ? 1 : 0;
-                jp->sizes[k] = r.status ? hdr + served : (size_t)JPG_HEADER_BYTES + r.length;
+                sv.flags[k] = r.status ? 1 : 0;
+                sv.sizes[k] = r.status ? hdr + served : (size_t)JPG_HEADER_BYTES + r.length;
                 if (!r.status) {
-                    (void)mlvfs_amd_jpeg_header_sampled(pw, ph, jp->quality, jp->sampling, file, JPG_HEADER_BYTES);
+                    (void)mlvfs_amd_jpeg_header_sampled(pw, ph, sv.quality, sv.sampling, file, JPG_HEADER_BYTES);
                     MLV_HIP(hipMemcpyAsync(file + JPG_HEADER_BYTES, streams + (size_t)(k - k0) * sstride, r.length, hipMemcpyDeviceToHost, s));
                     continue;
                 }
@@ -279,11 +281,9 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
     return MLVFS_AMD_OK;
 }
 
-// frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); ll: served losslessly;
-// rgb_gain != 0: served rendered (mlvfs_amd_mount_rgb), and no .dng header is written -- a file may be smaller than one
-int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results,
-                const Lossless *ll, int rgb_gain = 0, const Jpeg *jp = nullptr, const RgbMode &mode = RgbMode(),
-                const mlvfs_amd_look16_t *deep = nullptr)
+// frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); sv: what the call asks
+// for, its sizes and flags beginning at this batch
+int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results, const Serve &sv)
 {
     const mlvfs_amd_mount_opts_t &o = m.o;
     hipStream_t s = c->stream;
@@ -300,7 +300,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
     }
     // the frame's header: the proxy's where one is served, with the max_size the full-size write has
     auto write_header = [&](int k, size_t max_size) {
-        if (rgb_gain) return;
+        if (sv.gain_q8) return;
         if (m.proxy == 2) (void)mlvfs_amd_dng_header_proxy(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data(), 2, 0);
         else (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data());
     };
@@ -418,8 +418,8 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             for (int k = k0; k < k1; k++) final_at[k] = dst + (size_t)(k - k0) * dstride;
         }
     }
-    if (rgb_gain) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, rgb_gain, w, h, jp, mode, deep);
-    if (ll) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, *ll, sw, sh);
+    if (sv.gain_q8) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, w, h, sv);
+    if (sv.lossless) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, sv, sw, sh);
     const size_t served = (size_t)sw * sh * 2;
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
     MLV_HIP(hipStreamSynchronize(s));
@@ -586,15 +586,11 @@ int mlvfs_amd_bin2_dev(const void *d_frames, size_t stride, int width, int heigh
     return launch_bin2(d_frames, stride, d_out, out_stride, width, height, nframes, pick_stream(stream, c));
 }
 
-// every serving entry point; rgb_gain != 0: mlvfs_amd_mount_rgb, with jpeg_quality != 0 mlvfs_amd_mount_jpeg; mode: their full-size and
-// scaled forms; deep: mlvfs_amd_mount_rgb16 and its forms, with the call's deep look
-static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags, bool lossless,
-                       int batch_frames, int io_threads, int *results, int rgb_gain = 0, int jpeg_quality = 0, const RgbMode &mode = RgbMode(),
-                       const mlvfs_amd_look16_t *deep = nullptr)
+// every serving entry point; sv: what the call asks for, as the entry point states it -- the route's demosaic, the chroma sampling
+// and the rendering's size are settled here, under the handle's lock
+static int mount_serve(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results, Serve sv)
 {
-    const bool resampled = mode.kind == RgbMode::RESAMPLED, scaled = mode.kind == RgbMode::SCALED;
-    const bool full = mode.kind == RgbMode::FULL || resampled;                          // the renderings lie in d_full
-    if (!mount || !h_out || ((lossless || jpeg_quality) && (!sizes || !flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
+    if (!mount || !h_out || ((sv.lossless || sv.quality) && (!sv.sizes || !sv.flags))) { set_error("mount: null argument"); return MLVFS_AMD_ERR_ARG; }
     Mount &m = *(Mount *)mount;
     if (count < 0) { set_error("mount: negative frame count"); return MLVFS_AMD_ERR_ARG; }
     if (count == 0) return MLVFS_AMD_OK;
@@ -620,26 +616,15 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         if (!proxy_geom(w, h, &pw, &ph)) { set_error("mount: a proxy takes frames of 4x4 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
         size = dng_get_header_size() + (size_t)pw * ph * 2;
     }
-    if (rgb_gain) {
+    const bool full = sv.in_full();
+    if (sv.gain_q8) {
         if (m.proxy == 2) { set_error("mount: a handle that serves proxies does not render"); return MLVFS_AMD_ERR_ARG; }
-        int pw = w, ph = h;
-        if (full && !rgb_full_geom(w, h)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
-        if (m.resample_demosaic == 1 && resampled) {
-            if (!amz_resample_geom(w, h, mode.ow, mode.oh)) { set_error("mount: a resampled AMaZE rendering takes frames of 36x36 up to 2^25 pixels and 65535 a side, the width a multiple of 4, and a size of 1x1 up to the frame's, not %dx%d to %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
-        } else if (m.demosaic == 1 && resampled) { set_error("mount: with AMaZE set (mlvfs_amd_mount_set_demosaic) the resampled calls are not served"); return MLVFS_AMD_ERR_ARG; }
-        if (m.demosaic == 1 && full && !rgb_amaze_geom(w, h)) { set_error("mount: an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
-        if (!full && !rgb_geom(w, h, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
-        if (scaled) {
-            if (!scale_geom(w, h, mode.ow, mode.oh, &pw, &ph)) { set_error("mount: a scaled rendering of a %dx%d frame is 1x1 up to its half size, 65535 a side at most, not %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
-            pw = mode.ow;
-            ph = mode.oh;
-        }
-        if (resampled) {
-            if (!resample_geom(w, h, mode.ow, mode.oh)) { set_error("mount: a resampled rendering of a %dx%d frame is 1x1 up to its own size, 65535 a side at most, not %dx%d", w, h, mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
-            pw = mode.ow;
-            ph = mode.oh;
-        }
-        size = mlvfs_amd_rgb_header_size() + (size_t)(deep ? 6 : 3) * pw * ph;
+        bool unserved;
+        sv.route = mount_route(sv.route.size, sv.route.ow, sv.route.oh, m.demosaic, m.resample_demosaic, &unserved);
+        if (unserved) { set_error("mount: with AMaZE set (mlvfs_amd_mount_set_demosaic) the resampled calls are not served"); return MLVFS_AMD_ERR_ARG; }
+        if (!route_geom(sv.route, w, h, &sv.pw, &sv.ph)) return route_refuse("mount", sv.route, w, h);
+        sv.sampling = m.jpeg_sampling;
+        size = mlvfs_amd_rgb_header_size() + sv.bpx() * sv.pw * sv.ph;
         if (out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     }
     if (out_stride < size) { set_error("mount: out_stride %zu smaller than a .dng file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
@@ -651,22 +636,20 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     const size_t pn = o_pn_bytes(m.o, w, h, batch_frames);
     size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
     scratch = std::max(scratch, up256(4 * (size_t)65536 * sizeof(unsigned) * batch_frames) + up256(sizeof(HdrPreviewParams) * batch_frames));
-    if (lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
-    size_t full_bytes = full ? full_stride(resampled ? mode.ow : w, resampled ? mode.oh : h, deep ? 6 : 3) * batch_frames : 0;   // d_full: the batch's renderings ...
-    if (jpeg_quality) {
-        int pw = w, ph = h;
-        if (!full) (void)rgb_geom(w, h, &pw, &ph);
-        if (scaled || resampled) { pw = mode.ow; ph = mode.oh; }
+    if (sv.lossless) scratch = std::max(scratch, lje_fixed_bytes((uint32_t)(img / 2), batch_frames) + dstride * batch_frames);
+    size_t full_bytes = full ? full_stride(sv.pw, sv.ph, sv.bpx()) * batch_frames : 0;  // d_full: the batch's renderings ...
+    if (sv.quality) {
+        const int pw = sv.pw, ph = sv.ph;
         if (pw > 65535 || ph > 65535) { set_error("mount: a JPEG file takes renderings of up to 65535 a side, not %dx%d", pw, ph); return MLVFS_AMD_ERR_ARG; }
         if (const size_t room = full ? jpg_room(pw, ph) : std::min(jpg_room(pw, ph), dstride))
-            scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph, m.jpeg_sampling), m.jpeg_sampling), batch_frames));
+            scratch = std::max(scratch, jpg_scratch_bytes(jpg_layout(pw, ph, jpg_rowcap(room, ph, sv.sampling), sv.sampling), batch_frames));
         if (full) full_bytes += up256(jpg_room(pw, ph)) * batch_frames;                  // ... and their streams behind them
     }
     m.served = true;
     Calib cal;
     int rc = calib_on_device(m.dark, m.flat, c, w, h, bpp, 0, &cal);
     if (rc == MLVFS_AMD_OK) rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
-    if (rc == MLVFS_AMD_OK && rgb_gain) rc = m.ensure_rgb(batch_frames);
+    if (rc == MLVFS_AMD_OK && sv.gain_q8) rc = m.ensure_rgb(batch_frames);
     if (rc == MLVFS_AMD_OK && full) rc = m.d_full.reserve(full_bytes);
     for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
         int n = std::min(batch_frames, count - f0);
@@ -679,125 +662,184 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
             for (int k = 1; k < n; k++) if (fh[f0 + k].rawi_hdr.raw_info.black_level != cal.black) { n = k; break; }
         }
         rc = reader_load_batch(m.reader, first + f0, n, w, h, bpp, m.d_frames, dstride, io_threads, c->stream, &cal);
-        if (rc == MLVFS_AMD_OK) {
-            const Lossless ll{ lossless ? sizes + f0 : nullptr, lossless ? flags + f0 : nullptr };
-            const Jpeg jp{ jpeg_quality ? sizes + f0 : nullptr, jpeg_quality ? flags + f0 : nullptr, jpeg_quality, m.jpeg_sampling };
+        if (rc == MLVFS_AMD_OK)
             rc = serve_batch(m, c, fh.data() + f0, n, dstride, (uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, results ? results + f0 : nullptr,
-                             lossless ? &ll : nullptr, rgb_gain, jpeg_quality ? &jp : nullptr, mode, deep);
-        }
+                             sv.from(f0));
         f0 += n;
     }
     if (rc != MLVFS_AMD_OK) (void)hipStreamSynchronize(c->stream);
     return rc;
 }
 
+// what the rendering entry points check before mount_serve, one rule each, in this order: the deep look of a 16-bit call, the gain, a
+// JPEG call's quality, the size of a scaled or a resampled rendering
+static bool gain_ok(int gain_q8)
+{
+    if (gain_q8 >= 1 && gain_q8 <= 65535) return true;
+    set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8);
+    return false;
+}
+static bool quality_ok(int quality)
+{
+    if (quality >= 1 && quality <= 100) return true;
+    set_error("mount: a JPEG quality of %d (1 .. 100)", quality);
+    return false;
+}
+static bool size_ok(const RenderRoute &r)
+{
+    if (!r.sized() || (r.ow >= 1 && r.oh >= 1)) return true;
+    set_error("mount: a %s rendering of %dx%d", r.size == RenderRoute::SCALED ? "scaled" : "resampled", r.ow, r.oh);
+    return false;
+}
+enum class As { TIFF, TIFF16, JPEG };
+static int mount_render(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results, As as,
+                        const Serve &sv)
+{
+    if (as == As::TIFF16 && !sv.deep) { set_error("mount: null argument (a 16-bit rendering takes a deep look)"); return MLVFS_AMD_ERR_ARG; }
+    if (!gain_ok(sv.gain_q8) || (as == As::JPEG && !quality_ok(sv.quality)) || !size_ok(sv.route)) return MLVFS_AMD_ERR_ARG;
+    return mount_serve(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, sv);
+}
+static Serve rendered(int gain_q8, RenderRoute::Size size, int ow = 0, int oh = 0)
+{
+    Serve sv;
+    sv.gain_q8 = gain_q8;
+    sv.route = { size, false, ow, oh };
+    return sv;
+}
+static Serve rendered16(int gain_q8, const mlvfs_amd_look16_t *look, RenderRoute::Size size, int ow = 0, int oh = 0)
+{
+    Serve sv = rendered(gain_q8, size, ow, oh);
+    sv.deep = look;
+    return sv;
+}
+static Serve jpeg(int gain_q8, int quality, size_t *sizes, int *flags, RenderRoute::Size size, int ow = 0, int oh = 0)
+{
+    Serve sv = rendered(gain_q8, size, ow, oh);
+    sv.quality = quality;
+    sv.sizes = sizes;
+    sv.flags = flags;
+    return sv;
+}
+
 int mlvfs_amd_mount_dng(void *mount, int first, int count, void *h_out, size_t out_stride, int batch_frames, int io_threads, int *results)
 {
-    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results);
+    return mount_serve(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, Serve());
+}
+
+int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,
+                                 int batch_frames, int io_threads, int *results)
+{
+    Serve sv;
+    sv.lossless = true;
+    sv.sizes = sizes;
+    sv.flags = flags;
+    return mount_serve(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, sv);
 }
 
 int mlvfs_amd_mount_rgb(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int batch_frames, int io_threads,
                         int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8);
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF, rendered(gain_q8, RenderRoute::HALF));
 }
 
 int mlvfs_amd_mount_jpeg(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes, int *flags,
                          int batch_frames, int io_threads, int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality);
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::JPEG,
+                        jpeg(gain_q8, quality, sizes, flags, RenderRoute::HALF));
 }
 
 int mlvfs_amd_mount_rgb_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int batch_frames, int io_threads,
                              int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0, RgbMode{ RgbMode::FULL });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF, rendered(gain_q8, RenderRoute::FULL));
 }
 
 int mlvfs_amd_mount_jpeg_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, size_t *sizes,
                               int *flags, int batch_frames, int io_threads, int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality, RgbMode{ RgbMode::FULL });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::JPEG,
+                        jpeg(gain_q8, quality, sizes, flags, RenderRoute::FULL));
 }
 
 int mlvfs_amd_mount_rgb_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh, int batch_frames,
                                int io_threads, int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    if (ow < 1 || oh < 1) { set_error("mount: a scaled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0,
-                       RgbMode{ RgbMode::SCALED, ow, oh });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF,
+                        rendered(gain_q8, RenderRoute::SCALED, ow, oh));
 }
 
 int mlvfs_amd_mount_jpeg_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, int ow, int oh,
                                 size_t *sizes, int *flags, int batch_frames, int io_threads, int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
-    if (ow < 1 || oh < 1) { set_error("mount: a scaled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality,
-                       RgbMode{ RgbMode::SCALED, ow, oh });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::JPEG,
+                        jpeg(gain_q8, quality, sizes, flags, RenderRoute::SCALED, ow, oh));
 }
 
 int mlvfs_amd_mount_rgb_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh, int batch_frames,
                                   int io_threads, int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    if (ow < 1 || oh < 1) { set_error("mount: a resampled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0,
-                       RgbMode{ RgbMode::RESAMPLED, ow, oh });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF,
+                        rendered(gain_q8, RenderRoute::RESAMPLED, ow, oh));
 }
 
 int mlvfs_amd_mount_jpeg_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int quality, int ow, int oh,
                                    size_t *sizes, int *flags, int batch_frames, int io_threads, int *results)
 {
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    if (quality < 1 || quality > 100) { set_error("mount: a JPEG quality of %d (1 .. 100)", quality); return MLVFS_AMD_ERR_ARG; }
-    if (ow < 1 || oh < 1) { set_error("mount: a resampled rendering of %dx%d", ow, oh); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, false, batch_frames, io_threads, results, gain_q8, quality,
-                       RgbMode{ RgbMode::RESAMPLED, ow, oh });
-}
-
-// the three 16-bit TIFF calls: what the 8-bit ones check, and the call's deep look
-static int mount_rgb16(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
-                       int batch_frames, int io_threads, int *results, const RgbMode &mode)
-{
-    if (!look) { set_error("mount: null argument (a 16-bit rendering takes a deep look)"); return MLVFS_AMD_ERR_ARG; }
-    if (gain_q8 < 1 || gain_q8 > 65535) { set_error("mount: a gain_q8 of %d (1 .. 65535, 256 is unity)", gain_q8); return MLVFS_AMD_ERR_ARG; }
-    if (mode.kind == RgbMode::SCALED && (mode.ow < 1 || mode.oh < 1)) { set_error("mount: a scaled rendering of %dx%d", mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
-    if (mode.kind == RgbMode::RESAMPLED && (mode.ow < 1 || mode.oh < 1)) { set_error("mount: a resampled rendering of %dx%d", mode.ow, mode.oh); return MLVFS_AMD_ERR_ARG; }
-    return mount_serve(mount, first, count, h_out, out_stride, nullptr, nullptr, false, batch_frames, io_threads, results, gain_q8, 0, mode, look);
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::JPEG,
+                        jpeg(gain_q8, quality, sizes, flags, RenderRoute::RESAMPLED, ow, oh));
 }
 
 int mlvfs_amd_mount_rgb16(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
                           int batch_frames, int io_threads, int *results)
 {
-    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode());
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF16,
+                        rendered16(gain_q8, look, RenderRoute::HALF));
 }
 
 int mlvfs_amd_mount_rgb16_full(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, const mlvfs_amd_look16_t *look,
                                int batch_frames, int io_threads, int *results)
 {
-    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode{ RgbMode::FULL });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF16,
+                        rendered16(gain_q8, look, RenderRoute::FULL));
 }
 
 int mlvfs_amd_mount_rgb16_scaled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
                                  const mlvfs_amd_look16_t *look, int batch_frames, int io_threads, int *results)
 {
-    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode{ RgbMode::SCALED, ow, oh });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF16,
+                        rendered16(gain_q8, look, RenderRoute::SCALED, ow, oh));
 }
 
 int mlvfs_amd_mount_rgb16_resampled(void *mount, int first, int count, void *h_out, size_t out_stride, int gain_q8, int ow, int oh,
                                     const mlvfs_amd_look16_t *look, int batch_frames, int io_threads, int *results)
 {
-    return mount_rgb16(mount, first, count, h_out, out_stride, gain_q8, look, batch_frames, io_threads, results, RgbMode{ RgbMode::RESAMPLED, ow, oh });
+    return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF16,
+                        rendered16(gain_q8, look, RenderRoute::RESAMPLED, ow, oh));
 }
+
+// the size of a rendered 8-bit TIFF file of frame `index`: the handle's route for that size kind and its geometry.  A rendering's size
+// does not depend on whether the handle's settings let the call be served
+static size_t mount_rgb_size(const void *mount, int index, RenderRoute::Size size, int ow = 0, int oh = 0)
+{
+    if (!mount) { set_error("mount: null argument"); return 0; }
+    Mount &m = *(Mount *)mount;
+    frame_headers fh;
+    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
+    RenderRoute route;
+    {
+        std::lock_guard<std::mutex> lk(m.mu);
+        route = mount_route(size, ow, oh, m.demosaic, m.resample_demosaic);
+    }
+    int pw, ph;
+    if (!route_geom(route, fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, &pw, &ph)) { (void)route_refuse("mount", route, fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
+    return mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
+}
+
+size_t mlvfs_amd_mount_rgb_size(const void *mount, int index) { return mount_rgb_size(mount, index, RenderRoute::HALF); }
+size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index) { return mount_rgb_size(mount, index, RenderRoute::FULL); }
+size_t mlvfs_amd_mount_rgb_scaled_size(const void *mount, int index, int ow, int oh) { return mount_rgb_size(mount, index, RenderRoute::SCALED, ow, oh); }
+size_t mlvfs_amd_mount_rgb_resampled_size(const void *mount, int index, int ow, int oh) { return mount_rgb_size(mount, index, RenderRoute::RESAMPLED, ow, oh); }
 
 // a 16-bit file has the 8-bit file's header and twice its pixel bytes
 static size_t twice_the_pixels(size_t size8) { return size8 ? 2 * size8 - mlvfs_amd_rgb_header_size() : 0; }
@@ -807,365 +849,9 @@ size_t mlvfs_amd_mount_rgb16_scaled_size(const void *mount, int index, int ow, i
 {
     return twice_the_pixels(mlvfs_amd_mount_rgb_scaled_size(mount, index, ow, oh));
 }
-
 size_t mlvfs_amd_mount_rgb16_resampled_size(const void *mount, int index, int ow, int oh)
 {
     return twice_the_pixels(mlvfs_amd_mount_rgb_resampled_size(mount, index, ow, oh));
-}
-
-size_t mlvfs_amd_mount_rgb_resampled_size(const void *mount, int index, int ow, int oh)
-{
-    if (!mount) { set_error("mount: null argument"); return 0; }
-    Mount &m = *(Mount *)mount;
-    frame_headers fh;
-    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
-    if (!resample_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh)) {
-        set_error("mount: a resampled rendering of a %dx%d frame is 1x1 up to its own size, 65535 a side at most, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh);
-        return 0;
-    }
-    int resample_demosaic;
-    {
-        std::lock_guard<std::mutex> lk(m.mu);
-        resample_demosaic = m.resample_demosaic;
-    }
-    if (resample_demosaic == 1 && !amz_resample_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh)) {
-        set_error("mount: a resampled AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes);
-        return 0;
-    }
-    return mlvfs_amd_rgb_header_size() + (size_t)3 * ow * oh;
-}
-
-size_t mlvfs_amd_mount_rgb_scaled_size(const void *mount, int index, int ow, int oh)
-{
-    if (!mount) { set_error("mount: null argument"); return 0; }
-    Mount &m = *(Mount *)mount;
-    frame_headers fh;
-    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
-    int pw, ph;
-    if (!scale_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh, &pw, &ph)) {
-        set_error("mount: a scaled rendering of a %dx%d frame is 1x1 up to its half size, 65535 a side at most, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, ow, oh);
-        return 0;
-    }
-    return mlvfs_amd_rgb_header_size() + (size_t)3 * ow * oh;
-}
-
-int mlvfs_amd_rgb_fit(int width, int height, int box_w, int box_h, int *ow, int *oh)
-{
-    if (!ow || !oh) { set_error("rgb_fit: null argument"); return MLVFS_AMD_ERR_ARG; }
-    int pw, ph;
-    if (box_w < 1 || box_h < 1 || !scale_geom(width, height, 1, 1, &pw, &ph)) {
-        set_error("rgb_fit: a box of %dx%d, or a %dx%d frame that the scaled rendering does not take", box_w, box_h, width, height);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    int64_t fw = pw, fh = ph;
-    if (box_w < pw || box_h < ph) {
-        if ((int64_t)box_w * ph <= (int64_t)box_h * pw) {                // the width limits
-            fw = std::min(box_w, pw);
-            fh = std::max<int64_t>(1, (2 * fw * ph + pw) / (2 * (int64_t)pw));
-        } else {
-            fh = std::min(box_h, ph);
-            fw = std::max<int64_t>(1, (2 * fh * pw + ph) / (2 * (int64_t)ph));
-        }
-    }
-    *ow = (int)fw;
-    *oh = (int)fh;
-    return MLVFS_AMD_OK;
-}
-
-// mlvfs_amd_render_scaled_dev and mlvfs_amd_render_scaled_look_dev: the same checks before any device work
-static int render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
-                             size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream,
-                             const mlvfs_amd_look16_t *deep = nullptr, bool with_deep = false)
-{
-    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render_scaled: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("render_scaled: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    int pw, ph;
-    if (!scale_geom(width, height, ow, oh, &pw, &ph)) {
-        set_error("render_scaled: %dx%d to %dx%d not supported (2x2 up to 2^27 pixels, 65535 a side at half size; 1x1 up to the half size)", width, height, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * ow * oh;
-    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render_scaled: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
-        set_error("render_scaled: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (nframes == 0) return MLVFS_AMD_OK;
-    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
-    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
-    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
-    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render_scaled: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    LookArg lk;
-    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
-    return launch_render_scaled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c),
-                                with_look || with_deep ? &lk : nullptr, with_deep);
-}
-
-int mlvfs_amd_render_scaled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
-                                size_t out_stride, int nframes, void *stream)
-{
-    return render_scaled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream);
-}
-
-int mlvfs_amd_render_scaled_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                     void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
-{
-    return render_scaled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, look, true, stream);
-}
-
-int mlvfs_amd_render_scaled_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                     void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
-{
-    return render_scaled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream, look, true);
-}
-
-/* test hooks, host only: floor(in[k] / d) as k_scale_x16 computes it; how launch_render_scaled would divide a launch among workgroups */
-int mlvfs_amd_test_scale_div(uint32_t d, int n, const uint32_t *in, uint32_t *out)
-{
-    if (!d || n < 0 || !in || !out) { set_error("test_scale_div: bad argument"); return MLVFS_AMD_ERR_ARG; }
-    const ScDiv dv = scdiv_make(d);
-    for (int k = 0; k < n; k++) out[k] = scdiv_host(in[k], dv);
-    return MLVFS_AMD_OK;
-}
-
-int mlvfs_amd_test_scale_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8])
-{
-    int pw, ph;
-    if (!out || nframes < 1 || !scale_geom(width, height, ow, oh, &pw, &ph)) { set_error("test_scale_plan: bad argument"); return MLVFS_AMD_ERR_ARG; }
-    const ScalePlan p = scale_plan(pw, ph, ow, oh, nframes);
-    const int32_t v[8] = { width % 16 == 0, SC_CHUNK, SC_STRIP, (int32_t)p.uo, (int32_t)p.nstrips, (int32_t)p.bo, (int32_t)p.nbands, SC_BAND_ROWS };
-    std::copy(v, v + 8, out);
-    return MLVFS_AMD_OK;
-}
-
-int mlvfs_amd_rgb_fit_full(int width, int height, int box_w, int box_h, int *ow, int *oh)
-{
-    if (!ow || !oh) { set_error("rgb_fit_full: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (box_w < 1 || box_h < 1 || !resample_geom(width, height, 1, 1)) {
-        set_error("rgb_fit_full: a box of %dx%d, or a %dx%d frame that the resampled rendering does not take", box_w, box_h, width, height);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    int64_t fw, fh;
-    if ((int64_t)box_w * height <= (int64_t)box_h * width) {             // the width limits
-        fw = std::min(box_w, width);
-        fh = std::max<int64_t>(1, (2 * fw * height + width) / (2 * (int64_t)width));
-    } else {
-        fh = std::min(box_h, height);
-        fw = std::max<int64_t>(1, (2 * fh * width + height) / (2 * (int64_t)height));
-    }
-    *ow = (int)fw;
-    *oh = (int)fh;
-    return MLVFS_AMD_OK;
-}
-
-// mlvfs_amd_render_resampled_dev and its look and deep forms: render1's checks and the geometry, before any device work
-static int render_resampled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh, void *d_out,
-                                size_t out_stride, int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream,
-                                const mlvfs_amd_look16_t *deep = nullptr, bool with_deep = false)
-{
-    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render_resampled: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("render_resampled: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    if (!resample_geom(width, height, ow, oh)) {
-        set_error("render_resampled: %dx%d to %dx%d not supported (4x4 up to 2^25 pixels, 65535 a side; 1x1 up to the frame's size)", width, height, ow, oh);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * ow * oh;
-    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render_resampled: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
-        set_error("render_resampled: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (nframes == 0) return MLVFS_AMD_OK;
-    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
-    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
-    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
-    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render_resampled: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    LookArg lk;
-    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
-    return launch_render_resampled(d_frames, stride, d_params, d_out, out_stride, width, height, ow, oh, nframes, pick_stream(stream, c),
-                                   with_look || with_deep ? &lk : nullptr, with_deep);
-}
-
-int mlvfs_amd_render_resampled_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                   void *d_out, size_t out_stride, int nframes, void *stream)
-{
-    return render_resampled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream);
-}
-
-int mlvfs_amd_render_resampled_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                        void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
-{
-    return render_resampled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, look, true, stream);
-}
-
-int mlvfs_amd_render_resampled_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, int ow, int oh,
-                                        void *d_out, size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
-{
-    return render_resampled_dev(d_frames, stride, width, height, d_params, ow, oh, d_out, out_stride, nframes, nullptr, false, stream, look, true);
-}
-
-/* test hook, host only: how launch_render_resampled would divide a launch among workgroups */
-int mlvfs_amd_test_resample_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8])
-{
-    if (!out || nframes < 1 || !resample_geom(width, height, ow, oh)) { set_error("test_resample_plan: bad argument"); return MLVFS_AMD_ERR_ARG; }
-    int32_t v[8] = { 0, RS_STRIP, 0, 0, 0, 0, RS_BAND_ROWS, RS_ROWS };
-    if (resample_fast_geom(width, ow)) {
-        const ResamplePlan p = resample_plan(width, height, ow, oh, nframes);
-        v[0] = 1; v[2] = (int32_t)p.uo; v[3] = (int32_t)p.nstrips; v[4] = (int32_t)p.bo; v[5] = (int32_t)p.nbands;
-    }
-    std::copy(v, v + 8, out);
-    return MLVFS_AMD_OK;
-}
-
-size_t mlvfs_amd_mount_rgb_full_size(const void *mount, int index)
-{
-    if (!mount) { set_error("mount: null argument"); return 0; }
-    Mount &m = *(Mount *)mount;
-    frame_headers fh;
-    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
-    if (!rgb_full_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) { set_error("mount: a full-size rendering takes frames of 4x4 up to 2^25 pixels, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
-    int demosaic;
-    {
-        std::lock_guard<std::mutex> lk(m.mu);
-        demosaic = m.demosaic;
-    }
-    if (demosaic == 1 && !rgb_amaze_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes)) { set_error("mount: an AMaZE rendering takes frames of 36x36 up to 2^25 pixels, the width a multiple of 4, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
-    return mlvfs_amd_rgb_header_size() + (size_t)3 * fh.rawi_hdr.xRes * fh.rawi_hdr.yRes;
-}
-
-size_t mlvfs_amd_mount_rgb_size(const void *mount, int index)
-{
-    if (!mount) { set_error("mount: null argument"); return 0; }
-    Mount &m = *(Mount *)mount;
-    frame_headers fh;
-    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
-    int pw, ph;
-    if (!rgb_geom(fh.rawi_hdr.xRes, fh.rawi_hdr.yRes, &pw, &ph)) { set_error("mount: a rendering takes frames of 2x2 and more, not %dx%d", fh.rawi_hdr.xRes, fh.rawi_hdr.yRes); return 0; }
-    return mlvfs_amd_rgb_header_size() + (size_t)3 * pw * ph;
-}
-
-int mlvfs_amd_rgb_geom(int width, int height, int *pw, int *ph)
-{
-    if (!pw || !ph) { set_error("rgb_geom: null argument"); return MLVFS_AMD_ERR_ARG; }
-    int w2, h2;
-    if (!rgb_geom(width, height, &w2, &h2)) { set_error("rgb_geom: %dx%d not supported (2x2 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
-    *pw = w2;
-    *ph = h2;
-    return MLVFS_AMD_OK;
-}
-
-// mlvfs_amd_render2_dev and mlvfs_amd_render2_look_dev: the same checks before any device work
-static int render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream, const mlvfs_amd_look16_t *deep = nullptr,
-                       bool with_deep = false)
-{
-    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render2: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("render2: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    int pw, ph;
-    if (!rgb_geom(width, height, &pw, &ph)) { set_error("render2: %dx%d not supported (2x2 up to 2^27 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * pw * ph;
-    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render2: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
-        set_error("render2: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (nframes == 0) return MLVFS_AMD_OK;
-    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
-    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
-    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
-    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render2: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    LookArg lk;
-    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
-    return launch_render2(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c),
-                          with_look || with_deep ? &lk : nullptr, with_deep);
-}
-
-int mlvfs_amd_render2_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                          int nframes, void *stream)
-{
-    return render2_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream);
-}
-
-int mlvfs_amd_render2_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
-                               size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
-{
-    return render2_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, look, true, stream);
-}
-
-int mlvfs_amd_render2_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
-                               size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
-{
-    return render2_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream, look, true);
-}
-
-int mlvfs_amd_rgb_full_geom(int width, int height, int *pw, int *ph)
-{
-    if (!pw || !ph) { set_error("rgb_full_geom: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (!rgb_full_geom(width, height)) { set_error("rgb_full_geom: %dx%d not supported (4x4 up to 2^25 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
-    *pw = width;
-    *ph = height;
-    return MLVFS_AMD_OK;
-}
-
-// mlvfs_amd_render1_dev and mlvfs_amd_render1_look_dev: the same checks before any device work
-static int render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                       int nframes, const mlvfs_amd_look_t *look, bool with_look, void *stream, const mlvfs_amd_look16_t *deep = nullptr,
-                       bool with_deep = false)
-{
-    if (!d_frames || !d_out || !d_params || (with_look && !look) || (with_deep && !deep)) { set_error("render1: null argument"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes < 0) { set_error("render1: negative frame count"); return MLVFS_AMD_ERR_ARG; }
-    if (!rgb_full_geom(width, height)) { set_error("render1: %dx%d not supported (4x4 up to 2^25 pixels)", width, height); return MLVFS_AMD_ERR_ARG; }
-    const size_t img = (size_t)width * height * 2, pimg = (size_t)(with_deep ? 6 : 3) * width * height;
-    if (((uintptr_t)d_frames & 1) || ((uintptr_t)d_params & 3)) { set_error("render1: an odd source address, or parameters off a 4-byte boundary"); return MLVFS_AMD_ERR_ARG; }
-    if (nframes > 1 && (stride < img || out_stride < pimg || (stride & 1))) {
-        set_error("render1: strides %zu / %zu too small, or an odd source stride", stride, out_stride);
-        return MLVFS_AMD_ERR_ARG;
-    }
-    if (nframes == 0) return MLVFS_AMD_OK;
-    const uintptr_t a0 = (uintptr_t)d_frames, a1 = a0 + (size_t)(nframes - 1) * stride + img;
-    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + (size_t)(nframes - 1) * out_stride + pimg;
-    const uintptr_t p0 = (uintptr_t)d_params, p1 = p0 + (size_t)nframes * 13 * sizeof(int32_t);
-    if ((a0 < b1 && b0 < a1) || (p0 < b1 && b0 < p1)) { set_error("render1: the destination overlaps the source or the parameters (the rendering does not work in place)"); return MLVFS_AMD_ERR_ARG; }
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    LookArg lk;
-    if (with_look) if (const int rc = look_on_device(look, c, &lk)) return rc;
-    if (with_deep) if (const int rc = look16_on_device(deep, c, &lk)) return rc;
-    return launch_render1(d_frames, stride, d_params, d_out, out_stride, width, height, nframes, pick_stream(stream, c),
-                          with_look || with_deep ? &lk : nullptr, with_deep);
-}
-
-int mlvfs_amd_render1_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out, size_t out_stride,
-                          int nframes, void *stream)
-{
-    return render1_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream);
-}
-
-int mlvfs_amd_render1_look_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
-                               size_t out_stride, int nframes, const mlvfs_amd_look_t *look, void *stream)
-{
-    return render1_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, look, true, stream);
-}
-
-int mlvfs_amd_render1_deep_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_params, void *d_out,
-                               size_t out_stride, int nframes, const mlvfs_amd_look16_t *look, void *stream)
-{
-    return render1_dev(d_frames, stride, width, height, d_params, d_out, out_stride, nframes, nullptr, false, stream, look, true);
-}
-
-int mlvfs_amd_mount_dng_lossless(void *mount, int first, int count, void *h_out, size_t out_stride, size_t *sizes, int *flags,
-                                 int batch_frames, int io_threads, int *results)
-{
-    return mount_serve(mount, first, count, h_out, out_stride, sizes, flags, true, batch_frames, io_threads, results);
 }
 
 }  // extern "C"

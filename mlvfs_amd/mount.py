@@ -140,13 +140,19 @@ class Mount:
             raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
         return size
 
+    @staticmethod
+    def _results(results: np.ndarray | None, count: int) -> np.ndarray:
+        """the int32 array a serving call writes its per-frame results to: the caller's, checked, or one of its own"""
+        if results is None:
+            return np.zeros(max(count, 1), np.int32)
+        if not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous and results.size >= count):
+            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
+        return results
+
     def dng(self, first: int, count: int, batch: int = 8, io_threads: int = 0, results: np.ndarray | None = None) -> np.ndarray:
         """Frames first .. first + count - 1 as .dng files: a (count, dng_size) uint8 array."""
         out = np.zeros((count, self.dng_size(first) if count else 0), np.uint8)
-        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
-                                        and results.size >= count):
-            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
-        res = np.zeros(max(count, 1), np.int32) if results is None else results
+        res = self._results(results, count)
         lib.check(self.L.mlvfs_amd_mount_dng(self.h, first, count, lib.ptr(out), out.shape[1], batch, io_threads, lib.ptr(res)),
                   "mount_dng")
         return out
@@ -159,10 +165,7 @@ class Mount:
         out = np.zeros((count, stride), np.uint8)
         sizes = np.zeros(max(count, 1), np.uintp)
         flags = np.zeros(max(count, 1), np.int32)
-        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
-                                        and results.size >= count):
-            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
-        res = np.zeros(max(count, 1), np.int32) if results is None else results
+        res = self._results(results, count)
         lib.check(self.L.mlvfs_amd_mount_dng_lossless(self.h, first, count, lib.ptr(out), stride, lib.ptr(sizes), lib.ptr(flags), batch,
                                                       io_threads, lib.ptr(res)), "mount_dng_lossless")
         return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
@@ -179,22 +182,25 @@ class Mount:
         ow, oh = size
         return int(ow), int(oh)
 
+    # the C call of a rendering, by its size kind and its form ("rgb", "rgb16" or "jpeg"; "..._size": the size query).  The calls of the
+    # two kinds with a size take ow, oh behind the gain (and the quality), the size queries behind the index
+    RENDER_CALLS = {(kind, form): f"mount_{form}{kind}" for kind in ("", "_full", "_scaled", "_resampled") for form in ("rgb", "rgb16", "jpeg")}
+    RENDER_CALLS.update({(kind, form + "_size"): f"mount_{form}{kind}_size" for kind in ("", "_full", "_scaled", "_resampled") for form in ("rgb", "rgb16")})
+
+    def _render_call(self, form: str, full: bool, size, resample: bool):
+        """-> (the C function, its name for an error message, the (ow, oh) it takes or ()); size: _size_arg's"""
+        kind = "_resampled" if resample else "_scaled" if size is not None else "_full" if full else ""
+        name = self.RENDER_CALLS[kind, form]
+        return getattr(self.L, "mlvfs_amd_" + name), name, size or ()
+
     def rgb_size(self, index: int = 0, full: bool = False, size=None, bits: int = 8, resample: bool = False) -> int:
         """bytes of file `index` as rgb() serves it: the TIFF header + 3 * (W // 2) * (H // 2); full: + 3 * W * H; size=(ow, oh):
         + 3 * ow * oh, up to the half size, or with resample=True up to the frame's; bits=16: as rgb(look16=...) serves it, twice the
         pixel bytes"""
         if bits not in (8, 16):
             raise ValueError(f"{bits} bits per sample (8 or 16)")
-        size = self._size_arg(size, full, resample)
-        L, deep = self.L, bits == 16
-        if resample:
-            size = int((L.mlvfs_amd_mount_rgb16_resampled_size if deep else L.mlvfs_amd_mount_rgb_resampled_size)(self.h, index, *size))
-        elif size is not None:
-            size = int((L.mlvfs_amd_mount_rgb16_scaled_size if deep else L.mlvfs_amd_mount_rgb_scaled_size)(self.h, index, *size))
-        elif full:
-            size = int((L.mlvfs_amd_mount_rgb16_full_size if deep else L.mlvfs_amd_mount_rgb_full_size)(self.h, index))
-        else:
-            size = int((L.mlvfs_amd_mount_rgb16_size if deep else L.mlvfs_amd_mount_rgb_size)(self.h, index))
+        call, _, wh = self._render_call("rgb16_size" if bits == 16 else "rgb_size", full, self._size_arg(size, full, resample), resample)
+        size = int(call(self.h, index, *wh))
         if not size:
             raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
         return size
@@ -214,35 +220,12 @@ class Mount:
         gain_q8 = int(round(256 * gain))
         if not 1 <= gain_q8 <= 65535:
             raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
-        out = np.zeros((count, self.rgb_size(first, full, size, 16 if look16 is not None else 8, resample) if count else 0), np.uint8)
-        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
-                                        and results.size >= count):
-            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
-        res = np.zeros(max(count, 1), np.int32) if results is None else results
-        if look16 is not None:
-            if size is not None:
-                if resample:
-                    lib.check(self.L.mlvfs_amd_mount_rgb16_resampled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1],
-                                                                     look16.h, batch, io_threads, lib.ptr(res)), "mount_rgb16_resampled")
-                    return out
-                lib.check(self.L.mlvfs_amd_mount_rgb16_scaled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1],
-                                                              look16.h, batch, io_threads, lib.ptr(res)), "mount_rgb16_scaled")
-                return out
-            call = self.L.mlvfs_amd_mount_rgb16_full if full else self.L.mlvfs_amd_mount_rgb16
-            lib.check(call(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, look16.h, batch, io_threads, lib.ptr(res)),
-                      "mount_rgb16_full" if full else "mount_rgb16")
-            return out
-        if resample:
-            lib.check(self.L.mlvfs_amd_mount_rgb_resampled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1], batch,
-                                                           io_threads, lib.ptr(res)), "mount_rgb_resampled")
-            return out
-        if size is not None:
-            lib.check(self.L.mlvfs_amd_mount_rgb_scaled(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, size[0], size[1], batch,
-                                                        io_threads, lib.ptr(res)), "mount_rgb_scaled")
-            return out
-        call = self.L.mlvfs_amd_mount_rgb_full if full else self.L.mlvfs_amd_mount_rgb
-        lib.check(call(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, batch, io_threads, lib.ptr(res)),
-                  "mount_rgb_full" if full else "mount_rgb")
+        deep = look16 is not None
+        out = np.zeros((count, self.rgb_size(first, full, size, 16 if deep else 8, resample) if count else 0), np.uint8)
+        res = self._results(results, count)
+        call, name, wh = self._render_call("rgb16" if deep else "rgb", full, size, resample)
+        look = (look16.h,) if deep else ()
+        lib.check(call(self.h, first, count, lib.ptr(out), out.shape[1], gain_q8, *wh, *look, batch, io_threads, lib.ptr(res)), name)
         return out
 
     def jpeg(self, first: int, count: int, gain: float = 1.0, quality: int = 90, batch: int = 8, io_threads: int = 0,
@@ -263,20 +246,10 @@ class Mount:
         out = np.zeros((count, stride), np.uint8)
         sizes = np.zeros(max(count, 1), np.uintp)
         flags = np.zeros(max(count, 1), np.int32)
-        if results is not None and not (isinstance(results, np.ndarray) and results.dtype == np.int32 and results.flags.c_contiguous
-                                        and results.size >= count):
-            raise ValueError(f"results must be a C-contiguous int32 array of at least {count} entries")
-        res = np.zeros(max(count, 1), np.int32) if results is None else results
-        if resample:
-            lib.check(self.L.mlvfs_amd_mount_jpeg_resampled(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, size[0], size[1],
-                                                            lib.ptr(sizes), lib.ptr(flags), batch, io_threads, lib.ptr(res)), "mount_jpeg_resampled")
-        elif size is not None:
-            lib.check(self.L.mlvfs_amd_mount_jpeg_scaled(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, size[0], size[1],
-                                                         lib.ptr(sizes), lib.ptr(flags), batch, io_threads, lib.ptr(res)), "mount_jpeg_scaled")
-        else:
-            call = self.L.mlvfs_amd_mount_jpeg_full if full else self.L.mlvfs_amd_mount_jpeg
-            lib.check(call(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, lib.ptr(sizes), lib.ptr(flags), batch, io_threads,
-                           lib.ptr(res)), "mount_jpeg_full" if full else "mount_jpeg")
+        res = self._results(results, count)
+        call, name, wh = self._render_call("jpeg", full, size, resample)
+        lib.check(call(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, *wh, lib.ptr(sizes), lib.ptr(flags), batch, io_threads,
+                       lib.ptr(res)), name)
         return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
 
     def close(self) -> None:
