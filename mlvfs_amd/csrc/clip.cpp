@@ -1,12 +1,8 @@
-// clip.cpp -- per-clip state and the device-resident C API (PART 2 of
+// clip.cpp -- per-clip state and its part of the device-resident C API (PART 2 of
 // include/mlvfs_amd.h): pixel-map dependency analysis, stripe-coefficient
-// computation around the histogram kernels, fused pipeline entry point.
-#include "clip.h"
-#include <atomic>
-#include <thread>
+// computation around the histogram kernels.  The fused pass over a clip's frames: fused_pass.cpp.
+#include "fused_pass.h"
 #include <memory>
-#include <map>
-#include <set>
 
 #include <algorithm>
 #include <climits>
@@ -16,123 +12,6 @@
 #include <unordered_map>
 
 namespace mlv {
-
-KernelTimer &kernel_timer()
-{
-    static thread_local KernelTimer t;
-    return t;
-}
-
-// ------------------------------------------------------------------ glibc rand()
-// TYPE_3 additive feedback generator of glibc's random_r.c (public algorithm; the
-// reference calls libc rand() in stripes.c:129-130 and never seeds it, so a fresh
-// process starts from srand(1)).  x[i] = x[i-31] + x[i-3] mod 2^32 after a
-// Lehmer-seeded warm-up of 310 discarded words; output = x >> 1.
-// The recurrence is linear over Z/2^32, so the state k steps ahead is A^k times the state (A = 31x31 companion matrix):
-// long streams are cut into chunks whose start states come from a jump-ahead, and the chunks are generated by host threads.
-namespace {
-struct RandState { uint32_t x[31]; };                     // x[0] oldest: next = x[0] + x[28]
-
-RandState rand_seeded(unsigned seed)
-{
-    uint32_t x[34 + 310];
-    int32_t word = (int32_t)(seed ? seed : 1);
-    x[0] = (uint32_t)word;
-    for (int i = 1; i < 31; i++) {
-        const int64_t hi = word / 127773, lo = word % 127773;
-        int64_t nx = 16807 * lo - 2836 * hi;
-        if (nx < 0) nx += 2147483647;
-        word = (int32_t)nx;
-        x[i] = (uint32_t)word;
-    }
-    for (int i = 31; i < 34; i++) x[i] = x[i - 31];
-    for (int i = 34; i < 34 + 310; i++) x[i] = x[i - 31] + x[i - 3];
-    RandState s;
-    for (int i = 0; i < 31; i++) s.x[i] = x[34 + 310 - 31 + i];
-    return s;
-}
-
-struct Mat31 { uint32_t m[31][31]; };
-void mat_mul(const Mat31 &a, const Mat31 &b, Mat31 &c)
-{
-    for (int i = 0; i < 31; i++)
-        for (int j = 0; j < 31; j++) {
-            uint32_t acc = 0;
-            for (int k = 0; k < 31; k++) acc += a.m[i][k] * b.m[k][j];
-            c.m[i][j] = acc;
-        }
-}
-
-RandState rand_jump(const RandState &s, uint64_t k)        // state after k outputs
-{
-    if (k < 4096) {                                          // short: just step
-        uint32_t buf[31 + 4096];
-        memcpy(buf, s.x, sizeof s.x);
-        for (uint64_t i = 0; i < k; i++) buf[31 + i] = buf[i] + buf[i + 28];
-        RandState r;
-        memcpy(r.x, buf + k, sizeof r.x);
-        return r;
-    }
-    static Mat31 R, A, T;                                    // guarded by the caller's mutex
-    memset(&R, 0, sizeof R); memset(&A, 0, sizeof A);
-    for (int i = 0; i < 31; i++) R.m[i][i] = 1;
-    for (int i = 0; i < 30; i++) A.m[i][i + 1] = 1;          // shift
-    A.m[30][0] = 1; A.m[30][28] = 1;                         // new = x[0] + x[28]
-    for (uint64_t e = k; e; e >>= 1) {
-        if (e & 1) { mat_mul(A, R, T); R = T; }
-        mat_mul(A, A, T); A = T;
-    }
-    RandState r;
-    for (int i = 0; i < 31; i++) {
-        uint32_t acc = 0;
-        for (int j = 0; j < 31; j++) acc += R.m[i][j] * s.x[j];
-        r.x[i] = acc;
-    }
-    return r;
-}
-
-void rand_fill(RandState s, uint16_t *out, size_t n)        // n outputs starting from state s
-{
-    constexpr size_t B = 1 << 14;
-    std::vector<uint32_t> buf(31 + B);
-    memcpy(buf.data(), s.x, sizeof s.x);
-    for (size_t done = 0; done < n;) {
-        const size_t m = std::min(B, n - done);
-        uint32_t *x = buf.data();
-        for (size_t i = 0; i < m; i++) {
-            const uint32_t v = x[i] + x[i + 28];
-            x[31 + i] = v;
-            out[done + i] = (uint16_t)((v >> 1) % 1024);
-        }
-        memmove(x, x + m, 31 * sizeof(uint32_t));
-        done += m;
-    }
-}
-std::mutex g_rand_mutex;
-}  // namespace
-
-void glibc_rand_stream(uint16_t *out, size_t n, uint64_t skip, unsigned seed)
-{
-    if (n == 0) return;
-    const RandState s0 = rand_seeded(seed);
-    unsigned nt = std::thread::hardware_concurrency();
-    nt = nt ? std::min(nt, 32u) : 1;
-    if (n < (1u << 20)) nt = 1;
-    const size_t chunk = (n + nt - 1) / nt;
-    std::vector<RandState> starts(nt);
-    {
-        std::lock_guard<std::mutex> lk(g_rand_mutex);
-        for (unsigned t = 0; t < nt; t++) starts[t] = rand_jump(s0, skip + (uint64_t)t * chunk);
-    }
-    if (nt == 1) { rand_fill(starts[0], out, n); return; }
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; t++) {
-        const size_t b = (size_t)t * chunk, e = std::min(n, b + chunk);
-        if (b >= e) break;
-        th.emplace_back(rand_fill, starts[t], out + b, e - b);
-    }
-    for (auto &x : th) x.join();
-}
 
 // ------------------------------------------------------------------ stripes solve
 int stripes_solve(const int32_t *hist, const int32_t num[8], int frame_size, int32_t coeffs[8])
@@ -396,96 +275,6 @@ int Clip::fix_pixels_shared(void *d_frame, size_t stride, int black, ThreadCtx *
 // ------------------------------------------------------------------ stripes
 struct RecheckHost { int hist, a, b, r1, r2; };
 
-// The same stream generated on the device (k_rand_states / k_rand_fill): the powers (A^RAND_CHUNK)^(2^j) are built once on
-// the host and kept on every device that asks; the start state comes from the host jump-ahead.
-namespace {
-constexpr int RAND_NPOW = 24;                                 // chunks up to 2^24 * 992 values
-struct RandDev { uint32_t *d_pow2 = nullptr, *d_start = nullptr, *d_states = nullptr; size_t cap_states = 0; };
-std::map<int, RandDev> g_rand_dev;
-std::vector<uint32_t> g_rand_pow2;                             // [RAND_NPOW][31][31]
-}  // namespace
-
-// n values from state `s0` on (its words oldest first); *after, if wanted: the state behind them
-static int rand_stream_device_from(const RandState &s0, uint16_t *d_out, size_t n, hipStream_t stream, RandState *after);
-
-int rand_stream_device(uint16_t *d_out, size_t n, uint64_t skip, unsigned seed, hipStream_t stream)
-{
-    RandState s0;
-    {
-        std::lock_guard<std::mutex> lk(g_rand_mutex);             // (rand_jump's scratch matrices)
-        s0 = rand_jump(rand_seeded(seed), skip);
-    }
-    return rand_stream_device_from(s0, d_out, n, stream, nullptr);
-}
-
-static int rand_stream_device_from(const RandState &s0, uint16_t *d_out, size_t n, hipStream_t stream, RandState *after)
-{
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    if (after) *after = s0;
-    if (n == 0) return MLVFS_AMD_OK;
-    if (((uintptr_t)d_out & 15) != 0) { set_error("rand stream: output must be 16-byte aligned"); return MLVFS_AMD_ERR_ARG; }
-    const uint64_t nchunks64 = (n + RAND_CHUNK - 1) / RAND_CHUNK;
-    if (nchunks64 >> RAND_NPOW) { set_error("rand stream too long"); return MLVFS_AMD_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(g_rand_mutex);
-    if (g_rand_pow2.empty()) {
-        static Mat31 P, T;
-        memset(&P, 0, sizeof P);
-        for (int i = 0; i < 30; i++) P.m[i][i + 1] = 1;
-        P.m[30][0] = 1; P.m[30][28] = 1;
-        static Mat31 R;
-        memset(&R, 0, sizeof R);
-        for (int i = 0; i < 31; i++) R.m[i][i] = 1;
-        Mat31 Acc = P;
-        for (unsigned e = RAND_CHUNK; e; e >>= 1) {             // R = A^RAND_CHUNK
-            if (e & 1) { mat_mul(Acc, R, T); R = T; }
-            mat_mul(Acc, Acc, T); Acc = T;
-        }
-        g_rand_pow2.resize((size_t)RAND_NPOW * 31 * 31);
-        for (int j = 0; j < RAND_NPOW; j++) {
-            memcpy(&g_rand_pow2[(size_t)j * 961], R.m, sizeof R.m);
-            mat_mul(R, R, T); R = T;
-        }
-    }
-    RandDev &rd = g_rand_dev[c->dev->id];
-    if (!rd.d_pow2) {
-        MLV_HIP(hipMalloc(&rd.d_pow2, g_rand_pow2.size() * 4));
-        MLV_HIP(hipMalloc(&rd.d_start, 32 * 4));
-        MLV_HIP(hipMemcpy(rd.d_pow2, g_rand_pow2.data(), g_rand_pow2.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (rd.cap_states < nchunks64 * 31 * 4) {
-        if (rd.d_states) (void)hipFree(rd.d_states);
-        rd.d_states = nullptr; rd.cap_states = 0;
-        MLV_HIP(hipMalloc(&rd.d_states, nchunks64 * 31 * 4));
-        rd.cap_states = nchunks64 * 31 * 4;
-    }
-    MLV_HIP(hipMemcpyAsync(rd.d_start, s0.x, sizeof s0.x, hipMemcpyHostToDevice, stream));
-    int rc = launch_rand_stream(rd.d_start, rd.d_pow2, RAND_NPOW, (uint32_t)nchunks64, rd.d_states, d_out, n, stream);
-    if (rc) return rc;
-    if (after) {
-        // n = q chunks + r single steps: the chunk powers (A^RAND_CHUNK)^(2^j) applied to the vector for the set bits of q, then r steps
-        RandState v = s0;
-        const uint64_t q = n / RAND_CHUNK, r = n % RAND_CHUNK;
-        for (int j = 0; j < RAND_NPOW; j++) {
-            if (!((q >> j) & 1u)) continue;
-            const uint32_t *P = &g_rand_pow2[(size_t)j * 961];
-            RandState t;
-            for (int i = 0; i < 31; i++) {
-                uint32_t acc = 0;
-                for (int k = 0; k < 31; k++) acc += P[i * 31 + k] * v.x[k];
-                t.x[i] = acc;
-            }
-            v = t;
-        }
-        uint32_t buf[31 + RAND_CHUNK];
-        memcpy(buf, v.x, sizeof v.x);
-        for (uint64_t i = 0; i < r; i++) buf[31 + i] = buf[i] + buf[i + 28];
-        memcpy(after->x, buf + r, sizeof after->x);
-    }
-    MLV_HIP(hipStreamSynchronize(stream));                       // s0's copy has left; the per-device buffers are shared between threads
-    return MLVFS_AMD_OK;
-}
-
 int Clip::stripes_compute(const void *d_frame, int frame_size, int rand_mode, hipStream_t stream)
 {
     ThreadCtx *c = thread_ctx();
@@ -708,7 +497,7 @@ int mlvfs_amd_chroma_smooth_dev(const mlvfs_amd_geom_t *geom, const void *d_in, 
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
     if (method != 2 && method != 3 && method != 5) { set_error("Unsupported chroma smooth method"); return MLVFS_AMD_ERR_ARG; }
-    if (geom->black > 16384) { set_error("Black level too large for processing"); return MLVFS_AMD_ERR_ARG; }
+    if (black_too_large(geom->black)) { set_error("Black level too large for processing"); return MLVFS_AMD_ERR_ARG; }
     return launch_frame(c->dev, to_geom(geom), false, d_in, stride, d_out, stride, nframes, method, nullptr, false,
                         nullptr, pick_stream(stream, c));
 }
@@ -783,54 +572,6 @@ int mlvfs_amd_stripes_apply_dev(const mlvfs_amd_clip_t *clip_, void *d_frames, s
                                 clip->coef, nframes, pick_stream(stream, c));
 }
 
-int mlvfs_amd_timer_begin(int max_launches)
-{
-    if (!thread_ctx()) return MLVFS_AMD_ERR_HIP;
-    KernelTimer &tm = kernel_timer();
-    while ((int)tm.ev.size() < 2 * max_launches) {
-        hipEvent_t e;
-        MLV_HIP(hipEventCreate(&e));
-        tm.ev.push_back(e);
-    }
-    tm.used = 0;
-    tm.on = true;
-    return MLVFS_AMD_OK;
-}
-
-int mlvfs_amd_timer_end(float *ms, int cap)
-{
-    KernelTimer &tm = kernel_timer();
-    tm.on = false;
-    int n = 0;
-    for (int i = 0; i + 1 < tm.used && n < cap; i += 2, n++) {
-        MLV_HIP(hipEventSynchronize(tm.ev[i + 1]));
-        MLV_HIP(hipEventElapsedTime(&ms[n], tm.ev[i], tm.ev[i + 1]));
-    }
-    tm.used = 0;
-    return n;
-}
-
-void mlvfs_amd_rand_stream(uint16_t *out, size_t n, uint64_t skip, unsigned seed) { glibc_rand_stream(out, n, skip, seed); }
-
-int mlvfs_amd_rand_stream_dev(void *d_out, size_t n, uint64_t skip, unsigned seed, void *stream)
-{
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    return rand_stream_device((uint16_t *)d_out, n, skip, seed, pick_stream(stream, c));
-}
-
-// T16 layout of the fused kernel for this clip: decided once, from the first frame the clip processes with chroma smoothing
-// (30 % of the sampled pixels 1 .. 511 above black: the spread layout, k_frame.hip), unless the caller fixed it
-static int decide_t16_layout(Clip *clip, bool packed, const void *d_frame, hipStream_t s)
-{
-    if (clip->t16_layout != 0) return MLVFS_AMD_OK;
-    int share = 0;
-    int rc = dark_share(packed ? clip->g.bpp : 0, d_frame, clip->g.w, clip->g.h, clip->g.black, s, &share);
-    if (rc) return rc;
-    clip->t16_layout = share >= 307 ? 2 : 1;
-    return MLVFS_AMD_OK;
-}
-
 int mlvfs_amd_clip_set_t16_layout(mlvfs_amd_clip_t *clip_, int layout)
 {
     Clip *clip = reinterpret_cast<Clip *>(clip_);
@@ -843,352 +584,6 @@ int mlvfs_amd_clip_get_t16_layout(const mlvfs_amd_clip_t *clip_)
 {
     const Clip *clip = reinterpret_cast<const Clip *>(clip_);
     return clip ? clip->t16_layout : 0;
-}
-
-int mlvfs_amd_process_frames_dev(mlvfs_amd_clip_t *clip_, const void *d_packed, size_t packed_stride, void *d_out,
-                                 size_t out_stride, int nframes, int cs_method, int fix_pixels, int apply_stripes,
-                                 void *stream)
-{
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    Clip *clip = reinterpret_cast<Clip *>(clip_);
-    hipStream_t s = pick_stream(stream, c);
-    if (cs_method != 0 && clip->g.black > 16384) cs_method = 0;                  // get_raw2ev() == NULL: stage skipped
-    const bool patch = fix_pixels && clip->n_entries > 0;
-    const bool stripes = apply_stripes && clip->needed && (clip->g.w % 8 == 0);
-    const int geo = frame_geo_of(cs_method);
-    if (!patch && !stripes && cs_method == 0)
-        return launch_unpack(d_packed, packed_stride, d_out, out_stride, 0, (uint32_t)clip->g.w * clip->g.h, clip->g.bpp,
-                             nframes, s);
-    if (!frame_kernel_takes(clip->g, d_packed, packed_stride, d_out, out_stride, nframes)) {
-        // n-bit clips (dng.c:813-843 handles any depth) and 12- / 10-bit ones in geometries the fused loader does not take: unpack
-        // first, then the same stages on 16-bit frames
-        const size_t ustride = ((size_t)clip->g.w * clip->g.h * 2 + 255) / 256 * 256;
-        int rc = clip->d_unpacked.reserve(ustride * nframes);
-        if (rc) return rc;
-        rc = launch_unpack(d_packed, packed_stride, clip->d_unpacked, ustride, 0, (uint32_t)clip->g.w * clip->g.h, clip->g.bpp, nframes, s);
-        if (rc) return rc;
-        return mlvfs_amd_process_unpacked_dev(clip_, clip->d_unpacked, ustride, d_out, out_stride, nframes, cs_method, fix_pixels,
-                                              apply_stripes, stream);
-    }
-    if (patch) {
-        int rc = clip->d_patches.reserve(clip->patch_buffer_bytes(nframes));
-        if (rc) return rc;
-        rc = launch_pixfix_for_frame_kernel(clip->g.bpp, d_packed, packed_stride, clip->g.w, clip->g.h, clip->g.black, clip->d_entries,
-                                            clip->d_level_off, clip->n_levels, clip->n_level0, clip->n_entries, clip->d_patches,
-                                            clip->d_tile_rec[geo], clip->n_rec[geo],
-                                            Clip::cells_of(clip->d_patches, clip->n_entries, nframes), nframes, c->dev->luts, s);
-        if (rc) return rc;
-    }
-    if (cs_method != 0) {
-        int rc = decide_t16_layout(clip, true, d_packed, s);
-        if (rc) return rc;
-    }
-    const PatchView pv = clip->patch_view(clip->d_patches, nframes, geo);
-    return launch_frame(c->dev, clip->g, true, d_packed, packed_stride, d_out, out_stride, nframes, cs_method,
-                        patch ? &pv : nullptr, stripes, clip->coef, s, clip->t16_layout == 2);
-}
-
-// the same stages on frames that are already 16-bit in HBM (decoded LJ92 payloads, csrc/lj92.cpp)
-int mlvfs_amd_process_unpacked_dev(mlvfs_amd_clip_t *clip_, const void *d_frames, size_t stride, void *d_out, size_t out_stride,
-                                   int nframes, int cs_method, int fix_pixels, int apply_stripes, void *stream)
-{
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    Clip *clip = reinterpret_cast<Clip *>(clip_);
-    hipStream_t s = pick_stream(stream, c);
-    if (nframes <= 0) return MLVFS_AMD_OK;
-    if (cs_method != 0 && clip->g.black > 16384) cs_method = 0;
-    const bool patch = fix_pixels && clip->n_entries > 0;
-    const bool stripes = apply_stripes && clip->needed && (clip->g.w % 8 == 0);
-    const size_t row_bytes = (size_t)clip->g.w * clip->g.h * 2;
-    const int geo = frame_geo_of(cs_method);
-    if (!patch && !stripes && cs_method == 0) {
-        MLV_HIP(hipMemcpy2DAsync(d_out, out_stride, d_frames, stride, row_bytes, nframes, hipMemcpyDeviceToDevice, s));
-        return MLVFS_AMD_OK;
-    }
-    if (patch) {
-        int rc = clip->d_patches.reserve(clip->patch_buffer_bytes(nframes));
-        if (rc) return rc;
-        rc = launch_pixfix_for_frame_kernel(false, d_frames, stride, clip->g.w, clip->g.h, clip->g.black, clip->d_entries,
-                                            clip->d_level_off, clip->n_levels, clip->n_level0, clip->n_entries, clip->d_patches,
-                                            clip->d_tile_rec[geo], clip->n_rec[geo],
-                                            Clip::cells_of(clip->d_patches, clip->n_entries, nframes), nframes, c->dev->luts, s);
-        if (rc) return rc;
-    }
-    if (cs_method != 0) {
-        int rc = decide_t16_layout(clip, false, d_frames, s);
-        if (rc) return rc;
-    }
-    const PatchView pv = clip->patch_view(clip->d_patches, nframes, geo);
-    return launch_frame(c->dev, clip->g, false, d_frames, stride, d_out, out_stride, nframes, cs_method, patch ? &pv : nullptr,
-                        stripes, clip->coef, s, clip->t16_layout == 2);
-}
-
-// ---- frames that live in HOST memory: chunked, triple-buffered H2D -> fused kernel -> D2H ------------------------
-namespace {
-struct HostPipe {                       // per host thread and device
-    // One stream per STAGE (uploads, kernels, downloads), a ring of NS buffer slots, events between the stages.  All uploads
-    // queue on one stream and all downloads on another, so each direction of the link carries one transfer at a time, back to
-    // back (tools/pcie_bw.py: 48.6 GB/s each way when both run); with one stream per SLOT, each doing upload -> kernel ->
-    // download, transfers of the same direction interleaved and the pipeline stopped at 67 GB/s for both directions together.
-    static constexpr int NS = 4;
-    hipStream_t s[3] = { nullptr, nullptr, nullptr };       // 0 upload, 1 kernels, 2 download
-    hipEvent_t up[NS] = {}, run[NS] = {}, down[NS] = {};
-    DevBuf d_in[NS], d_out[NS], d_patch[NS];
-    int device = 0;
-    HostPipe() { (void)hipGetDevice(&device); }
-    HostPipe(const HostPipe &) = delete;
-    ~HostPipe()                                               // with the host thread that owned it
-    {
-        for (int k = 0; k < 3; k++)
-            if (s[k]) { (void)hipStreamSynchronize(s[k]); release_stream_state(device, s[k]); (void)hipStreamDestroy(s[k]); }
-        for (int k = 0; k < NS; k++) {
-            if (up[k]) (void)hipEventDestroy(up[k]);
-            if (run[k]) (void)hipEventDestroy(run[k]);
-            if (down[k]) (void)hipEventDestroy(down[k]);
-        }
-    }
-    int ensure(size_t in_bytes, size_t out_bytes, size_t patch_bytes)
-    {
-        for (int k = 0; k < 3; k++)
-            if (!s[k]) MLV_HIP(hipStreamCreateWithFlags(&s[k], hipStreamNonBlocking));
-        for (int k = 0; k < NS; k++)
-            if (!up[k]) {
-                MLV_HIP(hipEventCreateWithFlags(&up[k], hipEventDisableTiming));
-                MLV_HIP(hipEventCreateWithFlags(&run[k], hipEventDisableTiming));
-                MLV_HIP(hipEventCreateWithFlags(&down[k], hipEventDisableTiming));
-            }
-        for (int k = 0; k < NS; k++) {
-            if (const int rc = d_in[k].reserve(in_bytes)) return rc;
-            if (const int rc = d_out[k].reserve(out_bytes)) return rc;
-            if (const int rc = d_patch[k].reserve(patch_bytes)) return rc;
-        }
-        return MLVFS_AMD_OK;
-    }
-};
-thread_local std::map<int, HostPipe> t_pipe;
-}  // namespace
-
-int mlvfs_amd_process_frames_host(mlvfs_amd_clip_t *clip_, const void *h_packed, size_t packed_stride, void *h_out,
-                                  size_t out_stride, int nframes, int cs_method, int fix_pixels, int apply_stripes,
-                                  int chunk_frames)
-{
-    ThreadCtx *c = thread_ctx();
-    if (!c) return MLVFS_AMD_ERR_HIP;
-    Clip *clip = reinterpret_cast<Clip *>(clip_);
-    if (nframes <= 0) return MLVFS_AMD_OK;
-    if (chunk_frames <= 0) chunk_frames = 8;
-    if (chunk_frames > nframes) chunk_frames = nframes;
-    if (clip->g.bpp != 14) {
-        // other bit depths: chunks go through the device entry point (unpack + stages on 16-bit frames), one stream, no overlap
-        const size_t din = (packed_stride + 15) / 16 * 16, dout = ((size_t)clip->g.w * clip->g.h * 2 + 15) / 16 * 16;
-        HostPipe &hp0 = t_pipe[c->dev->id];
-        int rc0 = hp0.ensure(din * chunk_frames + 16, dout * chunk_frames, 0);
-        if (rc0) return rc0;
-        for (int f0 = 0; f0 < nframes; f0 += chunk_frames) {
-            const int n = std::min(chunk_frames, nframes - f0);
-            hipStream_t s0 = hp0.s[0];
-            MLV_HIP(hipMemcpy2DAsync(hp0.d_in[0], din, (const uint8_t *)h_packed + (size_t)f0 * packed_stride, packed_stride, packed_stride, n, hipMemcpyHostToDevice, s0));
-            rc0 = mlvfs_amd_process_frames_dev(clip_, hp0.d_in[0], din, hp0.d_out[0], dout, n, cs_method, fix_pixels, apply_stripes, s0);
-            if (rc0) return rc0;
-            MLV_HIP(hipMemcpy2DAsync((uint8_t *)h_out + (size_t)f0 * out_stride, out_stride, hp0.d_out[0], dout, (size_t)clip->g.w * clip->g.h * 2, n, hipMemcpyDeviceToHost, s0));
-            MLV_HIP(hipStreamSynchronize(s0));
-        }
-        return MLVFS_AMD_OK;
-    }
-    if (cs_method != 0 && clip->g.black > 16384) cs_method = 0;
-    const bool patch = fix_pixels && clip->n_entries > 0;
-    const bool stripes = apply_stripes && clip->needed && (clip->g.w % 8 == 0);
-    const size_t dstride_in = (packed_stride + 15) / 16 * 16, dstride_out = ((size_t)clip->g.w * clip->g.h * 2 + 15) / 16 * 16;
-    HostPipe &hp = t_pipe[c->dev->id];
-    const size_t patch_bytes = patch ? clip->patch_buffer_bytes(chunk_frames) : 0;
-    const int geo = frame_geo_of(cs_method);
-    int rc = hp.ensure(dstride_in * chunk_frames + 16, dstride_out * chunk_frames, patch_bytes);
-    if (rc) return rc;
-    const size_t row_bytes = (size_t)clip->g.w * clip->g.h * 2;
-    for (int f0 = 0, k = 0; f0 < nframes; f0 += chunk_frames, k++) {
-        const int n = std::min(chunk_frames, nframes - f0), slot = k % HostPipe::NS;
-        const uint8_t *src = (const uint8_t *)h_packed + (size_t)f0 * packed_stride;
-        uint8_t *dst = (uint8_t *)h_out + (size_t)f0 * out_stride;
-        // upload: the slot's input buffer is free once the kernels of its previous chunk have run
-        hipStream_t s = hp.s[0];
-        if (k >= HostPipe::NS) MLV_HIP(hipStreamWaitEvent(s, hp.run[slot], 0));
-        if (packed_stride == dstride_in) MLV_HIP(hipMemcpyAsync(hp.d_in[slot], src, packed_stride * n, hipMemcpyHostToDevice, s));
-        else MLV_HIP(hipMemcpy2DAsync(hp.d_in[slot], dstride_in, src, packed_stride, packed_stride, n, hipMemcpyHostToDevice, s));
-        MLV_HIP(hipEventRecord(hp.up[slot], s));
-        // kernels: after the upload, and after the slot's previous output has been downloaded
-        s = hp.s[1];
-        MLV_HIP(hipStreamWaitEvent(s, hp.up[slot], 0));
-        if (k >= HostPipe::NS) MLV_HIP(hipStreamWaitEvent(s, hp.down[slot], 0));
-        if (!patch && !stripes && cs_method == 0) {
-            rc = launch_unpack(hp.d_in[slot], dstride_in, hp.d_out[slot], dstride_out, 0, (uint32_t)clip->g.w * clip->g.h, 14, n, s);
-        } else {
-            if (patch) {
-                rc = launch_pixfix_for_frame_kernel(true, hp.d_in[slot], dstride_in, clip->g.w, clip->g.h, clip->g.black, clip->d_entries,
-                                                    clip->d_level_off, clip->n_levels, clip->n_level0, clip->n_entries, hp.d_patch[slot],
-                                                    clip->d_tile_rec[geo], clip->n_rec[geo],
-                                                    Clip::cells_of(hp.d_patch[slot], clip->n_entries, n), n, c->dev->luts, s);
-                if (rc) return rc;
-            }
-            if (cs_method != 0) {
-                rc = decide_t16_layout(clip, true, hp.d_in[slot], s);       // first chunk of the clip only (synchronises once)
-                if (rc) return rc;
-            }
-            const PatchView pv = clip->patch_view(hp.d_patch[slot], n, geo);
-            rc = launch_frame(c->dev, clip->g, true, hp.d_in[slot], dstride_in, hp.d_out[slot], dstride_out, n, cs_method,
-                              patch ? &pv : nullptr, stripes, clip->coef, s, clip->t16_layout == 2);
-        }
-        if (rc) return rc;
-        MLV_HIP(hipEventRecord(hp.run[slot], s));
-        // download
-        s = hp.s[2];
-        MLV_HIP(hipStreamWaitEvent(s, hp.run[slot], 0));
-        if (out_stride == dstride_out) MLV_HIP(hipMemcpyAsync(dst, hp.d_out[slot], out_stride * n, hipMemcpyDeviceToHost, s));
-        else MLV_HIP(hipMemcpy2DAsync(dst, out_stride, hp.d_out[slot], dstride_out, row_bytes, n, hipMemcpyDeviceToHost, s));
-        MLV_HIP(hipEventRecord(hp.down[slot], s));
-    }
-    for (int k = 0; k < 3; k++) MLV_HIP(hipStreamSynchronize(hp.s[k]));
-    return MLVFS_AMD_OK;
-}
-
-// Page-locked host buffers.  A host that allocates one per frame (process_frame's malloc, main.c:931) gets them from a pool:
-// freed buffers are kept by size (rounded up to 64 KiB) and handed out again -- locking pages costs about a millisecond per
-// 10 MB, a pool hit a mutex.  At most POOL_MAX_BYTES stay cached; more is given back to the runtime.
-namespace {
-struct HostPool {
-    std::mutex mu;
-    std::multimap<size_t, void *> free_by_size;
-    std::map<void *, size_t> size_of;             // every live or cached buffer
-    std::set<void *> cached_ptrs;                 // the cached ones: a second free of a buffer must not put it on the list twice
-    size_t cached = 0;
-    static constexpr size_t POOL_MAX_BYTES = (size_t)2 << 30;
-    ~HostPool() { for (auto &kv : free_by_size) (void)hipHostFree(kv.second); }
-};
-HostPool *const g_host_pool = new HostPool;                    // (never destroyed: frees may come while the process exits)
-// The address range every pool buffer so far lies in.  With the allocation shim EVERY free() and realloc() of the host asks whether
-// its pointer is the pool's: a pointer outside the range is answered without the pool's mutex and map (sixteen FUSE workers freeing
-// small strings met at that mutex).
-std::atomic<uintptr_t> g_pool_lo{ ~(uintptr_t)0 }, g_pool_hi{ 0 };
-inline bool outside_pool(const void *p)
-{
-    const uintptr_t a = (uintptr_t)p;
-    return a < g_pool_lo.load(std::memory_order_acquire) || a >= g_pool_hi.load(std::memory_order_acquire);
-}
-}
-
-// is [p, p + bytes) inside a live buffer of mlvfs_amd_host_alloc?  (page-locked and mapped: kernels can address it directly)
-int mlvfs_amd_host_owns(const void *p, size_t bytes)
-{
-    if (outside_pool(p)) return 0;
-    HostPool &hp = *g_host_pool;
-    std::lock_guard<std::mutex> lk(hp.mu);
-    auto it = hp.size_of.upper_bound(const_cast<void *>(p));
-    if (it == hp.size_of.begin()) return false;
-    --it;
-    const uint8_t *base = (const uint8_t *)it->first;
-    return (const uint8_t *)p >= base && (const uint8_t *)p + bytes <= base + it->second && !hp.cached_ptrs.count(it->first);
-}
-
-// bytes from p to the end of the live mlvfs_amd_host_alloc buffer that holds it (0: p is in none)
-size_t mlvfs_amd_host_size(const void *p)
-{
-    if (outside_pool(p)) return 0;
-    HostPool &hp = *g_host_pool;
-    std::lock_guard<std::mutex> lk(hp.mu);
-    auto it = hp.size_of.upper_bound(const_cast<void *>(p));
-    if (it == hp.size_of.begin()) return 0;
-    --it;
-    const uint8_t *base = (const uint8_t *)it->first;
-    if ((const uint8_t *)p < base || (const uint8_t *)p >= base + it->second || hp.cached_ptrs.count(it->first)) return 0;
-    return (size_t)(base + it->second - (const uint8_t *)p);
-}
-
-void *mlvfs_amd_host_alloc(size_t bytes)
-{
-    LibcRandGuard rand_guard;                      // HIP code may run: keep the caller's rand() stream out of its reach
-    if (!thread_ctx()) return nullptr;
-    const size_t want = (std::max<size_t>(bytes, 1) + 65535) / 65536 * 65536;
-    HostPool &hp = *g_host_pool;
-    {
-        std::lock_guard<std::mutex> lk(hp.mu);
-        auto it = hp.free_by_size.find(want);
-        if (it != hp.free_by_size.end()) {
-            void *p = it->second;
-            hp.free_by_size.erase(it);
-            hp.cached_ptrs.erase(p);
-            hp.cached -= want;
-            return p;
-        }
-    }
-    void *p = nullptr;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc(%zu) failed", want); return nullptr; }
-    std::lock_guard<std::mutex> lk(hp.mu);
-    hp.size_of[p] = want;
-    if ((uintptr_t)p < g_pool_lo.load()) g_pool_lo.store((uintptr_t)p, std::memory_order_release);
-    if ((uintptr_t)p + want > g_pool_hi.load()) g_pool_hi.store((uintptr_t)p + want, std::memory_order_release);
-    return p;
-}
-
-// is p inside ANY buffer the pool has handed out -- live or already freed (cached)?  What free() of the allocation shim asks: a
-// stale or second free of a pool buffer must come back to the pool, which reports it, and never reach the C library's free()
-int mlvfs_amd_host_knows(const void *p)
-{
-    if (outside_pool(p)) return 0;
-    HostPool &hp = *g_host_pool;
-    std::lock_guard<std::mutex> lk(hp.mu);
-    auto it = hp.size_of.upper_bound(const_cast<void *>(p));
-    if (it == hp.size_of.begin()) return 0;
-    --it;
-    const uint8_t *base = (const uint8_t *)it->first;
-    return (const uint8_t *)p >= base && (const uint8_t *)p < base + it->second;
-}
-
-// gives the cached (free) buffers back to the runtime; returns the bytes released.  A long-running host calls it when a clip of
-// another geometry starts, or never: at most POOL_MAX_BYTES stay cached
-size_t mlvfs_amd_host_trim(void)
-{
-    LibcRandGuard rand_guard;
-    HostPool &hp = *g_host_pool;
-    std::vector<void *> drop;
-    size_t bytes = 0;
-    {
-        std::lock_guard<std::mutex> lk(hp.mu);
-        for (auto &kv : hp.free_by_size) { drop.push_back(kv.second); hp.size_of.erase(kv.second); }
-        bytes = hp.cached;
-        hp.free_by_size.clear();
-        hp.cached_ptrs.clear();
-        hp.cached = 0;
-    }
-    for (void *p : drop) (void)hipHostFree(p);
-    return bytes;
-}
-
-void mlvfs_amd_host_free(void *p)
-{
-    if (!p) return;
-    LibcRandGuard rand_guard;
-    HostPool &hp = *g_host_pool;
-    {
-        std::lock_guard<std::mutex> lk(hp.mu);
-        auto it = hp.size_of.find(p);
-        if (it == hp.size_of.end()) {                            // not from mlvfs_amd_host_alloc: nothing this library may free
-            fprintf(stderr, "mlvfs_amd: mlvfs_amd_host_free(%p): not a buffer of mlvfs_amd_host_alloc, ignored\n", p);
-            return;
-        }
-        if (hp.cached_ptrs.count(p)) {                           // freed already (two owners would get it from the list)
-            fprintf(stderr, "mlvfs_amd: mlvfs_amd_host_free(%p): freed twice, ignored\n", p);
-            return;
-        }
-        if (hp.cached + it->second <= HostPool::POOL_MAX_BYTES) {
-            hp.free_by_size.emplace(it->second, p);
-            hp.cached_ptrs.insert(p);
-            hp.cached += it->second;
-            return;
-        }
-        hp.size_of.erase(it);
-    }
-    (void)hipHostFree(p);
 }
 
 }  // extern "C"

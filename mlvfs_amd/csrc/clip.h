@@ -73,10 +73,6 @@ struct Clip {
     {
         return (uint8_t *)patches + ((size_t)nframes * (size_t)n_entries * 8 + 15) / 16 * 16;
     }
-    PatchView patch_view(void *patches, int nframes, int geo) const
-    {
-        return PatchView{ cells_of(patches, n_entries, nframes), n_rec[geo], d_tile_off[geo] };
-    }
     DevBuf d_patches, d_scratch;
     // T16 layout of the fused kernel: 0 = not decided yet (from the first frame the clip processes), 1 = plain, 2 = spread
     int t16_layout = 0;
@@ -108,14 +104,11 @@ struct StripesWork {
 };
 
 // device-level pixel repair shared by the drop-in symbols and the dual-ISO path (dropin.cpp)
-struct ThreadCtx;
 bool focus_map_applies(struct frame_headers *fh, ThreadCtx *c, int dual_iso);      // a map file exists and has entries for this frame
 // n_patched (optional): entries of the patch list the repair left in c->d_patch ({position or -1, value} each)
 int focus_pixels_device(struct frame_headers *fh, ThreadCtx *c, void *d_frame, int dual_iso, bool *changed, int *n_patched = nullptr);
 int bad_pixels_device(struct frame_headers *fh, ThreadCtx *c, void *d_frame, int aggressive, int dual_iso, bool *changed, int *n_patched = nullptr);
 
-void glibc_rand_stream(uint16_t *out, size_t n, uint64_t skip, unsigned seed);
-int stripes_solve(const int32_t *hist, const int32_t num[8], int frame_size, int32_t coeffs[8]);
 
 // optional HIP-event timing of the dominant kernel (mlvfs_amd_timer_*)
 struct KernelTimer {
@@ -142,13 +135,9 @@ bool frame_kernel_takes(const Geom &g, const void *src, size_t src_stride, const
 int launch_pixfix(int packed, const void *frames, size_t stride, int w, int black, const void *entries,
                   const int *level_off, int n_levels, int n_level0, int n_entries, void *patches, void *scatter,
                   size_t scatter_stride, int nframes, const DeviceLuts &luts, hipStream_t stream);
-// both of the above for the fused kernel (one launch when the map is small)
-int launch_pixfix_for_frame_kernel(int packed, const void *frames, size_t stride, int w, int h, int black, const void *entries,
-                                   const int *level_off, int n_levels, int n_level0, int n_entries, void *patches,
-                                   const CellRec *recs, int n_rec, void *cells, int nframes, const DeviceLuts &luts, hipStream_t stream);
-// the four pixels of every listed cell after the repair (for the fused kernel): after launch_pixfix, on the same stream
-int launch_pixfix_cells(int packed, const void *frames, size_t stride, int w, int h, const CellRec *recs, int n_rec,
-                        const void *patches, int n_entries, void *cells, int nframes, hipStream_t stream);
+// both of the above for the fused kernel (one launch when the map is small): map's entries and tile lists of geometry `geo`, frames of g
+int launch_pixfix_for_frame_kernel(const Clip &map, int geo, const Geom &g, int packed, const void *frames, size_t stride, void *patches,
+                                   int nframes, const DeviceLuts &luts, hipStream_t stream);
 int launch_deflicker_hist(const void *d_frame, uint32_t samples, uint32_t white, unsigned *d_hist, hipStream_t s);
 // batches of frames `fstride` bytes apart (k_hdr.hip): the deflicker histograms of every frame in one launch and their medians (the
 // reference's 16-bit counters, one workgroup per frame) into d_med[nframes]
@@ -270,7 +259,11 @@ int launch_stripes_count(const void *d_frame, int w, int row0, int row1, int bla
 constexpr int RAND_CHUNK = 31 * 32;      // values per thread of the device generator of the rand() % 1024 stream
 int launch_rand_stream(const uint32_t *d_start, const uint32_t *d_pow2, int npow, uint32_t nchunks, uint32_t *d_states, uint16_t *d_out,
                        size_t n, hipStream_t stream);
+// the rand() % 1024 stream (rand_stream.cpp): a generator state, its words oldest first (next = x[0] + x[28])
+struct RandState { uint32_t x[31]; };
 int rand_stream_device(uint16_t *d_out, size_t n, uint64_t skip, unsigned seed, hipStream_t stream);
+// n values from state `s0` on; *after, if wanted: the state behind them
+int rand_stream_device_from(const RandState &s0, uint16_t *d_out, size_t n, hipStream_t stream, RandState *after);
 size_t stripes_hist_copies_bytes();
 int launch_hist_bump(int *d_hist, const int *d_idx, int n, hipStream_t stream);
 int launch_stripes_hist(const void *d_frame, int w, int row0, int row1, int black, int white, const unsigned char *d_counts,

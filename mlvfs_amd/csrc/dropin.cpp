@@ -7,7 +7,7 @@
 // Error behaviour: never abort, never errno; diagnostics on
 // stderr; on a HIP failure the frame is left untouched and the function returns
 // the reference's failure value.  There is deliberately no CPU fallback.
-#include "clip.h"
+#include "fused_pass.h"
 
 #include <atomic>
 #include <chrono>
@@ -185,8 +185,8 @@ int lazy_run(ThreadCtx *c, bool at_sync)
     (at_sync ? g_lazy_fused : g_lazy_early)++;
     std::shared_ptr<Clip> pix;
     pix.swap(z.pix);
-    const Geom g{ z.w, z.h, 14, z.black, z.white };
-    const bool patch = pix && pix->n_entries > 0;
+    // (the map is shared between threads and only read: the patch list is this thread's, the black level the frame's, no layout is decided)
+    const FusedPass p = fused_pass_of(Geom{ z.w, z.h, 14, z.black, z.white }, 14, z.cs, pix.get(), z.stripes, 1, z.coef);
     int rc = c->ensure_res((z.bytes + 15) / 16 * 16);
     // At the fetch, a frame buffer that comes from mlvfs_amd_host_alloc (page-locked, mapped: integration/mlvfs_amd_wrap_alloc.c
     // makes process_frame's malloc one) is written by the fused kernel itself, over the link: no download, no copy engine.  Sixteen
@@ -197,24 +197,8 @@ int lazy_run(ThreadCtx *c, bool at_sync)
     const bool zero_copy = zc_on && at_sync && ((uintptr_t)z.host % 16) == 0 && mlvfs_amd_host_owns(z.host, z.bytes) != 0;
     void *const d_out = zero_copy ? z.host : c->d_res[0];
     if (!rc && t_fail_next[1]) { t_fail_next[1] = 0; set_error("injected failure of the fused launch (test hook)"); rc = MLVFS_AMD_ERR_HIP; }
-    if (!rc) {
-        if (!patch && z.cs == 0 && !z.stripes)
-            rc = launch_unpack(c->d_a, 0, d_out, 0, 0, (uint32_t)(z.bytes / 2), 14, 1, c->stream);
-        else {
-            PatchView pv{};
-            if (patch) {
-                const int geo = frame_geo_of(z.cs);
-                rc = c->ensure_patch(pix->patch_buffer_bytes(1));
-                if (!rc)
-                    rc = launch_pixfix_for_frame_kernel(true, c->d_a, 0, z.w, z.h, z.black, pix->d_entries, pix->d_level_off, pix->n_levels,
-                                                        pix->n_level0, pix->n_entries, c->d_patch, pix->d_tile_rec[geo], pix->n_rec[geo],
-                                                        Clip::cells_of(c->d_patch, pix->n_entries, 1), 1, c->dev->luts, c->stream);
-                pv = pix->patch_view(c->d_patch, 1, geo);
-            }
-            if (!rc)
-                rc = launch_frame(c->dev, g, true, c->d_a, 0, d_out, 0, 1, z.cs, patch ? &pv : nullptr, z.stripes, z.coef, c->stream);
-        }
-    }
+    if (!rc && p.map) rc = c->ensure_patch(p.map->patch_buffer_bytes(1));
+    if (!rc) rc = run_fused_pass(c->dev, p, c->d_a, 0, d_out, 0, 1, c->d_patch, c->stream);
     if (!rc && zero_copy) {                        // the frame is in the caller's buffer once the stream has drained; no device copy is kept
         ProfScope prof_down(6);
         if (wait_stream(c->stream) != hipSuccess) { set_error("fused launch (zero copy): stream wait failed"); rc = MLVFS_AMD_ERR_HIP; }
@@ -593,7 +577,7 @@ void chroma_smooth(struct frame_headers *fh, uint16_t *image_data, int method)
     ProfScope prof_stage(3);
     LibcRandGuard rand_guard;                      // HIP code may run: keep the caller's rand() stream out of its reach
     const FrameView v = view_of(fh);
-    if (v.black > 16384) { fprintf(stderr, "Black level too large for processing\n"); return; }   // main.c:170-174
+    if (black_too_large(v.black)) { fprintf(stderr, "Black level too large for processing\n"); return; }   // main.c:170-174
     if (method != 2 && method != 3 && method != 5) { fprintf(stderr, "Unsupported chroma smooth method\n"); return; }
     ThreadCtx *c = thread_ctx();
     if (!c) return;
@@ -624,7 +608,7 @@ namespace mlv {
 bool cached_bad_clip(struct frame_headers *fh, ThreadCtx *c, int aggressive, std::shared_ptr<Clip> *out)
 {
     const FrameView v = view_of(fh);
-    if (v.black > 16384 || !v.guid) return false;
+    if (black_too_large(v.black) || !v.guid) return false;
     std::lock_guard<std::mutex> lk(g_bad_mutex);
     for (int i = 0; i < BAD_PIXEL_MAP_COUNT; i++) {
         BadMap &m = g_bad_maps[i];
@@ -646,7 +630,7 @@ int bad_pixels_device(struct frame_headers *fh, ThreadCtx *c, void *d_frame, int
     if (n_patched) *n_patched = 0;
     const FrameView v = view_of(fh);
     if (changed) *changed = false;
-    if (v.black > 16384) { fprintf(stderr, "Black level too large for processing\n"); return MLVFS_AMD_OK; }
+    if (black_too_large(v.black)) { fprintf(stderr, "Black level too large for processing\n"); return MLVFS_AMD_OK; }
     const size_t bytes = (size_t)v.w * v.h * 2;
     ClipRef clip;
     {
@@ -737,7 +721,7 @@ static ClipRef focus_clip_ref(struct frame_headers *fh, ThreadCtx *c, int dual_i
         if (m->camera == camera && m->raw_w == raw_w && m->raw_h == raw_h) fm = m;
     if (!fm) fm = load_focus_map(camera, raw_w, raw_h);
     if (fm->xy.empty()) return nullptr;                                              // no map for this camera: no-op
-    if (v.black > 16384) { fprintf(stderr, "raw2ev LUT error\n"); return nullptr; }
+    if (black_too_large(v.black)) { fprintf(stderr, "raw2ev LUT error\n"); return nullptr; }
     const std::string key = derived_key(v, c, dual_iso);
     ClipRef &slot = fm->clips[key];
     if (!slot) {
@@ -904,7 +888,7 @@ void stripes_apply_correction(struct frame_headers *fh, struct stripes_correctio
     LibcRandGuard rand_guard;                      // HIP code may run: keep the caller's rand() stream out of its reach
     if (!correction || !correction->correction_needed) return;                       // stripes.c:252-253
     const FrameView v = view_of(fh);
-    if (v.w % 8 != 0 || size == 0) return;
+    if (!stripes_apply_to(true, correction->correction_needed, v.w) || size == 0) return;
     ThreadCtx *c = thread_ctx();
     if (!c) return;
     // pixel i uses coefficient (i + offset % 8) % 8: rotate the table instead

@@ -289,27 +289,29 @@ __global__ __launch_bounds__(256) void k_pixfix_small(const uint8_t *__restrict_
     }
 }
 
-// patch list + cell records for the fused kernel: one launch for a small map, the flat grid + levels + cells for a large one
-int launch_pixfix_for_frame_kernel(int packed, const void *frames, size_t stride, int w, int h, int black, const void *entries,
-                                   const int *level_off, int n_levels, int n_level0, int n_entries, void *patches,
-                                   const CellRec *recs, int n_rec, void *cells, int nframes, const DeviceLuts &luts, hipStream_t stream)
+// patch list + cell records for the fused kernel: one launch for a small map, the flat grid + levels + cells for a large one.
+// g: the frames' geometry (a shared map serves frames of other black levels); patches: map.patch_buffer_bytes(nframes) bytes
+int launch_pixfix_for_frame_kernel(const Clip &map, int geo, const Geom &g, int packed, const void *frames, size_t stride, void *patches,
+                                   int nframes, const DeviceLuts &luts, hipStream_t stream)
 {
+    const int n_entries = map.n_entries, n_rec = map.n_rec[geo], bpp = packed == 1 ? 14 : packed;
     if (n_entries <= 0 || nframes <= 0) return MLVFS_AMD_OK;
-    const int bpp = packed == 1 ? 14 : packed;
+    const CellRec *recs = map.d_tile_rec[geo];
+    void *cells = Clip::cells_of(patches, n_entries, nframes);
     if (n_entries > 1024 || n_rec > 2048) {
-        int rc = launch_pixfix(packed, frames, stride, w, black, entries, level_off, n_levels, n_level0, n_entries, patches, nullptr, 0,
-                               nframes, luts, stream);
+        int rc = launch_pixfix(packed, frames, stride, g.w, g.black, map.d_entries, map.d_level_off, map.n_levels, map.n_level0, n_entries,
+                               patches, nullptr, 0, nframes, luts, stream);
         if (rc) return rc;
-        return launch_pixfix_cells(packed, frames, stride, w, h, recs, n_rec, patches, n_entries, cells, nframes, stream);
+        return launch_pixfix_cells(packed, frames, stride, g.w, g.h, recs, n_rec, patches, n_entries, cells, nframes, stream);
     }
     if (packed)
-        hipLaunchKernelGGL(k_pixfix_small<true>, dim3(nframes), dim3(256), 0, stream, (const uint8_t *)frames, stride, w, h, black,
-                           (const PixEntry *)entries, level_off, n_levels, n_entries, (int2 *)patches, recs, n_rec, (int4 *)cells,
-                           luts.t16, luts.u16, bpp);
+        hipLaunchKernelGGL(k_pixfix_small<true>, dim3(nframes), dim3(256), 0, stream, (const uint8_t *)frames, stride, g.w, g.h, g.black,
+                           (const PixEntry *)map.d_entries, (const int *)map.d_level_off, map.n_levels, n_entries, (int2 *)patches, recs,
+                           n_rec, (int4 *)cells, luts.t16, luts.u16, bpp);
     else
-        hipLaunchKernelGGL(k_pixfix_small<false>, dim3(nframes), dim3(256), 0, stream, (const uint8_t *)frames, stride, w, h, black,
-                           (const PixEntry *)entries, level_off, n_levels, n_entries, (int2 *)patches, recs, n_rec, (int4 *)cells,
-                           luts.t16, luts.u16, bpp);
+        hipLaunchKernelGGL(k_pixfix_small<false>, dim3(nframes), dim3(256), 0, stream, (const uint8_t *)frames, stride, g.w, g.h, g.black,
+                           (const PixEntry *)map.d_entries, (const int *)map.d_level_off, map.n_levels, n_entries, (int2 *)patches, recs,
+                           n_rec, (int4 *)cells, luts.t16, luts.u16, bpp);
     MLV_HIP(hipGetLastError());
     return MLVFS_AMD_OK;
 }

@@ -297,7 +297,7 @@ int launch_stripes_apply(void *d_frames, size_t stride, size_t npix, int w, int 
 }  // namespace mlv
 
 // ---------------------------------------------------------------- glibc rand() % 1024 stream on the device
-// x[i] = x[i-31] + x[i-3] (mod 2^32), output (x >> 1) % 1024 (see clip.cpp).  The recurrence is linear, so the state at the
+// x[i] = x[i-31] + x[i-3] (mod 2^32), output (x >> 1) % 1024 (see rand_stream.cpp).  The recurrence is linear, so the state at the
 // start of chunk c is (A^RAND_CHUNK)^c times the state at the start of the stream: k_rand_states applies the host-built
 // powers (A^RAND_CHUNK)^(2^j) for the set bits of c, k_rand_fill then lets one thread per chunk run its 992 = 31 * 32 values
 // with the 31-word ring in registers (31 unrolled steps per round), eight values per 16-byte store.

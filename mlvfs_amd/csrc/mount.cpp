@@ -55,7 +55,7 @@
 // mlvfs_amd_mount_set_resample_demosaic(1): the three resampled calls render through balance, amaze_launch and the resampling pass behind
 // it (amaze_render.cpp, k_amaze_resample.hip) instead of k_resample.hip, whatever set_demosaic says; placement, growth and everything
 // behind the renderings are the resampled route's.  At 0 (the default) the resampled calls are what they were, refused under set_demosaic(1).
-#include "clip.h"
+#include "fused_pass.h"
 #include "lj92enc.h"
 #include "jpeg.h"
 #include "render_route.h"
@@ -364,7 +364,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
         const int cs = o.chroma_smooth;
         if (!cs || o.dual_iso == 2) return 0;
         if (cs != 2 && cs != 3 && cs != 5) { fprintf(stderr, "Unsupported chroma smooth method\n"); return 0; }
-        if (fh[k].rawi_hdr.raw_info.black_level > 16384) { fprintf(stderr, "Black level too large for processing\n"); return 0; }
+        if (black_too_large(fh[k].rawi_hdr.raw_info.black_level)) { fprintf(stderr, "Black level too large for processing\n"); return 0; }
         return cs;
     };
     for (int k0 = 0, k1; k0 < n; k0 = k1) {
@@ -377,7 +377,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             // the clip's correction from this frame as it is after chroma smoothing (stripes_compute_correction), then applied to it
             uint8_t *src = F + a * dstride;
             if (cs) {
-                rc = launch_frame(c->dev, g, false, src, img, O + a * dstride, img, 1, cs, nullptr, false, nullptr, s);
+                rc = run_fused_pass(c->dev, fused_pass_of(g, 0, cs, nullptr, false, 0, nullptr), src, img, O + a * dstride, img, 1, nullptr, s);
                 if (rc) return rc;
                 src = O + a * dstride;
             }
@@ -391,17 +391,17 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
             memcpy(m.coef, cl.coef, sizeof m.coef);
             m.stripes_needed = cl.needed;
             m.stripes_known = true;
-            if (m.stripes_needed && w % 8 == 0) {
+            if (stripes_apply_to(true, m.stripes_needed, w)) {
                 rc = launch_stripes_apply(src, img, (size_t)w * h, w, g.black, g.white, m.coef, 1, s);
                 if (rc) return rc;
             }
             final_at[a] = src;
             a++;
         }
-        const bool stripes = o.fix_stripes && m.stripes_needed && w % 8 == 0;
-        for (int k = a; k < k1; k++) final_at[k] = (cs || stripes) ? O + k * dstride : F + k * dstride;
-        if (a < k1 && (cs || stripes)) {
-            rc = launch_frame(c->dev, g, false, F + a * dstride, dstride, O + a * dstride, dstride, k1 - a, cs, nullptr, stripes, m.coef, s);
+        const FusedPass p = fused_pass_of(g, 0, cs, nullptr, o.fix_stripes, m.stripes_needed, m.coef);     // (no map: the repairs ran above)
+        for (int k = a; k < k1; k++) final_at[k] = p.idle() ? F + k * dstride : O + k * dstride;
+        if (a < k1 && !p.idle()) {
+            rc = run_fused_pass(c->dev, p, F + a * dstride, dstride, O + a * dstride, dstride, k1 - a, nullptr, s);
             if (rc) return rc;
         }
     }

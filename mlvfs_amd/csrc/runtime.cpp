@@ -1,5 +1,5 @@
 // runtime.cpp -- host runtime of libmlvfs_amd.so: error string, EV tables and
-// their exact 16-bit re-encodings, per-device state, per-thread contexts.
+// their exact 16-bit re-encodings, per-device state, per-thread contexts, the kernel timer, the pool of page-locked host buffers.
 //
 // Threading model (SURVEY.md 8b "Threading"): libfuse calls the exported
 // functions from a pool of worker threads, one frame per call.  Each host thread
@@ -7,7 +7,7 @@
 // are shared read-only (tables), per-clip state is guarded by its own mutex.
 // Threads that never called mlvfs_amd_init() are spread round-robin over the
 // visible GPUs, which is the frame-parallel multi-GPU mode of the drop-in path.
-#include "common.h"
+#include "clip.h"
 
 #include <atomic>
 #include <climits>
@@ -17,6 +17,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 #include <vector>
 #include <string>
 #include <algorithm>
@@ -437,6 +438,12 @@ int ThreadCtx::ensure_patch(size_t need)
     return d_patch.reserve(need);
 }
 
+KernelTimer &kernel_timer()
+{
+    static thread_local KernelTimer t;
+    return t;
+}
+
 }  // namespace mlv
 
 // ------------------------------------------------------------------ C ABI
@@ -465,5 +472,173 @@ int mlvfs_amd_init(int device) { return mlv::bind_device(device); }
 const char *mlvfs_amd_last_error(void) { return mlv::g_err; }
 const char *mlvfs_amd_version(void) { return "mlvfs_amd 0.1.0 (gfx950)"; }
 
+int mlvfs_amd_timer_begin(int max_launches)
+{
+    if (!mlv::thread_ctx()) return MLVFS_AMD_ERR_HIP;
+    mlv::KernelTimer &tm = mlv::kernel_timer();
+    while ((int)tm.ev.size() < 2 * max_launches) {
+        hipEvent_t e;
+        MLV_HIP(hipEventCreate(&e));
+        tm.ev.push_back(e);
+    }
+    tm.used = 0;
+    tm.on = true;
+    return MLVFS_AMD_OK;
 }
 
+int mlvfs_amd_timer_end(float *ms, int cap)
+{
+    mlv::KernelTimer &tm = mlv::kernel_timer();
+    tm.on = false;
+    int n = 0;
+    for (int i = 0; i + 1 < tm.used && n < cap; i += 2, n++) {
+        MLV_HIP(hipEventSynchronize(tm.ev[i + 1]));
+        MLV_HIP(hipEventElapsedTime(&ms[n], tm.ev[i], tm.ev[i + 1]));
+    }
+    tm.used = 0;
+    return n;
+}
+
+// ------------------------------------------------------------------ mlvfs_amd_host_*: what the allocation shim asks on every free()
+using namespace mlv;
+
+// Page-locked host buffers.  A host that allocates one per frame (process_frame's malloc, main.c:931) gets them from a pool:
+// freed buffers are kept by size (rounded up to 64 KiB) and handed out again -- locking pages costs about a millisecond per
+// 10 MB, a pool hit a mutex.  At most POOL_MAX_BYTES stay cached; more is given back to the runtime.
+namespace {
+struct HostPool {
+    std::mutex mu;
+    std::multimap<size_t, void *> free_by_size;
+    std::map<void *, size_t> size_of;             // every live or cached buffer
+    std::set<void *> cached_ptrs;                 // the cached ones: a second free of a buffer must not put it on the list twice
+    size_t cached = 0;
+    static constexpr size_t POOL_MAX_BYTES = (size_t)2 << 30;
+    ~HostPool() { for (auto &kv : free_by_size) (void)hipHostFree(kv.second); }
+};
+HostPool *const g_host_pool = new HostPool;                    // (never destroyed: frees may come while the process exits)
+// The address range every pool buffer so far lies in.  With the allocation shim EVERY free() and realloc() of the host asks whether
+// its pointer is the pool's: a pointer outside the range is answered without the pool's mutex and map (sixteen FUSE workers freeing
+// small strings met at that mutex).
+std::atomic<uintptr_t> g_pool_lo{ ~(uintptr_t)0 }, g_pool_hi{ 0 };
+inline bool outside_pool(const void *p)
+{
+    const uintptr_t a = (uintptr_t)p;
+    return a < g_pool_lo.load(std::memory_order_acquire) || a >= g_pool_hi.load(std::memory_order_acquire);
+}
+}
+
+// is [p, p + bytes) inside a live buffer of mlvfs_amd_host_alloc?  (page-locked and mapped: kernels can address it directly)
+int mlvfs_amd_host_owns(const void *p, size_t bytes)
+{
+    if (outside_pool(p)) return 0;
+    HostPool &hp = *g_host_pool;
+    std::lock_guard<std::mutex> lk(hp.mu);
+    auto it = hp.size_of.upper_bound(const_cast<void *>(p));
+    if (it == hp.size_of.begin()) return false;
+    --it;
+    const uint8_t *base = (const uint8_t *)it->first;
+    return (const uint8_t *)p >= base && (const uint8_t *)p + bytes <= base + it->second && !hp.cached_ptrs.count(it->first);
+}
+
+// bytes from p to the end of the live mlvfs_amd_host_alloc buffer that holds it (0: p is in none)
+size_t mlvfs_amd_host_size(const void *p)
+{
+    if (outside_pool(p)) return 0;
+    HostPool &hp = *g_host_pool;
+    std::lock_guard<std::mutex> lk(hp.mu);
+    auto it = hp.size_of.upper_bound(const_cast<void *>(p));
+    if (it == hp.size_of.begin()) return 0;
+    --it;
+    const uint8_t *base = (const uint8_t *)it->first;
+    if ((const uint8_t *)p < base || (const uint8_t *)p >= base + it->second || hp.cached_ptrs.count(it->first)) return 0;
+    return (size_t)(base + it->second - (const uint8_t *)p);
+}
+
+void *mlvfs_amd_host_alloc(size_t bytes)
+{
+    LibcRandGuard rand_guard;                      // HIP code may run: keep the caller's rand() stream out of its reach
+    if (!thread_ctx()) return nullptr;
+    const size_t want = (std::max<size_t>(bytes, 1) + 65535) / 65536 * 65536;
+    HostPool &hp = *g_host_pool;
+    {
+        std::lock_guard<std::mutex> lk(hp.mu);
+        auto it = hp.free_by_size.find(want);
+        if (it != hp.free_by_size.end()) {
+            void *p = it->second;
+            hp.free_by_size.erase(it);
+            hp.cached_ptrs.erase(p);
+            hp.cached -= want;
+            return p;
+        }
+    }
+    void *p = nullptr;
+    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc(%zu) failed", want); return nullptr; }
+    std::lock_guard<std::mutex> lk(hp.mu);
+    hp.size_of[p] = want;
+    if ((uintptr_t)p < g_pool_lo.load()) g_pool_lo.store((uintptr_t)p, std::memory_order_release);
+    if ((uintptr_t)p + want > g_pool_hi.load()) g_pool_hi.store((uintptr_t)p + want, std::memory_order_release);
+    return p;
+}
+
+// is p inside ANY buffer the pool has handed out -- live or already freed (cached)?  What free() of the allocation shim asks: a
+// stale or second free of a pool buffer must come back to the pool, which reports it, and never reach the C library's free()
+int mlvfs_amd_host_knows(const void *p)
+{
+    if (outside_pool(p)) return 0;
+    HostPool &hp = *g_host_pool;
+    std::lock_guard<std::mutex> lk(hp.mu);
+    auto it = hp.size_of.upper_bound(const_cast<void *>(p));
+    if (it == hp.size_of.begin()) return 0;
+    --it;
+    const uint8_t *base = (const uint8_t *)it->first;
+    return (const uint8_t *)p >= base && (const uint8_t *)p < base + it->second;
+}
+
+// gives the cached (free) buffers back to the runtime; returns the bytes released.  A long-running host calls it when a clip of
+// another geometry starts, or never: at most POOL_MAX_BYTES stay cached
+size_t mlvfs_amd_host_trim(void)
+{
+    LibcRandGuard rand_guard;
+    HostPool &hp = *g_host_pool;
+    std::vector<void *> drop;
+    size_t bytes = 0;
+    {
+        std::lock_guard<std::mutex> lk(hp.mu);
+        for (auto &kv : hp.free_by_size) { drop.push_back(kv.second); hp.size_of.erase(kv.second); }
+        bytes = hp.cached;
+        hp.free_by_size.clear();
+        hp.cached_ptrs.clear();
+        hp.cached = 0;
+    }
+    for (void *p : drop) (void)hipHostFree(p);
+    return bytes;
+}
+
+void mlvfs_amd_host_free(void *p)
+{
+    if (!p) return;
+    LibcRandGuard rand_guard;
+    HostPool &hp = *g_host_pool;
+    {
+        std::lock_guard<std::mutex> lk(hp.mu);
+        auto it = hp.size_of.find(p);
+        if (it == hp.size_of.end()) {                            // not from mlvfs_amd_host_alloc: nothing this library may free
+            fprintf(stderr, "mlvfs_amd: mlvfs_amd_host_free(%p): not a buffer of mlvfs_amd_host_alloc, ignored\n", p);
+            return;
+        }
+        if (hp.cached_ptrs.count(p)) {                           // freed already (two owners would get it from the list)
+            fprintf(stderr, "mlvfs_amd: mlvfs_amd_host_free(%p): freed twice, ignored\n", p);
+            return;
+        }
+        if (hp.cached + it->second <= HostPool::POOL_MAX_BYTES) {
+            hp.free_by_size.emplace(it->second, p);
+            hp.cached_ptrs.insert(p);
+            hp.cached += it->second;
+            return;
+        }
+        hp.size_of.erase(it);
+    }
+    (void)hipHostFree(p);
+}
+
+}  // extern "C"
