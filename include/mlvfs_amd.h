@@ -1328,6 +1328,89 @@ int    mlvfs_amd_mount_set_resample_demosaic(void *mount, int which);
  * to 8; a band's source rows from floor(v0 H / oh) up to ceil(v1 H / oh), walked a step at a time from the first.                   */
 int    mlvfs_amd_test_amz_resample_plan(int width, int height, int ow, int oh, int nframes, int32_t out[8]);
 
+/* -- a clip's frames as device-resident tensors (csrc/k_tensor.hip, csrc/tensor.cpp, csrc/mount.cpp) ------------------ */
+/* The frame the mount would have served, written into the caller's device memory as a tensor: nothing crosses the link.  The definition
+ * is this project's (mlvfs_amd/tensor.py restates it in numpy).  Two kinds:
+ * RGB.    The source is a rendering exactly as a file route produces it: ph x pw pixels, interleaved R, G, B; 8-bit samples behind the
+ *         mlvfs_amd_mount_rgb* routes (with the handle's look if one is set), 16-bit samples behind the mlvfs_amd_mount_rgb16* routes
+ *         through the deep look of the call (an identity shaper and n = 0: linear light).  C = 3.  v = the sample;
+ *         unit = fl32(1 / 255) or fl32(1 / 65535), the double quotient rounded once to binary32.
+ * Bayer.  The source is the frame mlvfs_amd_mount_dng would have served: after every stage, 16-bit mosaic, RGGB.  C = 4 planes of
+ *         floor(H / 2) x floor(W / 2): R (2Y, 2X), G1 (2Y, 2X + 1), G2 (2Y + 1, 2X), B (2Y + 1, 2X + 1); an odd last row or column is
+ *         never read.  black and range = max(white - black, 1) from the header written for that frame in its final state (after a
+ *         dual-ISO conversion the x4 levels, so they differ from frame to frame in a mixed clip).  v = px - black as a signed integer,
+ *         clamped at neither end.  unit = fl32(1.0 / range), divided in double.  |black| > 2^30 is refused.
+ * The element of channel c:
+ *   F32   y = fl32(fl32(fl32(v) unit) scale_c), out = fl32(y + bias_c): three operations, each rounded to binary32 on its own, never fused
+ *   F16   that value converted by round-to-nearest-even: results below 2^-14 become subnormal halves, overflow gives infinity
+ *   BF16  that value converted by round-to-nearest-even
+ *   U8    8-bit RGB sources only: the sample itself, re-laid out         U16   16-bit RGB sources: the sample; Bayer: the raw px
+ *   For U8 and U16 scale and bias are not read; any other pair of source and integer dtype is refused.
+ * scale_c, bias_c: binary32 from the caller, each finite and either zero or of magnitude within [2^-64, 2^64]; anything else is refused.
+ *   Inside that range no intermediate binary32 is subnormal: the only gradual underflow of the definition is the conversion to half.
+ * Layout.  NCHW: C planes of ph x pw per frame; NHWC: C interleaved.  Frames lie out_stride bytes apart, a multiple of the element's size
+ *   and at least C ph pw elements; bytes between frames are never touched.
+ * Not built: the tensor written from inside the tone kernels, a proxy handle, JPEG, other CFA orders, the drop-in symbols.          */
+#define MLVFS_AMD_TENSOR_RGB       0
+#define MLVFS_AMD_TENSOR_BAYER     1
+#define MLVFS_AMD_TENSOR_HALF      0     /* the rendering of mlvfs_amd_mount_rgb / _rgb16 */
+#define MLVFS_AMD_TENSOR_FULL      1     /* of mlvfs_amd_mount_rgb_full / _rgb16_full */
+#define MLVFS_AMD_TENSOR_SCALED    2     /* of mlvfs_amd_mount_rgb_scaled / _rgb16_scaled, ow x oh */
+#define MLVFS_AMD_TENSOR_RESAMPLED 3     /* of mlvfs_amd_mount_rgb_resampled / _rgb16_resampled, ow x oh */
+#define MLVFS_AMD_TENSOR_F32       0
+#define MLVFS_AMD_TENSOR_F16       1
+#define MLVFS_AMD_TENSOR_BF16      2
+#define MLVFS_AMD_TENSOR_U8        3
+#define MLVFS_AMD_TENSOR_U16       4
+#define MLVFS_AMD_TENSOR_NCHW      0
+#define MLVFS_AMD_TENSOR_NHWC      1
+/* What a tensor call asks for.  For Bayer only kind, dtype, layout, scale and bias are read.  The device calls below read dtype, layout,
+ * scale and bias.                                                                                                                   */
+typedef struct {
+    int32_t kind;                        /* MLVFS_AMD_TENSOR_RGB, _BAYER */
+    int32_t size;                        /* MLVFS_AMD_TENSOR_HALF .. _RESAMPLED */
+    int32_t ow, oh;                      /* _SCALED, _RESAMPLED */
+    int32_t gain_q8;                     /* 1 .. 65535, 256 is unity */
+    int32_t dtype;                       /* MLVFS_AMD_TENSOR_F32 .. _U16 */
+    int32_t layout;                      /* MLVFS_AMD_TENSOR_NCHW, _NHWC */
+    int32_t reserved;                    /* 0 */
+    const mlvfs_amd_look16_t *look16;    /* the deep look of a 16-bit rendering, or NULL: the 8-bit rendering */
+    float scale[4], bias[4];
+} mlvfs_amd_tensor_spec_t;
+/* The pass alone, on a caller's renderings: nframes renderings of pw x ph pixels of three src_bits-bit samples (8 or 16), src_stride
+ * bytes apart -> their tensors, out_stride bytes apart.  Never in place; the source is not written.  Asynchronous on `stream`; every
+ * check happens before any device work and follows no pointer: nulls, pw, ph >= 1 and pw ph < 2^28, a negative count, src_bits, a dtype
+ * or layout that does not exist or is illegal for the source, scale or bias outside the range above (float dtypes), a source or a
+ * destination off its element's boundary, strides too small or no multiple of the element, a destination that overlaps the source.
+ * pw a multiple of 8 with both bases and strides 16-byte aligned takes the fast form (k_tensor_rgb_x8: 8 pixels per lane, 24 or 48
+ * source bytes as 64- and 128-bit loads, three runs of 8 elements or one of 24), anything else one pixel per lane (k_tensor_rgb_generic). */
+int    mlvfs_amd_tensor_rgb_dev(const void *d_src, size_t src_stride, int pw, int ph, int src_bits, const mlvfs_amd_tensor_spec_t *spec,
+                                void *d_out, size_t out_stride, int nframes, void *stream);
+/* What the Bayer pass reads per frame, from the frame's headers as they are: out = { black, range (reported as at most 2^31 - 1; unit
+ * is of the range itself), the bits of unit, 0 }.  Host code.  MLVFS_AMD_ERR_ARG, with out untouched: a null pointer, |black| > 2^30. */
+int    mlvfs_amd_tensor_bayer_params(const struct frame_headers *frame_headers, int32_t out[4]);
+/* The pass alone, on a caller's frames: nframes frames of width x height 16-bit pixels `stride` bytes apart -> their tensors of 4 planes
+ * of (height / 2) x (width / 2), frame k with the four parameters d_levels[4 k ..] (device memory, as mlvfs_amd_tensor_bayer_params
+ * yields them; the pass reads black and unit).  The checks are mlvfs_amd_tensor_rgb_dev's, with width, height >= 2, width height
+ * < 2^28, an odd source address or stride and levels off a 4-byte boundary or overlapped by the destination.  width a multiple of 16
+ * with both bases and strides 16-byte aligned takes the fast form (k_tensor_bayer_x8: 16 pixels of each of the two rows of a superpixel
+ * row per lane, 8 elements to each of four planes or 32 interleaved), anything else one superpixel per lane (k_tensor_bayer_generic). */
+int    mlvfs_amd_tensor_bayer_dev(const void *d_frames, size_t stride, int width, int height, const int32_t *d_levels,
+                                  const mlvfs_amd_tensor_spec_t *spec, void *d_out, size_t out_stride, int nframes, void *stream);
+/* Frames first .. first + count - 1 as tensors in the caller's device memory, out_stride bytes apart: the stages, the serve-order state
+ * and results[] of every other serving call; only the last step differs.  The rendering lies where the file routes leave it, and one
+ * launch of the pass per run of frames writes d_out in the place of the downloads; a Bayer tensor is read from the final frames.  The
+ * handle's look, demosaic settings, dark frame and flat field apply as they do to the file routes.  The call synchronises the library's
+ * stream before it returns.  May be interleaved with the other serving calls on one handle; a handle that never makes a tensor call
+ * serves byte for byte and launch for launch what it served before.  MLVFS_AMD_ERR_ARG before anything is launched: nulls, a spec
+ * outside the definition, a handle with mlvfs_amd_mount_set_proxy(2), a shape the route does not take, an out_stride below
+ * mlvfs_amd_mount_tensor_bytes or no multiple of the element, d_out that is not device memory on the handle's device (a host pointer,
+ * another device's) or off the element's boundary.                                                                                  */
+int    mlvfs_amd_mount_tensor(void *mount, int first, int count, void *d_out, size_t out_stride, const mlvfs_amd_tensor_spec_t *spec,
+                              int batch_frames, int io_threads, int *results);
+/* bytes of the tensor of frame `index`; 0 with the error set: no such frame, a spec outside the definition, a shape the route refuses */
+size_t mlvfs_amd_mount_tensor_bytes(const void *mount, int index, const mlvfs_amd_tensor_spec_t *spec);
+
 /* self tests that need no GPU (selection networks, LUT identities): 0 = pass */
 int mlvfs_amd_selftest_host(void);
 /* Test hook, host only: the two selection networks of k_frame_p5's pair step (csrc/median_nets.h) on the caller's values, n sets at a

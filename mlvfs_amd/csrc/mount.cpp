@@ -55,10 +55,15 @@
 // mlvfs_amd_mount_set_resample_demosaic(1): the three resampled calls render through balance, amaze_launch and the resampling pass behind
 // it (amaze_render.cpp, k_amaze_resample.hip) instead of k_resample.hip, whatever set_demosaic says; placement, growth and everything
 // behind the renderings are the resampled route's.  At 0 (the default) the resampled calls are what they were, refused under set_demosaic(1).
+//
+// mlvfs_amd_mount_tensor leaves the frame where it lies: the same stages and, for an RGB tensor, the same rendering in the same place,
+// then one launch of the tensor pass (k_tensor.hip) per run of frames into the caller's device memory in the place of the downloads; a
+// Bayer tensor is read from the final frames.  No header is written, nothing crosses the link, and no other call knows.
 #include "fused_pass.h"
 #include "lj92enc.h"
 #include "jpeg.h"
 #include "render_route.h"
+#include "tensor.h"
 
 #include <cstring>
 #include <string>
@@ -116,6 +121,7 @@ struct Serve {
     size_t *sizes = nullptr;
     int *flags = nullptr;
     int sampling = MLVFS_AMD_JPEG_420;       // the handle's, as the call found it
+    const mlvfs_amd_tensor_spec_t *tensor = nullptr;     // mlvfs_amd_mount_tensor: h_out is the caller's device memory, no file is written
     int pw = 0, ph = 0;                      // the rendering's size
 
     bool in_full() const { return route.size == RenderRoute::FULL || route.size == RenderRoute::RESAMPLED; }     // the renderings lie in d_full
@@ -253,6 +259,12 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
         const int32_t *par = (const int32_t *)m.d_rgb + (size_t)k0 * RGB_PARAMS;
         const int rc = route_launch(sv.route, c, final_at[k0], dstride, par, dst, rstride, w, h, k1 - k0, s, lk, deep);
         if (rc) return rc;
+        if (sv.tensor) {                                               // the rendering stays where it lies: the pass in the place of the downloads
+            const int rt = launch_tensor_rgb(dst, rstride, pw, ph, deep ? 16 : 8, sv.tensor->dtype, sv.tensor->layout, tensor_affine(*sv.tensor),
+                                             h_out + k0 * out_stride, out_stride, k1 - k0, s);
+            if (rt) return rt;
+            continue;
+        }
         std::vector<JpgOut> res(k1 - k0, JpgOut{ 0, 1 });
         const size_t room = sv.quality ? std::min(jpg_room(pw, ph), sstride) : 0;
         if (room) {
@@ -281,6 +293,29 @@ int fetch_rgb(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dst
     return MLVFS_AMD_OK;
 }
 
+// The batch's final frames as Bayer tensors: black, range and unit of every frame from its headers as they are now, one upload, runs of
+// frames that lie on one side of the slot pair in one launch each
+int fetch_bayer_tensor(Mount &m, ThreadCtx *c, const frame_headers *fh, int n, size_t dstride, const std::vector<uint8_t *> &final_at, uint8_t *d_out,
+                       size_t out_stride, int w, int h, const Serve &sv)
+{
+    hipStream_t s = c->stream;
+    uint8_t *const F = (uint8_t *)m.d_frames;
+    std::vector<int32_t> &levels = m.rgb_host;
+    levels.resize((size_t)n * TENSOR_LEVELS);
+    for (int k = 0; k < n; k++)
+        if (const int rc = mlvfs_amd_tensor_bayer_params(&fh[k], levels.data() + (size_t)k * TENSOR_LEVELS)) return rc;
+    MLV_HIP(hipMemcpyAsync(m.d_rgb, levels.data(), levels.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    for (int k0 = 0, k1; k0 < n; k0 = k1) {
+        const bool in_f = final_at[k0] == F + k0 * dstride;
+        for (k1 = k0 + 1; k1 < n && (final_at[k1] == F + k1 * dstride) == in_f; k1++) {}
+        const int rc = launch_tensor_bayer(final_at[k0], dstride, w, h, (const int32_t *)m.d_rgb + (size_t)k0 * TENSOR_LEVELS, sv.tensor->dtype,
+                                           sv.tensor->layout, tensor_affine(*sv.tensor), d_out + k0 * out_stride, out_stride, k1 - k0, s);
+        if (rc) return rc;
+    }
+    MLV_HIP(hipStreamSynchronize(s));
+    return MLVFS_AMD_OK;
+}
+
 // frames [f0, f0 + n) of the call, whose headers are fh[0 .. n), already in m.d_frames (frame k at k * dstride); sv: what the call asks
 // for, its sizes and flags beginning at this batch
 int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride, uint8_t *h_out, size_t out_stride, int *results, const Serve &sv)
@@ -300,7 +335,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
     }
     // the frame's header: the proxy's where one is served, with the max_size the full-size write has
     auto write_header = [&](int k, size_t max_size) {
-        if (sv.gain_q8) return;
+        if (sv.gain_q8 || sv.tensor) return;
         if (m.proxy == 2) (void)mlvfs_amd_dng_header_proxy(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data(), 2, 0);
         else (void)dng_get_header_data(&fh[k], h_out + k * out_stride, 0, max_size, o.fps, m.basename.data());
     };
@@ -419,6 +454,7 @@ int serve_batch(Mount &m, ThreadCtx *c, frame_headers *fh, int n, size_t dstride
         }
     }
     if (sv.gain_q8) return fetch_rgb(m, c, fh, n, dstride, final_at, h_out, out_stride, w, h, sv);
+    if (sv.tensor) return fetch_bayer_tensor(m, c, fh, n, dstride, final_at, h_out, out_stride, w, h, sv);
     if (sv.lossless) return fetch_lossless(m, c, fh, n, dstride, final_at, hdr_max, h_out, out_stride, sv, sw, sh);
     const size_t served = (size_t)sw * sh * 2;
     for (int k = 0; k < n; k++) MLV_HIP(hipMemcpyAsync(h_out + k * out_stride + hdr, final_at[k], served, hipMemcpyDeviceToHost, s));
@@ -617,6 +653,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         size = dng_get_header_size() + (size_t)pw * ph * 2;
     }
     const bool full = sv.in_full();
+    if (sv.tensor && m.proxy == 2) { set_error("mount: a handle that serves proxies does not serve tensors"); return MLVFS_AMD_ERR_ARG; }
     if (sv.gain_q8) {
         if (m.proxy == 2) { set_error("mount: a handle that serves proxies does not render"); return MLVFS_AMD_ERR_ARG; }
         bool unserved;
@@ -625,13 +662,38 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
         if (!route_geom(sv.route, w, h, &sv.pw, &sv.ph)) return route_refuse("mount", sv.route, w, h);
         sv.sampling = m.jpeg_sampling;
         size = mlvfs_amd_rgb_header_size() + sv.bpx() * sv.pw * sv.ph;
-        if (out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
+        if (!sv.tensor && out_stride < size) { set_error("mount: out_stride %zu smaller than a rendered file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
+    }
+    if (sv.tensor) {                                                   // the tensor's bytes in the place of a file's
+        const size_t es = tensor_elem(sv.tensor->dtype);
+        if (!sv.gain_q8) {
+            if (w < 2 || h < 2 || (uint64_t)w * (uint64_t)h >= (1u << 28)) { set_error("mount: a Bayer tensor takes frames of 2x2 up to 2^28 pixels, not %dx%d", w, h); return MLVFS_AMD_ERR_ARG; }
+            int32_t levels[TENSOR_LEVELS];
+            for (int k = 0; k < count; k++)
+                if (const int rl = mlvfs_amd_tensor_bayer_params(&fh[k], levels)) return rl;
+        }
+        size = sv.gain_q8 ? (size_t)3 * sv.pw * sv.ph * es : (size_t)4 * (w / 2) * (h / 2) * es;
+        if (out_stride < size || out_stride % es || (uintptr_t)h_out % es) {
+            set_error("mount: out_stride %zu smaller than a tensor (%zu), or the stride or the destination off the element's boundary", out_stride, size);
+            return MLVFS_AMD_ERR_ARG;
+        }
     }
     if (out_stride < size) { set_error("mount: out_stride %zu smaller than a .dng file (%zu)", out_stride, size); return MLVFS_AMD_ERR_ARG; }
     if (m.dark && !darkframe_fits(m.dark, w, h, bpp)) { set_error("mount: the dark frame does not have the geometry of frame %d (%dx%d at %d bits)", first, w, h, bpp); return MLVFS_AMD_ERR_ARG; }
     if (m.flat && !flatfield_fits(m.flat, w, h)) { set_error("mount: the flat field does not have the geometry of frame %d (%dx%d)", first, w, h); return MLVFS_AMD_ERR_ARG; }
     ThreadCtx *c = thread_ctx();
     if (!c) return MLVFS_AMD_ERR_HIP;
+    if (sv.tensor) {                                                   // device memory on the handle's device, its first byte and its last
+        const uint8_t *ends[2] = { (const uint8_t *)h_out, (const uint8_t *)h_out + (size_t)(count - 1) * out_stride + size - 1 };
+        for (const uint8_t *p : ends) {
+            hipPointerAttribute_t at{};
+            if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->dev->id) {
+                (void)hipGetLastError();
+                set_error("mount: d_out is not device memory on the handle's device (%d)", c->dev->id);
+                return MLVFS_AMD_ERR_ARG;
+            }
+        }
+    }
     const size_t img = (size_t)w * h * 2, dstride = up256(img);
     const size_t pn = o_pn_bytes(m.o, w, h, batch_frames);
     size_t scratch = std::max(pn, deflicker_batch_scratch_bytes(bpp > 15 ? 15 : bpp, batch_frames));
@@ -649,7 +711,7 @@ static int mount_serve(void *mount, int first, int count, void *h_out, size_t ou
     Calib cal;
     int rc = calib_on_device(m.dark, m.flat, c, w, h, bpp, 0, &cal);
     if (rc == MLVFS_AMD_OK) rc = m.ensure(c->dev->id, dstride * batch_frames, scratch);
-    if (rc == MLVFS_AMD_OK && sv.gain_q8) rc = m.ensure_rgb(batch_frames);
+    if (rc == MLVFS_AMD_OK && (sv.gain_q8 || sv.tensor)) rc = m.ensure_rgb(batch_frames);
     if (rc == MLVFS_AMD_OK && full) rc = m.d_full.reserve(full_bytes);
     for (int f0 = 0; rc == MLVFS_AMD_OK && f0 < count;) {
         int n = std::min(batch_frames, count - f0);
@@ -816,6 +878,54 @@ int mlvfs_amd_mount_rgb16_resampled(void *mount, int first, int count, void *h_o
 {
     return mount_render(mount, first, count, h_out, out_stride, batch_frames, io_threads, results, As::TIFF16,
                         rendered16(gain_q8, look, RenderRoute::RESAMPLED, ow, oh));
+}
+
+// what a tensor call's spec asks of the mount, beyond tensor_spec_ok: the kind, and for an RGB tensor the size kind, the size and the gain
+static bool tensor_mount_spec_ok(const mlvfs_amd_tensor_spec_t *spec)
+{
+    if (!spec) { set_error("mount: null argument"); return false; }
+    if (spec->kind != MLVFS_AMD_TENSOR_RGB && spec->kind != MLVFS_AMD_TENSOR_BAYER) { set_error("mount: a tensor kind of %d (0: RGB, 1: Bayer)", spec->kind); return false; }
+    const bool bayer = spec->kind == MLVFS_AMD_TENSOR_BAYER;
+    if (!tensor_spec_ok("mount", spec, bayer || spec->look16 ? 16 : 8, bayer ? 4 : 3)) return false;
+    if (bayer) return true;
+    if (spec->size < MLVFS_AMD_TENSOR_HALF || spec->size > MLVFS_AMD_TENSOR_RESAMPLED) { set_error("mount: a tensor size kind of %d (0 .. 3)", spec->size); return false; }
+    return gain_ok(spec->gain_q8) && size_ok({ (RenderRoute::Size)spec->size, false, spec->ow, spec->oh });
+}
+static_assert(RenderRoute::HALF == MLVFS_AMD_TENSOR_HALF && RenderRoute::FULL == MLVFS_AMD_TENSOR_FULL && RenderRoute::SCALED == MLVFS_AMD_TENSOR_SCALED &&
+              RenderRoute::RESAMPLED == MLVFS_AMD_TENSOR_RESAMPLED, "a spec's size kind is a route's");
+
+int mlvfs_amd_mount_tensor(void *mount, int first, int count, void *d_out, size_t out_stride, const mlvfs_amd_tensor_spec_t *spec, int batch_frames,
+                           int io_threads, int *results)
+{
+    if (!tensor_mount_spec_ok(spec)) return MLVFS_AMD_ERR_ARG;
+    Serve sv;
+    if (spec->kind == MLVFS_AMD_TENSOR_RGB) sv = spec->look16 ? rendered16(spec->gain_q8, spec->look16, (RenderRoute::Size)spec->size, spec->ow, spec->oh)
+                                                              : rendered(spec->gain_q8, (RenderRoute::Size)spec->size, spec->ow, spec->oh);
+    sv.tensor = spec;
+    return mount_serve(mount, first, count, d_out, out_stride, batch_frames, io_threads, results, sv);
+}
+
+size_t mlvfs_amd_mount_tensor_bytes(const void *mount, int index, const mlvfs_amd_tensor_spec_t *spec)
+{
+    if (!mount) { set_error("mount: null argument"); return 0; }
+    if (!tensor_mount_spec_ok(spec)) return 0;
+    Mount &m = *(Mount *)mount;
+    frame_headers fh;
+    if (index < 0 || !mlvfs_amd_mlv_frame_headers(m.reader, index, &fh)) { set_error("mount: frame %d has no usable headers", index); return 0; }
+    const int w = fh.rawi_hdr.xRes, h = fh.rawi_hdr.yRes;
+    const size_t es = tensor_elem(spec->dtype);
+    if (spec->kind == MLVFS_AMD_TENSOR_BAYER) {
+        if (w < 2 || h < 2 || (uint64_t)w * (uint64_t)h >= (1u << 28)) { set_error("mount: a Bayer tensor takes frames of 2x2 up to 2^28 pixels, not %dx%d", w, h); return 0; }
+        return (size_t)4 * (w / 2) * (h / 2) * es;
+    }
+    RenderRoute route;
+    {
+        std::lock_guard<std::mutex> lk(m.mu);
+        route = mount_route((RenderRoute::Size)spec->size, spec->ow, spec->oh, m.demosaic, m.resample_demosaic);
+    }
+    int pw, ph;
+    if (!route_geom(route, w, h, &pw, &ph)) { (void)route_refuse("mount", route, w, h); return 0; }
+    return (size_t)3 * pw * ph * es;
 }
 
 // the size of a rendered 8-bit TIFF file of frame `index`: the handle's route for that size kind and its geometry.  A rendering's size

@@ -33,6 +33,12 @@ class MountOpts(C.Structure):
                 ("deflicker", C.c_int32), ("fix_pattern_noise", C.c_int32), ("rand_mode", C.c_int32), ("fps", C.c_double)]
 
 
+class TensorSpec(C.Structure):
+    """mlvfs_amd_tensor_spec_t (include/mlvfs_amd.h; mlvfs_amd/tensor.py has the constants)"""
+    _fields_ = [("kind", C.c_int32), ("size", C.c_int32), ("ow", C.c_int32), ("oh", C.c_int32), ("gain_q8", C.c_int32), ("dtype", C.c_int32),
+                ("layout", C.c_int32), ("reserved", C.c_int32), ("look16", C.c_void_p), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
 # every symbol include/mlvfs_amd.h declares (tests/test_cabi.py checks the export table against the header)
 DROPIN_SYMBOLS = [
     "dng_get_image_data", "dng_get_header_data", "dng_get_header_size", "dng_get_image_size", "dng_get_size",
@@ -90,6 +96,7 @@ DEVICE_SYMBOLS = [
     "mlvfs_amd_test_amz_resample_plan",
     "mlvfs_amd_jpeg_header_sampled", "mlvfs_amd_jpeg_scratch_bytes_sampled", "mlvfs_amd_jpeg_mcus", "mlvfs_amd_jpeg_encode_sampled_dev",
     "mlvfs_amd_mount_set_jpeg_sampling",
+    "mlvfs_amd_tensor_rgb_dev", "mlvfs_amd_tensor_bayer_params", "mlvfs_amd_tensor_bayer_dev", "mlvfs_amd_mount_tensor", "mlvfs_amd_mount_tensor_bytes",
 ]
 
 
@@ -362,6 +369,12 @@ def load() -> C.CDLL:
     sig("mlvfs_amd_render_resampled_amaze_deep_dev", i, [vp, sz, i, i, vp, i, i, vp, sz, i, vp, vp])
     sig("mlvfs_amd_mount_set_resample_demosaic", i, [vp, i])
     sig("mlvfs_amd_test_amz_resample_plan", i, [i, i, i, i, i, vp])
+    tsp = C.POINTER(TensorSpec)
+    sig("mlvfs_amd_tensor_rgb_dev", i, [vp, sz, i, i, i, tsp, vp, sz, i, vp])
+    sig("mlvfs_amd_tensor_bayer_params", i, [fhp, vp])
+    sig("mlvfs_amd_tensor_bayer_dev", i, [vp, sz, i, i, vp, tsp, vp, sz, i, vp])
+    sig("mlvfs_amd_mount_tensor", i, [vp, i, i, vp, sz, tsp, i, i, vp])
+    sig("mlvfs_amd_mount_tensor_bytes", sz, [vp, i, tsp])
     _lib = L
     return L
 

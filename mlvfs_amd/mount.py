@@ -27,6 +27,10 @@
     m.set_resample_demosaic("amaze") makes the resample=True calls demosaic with AMaZE (include/mlvfs_amd.h, "resampled rendered frames
     demosaiced by AMaZE"; mlvfs_amd/amaze_resample.py is the definition).
 
+    t = m.tensor(0, 16, dtype=torch.float16, layout="NCHW") leaves the same renderings on the GPU as one (16, 3, h, w) torch tensor, and
+    m.tensor(0, 16, kind="bayer") the frames themselves as four planes, black-subtracted and scaled by their own levels: nothing crosses
+    the link (include/mlvfs_amd.h, "a clip's frames as device-resident tensors"; mlvfs_amd/tensor.py is the definition in numpy).
+
 Successive calls on one Mount serve frames in call order, like one fresh MLVFS process serving .dng reads in that order.
 """
 from __future__ import annotations
@@ -35,7 +39,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import lib
+from . import abi, lib
 from .pipeline import MlvfsOptions
 
 
@@ -251,6 +255,88 @@ class Mount:
         lib.check(call(self.h, first, count, lib.ptr(out), stride, gain_q8, quality, *wh, lib.ptr(sizes), lib.ptr(flags), batch, io_threads,
                        lib.ptr(res)), name)
         return [out[k, :int(sizes[k])].tobytes() for k in range(count)], [int(f) for f in flags[:count]]
+
+    def _tensor_spec(self, kind, dtype, layout, mean, std, gain, full, size, resample, look16):
+        """-> (lib.TensorSpec, C) of a tensor call's arguments; dtype: a torch dtype or its name"""
+        from . import tensor as T
+        if kind not in ("rgb", "bayer"):
+            raise ValueError(f'kind {kind!r} ("rgb" or "bayer")')
+        name = str(dtype).replace("torch.", "")
+        if name not in T.DTYPE_NAMES or layout not in T.LAYOUTS:
+            raise ValueError(f"dtype {dtype} (float32, float16, bfloat16, uint8, uint16) or layout {layout!r} (NCHW, NHWC)")
+        channels = 3 if kind == "rgb" else 4
+        scale, bias = T.normalisation(mean, std, channels)
+        spec = lib.TensorSpec(kind=T.RGB if kind == "rgb" else T.BAYER, dtype=T.DTYPE_NAMES[name], layout=T.LAYOUTS[layout])
+        spec.scale[:], spec.bias[:] = scale.tolist(), bias.tolist()
+        if kind == "rgb":
+            wh = self._size_arg(size, full, resample)
+            spec.size = T.RESAMPLED if resample else T.SCALED if wh is not None else T.FULL if full else T.HALF
+            spec.ow, spec.oh = wh or (0, 0)
+            spec.gain_q8 = int(round(256 * gain))
+            if not 1 <= spec.gain_q8 <= 65535:
+                raise ValueError(f"gain {gain} outside 1 / 256 .. 65535 / 256")
+            spec.look16 = look16.h if look16 is not None else None
+        return spec, channels
+
+    def tensor_bytes(self, index: int, spec) -> int:
+        """bytes of frame `index` as a tensor of that spec (a lib.TensorSpec)"""
+        size = int(self.L.mlvfs_amd_mount_tensor_bytes(self.h, index, C.byref(spec)))
+        if not size:
+            raise lib.MlvfsAmdError(self.L.mlvfs_amd_last_error().decode())
+        return size
+
+    def tensor(self, first: int, count: int, kind: str = "rgb", dtype=None, layout: str = "NCHW", mean=None, std=None, gain: float = 1.0,
+               full: bool = False, size=None, resample: bool = False, look16=None, out=None, batch: int = 8, io_threads: int = 0,
+               results: np.ndarray | None = None):
+        """Frames first .. first + count - 1 as one torch tensor on the handle's device, written there by the GPU: nothing crosses the
+        link (include/mlvfs_amd.h, "a clip's frames as device-resident tensors"; mlvfs_amd/tensor.py is the definition in numpy).
+        kind="rgb": the rendering rgb() would have served with the same gain, full, size, resample and look16 (and the handle's look),
+        shape (count, 3, h, w) for layout "NCHW" or (count, h, w, 3) for "NHWC".  kind="bayer": the frame dng() would have served as four
+        planes R, G1, G2, B of (H // 2, W // 2), px - black over white - black with that frame's own header levels, clamped at neither end.
+        dtype: torch.float16 (the default), float32, bfloat16 -- sample / 255 (or / 65535 with look16), then (x - mean) / std per channel --
+        or the integer samples themselves: torch.uint8 (8-bit rgb), torch.uint16 (rgb with look16, bayer: the raw pixels).
+        out: a tensor of that shape and dtype on the device to write into; its frames must be contiguous and may lie any stride apart
+        (out.stride(0)); anything else is refused.
+        The call synchronises torch's current stream before it starts, so that a consumer still reading `out` is not overwritten, and
+        the library's stream before it returns: the tensor is complete when the call returns.
+        Not on a handle that serves proxies."""
+        import torch
+        from . import tensor as T
+        dtype = torch.float16 if dtype is None else dtype
+        spec, channels = self._tensor_spec(kind, dtype, layout, mean, std, gain, full, size, resample, look16)
+        es = T.ELEM[spec.dtype]
+        if count < 1:
+            raise ValueError("a tensor call takes at least one frame")
+        nbytes = self.tensor_bytes(first, spec)
+        fh = abi.FrameHeaders()
+        handle = getattr(self._reader, "h", self._reader)
+        if not self.L.mlvfs_amd_mlv_frame_headers(handle, first, C.byref(fh)):
+            raise lib.MlvfsAmdError(f"frame {first} has no usable headers")
+        if kind == "bayer":
+            h, w = fh.rawi_hdr.yRes // 2, fh.rawi_hdr.xRes // 2
+        else:
+            w = spec.ow if spec.size in (T.SCALED, T.RESAMPLED) else fh.rawi_hdr.xRes // (2 if spec.size == T.HALF else 1)
+            h = nbytes // (es * 3 * w)
+        assert channels * h * w * es == nbytes
+        shape = (count,) + T.shape_of(channels, h, w, spec.layout)
+        device = torch.device("cuda", max(self.L.mlvfs_amd_thread_device(), 0))
+        tdtype = getattr(torch, str(dtype).replace("torch.", ""))
+        if out is None:
+            out = torch.empty(shape, dtype=tdtype, device=device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == tdtype and tuple(out.shape) == shape and out[0].is_contiguous()
+                  and (count == 1 or out.stride(0) >= channels * h * w)):
+            raise ValueError(f"out must be a {tdtype} tensor of shape {shape} on the GPU whose frames are contiguous")
+        res = self._results(results, count)
+        torch.cuda.current_stream(out.device).synchronize()
+        stride = (out.stride(0) if count > 1 else channels * h * w) * es
+        lib.check(self.L.mlvfs_amd_mount_tensor(self.h, first, count, C.c_void_p(out.data_ptr()), stride, C.byref(spec), batch, io_threads,
+                                                lib.ptr(res)), "mount_tensor")
+        return out
+
+    def tensors(self, first: int, count: int, batch: int = 8, **spec):
+        """tensor() batch by batch: a generator of tensors of up to `batch` frames each, in serve order; **spec: tensor()'s arguments"""
+        for f0 in range(first, first + count, batch):
+            yield self.tensor(f0, min(batch, first + count - f0), batch=batch, **spec)
 
     def close(self) -> None:
         if self.h:
