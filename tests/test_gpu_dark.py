@@ -16,8 +16,9 @@ from mlvfs_amd.pipeline import MlvfsOptions
 import dark_cases as dc
 from dark_cases import NAME
 from lossless_cases import jpeg_view
+from mount_harness import mount_opts
 from test_gpu_mlv_transcode import PAD, device_buffer, lj92_payload_check, plain_payload_check, reference_stream, split
-from test_gpu_mount import ORDER, compare, mount_opts
+from test_gpu_mount import ORDER, compare
 from test_gpu_ref_host import need_hosts, run_host, vpath
 from test_mlv_transcode import check_container
 

@@ -20,9 +20,10 @@ import dark_cases as dc
 import flat_cases as fc
 from flat_cases import NAME
 from lossless_cases import jpeg_view
+from mount_harness import mount_opts
 from test_gpu_bits import check_output, files_of
 from test_gpu_mlv_transcode import PAD, device_buffer, lj92_payload_check, plain_payload_check, reference_stream, split
-from test_gpu_mount import ORDER, compare, mount_opts
+from test_gpu_mount import ORDER, compare
 from test_gpu_ref_host import need_hosts, run_host, vpath
 from test_mlv_transcode import blocks_of, check_container
 

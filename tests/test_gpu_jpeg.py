@@ -3,21 +3,19 @@ mlvfs_amd_jpeg_encode_dev against the numpy definition of mlvfs_amd/jpeg.py on e
 mlvfs_amd_mount_jpeg against mlvfs_amd_mount_rgb on a second handle: each file is the definition's header and stream of the pixels the
 TIFF of the same frame holds, results[] are the same, and PIL opens every file.  All comparisons are for equality."""
 import ctypes as C
-import io
 import os
 
 import numpy as np
 import pytest
 
-from mlvfs_amd import jpeg, lib, mlvfile, render, synth
+from mlvfs_amd import jpeg, lib, render
 
 import jpeg_cases as jc
-from test_gpu_mlv_transcode import PAD, device_buffer, split
-from test_gpu_render import NAME, fresh, make_clip, open_mount
+from mount_harness import HDR as TIFF, check_jpegs, fresh, load_tool, make_clip, open_mount, run_tool, serve
+from test_gpu_mlv_transcode import PAD, device_buffer
 
 pytestmark = pytest.mark.gpu
 HDR = jpeg.HEADER_BYTES
-TIFF = render.HEADER_BYTES
 
 
 # ------------------------------------------------------------------ mlvfs_amd_jpeg_encode_dev
@@ -146,37 +144,11 @@ OPTION_SETS = [("none", dict()), ("cs5+badpix+stripes", dict(cs=5, badpix=1, str
 ORDER = ((2, 3, 1.0, 90), (0, 2, 2.5, 50))          # first, count, gain, quality: two calls at two qualities
 
 
-def serve(gpu, path, opts, kind, order=ORDER, batch=2):
-    """frames 2..4, then 0..1, in batches of 2, through one fresh handle -> (files, flags, results, qualities)"""
-    fresh(gpu)
-    r, m = open_mount(path, opts)
-    files, flags, results, quals = [], [], [], []
-    with r, m:
-        for first, count, gain, q in order:
-            res = np.full(count, -1, np.int32)
-            if kind == "jpeg":
-                a, fl = m.jpeg(first, count, gain=gain, quality=q, batch=batch, results=res)
-            else:
-                a, fl = [f.tobytes() for f in m.rgb(first, count, gain=gain, batch=batch, results=res)], [None] * count
-            files += a
-            flags += fl
-            results += list(res)
-            quals += [q] * count
-    return files, flags, results, quals
-
-
-def check_jpeg(tiffs, jpgs, flags, quals, w, h, label):
-    from PIL import Image
-    pw, ph = render.geom(w, h)
-    assert len(tiffs) == len(jpgs)
-    for k, (t, j, fl, q) in enumerate(zip(tiffs, jpgs, flags, quals)):
-        pixels = render.split_file(t, pw, ph)
-        want = jpeg.header(pw, ph, q) + jpeg.encode(pixels, q)
-        assert fl == 0 and len(want) < len(t), (label, k)
-        assert j == want, f"{label} frame {k}: not the definition's file of the pixels the TIFF holds"
-        with Image.open(io.BytesIO(j)) as im:
-            assert im.format == "JPEG" and im.mode == "RGB" and im.size == (pw, ph)
-            im.load()
+def check_jpeg(tiffs, jpgs, flags, order, w, h, label):
+    """every JPEG file is the definition's of the pixels the TIFF holds, at its call's quality, and none is the TIFF"""
+    size = render.geom(w, h)
+    check_jpegs([render.split_file(t, *size) for t in tiffs], jpgs, flags, size, label, [q for _, count, _, q in order for _ in range(count)])
+    assert flags == [0] * len(jpgs) and all(len(j) < len(t) for j, t in zip(jpgs, tiffs)), label
 
 
 CASES = [(p, w, h, name, opts) for p in ("plain", "lj92") for w, h in ((64, 48), (418, 266)) for name, opts in OPTION_SETS]
@@ -185,10 +157,10 @@ CASES = [(p, w, h, name, opts) for p in ("plain", "lj92") for w, h in ((64, 48),
 @pytest.mark.parametrize("payload,w,h,name,opts", CASES, ids=[f"{p}:{w}x{h}:{name}" for p, w, h, name, _ in CASES])
 def test_mount_jpeg_is_the_rendering_encoded(gpu, tmp_path, payload, w, h, name, opts):
     path = make_clip(tmp_path, payload, w, h)
-    tiffs, _, res_rgb, _ = serve(gpu, path, opts, "rgb")
-    jpgs, flags, res_jpg, quals = serve(gpu, path, opts, "jpeg")
+    tiffs, _, res_rgb, _ = serve(gpu, path, opts, "rgb", order=ORDER)
+    jpgs, flags, res_jpg, _ = serve(gpu, path, opts, "jpeg", order=ORDER)
     assert res_jpg == res_rgb
-    check_jpeg(tiffs, jpgs, flags, quals, w, h, f"{payload}:{w}x{h}:{name}")
+    check_jpeg(tiffs, jpgs, flags, ORDER, w, h, f"{payload}:{w}x{h}:{name}")
     assert len(set(jpgs)) == len(jpgs), "two frames encoded alike"
 
 
@@ -206,8 +178,8 @@ def test_mount_jpeg_interleaves_with_rgb_and_dng(gpu, tmp_path):
     opts = dict(cs=5, badpix=1, stripes=1)
     order = ((0, 8, 1.0, 75),)
     want_rgb, _, _, _ = serve(gpu, path, opts, "rgb", order=order, batch=4)
-    want_jpg, flags, _, quals = serve(gpu, path, opts, "jpeg", order=order, batch=4)
-    check_jpeg(want_rgb, want_jpg, flags, quals, 416, 264, "one kind")
+    want_jpg, flags, _, _ = serve(gpu, path, opts, "jpeg", order=order, batch=4)
+    check_jpeg(want_rgb, want_jpg, flags, order, 416, 264, "one kind")
     fresh(gpu)
     r, m = open_mount(path, opts)
     with r, m:
@@ -257,22 +229,12 @@ def test_mount_jpeg_refusals(gpu, tmp_path):
 
 def test_the_render_tool_writes_jpeg_files(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py --jpeg (its main(), in this process): the files are mlvfs_amd_mount_jpeg's"""
-    import importlib.util
-    import sys
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     path = make_clip(tmp_path, "plain", 64, 48, n=3)
     opts = dict(cs=5, stripes=1)
     want, flags, _, _ = serve(gpu, path, opts, "jpeg", order=((0, 3, 1.5, 80),))
-
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
     out = tmp_path / "out"
     assert run(out, ["--jpeg", "80"]) == 0
     names = sorted(os.listdir(out))

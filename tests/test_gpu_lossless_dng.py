@@ -6,13 +6,12 @@ CPU-side proof is tests/test_lossless_dng.py); the one frame that must fall back
 import numpy as np
 import pytest
 
-from mlvfs_amd import lj92, mlvfile, synth
+from mlvfs_amd import lj92, mlvfile
 from mlvfs_amd.mount import Mount
-from mlvfs_amd.pipeline import MlvfsOptions
 
 from lossless_cases import (BIG_H, BIG_W, H, W, assert_lossless_header, big_frames, fallback_frames, jpeg_view, long_stream_frames, max_class,
                             mount_stream_room)
-from test_gpu_mount import dual_clip, mount_opts
+from mount_harness import NAME, dual_clip, fresh, mount_opts, open_mount, payloads
 from test_gpu_ref_host import make_clip
 from test_lj92_encode import CASES as SMALL_CASES, material
 
@@ -103,17 +102,6 @@ def test_batch_encoder_takes_host_arrays(gpu, reference):
 
 
 # ------------------------------------------------------------------ the mount
-def _fresh(gpu):
-    gpu.free_focus_pixel_maps()                     # a fresh process: no bad-pixel map yet, no dual-ISO table caches
-    gpu.mlvfs_amd_dualiso_reset()
-
-
-def _open(path, opts):
-    opt, defl, fps = mount_opts(opts)
-    r = mlvfile.MlvReader(path)
-    return r, Mount(r, opt, deflicker=defl, fps=fps, basename="/M07-1234.MLV")
-
-
 def _check_files(reference, plain, files, flags, w, h, label=""):
     """every lossless file against the uncompressed one of the same frame; returns the compressed bytes"""
     total = 0
@@ -146,13 +134,13 @@ MOUNT_CASES = [
 @pytest.mark.parametrize("kind,opts", MOUNT_CASES, ids=[k + ":" + ",".join(f"{a}={b}" for a, b in o.items()) for k, o in MOUNT_CASES])
 def test_mount_lossless_against_uncompressed(gpu, reference, tmp_path, kind, opts):
     d = dual_clip(tmp_path, kind[5:], reference) if kind.startswith("dual:") else make_clip(tmp_path, kind, reference=reference)[0]
-    path = str(d / "M07-1234.MLV")
-    _fresh(gpu)
-    r, m = _open(path, opts)
+    path = str(d / NAME)
+    fresh(gpu)
+    r, m = open_mount(path, opts)
     with r, m:
         plain = list(m.dng(2, 3, batch=2)) + list(m.dng(0, 2, batch=2))
-    _fresh(gpu)
-    r, m = _open(path, opts)
+    fresh(gpu)
+    r, m = open_mount(path, opts)
     with r, m:
         res = np.full(3, -1, np.int32)
         a, fa = m.dng_lossless(2, 3, batch=2, results=res)
@@ -163,14 +151,14 @@ def test_mount_lossless_against_uncompressed(gpu, reference, tmp_path, kind, opt
 
 def test_mount_lossless_and_plain_calls_interleave_in_serve_order(gpu, tmp_path):
     d, _ = make_clip(tmp_path, "plain", n=8)
-    path = str(d / "M07-1234.MLV")
+    path = str(d / NAME)
     opts = dict(cs=5, badpix=1, stripes=1)
-    _fresh(gpu)
-    r, m = _open(path, opts)
+    fresh(gpu)
+    r, m = open_mount(path, opts)
     with r, m:
         want = m.dng(0, 8, batch=4)
-    _fresh(gpu)
-    r, m = _open(path, opts)
+    fresh(gpu)
+    r, m = open_mount(path, opts)
     with r, m:
         files, flags = m.dng_lossless(0, 4, batch=4)
         got = m.dng(4, 4, batch=4)
@@ -182,15 +170,15 @@ def test_mount_serves_a_class_16_frame_uncompressed(gpu, reference, tmp_path):
     d = tmp_path / "card"
     d.mkdir()
     frames = fallback_frames(n=5, at=2)
-    pl = [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames]
-    mlvfile.write_clip(str(d / "M07-1234.MLV"), pl, W, H, chunks=2, frame_space=32, shuffle=True)
-    path = str(d / "M07-1234.MLV")
-    _fresh(gpu)
-    r, m = _open(path, {})
+    pl = payloads(frames, "plain")[0]
+    mlvfile.write_clip(str(d / NAME), pl, W, H, chunks=2, frame_space=32, shuffle=True)
+    path = str(d / NAME)
+    fresh(gpu)
+    r, m = open_mount(path, {})
     with r, m:
         plain = m.dng(0, 5, batch=3)
-    _fresh(gpu)
-    r, m = _open(path, {})
+    fresh(gpu)
+    r, m = open_mount(path, {})
     with r, m:
         files, flags = m.dng_lossless(0, 5, batch=3)
     assert flags[2] & 1, "the frame whose first pixel is 0 must be served uncompressed"
@@ -212,15 +200,15 @@ def test_mount_serves_a_frame_whose_stream_is_longer_than_its_pixels_uncompresse
     cap, stride = mount_stream_room(W, H)
     long = oracle.lj92_encode(v, v.shape[1], v.shape[0], 16)
     assert max_class(long) < 16 and len(long) > stride == cap
-    pl = [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames]
-    mlvfile.write_clip(str(d / "M07-1234.MLV"), pl, W, H, chunks=2, frame_space=32, shuffle=True)
-    path = str(d / "M07-1234.MLV")
-    _fresh(gpu)
-    r, m = _open(path, {})
+    pl = payloads(frames, "plain")[0]
+    mlvfile.write_clip(str(d / NAME), pl, W, H, chunks=2, frame_space=32, shuffle=True)
+    path = str(d / NAME)
+    fresh(gpu)
+    r, m = open_mount(path, {})
     with r, m:
         plain = m.dng(0, 5, batch=3)
-    _fresh(gpu)
-    r, m = _open(path, {})
+    fresh(gpu)
+    r, m = open_mount(path, {})
     with r, m:
         files, flags = m.dng_lossless(0, 5, batch=3)
     assert flags[2] & 1, "a stream longer than the pixels must be served uncompressed"
@@ -232,14 +220,14 @@ def test_mount_serves_a_frame_whose_stream_is_longer_than_its_pixels_uncompresse
 
 def test_mount_lossless_full_size_batch(gpu, reference, tmp_path):
     frames = big_frames()
-    pl = [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames]
+    pl = payloads(frames, "plain")[0]
     path = str(tmp_path / "B.MLV")
     mlvfile.write_clip(path, pl, BIG_W, BIG_H)
     opts = dict(cs=5, stripes=1)
-    _fresh(gpu)
+    fresh(gpu)
     with mlvfile.MlvReader(path) as r, Mount(r, mount_opts(opts)[0], basename="/B.MLV") as m:
         plain = m.dng(0, 8, batch=8)
-    _fresh(gpu)
+    fresh(gpu)
     with mlvfile.MlvReader(path) as r, Mount(r, mount_opts(opts)[0], basename="/B.MLV") as m:
         files, flags = m.dng_lossless(0, 8, batch=8)
     total = _check_files(reference, list(plain), files, flags, BIG_W, BIG_H, "3584x1320")

@@ -3,7 +3,6 @@ of process_frame (mlvfs/main.c:908-1005) over batches of a clip's frames and han
 import ctypes as C
 import json
 import os
-import struct
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ from mlvfs_amd import lib, mlvfile, synth
 from mlvfs_amd.mount import Mount
 from mlvfs_amd.pipeline import MlvfsOptions
 
+from mount_harness import H, NAME, W, dual_clip, fresh, open_mount
 from test_gpu_ref_host import OPTION_SETS, make_clip, need_hosts, run_host, vpath
 
 pytestmark = pytest.mark.gpu
@@ -164,43 +164,14 @@ def test_batched_preview_equals_hdr_convert_data_frame_by_frame(gpu, oracle):
 
 
 # ------------------------------------------------------------------ the mount against the reference's process_frame text
-W, H = 416, 264
 ORDER = [2, 3, 4, 0, 1]
-
-
-def dual_clip(tmp_path, payload, reference=None, normal_at=(), n=5):
-    """a dual-ISO clip of any payload kind (make_clip builds them plain only); frames in normal_at are not dual ISO"""
-    d = tmp_path / "card"
-    d.mkdir()
-    frames = [synth.normal_frame(W, H, seed=9, frame=k, hot=60, cold=60) if k in normal_at else synth.dual_iso_frame(W, H, frame=k)
-              for k in range(n)]
-    vc = 1
-    if payload == "lj92":
-        from oracle import lj92_testenc as enc
-        from test_lj92 import quadrants
-        pl, vc = [struct.pack("<I", W * H * 2) + enc.encode(quadrants(f), 6, 14) for f in frames], 1 | 0x100
-    elif payload == "lzma":
-        pl, vc = [reference.lzma_payload(synth.pack_bits(f).tobytes()) for f in frames], 1 | 0x80
-    else:
-        pl = [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames]
-    mlvfile.write_clip(str(d / "M07-1234.MLV"), pl, W, H, chunks=2, frame_space=32, shuffle=True, video_class=vc)
-    return d
-
-
-def mount_opts(opts):
-    o = MlvfsOptions(chroma_smooth=opts.get("cs", 0), fix_bad_pixels=opts.get("badpix", 0), fix_stripes=opts.get("stripes", 0),
-                     dual_iso=opts.get("dual_iso", 0), fix_pattern_noise=opts.get("pnoise", 0),
-                     hdr_interpolation_method=opts.get("hdr_interp", 0), hdr_no_fullres=opts.get("no_fullres", 0),
-                     hdr_no_alias_map=opts.get("no_alias", 0))
-    return o, opts.get("deflicker", 0), opts.get("fps1000", 0) / 1000.0
 
 
 def serve(gpu, d, opts):
     """frames 2..4, then 0..1, in batches of 2, through one fresh mount; [(data, header)] in the order 2, 3, 4, 0, 1"""
-    gpu.free_focus_pixel_maps()                     # a fresh process: no bad-pixel map yet, no dual-ISO table caches
-    gpu.mlvfs_amd_dualiso_reset()
-    opt, defl, fps = mount_opts(opts)
-    with mlvfile.MlvReader(str(d / "M07-1234.MLV")) as r, Mount(r, opt, deflicker=defl, fps=fps, basename="/M07-1234.MLV") as m:
+    fresh(gpu)
+    r, m = open_mount(str(d / NAME), opts)
+    with r, m:
         files = np.concatenate([m.dng(2, 3, batch=2), m.dng(0, 2, batch=2)])
     return [(f[65536:].tobytes(), f[:65536].tobytes()) for f in files]
 

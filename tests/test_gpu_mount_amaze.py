@@ -3,87 +3,52 @@ mlvfs_amd_mount_set_demosaic(1) the three full-size calls serve the definition o
 to the pixels of the .dng file of the same clip and options, byte for byte -- TIFF, JPEG and 16-bit TIFF, with the handle's look too --
 and PIL opens every file at W x H; the linear filter afterwards serves the linear files; the calls interleave with dng() and the
 half-size calls; a clip whose frames go through the dual-ISO conversion's AMaZE first; the refusals.  The helpers are those of
-tests/test_gpu_mount_full.py and tests/test_gpu_render.py."""
-import io
+tests/mount_harness.py."""
+import os
 
 import numpy as np
 import pytest
 
-from mlvfs_amd import amaze_render, jpeg, lib, look, mlvfile, render, synth
+from mlvfs_amd import jpeg, lib, look, mlvfile, render, synth
 
 import deep_cases as dc
 import look_cases as lc
-from test_gpu_mount_full import QUALITY, check_jpegs, check_tiffs, serve_full
-from test_gpu_render import GAIN_A, GAIN_B, NAME, fresh, make_clip, open_mount, serve
+from mount_harness import (GAIN_A, GAIN_B, HDR, NAME, ORDER, QUALITY, check_jpegs, check_tiffs, fresh, load_tool, make_clip, open_mount, payloads,
+                           renderings, run_tool, serve)
 
 pytestmark = pytest.mark.gpu
-HDR = render.HEADER_BYTES
 OPTS = dict(cs=5, badpix=1, stripes=1)
 SIZES = [(64, 48), (148, 40)]            # a width the fast forms take, and one they do not
-ORDER = ((2, 3, GAIN_A), (0, 2, GAIN_B))
 LOOK, LOOK16 = lc.look_of("random17"), dc.look_of("random3")
+FULL = dict(full=True)
 
 
-def serve_amaze(gpu, path, opts, kind, order=ORDER, batch=2, lk=None, lk16=None):
-    """the clip through one fresh handle with AMaZE set -> (files, flags, results, gains); kind: rgb, jpeg or rgb16"""
-    fresh(gpu)
-    r, m = open_mount(path, opts)
-    files, flags, results, gains = [], [], [], []
-    with r, m:
+def amaze(lk=None):
+    """the setup of a handle that serves AMaZE at full size, with a look where one is given"""
+    def setup(m):
         m.set_demosaic("amaze")
         if lk is not None:
             m.set_look(lk)
-        for first, count, gain in order:
-            res = np.full(count, -1, np.int32)
-            if kind == "jpeg":
-                a, fl = m.jpeg(first, count, gain=gain, quality=QUALITY, batch=batch, results=res, full=True)
-            else:
-                a = m.rgb(first, count, gain=gain, batch=batch, results=res, full=True, look16=lk16 if kind == "rgb16" else None)
-                assert a.shape == (count, m.rgb_size(full=True, bits=16 if kind == "rgb16" else 8))
-                a, fl = [f.tobytes() for f in a], [None] * count
-            files += a
-            flags += fl
-            results += list(res)
-            gains += [gain] * count
-    return files, flags, results, gains
-
-
-def renderings(oracle, full, gains, w, h, **tone):
-    """the definition applied to every full-size .dng file"""
-    out = []
-    for f, gain in zip(full, gains):
-        assert len(f) == 65536 + w * h * 2
-        p = render.params_from_header(f[:65536], int(round(256 * gain)))
-        out.append(amaze_render.render(np.frombuffer(f, "<u2", offset=65536).reshape(h, w), p, oracle.amaze_demosaic, **tone))
-    return out
-
-
-def check_tiffs16(want, files, w, h, label):
-    from PIL import Image
-    assert len(want) == len(files)
-    for k, (px, t) in enumerate(zip(want, files)):
-        assert t == render.tiff_header(w, h, 16) + np.ascontiguousarray(px, "<u2").tobytes(), f"{label} frame {k}: not the definition's 16-bit file"
-        with Image.open(io.BytesIO(t)) as im:
-            assert im.size == (w, h), (label, k)
+    return setup
 
 
 @pytest.mark.parametrize("w,h", SIZES, ids=lambda v: str(v))
 def test_mount_amaze_serves_the_definitions_files(gpu, oracle, tmp_path, w, h):
     label = f"amaze {w}x{h}"
     path = make_clip(tmp_path, "plain", w, h)
-    full, res_full, _ = serve(gpu, path, OPTS, "dng")
-    tiffs, _, res_rgb, gains = serve_amaze(gpu, path, OPTS, "rgb")
-    jpgs, flags, res_jpg, _ = serve_amaze(gpu, path, OPTS, "jpeg")
+    full, _, res_full, _ = serve(gpu, path, OPTS, "dng")
+    tiffs, _, res_rgb, gains = serve(gpu, path, OPTS, "rgb", FULL, setup=amaze())
+    jpgs, flags, res_jpg, _ = serve(gpu, path, OPTS, "jpeg", FULL, setup=amaze())
     with look.Look16(*LOOK16) as lk16:
-        deep, _, res_deep, _ = serve_amaze(gpu, path, OPTS, "rgb16", lk16=lk16)
+        deep, _, res_deep, _ = serve(gpu, path, OPTS, "rgb", dict(FULL, look16=lk16), setup=amaze())
     assert res_rgb == res_full == res_jpg == res_deep
-    want = renderings(oracle, full, gains, w, h)
-    check_tiffs(want, tiffs, w, h, label)
-    check_jpegs(want, jpgs, flags, w, h, label)
-    check_tiffs16(renderings(oracle, full, gains, w, h, look16=LOOK16), deep, w, h, label)
+    want = renderings(full, gains, w, h, "full+amaze", amaze=oracle.amaze_demosaic)
+    check_tiffs(want, tiffs, (w, h), label)
+    check_jpegs(want, jpgs, flags, (w, h), label, QUALITY)
+    check_tiffs(renderings(full, gains, w, h, "full+amaze", amaze=oracle.amaze_demosaic, look16=LOOK16), deep, (w, h), label, bits=16)
     assert len(set(tiffs)) == len(tiffs)
     # another rendering than the linear filter's, which the same handle serves again once it is set back
-    linear, _, _, _ = serve_full(gpu, path, OPTS, "rgb", order=ORDER)
+    linear, _, _, _ = serve(gpu, path, OPTS, "rgb", FULL, order=ORDER)
     assert all(a != b for a, b in zip(linear, tiffs))
     fresh(gpu)
     r, m = open_mount(path, OPTS)
@@ -100,14 +65,14 @@ def test_mount_amaze_serves_the_definitions_files(gpu, oracle, tmp_path, w, h):
 def test_mount_amaze_with_a_look(gpu, oracle, tmp_path):
     w, h = SIZES[0]
     path = make_clip(tmp_path, "plain", w, h)
-    full, _, _ = serve(gpu, path, OPTS, "dng")
+    full, _, _, _ = serve(gpu, path, OPTS, "dng")
     with look.Look(*LOOK) as lk:
-        tiffs, _, _, gains = serve_amaze(gpu, path, OPTS, "rgb", lk=lk)
-        jpgs, flags, _, _ = serve_amaze(gpu, path, OPTS, "jpeg", lk=lk)
-    want = renderings(oracle, full, gains, w, h, look=LOOK)
-    check_tiffs(want, tiffs, w, h, "amaze with a look")
-    check_jpegs(want, jpgs, flags, w, h, "amaze with a look")
-    plain, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb")
+        tiffs, _, _, gains = serve(gpu, path, OPTS, "rgb", FULL, setup=amaze(lk))
+        jpgs, flags, _, _ = serve(gpu, path, OPTS, "jpeg", FULL, setup=amaze(lk))
+    want = renderings(full, gains, w, h, "full+amaze", amaze=oracle.amaze_demosaic, look=LOOK)
+    check_tiffs(want, tiffs, (w, h), "amaze with a look")
+    check_jpegs(want, jpgs, flags, (w, h), "amaze with a look", QUALITY)
+    plain, _, _, _ = serve(gpu, path, OPTS, "rgb", FULL, setup=amaze())
     assert all(a != b for a, b in zip(plain, tiffs))
 
 
@@ -115,10 +80,10 @@ def test_amaze_calls_interleave_with_the_other_calls(gpu, oracle, tmp_path):
     w, h = SIZES[0]
     path = make_clip(tmp_path, "plain", w, h, n=8)
     order = ((0, 8, GAIN_A),)
-    want_dng, _, _ = serve(gpu, path, OPTS, "dng", order=order, batch=4)
-    want_half, _, _ = serve(gpu, path, OPTS, "rgb", order=order, batch=4)
-    want_tiff, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", order=order, batch=4)
-    want_jpg, _, _, _ = serve_amaze(gpu, path, OPTS, "jpeg", order=order, batch=4)
+    want_dng, _, _, _ = serve(gpu, path, OPTS, "dng", order=order, batch=4)
+    want_half, _, _, _ = serve(gpu, path, OPTS, "rgb", order=order, batch=4)
+    want_tiff, _, _, _ = serve(gpu, path, OPTS, "rgb", FULL, order=order, batch=4, setup=amaze())
+    want_jpg, _, _, _ = serve(gpu, path, OPTS, "jpeg", FULL, order=order, batch=4, setup=amaze())
     fresh(gpu)
     r, m = open_mount(path, OPTS)
     with r, m, look.Look16(*LOOK16) as lk16:
@@ -135,7 +100,7 @@ def test_amaze_calls_interleave_with_the_other_calls(gpu, oracle, tmp_path):
     assert d == want_jpg[4:5] and efl == [0] and len(e[0]) < len(want_dng[5])
     half = jpeg.header(w // 2, h // 2, QUALITY) + jpeg.encode(render.split_file(want_half[6], w // 2, h // 2), QUALITY)
     assert f == [half]
-    check_tiffs16(renderings(oracle, want_dng[7:], [GAIN_A], w, h, look16=LOOK16), [g[0].tobytes()], w, h, "interleaved")
+    check_tiffs(renderings(want_dng[7:], [GAIN_A], w, h, "full+amaze", amaze=oracle.amaze_demosaic, look16=LOOK16), [g[0].tobytes()], (w, h), "interleaved", bits=16)
     fresh(gpu)
     r, m = open_mount(path, OPTS)
     with r, m:
@@ -149,40 +114,31 @@ def test_mount_amaze_behind_a_dual_iso_conversion(gpu, oracle, tmp_path):
     path = make_clip(tmp_path, "plain", w, h, dual=True, n=3)
     opts = dict(dual_iso=2, hdr_interp=0)
     order = ((0, 3, GAIN_A),)
-    full, res_full, _ = serve(gpu, path, opts, "dng", order=order)
-    tiffs, _, res_rgb, gains = serve_amaze(gpu, path, opts, "rgb", order=order)
+    full, _, res_full, _ = serve(gpu, path, opts, "dng", order=order)
+    tiffs, _, res_rgb, gains = serve(gpu, path, opts, "rgb", FULL, order=order, setup=amaze())
     assert res_rgb == res_full == [1, 1, 1]
-    check_tiffs(renderings(oracle, full, gains, w, h), tiffs, w, h, "dual ISO")
-    again, _, _ = serve(gpu, path, opts, "dng", order=order)
+    check_tiffs(renderings(full, gains, w, h, "full+amaze", amaze=oracle.amaze_demosaic), tiffs, (w, h), "dual ISO")
+    again, _, _, _ = serve(gpu, path, opts, "dng", order=order)
     assert again == full
 
 
 def test_the_render_tool_with_amaze(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py --full --demosaic amaze (its main(), in this process): TIFF, --jpeg, --bits 16 and --lut files are the mount's"""
-    import importlib.util
-    import os
-    import sys
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     w, h = SIZES[0]
     path = make_clip(tmp_path, "plain", w, h, n=3)
     order = ((0, 3, 1.5),)
-    want, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", order=order)
-    want_jpg, _, _, _ = serve_amaze(gpu, path, OPTS, "jpeg", order=order)
+    want, _, _, _ = serve(gpu, path, OPTS, "rgb", FULL, order=order, setup=amaze())
+    want_jpg, _, _, _ = serve(gpu, path, OPTS, "jpeg", FULL, order=order, setup=amaze())
     with look.Look16(look.shaper16("srgb")) as lk16:
-        want16, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb16", order=order, lk16=lk16)
+        want16, _, _, _ = serve(gpu, path, OPTS, "rgb", dict(FULL, look16=lk16), order=order, setup=amaze())
     cube = tmp_path / "t.cube"
     cube.write_text(lc.cube_text(3, lc.random_table(3)))
     with look.Look(look.shaper("srgb"), *look.read_cube(str(cube))) as lk:
-        want_lut, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", order=order, lk=lk)
+        want_lut, _, _, _ = serve(gpu, path, OPTS, "rgb", FULL, order=order, setup=amaze(lk))
 
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--bad-pix", "1", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--bad-pix", "1", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
 
     def files(out, ext):
         names = sorted(os.listdir(out))
@@ -196,7 +152,7 @@ def test_the_render_tool_with_amaze(gpu, tmp_path, monkeypatch, capsys):
     assert run(tmp_path / "c", ["--full", "--demosaic", "amaze", "--bits", "16"]) == 0 and files(tmp_path / "c", "tif") == want16
     assert run(tmp_path / "d", ["--full", "--demosaic", "amaze", "--lut", str(cube)]) == 0 and files(tmp_path / "d", "tif") == want_lut
     assert want_lut != want and want16 != want
-    linear, _, _, _ = serve_full(gpu, path, OPTS, "rgb", order=order)
+    linear, _, _, _ = serve(gpu, path, OPTS, "rgb", FULL, order=order)
     assert run(tmp_path / "e", ["--full"]) == 0 and files(tmp_path / "e", "tif") == linear
     capsys.readouterr()
     with pytest.raises(SystemExit):
@@ -208,7 +164,7 @@ def test_mount_amaze_refusals(gpu, tmp_path):
     w, h = SIZES[0]
     path = make_clip(tmp_path, "plain", w, h, n=4)
     size = HDR + w * h * 3
-    want, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", order=((0, 4, GAIN_A),))
+    want, _, _, _ = serve(gpu, path, OPTS, "rgb", FULL, order=((0, 4, GAIN_A),), setup=amaze())
     fresh(gpu)
     r, m = open_mount(path, OPTS)
     with r, m, look.Look16(*LOOK16) as lk16:
@@ -240,7 +196,7 @@ def test_mount_amaze_refusals(gpu, tmp_path):
     d = tmp_path / "narrow"
     d.mkdir()
     frames = [synth.normal_frame(34, 40, seed=5, frame=k) for k in range(2)]
-    narrow = mlvfile.write_clip(str(d / NAME), [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], 34, 40)[0]
+    narrow = mlvfile.write_clip(str(d / NAME), payloads(frames, "plain")[0], 34, 40)[0]
     fresh(gpu)
     r, m = open_mount(narrow, {})
     with r, m:

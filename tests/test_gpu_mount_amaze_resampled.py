@@ -4,39 +4,34 @@ mlvfs_amd/amaze_resample.py (the checker's AMaZE) applied to the pixels of the .
 TIFF, JPEG and 16-bit TIFF, with the handle's look too -- and PIL opens every file at ow x oh; results[], sizes[] and flags[]; the
 linear files come back when the setter returns to 0; every kind of call interleaves on one handle; a handle that never calls the setter
 serves what it served; a clip whose frames go through the dual-ISO conversion's AMaZE first; the refusals; the tool.  The helpers are
-those of tests/test_gpu_render.py, tests/test_gpu_mount_scaled.py and tests/test_gpu_mount_resampled.py."""
-import io
+those of tests/mount_harness.py."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from mlvfs_amd import amaze_resample, jpeg, lib, look, mlvfile, render, synth
+from mlvfs_amd import amaze_resample, lib, look, mlvfile, synth
 
 import deep_cases as dc
 import look_cases as lc
-from test_gpu_mount_resampled import serve_resampled
-from test_gpu_mount_scaled import check_jpegs, check_tiffs
-from test_gpu_render import GAIN_A, GAIN_B, NAME, fresh, make_clip, open_mount, serve
+from mount_harness import (GAIN_A, GAIN_B, HDR, NAME, ORDER, QUALITY, check_jpegs, check_tiffs, fresh, load_tool, make_clip, open_mount, payloads,
+                           renderings, run_tool, serve)
 
 pytestmark = pytest.mark.gpu
-HDR = render.HEADER_BYTES
-QUALITY = 85
 OPTS = dict(cs=5, badpix=1, stripes=1)
-ORDER = ((2, 3, GAIN_A), (0, 2, GAIN_B))
 LOOK, LOOK16 = lc.look_of("random17"), dc.look_of("random3")
 # payload, frame, size: a width the fast form takes at a ratio it takes, one it does not (148 is no multiple of 8), and the fast width
 # at a ratio below a half (the generic form)
 CASES = [("plain", 64, 48, (48, 36)), ("lzma", 148, 40, (111, 27)), ("lj92", 64, 48, (63, 47)), ("plain", 64, 48, (30, 48))]
 
 
-def serve_amaze(gpu, path, opts, kind, size, order=ORDER, batch=2, lk=None, lk16=None, full_demosaic=None, quality=QUALITY):
-    """the clip through one fresh handle with AMaZE set for the resampled calls -> (files, flags, results, gains); kind: rgb or jpeg"""
-    fresh(gpu)
-    r, m = open_mount(path, opts)
-    files, flags, results, gains = [], [], [], []
-    with r, m:
+def resampled(size, **more):
+    return dict(size=size, resample=True, **more)
+
+
+def amaze(lk=None, full_demosaic=None):
+    """the setup of a handle that serves AMaZE in the resampled calls, with a look and a full-size demosaic where they are given"""
+    def setup(m):
         assert m.resample_demosaic == "linear"
         m.set_resample_demosaic("amaze")
         assert m.resample_demosaic == "amaze"
@@ -44,62 +39,29 @@ def serve_amaze(gpu, path, opts, kind, size, order=ORDER, batch=2, lk=None, lk16
             m.set_demosaic(full_demosaic)
         if lk is not None:
             m.set_look(lk)
-        for first, count, gain in order:
-            res = np.full(count, -1, np.int32)
-            if kind == "jpeg":
-                a, fl = m.jpeg(first, count, gain=gain, quality=quality, batch=batch, results=res, size=size, resample=True)
-            else:
-                bits = 16 if lk16 is not None else 8
-                a = m.rgb(first, count, gain=gain, batch=batch, results=res, size=size, resample=True, look16=lk16)
-                nbytes = m.rgb_size(size=size, resample=True, bits=bits)
-                assert a.shape == (count, nbytes) and nbytes == HDR + (bits // 8) * 3 * size[0] * size[1]
-                a, fl = [f.tobytes() for f in a], [None] * count
-            files += a
-            flags += fl
-            results += list(res)
-            gains += [gain] * count
-    return files, flags, results, gains
-
-
-def renderings(oracle, full, gains, w, h, size, **tone):
-    """the definition applied to every full-size .dng file"""
-    out = []
-    for f, gain in zip(full, gains):
-        assert len(f) == 65536 + w * h * 2
-        p = render.params_from_header(f[:65536], int(round(256 * gain)))
-        out.append(amaze_resample.render(np.frombuffer(f, "<u2", offset=65536).reshape(h, w), p, oracle.amaze_demosaic, size[0], size[1], **tone))
-    return out
-
-
-def check_tiffs16(want, files, size, label):
-    from PIL import Image
-    assert len(want) == len(files)
-    for k, (px, t) in enumerate(zip(want, files)):
-        assert t == render.tiff_header(size[0], size[1], 16) + np.ascontiguousarray(px, "<u2").tobytes(), f"{label} frame {k}: not the definition's 16-bit file"
-        with Image.open(io.BytesIO(t)) as im:
-            assert im.size == size, (label, k)
+    return setup
 
 
 @pytest.mark.parametrize("payload,w,h,size", CASES, ids=lambda v: str(v))
 def test_mount_serves_the_definitions_files(gpu, oracle, reference, tmp_path, payload, w, h, size):
     label = f"amaze {payload} {w}x{h}->{size}"
     path = make_clip(tmp_path, payload, w, h, reference=reference)
-    full, res_full, _ = serve(gpu, path, OPTS, "dng")
-    tiffs, _, res_rgb, gains = serve_amaze(gpu, path, OPTS, "rgb", size)
-    jpgs, flags, res_jpg, _ = serve_amaze(gpu, path, OPTS, "jpeg", size)
+    full, _, res_full, _ = serve(gpu, path, OPTS, "dng")
+    tiffs, _, res_rgb, gains = serve(gpu, path, OPTS, "rgb", resampled(size), setup=amaze())
+    jpgs, flags, res_jpg, _ = serve(gpu, path, OPTS, "jpeg", resampled(size), setup=amaze())
     with look.Look16(*LOOK16) as lk16:
-        deep, _, res_deep, _ = serve_amaze(gpu, path, OPTS, "rgb", size, lk16=lk16)
+        deep, _, res_deep, _ = serve(gpu, path, OPTS, "rgb", resampled(size, look16=lk16), setup=amaze())
     assert res_rgb == res_full == res_jpg == res_deep and all(r in (0, 1) for r in res_full)
-    want = renderings(oracle, full, gains, w, h, size)
+    want = renderings(full, gains, w, h, "resampled+amaze", size, oracle.amaze_demosaic)
     check_tiffs(want, tiffs, size, label)
-    check_jpegs(want, jpgs, flags, size, label)
-    check_tiffs16(renderings(oracle, full, gains, w, h, size, look16=LOOK16), deep, size, label)
+    check_jpegs(want, jpgs, flags, size, label, QUALITY)
+    check_tiffs(renderings(full, gains, w, h, "resampled+amaze", size, oracle.amaze_demosaic, look16=LOOK16), deep, size, label, bits=16)
     assert len(set(tiffs)) == len(tiffs)
     # whatever set_demosaic says
-    again, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", size, full_demosaic="amaze")
+    again, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(size), setup=amaze(full_demosaic="amaze"))
     assert again == tiffs
     # another rendering than the linear filter's, which the same handle serves again once the setter is back at 0
-    linear, _, _, _ = serve_resampled(gpu, path, OPTS, "rgb", size, order=ORDER)
+    linear, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(size), order=ORDER)
     assert all(a != b for a, b in zip(linear, tiffs))
     fresh(gpu)
     r, m = open_mount(path, OPTS)
@@ -116,14 +78,14 @@ def test_mount_serves_the_definitions_files(gpu, oracle, reference, tmp_path, pa
 def test_mount_with_a_look(gpu, oracle, tmp_path):
     w, h, size = 64, 48, (48, 36)
     path = make_clip(tmp_path, "plain", w, h)
-    full, _, _ = serve(gpu, path, OPTS, "dng")
+    full, _, _, _ = serve(gpu, path, OPTS, "dng")
     with look.Look(*LOOK) as lk:
-        tiffs, _, _, gains = serve_amaze(gpu, path, OPTS, "rgb", size, lk=lk)
-        jpgs, flags, _, _ = serve_amaze(gpu, path, OPTS, "jpeg", size, lk=lk)
-    want = renderings(oracle, full, gains, w, h, size, look=LOOK)
+        tiffs, _, _, gains = serve(gpu, path, OPTS, "rgb", resampled(size), setup=amaze(lk))
+        jpgs, flags, _, _ = serve(gpu, path, OPTS, "jpeg", resampled(size), setup=amaze(lk))
+    want = renderings(full, gains, w, h, "resampled+amaze", size, oracle.amaze_demosaic, look=LOOK)
     check_tiffs(want, tiffs, size, "amaze resampled with a look")
-    check_jpegs(want, jpgs, flags, size, "amaze resampled with a look")
-    plain, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", size)
+    check_jpegs(want, jpgs, flags, size, "amaze resampled with a look", QUALITY)
+    plain, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(size), setup=amaze())
     assert all(a != b for a, b in zip(plain, tiffs))
 
 
@@ -131,8 +93,8 @@ def test_sizes_and_flags_as_the_c_call_reports_them(gpu, tmp_path):
     w, h, size = 64, 48, (48, 36)
     path = make_clip(tmp_path, "plain", w, h, n=4)
     order = ((0, 4, GAIN_A),)
-    want, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", size, order=order)
-    want_jpg, want_fl, _, _ = serve_amaze(gpu, path, OPTS, "jpeg", size, order=order)
+    want, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(size), order=order, setup=amaze())
+    want_jpg, want_fl, _, _ = serve(gpu, path, OPTS, "jpeg", resampled(size), order=order, setup=amaze())
     nbytes = HDR + 48 * 36 * 3
     st = nbytes + 37
     fresh(gpu)
@@ -163,14 +125,14 @@ def test_every_kind_of_call_interleaves(gpu, oracle, tmp_path):
     A, B = (48, 36), (64, 16)
     path = make_clip(tmp_path, "plain", w, h, n=8)
     order = ((0, 8, GAIN_A),)
-    want_dng, _, _ = serve(gpu, path, OPTS, "dng", order=order, batch=4)
-    want_half, _, _ = serve(gpu, path, OPTS, "rgb", order=order, batch=4)
-    want_a, _, _, gains = serve_amaze(gpu, path, OPTS, "rgb", A, order=order, batch=4)
-    want_b, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", B, order=order, batch=4)
-    jpg_b, flags, _, _ = serve_amaze(gpu, path, OPTS, "jpeg", B, order=order, batch=4)
-    check_tiffs(renderings(oracle, want_dng, gains, w, h, A), want_a, A, "one size")
-    check_tiffs(renderings(oracle, want_dng, gains, w, h, B), want_b, B, "another")
-    ident, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", (w, h), order=((0, 2, GAIN_A),), batch=2)
+    want_dng, _, _, _ = serve(gpu, path, OPTS, "dng", order=order, batch=4)
+    want_half, _, _, _ = serve(gpu, path, OPTS, "rgb", order=order, batch=4)
+    want_a, _, _, gains = serve(gpu, path, OPTS, "rgb", resampled(A), order=order, batch=4, setup=amaze())
+    want_b, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(B), order=order, batch=4, setup=amaze())
+    jpg_b, flags, _, _ = serve(gpu, path, OPTS, "jpeg", resampled(B), order=order, batch=4, setup=amaze())
+    check_tiffs(renderings(want_dng, gains, w, h, "resampled+amaze", A, oracle.amaze_demosaic), want_a, A, "one size")
+    check_tiffs(renderings(want_dng, gains, w, h, "resampled+amaze", B, oracle.amaze_demosaic), want_b, B, "another")
+    ident, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled((w, h)), order=((0, 2, GAIN_A),), batch=2, setup=amaze())
     fresh(gpu)
     r, m = open_mount(path, OPTS)
     with r, m, look.Look16(*LOOK16) as lk16:
@@ -186,7 +148,7 @@ def test_every_kind_of_call_interleaves(gpu, oracle, tmp_path):
         i2 = [x.tobytes() for x in m.rgb(0, 2, batch=2, full=True)]          # the AMaZE full-size rendering is the identity size
     assert a[0].tobytes() == want_half[0] and [x.tobytes() for x in b] == want_a[1:3] and c[0].tobytes() == want_dng[3]
     assert d == jpg_b[4:5] and i2 == ident
-    check_tiffs16(renderings(oracle, want_dng[7:], [GAIN_A], w, h, B, look16=LOOK16), [g[0].tobytes()], B, "interleaved")
+    check_tiffs(renderings(want_dng[7:], [GAIN_A], w, h, "resampled+amaze", B, oracle.amaze_demosaic, look16=LOOK16), [g[0].tobytes()], B, "interleaved", bits=16)
     fresh(gpu)
     r, m = open_mount(path, OPTS)
     with r, m:
@@ -218,7 +180,7 @@ def test_a_handle_that_never_calls_the_setter_serves_what_it_served(gpu, tmp_pat
             out.append(m.rgb(5, 1, batch=2, full=True).tobytes())
         return out
 
-    linear, _, _, _ = serve_resampled(gpu, path, OPTS, "rgb", size, order=((0, 2, GAIN_A),))
+    linear, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(size), order=((0, 2, GAIN_A),))
     a = run(False)
     assert a == run(True) and a[1] == b"".join(linear)
 
@@ -229,11 +191,11 @@ def test_behind_a_dual_iso_conversion(gpu, oracle, tmp_path):
     path = make_clip(tmp_path, "plain", w, h, dual=True, n=3)
     opts = dict(dual_iso=2, hdr_interp=0)
     order = ((0, 3, GAIN_A),)
-    full, res_full, _ = serve(gpu, path, opts, "dng", order=order)
-    tiffs, _, res_rgb, gains = serve_amaze(gpu, path, opts, "rgb", size, order=order)
+    full, _, res_full, _ = serve(gpu, path, opts, "dng", order=order)
+    tiffs, _, res_rgb, gains = serve(gpu, path, opts, "rgb", resampled(size), order=order, setup=amaze())
     assert res_rgb == res_full == [1, 1, 1]
-    check_tiffs(renderings(oracle, full, gains, w, h, size), tiffs, size, "dual ISO")
-    again, _, _ = serve(gpu, path, opts, "dng", order=order)
+    check_tiffs(renderings(full, gains, w, h, "resampled+amaze", size, oracle.amaze_demosaic), tiffs, size, "dual ISO")
+    again, _, _, _ = serve(gpu, path, opts, "dng", order=order)
     assert again == full
 
 
@@ -241,7 +203,7 @@ def test_refusals(gpu, tmp_path):
     w, h, size = 64, 48, (48, 36)
     path = make_clip(tmp_path, "plain", w, h, n=4)
     nbytes = HDR + 48 * 36 * 3
-    want, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", size, order=((0, 4, GAIN_A),))
+    want, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(size), order=((0, 4, GAIN_A),), setup=amaze())
     fresh(gpu)
     r, m = open_mount(path, OPTS)
     with r, m, look.Look16(*LOOK16) as lk16:
@@ -278,7 +240,7 @@ def test_refusals(gpu, tmp_path):
     d = tmp_path / "narrow"
     d.mkdir()
     frames = [synth.normal_frame(34, 40, seed=5, frame=k) for k in range(2)]
-    narrow = mlvfile.write_clip(str(d / NAME), [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], 34, 40)[0]
+    narrow = mlvfile.write_clip(str(d / NAME), payloads(frames, "plain")[0], 34, 40)[0]
     fresh(gpu)
     r, m = open_mount(narrow, {})
     with r, m:
@@ -300,47 +262,40 @@ def test_refusals(gpu, tmp_path):
 def test_the_render_tool(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py --resample (--size | --fit) --demosaic amaze (its main(), in this process): TIFF, --jpeg, --bits 16 and --lut
     files are the mount's"""
-    import importlib.util
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     w, h = 64, 48
     path = make_clip(tmp_path, "plain", w, h, n=3)
     order = ((0, 3, 1.5),)
     fit = amaze_resample.fit(w, h, 60, 36)
     assert fit == (48, 36)
-    want, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", fit, order=order)
-    want_jpg, _, _, _ = serve_amaze(gpu, path, OPTS, "jpeg", fit, order=order, quality=QUALITY)
-    want_size, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", (50, 40), order=order)
+    want, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(fit), order=order, setup=amaze())
+    want_jpg, _, _, _ = serve(gpu, path, OPTS, "jpeg", resampled(fit), order=order, quality=QUALITY, setup=amaze())
+    want_size, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled((50, 40)), order=order, setup=amaze())
     with look.Look16(look.shaper16("srgb")) as lk16:
-        want16, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", fit, order=order, lk16=lk16)
+        want16, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(fit, look16=lk16), order=order, setup=amaze())
     cube = tmp_path / "t.cube"
     cube.write_text(lc.cube_text(3, lc.random_table(3)))
     with look.Look(look.shaper("srgb"), *look.read_cube(str(cube))) as lk:
-        want_lut, _, _, _ = serve_amaze(gpu, path, OPTS, "rgb", fit, order=order, lk=lk)
+        want_lut, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(fit), order=order, setup=amaze(lk))
 
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--bad-pix", "1", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--bad-pix", "1", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
 
     def files(out, ext):
         names = sorted(os.listdir(out))
         assert names == ["M07-1234_%06d.%s" % (k, ext) for k in range(3)]
         return [open(out / n, "rb").read() for n in names]
 
-    amaze = ["--resample", "--fit", "60x36", "--demosaic", "amaze"]
-    assert run(tmp_path / "a", amaze) == 0 and files(tmp_path / "a", "tif") == want
+    argv = ["--resample", "--fit", "60x36", "--demosaic", "amaze"]
+    assert run(tmp_path / "a", argv) == 0 and files(tmp_path / "a", "tif") == want
     with Image.open(tmp_path / "a" / "M07-1234_000000.tif") as im:
         assert im.mode == "RGB" and im.size == fit
-    assert run(tmp_path / "b", amaze + ["--jpeg", str(QUALITY)]) == 0 and files(tmp_path / "b", "jpg") == want_jpg
-    assert run(tmp_path / "c", amaze + ["--bits", "16"]) == 0 and files(tmp_path / "c", "tif") == want16
-    assert run(tmp_path / "d", amaze + ["--lut", str(cube)]) == 0 and files(tmp_path / "d", "tif") == want_lut
+    assert run(tmp_path / "b", argv + ["--jpeg", str(QUALITY)]) == 0 and files(tmp_path / "b", "jpg") == want_jpg
+    assert run(tmp_path / "c", argv + ["--bits", "16"]) == 0 and files(tmp_path / "c", "tif") == want16
+    assert run(tmp_path / "d", argv + ["--lut", str(cube)]) == 0 and files(tmp_path / "d", "tif") == want_lut
     assert run(tmp_path / "e", ["--resample", "--size", "50x40", "--demosaic", "amaze"]) == 0 and files(tmp_path / "e", "tif") == want_size
     assert want_lut != want and want16 != want
-    linear, _, _, _ = serve_resampled(gpu, path, OPTS, "rgb", fit, order=order)
+    linear, _, _, _ = serve(gpu, path, OPTS, "rgb", resampled(fit), order=order)
     assert run(tmp_path / "f", ["--resample", "--fit", "60x36"]) == 0 and files(tmp_path / "f", "tif") == linear and linear != want
     capsys.readouterr()
     with pytest.raises(SystemExit):

@@ -14,10 +14,9 @@ from mlvfs_amd import lib, look, render
 
 import deep_cases as dp
 import look_cases as lc
-from test_gpu_render import fresh, make_clip, open_mount
+from mount_harness import HDR, fresh, load_tool, make_clip, open_mount, out_size, route_args, run_tool, serve
 
 pytestmark = pytest.mark.gpu
-HDR = render.HEADER_BYTES
 LOOKS = {name: (S, n, T) for name, S, n, T in dp.looks()}
 OPTS = dict(cs=5, badpix=1, stripes=1)
 SCALED = {(64, 48): (21, 16), (418, 266): (140, 89)}
@@ -25,17 +24,9 @@ ROUTES = ("half", "full", "scaled")
 GAIN = 1.5
 
 
-def route_args(route, w, h):
-    return dict(full=True) if route == "full" else dict(size=SCALED[(w, h)]) if route == "scaled" else dict()
-
-
-def out_size(route, w, h):
-    return (w // 2, h // 2) if route == "half" else (w, h) if route == "full" else SCALED[(w, h)]
-
-
 def want_files(dngs, w, h, route, lk, gain=GAIN):
     """the definition applied to every .dng file: header + samples"""
-    ow, oh = out_size(route, w, h)
+    ow, oh = out_size(route, w, h, SCALED[(w, h)])
     out = []
     for f in dngs:
         assert len(f) == 65536 + w * h * 2
@@ -46,10 +37,7 @@ def want_files(dngs, w, h, route, lk, gain=GAIN):
 
 
 def serve_dng(gpu, path, n, opts=OPTS):
-    fresh(gpu)
-    r, m = open_mount(path, opts)
-    with r, m:
-        return [f.tobytes() for f in m.dng(0, n, batch=2)]
+    return serve(gpu, path, opts, "dng", order=((0, n, 1.0),))[0]
 
 
 @pytest.mark.parametrize("payload,w,h,name", [("plain", 64, 48, "random3"), ("lj92", 64, 48, "linear0"), ("plain", 418, 266, "srgb17"),
@@ -60,14 +48,15 @@ def test_mount_rgb16_is_the_dng_file_rendered_at_16_bits(gpu, tmp_path, payload,
     dngs = serve_dng(gpu, path, 5)
     with look.Look16(*LOOKS[name]) as lk:
         for route in ROUTES:
-            ow, oh = out_size(route, w, h)
+            ow, oh = out_size(route, w, h, SCALED[(w, h)])
+            kw = route_args(route, SCALED[(w, h)])
             fresh(gpu)
             r, m = open_mount(path, OPTS)
             with r, m:
                 res = np.full(5, -1, np.int32)
-                size = m.rgb_size(0, bits=16, **route_args(route, w, h))
-                assert size == HDR + 6 * ow * oh == 2 * m.rgb_size(0, **route_args(route, w, h)) - HDR
-                files = [f.tobytes() for f in m.rgb(0, 5, gain=GAIN, batch=2, results=res, look16=lk, **route_args(route, w, h))]
+                size = m.rgb_size(0, bits=16, **kw)
+                assert size == HDR + 6 * ow * oh == 2 * m.rgb_size(0, **kw) - HDR
+                files = [f.tobytes() for f in m.rgb(0, 5, gain=GAIN, batch=2, results=res, look16=lk, **kw)]
             assert all(v in (0, 1) for v in res)
             want = want_files(dngs, w, h, route, LOOKS[name])
             for k in range(5):
@@ -177,13 +166,8 @@ def test_out_stride_and_the_refusals(gpu, tmp_path):
 def test_the_render_tool_writes_16_bit_files(gpu, tmp_path, monkeypatch):
     """tools/mlv_render.py --bits 16 (its main(), in this process): behind a log2 curve with no table, behind the default sRGB curve with
     a 3^3 .cube table at full size, and linear at a smaller size -- the mount's files, which PIL opens; --bits 16 --jpeg is an error"""
-    import importlib.util
-    import sys
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool16", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     w, h = 64, 48
     path = make_clip(tmp_path, "plain", w, h, n=3)
     opts = dict(cs=5, stripes=1)
@@ -192,11 +176,7 @@ def test_the_render_tool_writes_16_bit_files(gpu, tmp_path, monkeypatch):
     cube = tmp_path / "grade.cube"
     cube.write_text(lc.cube_text(3, T))
 
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5", "--bits", "16"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5", "--bits", "16"] + extra)
     for k, (lk, extra, route) in enumerate([((look.shaper16_log2(12), 0, None), ["--lut-input", "log2:12"], "half"),
                                             ((look.shaper16_srgb(), 3, T), ["--lut", str(cube), "--full"], "full"),
                                             ((look.shaper16_linear(), 0, None), ["--lut-input", "linear", "--size", "21x16"], "scaled")]):
@@ -206,7 +186,7 @@ def test_the_render_tool_writes_16_bit_files(gpu, tmp_path, monkeypatch):
         assert names == ["M07-1234_%06d.tif" % i for i in range(3)]
         assert [open(out / n, "rb").read() for n in names] == want_files(dngs, w, h, route, lk)
         with Image.open(out / names[0]) as im:
-            assert im.mode == "RGB" and im.size == out_size(route, w, h)
+            assert im.mode == "RGB" and im.size == out_size(route, w, h, SCALED[(w, h)])
             im.load()
     for extra in (["--jpeg"], ["--jpeg", "80"], ["--lut-input", "gamma"]):
         with pytest.raises(SystemExit):

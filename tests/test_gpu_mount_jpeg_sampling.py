@@ -3,117 +3,78 @@ header and stream mlvfs_amd/jpeg.py gives, at the sampling set, for the numpy re
 and the resampled route on plain and LJ92 clips, the full-size route with AMaZE --; samplings interleave on one handle and with the
 other serving calls; a handle that never sets one serves 4:2:0; the TIFF is served where the JPEG file would be larger; and
 tools/mlv_render.py --sampling.  All comparisons are for equality."""
-import io
 import os
 
-import numpy as np
 import pytest
 
-from mlvfs_amd import amaze_render, jpeg, lib, mlvfile, render, resample, synth
+from mlvfs_amd import jpeg, lib, render, synth
 
-from test_gpu_render import GAIN_A, GAIN_B, NAME, fresh, make_clip, open_mount, serve
+from mount_harness import GAIN_A, HDR as TIFF, QUALITY, check_jpegs, fresh, load_tool, make_clip, noise_clip, open_mount, renderings, run_tool, serve
 
 pytestmark = pytest.mark.gpu
 HDR = jpeg.HEADER_BYTES
-TIFF = render.HEADER_BYTES
 NAMES = {"4:2:0": 420, "4:2:2": 422, "4:4:4": 444}
 OPTS = dict(cs=5, badpix=1, stripes=1)
-ORDER = ((2, 3, GAIN_A), (0, 2, GAIN_B))
-QUALITY = 85
 
 
-@pytest.fixture(scope="module")
-def lut():
-    return render.srgb_lut12()
-
-
-def serve_jpeg(gpu, path, opts, sampling, order=ORDER, batch=2, quality=QUALITY, amaze=False, **route):
-    """the clip through one fresh handle at `sampling` (None: never set) -> (files, flags, results, gains)"""
-    fresh(gpu)
-    r, m = open_mount(path, opts)
-    files, flags, results, gains = [], [], [], []
-    with r, m:
+def sampled(sampling, amaze=False):
+    """the setup of a handle that serves JPEG files at `sampling` (None: never set)"""
+    def setup(m):
         if amaze:
             m.set_demosaic("amaze")
         if sampling is not None:
             m.set_jpeg_sampling(sampling)
-        for first, count, gain in order:
-            res = np.full(count, -1, np.int32)
-            a, fl = m.jpeg(first, count, gain=gain, quality=quality, batch=batch, results=res, **route)
-            files += a
-            flags += fl
-            results += list(res)
-            gains += [gain] * count
-    return files, flags, results, gains
+    return setup
 
 
-def raw_of(full, w, h, gains):
-    """[(the frame, its rendering parameters)] of full-size .dng files"""
-    out = []
-    for f, gain in zip(full, gains):
-        assert len(f) == 65536 + w * h * 2
-        out.append((np.frombuffer(f, "<u2", offset=65536).reshape(h, w), render.params_from_header(f[:65536], int(round(256 * gain)))))
-    return out
-
-
-def check_files(want, files, flags, sampling, quality, label):
-    """want: the numpy renderings; every file is the definition's at `sampling`, and PIL opens it at the rendering's size"""
-    from PIL import Image
-    assert len(want) == len(files) == len(flags)
-    for k, (px, j, fl) in enumerate(zip(want, files, flags)):
-        ph, pw = px.shape[:2]
-        file = jpeg.header(pw, ph, quality, NAMES[sampling]) + jpeg.encode(px, quality, None, NAMES[sampling])
-        assert len(file) <= TIFF + 3 * pw * ph and fl == 0, (label, k)
-        assert j == file, f"{label} frame {k}: not the definition's {sampling} file of the route's rendering"
-        assert jpeg.file_sampling(j) == NAMES[sampling]
-        with Image.open(io.BytesIO(j)) as im:
-            assert im.format == "JPEG" and im.mode == "RGB" and im.size == (pw, ph)
-            im.load()
+def check_files(want, files, flags, size, sampling, quality, label):
+    """every file is the definition's at `sampling`, which PIL opens at the rendering's size, and none is the TIFF"""
+    check_jpegs(want, files, flags, size, label, quality, NAMES[sampling])
+    assert flags == [0] * len(files) and all(len(j) <= TIFF + 3 * size[0] * size[1] for j in files), label
 
 
 CASES = [(p, w, h, size) for p in ("plain", "lj92") for (w, h), size in (((64, 48), (33, 25)), ((418, 266), (280, 178)))]
 
 
 @pytest.mark.parametrize("payload,w,h,size", CASES, ids=[f"{p}:{w}x{h}" for p, w, h, _ in CASES])
-def test_half_size_and_resampled_files_at_both_samplings(gpu, lut, tmp_path, payload, w, h, size):
+def test_half_size_and_resampled_files_at_both_samplings(gpu, tmp_path, payload, w, h, size):
     path = make_clip(tmp_path, payload, w, h)
-    full, res_full, gains = serve(gpu, path, OPTS, "dng")
-    raws = raw_of(full, w, h, gains)
-    half = [render.render(f, p, lut) for f, p in raws]
-    resampled = [resample.render(f, p, size[0], size[1], lut) for f, p in raws]
+    full, _, res_full, gains = serve(gpu, path, OPTS, "dng")
+    half = renderings(full, gains, w, h, "half")
+    resampled = renderings(full, gains, w, h, "resampled", size)
     for sampling in ("4:2:2", "4:4:4"):
-        files, flags, res, _ = serve_jpeg(gpu, path, OPTS, sampling)
+        files, flags, res, _ = serve(gpu, path, OPTS, "jpeg", setup=sampled(sampling))
         assert res == res_full
-        check_files(half, files, flags, sampling, QUALITY, f"{payload}:{w}x{h} half {sampling}")
+        check_files(half, files, flags, render.geom(w, h), sampling, QUALITY, f"{payload}:{w}x{h} half {sampling}")
         assert len(set(files)) == len(files), "two frames encoded alike"
-        files, flags, res, _ = serve_jpeg(gpu, path, OPTS, sampling, size=size, resample=True)
+        files, flags, res, _ = serve(gpu, path, OPTS, "jpeg", dict(size=size, resample=True), setup=sampled(sampling))
         assert res == res_full
-        check_files(resampled, files, flags, sampling, QUALITY, f"{payload}:{w}x{h} resampled {sampling}")
+        check_files(resampled, files, flags, size, sampling, QUALITY, f"{payload}:{w}x{h} resampled {sampling}")
 
 
 def test_full_size_amaze_files_at_both_samplings(gpu, oracle, tmp_path):
     w, h = 64, 48
     path = make_clip(tmp_path, "plain", w, h)
-    full, res_full, gains = serve(gpu, path, OPTS, "dng")
-    want = [amaze_render.render(f, p, oracle.amaze_demosaic) for f, p in raw_of(full, w, h, gains)]
+    full, _, res_full, gains = serve(gpu, path, OPTS, "dng")
+    want = renderings(full, gains, w, h, "full+amaze", amaze=oracle.amaze_demosaic)
     for sampling in ("4:2:2", "4:4:4"):
-        files, flags, res, _ = serve_jpeg(gpu, path, OPTS, sampling, amaze=True, full=True)
+        files, flags, res, _ = serve(gpu, path, OPTS, "jpeg", dict(full=True), setup=sampled(sampling, amaze=True))
         assert res == res_full
-        check_files(want, files, flags, sampling, QUALITY, f"amaze {sampling}")
+        check_files(want, files, flags, (w, h), sampling, QUALITY, f"amaze {sampling}")
 
 
-def test_samplings_interleave_on_one_handle_and_with_rgb_and_dng(gpu, lut, tmp_path):
+def test_samplings_interleave_on_one_handle_and_with_rgb_and_dng(gpu, tmp_path):
     w, h, q = 416, 264, 75
     path = make_clip(tmp_path, "plain", w, h, n=8)
     order = ((0, 8, GAIN_A),)
-    full, _, gains = serve(gpu, path, OPTS, "dng", order=order, batch=4)
-    want_rgb, _, _ = serve(gpu, path, OPTS, "rgb", order=order, batch=4)
-    raws = raw_of(full, w, h, gains)
-    half = [render.render(f, p, lut) for f, p in raws]
+    full, _, _, gains = serve(gpu, path, OPTS, "dng", order=order, batch=4)
+    want_rgb, _, _, _ = serve(gpu, path, OPTS, "rgb", order=order, batch=4)
+    half = renderings(full, gains, w, h, "half")
     size = (300, 190)
+    resampled = {k: renderings(full[k:k + 1], gains[k:k + 1], w, h, "resampled", size)[0] for k in (4, 7)}
     file = lambda px, s: jpeg.header(px.shape[1], px.shape[0], q, s) + jpeg.encode(px, q, None, s)
     # a handle that never calls the setter: the files of the call as it was, which are the definition's without a sampling
-    never, flags, _, _ = serve_jpeg(gpu, path, OPTS, None, order=order, batch=4, quality=q)
+    never, flags, _, _ = serve(gpu, path, OPTS, "jpeg", order=order, batch=4, quality=q)
     assert flags == [0] * 8 and never == [jpeg.header(w // 2, h // 2, q) + jpeg.encode(px, q) for px in half]
     fresh(gpu)
     r, m = open_mount(path, OPTS)
@@ -130,26 +91,18 @@ def test_samplings_interleave_on_one_handle_and_with_rgb_and_dng(gpu, lut, tmp_p
     assert fa + fb + fd + ff + fg == [0] * 6
     assert a == [file(px, 444) for px in half[:2]] and b == [file(half[2], 422)]
     assert c[0].tobytes() == full[3] and e[0].tobytes() == want_rgb[5]
-    assert d == [file(resample.render(*raws[4], size[0], size[1], lut), 422)]
+    assert d == [file(resampled[4], 422)]
     assert f == never[6:7]
-    assert g == [file(resample.render(*raws[7], size[0], size[1], lut), 444)]
-
-
-def noise_clip(tmp_path, w, h, n=2):
-    rng = np.random.default_rng(11)
-    frames = [rng.integers(synth.BLACK, synth.WHITE + 1, (h, w)).astype(np.uint16) for _ in range(n)]
-    path = str(tmp_path / NAME)
-    mlvfile.write_clip(path, [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], w, h)
-    return path
+    assert g == [file(resampled[7], 444)]
 
 
 def test_the_tiff_is_served_where_the_444_file_would_be_larger(gpu, tmp_path):
     """noise at quality 100: the definition's 4:4:4 stream does not fit beside 629 bytes of header in the TIFF's 256 + 3 W' H', so the
     TIFF is served with flag bit 0; every sampling follows the one rule"""
     w, h, q = 64, 48, 100
-    path = noise_clip(tmp_path, w, h)
+    path = noise_clip(tmp_path, w, h, n=2, flat_at=(), top=synth.WHITE + 1)
     order = ((0, 2, GAIN_A),)
-    tiffs, _, _ = serve(gpu, path, {}, "rgb", order=order)
+    tiffs, _, _, _ = serve(gpu, path, {}, "rgb", order=order)
     pw, ph = render.geom(w, h)
     pixels = [render.split_file(t, pw, ph) for t in tiffs]
     for sampling, code in NAMES.items():
@@ -157,7 +110,7 @@ def test_the_tiff_is_served_where_the_444_file_would_be_larger(gpu, tmp_path):
         larger = [HDR + len(s) > len(t) for s, t in zip(streams, tiffs)]
         if code == 444:
             assert larger == [True, True], "the case does not reach the rule: " + str([len(s) for s in streams])
-        files, flags, _, _ = serve_jpeg(gpu, path, {}, sampling, order=order, quality=q)
+        files, flags, _, _ = serve(gpu, path, {}, "jpeg", order=order, quality=q, setup=sampled(sampling))
         assert flags == [int(x) for x in larger], sampling
         for k in range(2):
             assert files[k] == (tiffs[k] if larger[k] else jpeg.header(pw, ph, q, code) + streams[k]), (sampling, k)
@@ -182,24 +135,14 @@ def test_set_jpeg_sampling_refusals(gpu, tmp_path):
 
 def test_the_render_tool_takes_a_sampling(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py --jpeg Q --sampling (its main(), in this process): the files are the mount's at that sampling, and PIL opens them"""
-    import importlib.util
-    import sys
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     path = make_clip(tmp_path, "plain", 64, 48, n=3)
     opts = dict(cs=5, stripes=1)
-
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
     names = ["M07-1234_%06d.jpg" % k for k in range(3)]
     for arg, sampling in (("444", "4:4:4"), ("422", "4:2:2"), ("420", "4:2:0")):
-        want, flags, _, _ = serve_jpeg(gpu, path, opts, sampling, order=((0, 3, 1.5),), quality=80)
+        want, flags, _, _ = serve(gpu, path, opts, "jpeg", order=((0, 3, 1.5),), quality=80, setup=sampled(sampling))
         out = tmp_path / ("out" + arg)
         assert run(out, ["--jpeg", "80", "--sampling", arg]) == 0 and flags == [0, 0, 0]
         assert sorted(os.listdir(out)) == names and [open(out / n, "rb").read() for n in names] == want
@@ -208,7 +151,7 @@ def test_the_render_tool_takes_a_sampling(gpu, tmp_path, monkeypatch, capsys):
                 assert im.format == "JPEG" and im.mode == "RGB" and im.size == (32, 24)
                 im.load()
             assert jpeg.file_sampling(open(out / n, "rb").read()) == NAMES[sampling]
-    plain, _, _, _ = serve_jpeg(gpu, path, opts, None, order=((0, 3, 1.5),), quality=80)
+    plain, _, _, _ = serve(gpu, path, opts, "jpeg", order=((0, 3, 1.5),), quality=80)
     assert run(tmp_path / "plain", ["--jpeg", "80"]) == 0 and [open(tmp_path / "plain" / n, "rb").read() for n in names] == plain == want
     capsys.readouterr()
     with pytest.raises(SystemExit):

@@ -4,99 +4,22 @@ the .dng the same options serve (for JPEG: mlvfs_amd/jpeg.py's encoding of that)
 and the generic kernels; a look is set, changed and cleared between calls on one handle while the .dng calls in between serve what a
 handle without a look serves; a handle that set and cleared a look serves what one that never did serves; and tools/mlv_render.py
 --lut writes those files from a .cube text.  All comparisons are for equality."""
-import io
 import os
 
 import numpy as np
 import pytest
 
-from mlvfs_amd import demosaic, jpeg, look, render, scale
+from mlvfs_amd import demosaic, look, render, scale
 
 import look_cases as lc
 import render_cases as rc
-from test_gpu_render import ORDER, fresh, make_clip, open_mount, serve
+from mount_harness import QUALITY, check_jpegs, check_tiffs, fresh, load_tool, make_clip, open_mount, out_size, renderings, route_args, run_tool, serve
 
 pytestmark = pytest.mark.gpu
-HDR = render.HEADER_BYTES
-QUALITY = 85
 LOOKS = {name: (S, n, T) for name, S, n, T in lc.looks()}
 OPTION_SETS = [("none", dict()), ("cs5+badpix+stripes", dict(cs=5, badpix=1, stripes=1))]
 SIZE_OF = {(64, 48): (21, 16), (418, 266): (140, 89)}
-ROUTES = [("half", dict()), ("full", dict(full=True)), ("scaled", None)]           # scaled: size=SIZE_OF[(w, h)]
-
-
-def route_args(route, w, h):
-    return dict(size=SIZE_OF[(w, h)]) if route == "scaled" else dict(ROUTES)[route]
-
-
-def out_size(route, w, h):
-    return (w // 2, h // 2) if route == "half" else (w, h) if route == "full" else SIZE_OF[(w, h)]
-
-
-def serve_look(gpu, path, opts, kind, args, lk, order=ORDER, batch=2):
-    """frames 2..4, then 0..1 (at another gain), in batches of 2, through one fresh handle with the look set -> (files, flags, results, gains)"""
-    fresh(gpu)
-    r, m = open_mount(path, opts)
-    files, flags, results, gains = [], [], [], []
-    with r, m:
-        m.set_look(lk)
-        for first, count, gain in order:
-            res = np.full(count, -1, np.int32)
-            if kind == "jpeg":
-                a, fl = m.jpeg(first, count, gain=gain, quality=QUALITY, batch=batch, results=res, **args)
-            else:
-                a = m.rgb(first, count, gain=gain, batch=batch, results=res, **args)
-                a, fl = [f.tobytes() for f in a], [None] * count
-            files += a
-            flags += fl
-            results += list(res)
-            gains += [gain] * count
-    return files, flags, results, gains
-
-
-def renderings(full, gains, w, h, route, lk):
-    """the definition, with the look, applied to every full-size .dng file"""
-    out = []
-    for f, gain in zip(full, gains):
-        assert len(f) == 65536 + w * h * 2
-        p = render.params_from_header(f[:65536], int(round(256 * gain)))
-        px = np.frombuffer(f, "<u2", offset=65536).reshape(h, w)
-        if route == "half":
-            out.append(render.render(px, p, look=lk))
-        elif route == "full":
-            out.append(demosaic.render(px, p, look=lk))
-        else:
-            out.append(scale.render(px, p, *SIZE_OF[(w, h)], look=lk))
-    return out
-
-
-def check_tiffs(want, tiffs, size, label):
-    from PIL import Image
-    ow, oh = size
-    assert len(want) == len(tiffs)
-    for k, (px, t) in enumerate(zip(want, tiffs)):
-        assert len(t) == HDR + ow * oh * 3, (label, k)
-        got = render.split_file(t, ow, oh)
-        assert np.array_equal(got, px), f"{label} frame {k}: {(got != px).sum()} bytes are not the definition's of the .dng file with the look"
-        assert t[:HDR] == render.tiff_header(ow, oh), (label, k)
-        with Image.open(io.BytesIO(t)) as im:
-            assert im.mode == "RGB" and im.size == (ow, oh) and np.array_equal(np.asarray(im), px), (label, k)
-
-
-def check_jpegs(want, files, flags, size, label, quality=QUALITY):
-    """each file: the definition's JPEG file of the rendering, or, where that is the larger, the TIFF with flag bit 0"""
-    from PIL import Image
-    ow, oh = size
-    assert len(want) == len(files) == len(flags)
-    for k, (px, j, fl) in enumerate(zip(want, files, flags)):
-        file = jpeg.header(ow, oh, quality) + jpeg.encode(px, quality)
-        tiff = render.tiff_header(ow, oh) + px.tobytes()
-        fallback = len(file) > len(tiff)
-        assert fl == int(fallback), (label, k, fl, len(file), len(tiff))
-        assert j == (tiff if fallback else file), f"{label} frame {k}: not the definition's file of the rendering with the look"
-        with Image.open(io.BytesIO(j)) as im:
-            assert im.format == ("TIFF" if fallback else "JPEG") and im.mode == "RGB" and im.size == (ow, oh)
-            im.load()
+ROUTES = ("half", "full", "scaled")                                                # scaled: size=SIZE_OF[(w, h)]
 
 
 # the look of each case: every N, the edge table, the non-monotone shapers and the linear one take their turn
@@ -110,17 +33,18 @@ def test_mount_look_is_the_dng_file_rendered_with_the_look(gpu, tmp_path, k):
     lname = LOOK_OF_CASE[k]
     label = f"{payload}:{w}x{h}:{name}:{lname}"
     path = make_clip(tmp_path, payload, w, h)
-    full, res_full, _ = serve(gpu, path, opts, "dng")
-    plain_half, _, _ = serve(gpu, path, opts, "rgb")
+    full, _, res_full, _ = serve(gpu, path, opts, "dng")
+    plain_half, _, _, _ = serve(gpu, path, opts, "rgb")
     with look.Look(*LOOKS[lname]) as lk:
-        for route, _ in ROUTES:
-            args, size = route_args(route, w, h), out_size(route, w, h)
-            tiffs, _, res_rgb, gains = serve_look(gpu, path, opts, "rgb", args, lk)
-            jpgs, flags, res_jpg, _ = serve_look(gpu, path, opts, "jpeg", args, lk)
+        set_look = lambda m: m.set_look(lk)
+        for route in ROUTES:
+            args, size = route_args(route, SIZE_OF[(w, h)]), out_size(route, w, h, SIZE_OF[(w, h)])
+            tiffs, _, res_rgb, gains = serve(gpu, path, opts, "rgb", args, setup=set_look)
+            jpgs, flags, res_jpg, _ = serve(gpu, path, opts, "jpeg", args, setup=set_look)
             assert res_rgb == res_full == res_jpg and all(r in (0, 1) for r in res_full), (label, route)
-            want = renderings(full, gains, w, h, route, LOOKS[lname])
+            want = renderings(full, gains, w, h, route, SIZE_OF[(w, h)], look=LOOKS[lname])
             check_tiffs(want, tiffs, size, f"{label}:{route}")
-            check_jpegs(want, jpgs, flags, size, f"{label}:{route}")
+            check_jpegs(want, jpgs, flags, size, f"{label}:{route}", QUALITY)
             if route == "half":                                  # the look did something, unless it is the identity
                 assert (tiffs == plain_half) == (lname == "identity17"), label
 
@@ -158,7 +82,7 @@ def test_a_look_is_set_changed_and_cleared_between_calls(gpu, tmp_path):
     assert np.array_equal(render.split_file(b3[0].tobytes(), w, h), demosaic.render(px[3], par[3], look=B))
     assert np.array_equal(render.split_file(b4[0].tobytes(), 21, 16), scale.render(px[4], par[4], 21, 16, look=B))
     assert np.array_equal(render.split_file(p5[0].tobytes(), 32, 24), render.render(px[5], par[5]))
-    check_jpegs([render.render(px[7], par[7], look=A)], j7, f7, (32, 24), "look A as JPEG")
+    check_jpegs([render.render(px[7], par[7], look=A)], j7, f7, (32, 24), "look A as JPEG", QUALITY)
     fresh(gpu)
     r, m = open_mount(path, opts)
     with r, m:
@@ -192,12 +116,7 @@ def test_a_handle_that_set_and_cleared_a_look_serves_what_one_without_serves(gpu
 def test_the_render_tool_takes_a_cube_file(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py --lut (its main(), in this process) on a 3^3 .cube text: the files are the mount's with that look, behind
     each of the three shapers"""
-    import importlib.util
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     path = make_clip(tmp_path, "plain", 64, 48, n=3)
     opts = dict(cs=5, stripes=1)
     T = lc.random_table(3, 4)
@@ -205,15 +124,11 @@ def test_the_render_tool_takes_a_cube_file(gpu, tmp_path, monkeypatch, capsys):
     cube.write_text(lc.cube_text(3, T))
     assert look.read_cube(cube)[1].tolist() == T.tolist()
 
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
     for k, (shaper, extra, args) in enumerate([("srgb", [], dict()), ("linear", ["--lut-input", "linear", "--size", "20x15"], dict(size=(20, 15))),
                                                ("log2:10", ["--lut-input", "log2:10", "--full"], dict(full=True))]):
         with look.Look(look.shaper(shaper), 3, T) as lk:
-            want, _, _, _ = serve_look(gpu, path, opts, "rgb", args, lk, order=((0, 3, 1.5),))
+            want, _, _, _ = serve(gpu, path, opts, "rgb", args, order=((0, 3, 1.5),), setup=lambda m: m.set_look(lk))
         out = tmp_path / f"out{k}"
         assert run(out, ["--lut", str(cube)] + extra) == 0
         names = sorted(os.listdir(out))

@@ -3,72 +3,26 @@ mlvfs_amd_mount_rgb_resampled against a full-size .dng mount of the same clip an
 mlvfs_amd/resample.py applied to the pixels of the .dng file, with the parameters the tags of that file's header give -- and
 mlvfs_amd_mount_jpeg_resampled against mlvfs_amd/jpeg.py's encoding of that rendering; the 16-bit call and a handle's look; results[],
 sizes[] and flags[]; PIL opens every file at ow x oh; every kind of call interleaves on one handle, and a handle that never makes a
-resampled call is left as it was; strides; the refusals; a failed growth of the full-size buffer; the tool.  The clips and option sets
-are those of tests/test_gpu_render.py.  All comparisons are for equality."""
-import io
+resampled call is left as it was; strides; the refusals; a failed growth of the full-size buffer; the tool.  The clips, option sets and
+helpers are those of tests/mount_harness.py.  All comparisons are for equality."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from mlvfs_amd import jpeg, lib, look, render, resample, synth
-from mlvfs_amd.dark import Dark
-from mlvfs_amd.flat import Flat
+from mlvfs_amd import lib, look, resample
 
-import dark_cases as dc
 import deep_cases as dp
-import flat_cases as fc
 import look_cases as lc
 import resample_cases as rs
-from test_gpu_mount_scaled import check_jpegs, check_tiffs
-from test_gpu_render import GAIN_A, OPTION_SETS, ORDER, PAYLOADS, fresh, make_clip, open_mount, serve
+from mount_harness import (GAIN_A, HDR, OPTION_SETS, PAYLOADS, QUALITY, calibration, check_jpegs, check_tiffs, fresh, load_tool, make_clip,
+                           open_mount, renderings, run_tool, serve)
 
 pytestmark = pytest.mark.gpu
-HDR = render.HEADER_BYTES
-JHDR = jpeg.HEADER_BYTES
-QUALITY = 85
 
 
-@pytest.fixture(scope="module")
-def lut():
-    return render.srgb_lut12()
-
-
-def serve_resampled(gpu, path, opts, kind, size, dark=None, flat=None, order=ORDER, batch=2, quality=QUALITY, lk=None, lk16=None):
-    """frames 2..4, then 0..1 (at another gain), in batches of 2, through one fresh handle -> (files, flags, results, gains)"""
-    fresh(gpu)
-    r, m = open_mount(path, opts, dark, flat)
-    files, flags, results, gains = [], [], [], []
-    with r, m:
-        if lk is not None:
-            m.set_look(lk)
-        for first, count, gain in order:
-            res = np.full(count, -1, np.int32)
-            if kind == "jpeg":
-                a, fl = m.jpeg(first, count, gain=gain, quality=quality, batch=batch, results=res, size=size, resample=True)
-            else:
-                bits = 16 if lk16 is not None else 8
-                a = m.rgb(first, count, gain=gain, batch=batch, results=res, size=size, resample=True, look16=lk16)
-                nbytes = m.rgb_size(size=size, resample=True, bits=bits)
-                assert a.shape == (count, nbytes) and nbytes == HDR + (bits // 8) * 3 * size[0] * size[1]
-                assert gpu.mlvfs_amd_mount_rgb_resampled_size(m.h, first, *size) == HDR + 3 * size[0] * size[1]
-                a, fl = [f.tobytes() for f in a], [None] * count
-            files += a
-            flags += fl
-            results += list(res)
-            gains += [gain] * count
-    return files, flags, results, gains
-
-
-def renderings(full, gains, w, h, size, lut=None, **how):
-    """the definition applied to every full-size .dng file"""
-    out = []
-    for f, gain in zip(full, gains):
-        assert len(f) == 65536 + w * h * 2
-        p = render.params_from_header(f[:65536], int(round(256 * gain)))
-        out.append(resample.render(np.frombuffer(f, "<u2", offset=65536).reshape(h, w), p, size[0], size[1], lut, **how))
-    return out
+def resampled(size, **more):
+    return dict(size=size, resample=True, **more)
 
 
 # every payload kind, both of the mount tests' frame sizes (the fast and the generic form), every option set, each at a size of its own
@@ -79,61 +33,55 @@ CASES = [(pl, w, h, SIZES_OF[(w, h)][k], name, opts, cal) for pl in PAYLOADS for
 
 
 @pytest.mark.parametrize("payload,w,h,size,name,opts,cal", CASES, ids=[f"{pl}:{w}x{h}->{s[0]}x{s[1]}:{name}" for pl, w, h, s, name, _, _ in CASES])
-def test_mount_resampled_is_the_full_size_file_resampled(gpu, reference, lut, tmp_path, payload, w, h, size, name, opts, cal):
+def test_mount_resampled_is_the_full_size_file_resampled(gpu, reference, tmp_path, payload, w, h, size, name, opts, cal):
     label = f"{payload}:{w}x{h}->{size}:{name}"
     path = make_clip(tmp_path, payload, w, h, dual=bool(opts.get("dual_iso")), reference=reference)
-    with Dark.from_plane(dc.dark_plane(w, h) if cal else np.zeros((1, 1), np.uint16), 14, synth.BLACK) as dark, \
-            Flat.from_plane(fc.clip_flat(w, h) if cal else np.full((1, 1), 3000, np.uint16), 14, synth.BLACK) as flat:
-        cal_args = dict(dark=dark, flat=flat) if cal else {}
-        full, res_full, _ = serve(gpu, path, opts, "dng", **cal_args)
-        tiffs, _, res_rgb, gains = serve_resampled(gpu, path, opts, "rgb", size, **cal_args)
-        jpgs, flags, res_jpg, _ = serve_resampled(gpu, path, opts, "jpeg", size, **cal_args)
+    with calibration(cal, w, h) as cal_args:
+        full, _, res_full, _ = serve(gpu, path, opts, "dng", **cal_args)
+        tiffs, _, res_rgb, gains = serve(gpu, path, opts, "rgb", resampled(size), **cal_args)
+        jpgs, flags, res_jpg, _ = serve(gpu, path, opts, "jpeg", resampled(size), **cal_args)
     assert res_rgb == res_full == res_jpg and all(r in (0, 1) for r in res_full)
-    want = renderings(full, gains, w, h, size, lut)
+    want = renderings(full, gains, w, h, "resampled", size)
     check_tiffs(want, tiffs, size, label)
-    check_jpegs(want, jpgs, flags, size, label)
+    check_jpegs(want, jpgs, flags, size, label, QUALITY)
     assert len(set(tiffs)) == len(tiffs), "two frames rendered alike"
 
 
 @pytest.mark.parametrize("w,h,size", [(64, 48, (48, 36)), (418, 266, (417, 265))], ids=lambda v: str(v))
 def test_mount_resampled_with_a_look_and_at_16_bits(gpu, tmp_path, w, h, size):
-    from PIL import Image
     path = make_clip(tmp_path, "plain", w, h)
     opts = dict(cs=5, badpix=1, stripes=1)
     name, S, n, T = lc.looks()[1]
     name16, S16, n16, T16 = dp.looks()[1]
-    full, res_full, _ = serve(gpu, path, opts, "dng")
+    full, _, res_full, _ = serve(gpu, path, opts, "dng")
     with look.Look(S, n, T) as lk, look.Look16(S16, n16, T16) as lk16:
-        tiffs, _, res_rgb, gains = serve_resampled(gpu, path, opts, "rgb", size, lk=lk)
-        jpgs, flags, _, _ = serve_resampled(gpu, path, opts, "jpeg", size, lk=lk)
-        deep, _, res16, _ = serve_resampled(gpu, path, opts, "rgb", size, lk=lk, lk16=lk16)        # the handle's look does not touch these
+        set_look = lambda m: m.set_look(lk)
+        tiffs, _, res_rgb, gains = serve(gpu, path, opts, "rgb", resampled(size), setup=set_look)
+        jpgs, flags, _, _ = serve(gpu, path, opts, "jpeg", resampled(size), setup=set_look)
+        deep, _, res16, _ = serve(gpu, path, opts, "rgb", resampled(size, look16=lk16), setup=set_look)       # the handle's look does not touch these
     assert res_rgb == res_full == res16
-    want = renderings(full, gains, w, h, size, look=(S, n, T))
+    want = renderings(full, gains, w, h, "resampled", size, look=(S, n, T))
     check_tiffs(want, tiffs, size, name)
-    check_jpegs(want, jpgs, flags, size, name)
-    want16 = renderings(full, gains, w, h, size, look16=(S16, n16, T16))
-    for k, (px, t) in enumerate(zip(want16, deep)):
-        assert t[:HDR] == render.tiff_header(size[0], size[1], 16) and np.array_equal(render.split_file16(t, *size), px), (name16, k)
-        with Image.open(io.BytesIO(t)) as im:
-            assert im.size == size, k
+    check_jpegs(want, jpgs, flags, size, name, QUALITY)
+    check_tiffs(renderings(full, gains, w, h, "resampled", size, look16=(S16, n16, T16)), deep, size, name16, bits=16)
 
 
-def test_resampled_calls_interleave_with_every_other_kind(gpu, lut, tmp_path):
+def test_resampled_calls_interleave_with_every_other_kind(gpu, tmp_path):
     w, h = 416, 264
     path = make_clip(tmp_path, "plain", w, h, n=8)
     opts = dict(cs=5, badpix=1, stripes=1)
     order = ((0, 8, GAIN_A),)
     A, B = (300, 190), (416, 88)
-    want_dng, _, _ = serve(gpu, path, opts, "dng", order=order, batch=4)
-    want_half, _, _ = serve(gpu, path, opts, "rgb", order=order, batch=4)
-    want_a, _, _, gains = serve_resampled(gpu, path, opts, "rgb", A, order=order, batch=4)
-    want_b, _, _, _ = serve_resampled(gpu, path, opts, "rgb", B, order=order, batch=4)
-    jpg_b, flags, _, _ = serve_resampled(gpu, path, opts, "jpeg", B, order=order, batch=4)
-    check_tiffs(renderings(want_dng, gains, w, h, A, lut), want_a, A, "one size")
-    check_tiffs(renderings(want_dng, gains, w, h, B, lut), want_b, B, "another")
-    check_jpegs(renderings(want_dng, gains, w, h, B, lut), jpg_b, flags, B, "another")
+    want_dng, _, _, _ = serve(gpu, path, opts, "dng", order=order, batch=4)
+    want_half, _, _, _ = serve(gpu, path, opts, "rgb", order=order, batch=4)
+    want_a, _, _, gains = serve(gpu, path, opts, "rgb", resampled(A), order=order, batch=4)
+    want_b, _, _, _ = serve(gpu, path, opts, "rgb", resampled(B), order=order, batch=4)
+    jpg_b, flags, _, _ = serve(gpu, path, opts, "jpeg", resampled(B), order=order, batch=4)
+    check_tiffs(renderings(want_dng, gains, w, h, "resampled", A), want_a, A, "one size")
+    check_tiffs(renderings(want_dng, gains, w, h, "resampled", B), want_b, B, "another")
+    check_jpegs(renderings(want_dng, gains, w, h, "resampled", B), jpg_b, flags, B, "another", QUALITY)
     # the identity size is the full-size call's file
-    ident, _, _, _ = serve_resampled(gpu, path, opts, "rgb", (w, h), order=((0, 2, GAIN_A),), batch=2)
+    ident, _, _, _ = serve(gpu, path, opts, "rgb", resampled((w, h)), order=((0, 2, GAIN_A),), batch=2)
     fresh(gpu)
     r, m = open_mount(path, opts)
     with r, m:
@@ -150,10 +98,8 @@ def test_resampled_calls_interleave_with_every_other_kind(gpu, lut, tmp_path):
         g = m.rgb(7, 1, batch=2, size=B, resample=True)
     assert a[0].tobytes() == want_half[0] and [x.tobytes() for x in b] == want_a[1:3] and c[0].tobytes() == want_dng[3]
     assert d == jpg_b[4:5] and g[0].tobytes() == want_b[7]
-    assert np.array_equal(resample.split_file(e[0].tobytes(), w, h), renderings(want_dng[5:6], gains[5:6], w, h, (w, h), lut)[0])
-    from mlvfs_amd import scale
-    p = render.params_from_header(want_dng[6][:65536], 256)
-    assert np.array_equal(scale.split_file(f[0].tobytes(), 52, 33), scale.render(np.frombuffer(want_dng[6], "<u2", offset=65536).reshape(h, w), p, 52, 33, lut))
+    assert np.array_equal(resample.split_file(e[0].tobytes(), w, h), renderings(want_dng[5:6], gains[5:6], w, h, "resampled", (w, h))[0])
+    assert np.array_equal(resample.split_file(f[0].tobytes(), 52, 33), renderings(want_dng[6:7], gains[6:7], w, h, "scaled", (52, 33))[0])
 
 
 def test_a_handle_without_resampled_calls_serves_what_a_fresh_one_does(gpu, tmp_path):
@@ -179,13 +125,13 @@ def test_a_handle_without_resampled_calls_serves_what_a_fresh_one_does(gpu, tmp_
     assert run(False) == run(True)
 
 
-def test_mount_resampled_refusals_strides_and_a_failed_growth(gpu, lut, tmp_path):
+def test_mount_resampled_refusals_strides_and_a_failed_growth(gpu, tmp_path):
     w, h, size = 64, 48, (50, 40)
     path = make_clip(tmp_path, "plain", w, h, n=4)
     opts = dict(cs=5, stripes=1)
     order = ((0, 4, GAIN_A),)
-    want, _, _, _ = serve_resampled(gpu, path, opts, "rgb", size, order=order)
-    want_jpg, want_fl, _, _ = serve_resampled(gpu, path, opts, "jpeg", size, order=order)
+    want, _, _, _ = serve(gpu, path, opts, "rgb", resampled(size), order=order)
+    want_jpg, want_fl, _, _ = serve(gpu, path, opts, "jpeg", resampled(size), order=order)
     nbytes = HDR + 50 * 40 * 3
     fresh(gpu)
     r, m = open_mount(path, opts)
@@ -246,26 +192,18 @@ def test_mount_resampled_refusals_strides_and_a_failed_growth(gpu, lut, tmp_path
         assert m.dng(0, 2, batch=2).shape == (2, 65536 + 32 * 24 * 2)        # the refusal served nothing and spoilt nothing
 
 
-def test_the_render_tool_resamples(gpu, lut, tmp_path, monkeypatch, capsys):
+def test_the_render_tool_resamples(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py --resample --size and --fit (its main(), in this process), and what --resample excludes"""
-    import importlib.util
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     path = make_clip(tmp_path, "plain", 64, 48, n=3)
     opts = dict(cs=5, stripes=1)
-    want, _, _, _ = serve_resampled(gpu, path, opts, "rgb", (50, 40), order=((0, 3, 1.5),))
+    want, _, _, _ = serve(gpu, path, opts, "rgb", resampled((50, 40)), order=((0, 3, 1.5),))
     fit = resample.fit(64, 48, 60, 36)
     assert fit == (48, 36)
-    want_fit, _, _, _ = serve_resampled(gpu, path, opts, "jpeg", fit, order=((0, 3, 1.5),), quality=90)
+    want_fit, _, _, _ = serve(gpu, path, opts, "jpeg", resampled(fit), order=((0, 3, 1.5),), quality=90)
 
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
     assert run(tmp_path / "a", ["--resample", "--size", "50x40"]) == 0
     names = sorted(os.listdir(tmp_path / "a"))
     assert [open(tmp_path / "a" / n, "rb").read() for n in names] == want

@@ -3,7 +3,7 @@ against a full-size .dng mount of the same clip and options -- the TIFF's pixels
 the pixels of the .dng file, with the parameters the tags of that file's header give -- and mlvfs_amd_mount_jpeg_scaled against
 mlvfs_amd/jpeg.py's encoding of that rendering; results[], sizes[] and flags[]; PIL opens every file at ow x oh; calls at two sizes
 interleave with the half-size call and the others on one handle and leave a handle that never makes them as it was; the refusals; the
-tool.  The clips and option sets are those of tests/test_gpu_render.py.  All comparisons are for equality."""
+tool.  The clips, option sets and helpers are those of tests/mount_harness.py.  All comparisons are for equality."""
 import io
 import os
 
@@ -11,83 +11,13 @@ import numpy as np
 import pytest
 
 from mlvfs_amd import jpeg, lib, mlvfile, render, scale, synth
-from mlvfs_amd.dark import Dark
-from mlvfs_amd.flat import Flat
 
-import dark_cases as dc
-import flat_cases as fc
 import scale_cases as sc
-from test_gpu_render import GAIN_A, NAME, OPTION_SETS, ORDER, fresh, make_clip, open_mount, serve
+from mount_harness import (GAIN_A, HDR, OPTION_SETS, QUALITY, calibration, check_jpegs, check_tiffs, fresh, load_tool, make_clip, noise_clip,
+                           open_mount, payloads, renderings, run_tool, serve)
 
 pytestmark = pytest.mark.gpu
-HDR = render.HEADER_BYTES
 JHDR = jpeg.HEADER_BYTES
-QUALITY = 85
-
-
-@pytest.fixture(scope="module")
-def lut():
-    return render.srgb_lut12()
-
-
-def serve_scaled(gpu, path, opts, kind, size, dark=None, flat=None, order=ORDER, batch=2, quality=QUALITY):
-    """frames 2..4, then 0..1 (at another gain), in batches of 2, through one fresh handle -> (files, flags, results, gains)"""
-    fresh(gpu)
-    r, m = open_mount(path, opts, dark, flat)
-    files, flags, results, gains = [], [], [], []
-    with r, m:
-        for first, count, gain in order:
-            res = np.full(count, -1, np.int32)
-            if kind == "jpeg":
-                a, fl = m.jpeg(first, count, gain=gain, quality=quality, batch=batch, results=res, size=size)
-            else:
-                a = m.rgb(first, count, gain=gain, batch=batch, results=res, size=size)
-                assert a.shape == (count, m.rgb_size(size=size)) and m.rgb_size(size=size) == gpu.mlvfs_amd_mount_rgb_scaled_size(m.h, first, *size)
-                a, fl = [f.tobytes() for f in a], [None] * count
-            files += a
-            flags += fl
-            results += list(res)
-            gains += [gain] * count
-    return files, flags, results, gains
-
-
-def renderings(full, gains, w, h, size, lut):
-    """the definition applied to every full-size .dng file"""
-    out = []
-    for f, gain in zip(full, gains):
-        assert len(f) == 65536 + w * h * 2
-        p = render.params_from_header(f[:65536], int(round(256 * gain)))
-        out.append(scale.render(np.frombuffer(f, "<u2", offset=65536).reshape(h, w), p, size[0], size[1], lut))
-    return out
-
-
-def check_tiffs(want, tiffs, size, label):
-    from PIL import Image
-    ow, oh = size
-    assert len(want) == len(tiffs)
-    for k, (px, t) in enumerate(zip(want, tiffs)):
-        assert len(t) == HDR + ow * oh * 3, (label, k)
-        got = scale.split_file(t, ow, oh)
-        assert np.array_equal(got, px), f"{label} frame {k}: {(got != px).sum()} bytes are not the definition's of the full-size .dng file"
-        assert t[:HDR] == render.tiff_header(ow, oh), (label, k)
-        with Image.open(io.BytesIO(t)) as im:
-            assert im.mode == "RGB" and im.size == (ow, oh) and np.array_equal(np.asarray(im), px), (label, k)
-
-
-def check_jpegs(want, files, flags, size, label, quality=QUALITY):
-    """each file: the definition's JPEG file of the rendering, or, where that is the larger, the TIFF with flag bit 0"""
-    from PIL import Image
-    ow, oh = size
-    assert len(want) == len(files) == len(flags)
-    for k, (px, j, fl) in enumerate(zip(want, files, flags)):
-        file = jpeg.header(ow, oh, quality) + jpeg.encode(px, quality)
-        tiff = render.tiff_header(ow, oh) + px.tobytes()
-        fallback = len(file) > len(tiff)
-        assert fl == int(fallback), (label, k, fl, len(file), len(tiff))
-        assert j == (tiff if fallback else file), f"{label} frame {k}: not the definition's file of the rendering"
-        with Image.open(io.BytesIO(j)) as im:
-            assert im.format == ("TIFF" if fallback else "JPEG") and im.mode == "RGB" and im.size == (ow, oh)
-            im.load()
 
 
 # one payload kind -- the scaling sits behind every stage that depends on it --, both of the mount tests' frame sizes (the fast and the
@@ -98,64 +28,52 @@ CASES = [(w, h, SIZES_OF[(w, h)][k], name, opts, cal) for w, h in sc.MOUNT_SIZES
 
 
 @pytest.mark.parametrize("w,h,size,name,opts,cal", CASES, ids=[f"{w}x{h}->{s[0]}x{s[1]}:{name}" for w, h, s, name, _, _ in CASES])
-def test_mount_scaled_is_the_full_size_file_scaled(gpu, lut, tmp_path, w, h, size, name, opts, cal):
+def test_mount_scaled_is_the_full_size_file_scaled(gpu, tmp_path, w, h, size, name, opts, cal):
     label = f"{w}x{h}->{size}:{name}"
     path = make_clip(tmp_path, "plain", w, h, dual=bool(opts.get("dual_iso")))
-    with Dark.from_plane(dc.dark_plane(w, h) if cal else np.zeros((1, 1), np.uint16), 14, synth.BLACK) as dark, \
-            Flat.from_plane(fc.clip_flat(w, h) if cal else np.full((1, 1), 3000, np.uint16), 14, synth.BLACK) as flat:
-        cal_args = dict(dark=dark, flat=flat) if cal else {}
-        full, res_full, _ = serve(gpu, path, opts, "dng", **cal_args)
-        tiffs, _, res_rgb, gains = serve_scaled(gpu, path, opts, "rgb", size, **cal_args)
-        jpgs, flags, res_jpg, _ = serve_scaled(gpu, path, opts, "jpeg", size, **cal_args)
+    with calibration(cal, w, h) as cal_args:
+        full, _, res_full, _ = serve(gpu, path, opts, "dng", **cal_args)
+        tiffs, _, res_rgb, gains = serve(gpu, path, opts, "rgb", dict(size=size), **cal_args)
+        jpgs, flags, res_jpg, _ = serve(gpu, path, opts, "jpeg", dict(size=size), **cal_args)
     assert res_rgb == res_full == res_jpg and all(r in (0, 1) for r in res_full)
-    want = renderings(full, gains, w, h, size, lut)
+    want = renderings(full, gains, w, h, "scaled", size)
     check_tiffs(want, tiffs, size, label)
-    check_jpegs(want, jpgs, flags, size, label)
+    check_jpegs(want, jpgs, flags, size, label, QUALITY)
     assert len(set(tiffs)) == len(tiffs), "two frames rendered alike"
 
 
-def test_mount_scaled_uses_the_x4_levels_of_a_converted_frame(gpu, lut, tmp_path):
+def test_mount_scaled_uses_the_x4_levels_of_a_converted_frame(gpu, tmp_path):
     """416x264, the size the dual-ISO tests convert at (and one the fast kernel takes): a mixed clip, frames 1 and 3 are not dual ISO
     and keep their levels"""
-    from test_gpu_mount import dual_clip
-    path = str(dual_clip(tmp_path, "plain", normal_at=(1, 3)) / NAME)
+    path = make_clip(tmp_path, "plain", 416, 264, normal_at=(1, 3))
     opts = dict(dual_iso=2, hdr_interp=1, cs=2)
     order = ((0, 5, GAIN_A),)
     size = scale.fit(416, 264, 100, 100)
     assert size == (100, 63)
-    full, res_full, _ = serve(gpu, path, opts, "dng", order=order, batch=3)
-    tiffs, _, res_rgb, gains = serve_scaled(gpu, path, opts, "rgb", size, order=order, batch=3)
-    jpgs, flags, res_jpg, _ = serve_scaled(gpu, path, opts, "jpeg", size, order=order, batch=3)
+    full, _, res_full, _ = serve(gpu, path, opts, "dng", order=order, batch=3)
+    tiffs, _, res_rgb, gains = serve(gpu, path, opts, "rgb", dict(size=size), order=order, batch=3)
+    jpgs, flags, res_jpg, _ = serve(gpu, path, opts, "jpeg", dict(size=size), order=order, batch=3)
     assert res_full == res_rgb == res_jpg == [1, 0, 1, 0, 1]
     levels = [render.header_colour(f[:65536])[:2] for f in full]
     assert levels[0] == (4 * 2048, 4 * 15000) and levels[1] == (2048, 15000)
-    want = renderings(full, gains, 416, 264, size, lut)
+    want = renderings(full, gains, 416, 264, "scaled", size)
     check_tiffs(want, tiffs, size, "mixed dual ISO")
-    check_jpegs(want, jpgs, flags, size, "mixed dual ISO")
+    check_jpegs(want, jpgs, flags, size, "mixed dual ISO", QUALITY)
     assert flags == [0] * 5 and all(JHDR < len(j) < len(t) for j, t in zip(jpgs, tiffs))
 
 
-def noise_clip(tmp_path, w, h, flat_at=(1,)):
-    """frames of noise from black to white; those in flat_at one grey level"""
-    g = np.random.default_rng(11)
-    frames = [np.full((h, w), 6000, np.uint16) if k in flat_at else g.integers(synth.BLACK, 15000, (h, w)).astype(np.uint16) for k in range(3)]
-    path = str(tmp_path / NAME)
-    mlvfile.write_clip(path, [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], w, h)
-    return path
-
-
-def test_mount_jpeg_scaled_serves_the_tiff_where_that_is_smaller(gpu, lut, tmp_path):
+def test_mount_jpeg_scaled_serves_the_tiff_where_that_is_smaller(gpu, tmp_path):
     """noise at quality 100 at 13 x 11: 629 bytes of header and the stream are more than the TIFF's 685 bytes; the flat frame between
     the two noise frames stays a JPEG file"""
     w, h, size = 64, 48, (13, 11)
     path = noise_clip(tmp_path, w, h)
     order = ((0, 3, GAIN_A),)
-    full, res_full, _ = serve(gpu, path, {}, "dng", order=order, batch=3)
-    tiffs, _, res_rgb, gains = serve_scaled(gpu, path, {}, "rgb", size, order=order, batch=3)
-    files, flags, res_jpg, _ = serve_scaled(gpu, path, {}, "jpeg", size, order=order, batch=3, quality=100)
-    want = renderings(full, gains, w, h, size, lut)
+    full, _, res_full, _ = serve(gpu, path, {}, "dng", order=order, batch=3)
+    tiffs, _, res_rgb, gains = serve(gpu, path, {}, "rgb", dict(size=size), order=order, batch=3)
+    files, flags, res_jpg, _ = serve(gpu, path, {}, "jpeg", dict(size=size), order=order, batch=3, quality=100)
+    want = renderings(full, gains, w, h, "scaled", size)
     check_tiffs(want, tiffs, size, "noise")
-    check_jpegs(want, files, flags, size, "noise", quality=100)
+    check_jpegs(want, files, flags, size, "noise", 100)
     assert flags == [1, 0, 1] and files[0] == tiffs[0] and files[2] == tiffs[2] and len(files[0]) == HDR + 13 * 11 * 3 and res_jpg == res_rgb == res_full
     assert JHDR < len(files[1]) < len(tiffs[1])
     # sizes[] as the C call reports them, and nothing behind a file is touched
@@ -173,21 +91,21 @@ def test_mount_jpeg_scaled_serves_the_tiff_where_that_is_smaller(gpu, lut, tmp_p
             assert out[at:at + int(sizes[k])].tobytes() == files[k] and (out[at + int(sizes[k]):at + stride] == 0xA5).all(), k
 
 
-def test_scaled_calls_of_two_sizes_interleave_with_the_others(gpu, lut, tmp_path):
+def test_scaled_calls_of_two_sizes_interleave_with_the_others(gpu, tmp_path):
     path = make_clip(tmp_path, "plain", 416, 264, n=8)
     opts = dict(cs=5, badpix=1, stripes=1)
     order = ((0, 8, GAIN_A),)
     A, B = (160, 101), (52, 33)
-    want_dng, _, _ = serve(gpu, path, opts, "dng", order=order, batch=4)
-    want_half, _, _ = serve(gpu, path, opts, "rgb", order=order, batch=4)
-    want_a, _, _, gains = serve_scaled(gpu, path, opts, "rgb", A, order=order, batch=4)
-    want_b, _, _, _ = serve_scaled(gpu, path, opts, "rgb", B, order=order, batch=4)
-    jpg_b, flags, _, _ = serve_scaled(gpu, path, opts, "jpeg", B, order=order, batch=4)
-    check_tiffs(renderings(want_dng, gains, 416, 264, A, lut), want_a, A, "one size")
-    check_tiffs(renderings(want_dng, gains, 416, 264, B, lut), want_b, B, "another")
-    check_jpegs(renderings(want_dng, gains, 416, 264, B, lut), jpg_b, flags, B, "another")
+    want_dng, _, _, _ = serve(gpu, path, opts, "dng", order=order, batch=4)
+    want_half, _, _, _ = serve(gpu, path, opts, "rgb", order=order, batch=4)
+    want_a, _, _, gains = serve(gpu, path, opts, "rgb", dict(size=A), order=order, batch=4)
+    want_b, _, _, _ = serve(gpu, path, opts, "rgb", dict(size=B), order=order, batch=4)
+    jpg_b, flags, _, _ = serve(gpu, path, opts, "jpeg", dict(size=B), order=order, batch=4)
+    check_tiffs(renderings(want_dng, gains, 416, 264, "scaled", A), want_a, A, "one size")
+    check_tiffs(renderings(want_dng, gains, 416, 264, "scaled", B), want_b, B, "another")
+    check_jpegs(renderings(want_dng, gains, 416, 264, "scaled", B), jpg_b, flags, B, "another", QUALITY)
     # the identity size is the half-size call's file
-    ident, _, _, _ = serve_scaled(gpu, path, opts, "rgb", (208, 132), order=order, batch=4)
+    ident, _, _, _ = serve(gpu, path, opts, "rgb", dict(size=(208, 132)), order=order, batch=4)
     assert ident == want_half
     fresh(gpu)
     r, m = open_mount(path, opts)
@@ -229,12 +147,12 @@ def test_a_handle_without_scaled_calls_serves_what_a_fresh_one_does(gpu, tmp_pat
     assert run(False) == run(True)
 
 
-def test_mount_scaled_refusals_and_strides(gpu, lut, tmp_path):
+def test_mount_scaled_refusals_and_strides(gpu, tmp_path):
     w, h, size = 64, 48, (20, 15)
     path = make_clip(tmp_path, "plain", w, h, n=4)
     opts = dict(cs=5, stripes=1)
     order = ((0, 4, GAIN_A),)
-    want, _, _, _ = serve_scaled(gpu, path, opts, "rgb", size, order=order)
+    want, _, _, _ = serve(gpu, path, opts, "rgb", dict(size=size), order=order)
     nbytes = HDR + 20 * 15 * 3
     fresh(gpu)
     r, m = open_mount(path, opts)
@@ -264,46 +182,37 @@ def test_mount_scaled_refusals_and_strides(gpu, lut, tmp_path):
         assert m.dng(0, 2, batch=2).shape == (2, 65536 + 32 * 24 * 2)        # the refusal served nothing and spoilt nothing
 
 
-def test_mount_scaled_at_3584x1320(gpu, lut, tmp_path):
+def test_mount_scaled_at_3584x1320(gpu, tmp_path):
     from PIL import Image
     w, h = sc.BIG_W, sc.BIG_H
     frames = [synth.normal_frame(w, h, seed=1, frame=k) for k in range(2)]
     path = str(tmp_path / "B.MLV")
-    mlvfile.write_clip(path, [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], w, h)
+    mlvfile.write_clip(path, payloads(frames, "plain")[0], w, h)
     opts = dict(cs=5, stripes=1)
     order = ((0, 2, GAIN_A),)
     size = scale.fit(w, h, 1280, 720)
     assert size == (1280, 471)
-    full, _, _ = serve(gpu, path, opts, "dng", order=order)
-    tiffs, _, _, gains = serve_scaled(gpu, path, opts, "rgb", size, order=order)
-    want = renderings(full, gains, w, h, size, lut)
+    full, _, _, _ = serve(gpu, path, opts, "dng", order=order)
+    tiffs, _, _, gains = serve(gpu, path, opts, "rgb", dict(size=size), order=order)
+    want = renderings(full, gains, w, h, "scaled", size)
     check_tiffs(want, tiffs, size, "3584x1320")
-    jpgs, flags, _, _ = serve_scaled(gpu, path, opts, "jpeg", (160, 59), order=((0, 1, GAIN_A),), batch=1)
-    check_jpegs(renderings(full[:1], gains[:1], w, h, (160, 59), lut), jpgs, flags, (160, 59), "thumbnail")
+    jpgs, flags, _, _ = serve(gpu, path, opts, "jpeg", dict(size=(160, 59)), order=((0, 1, GAIN_A),), batch=1)
+    check_jpegs(renderings(full[:1], gains[:1], w, h, "scaled", (160, 59)), jpgs, flags, (160, 59), "thumbnail", QUALITY)
     with Image.open(io.BytesIO(jpgs[0])) as im:
         assert im.format == "JPEG" and im.size == (160, 59)
 
 
-def test_the_render_tool_scaled(gpu, lut, tmp_path, monkeypatch, capsys):
+def test_the_render_tool_scaled(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py --size and --fit (its main(), in this process): the files are mlvfs_amd_mount_rgb_scaled's and
     mlvfs_amd_mount_jpeg_scaled's; the two options exclude each other and --full"""
-    import importlib.util
-    import sys
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     path = make_clip(tmp_path, "plain", 64, 48, n=3)
     opts = dict(cs=5, stripes=1)
-    want, _, _, _ = serve_scaled(gpu, path, opts, "rgb", (20, 15), order=((0, 3, 1.5),))
-    want_jpg, _, _, _ = serve_scaled(gpu, path, opts, "jpeg", (16, 12), order=((0, 3, 1.5),), quality=80)
+    want, _, _, _ = serve(gpu, path, opts, "rgb", dict(size=(20, 15)), order=((0, 3, 1.5),))
+    want_jpg, _, _, _ = serve(gpu, path, opts, "jpeg", dict(size=(16, 12)), order=((0, 3, 1.5),), quality=80)
 
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
     out = tmp_path / "out"
     assert run(out, ["--size", "20x15"]) == 0
     names = sorted(os.listdir(out))

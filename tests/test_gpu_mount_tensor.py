@@ -12,22 +12,19 @@ import numpy as np
 import pytest
 
 from mlvfs_amd import lib, look, mlvfile, render, synth, tensor as T
-from mlvfs_amd.dark import Dark
-from mlvfs_amd.flat import Flat
 
-import dark_cases as dc
 import deep_cases as dp
-import flat_cases as fc
 import look_cases as lc
-from test_gpu_render import NAME, fresh, make_clip, open_mount
+import mount_harness
+from mount_harness import H as DH, W as DW, calibration, fresh, load_tool, make_clip, open_mount, payloads, route_args, run_tool, serve_calls as serve
 
 pytestmark = pytest.mark.gpu
 GAIN = 1.5
 ORDER = ((2, 3), (0, 2))                                 # frames 2..4, then 0..1, in batches of 2
 DEEP = {name: (S, n, Tb) for name, S, n, Tb in dp.looks()}
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-ROUTES = {"half": dict(), "full": dict(full=True), "scaled": dict(size=(20, 13)), "resampled": dict(size=(301, 190), resample=True),
-          "resampled_small": dict(size=(45, 29), resample=True)}
+SIZES = {"scaled": (20, 13), "resampled": (301, 190), "resampled_small": (45, 29)}
+ROUTES = {route: route_args(route.split("_")[0], SIZES.get(route)) for route in ("half", "full", "scaled", "resampled", "resampled_small")}
 TORCH_NAMES = {T.F32: "float32", T.F16: "float16", T.BF16: "bfloat16", T.U8: "uint8", T.U16: "uint16"}
 
 
@@ -40,8 +37,7 @@ def tensor_bytes(t):
 
 
 def out_size(route, w, h):
-    kw = ROUTES[route]
-    return kw["size"] if "size" in kw else (w, h) if kw.get("full") else (w // 2, h // 2)
+    return mount_harness.out_size(ROUTES[route], w, h)
 
 
 def want_rgb(files, route, w, h, deep, dtype, layout, scale, bias):
@@ -59,24 +55,9 @@ def want_bayer(dngs, w, h, dtype, layout, scale, bias):
     return out
 
 
-def serve(gpu, path, opts, call, order=ORDER, batch=2, setup=None, **cal):
-    """`call(m, first, count, results)` for each part of the order through one fresh handle -> (what the calls returned, results)"""
-    fresh(gpu)
-    r, m = open_mount(path, opts, **cal)
-    got, results = [], []
-    with r, m:
-        if setup:
-            setup(m)
-        for first, count in order:
-            res = np.full(count, -1, np.int32)
-            got.append(call(m, first, count, res))
-            results += list(res)
-    return got, results
-
-
 def serve_dng(gpu, path, opts, order=ORDER, **cal):
-    got, res = serve(gpu, path, opts, lambda m, f, c, r: m.dng(f, c, batch=2, results=r), order, **cal)
-    return [f.tobytes() for a in got for f in a], res
+    files, _, res, _ = mount_harness.serve(gpu, path, opts, "dng", order=[(f, c, GAIN) for f, c in order], **cal)
+    return files, res
 
 
 def check_route(gpu, path, opts, w, h, route, tone, dtype, layout, norm, cal, order=ORDER, amaze=False):
@@ -134,9 +115,7 @@ def test_mount_tensor_is_the_definition_of_the_served_file(gpu, tmp_path, payloa
     """the four sizes, each with another tone, dtype, layout and normalisation from case to case, and the Bayer tensor"""
     i = CASES.index((payload, w, h, name, opts, cal))
     path = make_clip(tmp_path, payload, w, h)
-    with Dark.from_plane(dc.dark_plane(w, h) if cal else np.zeros((1, 1), np.uint16), 14, synth.BLACK) as dark, \
-            Flat.from_plane(fc.clip_flat(w, h) if cal else np.full((1, 1), 3000, np.uint16), 14, synth.BLACK) as flat:
-        cal_args = dict(dark=dark, flat=flat) if cal else {}
+    with calibration(cal, w, h) as cal_args:
         for j, route in enumerate(("half", "full", "scaled", "resampled" if w > 301 else "resampled_small")):
             tone = TONES[(i + j) % 3]
             legal = [d for d in (T.F16, T.F32, T.BF16, T.U8, T.U16) if T.legal(d, 16 if tone == "deep" else 8)]
@@ -147,8 +126,7 @@ def test_mount_tensor_is_the_definition_of_the_served_file(gpu, tmp_path, payloa
 @pytest.mark.parametrize("payload", ["plain", "lj92"])
 def test_mount_tensor_on_a_mixed_dual_iso_clip(gpu, tmp_path, payload):
     """dual_iso = 2, frame 1 is not dual ISO: the converted frames have the x4 levels, in the Bayer tensor's unit as in the rendering"""
-    from test_gpu_mount import H as DH, W as DW, dual_clip
-    path = str(dual_clip(tmp_path, payload, normal_at=(1,), n=3) / NAME)
+    path = make_clip(tmp_path, payload, DW, DH, normal_at=(1,), n=3)
     opts = dict(dual_iso=2, hdr_interp=1, cs=2)
     order = ((0, 3),)
     dngs, res = check_bayer(gpu, path, opts, DW, DH, T.F32 if payload == "plain" else T.F16, T.NCHW, False, {}, order)
@@ -258,7 +236,7 @@ def test_mount_tensor_at_3584x1320(gpu, tmp_path):
     w, h = 3584, 1320
     frame = synth.normal_frame(w, h, seed=1, frame=0)
     path = str(tmp_path / "B.MLV")
-    mlvfile.write_clip(path, [np.ascontiguousarray(synth.pack_bits(frame), "<u2").tobytes()], w, h)
+    mlvfile.write_clip(path, payloads([frame], "plain")[0], w, h)
     opts = dict(cs=5, stripes=1)
     scale, bias = T.normalisation(MEAN, STD, 3)
     for route in ("half", "full"):
@@ -272,21 +250,12 @@ def test_mount_tensor_at_3584x1320(gpu, tmp_path):
 
 def test_the_tensor_tool_writes_the_tensors(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_tensor.py (its main(), in this process): the .npy files hold Mount.tensor's frames; a second run overwrites nothing"""
-    import importlib.util
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_tensor_tool", os.path.join(root, "tools", "mlv_tensor.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_tensor")
     w, h = 64, 48
     path = make_clip(tmp_path, "plain", w, h, n=3)
     opts = dict(cs=5, stripes=1)
 
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_tensor.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2"] + extra)
     for k, (extra, kw) in enumerate([(["--gain", "1.5", "--mean", "0.485,0.456,0.406", "--std", "0.229,0.224,0.225"], dict(gain=1.5, mean=MEAN, std=STD)),
                                      (["--kind", "bayer", "--dtype", "bfloat16", "--layout", "NHWC"], dict(kind="bayer", dtype="bfloat16", layout="NHWC")),
                                      (["--size", "20x13", "--dtype", "uint8"], dict(size=(20, 13), dtype="uint8"))]):

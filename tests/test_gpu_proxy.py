@@ -10,21 +10,14 @@ import numpy as np
 import pytest
 
 from mlvfs_amd import lib, mlvfile, synth
-from mlvfs_amd.dark import Dark
-from mlvfs_amd.flat import Flat
-from mlvfs_amd.mount import Mount
 
-import dark_cases as dc
-import flat_cases as fc
 import proxy_cases as pc
 from lossless_cases import jpeg_view, max_class
+from mount_harness import H, NAME, PAYLOADS, W, calibration, dual_clip, fresh, load_tool, open_mount, payloads, run_tool
 from test_gpu_mlv_transcode import PAD, device_buffer, split
-from test_gpu_mount import dual_clip, mount_opts
 from test_gpu_ref_host import make_clip
 
 pytestmark = pytest.mark.gpu
-W, H = 416, 264
-NAME = "M07-1234.MLV"
 
 
 # ------------------------------------------------------------------ mlvfs_amd_bin2_dev
@@ -104,24 +97,12 @@ OPTION_SETS = [
     ("dual_iso=2,amaze", dict(dual_iso=2, hdr_interp=0), False),
     ("cs5+stripes,dark+flat", dict(cs=5, stripes=1), True),
 ]
-PAYLOADS = ["plain", "lzma", "lj92"]
-
-
-def fresh(gpu):
-    gpu.free_focus_pixel_maps()                     # a fresh process: no bad-pixel map yet, no dual-ISO table caches
-    gpu.mlvfs_amd_dualiso_reset()
-
-
-def open_mount(path, opts, proxy, dark=None, flat=None):
-    opt, defl, fps = mount_opts(opts)
-    r = mlvfile.MlvReader(path)
-    return r, Mount(r, opt, deflicker=defl, fps=fps, basename="/" + NAME, dark=dark, flat=flat, proxy=proxy)
 
 
 def serve(gpu, path, opts, proxy, dark=None, flat=None, lossless=False, order=((2, 3), (0, 2)), batch=2):
     """frames 2..4, then 0..1, in batches of 2, through one fresh handle -> (files, flags or None, results, dng_size)"""
     fresh(gpu)
-    r, m = open_mount(path, opts, proxy, dark, flat)
+    r, m = open_mount(path, opts, dark, flat, proxy)
     files, flags, results = [], [], []
     with r, m:
         size = m.dng_size()
@@ -185,9 +166,7 @@ def test_mount_proxy_is_the_full_size_file_binned(gpu, reference, tmp_path, payl
     else:
         d, _ = make_clip(tmp_path, payload, reference=reference)
     path = str(d / NAME)
-    with Dark.from_plane(dc.dark_plane(W, H) if cal else np.zeros((1, 1), np.uint16), 14, synth.BLACK) as dark, \
-            Flat.from_plane(fc.clip_flat(W, H) if cal else np.full((1, 1), 3000, np.uint16), 14, synth.BLACK) as flat:
-        cal_args = dict(dark=dark, flat=flat) if cal else {}
+    with calibration(cal, W, H) as cal_args:
         full, _, res_full, size_full = serve(gpu, path, opts, 1, **cal_args)
         proxy, _, res_proxy, size_proxy = serve(gpu, path, opts, 2, **cal_args)
         files, flags, res_ll, _ = serve(gpu, path, opts, 2, lossless=True, **cal_args)
@@ -201,8 +180,7 @@ def plain_clip(tmp_path, frames, name=NAME):
     d = tmp_path / "card"
     d.mkdir(exist_ok=True)
     h, w = frames[0].shape
-    mlvfile.write_clip(str(d / name), [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], w, h, chunks=2, frame_space=32,
-                       shuffle=True)
+    mlvfile.write_clip(str(d / name), payloads(frames, "plain")[0], w, h, chunks=2, frame_space=32, shuffle=True)
     return str(d / name)
 
 
@@ -244,7 +222,7 @@ def test_mount_proxy_calls_of_both_kinds_interleave_in_serve_order(gpu, tmp_path
     want, _, _, _ = serve(gpu, path, opts, 2, order=((0, 8),), batch=4)
     want_ll, flags_ll, _, _ = serve(gpu, path, opts, 2, lossless=True, order=((0, 8),), batch=4)
     fresh(gpu)
-    r, m = open_mount(path, opts, 2)
+    r, m = open_mount(path, opts, proxy=2)
     with r, m:
         a, fa = m.dng_lossless(0, 3, batch=2)
         b = m.dng(3, 3, batch=2)
@@ -260,7 +238,7 @@ def test_mount_proxy_strides_set_proxy_after_a_frame_and_factor_1(gpu, tmp_path)
     full, _, _, size_full = serve(gpu, path, opts, 1, order=((0, 4),))
     proxy, _, _, size = serve(gpu, path, opts, 2, order=((0, 4),))
     fresh(gpu)
-    r, m = open_mount(path, opts, 2)
+    r, m = open_mount(path, opts, proxy=2)
     with r, m:
         out = np.full(4 * size + 64, 0xA5, np.uint8)
         sizes, flags = np.zeros(4, np.uintp), np.zeros(4, np.int32)
@@ -279,7 +257,7 @@ def test_mount_proxy_strides_set_proxy_after_a_frame_and_factor_1(gpu, tmp_path)
         assert m.dng_size() == size
     # factor 1: today's bytes
     fresh(gpu)
-    r, m = open_mount(path, opts, 1)
+    r, m = open_mount(path, opts, proxy=1)
     with r, m:
         m.set_proxy(2)
         m.set_proxy(1)
@@ -293,7 +271,7 @@ def test_mount_proxy_full_size(gpu, reference, tmp_path):
     w, h = pc.BIG_W, pc.BIG_H
     frames = [synth.normal_frame(w, h, seed=1, frame=k) for k in range(2)]
     path = str(tmp_path / "B.MLV")
-    mlvfile.write_clip(path, [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], w, h)
+    mlvfile.write_clip(path, payloads(frames, "plain")[0], w, h)
     opts = dict(cs=5, stripes=1)
     full, _, _, _ = serve(gpu, path, opts, 1, order=((0, 2),))
     proxy, _, _, size = serve(gpu, path, opts, 2, order=((0, 2),))
@@ -307,23 +285,13 @@ def test_mount_proxy_full_size(gpu, reference, tmp_path):
 def test_the_proxy_tool_writes_the_sequence_and_overwrites_nothing(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_proxy.py (its main(), in this process): the files are the proxy handle's, uncompressed and lossless; a second run
     into the same place is refused and leaves the files"""
-    import importlib.util
     import os
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_proxy_tool", os.path.join(root, "tools", "mlv_proxy.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_proxy")
     path = plain_clip(tmp_path, [synth.normal_frame(64, 48, seed=9, frame=k, hot=8, cold=8) for k in range(3)])
     opts = dict(cs=5, stripes=1)
     want, _, _, _ = serve(gpu, path, opts, 2, order=((0, 3),))
     want_ll, _, _, _ = serve(gpu, path, opts, 2, lossless=True, order=((0, 3),))
-
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_proxy.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2"] + extra)
-        return tool.main()
-
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2"] + extra)
     for extra, files in (([], want), (["--lossless"], want_ll)):
         out = tmp_path / ("out" + "".join(extra))
         assert run(out, extra) == 0

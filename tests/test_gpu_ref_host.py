@@ -13,13 +13,14 @@ mlvfs_load_chunks / mlvfs_close_chunks) linked three ways by oracle/Makefile --
 text only as compiled code under the git-ignored oracle/_ref/ (they travel to the GPU box like libmlvfs_ref.so); the
 command-line driver around them is oracle/ref_host_driver.inc."""
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
 from mlvfs_amd import mlvfile, synth
+
+from mount_harness import payloads
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -50,15 +51,7 @@ def make_clip(tmp_path, kind, n=5, w=W, h=H, reference=None):
     d = tmp_path / "card"
     d.mkdir()
     frames = [synth.dual_iso_frame(w, h, frame=k) if kind == "dual_iso" else synth.normal_frame(w, h, seed=9, frame=k, hot=60, cold=60) for k in range(n)]
-    vc = 1
-    if kind == "lj92":
-        from oracle import lj92_testenc as enc
-        from test_lj92 import quadrants
-        pl, vc = [struct.pack("<I", w * h * 2) + enc.encode(quadrants(f), 6, 14) for f in frames], 1 | 0x100
-    elif kind == "lzma":
-        pl, vc = [reference.lzma_payload(synth.pack_bits(f).tobytes()) for f in frames], 1 | 0x80
-    else:
-        pl = [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames]
+    pl, vc = payloads(frames, kind, reference)
     mlvfile.write_clip(str(d / "M07-1234.MLV"), pl, w, h, chunks=2, frame_space=32, shuffle=True, video_class=vc)
     return d, frames
 

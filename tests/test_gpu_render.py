@@ -4,26 +4,19 @@ pixels are the definition applied to the pixels of the full-size .dng file, with
 (so every stage in front of the rendering ran as it does for a .dng, and the levels are the frame's final ones), results[] are the
 same, and PIL opens every file.  All comparisons are for equality."""
 import ctypes as C
-import io
-import struct
+import os
 
 import numpy as np
 import pytest
 
 from mlvfs_amd import lib, mlvfile, render, synth
-from mlvfs_amd.dark import Dark
-from mlvfs_amd.flat import Flat
-from mlvfs_amd.mount import Mount
 
-import dark_cases as dc
-import flat_cases as fc
 import render_cases as rc
+from mount_harness import (GAIN_A, HDR, OPTION_SETS, PAYLOADS, calibration, check_tiffs, fresh, load_tool, lut, make_clip, open_mount, payloads,
+                           renderings, run_tool, serve)
 from test_gpu_mlv_transcode import PAD, device_buffer, split
-from test_gpu_mount import mount_opts
 
 pytestmark = pytest.mark.gpu
-NAME = "M07-1234.MLV"
-HDR = render.HEADER_BYTES
 
 
 # ------------------------------------------------------------------ mlvfs_amd_render2_dev
@@ -50,23 +43,18 @@ def run_render2(gpu, frames, params, src_off, dst_off, aligned):
     return [p.reshape(ph, pw, 3) for p in parts], rest
 
 
-@pytest.fixture(scope="module")
-def lut():
-    return render.srgb_lut12()
-
-
 @pytest.mark.parametrize("w,h", rc.SIZES, ids=lambda v: str(v))
-def test_render2_dev_equals_numpy(gpu, lut, w, h):
+def test_render2_dev_equals_numpy(gpu, w, h):
     for batch, src_off, dst_off, aligned in rc.dev_cases(w, h):
         frames, params = [f for f, _ in batch], [p for _, p in batch]
         got, rest = run_render2(gpu, frames, params, src_off, dst_off, aligned)
         assert (rest == PAD).all(), (len(batch), src_off, dst_off, "bytes outside the renderings changed")
         for k, (f, p) in enumerate(batch):
-            want = render.render(f, p, lut)
+            want = render.render(f, p, lut())
             assert np.array_equal(got[k], want), (len(batch), src_off, dst_off, k, int((got[k] != want).sum()))
 
 
-def test_render2_dev_extreme_parameters(gpu, lut):
+def test_render2_dev_extreme_parameters(gpu):
     """black at both ends of its type and below zero, A at its cap, the largest K a forward matrix of shorts can give"""
     w, h = 48, 6
     f = rc.full_frame(w, h, 0, 65535, seed=77)
@@ -78,14 +66,14 @@ def test_render2_dev_extreme_parameters(gpu, lut):
         got, rest = run_render2(gpu, [f] * len(sets), sets, off, 0, aligned)
         assert (rest == PAD).all()
         for k, p in enumerate(sets):
-            assert np.array_equal(got[k], render.render(f, p, lut)), (aligned, k)
+            assert np.array_equal(got[k], render.render(f, p, lut())), (aligned, k)
 
 
-def test_render2_dev_full_size(gpu, lut):
+def test_render2_dev_full_size(gpu):
     (b0, w0), p0 = rc.param_set(2)
     (b1, w1), p1 = rc.param_set(3)
     frames = [rc.range_frame(rc.BIG_W, rc.BIG_H, b0, w0, seed=1), rc.grey_ramp(rc.BIG_W, rc.BIG_H, b1, w1)]
-    want = [render.render(frames[0], p0, lut), render.render(frames[1], p1, lut)]
+    want = [render.render(frames[0], p0, lut()), render.render(frames[1], p1, lut())]
     got, rest = run_render2(gpu, frames, [p0, p1], 0, 0, True)
     assert (rest == PAD).all()
     for k in range(2):
@@ -120,121 +108,40 @@ def test_render2_dev_refusals_leave_the_destination(gpu):
 
 
 # ------------------------------------------------------------------ the mount
-OPTION_SETS = [
-    ("none", dict(), False),
-    ("cs5+badpix+stripes", dict(cs=5, badpix=1, stripes=1), False),
-    ("pnoise+deflicker", dict(pnoise=1, deflicker=3000), False),
-    ("dual_iso=2", dict(dual_iso=2, hdr_interp=0), False),
-    ("dark+flat", dict(), True),
-]
-PAYLOADS = ["plain", "lzma", "lj92"]
-GAIN_A, GAIN_B = 1.0, 2.5                            # the two calls of a serve
-
-
-def fresh(gpu):
-    gpu.free_focus_pixel_maps()                     # a fresh process: no bad-pixel map yet, no dual-ISO table caches
-    gpu.mlvfs_amd_dualiso_reset()
-
-
-def make_clip(tmp_path, payload, w, h, dual=False, reference=None, n=5, name=NAME):
-    """-> the clip's path; dual: dual-ISO frames"""
-    d = tmp_path / "card"
-    d.mkdir(exist_ok=True)
-    frames = [synth.dual_iso_frame(w, h, frame=k) if dual else synth.normal_frame(w, h, seed=9, frame=k, hot=60, cold=60) for k in range(n)]
-    vc = 1
-    if payload == "lj92":
-        from oracle import lj92_testenc as enc
-        from test_lj92 import quadrants
-        pl, vc = [struct.pack("<I", w * h * 2) + enc.encode(quadrants(f), 6, 14) for f in frames], 1 | 0x100
-    elif payload == "lzma":
-        pl, vc = [reference.lzma_payload(synth.pack_bits(f).tobytes()) for f in frames], 1 | 0x80
-    else:
-        pl = [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames]
-    mlvfile.write_clip(str(d / name), pl, w, h, chunks=2, frame_space=32, shuffle=True, video_class=vc)
-    return str(d / name)
-
-
-def open_mount(path, opts, dark=None, flat=None, proxy=1):
-    opt, defl, fps = mount_opts(opts)
-    r = mlvfile.MlvReader(path)
-    return r, Mount(r, opt, deflicker=defl, fps=fps, basename="/" + NAME, dark=dark, flat=flat, proxy=proxy)
-
-
-ORDER = ((2, 3, GAIN_A), (0, 2, GAIN_B))
-
-
-def serve(gpu, path, opts, kind, dark=None, flat=None, order=ORDER, batch=2):
-    """frames 2..4, then 0..1 (at another gain), in batches of 2, through one fresh handle -> (files, results, gains)"""
-    fresh(gpu)
-    r, m = open_mount(path, opts, dark, flat)
-    files, results, gains = [], [], []
-    with r, m:
-        for first, count, gain in order:
-            res = np.full(count, -1, np.int32)
-            if kind == "rgb":
-                a = m.rgb(first, count, gain=gain, batch=batch, results=res)
-                assert a.shape == (count, m.rgb_size()) and m.rgb_size() == gpu.mlvfs_amd_mount_rgb_size(m.h, first)
-            else:
-                a = m.dng(first, count, batch=batch, results=res)
-            files += [f.tobytes() for f in a]
-            results += list(res)
-            gains += [gain] * count
-    return files, results, gains
-
-
-def check_rgb(full, rgb, gains, w, h, label, lut):
-    """every rendered file against the full-size .dng of the same frame"""
-    from PIL import Image
-    pw, ph = render.geom(w, h)
-    assert len(full) == len(rgb)
-    for k, (f, t, gain) in enumerate(zip(full, rgb, gains)):
-        assert len(f) == 65536 + w * h * 2 and len(t) == HDR + pw * ph * 3, (label, k)
-        p = render.params_from_header(f[:65536], int(round(256 * gain)))
-        want = render.render(np.frombuffer(f, "<u2", offset=65536).reshape(h, w), p, lut)
-        got = render.split_file(t, pw, ph)
-        assert np.array_equal(got, want), f"{label} frame {k}: {(got != want).sum()} bytes are not the definition's of the full-size file"
-        assert t[:HDR] == render.tiff_header(pw, ph), (label, k)
-        with Image.open(io.BytesIO(t)) as im:
-            assert im.mode == "RGB" and im.size == (pw, ph) and np.array_equal(np.asarray(im), want), (label, k)
-
-
 CASES = [(p, w, h, name, opts, cal) for p in PAYLOADS for w, h in rc.MOUNT_SIZES for name, opts, cal in OPTION_SETS]
 
 
 @pytest.mark.parametrize("payload,w,h,name,opts,cal", CASES, ids=[f"{p}:{w}x{h}:{name}" for p, w, h, name, _, _ in CASES])
-def test_mount_rgb_is_the_full_size_file_rendered(gpu, reference, lut, tmp_path, payload, w, h, name, opts, cal):
+def test_mount_rgb_is_the_full_size_file_rendered(gpu, reference, tmp_path, payload, w, h, name, opts, cal):
     path = make_clip(tmp_path, payload, w, h, dual=bool(opts.get("dual_iso")), reference=reference)
-    with Dark.from_plane(dc.dark_plane(w, h) if cal else np.zeros((1, 1), np.uint16), 14, synth.BLACK) as dark, \
-            Flat.from_plane(fc.clip_flat(w, h) if cal else np.full((1, 1), 3000, np.uint16), 14, synth.BLACK) as flat:
-        cal_args = dict(dark=dark, flat=flat) if cal else {}
-        full, res_full, _ = serve(gpu, path, opts, "dng", **cal_args)
-        rgb, res_rgb, gains = serve(gpu, path, opts, "rgb", **cal_args)
+    with calibration(cal, w, h) as cal_args:
+        full, _, res_full, _ = serve(gpu, path, opts, "dng", **cal_args)
+        rgb, _, res_rgb, gains = serve(gpu, path, opts, "rgb", **cal_args)
     assert res_rgb == res_full and all(r in (0, 1) for r in res_full)
-    check_rgb(full, rgb, gains, w, h, f"{payload}:{w}x{h}:{name}", lut)
+    check_tiffs(renderings(full, gains, w, h, "half"), rgb, render.geom(w, h), f"{payload}:{w}x{h}:{name}")
     assert len({f for f in rgb}) == len(rgb), "two frames rendered alike"
 
 
-def test_mount_rgb_uses_the_x4_levels_of_a_converted_frame(gpu, lut, tmp_path):
+def test_mount_rgb_uses_the_x4_levels_of_a_converted_frame(gpu, tmp_path):
     """416x264, the size the dual-ISO tests convert at: a mixed clip, frames 1 and 3 are not dual ISO and keep their levels"""
-    from test_gpu_mount import dual_clip
-    path = str(dual_clip(tmp_path, "plain", normal_at=(1, 3)) / NAME)
+    path = make_clip(tmp_path, "plain", 416, 264, normal_at=(1, 3))
     opts = dict(dual_iso=2, hdr_interp=1, cs=2)
     order = ((0, 5, GAIN_A),)
-    full, res_full, _ = serve(gpu, path, opts, "dng", order=order, batch=3)
-    rgb, res_rgb, gains = serve(gpu, path, opts, "rgb", order=order, batch=3)
+    full, _, res_full, _ = serve(gpu, path, opts, "dng", order=order, batch=3)
+    rgb, _, res_rgb, gains = serve(gpu, path, opts, "rgb", order=order, batch=3)
     assert res_full == res_rgb == [1, 0, 1, 0, 1]
     levels = [render.header_colour(f[:65536])[:2] for f in full]
     assert levels[0] == (4 * 2048, 4 * 15000) and levels[1] == (2048, 15000)
-    check_rgb(full, rgb, gains, 416, 264, "mixed dual ISO", lut)
+    check_tiffs(renderings(full, gains, 416, 264, "half"), rgb, render.geom(416, 264), "mixed dual ISO")
 
 
-def test_mount_rgb_and_dng_calls_interleave_in_serve_order(gpu, lut, tmp_path):
+def test_mount_rgb_and_dng_calls_interleave_in_serve_order(gpu, tmp_path):
     path = make_clip(tmp_path, "plain", 416, 264, n=8)
     opts = dict(cs=5, badpix=1, stripes=1)
     order = ((0, 8, GAIN_A),)
-    want_dng, _, _ = serve(gpu, path, opts, "dng", order=order, batch=4)
-    want_rgb, _, gains = serve(gpu, path, opts, "rgb", order=order, batch=4)
-    check_rgb(want_dng, want_rgb, gains, 416, 264, "one kind", lut)
+    want_dng, _, _, _ = serve(gpu, path, opts, "dng", order=order, batch=4)
+    want_rgb, _, _, gains = serve(gpu, path, opts, "rgb", order=order, batch=4)
+    check_tiffs(renderings(want_dng, gains, 416, 264, "half"), want_rgb, render.geom(416, 264), "one kind")
     fresh(gpu)
     r, m = open_mount(path, opts)
     with r, m:
@@ -247,12 +154,12 @@ def test_mount_rgb_and_dng_calls_interleave_in_serve_order(gpu, lut, tmp_path):
     assert flags == [0] and len(c[0]) < len(want_dng[5])
 
 
-def test_mount_rgb_strides_and_a_proxy_handle(gpu, lut, tmp_path):
+def test_mount_rgb_strides_and_a_proxy_handle(gpu, tmp_path):
     w, h = 64, 48
     path = make_clip(tmp_path, "plain", w, h, n=4)
     opts = dict(cs=5, stripes=1)
     order = ((0, 4, GAIN_A),)
-    want, _, _ = serve(gpu, path, opts, "rgb", order=order)
+    want, _, _, _ = serve(gpu, path, opts, "rgb", order=order)
     size = HDR + 32 * 24 * 3
     assert size < 65536, "the file is smaller than a .dng header: no header of that kind may be written on the way"
     fresh(gpu)
@@ -279,39 +186,28 @@ def test_mount_rgb_strides_and_a_proxy_handle(gpu, lut, tmp_path):
         assert m.dng(0, 2, batch=2).shape == (2, 65536 + 32 * 24 * 2)        # the refusal served nothing and spoilt nothing
 
 
-def test_mount_rgb_full_size(gpu, lut, tmp_path):
+def test_mount_rgb_full_size(gpu, tmp_path):
     w, h = rc.BIG_W, rc.BIG_H
     frames = [synth.normal_frame(w, h, seed=1, frame=k) for k in range(2)]
     path = str(tmp_path / "B.MLV")
-    mlvfile.write_clip(path, [np.ascontiguousarray(synth.pack_bits(f), "<u2").tobytes() for f in frames], w, h)
+    mlvfile.write_clip(path, payloads(frames, "plain")[0], w, h)
     opts = dict(cs=5, stripes=1)
     order = ((0, 2, GAIN_A),)
-    full, _, _ = serve(gpu, path, opts, "dng", order=order)
-    rgb, _, gains = serve(gpu, path, opts, "rgb", order=order)
+    full, _, _, _ = serve(gpu, path, opts, "dng", order=order)
+    rgb, _, _, gains = serve(gpu, path, opts, "rgb", order=order)
     assert len(rgb[0]) == HDR + 1792 * 660 * 3
-    check_rgb(full, rgb, gains, w, h, "3584x1320", lut)
+    check_tiffs(renderings(full, gains, w, h, "half"), rgb, render.geom(w, h), "3584x1320")
 
 
-def test_the_render_tool_writes_the_sequence_and_overwrites_nothing(gpu, lut, tmp_path, monkeypatch, capsys):
+def test_the_render_tool_writes_the_sequence_and_overwrites_nothing(gpu, tmp_path, monkeypatch, capsys):
     """tools/mlv_render.py (its main(), in this process): the files are mlvfs_amd_mount_rgb's; a second run into the same place is
     refused and leaves the files"""
-    import importlib.util
-    import os
-    import sys
     from PIL import Image
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mlv_render_tool", os.path.join(root, "tools", "mlv_render.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("mlv_render")
     path = make_clip(tmp_path, "plain", 64, 48, n=3)
     opts = dict(cs=5, stripes=1)
-    want, _, _ = serve(gpu, path, opts, "rgb", order=((0, 3, 1.5),))
-
-    def run(out, extra):
-        fresh(gpu)
-        monkeypatch.setattr(sys, "argv", ["mlv_render.py", path, str(out), "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
-        return tool.main()
-
+    want, _, _, _ = serve(gpu, path, opts, "rgb", order=((0, 3, 1.5),))
+    run = lambda out, extra: run_tool(gpu, monkeypatch, tool, [path, out, "--cs", "5", "--stripes", "--batch", "2", "--gain", "1.5"] + extra)
     out = tmp_path / "out"
     assert run(out, []) == 0
     names = sorted(os.listdir(out))
