@@ -1,5 +1,6 @@
 """tools/side_sweep.py [seed] [cases] -- fix_pattern_noise and hdr_convert_data (drop-in symbols) against the oracle over random
-geometries and material: flat / noisy / edgy frames with clipped and black runs for the pattern-noise medians; dual-ISO frames with
+geometries and material: flat / noisy / edgy frames with clipped and black runs for the pattern-noise medians, full-range 16-bit noise
+and a walk on both sides of 32768 (negative int16, every wrap) under a random white level; dual-ISO frames with
 columns of clipped bright and deep-shadow dark pixels (chains of rewritten rows) for the preview.  A debug aid beyond the test suite."""
 import ctypes as C, os, sys
 import numpy as np
@@ -17,19 +18,27 @@ try:
     for it in range(cases):
         # ---- pattern noise
         w, h = int(rng.integers(12, 700)) * 2, int(rng.integers(12, 400)) * 2
-        kind = it % 4
+        kind = it % 6
+        white = WHITE
         if kind == 0: f = synth.normal_frame(w, h, seed=int(rng.integers(1, 999)))
         elif kind == 1: f = synth.adversarial_frame(w, h, seed=int(rng.integers(1, 999)))
         elif kind == 2: f = (BLACK + rng.integers(0, 60, (h, w)) + 3000 * (rng.random((h, w)) < 0.02)).astype(np.uint16)       # flat with outliers: long runs
-        else:
+        elif kind == 3:
             base = np.cumsum(rng.integers(-300, 301, (h, w)), axis=1) % 12000 + BLACK                                           # edgy: short runs
             f = np.clip(base + 16000 * (rng.random((h, w)) < 0.01), 0, 16383).astype(np.uint16)
-        want = o.fix_pattern_noise(f, WHITE)
+        elif kind == 4:
+            f = rng.integers(0, 65536, (h, w)).astype(np.uint16)                                                                # full range: every int16 wrap
+            white = int(rng.integers(-32768, 65536))
+        else:
+            base = 32768 + np.cumsum(rng.integers(-40, 41, (h, w)), axis=1) + rng.integers(-300, 301, (h, 1))                   # a walk on both sides of 32768
+            f = ((base + rng.integers(-300, 301, (h, w))) & 0xFFFF).astype(np.uint16)
+            white = int(rng.choice([65535, -1, 32767, int(rng.integers(-1500, 1500)) - 32768 * int(rng.integers(0, 2))]))
+        want = o.fix_pattern_noise(f, white)
         got = f.copy()
-        gpu.fix_pattern_noise(lib.ptr(got), w, h, WHITE, 0)
+        gpu.fix_pattern_noise(lib.ptr(got), w, h, white, 0)
         if not np.array_equal(got, want):
             bad_pn += 1
-            sys.stderr.write(f"pattern noise MISMATCH case {it}: {w}x{h} kind {kind}, {(got != want).sum()} px\n")
+            sys.stderr.write(f"pattern noise MISMATCH case {it}: {w}x{h} kind {kind} white {white}, {(got != want).sum()} px\n")
         # ---- preview
         w, h = int(rng.integers(20, 500)) * 2, int(rng.integers(40, 400))
         f = synth.dual_iso_frame(w, h, seed=int(rng.integers(1, 999)))
